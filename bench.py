@@ -8,13 +8,17 @@ Cholesky of the 6000 x 6000 reduced camera system (MFMA) -> back-substitution ->
 update -> residual kernel at the trial point (stba_ba_lm_iterations: every iteration does all
 of that, accepted or not).  Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--cams C --pts P --obs-per-pt M]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--cams C --pts P --obs-per-pt M] [--dump-outputs DIR]
 
 Protocol: W untimed warm-up steps, then R repetitions of EXACTLY K timed steps, each repetition
 from the same start point and bracketed by barrier + device synchronisation, max over ranks; the JSON line
 reports the MEDIAN repetition (`value`, `ms_per_step`) and lists all of them.  A speed-up over the CPU leg is
 printed only after the GPU leg and the CPU leg, run for the same fixed iteration count from the same start,
 agree in final cost (1e-6 relative) and camera poses (1e-5).
+
+--dump-outputs DIR: what the LAST timed repetition handed its caller -- the camera poses, the landmarks and the
+per-iteration trace (--config c4: the node poses and the trace) -- goes to DIR/<name>.npy in FP64, so that two builds
+can be compared output for output on the same seeded inputs.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` re-launches itself under torch.distributed.run
 (--nproc-per-node N, 127.0.0.1); when the driver already launched N ranks (WORLD_SIZE set) it must equal
@@ -308,6 +312,30 @@ def pose_err(a, b):
     return float(dq), float(np.abs(a[:, 4:] - b[:, 4:]).max())
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6       # array data of --dump-outputs (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array -> path/<name>.npy in FP64, at most DUMP_MAX_BYTES in all.  Smallest first, an array is written whole
+    if it fits its share of what is left; a larger one keeps a fixed sample of its rows (seed 0, in order) that depends only on the
+    shapes: the same rows on every run with the same arguments.
+    Returns {name: {"shape", "rows_of"}} for the JSON line (rows_of: the row count before sampling, None if written whole)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    budget, left, written = DUMP_MAX_BYTES, len(arrays), {}
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        share = budget // left
+        left -= 1
+        rows_of = None
+        if a.nbytes > share and a.ndim > 0:
+            rows_of = len(a)
+            a = a[np.sort(np.random.default_rng(0).choice(rows_of, share // (a.nbytes // rows_of), replace=False))]
+        budget -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "rows_of": rows_of}
+    return {"dir": os.path.abspath(path), "arrays": written}
+
+
 def ceres_row(scene_file, n_iter):
     """opportunistic real-Ceres baseline: built only if a Ceres installation is found on this
     box (header + library), semantics of st20-g2o/src/include/test_ceres.h:98-152 (SPARSE_SCHUR, analytic
@@ -466,6 +494,7 @@ def bench_c4(args):
         dt = time.perf_counter() - t0
         reps.append((dt, summ.num_iterations, pcg_total, summ.final_cost, summ.initial_cost, summ.termination_type, e.pcg_summary().as_dict(),
                      e.get_poses(), [int(x) for x in tr[:, 6]]))
+    last_outputs = {"poses": reps[-1][7], "trace": tr}       # (--dump-outputs: the last timed solve, before the sort by time)
     reps.sort(key=lambda r: r[0])
     dt, iters, pcg_total, fcost, icost, term, pcg_sum, gpu_poses, gpu_acc = reps[len(reps) // 2]
     # the same solve with EXACT steps (PCG to 1e-12): what the forcing sequence saves, and the run the oracle's trace is held against
@@ -531,6 +560,8 @@ def bench_c4(args):
         "edges_per_sec_linearize": m / (ms_lin * 1e-3), "edges_per_sec_matvec": m / (ms_mv * 1e-3),
         "build_head": build_head(),
     }
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
     if not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_py as O       # cpu_baseline leg + matched-result gate only
@@ -591,6 +622,9 @@ def main():
                     help="rehearsal of the N-rank path on a one-GPU box: all ranks on device 0 (use with --backend gloo --hook torch; the times mean nothing)")
     ap.add_argument("--second-cams", type=int, default=100)
     ap.add_argument("--second-pts", type=int, default=1000000)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed repetition computed (cams, pts, trace; --config c4: poses, trace) "
+                         "as DIR/<name>.npy, FP64, at most 64 MB (a fixed, seeded sample of the rows beyond that)")
     args = ap.parse_args()
     want_second = (args.second_scene or args.gpus > 1) and not args.no_second_scene and not args.dense_visibility
     if args.config == "c4":
@@ -694,6 +728,17 @@ def main():
     it_per_s = 1e3 / ms_step
     cams_same, _ = ranks_hold_identical_cameras(eng, torch, dist, world, have_gpu, args)
     rank_check = LAST_RANK_CHECK
+    dumped = None
+    if args.dump_outputs:
+        # the last repetition's result, read before the instrumented run below starts again from cams0 / pts0; with several ranks the
+        # landmark shards (contiguous ranges, rank order) are put back together on rank 0, the cameras and the trace are every rank's
+        cams_out, pts_out = eng.get_params()
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(pts_out, parts, dst=0)
+            pts_out = np.concatenate(parts) if rank == 0 else None
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"cams": cams_out, "pts": pts_out, "trace": trace})
     out = {
         "metric": "LM iterations/sec + residuals/sec, 1k-cam/100k-pt BA",
         "value": it_per_s, "unit": "LM iterations/s",
@@ -711,6 +756,8 @@ def main():
         "camera_blocks_identical_on_all_ranks": bool(cams_same),    # every rank factors the same reduced system: compared in-run, bit for bit
         "rank_check": rank_check,       # (several ranks: largest distance of a rank's camera blocks from rank 0's, factorisation time-outs per rank)
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     # Device time per phase: ONE MORE run of K steps with stba_lm_options::phase_timing on (hipEvents between the phases; the
     # timed repetitions above run without them: an event record costs ~5 us of idle GPU and an iteration would take eight),
     # per step; with several ranks the MAXIMUM over ranks, plus what explains an N > 1 line: the cross-rank sum's device time
