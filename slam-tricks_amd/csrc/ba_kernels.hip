@@ -207,15 +207,20 @@ int launch_absmax(const double* v, size_t n, const double* v2, size_t n2, double
 
 // The whole trial block of one LM iteration in ONE launch behind the residual-only kernel: out[0] = sum of that kernel's
 // cost partials (summation order of sum_partials_kernel), out[1..3] / out[5..7] the three sums of the landmark / camera
-// update's partials (order of trial_sums_kernel), out[4] = 1 if the factorisation timed out on this rank; and, if host_out is given, the block plus the
-// factorisation's flag written straight into mapped host memory (export_trial_kernel): three launches less.
+// update's partials (order of trial_sums_kernel), out[4] = 1 if the factorisation timed out on this rank; out[9], out[10]: cost2 and
+// |g|max of the last reduced-system build -- *lin_cost2, and the largest of gpmax[0, n_gpmax) and |gc[0, n_g)| -- which the LM loop
+// reads one iteration late (out[8] is the caller's); and, if host_out is given, the block with the factorisation's flag in slot 8
+// written straight into mapped host memory (export_trial_kernel): three launches less.
+__device__ __forceinline__ double max_keep(double m, double x) { return m < x ? x : m; }     // std::max(m, x): a NaN x never wins
 __global__ __launch_bounds__(256) void trial_finish_kernel(const double* __restrict__ cost_partial, int n_cost,
                                                            const double* __restrict__ part_p, int n_p, const double* __restrict__ part_c,
-                                                           int n_c, const int* __restrict__ flag, double* __restrict__ out,
-                                                           double* __restrict__ host_out, double host_seq) {
+                                                           int n_c, const int* __restrict__ flag, const double* __restrict__ lin_cost2,
+                                                           const double* __restrict__ gpmax, int n_gpmax, const double* __restrict__ gc,
+                                                           int n_g, double* __restrict__ out, double* __restrict__ host_out, double host_seq) {
     // the seven sums side by side: per thread a strided share of each, then ONE tree for all of them (every sum in the order it
-    // always had: strided shares, then halving)
-    __shared__ double s[7][256];
+    // always had: strided shares, then halving); the max in the same tree (from +0.0 and never a NaN, as the host's std::max did it:
+    // a max does not depend on the order, the bits are the same)
+    __shared__ double s[8][256];
     __shared__ double res[8];
     {
         double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -231,20 +236,26 @@ __global__ __launch_bounds__(256) void trial_finish_kernel(const double* __restr
 #pragma unroll
             for (int k = 0; k < 3; ++k) v[4 + k] += part_c[(size_t)i * 4 + k];
         }
+        double m = 0.0;
+        for (int i = threadIdx.x; i < n_gpmax; i += 256) m = max_keep(m, gpmax[i]);
+#pragma unroll 4
+        for (int i = threadIdx.x; i < n_g; i += 256) m = max_keep(m, fabs(gc[i]));
 #pragma unroll
         for (int q = 0; q < 7; ++q) s[q][threadIdx.x] = v[q];
+        s[7][threadIdx.x] = m;
         __syncthreads();
         for (int off = 128; off > 0; off >>= 1) {
             if (threadIdx.x < off) {
 #pragma unroll
                 for (int q = 0; q < 7; ++q) s[q][threadIdx.x] += s[q][threadIdx.x + off];
+                s[7][threadIdx.x] = max_keep(s[7][threadIdx.x], s[7][threadIdx.x + off]);
             }
             __syncthreads();
         }
-        if (threadIdx.x < 7) res[threadIdx.x] = s[threadIdx.x][0];
+        if (threadIdx.x < 8) res[threadIdx.x] = s[threadIdx.x][0];
         __syncthreads();
     }
-    __shared__ double hp[9];
+    __shared__ double hp[11];
     if (threadIdx.x < 8) {
         // block layout (stba_engine.hip, TS_*): [cost2, step2, x2, model | timed out | the three camera sums]; entry 4 = 1.0 if the
         // factorisation of this iteration timed out on this rank (CHOL_FLAG_TIMEOUT): it lies inside the prefix the ranks sum
@@ -253,18 +264,22 @@ __global__ __launch_bounds__(256) void trial_finish_kernel(const double* __restr
         out[k] = v;
         hp[k] = v;
     } else if (threadIdx.x == 8) hp[8] = (double)flag[0];
+    else if (threadIdx.x == 9) out[9] = hp[9] = lin_cost2[0];
+    else if (threadIdx.x == 10) out[10] = hp[10] = res[7];
     if (host_out) {
-        // the host polls the block (no event on the stream: an event record is ~5 us of idle GPU): the eight sums and the
-        // factorisation's flag as a STAMPED BLOCK, every 64-byte line with the sequence number and a check word of its own (common.hpp)
+        // the host polls the block (no event on the stream: an event record is ~5 us of idle GPU): the eight sums, the
+        // factorisation's flag and the build's two scalars as a STAMPED BLOCK, every 64-byte line with the sequence number and a
+        // check word of its own (common.hpp)
         __syncthreads();
-        if (threadIdx.x < 64) stamped_store_wave(host_out, hp, 9, host_seq, threadIdx.x);
+        if (threadIdx.x < 64) stamped_store_wave(host_out, hp, 11, host_seq, threadIdx.x);
     }
 }
 
 int launch_trial_finish(const double* cost_partial, int n_cost, const double* part_p, int n_p, const double* part_c, int n_c,
-                        const int* flag, double* out, double* host_out, double host_seq, hipStream_t st) {
-    hipLaunchKernelGGL(trial_finish_kernel, dim3(1), dim3(256), 0, st, cost_partial, n_cost, part_p, n_p, part_c, n_c, flag, out, host_out,
-                       host_seq);
+                        const int* flag, const double* lin_cost2, const double* gpmax, int n_gpmax, const double* gc, int n_g,
+                        double* out, double* host_out, double host_seq, hipStream_t st) {
+    hipLaunchKernelGGL(trial_finish_kernel, dim3(1), dim3(256), 0, st, cost_partial, n_cost, part_p, n_p, part_c, n_c, flag, lin_cost2,
+                       gpmax, n_gpmax, gc, n_g, out, host_out, host_seq);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
@@ -1210,13 +1225,9 @@ __global__ __launch_bounds__(256) void ba_reduced_finalize_kernel(int n_cams, in
                                                                   double* __restrict__ ex_diag, double* __restrict__ ex_gc,
                                                                   double* __restrict__ scale, int init_scale, int use_scaling,
                                                                   double radius, double dmin, double dmax, double* __restrict__ dc,
-                                                                  int blocks_cam, const double* __restrict__ scalars, int n_scalars,
-                                                                  double* __restrict__ host_out, int reduced) {
+                                                                  int blocks_cam, int reduced) {
     // (reduced != 0 -- several ranks, behind the cross-rank sum: the camera blocks are in S already and diag(Hcc), gc come
     // summed over the ranks from ex_diag / ex_gc; what is left is the LM diagonal, the damping and the padding)
-    // (host_out: the scalar slots and the gradient gc also go straight into mapped host memory -- [scalars | gc] -- where
-    // the LM loop reads them one synchronisation later: export_linear_kernel's launch saved)
-    if (host_out && blockIdx.x == 0 && (int)threadIdx.x < n_scalars) host_out[threadIdx.x] = scalars[threadIdx.x];
     if ((int)blockIdx.x >= blocks_cam) {
         // padding rows (chol_pad_kernel); the first n entries of the last row are written by the diagonal threads below
         const int r = n + ((int)blockIdx.x - blocks_cam);
@@ -1243,7 +1254,6 @@ __global__ __launch_bounds__(256) void ba_reduced_finalize_kernel(int n_cams, in
     double sd = S[(size_t)i * lda + i] + (reduced ? 0.0 : h);
     const double g = reduced ? ex_gc[i] : gc[i];
     if (!reduced) { ex_diag[i] = h; ex_gc[i] = g; }
-    if (host_out) host_out[n_scalars + i] = g;
     double rv = rhs[i] - (reduced ? 0.0 : g);
     // lm_diagonal_kernel, kind 2
     double sc = 1.0;
@@ -1266,12 +1276,10 @@ __global__ __launch_bounds__(256) void ba_reduced_finalize_kernel(int n_cams, in
 
 int launch_reduced_finalize(int n_cams, int n, const double* Hcc, const double* gc, const unsigned char* cam_fixed, double* S, int lda,
                             double* rhs, double* ex_diag, double* ex_gc, double* scale, int init_scale, int use_scaling,
-                            double radius, double dmin, double dmax, double* dc, const double* scalars, int n_scalars,
-                            double* host_out, int reduced, hipStream_t st) {
+                            double radius, double dmin, double dmax, double* dc, int reduced, hipStream_t st) {
     const int blocks_cam = (n_cams * 36 + 255) / 256;
     hipLaunchKernelGGL(ba_reduced_finalize_kernel, dim3(blocks_cam + (lda - n)), dim3(256), 0, st, n_cams, n, Hcc, gc, cam_fixed, S, lda,
-                       rhs, ex_diag, ex_gc, scale, init_scale, use_scaling, radius, dmin, dmax, dc, blocks_cam, scalars, n_scalars, host_out,
-                       reduced);
+                       rhs, ex_diag, ex_gc, scale, init_scale, use_scaling, radius, dmin, dmax, dc, blocks_cam, reduced);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }

@@ -36,7 +36,8 @@ int launch_point_blocks(int n_pts, const int* pt_start, const double* J8, const 
 int launch_linear_finish(const double* cost_partial, int n_cost, const double* gpmax_partial, int n_gp, double* cost2_out,
                          double* slots, int n_slots, int cost_slot, int max_slot, hipStream_t st);
 int launch_trial_finish(const double* cost_partial, int n_cost, const double* part_p, int n_p, const double* part_c, int n_c,
-                        const int* flag, double* out, double* host_out, double host_seq, hipStream_t st);
+                        const int* flag, const double* lin_cost2, const double* gpmax, int n_gpmax, const double* gc, int n_g,
+                        double* out, double* host_out, double host_seq, hipStream_t st);
 int launch_camera_blocks(int n_cams, int n_chunks, const int* chunk_begin, const int* chunk_end,
                          const int* cam_chunk_start, const int* cam_perm, const double* J8, const unsigned char* omask,
                          const double* Jc12, const double2* r, double* partial, double* Hcc, double* gc, hipStream_t st);
@@ -106,8 +107,7 @@ int launch_reduced_add_camera(int n_cams, const double* Hcc, const double* gc, d
                               double* ex_diag, double* ex_gc, hipStream_t st);
 int launch_reduced_finalize(int n_cams, int n, const double* Hcc, const double* gc, const unsigned char* cam_fixed, double* S, int lda,
                             double* rhs, double* ex_diag, double* ex_gc, double* scale, int init_scale, int use_scaling,
-                            double radius, double dmin, double dmax, double* dc, const double* scalars, int n_scalars,
-                            double* host_out, int reduced, hipStream_t st);
+                            double radius, double dmin, double dmax, double* dc, int reduced, hipStream_t st);
 int launch_reduced_damp(int n, const double* dc, const unsigned char* cam_fixed, double* S, int lda, double* rhs,
                         hipStream_t st);
 // the landmark half of the trial point made by the back-substitution kernel itself (LM loop): pts_new = pts (+) dxp and one

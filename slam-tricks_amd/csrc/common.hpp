@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -131,6 +132,75 @@ inline bool stamped_try_read(const volatile double* in, int n_payload, Accept ac
     if (stamp_out) *stamp_out = first_stamp;
     return true;
 }
+
+// host: waits for a stamped block.  Polls (with a pause) until stamped_try_read accepts it; every STAMPED_QUERY_EVERY polls it asks
+// stream_state(&why) about the stream that writes the block -- failed: an error (why says what); finished: nothing more will be
+// written, so one more read decides (an error if the block is still not there); running: on, unless limit_s seconds have passed.
+// `who` begins every message.  The product passes hip_stream_state(st); the CPU test passes a fake.
+enum class StreamState { running, finished, failed };
+constexpr unsigned long STAMPED_QUERY_EVERY = 1ul << 14;
+template <class Accept, class StreamCheck>
+inline int stamped_wait(const volatile double* block, int n_payload, Accept accept, double* payload, StreamCheck stream_state,
+                        const char* who, double limit_s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned long n = 1; !stamped_try_read(block, n_payload, accept, payload); ++n) {
+        if (n % STAMPED_QUERY_EVERY == 0) {
+            std::string why;
+            const StreamState s = stream_state(&why);
+            if (s == StreamState::failed) return fail(STBA_ERR_HIP, std::string(who) + ": stream failed: " + why);
+            if (s == StreamState::finished) {
+                if (stamped_try_read(block, n_payload, accept, payload)) return STBA_OK;
+                return fail(STBA_ERR_HIP, std::string(who) + ": the stream finished without writing the block the host waits for");
+            }
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
+                return fail(STBA_ERR_HIP, std::string(who) + ": timed out waiting for the device");
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return STBA_OK;
+}
+// stamped_wait's look at a HIP stream: a finished stream is synchronised once, which settles what it wrote
+inline auto hip_stream_state(hipStream_t st) {
+    return [st](std::string* why) {
+        hipError_t q = hipStreamQuery(st);
+        if (q == hipErrorNotReady) return StreamState::running;
+        if (q == hipSuccess) q = hipStreamSynchronize(st);
+        if (q == hipSuccess) return StreamState::finished;
+        *why = hipGetErrorString(q);
+        return StreamState::failed;
+    };
+}
+
+// pinned host memory that a kernel reads or writes over the bus: every stamped block, and the small dense step's inputs.
+// (COHERENT: without the flag the memory may be coarse-grained, and what a kernel wrote into it is only promised to the host at a
+// synchronisation point -- a polling host reads stale words.)  Plain data with no destructor: its owner calls release() while the HIP
+// runtime is still there (the small dense step's pooled buffers are never released: the runtime may be gone at process exit).
+struct MappedBuffer {
+    double* host = nullptr;
+    double* dev = nullptr;        // the device's address of the same memory
+    size_t count = 0;             // doubles
+    int alloc(size_t n) {         // (zeroed; on failure the buffer is left empty: count 0, no address)
+        release();
+        void *h = nullptr, *d = nullptr;
+        STBA_HIP(hipHostMalloc(&h, n * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+        const hipError_t e = hipHostGetDevicePointer(&d, h, 0);
+        if (e != hipSuccess) {
+            (void)hipHostFree(h);
+            return fail(STBA_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+        }
+        host = static_cast<double*>(h); dev = static_cast<double*>(d); count = n;
+        zero();
+        return STBA_OK;
+    }
+    void zero() { if (host) memset(host, 0, count * sizeof(double)); }
+    void release() {
+        if (host) (void)hipHostFree(host);
+        host = dev = nullptr;
+        count = 0;
+    }
+};
 
 // ---- dense Cholesky on the device (dense_chol.hip) -----------------------------------------
 constexpr int CHOL_NB = 128;

@@ -1342,9 +1342,9 @@ struct stba_pg {
            *part_cz = nullptr, *part_u = nullptr, *scal_dev = nullptr, *contrib = nullptr, *Dc = nullptr;
     int* cflag = nullptr;            // [0]: pivot flag of the coarse factorisation, [1]: coarse operators that failed (this solve)
     PcgState* state = nullptr;
-    double *exp_host = nullptr, *exp_dev = nullptr;      // mapped: the launch-path PCG's stamped block (PX_*)
+    MappedBuffer exp;                                    // the launch-path PCG's stamped block (PX_*)
     double fin_vals[8] = {0};                            // the host's validated copy of the last trial / linearisation block
-    double *fin_host = nullptr, *fin_dev = nullptr;      // mapped: trial / linearisation scalars + sequence number
+    MappedBuffer fin;                                    // the trial / linearisation scalars' stamped block
     double seq = 0.0;
     int nb_nodes4 = 1;
     // ---- round 5: the PCG solve as one persistent kernel (pg_pcg_persistent_kernel)
@@ -1383,8 +1383,8 @@ void pg_free(stba_pg* g) {
     for (auto& e : g->ev_job) if (e) (void)hipEventDestroy(e);
     for (auto& e : g->ev_t) if (e) (void)hipEventDestroy(e);
     F(g->Ainv2);
-    if (g->exp_host) (void)hipHostFree(g->exp_host);
-    if (g->fin_host) (void)hipHostFree(g->fin_host);
+    g->exp.release();
+    g->fin.release();
     if (g->own && g->st) (void)hipStreamDestroy(g->st);
     delete g;
 }
@@ -1476,31 +1476,6 @@ static int pg_second_stream(stba_pg* g) {
     return STBA_OK;
 }
 
-// waits until the sequence number behind a block in mapped host memory is `seq` (the stream is queried now and then so
-// that a device fault ends the wait)
-// (round 6: the blocks are STAMPED blocks, common.hpp -- a sequence number BEHIND a block was seen by the host ahead of payload in
-// another cache line -- and the host works on the validated copy `payload`)
-static int pg_wait_block(stba_pg* g, const volatile double* block, int n_payload, double want, bool at_least, double* payload) {
-    const double t0 = wall();
-    auto takes = [want, at_least](double st) { return at_least ? (st >= want) : (st == want); };
-    for (unsigned long k = 1; !stamped_try_read(block, n_payload, takes, payload); ++k) {
-        if ((k & 0x3fff) == 0) {
-            const hipError_t q = hipStreamQuery(g->st);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(STBA_ERR_HIP, std::string("pose graph: stream failed: ") + hipGetErrorString(q));
-            if (q == hipSuccess) {
-                STBA_HIP(hipStreamSynchronize(g->st));
-                if (!stamped_try_read(block, n_payload, takes, payload)) return fail(STBA_ERR_HIP, "pose graph: the device never wrote the block the host waits for");
-                break;
-            }
-            if (wall() - t0 > 120.0) return fail(STBA_ERR_HIP, "pose graph: timed out waiting for the device");
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    return STBA_OK;
-}
-
 // the first stream waits for an event of the second one only if the event has NOT fired yet when the dependent work is enqueued: a
 // wait packet costs ~10 us of idle GPU even when its event has long fired (dense_chol.hip's note on the same), and here it nearly
 // always has -- the job it guards started a whole PCG solve earlier.  The data flow is the same either way: same bits.
@@ -1569,12 +1544,8 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
         return bail(fail(STBA_ERR_HIP, "stba_pg_create: memset"));
     g->nb_nodes4 = (n_nodes + PG_NPW - 1) / PG_NPW;
     A_(dalloc(&g->part_u, (size_t)g->nb_nodes * 4 + 4)); A_(dalloc(&g->scal_dev, 16)); A_(dalloc(&g->state, 1)); A_(dalloc(&g->cflag, 2));
-    if (hipHostMalloc(reinterpret_cast<void**>(&g->exp_host), (size_t)stamped_doubles(PX_COUNT) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&g->exp_dev), g->exp_host, 0) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&g->fin_host), 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&g->fin_dev), g->fin_host, 0) != hipSuccess)
+    if (g->exp.alloc((size_t)stamped_doubles(PX_COUNT)) != STBA_OK || g->fin.alloc(16) != STBA_OK)
         return bail(fail(STBA_ERR_ALLOC, "stba_pg_create: mapped host memory"));
-    memset(g->exp_host, 0, (size_t)stamped_doubles(PX_COUNT) * sizeof(double)); memset(g->fin_host, 0, 16 * sizeof(double));
     memset(&g->last_pcg, 0, sizeof g->last_pcg);
 #undef A_
     {   // edge ends sorted by node (counting sort; stable: a node's ends in edge order)
@@ -1721,7 +1692,7 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     stba_pcg_summary ps;
     memset(&ps, 0, sizeof ps);
     ps.coarse_dim = coarse ? g->nc : 0;
-    double* fin = g->fin_vals;          // (the validated copy of the mapped block g->fin_host: pg_wait_block)
+    double* fin = g->fin_vals;          // (the validated copy of the mapped block g->fin)
     // the PCG solve as one kernel: one rank, a coarse space whose groups fit a workgroup (<= 64 nodes, all their edge-end products
     // in LDS) and are all resident at once (one per CU)
     bool pp_ok = pcg.one_kernel_solve != 0 && !multi && coarse && g->agg <= 64 && g->na <= 256 && g->nc <= PP_NCMAX &&
@@ -1774,14 +1745,15 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     auto linearize_finish = [&](double* cost, double* gmax, double* g2) -> int {
         g->seq += 1.0;
         if (!multi) {
-            hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->fin_dev, g->seq);
+            hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->fin.dev, g->seq);
         } else {
             hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->scal_dev, g->seq);
             if (g->ar(g->ar_user, g->scal_dev, 1, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-            hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 3, g->scal_dev, g->fin_dev, g->seq);
+            hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 3, g->scal_dev, g->fin.dev, g->seq);
         }
         STBA_HIP(hipGetLastError());
-        STBA_TRY(pg_wait_block(g, g->fin_host, 3, g->seq, false, fin));
+        const double seq = g->seq;
+        STBA_TRY(stamped_wait(g->fin.host, 3, [seq](double st) { return st == seq; }, fin, hip_stream_state(g->st), "pose graph", 120.0));
         *cost = 0.5 * fin[0]; *gmax = fin[1]; *g2 = fin[2];
         return STBA_OK;
     };
@@ -1919,20 +1891,21 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
         auto pcg_by_launches = [&]() -> int {
             // (every kernel of the previous solve has finished -- the host has read the trial block behind them -- so the exported
             // block can be taken back: the wait below must not see the previous solve's tick count and `done`)
-            memset(g->exp_host, 0, (size_t)stamped_doubles(PX_COUNT) * sizeof(double));
+            g->exp.zero();
             std::atomic_thread_fence(std::memory_order_seq_cst);
             hipLaunchKernelGGL(pg_pcg_init4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, g->g, g->Minv, AdP, g->x, g->rr, g->z,
                                g->rc_part, g->part_a);
             if (coarse)
                 hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, (const PcgState*)nullptr, Ainv_use, g->rc_part,
                                    g->zc, g->part_cz);
-            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp_dev,
+            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
                                g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
             STBA_HIP(hipGetLastError());
             int enq = 0;
             bool pcg_done = false;
             double px[PX_COUNT];
-            STBA_TRY(pg_wait_block(g, g->exp_host, PX_COUNT, 1.0, true, px));          // (also: the previous solve's ticks are gone)
+            STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [](double st) { return st >= 1.0; }, px, hip_stream_state(g->st), "pose graph",
+                                  120.0));          // (also: the previous solve's ticks are gone)
             if (px[PX_DONE] != 0.0) pcg_done = true;
             while (!pcg_done && enq < pcg.max_iterations) {
                 const int todo = std::min(chunk, pcg.max_iterations - enq);
@@ -1955,14 +1928,15 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
                         hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, g->state, Ainv_use, g->rc_part, g->zc,
                                            g->part_cz);
                     hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, slot, 0, eta_k, pcg.max_iterations, g->state,
-                                       g->exp_dev, g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+                                       g->exp.dev, g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
                 }
                 STBA_HIP(hipGetLastError());
                 // one rank: the host looks at the chunk BEFORE the one it has just enqueued (the stream never runs dry; the kernels of a
                 // chunk enqueued past convergence return at once).  Several ranks: every rank must enqueue the same collectives, so the
                 // decision waits for the chunk itself -- the solve state is replicated and every rank sees the same `done`.
-                const int want = 1 + (multi ? enq : enq - todo);
-                STBA_TRY(pg_wait_block(g, g->exp_host, PX_COUNT, (double)want, true, px));
+                const double want = 1 + (multi ? enq : enq - todo);
+                STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [want](double st) { return st >= want; }, px, hip_stream_state(g->st), "pose graph",
+                                      120.0));
                 if (px[PX_DONE] != 0.0) pcg_done = true;
             }
             return STBA_OK;
@@ -2016,15 +1990,16 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
             g->seq += 1.0;
             if (!multi) {
                 hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
-                                   g->state, g->fin_dev, g->seq);
+                                   g->state, g->fin.dev, g->seq);
             } else {
                 hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
                                    g->state, g->scal_dev, g->seq);
                 if (g->ar(g->ar_user, g->scal_dev, 2, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");      // cost and |J x|^2 over the edge shards
-                hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 8, g->scal_dev, g->fin_dev, g->seq);
+                hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 8, g->scal_dev, g->fin.dev, g->seq);
             }
             STBA_HIP(hipGetLastError());
-            STBA_TRY(pg_wait_block(g, g->fin_host, 8, g->seq, false, fin));
+            const double seq = g->seq;
+            STBA_TRY(stamped_wait(g->fin.host, 8, [seq](double st) { return st == seq; }, fin, hip_stream_state(g->st), "pose graph", 120.0));
             return STBA_OK;
         };
         const bool one_kernel = pp_ok && !g->pp_disabled;

@@ -16,7 +16,6 @@
 #include "ba_kernels.hpp"
 
 #include <atomic>
-#include <chrono>
 #include <mutex>
 #include <vector>
 
@@ -140,17 +139,13 @@ __global__ __launch_bounds__(SD_THREADS) void dense_small_step_kernel(SmallStepA
 std::mutex g_pool_mutex;
 std::vector<SmallDenseWs*> g_pool;
 
-double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 
 struct SmallDenseWs {
     int device = -1;
     hipStream_t st = nullptr;
-    double *hJ = nullptr, *hr = nullptr, *hout = nullptr;      // pinned, mapped
-    double *dJ = nullptr, *dr = nullptr, *dout = nullptr;      // their device addresses
+    MappedBuffer J, r, out;       // J and r: written by the user's Evaluate; out: the step's stamped block
     double *scratch = nullptr, *H = nullptr, *g = nullptr, *scale = nullptr;
-    size_t cap_j = 0, cap_r = 0;
     double stamp = 0.0;
     double result[2 * SMALL_DENSE_MAX_N + 2];      // the host's validated copy of the last step's block
 };
@@ -160,20 +155,21 @@ bool small_dense_fits(int n_res, int n) {
 }
 
 static int ws_grow(SmallDenseWs* w, size_t need_j, size_t need_r) {
-    if (need_j > w->cap_j || need_r > w->cap_r) {
-        if (w->hJ) (void)hipHostFree(w->hJ);
-        if (w->hr) (void)hipHostFree(w->hr);
-        if (w->scratch) (void)hipFree(w->scratch);
-        w->hJ = w->hr = w->scratch = nullptr; w->cap_j = w->cap_r = 0;
-        const size_t cj = std::max<size_t>(need_j, 4096), cr = std::max<size_t>(need_r, 1024);
-        STBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->hJ), cj * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        STBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->hr), cr * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        STBA_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&w->dJ), w->hJ, 0));
-        STBA_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&w->dr), w->hr, 0));
+    if (need_j <= w->J.count && need_r <= w->r.count) return STBA_OK;
+    w->J.release(); w->r.release();
+    if (w->scratch) (void)hipFree(w->scratch);
+    w->scratch = nullptr;
+    const size_t cj = std::max<size_t>(need_j, 4096), cr = std::max<size_t>(need_r, 1024);
+    auto grow = [&]() -> int {
+        STBA_TRY(w->J.alloc(cj));
+        STBA_TRY(w->r.alloc(cr));
         STBA_HIP(hipMalloc(reinterpret_cast<void**>(&w->scratch), (cj + cr) * sizeof(double)));
-        w->cap_j = cj; w->cap_r = cr;
-    }
-    return STBA_OK;
+        return STBA_OK;
+    };
+    const int rc = grow();
+    // (a growth that failed half way leaves NO capacity: the pooled workspace must not pass for one with a device scratch)
+    if (rc != STBA_OK) { w->J.release(); w->r.release(); w->scratch = nullptr; }
+    return rc;
 }
 
 int small_dense_acquire(SmallDenseWs** out, int n_res, int n) {
@@ -192,13 +188,11 @@ int small_dense_acquire(SmallDenseWs** out, int n_res, int n) {
         auto fail_new = [&](int rc) { delete w; return rc; };       // (a half-made workspace is dropped; its few buffers leak with the failed device)
         if (hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking) != hipSuccess) return fail_new(fail(STBA_ERR_HIP, "small dense workspace: hipStreamCreate"));
         const size_t nn = SMALL_DENSE_MAX_N;
-        if (hipHostMalloc(reinterpret_cast<void**>(&w->hout), (size_t)stamped_doubles(SD_OUT_PAYLOAD_MAX) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer(reinterpret_cast<void**>(&w->dout), w->hout, 0) != hipSuccess ||
+        if (w->out.alloc((size_t)stamped_doubles(SD_OUT_PAYLOAD_MAX)) != STBA_OK ||
             hipMalloc(reinterpret_cast<void**>(&w->H), nn * nn * sizeof(double)) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&w->g), nn * sizeof(double)) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&w->scale), nn * sizeof(double)) != hipSuccess)
             return fail_new(fail(STBA_ERR_ALLOC, "small dense workspace: allocation failed"));
-        memset(w->hout, 0, (size_t)stamped_doubles(SD_OUT_PAYLOAD_MAX) * sizeof(double));
     }
     const int rc = ws_grow(w, (size_t)n_res * (size_t)n, (size_t)n_res);
     if (rc != STBA_OK) { small_dense_release(w); return rc; }
@@ -212,13 +206,13 @@ void small_dense_release(SmallDenseWs* w) {
     g_pool.push_back(w);          // kept for the next solve of this process (a few MB; never freed: the HIP runtime may be gone at exit)
 }
 
-double* small_dense_J(SmallDenseWs* w) { return w->hJ; }
-double* small_dense_r(SmallDenseWs* w) { return w->hr; }
+double* small_dense_J(SmallDenseWs* w) { return w->J.host; }
+double* small_dense_r(SmallDenseWs* w) { return w->r.host; }
 
 int small_dense_step(SmallDenseWs* w, int n_res, int n, bool relinearize, bool first, bool jacobi, double radius, double dmin,
                      double dmax, const double** dx, const double** g, double* model_change, int* pivot_flag) {
     SmallStepArgs a;
-    a.J = w->dJ; a.r = w->dr; a.scratch = w->scratch; a.H = w->H; a.g = w->g; a.scale = w->scale; a.out = w->dout;
+    a.J = w->J.dev; a.r = w->r.dev; a.scratch = w->scratch; a.H = w->H; a.g = w->g; a.scale = w->scale; a.out = w->out.dev;
     a.n_res = n_res; a.n = n; a.relinearize = relinearize ? 1 : 0; a.first = first ? 1 : 0; a.jacobi = jacobi ? 1 : 0;
     a.radius = radius; a.dmin = dmin; a.dmax = dmax;
     w->stamp += 1.0;
@@ -226,26 +220,9 @@ int small_dense_step(SmallDenseWs* w, int n_res, int n, bool relinearize, bool f
     std::atomic_thread_fence(std::memory_order_release);          // the callback's stores into the mapped buffers come first
     hipLaunchKernelGGL(dense_small_step_kernel, dim3(1), dim3(SD_THREADS), 0, w->st, a);
     STBA_HIP(hipGetLastError());
-    volatile double* h = w->hout;
-    const double t0 = wall_now();
     const double want = a.stamp;
-    auto is_mine = [want](double st) { return st == want; };
-    for (unsigned long spin = 1; !stamped_try_read(h, 2 * n + 2, is_mine, w->result); ++spin) {
-        if ((spin & 0xfff) == 0) {
-            const hipError_t q = hipStreamQuery(w->st);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(STBA_ERR_HIP, std::string("small dense step: ") + hipGetErrorString(q));
-            if (q == hipSuccess) {
-                // the kernel is done: one synchronise settles what the host may read
-                STBA_HIP(hipStreamSynchronize(w->st));
-                if (!stamped_try_read(h, 2 * n + 2, is_mine, w->result)) return fail(STBA_ERR_HIP, "small dense step: the result never arrived in mapped host memory");
-                break;
-            }
-            if (wall_now() - t0 > 60.0) return fail(STBA_ERR_HIP, "small dense step: timed out");
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    STBA_TRY(stamped_wait(w->out.host, 2 * n + 2, [want](double st) { return st == want; }, w->result, hip_stream_state(w->st),
+                          "small dense step", 60.0));
     *dx = w->result; *g = w->result + n;
     *model_change = w->result[2 * n];
     *pivot_flag = (int)w->result[2 * n + 1];

@@ -59,8 +59,11 @@ enum { SC_COST2 = 0, SC_GPMAX0 = 8, SC_MAX_WORLD = 64 };
 // trial-point scalars: [0..3] summed across ranks (landmark shards), [4..6] camera terms
 // (TS_TIMEOUT: 1.0 if this rank's persistent factorisation gave up -- it sits inside the all-reduced prefix of the block, so with
 // several ranks every rank sees the NUMBER of ranks that timed out and they all take the recovery path together)
+// Behind them: TS_SPEC_COST2, the cost of the speculative linearisation at the trial point (in the host's copy of the block: the
+// factorisation's flag); then cost2 and |g|max of the LAST reduced-system build (ex_scalar, ex_gc), which the LM loop reads one
+// iteration late -- outside the summed prefix, and equal on every rank (both come from the all-reduced extras).
 enum { TS_COST2 = 0, TS_STEP2 = 1, TS_X2 = 2, TS_MODEL = 3, TS_TIMEOUT = 4, TS_CAM = 5, TS_COUNT = 8,
-       TS_SPEC_COST2 = 8 };      // (behind the trial block: cost of the speculative linearisation at the trial point)
+       TS_SPEC_COST2 = 8, TS_LIN_COST2 = 9, TS_LIN_GMAX = 10, TS_BLOCK = 11 };
 
 }  // namespace stba
 
@@ -129,11 +132,10 @@ struct stba_ba {
     double* Sbuf = nullptr;   // [S lda*lda | ex_diag lda | ex_gc lda | rhs lda | ex_scalar lda]
     double *dxc = nullptr, *dxp = nullptr;
     double *cost_partial = nullptr, *upd_partial_c = nullptr, *upd_partial_p = nullptr;
-    double* trial = nullptr;   // TS_COUNT + 1 doubles
-    double* ts_host = nullptr;   // mapped pinned host memory: the trial block + the factorisation flag, written by a kernel
-    double* ts_host_dev = nullptr;
+    double* trial = nullptr;   // TS_BLOCK doubles
+    MappedBuffer ts_host;        // the trial block + the factorisation flag as a stamped block, written by a kernel
     double ts_seq = 0.0;         // sequence number of the last trial block asked for (the stamp of the block's lines)
-    double ts_vals[TS_COUNT + 1] = {0};      // the host's validated copy of the last trial block (ba_wait_trial)
+    double ts_vals[TS_BLOCK] = {0};          // the host's copy of the last trial block (validated, or downloaded after a synchronise)
     int* flag = nullptr;
     int lin_grid = 1;
     stba_allreduce_fn ar = nullptr;
@@ -145,9 +147,6 @@ struct stba_ba {
     bool ar_timing_pending = false, ar_timing_on = false;
     double ar_ms = 0.0, ar_bytes = 0.0; int ar_calls = 0;   // accumulated over one LM run
     hipEvent_t ev[15] = {};     // [12]: the trial block has reached the host; [13], [14]: second pair for the speculative linearisation
-    double* lin_pin = nullptr;      // pinned host copy of [scalars (SC_GPMAX0 + world) | gc (n)], read one solve later
-    double* lin_pin_dev = nullptr;  // (its device address)
-    bool lin_exported = false;      // the last reduced-system build wrote lin_pin itself
 
     double* S() const { return Sbuf; }
     double* ex_diag() const { return Sbuf + (size_t)lda * lda; }
@@ -184,8 +183,7 @@ static void ba_free(stba_ba* b) {
     F(b->cost_partial); F(b->upd_partial_c); F(b->upd_partial_p); F(b->trial); F(b->flag);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
-    if (b->lin_pin) (void)hipHostFree(b->lin_pin);
-    if (b->ts_host) (void)hipHostFree(b->ts_host);
+    b->ts_host.release();
     if (b->st) { (void)hipStreamSynchronize(b->st); chol_forget_stream(b->st); }
     if (b->own_stream && b->st) (void)hipStreamDestroy(b->st);
     delete b;
@@ -355,18 +353,6 @@ static int ba_plan_pack(stba_ba* b) {
     return STBA_OK;
 }
 
-// pinned, mapped host copy of [scalars (SC_GPMAX0 + world) | gc (n)] of a linearisation, read one solve later
-static int ba_lin_pin(stba_ba* b) {
-    if (b->lin_pin) return STBA_OK;
-    const size_t nh = (size_t)SC_GPMAX0 + b->world;
-    // (COHERENT, like every block the host reads behind a POLLED stamp rather than a stream synchronisation: without the flag the
-    // memory may be coarse-grained, and what a kernel wrote into it is only promised to the host at a synchronisation point --
-    // round 6: one run in several of tests/test_gpu_parity.py read a stale gradient norm here and stopped one iteration early)
-    STBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->lin_pin), (nh + (size_t)b->n) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    STBA_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->lin_pin_dev), b->lin_pin, 0));
-    return STBA_OK;
-}
-
 // device time of the last cross-rank sum of the reduced system: read once its events have completed (after a
 // synchronisation of the stream; a pair still in flight is waited for -- only on the multi-rank path)
 static void ba_collect_allreduce_time(stba_ba* b) {
@@ -423,8 +409,7 @@ static int ba_schur_step(stba_ba* b) {
     return launch_schur_rows(sa, b->n_tasks, b->st);
 }
 
-static int ba_build_reduced(stba_ba* b, const Damping& dm, bool export_host = false) {
-    b->lin_exported = false;
+static int ba_build_reduced(stba_ba* b, const Damping& dm) {
     const int init_scale = b->scale_init ? 0 : 1;
     // (the three extras vectors behind S -- diag, gc, rhs -- are zeroed on the way; the scalar slots are kept)
     double* extras = b->Sbuf + (size_t)b->lda * b->lda;
@@ -439,15 +424,8 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm, bool export_host = fa
     STBA_TRY(ba_schur_step(b));
     if (!b->ar && !dm.explicit_d && b->n == 6 * b->nc) {
         // one rank: camera blocks, LM diagonal, damping and padding in one launch
-        double* host_out = nullptr;
-        if (export_host) {          // (cost, |g|max slots and the gradient go to mapped host memory in the same launch)
-            STBA_TRY(ba_lin_pin(b));
-            host_out = b->lin_pin_dev;
-            b->lin_exported = true;
-        }
         STBA_TRY(launch_reduced_finalize(b->nc, b->n, b->Hcc, b->gc, b->cam_fixed, b->S(), b->lda, b->rhs(), b->ex_diag(), b->ex_gc(),
-                                         b->scale_c, init_scale, dm.use_scaling, dm.radius, dm.dmin, dm.dmax, b->dc, b->ex_scalar(),
-                                         SC_GPMAX0 + b->world, host_out, 0, b->st));
+                                         b->scale_c, init_scale, dm.use_scaling, dm.radius, dm.dmin, dm.dmax, b->dc, 0, b->st));
         b->scale_init = true;
         return STBA_OK;
     }
@@ -475,13 +453,9 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm, bool export_host = fa
         STBA_HIP(hipGetLastError());
     }
     if (!dm.explicit_d && b->n == 6 * b->nc) {
-        // behind the cross-rank sum: LM diagonal of the summed diag(Hcc), damping, padding (and the export of the scalars
-        // and the gradient to the host) in ONE launch, as on one rank
-        double* host_out = nullptr;
-        if (export_host) { STBA_TRY(ba_lin_pin(b)); host_out = b->lin_pin_dev; b->lin_exported = true; }
+        // behind the cross-rank sum: LM diagonal of the summed diag(Hcc), damping and padding in ONE launch, as on one rank
         STBA_TRY(launch_reduced_finalize(b->nc, b->n, b->Hcc, b->gc, b->cam_fixed, b->S(), b->lda, b->rhs(), b->ex_diag(), b->ex_gc(),
-                                         b->scale_c, init_scale, dm.use_scaling, dm.radius, dm.dmin, dm.dmax, b->dc, b->ex_scalar(),
-                                         SC_GPMAX0 + b->world, host_out, 1, b->st));
+                                         b->scale_c, init_scale, dm.use_scaling, dm.radius, dm.dmin, dm.dmax, b->dc, 1, b->st));
         b->scale_init = true;
         return STBA_OK;
     }
@@ -503,12 +477,12 @@ static int ba_fill_scalar_slots(stba_ba* b, double* cost2_dev) {
 
 // the trial block and the factorisation's flag into mapped host memory (several ranks; one rank: trial_finish_kernel does it)
 __global__ void export_trial_kernel(const double* __restrict__ trial, const int* __restrict__ flag, double* __restrict__ out, double seq) {
-    __shared__ double hp[TS_COUNT + 1];
+    __shared__ double hp[TS_BLOCK];
     const int k = threadIdx.x;
-    if (k < TS_COUNT) hp[k] = trial[k];
-    else if (k == TS_COUNT) hp[k] = (double)flag[0];
+    if (k == TS_SPEC_COST2) hp[k] = (double)flag[0];
+    else if (k < TS_BLOCK) hp[k] = trial[k];
     __syncthreads();
-    stamped_store_wave(out, hp, TS_COUNT + 1, seq, k);      // (one wave of 64; a stamped block: the host validates every line, see ba_wait_trial)
+    stamped_store_wave(out, hp, TS_BLOCK, seq, k);      // (one wave of 64; a stamped block: the host validates every line)
 }
 
 // back-substitution of the LM loop: dxp, and on the way the trial point (landmarks and cameras) + its step statistics
@@ -519,9 +493,9 @@ static int ba_backsub_trial(stba_ba* b) {
 }
 
 // trial point: both manifold updates (one launch), the residual-only kernel, and ONE launch that finishes every sum of
-// the trial block -- and, when host_out is given (one rank, nobody watching), writes the block and the factorisation's
-// flag straight into mapped host memory: the host waits for an event behind it instead of a device-to-host copy + stream
-// synchronisation, and the stream can go on
+// the trial block -- and, when host_out is given (nobody watching), writes the block and the factorisation's flag straight
+// into mapped host memory as a stamped block: the host polls it instead of a device-to-host copy + stream synchronisation,
+// and the stream can go on
 // (updated: the back-substitution kernel has made the trial point and the partial sums of its step already, see ba_backsub_trial)
 // (with_jac: the stream is going to linearise at the trial point anyway (speculation, see ba_run_lm) -- then THAT kernel
 // evaluates the trial point: residuals, Jacobian records and the cost partials in one pass instead of a residual-only pass
@@ -533,44 +507,19 @@ static int ba_trial(stba_ba* b, double* host_out, bool updated = false, bool wit
         STBA_TRY(launch_update(b->nc, b->np, b->cams[cur], b->pts[cur], b->dxc, b->dxp, b->cam_fixed, b->pt_fixed,
                                b->ex_gc(), b->dc, b->gp, b->dp, b->cams[nxt], b->pts[nxt], b->upd_partial_c,
                                b->upd_partial_p, b->st));
-    static_assert(TS_COST2 == 0 && TS_STEP2 == 1 && TS_X2 == 2 && TS_MODEL == 3 && TS_TIMEOUT == 4 && TS_CAM == 5 && TS_COUNT == 8, "trial_finish_kernel writes this layout");
+    static_assert(TS_COST2 == 0 && TS_STEP2 == 1 && TS_X2 == 2 && TS_MODEL == 3 && TS_TIMEOUT == 4 && TS_CAM == 5 && TS_COUNT == 8 &&
+                  TS_SPEC_COST2 == 8 && TS_LIN_COST2 == 9 && TS_LIN_GMAX == 10 && TS_BLOCK == 11, "trial_finish_kernel writes this layout");
     if (with_jac) STBA_TRY(ba_linearize_lm(b, nxt));
     else if (b->hl_fn) STBA_TRY(ba_host_linearize(b, nxt, false));
     else STBA_TRY(launch_linearize(lin_args(b, nxt, false), false, b->lin_grid, b->st));
-    STBA_TRY(launch_trial_finish(b->cost_partial, b->lin_grid, b->upd_partial_p, b->np > 0 ? pb : 0, b->upd_partial_c, cb, b->flag, b->trial,
+    STBA_TRY(launch_trial_finish(b->cost_partial, b->lin_grid, b->upd_partial_p, b->np > 0 ? pb : 0, b->upd_partial_c, cb, b->flag,
+                                 b->ex_scalar() + SC_COST2, b->ex_scalar() + SC_GPMAX0, b->world, b->ex_gc(), b->n, b->trial,
                                  b->ar ? nullptr : host_out, host_seq, b->st));
     if (b->ar) {
         if (b->ar(b->ar_user, b->trial, TS_TIMEOUT + 1, b->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
         // (several ranks: the block goes to the host behind the cross-rank sum of its first five entries)
         if (host_out) hipLaunchKernelGGL(export_trial_kernel, dim3(1), dim3(64), 0, b->st, b->trial, b->flag, host_out, host_seq);
         STBA_HIP(hipGetLastError());
-    }
-    return STBA_OK;
-}
-
-// The host's side of the mapped-memory hand-off: the trial block is complete once the sequence number behind it is the
-// one this iteration's kernel was given.  (No event: a record between two kernels costs the GPU ~5 us, and the stream goes
-// straight on with the speculative work.)  The stream is queried now and then so that a device fault ends the wait.
-// (round 6: the block is a STAMPED block -- every 64-byte line carries the sequence number and a check word, common.hpp -- and the
-// host works on its validated copy b->ts_vals: a sequence number BEHIND the block was seen ahead of the block's other line)
-static int ba_wait_trial(stba_ba* b, double seq) {
-    volatile double* h = b->ts_host;
-    const double t0 = wall_s();
-    auto is_mine = [seq](double st) { return st == seq; };
-    for (unsigned long n = 1; !stamped_try_read(h, TS_COUNT + 1, is_mine, b->ts_vals); ++n) {
-        if ((n & 0x3fff) == 0) {
-            const hipError_t q = hipStreamQuery(b->st);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(STBA_ERR_HIP, std::string("stream failed while waiting for the trial point: ") + hipGetErrorString(q));
-            if (q == hipSuccess) {
-                STBA_HIP(hipStreamSynchronize(b->st));
-                if (!stamped_try_read(h, TS_COUNT + 1, is_mine, b->ts_vals)) return fail(STBA_ERR_HIP, "the trial block never arrived in mapped host memory");
-                break;
-            }
-            if (wall_s() - t0 > 120.0) return fail(STBA_ERR_HIP, "timed out waiting for the trial point");
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
     }
     return STBA_OK;
 }
@@ -611,36 +560,6 @@ static int ba_read_linear_scalars(stba_ba* b, double* cost, double* gmax) {
     for (double v : g) m = std::max(m, std::fabs(v));
     *gmax = m;
     return STBA_OK;
-}
-
-// The same read, split: the copies are enqueued behind the reduced-system build into pinned memory and
-// consumed after the NEXT synchronisation (the trial point's), so that the factorisation is enqueued without
-// a host round trip in between (a 115 us bubble per iteration at C5)
-__global__ __launch_bounds__(256) void export_linear_kernel(const double* __restrict__ scalars, int nh, const double* __restrict__ gc,
-                                                            int n, double* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < nh) out[i] = scalars[i];
-    else if (i < nh + n) out[i] = gc[i - nh];
-}
-// (written by a kernel into mapped host memory: two device-to-host copies here cost ~30 us of idle GPU between the
-// compute queue and the copy engine, in front of every factorisation)
-static int ba_request_linear_scalars(stba_ba* b) {
-    if (b->lin_exported) return STBA_OK;         // (the reduced-system build wrote them on the way)
-    const size_t nh = (size_t)SC_GPMAX0 + b->world;
-    STBA_TRY(ba_lin_pin(b));
-    const int total = (int)nh + b->n;
-    hipLaunchKernelGGL(export_linear_kernel, dim3((total + 255) / 256), dim3(256), 0, b->st, b->ex_scalar(), (int)nh, b->ex_gc(), b->n,
-                       b->lin_pin_dev);
-    STBA_HIP(hipGetLastError());
-    return STBA_OK;
-}
-static void ba_finish_linear_scalars(const stba_ba* b, double* cost, double* gmax) {   // after a stream synchronisation
-    const size_t nh = (size_t)SC_GPMAX0 + b->world;
-    *cost = 0.5 * b->lin_pin[SC_COST2];
-    double m = 0.0;
-    for (int k = 0; k < b->world; ++k) m = std::max(m, b->lin_pin[SC_GPMAX0 + k]);
-    for (int k = 0; k < b->n; ++k) m = std::max(m, std::fabs(b->lin_pin[nh + k]));
-    *gmax = m;
 }
 
 static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterations, stba_lm_summary* sum,
@@ -745,24 +664,20 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         if (timing) STBA_HIP(hipEventRecord(ev[4], b->st));
         STBA_TRY(ba_backsub_trial(b));
         if (timing) STBA_HIP(hipEventRecord(ev[5], b->st));
-        // Nobody watches the iterations and there is one rank: the host learns the trial point's scalars through mapped
-        // memory and an event, and meanwhile the stream already linearises AT THE TRIAL POINT -- a step is accepted far
+        // Nobody watches the iterations and there is one rank: the host learns the trial point's scalars through a stamped
+        // block in mapped memory, and meanwhile the stream already linearises AT THE TRIAL POINT -- a step is accepted far
         // more often than not, and the host's round trip (wake-up, decision, enqueue: ~35 us) would otherwise be a
         // bubble on the GPU in every iteration.  A rejected step costs one linearisation at the old point (below).
         // (With several ranks too: every rank takes the same decision from the same all-reduced block, and the collectives of
         // the speculative build are enqueued on the stream like everything else.)
         const bool fast = deferred_ok && SPECULATE && !b->hl_fn;      // (host-linearised factors: the callback is synchronous host work)
-        if (fast && !b->ts_host) {
-            STBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->ts_host), (size_t)stamped_doubles(TS_COUNT + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-            STBA_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->ts_host_dev), b->ts_host, 0));
-            memset(b->ts_host, 0, (size_t)stamped_doubles(TS_COUNT + 1) * sizeof(double));
-        }
+        if (fast && !b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
         // (the speculative linearisation IS the evaluation of the trial point: one pass over the observations, not two)
         const bool speculate = fast && !(fixed && iter >= max_iter);
         const double seq = fast ? (b->ts_seq += 1.0) : 0.0;
-        STBA_TRY(ba_trial(b, fast ? b->ts_host_dev : nullptr, true, speculate, seq));
+        STBA_TRY(ba_trial(b, fast ? b->ts_host.dev : nullptr, true, speculate, seq));
         if (timing) STBA_HIP(hipEventRecord(ev[6], b->st));
-        double ts[TS_COUNT];
+        const double* ts = b->ts_vals;
         bool speculated = false;
         if (fast) {
             if (speculate) {
@@ -774,17 +689,18 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
                 STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_SPEC_COST2));
                 speculated = true;
             }
-            STBA_TRY(ba_wait_trial(b, seq));
-            for (int k = 0; k < TS_COUNT; ++k) ts[k] = b->ts_vals[k];
-            flag_h = (int)b->ts_vals[TS_COUNT];
+            // (a polled stamped block, no event: a record between two kernels costs the GPU ~5 us, and the stream goes straight on)
+            STBA_TRY(stamped_wait(b->ts_host.host, TS_BLOCK, [seq](double st) { return st == seq; }, b->ts_vals, hip_stream_state(b->st),
+                                  "trial point", 120.0));
+            flag_h = (int)ts[TS_SPEC_COST2];           // (the host's block carries the flag in that slot)
         } else {
-            STBA_TRY(download(ts, b->trial, TS_COUNT, b->st));
+            STBA_TRY(download(b->ts_vals, b->trial, TS_BLOCK, b->st));
             STBA_TRY(download(&flag_h, b->flag, 1, b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
         }
         if (pending) {
-            double c2, g2;
-            ba_finish_linear_scalars(b, &c2, &g2);
+            // (cost2 and |g|max of the build behind the previous iteration: trial_finish_kernel read them on the way)
+            const double c2 = 0.5 * ts[TS_LIN_COST2], g2 = ts[TS_LIN_GMAX];
             if (timing && hipEventElapsedTime(&ms, ev[pending_lin_ev], ev[pending_lin_ev + 1]) == hipSuccess) s.ms_linearize += ms;
             if (timing && hipEventElapsedTime(&ms, ev[10], ev[11]) == hipSuccess) s.ms_schur += ms;
             L.gmax = g2;
@@ -902,14 +818,13 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             // next reduced-system build (one collective per iteration); build it now.
             dm.radius = L.radius;
             if (timing) STBA_HIP(hipEventRecord(ev[e2], b->st));
-            STBA_TRY(ba_build_reduced(b, dm, deferred_ok));
+            STBA_TRY(ba_build_reduced(b, dm));
             if (timing) STBA_HIP(hipEventRecord(ev[e2 + 1], b->st));
             build_end_ev = e2 + 1;
             need_build = false;
             lin_timing_pending = false;
             if (deferred_ok) {
-                // (cost, |g|max) of the new point are consumed after the next synchronisation
-                STBA_TRY(ba_request_linear_scalars(b));
+                // (cost, |g|max) of the new point arrive with the next iteration's trial block
                 pending = true; pending_accepted = accepted; pending_iter = iter;
                 pending_lin_ev = spec_ev;
                 if (accepted) L.cost = new_cost;
@@ -948,7 +863,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     STBA_HIP(hipStreamSynchronize(b->st));
     if (pending) {      // the loop ended (iteration / radius limit) before the last linearisation's scalars were read
         double c2, g2;
-        ba_finish_linear_scalars(b, &c2, &g2);
+        STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
         L.gmax = g2;
         if (pending_accepted) L.cost = c2;
         if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
@@ -1529,7 +1444,7 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
     A_(dev_alloc(&b->cost_partial, (size_t)b->lin_grid));
     A_(dev_alloc(&b->upd_partial_c, (size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
     A_(dev_alloc(&b->upd_partial_p, (size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
-    A_(dev_alloc(&b->trial, (size_t)TS_COUNT + 1)); A_(dev_alloc(&b->flag, 1));
+    A_(dev_alloc(&b->trial, (size_t)TS_BLOCK)); A_(dev_alloc(&b->flag, 1));
 
     tmark("device allocations");
     A_(upload(b->cams[0], cams, nc * 7, b->st)); A_(upload(b->pts[0], pts, np * 3, b->st));
@@ -1667,7 +1582,6 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
     b->ar = fn; b->ar_user = user; b->rank = rank; b->world = world_size;
-    if (b->lin_pin) { (void)hipHostFree(b->lin_pin); b->lin_pin = nullptr; }     // sized by the world of its first use
     // what travels is decided again with the new group (the union pattern belongs to the group)
     b->pk_state = 0; b->pk_nz = 0;
     if (b->pk_blocks) { (void)hipFree(b->pk_blocks); b->pk_blocks = nullptr; }

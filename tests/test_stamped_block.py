@@ -2,7 +2,7 @@
 memory.  Round 6 measured that a sequence number written BEHIND the payload can be seen by the host ahead of payload in another
 cache line (tools/dbg/tri_repeat.py: 23 of 300 runs of the reference's 600 per-landmark solves ended somewhere else), so every line
 carries its stamp and a check word and the host validates what it reads.  Here: the host-side validator against hand-packed lines,
-torn ones included (no device needed)."""
+torn ones included, and the host's wait (stamped_wait) against a fake stream check (no device needed)."""
 import os
 import subprocess
 
