@@ -37,6 +37,16 @@ inline int fail(int code, const std::string& msg) {
 
 int require_device();   // STBA_OK or STBA_ERR_NO_DEVICE (there is no CPU fallback)
 
+// device buffer of `count` T (at least one)
+template <class T>
+inline int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+    if (e != hipSuccess) return fail(STBA_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return STBA_OK;
+}
+
 // Experiment knobs (environment variables) exist only in builds with -DSTBA_DEBUG_KNOBS (STBA_DEBUG_KNOBS=1 in the
 // environment of slam-tricks_amd/build.py); the product library reads no environment variables for its schedules.
 #ifdef STBA_DEBUG_KNOBS

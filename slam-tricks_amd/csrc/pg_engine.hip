@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "lm_policy.hpp"
 
 namespace stba {
 namespace {
@@ -1300,15 +1301,6 @@ __global__ __launch_bounds__(256) void pg_update4_kernel(int n_nodes, const doub
     if (threadIdx.x == 0) { partial[blockIdx.x * 4] = out3[0]; partial[blockIdx.x * 4 + 1] = out2[0]; partial[blockIdx.x * 4 + 2] = out2[1]; partial[blockIdx.x * 4 + 3] = 0.0; }
 }
 
-template <class T>
-int dalloc(T** p, size_t n) {
-    *p = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(STBA_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return STBA_OK;
-}
-double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 }  // namespace stba
 
@@ -1452,9 +1444,9 @@ static int pg_setup_coarse(stba_pg* g, int group_opt) {
     F(g->AdP); F(g->Ac0); F(g->W); F(g->Ainv); F(g->Ainv2); F(g->inv_work); F(g->rc_part); F(g->zc); F(g->part_cz); F(g->Dc);
     g->AdP = g->Ac0 = g->W = g->Ainv = g->Ainv2 = g->inv_work = g->rc_part = g->zc = g->part_cz = g->Dc = nullptr;
     g->agg = 0;
-    STBA_TRY(dalloc(&g->AdP, (size_t)g->n * 36)); STBA_TRY(dalloc(&g->Ac0, (size_t)nc * nc)); STBA_TRY(dalloc(&g->W, (size_t)4 * np * np));
-    STBA_TRY(dalloc(&g->Ainv, (size_t)nc * nc)); STBA_TRY(dalloc(&g->Ainv2, (size_t)nc * nc)); STBA_TRY(dalloc(&g->Dc, (size_t)na * 36)); STBA_TRY(dalloc(&g->inv_work, chol_spd_inverse_workspace_doubles(np)));
-    STBA_TRY(dalloc(&g->rc_part, (size_t)na * parts * 6)); STBA_TRY(dalloc(&g->zc, (size_t)nc)); STBA_TRY(dalloc(&g->part_cz, (size_t)((nc + 3) / 4) * 2 + 2));
+    STBA_TRY(dev_alloc(&g->AdP, (size_t)g->n * 36)); STBA_TRY(dev_alloc(&g->Ac0, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->W, (size_t)4 * np * np));
+    STBA_TRY(dev_alloc(&g->Ainv, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->Ainv2, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->Dc, (size_t)na * 36)); STBA_TRY(dev_alloc(&g->inv_work, chol_spd_inverse_workspace_doubles(np)));
+    STBA_TRY(dev_alloc(&g->rc_part, (size_t)na * parts * 6)); STBA_TRY(dev_alloc(&g->zc, (size_t)nc)); STBA_TRY(dev_alloc(&g->part_cz, (size_t)((nc + 3) / 4) * 2 + 2));
     STBA_HIP(hipMemsetAsync(g->rc_part, 0, (size_t)na * parts * 6 * sizeof(double), g->st));
     static DeviceOnce attr;
     STBA_TRY(attr.run([]() -> int {
@@ -1525,25 +1517,25 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
     auto bail = [&](int c) { pg_free(g); return c; };
 #define A_(call) do { rc = (call); if (rc != STBA_OK) return bail(rc); } while (0)
     const size_t n = (size_t)n_nodes, m = (size_t)n_edges;
-    A_(dalloc(&g->poses[0], n * 7)); A_(dalloc(&g->poses[1], n * 7)); A_(dalloc(&g->ei, m)); A_(dalloc(&g->ej, m));
-    A_(dalloc(&g->meas, m * 7)); A_(dalloc(&g->r, m * 6)); A_(dalloc(&g->Ji, m * 36)); A_(dalloc(&g->Jj, m * 36));
-    A_(dalloc(&g->g, n * 42)); g->Hd = g->g + n * 6;      // [gradient 6n | diagonal blocks 36n]: one cross-rank sum
-    A_(dalloc(&g->Minv, n * 36)); A_(dalloc(&g->d, n * 6)); A_(dalloc(&g->scalar, 1));
-    A_(dalloc(&g->scale, n * 6)); A_(dalloc(&g->x, n * 6)); A_(dalloc(&g->rr, n * 6)); A_(dalloc(&g->z, n * 6));
-    A_(dalloc(&g->p, n * 6)); A_(dalloc(&g->q, n * 6));
+    A_(dev_alloc(&g->poses[0], n * 7)); A_(dev_alloc(&g->poses[1], n * 7)); A_(dev_alloc(&g->ei, m)); A_(dev_alloc(&g->ej, m));
+    A_(dev_alloc(&g->meas, m * 7)); A_(dev_alloc(&g->r, m * 6)); A_(dev_alloc(&g->Ji, m * 36)); A_(dev_alloc(&g->Jj, m * 36));
+    A_(dev_alloc(&g->g, n * 42)); g->Hd = g->g + n * 6;      // [gradient 6n | diagonal blocks 36n]: one cross-rank sum
+    A_(dev_alloc(&g->Minv, n * 36)); A_(dev_alloc(&g->d, n * 6)); A_(dev_alloc(&g->scalar, 1));
+    A_(dev_alloc(&g->scale, n * 6)); A_(dev_alloc(&g->x, n * 6)); A_(dev_alloc(&g->rr, n * 6)); A_(dev_alloc(&g->z, n * 6));
+    A_(dev_alloc(&g->p, n * 6)); A_(dev_alloc(&g->q, n * 6));
     const size_t np_ = (size_t)std::max(g->nb_vec, std::max(g->nb_nodes, g->nb_edges)) * 2 + 2;
-    A_(dalloc(&g->part_e, np_)); A_(dalloc(&g->part_a, np_)); A_(dalloc(&g->part_b, np_)); A_(dalloc(&g->part_c, np_));
-    A_(dalloc(&g->part_d, np_));
-    if (node_fixed) A_(dalloc(&g->fixed, n));
-    A_(dalloc(&g->node_start, n + 1)); A_(dalloc(&g->end_code, 2 * m)); A_(dalloc(&g->u, 12 * m));
-    A_(dalloc(&g->end_node, 2 * m)); A_(dalloc(&g->contrib, 2 * m * 28));
-    A_(dalloc(&g->end_pos, 2 * m)); A_(dalloc(&g->end_rem, 2 * m)); A_(dalloc(&g->Bend, 72 * m)); A_(dalloc(&g->ubuf, 12 * n));
-    A_(dalloc(&g->pbuf, (size_t)2 * 256 * PP_SLOT)); A_(dalloc(&g->ustamp, (size_t)256 * PP_STAMP)); A_(dalloc(&g->pstamp, (size_t)256 * PP_STAMP));
+    A_(dev_alloc(&g->part_e, np_)); A_(dev_alloc(&g->part_a, np_)); A_(dev_alloc(&g->part_b, np_)); A_(dev_alloc(&g->part_c, np_));
+    A_(dev_alloc(&g->part_d, np_));
+    if (node_fixed) A_(dev_alloc(&g->fixed, n));
+    A_(dev_alloc(&g->node_start, n + 1)); A_(dev_alloc(&g->end_code, 2 * m)); A_(dev_alloc(&g->u, 12 * m));
+    A_(dev_alloc(&g->end_node, 2 * m)); A_(dev_alloc(&g->contrib, 2 * m * 28));
+    A_(dev_alloc(&g->end_pos, 2 * m)); A_(dev_alloc(&g->end_rem, 2 * m)); A_(dev_alloc(&g->Bend, 72 * m)); A_(dev_alloc(&g->ubuf, 12 * n));
+    A_(dev_alloc(&g->pbuf, (size_t)2 * 256 * PP_SLOT)); A_(dev_alloc(&g->ustamp, (size_t)256 * PP_STAMP)); A_(dev_alloc(&g->pstamp, (size_t)256 * PP_STAMP));
     if (hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess ||
         hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess)
         return bail(fail(STBA_ERR_HIP, "stba_pg_create: memset"));
     g->nb_nodes4 = (n_nodes + PG_NPW - 1) / PG_NPW;
-    A_(dalloc(&g->part_u, (size_t)g->nb_nodes * 4 + 4)); A_(dalloc(&g->scal_dev, 16)); A_(dalloc(&g->state, 1)); A_(dalloc(&g->cflag, 2));
+    A_(dev_alloc(&g->part_u, (size_t)g->nb_nodes * 4 + 4)); A_(dev_alloc(&g->scal_dev, 16)); A_(dev_alloc(&g->state, 1)); A_(dev_alloc(&g->cflag, 2));
     if (g->exp.alloc((size_t)stamped_doubles(PX_COUNT)) != STBA_OK || g->fin.alloc(16) != STBA_OK)
         return bail(fail(STBA_ERR_ALLOC, "stba_pg_create: mapped host memory"));
     memset(&g->last_pcg, 0, sizeof g->last_pcg);
@@ -1672,7 +1664,7 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     if (pcg_in) pcg = *pcg_in; else stba_pcg_default_options(&pcg);
     stba_lm_summary s;
     memset(&s, 0, sizeof s);
-    const double t0 = wall();
+    const double t0 = wall_s();
     const int N = 6 * g->n;
     STBA_TRY(pg_setup_coarse(g, pcg.coarse_group));
     const bool coarse = g->agg > 0;
@@ -1784,11 +1776,11 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     STBA_TRY(linearize_enqueue());
     STBA_TRY(linearize_finish(&cost, &gmax, &g2));
     s.initial_cost = cost;
-    double radius = opt.initial_trust_region_radius, decrease = 2.0;
+    TrustRegion region(opt);
     bool scale_init = false;
     int iter = 0;
     double eta = pcg.forcing_eta0;
-    if (trace) { memset(trace, 0, sizeof(double) * STBA_TRACE_COLS); trace[0] = cost; trace[2] = gmax; trace[5] = radius; trace[6] = 1; }
+    trace_start(trace, cost, gmax, region.radius);
     s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
     bool done = gmax <= opt.gradient_tolerance;
     if (done) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; }
@@ -1797,13 +1789,13 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     double last_rel_decrease = 1.0;      // of the last accepted step: (cost before - cost after) / cost before
     while (!done) {
         if (iter >= opt.max_num_iterations) break;
-        if (radius < opt.min_trust_region_radius) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
+        if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
         ++iter;
         const bool head_was_done = head_done;       // (behind an accepted step the preconditioner and the job's head are already on their way)
         if (!head_done) {
             if (g->job_reads_pending) { STBA_TRY(pg_wait_if_pending(g->st, g->ev_read)); g->job_reads_pending = false; }    // (a rejected step: no linearisation in between)
             hipLaunchKernelGGL(pg_precond_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->Hd, g->scale, scale_init ? 0 : 1,
-                               opt.jacobi_scaling, radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
+                               opt.jacobi_scaling, region.radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
             scale_init = true;
         }
         head_done = false;
@@ -2037,37 +2029,23 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
         const double model_change = -gx - 0.5 * xhx;
         const double step_norm = std::sqrt(step2), x_norm = std::sqrt(x2);
         ok = ok && model_change > 0.0 && std::isfinite(model_change) && std::isfinite(new_cost);
-        double cost_change = 0.0, rho = 0.0;
-        bool accepted = false, stop = false;
-        if (ok) {
-            cost_change = cost - new_cost;
-            rho = cost_change / model_change;
-            if (step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_PARAMETER; stop = true;
-            } else if (std::fabs(cost_change) <= opt.function_tolerance * cost) {
-                if (opt.function_tolerance_takes_step && rho > opt.min_relative_decrease) { g->cur = nxt; cost = new_cost; ++s.num_successful_steps; accepted = true; g->coarse_valid = false; }
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_FUNCTION; stop = true;
-            }
-            if (!stop) accepted = rho > opt.min_relative_decrease;
+        const StepVerdict v = judge_step(opt, cost, ok, new_cost, model_change, step_norm, x_norm);
+        trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
+        if (v.stop) {        // (no progress line)
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
+            if (v.accepted) { g->cur = nxt; cost = new_cost; ++s.num_successful_steps; g->coarse_valid = false; }
+            break;
         }
-        if (trace) {
-            double* tr = trace + (size_t)iter * STBA_TRACE_COLS;
-            tr[0] = ok ? new_cost : cost; tr[1] = cost_change; tr[2] = gmax; tr[3] = ok ? step_norm : 0.0; tr[4] = rho; tr[5] = radius;
-            tr[6] = accepted ? 1 : 0;
-        }
-        if (stop) break;
-        if (accepted) {
+        if (v.accepted) {
             g->cur = nxt;
             ++s.num_successful_steps;
-            last_rel_decrease = cost > 0.0 ? cost_change / cost : 1.0;
-            const double t = 2.0 * rho - 1.0;
-            radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-            decrease = 2.0;
+            last_rel_decrease = cost > 0.0 ? v.cost_change / cost : 1.0;
+            region.accept(v.rho, opt);
             double c2, g2_new = 0.0;
             STBA_TRY(linearize_enqueue());
             if (async_inv && build_on_st2) {        // the next iteration's preconditioner kernel and the head of its job, at once (job_head)
                 hipLaunchKernelGGL(pg_precond_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->Hd, g->scale, scale_init ? 0 : 1,
-                                   opt.jacobi_scaling, radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
+                                   opt.jacobi_scaling, region.radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
                 scale_init = true;
                 STBA_HIP(hipEventRecord(g->ev_in, g->st));
                 STBA_TRY(job_head());
@@ -2084,23 +2062,25 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
                 // (round 6) about to converge -- the step just taken changed the cost by less than 100 x the function tolerance: the
                 // error of the LAST inexact step is what the converged poses keep (about eta x its length; on C4 the last step still
                 // moves poses by 3.6e-3, and Eisenstat & Walker leave eta ~ 1e-2 there: 4e-5 in the poses, north_star asks for 1e-5)
-                if (pcg.forcing_eta_final > 0.0 && cost_change <= 100.0 * opt.function_tolerance * (cost + cost_change))
+                if (pcg.forcing_eta_final > 0.0 && v.cost_change <= 100.0 * opt.function_tolerance * (cost + v.cost_change))
                     eta = std::max(pcg.forcing_eta_min, std::min(eta, pcg.forcing_eta_final));
             }
             g2 = g2_new;
-            if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius; }
+            if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
+            // (the gradient is tested here, before the progress line: none is printed for the converging iteration)
             if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
         } else {
             ++s.num_unsuccessful_steps;
-            radius /= decrease; decrease *= 2.0;
-            if (trace) trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius;
+            region.reject();
+            if (trace) trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius;
         }
-        if (opt.minimizer_progress_to_stdout)
-            printf("%4d  %.6e   % .2e    %.2e   %.2e  % .2e  %.2e  pcg %d eta %.1e%s\n", iter, cost, cost_change, gmax, step_norm, rho, radius, k, eta_k,
-                   capped ? " CAP" : "");
+        if (opt.minimizer_progress_to_stdout) {
+            char tail[64];
+            snprintf(tail, sizeof tail, "  pcg %d eta %.1e%s", k, eta_k, capped ? " CAP" : "");
+            progress_step(iter, cost, v, gmax, step_norm, region.radius, tail);
+        }
     }
-    s.num_iterations = iter; s.final_cost = cost; s.final_radius = radius; s.final_gradient_max_norm = gmax;
-    s.seconds_total = wall() - t0;
+    finish_summary(&s, iter, cost, region.radius, gmax, t0);
     if (summary) *summary = s;
     if (pcg_iterations_total) *pcg_iterations_total = ps.iterations_total;
     if (coarse) {        // (how many coarse operators could not be factored: counted on the device, read once per solve)

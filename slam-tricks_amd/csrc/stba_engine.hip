@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "lm_policy.hpp"
 
 namespace stba {
 
@@ -24,19 +25,6 @@ int require_device() {
         return fail(STBA_ERR_NO_DEVICE, std::string("no HIP device visible (") +
                                             (e == hipSuccess ? "count=0" : hipGetErrorString(e)) +
                                             "); libstba has no CPU fallback");
-    return STBA_OK;
-}
-
-static double wall_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-template <class T>
-static int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) return fail(STBA_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
     return STBA_OK;
 }
 
@@ -524,29 +512,6 @@ static int ba_trial(stba_ba* b, double* host_out, bool updated = false, bool wit
     return STBA_OK;
 }
 
-struct LMState {
-    double cost = 0, gmax = 0, radius = 0, decrease = 2.0, x_norm = 0;
-};
-
-static void default_options(stba_lm_options* o) {
-    o->max_num_iterations = 50;
-    o->initial_trust_region_radius = 1e4;
-    o->max_trust_region_radius = 1e16;
-    o->min_trust_region_radius = 1e-32;
-    o->min_relative_decrease = 1e-3;
-    o->min_lm_diagonal = 1e-6;
-    o->max_lm_diagonal = 1e32;
-    o->function_tolerance = 1e-6;
-    o->gradient_tolerance = 1e-10;
-    o->parameter_tolerance = 1e-8;
-    o->jacobi_scaling = 1;
-    o->num_threads = 1;
-    o->minimizer_progress_to_stdout = 0;
-    o->update_state_every_iteration = 0;
-    o->phase_timing = 0;
-    o->function_tolerance_takes_step = 1;      // (stba.h: why the step is taken by default although Ceres >= 1.12 does not)
-}
-
 // reads {cost2, gpmax slots, gc} after a reduced-system build and returns cost / gradient max norm
 static int ba_read_linear_scalars(stba_ba* b, double* cost, double* gmax) {
     std::vector<double> h((size_t)SC_GPMAX0 + b->world);
@@ -581,8 +546,8 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     b->ar_ms = 0.0; b->ar_bytes = 0.0; b->ar_calls = 0; b->ar_timing_pending = false;
     Damping dm;
     dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
-    LMState L;
-    L.radius = opt.initial_trust_region_radius;
+    TrustRegion region(opt);
+    double cost = 0.0, gmax = 0.0;
 
     // ---- iteration 0: linearise at the start point
     if (timing) STBA_HIP(hipEventRecord(ev[0], b->st));
@@ -612,7 +577,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
                 s.termination_reason = fixed ? STBA_TERM_FIXED : STBA_TERM_MAX_ITER;
                 break;
             }
-            if (!fixed && L.radius < opt.min_trust_region_radius) {
+            if (!fixed && region.below_min(opt)) {
                 s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS;
                 break;
             }
@@ -621,7 +586,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         // (an event record is a packet of its own on the queue, ~5 us of idle GPU between two kernels: none is recorded that
         // is not needed -- when the system was built behind the previous iteration, that build's end event is the start of
         // this solve)
-        dm.radius = L.radius;
+        dm.radius = region.radius;
         const bool built_here = need_build;
         if (need_build) {
             if (timing) STBA_HIP(hipEventRecord(ev[2], b->st));
@@ -631,24 +596,19 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         }
         const int solve_start_ev = build_end_ev;
         if (first) {
-            STBA_TRY(ba_read_linear_scalars(b, &L.cost, &L.gmax));
-            s.initial_cost = L.cost;
-            if (trace) {
-                memset(trace, 0, sizeof(double) * STBA_TRACE_COLS);
-                trace[0] = L.cost; trace[2] = L.gmax; trace[5] = L.radius; trace[6] = 1;
-            }
+            STBA_TRY(ba_read_linear_scalars(b, &cost, &gmax));
+            s.initial_cost = cost;
+            trace_start(trace, cost, gmax, region.radius);
             first = false;
-            if (opt.minimizer_progress_to_stdout)
-                printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n"
-                       "%4d  %.6e    0.00e+00    %.2e   0.00e+00   0.00e+00  %.2e\n", 0, L.cost, L.gmax, L.radius);
+            if (opt.minimizer_progress_to_stdout) progress_start(cost, gmax, region.radius);     // (the only loop with a header)
             // Ceres: a residual block that returns a non-finite value fails its evaluation, and a failed evaluation of the START
             // point ends the solve as FAILURE before any step ("Initial residual and Jacobian evaluation failed"); at a trial
             // point it is an unsuccessful step -- the rho test rejects a non-finite cost.  (oracle.c: orc_ba_solve)
-            if (!std::isfinite(L.cost)) {
+            if (!std::isfinite(cost)) {
                 s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL;
                 break;
             }
-            if (!fixed && L.gmax <= opt.gradient_tolerance) {
+            if (!fixed && gmax <= opt.gradient_tolerance) {
                 s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
                 break;
             }
@@ -703,8 +663,8 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             const double c2 = 0.5 * ts[TS_LIN_COST2], g2 = ts[TS_LIN_GMAX];
             if (timing && hipEventElapsedTime(&ms, ev[pending_lin_ev], ev[pending_lin_ev + 1]) == hipSuccess) s.ms_linearize += ms;
             if (timing && hipEventElapsedTime(&ms, ev[10], ev[11]) == hipSuccess) s.ms_schur += ms;
-            L.gmax = g2;
-            if (pending_accepted) L.cost = c2;
+            gmax = g2;
+            if (pending_accepted) cost = c2;
             if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
             pending = false;
             if (pending_accepted && !fixed && g2 <= opt.gradient_tolerance) {
@@ -757,49 +717,27 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         const double step_norm = std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]);
         x_norm = std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]);
         const double model_change = ts[TS_MODEL] + ts[TS_CAM + 2];
+        // (a non-finite trial cost makes the step not ok: row [cost, 0, ., 0, 0], no stop test)
         if (step_ok && (!(model_change > 0.0) || !std::isfinite(model_change) || !std::isfinite(new_cost)))
             step_ok = false;
-        double cost_change = 0.0, rho = 0.0;
-        bool accepted = false, stop = false;
-        if (step_ok) {
-            cost_change = L.cost - new_cost;
-            rho = cost_change / model_change;
-            if (!fixed) {
-                if (step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-                    s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_PARAMETER;
-                    stop = true;
-                } else if (std::fabs(cost_change) <= opt.function_tolerance * L.cost) {
-                    // (function_tolerance_takes_step, stba.h: 1 = the decreasing step is taken before convergence is reported; 0 = not)
-                    if (opt.function_tolerance_takes_step && rho > opt.min_relative_decrease) {
-                        b->cur ^= 1; L.cost = new_cost; ++s.num_successful_steps; accepted = true;
-                    }
-                    s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_FUNCTION;
-                    stop = true;
-                }
-            }
-            if (!stop) accepted = rho > opt.min_relative_decrease;
-        }
-        if (trace) {
-            double* tr = trace + (size_t)iter * STBA_TRACE_COLS;
-            tr[0] = step_ok ? new_cost : L.cost; tr[1] = cost_change; tr[2] = L.gmax; tr[3] = step_ok ? step_norm : 0.0;
-            tr[4] = rho; tr[5] = L.radius; tr[6] = accepted ? 1 : 0;
-        }
-        if (stop) {
-            if (accepted) b->have_lin = b->have_blocks = false;
-            if (cb) (void)cb(cb_user, iter, L.cost, cost_change, L.gmax, step_norm, L.radius, accepted ? 1 : 0);
-            break;
-        }
+        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, !fixed);
+        const bool accepted = v.accepted;
         if (accepted) {
             b->cur ^= 1;
-            L.cost = new_cost;
+            cost = new_cost;
             ++s.num_successful_steps;
-            const double t = 2.0 * rho - 1.0;
-            L.radius = std::min(opt.max_trust_region_radius, L.radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-            L.decrease = 2.0;
-        } else {
+        }
+        trace_step(trace, iter, step_ok, cost, new_cost, v, gmax, step_norm, region.radius);
+        if (v.stop) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
+            if (accepted) b->have_lin = b->have_blocks = false;
+            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0);
+            break;
+        }
+        if (accepted) region.accept(v.rho, opt);
+        else {
             ++s.num_unsuccessful_steps;
-            L.radius /= L.decrease;
-            L.decrease *= 2.0;
+            region.reject();
         }
         need_build = true;
         if ((accepted || fixed) && !(fixed && iter >= max_iter)) {
@@ -816,7 +754,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             }
             // gradient of the new point is needed for the convergence test: it arrives with the
             // next reduced-system build (one collective per iteration); build it now.
-            dm.radius = L.radius;
+            dm.radius = region.radius;
             if (timing) STBA_HIP(hipEventRecord(ev[e2], b->st));
             STBA_TRY(ba_build_reduced(b, dm));
             if (timing) STBA_HIP(hipEventRecord(ev[e2 + 1], b->st));
@@ -827,7 +765,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
                 // (cost, |g|max) of the new point arrive with the next iteration's trial block
                 pending = true; pending_accepted = accepted; pending_iter = iter;
                 pending_lin_ev = spec_ev;
-                if (accepted) L.cost = new_cost;
+                if (accepted) cost = new_cost;
             } else {
                 double c2, g2;
                 STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
@@ -835,8 +773,8 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
                     (void)hipEventElapsedTime(&ms, ev[0], ev[1]); s.ms_linearize += ms;
                     (void)hipEventElapsedTime(&ms, ev[2], ev[3]); s.ms_schur += ms;
                 }
-                L.gmax = g2;
-                if (accepted) L.cost = c2;   // same value as new_cost up to summation order
+                gmax = g2;
+                if (accepted) cost = c2;   // same value as new_cost up to summation order
             }
         }
         else if (speculated && !accepted) {
@@ -845,17 +783,15 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             STBA_TRY(ba_normal_blocks(b));
             STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
         }
-        if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = L.gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = L.radius; }
-        if (opt.minimizer_progress_to_stdout)
-            printf("%4d  %.6e   % .2e    %.2e   %.2e  % .2e  %.2e\n", iter, L.cost, cost_change, L.gmax, step_norm, rho,
-                   L.radius);
+        if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
+        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
         if (cb) {
-            if (cb(cb_user, iter, L.cost, cost_change, L.gmax, step_norm, L.radius, accepted ? 1 : 0) != 0) {
+            if (cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0) != 0) {
                 s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER;
                 break;
             }
         }
-        if (!pending && accepted && !fixed && L.gmax <= opt.gradient_tolerance) {
+        if (!pending && accepted && !fixed && gmax <= opt.gradient_tolerance) {
             s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
             break;
         }
@@ -864,8 +800,8 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     if (pending) {      // the loop ended (iteration / radius limit) before the last linearisation's scalars were read
         double c2, g2;
         STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
-        L.gmax = g2;
-        if (pending_accepted) L.cost = c2;
+        gmax = g2;
+        if (pending_accepted) cost = c2;
         if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
         if (pending_accepted && !fixed && g2 <= opt.gradient_tolerance &&
             (s.termination_reason == STBA_TERM_MAX_ITER || s.termination_reason == STBA_TERM_MIN_RADIUS)) {
@@ -875,11 +811,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     }
     ba_collect_allreduce_time(b);
     s.ms_allreduce = b->ar_ms; s.allreduce_bytes = b->ar_bytes; s.allreduce_calls = b->ar_calls;
-    s.num_iterations = iter;
-    s.final_cost = L.cost;
-    s.final_radius = L.radius;
-    s.final_gradient_max_norm = L.gmax;
-    s.seconds_total = wall_s() - t_start;
+    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     if (sum) *sum = s;
     return STBA_OK;
@@ -2084,23 +2016,119 @@ int stba_calib_gauss_newton(int n_views, int n_corners, double* params, const do
     return STBA_OK;
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------
-// The same LM loop for SMALL problems (<= 32 local parameters: the reference's PnP call sites, its per-landmark triangulation,
-// the bounds demo, the curve fit): one kernel launch per step (small_dense.hip), no allocation, no copy and no synchronise per
-// solve -- the published workload of the reference is 0.12-0.22 ms per Solve() (st17-ceres/img/release.png), the general path
-// below took 3.5 ms.  Control flow, constants and trace columns are those of the general loop, statement for statement.
+// Dense LM problems: residual blocks evaluated by a host callback (the user's CostFunction::Evaluate), the damped normal equations
+// solved on the device.  One loop (dense_lm) over two step providers:
+//  - SmallDenseSteps, <= 32 local parameters (the reference's PnP call sites, its per-landmark triangulation, the bounds demo, the
+//    curve fit): one kernel launch per step (small_dense.hip), no allocation, no copy and no synchronise per solve -- the published
+//    workload of the reference is 0.12-0.22 ms per Solve() (st17-ceres/img/release.png), the general path took 3.5 ms;
+//  - GeneralDenseSteps: normal equations on the device, damping and model change on the host, the dense Cholesky of DenseWs.
+// A provider holds r and J (where the callback writes), g and dx of the last linearisation / step, and
+//   linearize(radius): r and J hold the callback's output at x -- make g (and on the small path the step at `radius`);
+//   step(radius, &model_change, &flag_ok): the step at `radius` for the current linearisation.
 // ---------------------------------------------------------------------------------------------
-static int dense_solve_small(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_params, int n, int n_res, double* x,
-                             const double* lower, const double* upper, const stba_lm_options& opt, stba_lm_summary* summary,
-                             double* trace, stba_iteration_callback cb, void* cb_user) {
+namespace stba {
+namespace {
+
+struct SmallDenseSteps {
+    static constexpr bool linearizes_failed_start = false;     // (a non-finite start cost: no device step, row 0's gradient is 0)
+    const stba_lm_options& opt;
+    const int n_res, n;
     SmallDenseWs* ws = nullptr;
-    STBA_TRY(small_dense_acquire(&ws, n_res, n));
-    struct Release { SmallDenseWs* w; ~Release() { small_dense_release(w); } } release{ws};
-    double* r = small_dense_r(ws);
-    double* J = small_dense_J(ws);
-    constexpr int NMAX = SMALL_DENSE_MAX_N;
+    double *r = nullptr, *J = nullptr;
+    double dx[SMALL_DENSE_MAX_N], g[SMALL_DENSE_MAX_N];
+    double model_change = 0.0;
+    int flag_h = 0;
+    bool first = true, have_step = false;
+    SmallDenseSteps(const stba_lm_options& o, int n_res_, int n_) : opt(o), n_res(n_res_), n(n_) {}
+    ~SmallDenseSteps() { if (ws) small_dense_release(ws); }
+    int init() {
+        STBA_TRY(small_dense_acquire(&ws, n_res, n));
+        r = small_dense_r(ws); J = small_dense_J(ws);
+        return STBA_OK;
+    }
+    int run(bool relinearize, double radius) {     // (H + D) dx = -g on the device; g refreshed when relinearised
+        const double *dxp = nullptr, *gp = nullptr;
+        STBA_TRY(small_dense_step(ws, n_res, n, relinearize, first, opt.jacobi_scaling != 0, radius, opt.min_lm_diagonal,
+                                  opt.max_lm_diagonal, &dxp, &gp, &model_change, &flag_h));
+        first = false;
+        for (int a = 0; a < n; ++a) { dx[a] = dxp[a]; g[a] = gp[a]; }
+        return STBA_OK;
+    }
+    int linearize(double radius) {      // the next iteration's step rides along with the new linearisation
+        STBA_TRY(run(true, radius));
+        have_step = true;
+        return STBA_OK;
+    }
+    int step(double radius, double* mc, bool* flag_ok) {
+        if (!have_step) STBA_TRY(run(false, radius));
+        have_step = false;
+        *mc = model_change;
+        *flag_ok = flag_h == 0;
+        return STBA_OK;
+    }
+};
+
+struct GeneralDenseSteps {
+    static constexpr bool linearizes_failed_start = true;      // (a non-finite start cost: linearised all the same, row 0 has its gradient)
+    const stba_lm_options& opt;
+    const int n_res, n;
+    DenseWs w;
+    double *dJ = nullptr, *dr = nullptr, *dH = nullptr, *dg = nullptr;
+    std::vector<double> rv, Jv, H, Hd, gv, dxv, scale, dvec;
+    double *r = nullptr, *J = nullptr, *g = nullptr, *dx = nullptr;
+    bool first = true;
+    GeneralDenseSteps(const stba_lm_options& o, int n_res_, int n_) : opt(o), n_res(n_res_), n(n_) {}
+    ~GeneralDenseSteps() { (void)hipFree(dJ); (void)hipFree(dr); (void)hipFree(dH); (void)hipFree(dg); }
+    int init() {
+        STBA_TRY(w.init(n, nullptr));
+        STBA_TRY(dev_alloc(&dJ, (size_t)n_res * n)); STBA_TRY(dev_alloc(&dr, (size_t)n_res));
+        STBA_TRY(dev_alloc(&dH, (size_t)n * n)); STBA_TRY(dev_alloc(&dg, (size_t)n));
+        rv.resize(n_res); Jv.resize((size_t)n_res * n); H.resize((size_t)n * n); Hd.resize((size_t)n * n);
+        gv.resize(n); dxv.resize(n); scale.resize(n); dvec.resize(n);
+        r = rv.data(); J = Jv.data(); g = gv.data(); dx = dxv.data();
+        return STBA_OK;
+    }
+    int linearize(double) {     // H = J^T J, g = J^T r on the device; the Jacobi scale from the first linearisation
+        STBA_TRY(upload(dJ, J, Jv.size(), w.st)); STBA_TRY(upload(dr, r, rv.size(), w.st));
+        STBA_HIP(hipMemsetAsync(dH, 0, (size_t)n * n * sizeof(double), w.st));
+        STBA_TRY(launch_dense_normal(n_res, n, dJ, dr, dH, n, dg, w.st));
+        STBA_TRY(download(H.data(), dH, H.size(), w.st)); STBA_TRY(download(g, dg, gv.size(), w.st));
+        STBA_HIP(hipStreamSynchronize(w.st));
+        if (first)
+            for (int a = 0; a < n; ++a) scale[a] = opt.jacobi_scaling ? 1.0 / (1.0 + std::sqrt(H[(size_t)a * n + a])) : 1.0;
+        first = false;
+        return STBA_OK;
+    }
+    int step(double radius, double* model_change, bool* flag_ok) {
+        Hd = H;
+        for (int a = 0; a < n; ++a) {
+            const double s2 = scale[a] * scale[a];
+            const double d = std::min(std::max(H[(size_t)a * n + a] * s2, opt.min_lm_diagonal), opt.max_lm_diagonal);
+            dvec[a] = d / radius / s2;
+            Hd[(size_t)a * n + a] += dvec[a];
+            dx[a] = -g[a];
+        }
+        int flag_h = 0;
+        STBA_TRY(w.load_factor_solve(Hd.data(), dx, &flag_h));
+        STBA_TRY(download(dx, w.x, (size_t)n, w.st));
+        STBA_HIP(hipStreamSynchronize(w.st));
+        STBA_TRY(chol_flag_status(flag_h));
+        *model_change = 0.0;
+        *flag_ok = flag_h == 0;
+        if (*flag_ok)
+            for (int a = 0; a < n; ++a) *model_change += -0.5 * g[a] * dx[a] + 0.5 * dvec[a] * dx[a] * dx[a];
+        return STBA_OK;
+    }
+};
+
+template <class Steps>
+int dense_lm(Steps& S, stba_residual_fn fn, stba_plus_fn plus, void* user, int n_params, int n, int n_res, double* x,
+             const double* lower, const double* upper, const stba_lm_options& opt, stba_lm_summary* summary, double* trace,
+             stba_iteration_callback cb, void* cb_user) {
     std::vector<double> xn((size_t)n_params), rn((size_t)n_res);
-    double dx[NMAX], g[NMAX];
     stba_lm_summary s;
     memset(&s, 0, sizeof s);
     const double t_start = wall_s();
@@ -2108,9 +2136,9 @@ static int dense_solve_small(stba_residual_fn fn, stba_plus_fn plus, void* user,
     auto gmax_of = [&]() {
         double m = 0.0;
         for (int a = 0; a < n; ++a) {
-            if (!bounded) m = std::max(m, std::fabs(g[a]));
+            if (!bounded) m = std::max(m, std::fabs(S.g[a]));
             else {
-                double y = x[a] - g[a];
+                double y = x[a] - S.g[a];
                 if (lower && y < lower[a]) y = lower[a];
                 if (upper && y > upper[a]) y = upper[a];
                 m = std::max(m, std::fabs(x[a] - y));
@@ -2119,48 +2147,35 @@ static int dense_solve_small(stba_residual_fn fn, stba_plus_fn plus, void* user,
         return m;
     };
     auto norm_of = [&](const double* v, int k) { double q = 0; for (int a = 0; a < k; ++a) q += v[a] * v[a]; return std::sqrt(q); };
-    double model_change = 0.0;
-    int flag_h = 0;
-    bool first = true;
-    auto step = [&](bool relinearize, double radius) -> int {     // (H + D) dx = -g on the device; g refreshed when relinearised
-        const double *dxp = nullptr, *gp = nullptr;
-        STBA_TRY(small_dense_step(ws, n_res, n, relinearize, first, opt.jacobi_scaling != 0, radius, opt.min_lm_diagonal,
-                                  opt.max_lm_diagonal, &dxp, &gp, &model_change, &flag_h));
-        first = false;
-        for (int a = 0; a < n; ++a) { dx[a] = dxp[a]; g[a] = gp[a]; }
-        return STBA_OK;
-    };
 
-    if (fn(user, x, r, J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
+    if (fn(user, x, S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
     double cost = 0.0;
-    for (int i = 0; i < n_res; ++i) cost += r[i] * r[i];
+    for (int i = 0; i < n_res; ++i) cost += S.r[i] * S.r[i];
     cost *= 0.5;
     s.initial_cost = cost;
-    double radius = opt.initial_trust_region_radius, decrease = 2.0, x_norm = norm_of(x, n_params), gmax = 0.0;
-    int iter = 0;
-    bool done = false, have_step = false;
-    s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
-    if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }
-    else {
-        STBA_TRY(step(true, radius));
-        have_step = true;
+    TrustRegion region(opt);
+    double x_norm = norm_of(x, n_params), gmax = 0.0;
+    if (std::isfinite(cost) || Steps::linearizes_failed_start) {
+        STBA_TRY(S.linearize(region.radius));
         gmax = gmax_of();
-        if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; done = true; }
     }
-    if (trace) { memset(trace, 0, sizeof(double) * STBA_TRACE_COLS); trace[0] = cost; trace[2] = gmax; trace[5] = radius; trace[6] = 1; }
+    trace_start(trace, cost, gmax, region.radius);
+    int iter = 0;
+    bool done = false;
+    s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
+    if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }    // (Ceres: initial evaluation failed, see stba_ba_solve)
+    else if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; done = true; }
     while (!done) {
         if (iter >= opt.max_num_iterations) { s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER; break; }
-        if (radius < opt.min_trust_region_radius) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
+        if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
         ++iter;
-        if (!have_step) STBA_TRY(step(false, radius));
-        have_step = false;
-        bool ok = (flag_h == 0);
-        double new_cost = 0.0, step_norm = 0.0, rho = 0.0, cost_change = 0.0;
+        double model_change = 0.0, new_cost = 0.0, step_norm = 0.0;
+        bool ok = false;
+        STBA_TRY(S.step(region.radius, &model_change, &ok));
         if (ok && (!(model_change > 0.0) || !std::isfinite(model_change))) ok = false;
-        bool accepted = false;
         if (ok) {
-            if (plus) plus(user, x, dx, xn.data());
-            else for (int a = 0; a < n_params; ++a) xn[a] = x[a] + dx[a];
+            if (plus) plus(user, x, S.dx, xn.data());
+            else for (int a = 0; a < n_params; ++a) xn[a] = x[a] + S.dx[a];
             if (bounded)
                 for (int a = 0; a < n_params; ++a) {
                     if (lower && xn[a] < lower[a]) xn[a] = lower[a];
@@ -2173,64 +2188,43 @@ static int dense_solve_small(stba_residual_fn fn, stba_plus_fn plus, void* user,
             new_cost *= 0.5;
             for (int a = 0; a < n_params; ++a) step_norm += (xn[a] - x[a]) * (xn[a] - x[a]);
             step_norm = std::sqrt(step_norm);
-            cost_change = cost - new_cost;
-            rho = cost_change / model_change;
-            if (trace) { double* tr = trace + (size_t)iter * STBA_TRACE_COLS; tr[0] = new_cost; tr[1] = cost_change; tr[3] = step_norm; tr[4] = rho; }
-            if (step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_PARAMETER;
-                if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius; trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; }
-                if (cb) (void)cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, 0);
-                break;
-            }
-            if (std::fabs(cost_change) <= opt.function_tolerance * cost) {
-                const bool take = opt.function_tolerance_takes_step && rho > opt.min_relative_decrease;      // (stba.h)
-                if (take) {
-                    memcpy(x, xn.data(), sizeof(double) * n_params); cost = new_cost; ++s.num_successful_steps;
-                    if (trace) trace[(size_t)iter * STBA_TRACE_COLS + 6] = 1;
-                }
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_FUNCTION;
-                if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius; trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; }
-                if (cb) (void)cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, take ? 1 : 0);
-                break;
-            }
-            accepted = rho > opt.min_relative_decrease;
         }
-        if (accepted) {
-            memcpy(x, xn.data(), sizeof(double) * n_params);
-            cost = new_cost; x_norm = norm_of(x, n_params); ++s.num_successful_steps;
-            if (fn(user, x, r, J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-            const double t = 2.0 * rho - 1.0;
-            radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-            decrease = 2.0;
-            STBA_TRY(step(true, radius));             // the next iteration's step rides along with the new linearisation
-            have_step = true;
+        // (a non-finite trial cost stays ok here, unlike BA and the pose graph: it is judged, and its NaN rho reaches the trace)
+        const StepVerdict v = judge_step(opt, cost, ok, new_cost, model_change, step_norm, x_norm);
+        if (v.accepted) { memcpy(x, xn.data(), sizeof(double) * n_params); cost = new_cost; ++s.num_successful_steps; }
+        if (v.stop) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
+            trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
+            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, v.accepted ? 1 : 0);
+            break;
+        }
+        if (v.accepted) {
+            x_norm = norm_of(x, n_params);
+            if (fn(user, x, S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
+            region.accept(v.rho, opt);
+            STBA_TRY(S.linearize(region.radius));
             gmax = gmax_of();
         } else {
             ++s.num_unsuccessful_steps;
-            radius /= decrease; decrease *= 2.0;
+            region.reject();
         }
-        if (trace) {
-            double* tr = trace + (size_t)iter * STBA_TRACE_COLS;
-            if (!ok) { tr[0] = cost; tr[1] = 0; tr[3] = 0; tr[4] = 0; }
-            tr[2] = gmax; tr[5] = radius; tr[6] = accepted ? 1 : 0;
-        }
-        if (opt.minimizer_progress_to_stdout)
-            printf("%4d  %.6e   % .2e    %.2e   %.2e  % .2e  %.2e\n", iter, cost, cost_change, gmax, step_norm, rho, radius);
-        if (cb && cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, accepted ? 1 : 0) != 0) {
+        trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
+        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
+        if (cb && cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, v.accepted ? 1 : 0) != 0) {
             s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER; break;
         }
-        if (accepted && gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
+        if (v.accepted && gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
     }
-    s.num_iterations = iter; s.final_cost = cost; s.final_radius = radius; s.final_gradient_max_norm = gmax;
-    s.seconds_total = wall_s() - t_start;
+    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
     if (summary) *summary = s;
     return STBA_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// small dense LM problems: residual blocks evaluated by a host callback (the user's
-// CostFunction::Evaluate), normal equations + damped Cholesky step on the device.
-// ---------------------------------------------------------------------------------------------
+}  // namespace
+}  // namespace stba
+
+extern "C" {
+
 int stba_dense_solve(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_params, int n_local, int n_res,
                      double* x, const double* lower, const double* upper, const stba_lm_options* opt_in,
                      stba_lm_summary* summary, double* trace, stba_iteration_callback cb, void* cb_user) {
@@ -2244,148 +2238,14 @@ int stba_dense_solve(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_p
     stba_lm_options opt;
     if (opt_in) opt = *opt_in; else default_options(&opt);
     const int n = n_local;
-    if (small_dense_fits(n_res, n))
-        return dense_solve_small(fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
-    DenseWs w;
-    STBA_TRY(w.init(n, nullptr));
-    double *dJ = nullptr, *dr = nullptr, *dH = nullptr, *dg = nullptr;
-    STBA_TRY(dev_alloc(&dJ, (size_t)n_res * n)); STBA_TRY(dev_alloc(&dr, (size_t)n_res));
-    STBA_TRY(dev_alloc(&dH, (size_t)n * n)); STBA_TRY(dev_alloc(&dg, (size_t)n));
-    struct Guard { double *a, *b, *c, *d; ~Guard() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); } } guard{dJ, dr, dH, dg};
-    std::vector<double> r(n_res), J((size_t)n_res * n), H((size_t)n * n), Hd((size_t)n * n), g(n), dx(n), scale(n),
-        xn(n_params), rn(n_res), dvec(n);
-    stba_lm_summary s;
-    memset(&s, 0, sizeof s);
-    const double t_start = wall_s();
-    const bool bounded = lower || upper;
-
-    auto linearize = [&]() -> int {   // H = J^T J, g = J^T r on the device
-        STBA_TRY(upload(dJ, J.data(), J.size(), w.st)); STBA_TRY(upload(dr, r.data(), r.size(), w.st));
-        STBA_HIP(hipMemsetAsync(dH, 0, (size_t)n * n * sizeof(double), w.st));
-        STBA_TRY(launch_dense_normal(n_res, n, dJ, dr, dH, n, dg, w.st));
-        STBA_TRY(download(H.data(), dH, H.size(), w.st)); STBA_TRY(download(g.data(), dg, g.size(), w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        return STBA_OK;
-    };
-    auto gmax_of = [&]() {
-        double m = 0.0;
-        for (int a = 0; a < n; ++a) {
-            if (!bounded) m = std::max(m, std::fabs(g[a]));
-            else {
-                double y = x[a] - g[a];
-                if (lower && y < lower[a]) y = lower[a];
-                if (upper && y > upper[a]) y = upper[a];
-                m = std::max(m, std::fabs(x[a] - y));
-            }
-        }
-        return m;
-    };
-    auto norm_of = [&](const double* v, int k) { double q = 0; for (int a = 0; a < k; ++a) q += v[a] * v[a]; return std::sqrt(q); };
-
-    if (fn(user, x, r.data(), J.data()) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-    double cost = 0.0;
-    for (double v : r) cost += v * v;
-    cost *= 0.5;
-    s.initial_cost = cost;
-    STBA_TRY(linearize());
-    for (int a = 0; a < n; ++a) scale[a] = opt.jacobi_scaling ? 1.0 / (1.0 + std::sqrt(H[(size_t)a * n + a])) : 1.0;
-    double gmax = gmax_of(), radius = opt.initial_trust_region_radius, decrease = 2.0, x_norm = norm_of(x, n_params);
-    int iter = 0;
-    if (trace) { memset(trace, 0, sizeof(double) * STBA_TRACE_COLS); trace[0] = cost; trace[2] = gmax; trace[5] = radius; trace[6] = 1; }
-    s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
-    bool done = false;
-    if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }    // (Ceres: initial evaluation failed, see stba_ba_solve)
-    else if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; done = true; }
-    while (!done) {
-        if (iter >= opt.max_num_iterations) { s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER; break; }
-        if (radius < opt.min_trust_region_radius) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
-        ++iter;
-        Hd = H;
-        for (int a = 0; a < n; ++a) {
-            const double s2 = scale[a] * scale[a];
-            const double d = std::min(std::max(H[(size_t)a * n + a] * s2, opt.min_lm_diagonal), opt.max_lm_diagonal);
-            dvec[a] = d / radius / s2;
-            Hd[(size_t)a * n + a] += dvec[a];
-            dx[a] = -g[a];
-        }
-        int flag_h = 0;
-        STBA_TRY(w.load_factor_solve(Hd.data(), dx.data(), &flag_h));
-        STBA_TRY(download(dx.data(), w.x, (size_t)n, w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        STBA_TRY(chol_flag_status(flag_h));
-        bool ok = (flag_h == 0);
-        double model_change = 0.0, new_cost = 0.0, step_norm = 0.0, rho = 0.0, cost_change = 0.0;
-        if (ok) {
-            for (int a = 0; a < n; ++a) model_change += -0.5 * g[a] * dx[a] + 0.5 * dvec[a] * dx[a] * dx[a];
-            if (!(model_change > 0.0) || !std::isfinite(model_change)) ok = false;
-        }
-        bool accepted = false;
-        if (ok) {
-            if (plus) plus(user, x, dx.data(), xn.data());
-            else for (int a = 0; a < n_params; ++a) xn[a] = x[a] + dx[a];
-            if (bounded)
-                for (int a = 0; a < n_params; ++a) {
-                    if (lower && xn[a] < lower[a]) xn[a] = lower[a];
-                    if (upper && xn[a] > upper[a]) xn[a] = upper[a];
-                }
-            if (fn(user, xn.data(), rn.data(), nullptr) != 0) ok = false;
-        }
-        if (ok) {
-            for (double v : rn) new_cost += v * v;
-            new_cost *= 0.5;
-            for (int a = 0; a < n_params; ++a) step_norm += (xn[a] - x[a]) * (xn[a] - x[a]);
-            step_norm = std::sqrt(step_norm);
-            cost_change = cost - new_cost;
-            rho = cost_change / model_change;
-            if (trace) { double* tr = trace + (size_t)iter * STBA_TRACE_COLS; tr[0] = new_cost; tr[1] = cost_change; tr[3] = step_norm; tr[4] = rho; }
-            if (step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_PARAMETER;
-                if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius; trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; }
-                if (cb) (void)cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, 0);
-                break;
-            }
-            if (std::fabs(cost_change) <= opt.function_tolerance * cost) {
-                const bool take = opt.function_tolerance_takes_step && rho > opt.min_relative_decrease;      // (stba.h)
-                if (take) {
-                    memcpy(x, xn.data(), sizeof(double) * n_params); cost = new_cost; ++s.num_successful_steps;
-                    if (trace) trace[(size_t)iter * STBA_TRACE_COLS + 6] = 1;
-                }
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_FUNCTION;
-                if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 5] = radius; trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; }
-                if (cb) (void)cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, take ? 1 : 0);
-                break;
-            }
-            accepted = rho > opt.min_relative_decrease;
-        }
-        if (accepted) {
-            memcpy(x, xn.data(), sizeof(double) * n_params);
-            cost = new_cost; x_norm = norm_of(x, n_params); ++s.num_successful_steps;
-            if (fn(user, x, r.data(), J.data()) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-            STBA_TRY(linearize());
-            gmax = gmax_of();
-            const double t = 2.0 * rho - 1.0;
-            radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-            decrease = 2.0;
-        } else {
-            ++s.num_unsuccessful_steps;
-            radius /= decrease; decrease *= 2.0;
-        }
-        if (trace) {
-            double* tr = trace + (size_t)iter * STBA_TRACE_COLS;
-            if (!ok) { tr[0] = cost; tr[1] = 0; tr[3] = 0; tr[4] = 0; }
-            tr[2] = gmax; tr[5] = radius; tr[6] = accepted ? 1 : 0;
-        }
-        if (opt.minimizer_progress_to_stdout)
-            printf("%4d  %.6e   % .2e    %.2e   %.2e  % .2e  %.2e\n", iter, cost, cost_change, gmax, step_norm, rho, radius);
-        if (cb && cb(cb_user, iter, cost, cost_change, gmax, step_norm, radius, accepted ? 1 : 0) != 0) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER; break;
-        }
-        if (accepted && gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
+    if (small_dense_fits(n_res, n)) {
+        SmallDenseSteps S(opt, n_res, n);
+        STBA_TRY(S.init());
+        return dense_lm(S, fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
     }
-    s.num_iterations = iter; s.final_cost = cost; s.final_radius = radius; s.final_gradient_max_norm = gmax;
-    s.seconds_total = wall_s() - t_start;
-    if (summary) *summary = s;
-    return STBA_OK;
+    GeneralDenseSteps S(opt, n_res, n);
+    STBA_TRY(S.init());
+    return dense_lm(S, fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
 }
 
 }  // extern "C"
