@@ -129,7 +129,8 @@ void orc_so3r3_plus(const double x[3], const double d[3], double out[3]) {
     orc_so3_log(qc, out);
 }
 
-/* V(theta) of SE3::exp:  I + (1-cos)/th^2 K + (th - sin)/th^3 K^2 */
+/* V(theta) of SE3::exp:  I + (1-cos)/th^2 K + (th - sin)/th^3 K^2; (1-cos)/th^2 as (sin(th/2)/(th/2))^2/2, which has no
+ * cancellation (the literal form is 0 instead of 1/2 where cos th rounds to 1), the same as the device's left_jacobian_coeffs */
 static void so3_left_jacobian(const double w[3], double V[9]) {
     const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
     double K[9], K2[9];
@@ -145,8 +146,8 @@ static void so3_left_jacobian(const double w[3], double V[9]) {
         a = 0.5 - th2 / 24.0;
         b = 1.0 / 6.0 - th2 / 120.0;
     } else {
-        const double th = sqrt(th2);
-        a = (1.0 - cos(th)) / th2;
+        const double th = sqrt(th2), s = sin(0.5 * th) / (0.5 * th);
+        a = 0.5 * s * s;
         b = (th - sin(th)) / (th2 * th);
     }
     for (int i = 0; i < 9; ++i) V[i] = a * K[i] + b * K2[i];

@@ -306,16 +306,25 @@ __host__ __device__ inline void so3_plus(const double q[4], const double d[3], d
     out[0] = ox / n; out[1] = oy / n; out[2] = oz / n; out[3] = ow / n;
 }
 
+// the coefficients of the SO3 left Jacobian V(theta) = I + a K + b K^2, K = hat(theta), from th2 = |theta|^2:
+// a = (1 - cos th) / th^2 = (sin(th/2) / (th/2))^2 / 2, the second form free of cancellation (the first is 0 instead of 1/2 where
+// cos th rounds to 1, 1e-10 < th < 2e-8, and loses leading digits up to th ~ 1e-5); b = (th - sin th) / th^3 is kept literal:
+// its error enters V as b th^2 <= 1e-16.  oracle/oracle.c computes the same.
+__host__ __device__ inline void left_jacobian_coeffs(double th2, double& a, double& b) {
+    if (th2 < 1e-20) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; return; }
+    const double th = sqrt(th2), s = sin(0.5 * th) / (0.5 * th);
+    a = 0.5 * s * s;
+    b = (th - sin(th)) / (th2 * th);
+}
+
 // Sophus SE3::exp for the tangent [rho, theta]: rotation matrix + translation V(theta) rho
 __host__ __device__ inline void se3_exp_rt(const double xi[6], double R[9], double t[3]) {
     double q[4];
     so3_exp(xi + 3, q);
     quat_to_rot(q, R);
     const double w0 = xi[3], w1 = xi[4], w2 = xi[5];
-    const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
     double a, b;
-    if (th2 < 1e-20) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-    else { const double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+    left_jacobian_coeffs(w0 * w0 + w1 * w1 + w2 * w2, a, b);
     // V = I + a K + b K^2,  K = hat(w)
     const double K[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
     double K2[9];
@@ -343,10 +352,8 @@ __host__ __device__ inline void so3_log(const double* q, double* w) {
     w[0] = k * q[0]; w[1] = k * q[1]; w[2] = k * q[2];
 }
 __host__ __device__ inline void so3_left_jacobian(const double* w, double* Vm) {
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
     double a, b;
-    if (th2 < 1e-20) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-    else { const double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+    left_jacobian_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], a, b);
     const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {

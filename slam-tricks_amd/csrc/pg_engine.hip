@@ -77,17 +77,8 @@ __host__ __device__ inline void se3_log7(const double* T, double* xi) {
     if (n2 < 1e-20) k = 2.0 / qw - (2.0 / 3.0) * n2 / (qw * qw * qw);
     else { const double n = sqrt(n2); k = 2.0 * ((qw < 0) ? atan2(-n, -qw) : atan2(n, qw)) / n; }
     const double w[3] = {k * T[0], k * T[1], k * T[2]};
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double a, b;
-    if (th2 < 1e-20) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-    else { const double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
-    double K[9], V[9];
-    hat3d(w, K);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double k2 = K[i * 3] * K[j] + K[i * 3 + 1] * K[3 + j] + K[i * 3 + 2] * K[6 + j];
-            V[i * 3 + j] = (i == j ? 1.0 : 0.0) + a * K[i * 3 + j] + b * k2;
-        }
+    double V[9];
+    so3_left_jacobian(w, V);
     // rho = V^-1 t
     const double aa = V[0], bb = V[1], cc = V[2], dd = V[3], ee = V[4], ff = V[5], gg = V[6], hh = V[7], ii = V[8];
     const double C0 = ee * ii - ff * hh, C1 = ff * gg - dd * ii, C2 = dd * hh - ee * gg;

@@ -340,6 +340,13 @@ def curve_fit_data(n=1000, seed=17, abc=(1.0, 2.0, 3.0), sigma=0.1):
 
 
 # --------------------------------------------------------------------------- st3 calibration (C3)
+def _left_jacobian_coeffs(a):
+    """(sin a / a, (1 - cos a) / a^2, (a - sin a) / a^3) of the angle a > 0; the second as (sin(a/2) / (a/2))^2 / 2, without the
+    cancellation of 1 - cos a (which is 0 where cos a rounds to 1)"""
+    h = np.sin(0.5 * a) / (0.5 * a)
+    return np.sin(a) / a, 0.5 * h * h, (a - np.sin(a)) / (a ** 3)
+
+
 def se3_exp(xi):
     """Sophus SE3::exp, tangent [rho, theta] -> (R, t)"""
     rho, th = np.asarray(xi[:3], float), np.asarray(xi[3:], float)
@@ -349,23 +356,27 @@ def se3_exp(xi):
         R = np.eye(3) + K + 0.5 * K @ K
         V = np.eye(3) + 0.5 * K + K @ K / 6.0
     else:
-        R = np.eye(3) + np.sin(a) / a * K + (1 - np.cos(a)) / (a * a) * K @ K
-        V = np.eye(3) + (1 - np.cos(a)) / (a * a) * K + (a - np.sin(a)) / (a ** 3) * K @ K
+        s, c, b = _left_jacobian_coeffs(a)
+        R = np.eye(3) + s * K + c * K @ K
+        V = np.eye(3) + c * K + b * K @ K
     return R, V @ rho
 
 
 def se3_log(R, t):
-    c = np.clip((np.trace(R) - 1) / 2, -1, 1)
-    a = np.arccos(c)
-    if a < 1e-10:
-        th = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / 2
-    else:
-        th = a / (2 * np.sin(a)) * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    """Sophus SE3::log of (R, t) -> [rho, theta]: the angle from the quaternion, 2 atan2(|xyz|, w) with w >= 0, which keeps
+    its digits near 0 and near pi (arccos of the trace loses half of them at 0, and sin theta vanishes at pi)"""
+    q = quat_from_rot(R)
+    if q[3] < 0:
+        q = -q
+    n = np.linalg.norm(q[:3])
+    a = 2.0 * np.arctan2(n, q[3])
+    th = q[:3] * (a / n) if n > 0 else np.zeros(3)
     K = np.array([[0, -th[2], th[1]], [th[2], 0, -th[0]], [-th[1], th[0], 0]])
     if a < 1e-10:
         V = np.eye(3) + 0.5 * K + K @ K / 6.0
     else:
-        V = np.eye(3) + (1 - np.cos(a)) / (a * a) * K + (a - np.sin(a)) / (a ** 3) * K @ K
+        _, c, b = _left_jacobian_coeffs(a)
+        V = np.eye(3) + c * K + b * K @ K
     return np.concatenate([np.linalg.solve(V, t), th])
 
 
