@@ -255,6 +255,29 @@ int stba_ba_time_linearize(stba_ba* ba, int reps, double* ms_avg);
  * FP64 atomics and of observation pairs of one launch (either may be NULL) */
 int stba_ba_time_schur(stba_ba* ba, int reps, double* ms_avg, double* lds_atomics_per_launch, double* pairs_per_launch);
 
+/* --- covariance (ceres::Covariance) ------------------------------------------------------- */
+/* C = (J^T J)^-1 of the UNDAMPED, unscaled problem at the current parameters (not multiplied by a residual variance, as in Ceres),
+ * in the engine's tangent coordinates: per camera [dtheta(3) of q <- q (x) exp(dtheta), dt(3)], per landmark its 3 coordinates.
+ * Constant dofs (cam_fixed) and constant landmarks (pt_fixed) have zero rows and columns in every block.
+ * stba_ba_covariance_compute re-linearises (through the host lineariser if one is set), builds the undamped reduced camera system S
+ * = U - E V^-1 E^T (the explicit-damping path of stba_ba_reduced_system with zero damping, either Schur form) and inverts it on the
+ * device; Sigma_cc = S^-1 (lower triangle, packed) and every V_j^-1 stay on the device until the next compute,
+ * stba_ba_covariance_release or stba_ba_destroy.  It needs 4 np^2 doubles for the length of the call (np: 6 n_cams rounded up to
+ * 128; 1.16 GB at 1000 cameras) and n (n + 1) / 2 afterwards.  The LM state is left as it was: a later stba_ba_solve is
+ * bit-identical to one without this call.
+ * rank test: rcond = smallest / largest Cholesky pivot, once for S (over the free dofs) and for every free landmark's V_j.  If any is
+ * below min_rcond (Ceres' min_reciprocal_condition_number, 1e-14) the call fails with STBA_ERR_NOT_POSITIVE_DEFINITE and
+ * stba_last_error() names S, or how many landmarks failed and the first.  This pivot ratio is a cheap test, NOT a condition number
+ * estimate; fixing the gauge is the caller's job (see DESIGN.md for what it does on a gauge-free scene).  *rcond_out (may be NULL):
+ * the smallest ratio found.  With an all-reduce hook or communicator set (several ranks): STBA_ERR_STATE. */
+int stba_ba_covariance_compute(stba_ba* ba, double min_rcond, double* rcond_out);
+/* out[n_pairs*36]: the 6x6 block Sigma_cc[cam_a[k], cam_b[k]] row-major per pair (b < a: the transpose of the stored block) */
+int stba_ba_camera_covariance(stba_ba* ba, int n_pairs, const int* cam_a, const int* cam_b, double* out);
+/* out[n*9]: the 3x3 marginal covariance of landmarks pts[0..n) (pts = NULL: all n_pts landmarks in order, n = n_pts):
+ * V_j^-1 + sum over pairs of its observations F_a^T Sigma_cc[a, b] F_b, F_a = E_{a,j} V_j^-1 (covariance.hip) */
+int stba_ba_point_covariance(stba_ba* ba, int n, const int* pts, double* out);
+int stba_ba_covariance_release(stba_ba* ba);
+
 /* ================================ dense SPD solver ======================================== */
 /* A: n*n row-major SPD (lower triangle read), overwritten by L (lower).  Runs the blocked MFMA
  * Cholesky on the device.  Returns STBA_ERR_NOT_POSITIVE_DEFINITE if a pivot fails. */
@@ -457,6 +480,12 @@ int stba_dense_solve(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_p
                      int n_res, double* x, const double* lower, const double* upper,
                      const stba_lm_options* opt, stba_lm_summary* summary, double* trace,
                      stba_iteration_callback cb, void* cb_user);
+
+/* covariance of a small dense problem (not a bundle adjustment) at x: the callback is evaluated once, J^T J formed on the device as
+ * in stba_dense_solve's general path and inverted there; cov[n_local*n_local] row-major in LOCAL coordinates.  Same limits as the
+ * dense solve (4096 local parameters, 2.7e8 Jacobian entries) and the same pivot test as stba_ba_covariance_compute. */
+int stba_dense_covariance(stba_residual_fn fn, void* user, int n_params, int n_local, int n_res, const double* x, double min_rcond,
+                          double* cov, double* rcond_out);
 
 #ifdef __cplusplus
 }

@@ -1200,20 +1200,25 @@ inline void DensePlus(void* user, const double* x, const double* d, double* out)
 
 struct DenseSync { DenseCtx* c; const double* x; };
 
-inline bool SolveDense(const Solver::Options& o, Problem* p, Solver::Summary* sum) {
-    DenseCtx c;
+// the variable blocks of the dense path (used by a residual block and not constant), their offsets, and the scratch of DenseResidual
+inline void DenseLayout(Problem* p, DenseCtx& c, bool* any_bounds, bool* any_local) {
     c.p = p;
-    bool any_bounds = false, any_local = false;
     std::vector<unsigned char> used(p->blocks().size(), 0);
     for (auto& r : p->residuals()) for (int k : r.blocks) used[(size_t)k] = 1;
     for (auto& b : p->blocks()) {
         if (!used[(size_t)b.index] || b.constant) continue;
         c.var_blocks.push_back(b.index); c.amb_off.push_back(c.n_amb); c.loc_off.push_back(c.n_loc);
         c.n_amb += b.size; c.n_loc += b.local_size();
-        any_bounds |= !b.lower.empty(); any_local |= (b.local != nullptr);
+        *any_bounds |= !b.lower.empty(); *any_local |= (b.local != nullptr);
     }
     c.n_res = p->NumResiduals();
     c.Prepare();
+}
+
+inline bool SolveDense(const Solver::Options& o, Problem* p, Solver::Summary* sum) {
+    DenseCtx c;
+    bool any_bounds = false, any_local = false;
+    DenseLayout(p, c, &any_bounds, &any_local);
     if (c.n_loc == 0 || c.n_res == 0) { sum->termination_type = CONVERGENCE; sum->message = "nothing to optimise"; return true; }
     if (c.n_loc > 4096 || (double)c.n_loc * c.n_res > 2.7e8) { sum->termination_type = FAILURE; sum->message = "generic (callback) problems are limited to 4096 local parameters and 2.7e8 Jacobian entries; use ReprojectionFactor for large bundle adjustment"; return false; }
     std::vector<double> x(c.n_amb), lo, up;
@@ -1392,6 +1397,203 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
     summary->preprocessor_time_in_seconds = ph.recognise + ph.pack + ph.engine_create;
     summary->postprocessor_time_in_seconds = ph.write_back + ph.verify;
 }
+
+// ------------------------------------------------------------------------------------------
+// Covariance (the Ceres <= 2.1 surface): C = (J^T J)^-1 of the undamped problem at the parameter values the blocks hold when
+// Compute is called, not multiplied by a residual variance.  It is computed on the device and nowhere else:
+//   * "gpu-ba": every residual block is the reprojection factor (built-in, or a user cost function recognised as it at the current
+//     point, as Solve recognises it) -> stba_ba_covariance_compute with device Jacobians;
+//   * "gpu-ba-hostjac": BA-shaped with another factor -> the same with the user's cost functions as the host lineariser;
+//   * "gpu-dense": anything else within the dense solve's limits -> stba_dense_covariance.
+// On the BA routes a requested pair must be two camera blocks (rotation / position, of one camera or of two) or one landmark with
+// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: no robust losses (refused
+// as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
+// factorisations (stba.h, stba_ba_covariance_compute) -- not a condition number estimate.  algorithm_type and num_threads are
+// accepted for source compatibility and do not change the computation.
+// (not in Ceres) execution_path() and message(): which route ran, and why Compute returned false.
+enum CovarianceAlgorithmType { DENSE_SVD, SPARSE_QR, SUITE_SPARSE_QR, EIGEN_SPARSE_QR };
+
+class Covariance {
+public:
+    struct Options {
+        CovarianceAlgorithmType algorithm_type = SPARSE_QR;
+        double min_reciprocal_condition_number = 1e-14;
+        int null_space_rank = 0;
+        int num_threads = 1;
+        bool apply_loss_function = true;
+    };
+    explicit Covariance(const Options& options) : options_(options) {}
+
+    bool Compute(const std::vector<std::pair<const double*, const double*>>& covariance_blocks, Problem* problem) {
+        blocks_.clear(); tangent_.clear(); path_.clear(); message_.clear();
+        const bool ok = ComputeImpl(covariance_blocks, problem);
+        if (!ok) std::fprintf(stderr, "stba_ceres::Covariance: %s\n", message_.c_str());
+        return ok;
+    }
+    // Ja C Jb^T in the ambient space of the two blocks (J: LocalParameterization::ComputeJacobian at Compute's point; the identity
+    // for a block without one), row-major size(a) x size(b)
+    bool GetCovarianceBlock(const double* a, const double* b, double* cov) const {
+        const auto ia = blocks_.find(a), ib = blocks_.find(b);
+        const auto it = tangent_.find({a, b});
+        if (ia == blocks_.end() || ib == blocks_.end() || it == tangent_.end()) return false;
+        const Info &A = ia->second, &B = ib->second;
+        std::vector<double> t((size_t)A.size * B.local, 0.0);            // Ja C
+        for (int r = 0; r < A.size; ++r)
+            for (int c = 0; c < B.local; ++c) {
+                double s = 0.0;
+                for (int k = 0; k < A.local; ++k) s += A.jac[(size_t)r * A.local + k] * it->second[(size_t)k * B.local + c];
+                t[(size_t)r * B.local + c] = s;
+            }
+        for (int r = 0; r < A.size; ++r)
+            for (int c = 0; c < B.size; ++c) {
+                double s = 0.0;
+                for (int k = 0; k < B.local; ++k) s += t[(size_t)r * B.local + k] * B.jac[(size_t)c * B.local + k];
+                cov[(size_t)r * B.size + c] = s;
+            }
+        return true;
+    }
+    // C itself, row-major local(a) x local(b)
+    bool GetCovarianceBlockInTangentSpace(const double* a, const double* b, double* cov) const {
+        const auto it = tangent_.find({a, b});
+        if (it == tangent_.end()) return false;
+        std::copy(it->second.begin(), it->second.end(), cov);
+        return true;
+    }
+    const std::string& execution_path() const { return path_; }      // "gpu-ba" | "gpu-ba-hostjac" | "gpu-dense" (empty: none ran)
+    const std::string& message() const { return message_; }
+
+private:
+    struct Info { int size = 0, local = 0; std::vector<double> jac; };   // jac: size x local
+    Options options_;
+    std::map<const double*, Info> blocks_;
+    std::map<std::pair<const double*, const double*>, std::vector<double>> tangent_;
+    std::string path_, message_;
+
+    bool Fail(const std::string& m) { message_ = m; blocks_.clear(); tangent_.clear(); return false; }
+    static std::string PairName(size_t k) { return "pair " + std::to_string(k); }
+    // both orders of a computed pair; the block of (b, a) is the transpose
+    void Store(const double* a, const double* b, int la, int lb, std::vector<double> t) {
+        std::vector<double> tt((size_t)la * lb);
+        for (int r = 0; r < la; ++r) for (int c = 0; c < lb; ++c) tt[(size_t)c * la + r] = t[(size_t)r * lb + c];
+        tangent_[{a, b}] = std::move(t);
+        tangent_[{b, a}] = std::move(tt);
+    }
+
+    bool ComputeImpl(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p) {
+        using namespace internal;
+        if (p->NumLossFunctions() > 0)
+            return Fail(std::to_string(p->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are not implemented by this layer -- no covariance computed");
+        if (options_.null_space_rank != 0)
+            return Fail("null_space_rank = " + std::to_string(options_.null_space_rank) + ": this layer has no pseudo-inverse (only 0 is supported)");
+        std::unordered_map<const double*, int> index;
+        for (auto& b : p->blocks()) index[b.ptr] = b.index;
+        for (size_t k = 0; k < pairs.size(); ++k)
+            if (!index.count(pairs[k].first) || !index.count(pairs[k].second)) return Fail(PairName(k) + " names a parameter block that is not in the problem");
+        for (auto& b : p->blocks()) {
+            Info in;
+            in.size = b.size; in.local = b.local_size();
+            in.jac.assign((size_t)in.size * in.local, 0.0);
+            if (b.local) { if (!b.local->ComputeJacobian(b.ptr, in.jac.data())) return Fail("LocalParameterization::ComputeJacobian failed"); }
+            else for (int k = 0; k < in.size; ++k) in.jac[(size_t)k * in.local + k] = 1.0;
+            blocks_[b.ptr] = std::move(in);
+        }
+        BaLayout L;
+        bool ba = DetectBa(*p, &L, true, options_.num_threads);
+        if (ba) for (int rb : L.rot_block) ba = ba && UsesQuaternionRightPlus(p->blocks()[rb].local);
+        bool host = false;
+        if (!ba) {
+            L = BaLayout();
+            host = DetectBa(*p, &L, false);
+            if (host) for (int rb : L.rot_block) host = host && UsesQuaternionRightPlus(p->blocks()[rb].local);
+        }
+        if (ba || host) return ComputeBa(pairs, p, L, index, host);
+        return ComputeDense(pairs, p, index);
+    }
+
+    bool ComputeBa(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p, const internal::BaLayout& L,
+                   const std::unordered_map<const double*, int>& index, bool host) {
+        using namespace internal;
+        const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
+        auto& blk = p->blocks();
+        // block index -> (camera, 0 | 3) or landmark
+        std::vector<int> cam_of(blk.size(), -1), off_of(blk.size(), 0), pt_of(blk.size(), -1);
+        for (int c = 0; c < nc; ++c) { cam_of[L.rot_block[c]] = c; cam_of[L.pos_block[c]] = c; off_of[L.pos_block[c]] = 3; }
+        for (int j = 0; j < np; ++j) pt_of[L.pt_block[j]] = j;
+        std::vector<int> ca, cb, pj;
+        for (size_t k = 0; k < pairs.size(); ++k) {
+            const int a = index.at(pairs[k].first), b = index.at(pairs[k].second);
+            if (cam_of[a] >= 0 && cam_of[b] >= 0) { ca.push_back(cam_of[a]); cb.push_back(cam_of[b]); }
+            else if (pt_of[a] >= 0 && a == b) pj.push_back(pt_of[a]);
+            else return Fail(PairName(k) + " is neither two camera blocks nor one landmark with itself: the bundle-adjustment route has no "
+                             "camera-landmark or landmark-landmark blocks");
+        }
+        path_ = host ? "gpu-ba-hostjac" : "gpu-ba";
+        std::vector<double> cams((size_t)nc * 7), pts((size_t)np * 3);
+        std::vector<unsigned char> cam_fixed((size_t)nc * 6, 0), pt_fixed((size_t)np, 0);
+        for (int c = 0; c < nc; ++c) {
+            const auto& rb = blk[L.rot_block[c]]; const auto& pb = blk[L.pos_block[c]];
+            std::memcpy(&cams[(size_t)c * 7], rb.ptr, 4 * sizeof(double));
+            std::memcpy(&cams[(size_t)c * 7 + 4], pb.ptr, 3 * sizeof(double));
+            for (int k = 0; k < 3; ++k) { cam_fixed[(size_t)c * 6 + k] = rb.constant; cam_fixed[(size_t)c * 6 + 3 + k] = pb.constant; }
+        }
+        for (int j = 0; j < np; ++j) { std::memcpy(&pts[(size_t)j * 3], blk[L.pt_block[j]].ptr, 3 * sizeof(double)); pt_fixed[j] = blk[L.pt_block[j]].constant; }
+        stba_ba* ba = nullptr;
+        if (stba_ba_create(&ba, nc, np, no, cams.data(), pts.data(), L.obs_cam.data(), L.obs_pt.data(), L.feat.data(), cam_fixed.data(),
+                           pt_fixed.data(), nullptr) != STBA_OK)
+            return Fail(std::string("stba_ba_create: ") + stba_last_error());
+        struct Destroy { stba_ba* b; ~Destroy() { stba_ba_destroy(b); } } destroy{ba};
+        BaHostCtx hctx{p, &L, options_.num_threads};
+        if (host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, &hctx) != STBA_OK) return Fail(std::string("stba_ba_set_host_linearizer: ") + stba_last_error());
+        double rc = 0.0;
+        if (stba_ba_covariance_compute(ba, options_.min_reciprocal_condition_number, &rc) != STBA_OK)
+            return Fail(std::string("stba_ba_covariance_compute: ") + stba_last_error());
+        std::vector<double> cblk(ca.size() * 36), pblk(pj.size() * 9);
+        if (stba_ba_camera_covariance(ba, (int)ca.size(), ca.data(), cb.data(), cblk.data()) != STBA_OK ||
+            stba_ba_point_covariance(ba, (int)pj.size(), pj.data(), pblk.data()) != STBA_OK)
+            return Fail(std::string("covariance blocks: ") + stba_last_error());
+        size_t kc = 0, kp = 0;
+        for (auto& pr : pairs) {
+            const int a = index.at(pr.first), b = index.at(pr.second);
+            std::vector<double> t;
+            if (cam_of[a] >= 0 && cam_of[b] >= 0) {
+                const double* s6 = &cblk[kc++ * 36];
+                t.resize(9);
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) t[(size_t)r * 3 + c] = s6[(size_t)(off_of[a] + r) * 6 + off_of[b] + c];
+            } else { const double* s3 = &pblk[kp++ * 9]; t.assign(s3, s3 + 9); }
+            Store(pr.first, pr.second, 3, 3, std::move(t));
+        }
+        return true;
+    }
+
+    bool ComputeDense(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p,
+                      const std::unordered_map<const double*, int>& index) {
+        using namespace internal;
+        DenseCtx c;
+        bool any_bounds = false, any_local = false;
+        DenseLayout(p, c, &any_bounds, &any_local);
+        if (c.n_loc == 0 || c.n_res == 0) return Fail("nothing to compute: no variable parameter block or no residual");
+        if (c.n_loc > 4096 || (double)c.n_loc * c.n_res > 2.7e8)
+            return Fail("generic (callback) problems are limited to 4096 local parameters and 2.7e8 Jacobian entries");
+        path_ = "gpu-dense";
+        std::vector<double> x(c.n_amb), cov((size_t)c.n_loc * c.n_loc);
+        for (size_t v = 0; v < c.var_blocks.size(); ++v) std::memcpy(&x[c.amb_off[v]], p->blocks()[c.var_blocks[v]].ptr, sizeof(double) * p->blocks()[c.var_blocks[v]].size);
+        double rc = 0.0;
+        if (stba_dense_covariance(&DenseResidual, &c, c.n_amb, c.n_loc, c.n_res, x.data(), options_.min_reciprocal_condition_number, cov.data(), &rc) != STBA_OK)
+            return Fail(std::string("stba_dense_covariance: ") + stba_last_error());
+        std::vector<int> var_of(p->blocks().size(), -1);
+        for (size_t v = 0; v < c.var_blocks.size(); ++v) var_of[c.var_blocks[v]] = (int)v;
+        for (auto& pr : pairs) {
+            const int a = index.at(pr.first), b = index.at(pr.second);
+            const int la = p->blocks()[a].local_size(), lb = p->blocks()[b].local_size();
+            std::vector<double> t((size_t)la * lb, 0.0);
+            if (var_of[a] >= 0 && var_of[b] >= 0)
+                for (int r = 0; r < la; ++r)
+                    for (int q = 0; q < lb; ++q) t[(size_t)r * lb + q] = cov[(size_t)(c.loc_off[var_of[a]] + r) * c.n_loc + c.loc_off[var_of[b]] + q];
+            Store(pr.first, pr.second, la, lb, std::move(t));
+        }
+        return true;
+    }
+};
 
 }  // namespace stba_ceres
 #endif

@@ -74,7 +74,9 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_pg_solve", "stba_pg_last_pcg_summary", "stba_pg_time_kernels", "stba_dense_solve", "stba_corners_read", "stba_corners_write", "stba_zhang_init", "stba_two_view_init", "stba_odometry_read", "stba_odometry_write", "stba_trajectory_ate",
            "stba_comm_unique_id", "stba_comm_create", "stba_comm_destroy", "stba_comm_rank", "stba_comm_allreduce_sum",
            "stba_comm_allreduce_hook", "stba_ba_set_comm", "stba_pg_set_comm",
-           "stba_ba_set_features", "stba_get_device", "stba_set_device"]
+           "stba_ba_set_features", "stba_get_device", "stba_set_device",
+           "stba_ba_covariance_compute", "stba_ba_camera_covariance", "stba_ba_point_covariance", "stba_ba_covariance_release",
+           "stba_dense_covariance"]
 
 
 def lib():
@@ -293,6 +295,29 @@ class BAEngine:
         cb = ITER_CB(callback) if callback else C.cast(None, ITER_CB)
         _chk(lib().stba_ba_solve(self._h, C.byref(opt), C.byref(summ), _p(trace), cb, None), "stba_ba_solve")
         return summ, trace[: summ.num_iterations + 1]
+
+    def covariance(self, cam_pairs=None, points=None, min_rcond=1e-14):
+        """covariance of the undamped problem at the current parameters (stba_ba_covariance_compute): returns
+        (cam_blocks [k,6,6], point_blocks [m,3,3], rcond).  cam_pairs: (a, b) pairs, default every camera's diagonal block;
+        points: landmark indices, default all.  Tangent coordinates [rot(3), pos(3)] per camera, 3 per landmark."""
+        L = lib()
+        rc = C.c_double()
+        _chk(L.stba_ba_covariance_compute(self._h, C.c_double(min_rcond), C.byref(rc)), "stba_ba_covariance_compute")
+        if cam_pairs is None:
+            ca = cb = np.arange(self.nc, dtype=np.int32)
+        else:
+            pr = np.asarray(cam_pairs, dtype=np.int32).reshape(-1, 2)
+            ca, cb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        cam = np.zeros((len(ca), 6, 6))
+        _chk(L.stba_ba_camera_covariance(self._h, len(ca), _p(ca), _p(cb), _p(cam)), "stba_ba_camera_covariance")
+        pts = None if points is None else np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        m = self.np_ if pts is None else len(pts)
+        pb = np.zeros((m, 3, 3))
+        _chk(L.stba_ba_point_covariance(self._h, m, _p(pts), _p(pb)), "stba_ba_point_covariance")
+        return cam, pb, rc.value
+
+    def covariance_release(self):
+        _chk(lib().stba_ba_covariance_release(self._h), "stba_ba_covariance_release")
 
     def lm_iterations(self, iterations, opt=None, **kw):
         opt = opt or default_options(**kw)

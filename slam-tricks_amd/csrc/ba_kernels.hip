@@ -284,48 +284,6 @@ int launch_trial_finish(const double* cost_partial, int n_cost, const double* pa
     return STBA_OK;
 }
 
-// compact Jacobian of observation i -> the 2x6 camera block (d/dtheta | d/dt) and the 2x3 landmark block; columns of
-// constant dofs (mask bits 0..5) and of constant landmarks (bit 6) are zero, as the stored form used to have them
-// GEN (host-linearised factors, stba_ba_set_host_linearizer): the landmark block is still the record's P (so the landmark kernels
-// need no second form), the camera block is NOT a function of it and comes from its own array Jc12 [n_obs][12] (2 x 6 row-major).
-template <bool GEN = false>
-__device__ inline void load_jc_jp(const double* __restrict__ J8, const unsigned char* __restrict__ omask, int i,
-                                  double jc[12], double jp[6], const double* __restrict__ Jc12 = nullptr) {
-    const double2* pj = reinterpret_cast<const double2*>(J8 + (size_t)i * 8);
-    const double2 v0 = pj[0], v1 = pj[1], v2 = pj[2], v3 = pj[3];
-    const unsigned m = omask ? omask[i] : 0u;
-    if constexpr (GEN) {
-        const double2* pc = reinterpret_cast<const double2*>(Jc12 + (size_t)i * 12);
-        const double P[6] = {v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-        const bool pf = (m & 64u) != 0u;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const double2 v = pc[k];
-            jc[2 * k] = ((m >> ((2 * k) % 6)) & 1u) ? 0.0 : v.x;
-            jc[2 * k + 1] = ((m >> ((2 * k + 1) % 6)) & 1u) ? 0.0 : v.y;
-            jp[k] = pf ? 0.0 : P[k];
-        }
-        return;
-    }
-    const double xn = v0.x, yn = v0.y;
-    const double P[6] = {v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-    jc[0] = (m & 1u) ? 0.0 : xn * yn;
-    jc[1] = (m & 2u) ? 0.0 : -(1.0 + xn * xn);
-    jc[2] = (m & 4u) ? 0.0 : yn;
-    jc[6] = (m & 1u) ? 0.0 : 1.0 + yn * yn;
-    jc[7] = (m & 2u) ? 0.0 : -xn * yn;
-    jc[8] = (m & 4u) ? 0.0 : -xn;
-    const bool pf = (m & 64u) != 0u;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const bool fx = (m >> (3 + k)) & 1u;
-        jc[3 + k] = fx ? 0.0 : -P[k];
-        jc[9 + k] = fx ? 0.0 : -P[3 + k];
-        jp[k] = pf ? 0.0 : P[k];
-        jp[3 + k] = pf ? 0.0 : P[3 + k];
-    }
-}
-
 // stage entry points (stba_ba_evaluate) hand out the expanded form
 __global__ __launch_bounds__(256) void ba_expand_jacobian_kernel(int n_obs, const double* __restrict__ J8,
                                                                  const unsigned char* __restrict__ omask,

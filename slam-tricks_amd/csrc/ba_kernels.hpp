@@ -22,6 +22,48 @@ struct LinArgs {
     double* cost_partial;            // [grid]
 };
 
+// compact Jacobian of observation i -> the 2x6 camera block (d/dtheta | d/dt) and the 2x3 landmark block; columns of
+// constant dofs (mask bits 0..5) and of constant landmarks (bit 6) are zero, as the stored form used to have them
+// GEN (host-linearised factors, stba_ba_set_host_linearizer): the landmark block is still the record's P (so the landmark kernels
+// need no second form), the camera block is NOT a function of it and comes from its own array Jc12 [n_obs][12] (2 x 6 row-major).
+template <bool GEN = false>
+__device__ inline void load_jc_jp(const double* __restrict__ J8, const unsigned char* __restrict__ omask, int i,
+                                  double jc[12], double jp[6], const double* __restrict__ Jc12 = nullptr) {
+    const double2* pj = reinterpret_cast<const double2*>(J8 + (size_t)i * 8);
+    const double2 v0 = pj[0], v1 = pj[1], v2 = pj[2], v3 = pj[3];
+    const unsigned m = omask ? omask[i] : 0u;
+    if constexpr (GEN) {
+        const double2* pc = reinterpret_cast<const double2*>(Jc12 + (size_t)i * 12);
+        const double P[6] = {v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
+        const bool pf = (m & 64u) != 0u;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double2 v = pc[k];
+            jc[2 * k] = ((m >> ((2 * k) % 6)) & 1u) ? 0.0 : v.x;
+            jc[2 * k + 1] = ((m >> ((2 * k + 1) % 6)) & 1u) ? 0.0 : v.y;
+            jp[k] = pf ? 0.0 : P[k];
+        }
+        return;
+    }
+    const double xn = v0.x, yn = v0.y;
+    const double P[6] = {v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
+    jc[0] = (m & 1u) ? 0.0 : xn * yn;
+    jc[1] = (m & 2u) ? 0.0 : -(1.0 + xn * xn);
+    jc[2] = (m & 4u) ? 0.0 : yn;
+    jc[6] = (m & 1u) ? 0.0 : 1.0 + yn * yn;
+    jc[7] = (m & 2u) ? 0.0 : -xn * yn;
+    jc[8] = (m & 4u) ? 0.0 : -xn;
+    const bool pf = (m & 64u) != 0u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const bool fx = (m >> (3 + k)) & 1u;
+        jc[3 + k] = fx ? 0.0 : -P[k];
+        jc[9 + k] = fx ? 0.0 : -P[3 + k];
+        jp[k] = pf ? 0.0 : P[k];
+        jp[3 + k] = pf ? 0.0 : P[3 + k];
+    }
+}
+
 size_t lin_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac);
 int launch_linearize(const LinArgs& a, bool with_jac, int grid, hipStream_t st);
 int launch_sum_partials(const double* partial, int n, int stride, int K, double* out, hipStream_t st);
@@ -137,6 +179,27 @@ int launch_calib_arrow_iteration(int n_views, int n_corners, double* params, con
                                  double* scratch, int* state, double* sse_trace, hipStream_t st);
 int launch_dense_normal(int n_res, int n, const double* J, const double* r, double* H, int ldh, double* g,
                         hipStream_t st);
+
+// ---- covariance (covariance.hip): Sigma_cc = S^-1 and the landmark marginals of a bundle adjustment at its current point
+struct BaCovInputs {
+    int nc, np, no, n, lda;
+    hipStream_t st;
+    const int* pt_start; const int* obs_cam;          // the engine's landmark-major observation order
+    const double* J8; const double* Jc12;             // Jc12: host-linearised factors only (else null)
+    const unsigned char* omask; const unsigned char* cam_fixed; const unsigned char* pt_fixed;
+    const double* Hpp6; const double* Hinv6;          // undamped landmark blocks and their inverses
+    const double* S;                                  // undamped reduced camera system (lower triangle), leading dimension lda
+};
+struct CovStore;
+void cov_store_free(CovStore* c);
+int cov_compute(const BaCovInputs& in, double min_rcond, CovStore** out, double* rcond_out);
+int cov_camera_blocks(const CovStore* c, int n_pairs, const int* cam_a, const int* cam_b, double* out);
+int cov_point_blocks(const CovStore* c, int n, const int* pts, double* out);
+// inverse of the SPD matrix whose lower triangle is A (n x n, leading dimension lda, device) -> packed lower triangle sig (device,
+// row i at i (i + 1) / 2); *rcond = smallest / largest Cholesky pivot over the rows that are not constant dofs (cam_fixed: bit a of
+// byte i / 6 marks row i; may be null); *pivot_row = 0, or row + 1 of the first pivot that is not positive
+int cov_spd_inverse_packed(const double* A, int lda, int n, const unsigned char* cam_fixed, double* sig, double* rcond, int* pivot_row,
+                           hipStream_t st);
 
 // ---- small dense problems (small_dense.hip): one kernel launch per LM step, pooled workspace, mapped host buffers
 constexpr int SMALL_DENSE_MAX_N = 32;

@@ -135,6 +135,7 @@ struct stba_ba {
     bool ar_timing_pending = false, ar_timing_on = false;
     double ar_ms = 0.0, ar_bytes = 0.0; int ar_calls = 0;   // accumulated over one LM run
     hipEvent_t ev[15] = {};     // [12]: the trial block has reached the host; [13], [14]: second pair for the speculative linearisation
+    CovStore* cov = nullptr;    // the last stba_ba_covariance_compute (covariance.hip), until the next one, a release or destroy
 
     double* S() const { return Sbuf; }
     double* ex_diag() const { return Sbuf + (size_t)lda * lda; }
@@ -160,6 +161,7 @@ namespace stba {
 
 static void ba_free(stba_ba* b) {
     b->create_leftovers.reset();                        // (what stba_ba_create's plan left on the host)
+    cov_store_free(b->cov);
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
     F(b->pt_start); F(b->cam_perm); F(b->chunk_begin); F(b->chunk_end); F(b->cam_chunk_start); F(b->cam_fixed);
@@ -524,6 +526,27 @@ static int ba_read_linear_scalars(stba_ba* b, double* cost, double* gmax) {
     for (int k = 0; k < b->world; ++k) m = std::max(m, h[SC_GPMAX0 + k]);
     for (double v : g) m = std::max(m, std::fabs(v));
     *gmax = m;
+    return STBA_OK;
+}
+
+// covariance (covariance.hip): linearisation, landmark blocks and the UNDAMPED reduced system at the current parameters, through the
+// explicit-damping path of stba_ba_reduced_system with dc = dp = 0 (constant dofs get their 1 on the diagonal as always).  The LM
+// state stays as it was: parameters and their buffers, the Jacobi scale (ba_build_reduced marks it made; this path made none) and
+// the speculation's stamped block; every solve starts with a linearisation of its own.
+static int ba_cov_build(stba_ba* b) {
+    const bool scale_init = b->scale_init;
+    STBA_TRY(ba_linearize(b, b->cur, b->trial + TS_COST2));
+    STBA_TRY(ba_normal_blocks(b));
+    STBA_HIP(hipMemsetAsync(b->dc, 0, (size_t)b->n * sizeof(double), b->st));
+    STBA_HIP(hipMemsetAsync(b->dp, 0, (size_t)b->np * 3 * sizeof(double), b->st));
+    STBA_HIP(hipMemsetAsync(b->ex_scalar(), 0, (size_t)b->lda * sizeof(double), b->st));
+    Damping dm;
+    dm.explicit_d = true;
+    const int rc = ba_build_reduced(b, dm);
+    b->scale_init = scale_init;
+    STBA_TRY(rc);
+    b->have_lin = b->have_blocks = true;
+    b->have_reduced = b->have_dxc = b->have_dxp = false;
     return STBA_OK;
 }
 
@@ -1722,6 +1745,39 @@ int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics
     return STBA_OK;
 }
 
+int stba_ba_covariance_compute(stba_ba* b, double min_rcond, double* rcond_out) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (b->ar) return fail(STBA_ERR_STATE, "stba_ba_covariance_compute: the engine holds one landmark shard of several ranks; covariance needs one rank");
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    STBA_TRY(ba_cov_build(b));
+    BaCovInputs in;
+    in.nc = b->nc; in.np = b->np; in.no = b->no; in.n = b->n; in.lda = b->lda; in.st = b->st;
+    in.pt_start = b->pt_start; in.obs_cam = b->obs_cam; in.J8 = b->J8; in.Jc12 = b->hl_fn ? b->Jc12 : nullptr;
+    in.omask = b->omask; in.cam_fixed = b->cam_fixed; in.pt_fixed = b->pt_fixed;
+    in.Hpp6 = b->Hpp6; in.Hinv6 = b->Hinv6; in.S = b->S();
+    return cov_compute(in, min_rcond, &b->cov, rcond_out);
+}
+
+int stba_ba_camera_covariance(stba_ba* b, int n_pairs, const int* cam_a, const int* cam_b, double* out) {
+    if (!b || n_pairs < 0 || (n_pairs > 0 && (!cam_a || !cam_b || !out))) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_covariance: bad argument");
+    if (!b->cov) return fail(STBA_ERR_STATE, "stba_ba_camera_covariance needs stba_ba_covariance_compute first");
+    return cov_camera_blocks(b->cov, n_pairs, cam_a, cam_b, out);
+}
+
+int stba_ba_point_covariance(stba_ba* b, int n, const int* pts, double* out) {
+    if (!b || n < 0 || (n > 0 && !out)) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_point_covariance: bad argument");
+    if (!b->cov) return fail(STBA_ERR_STATE, "stba_ba_point_covariance needs stba_ba_covariance_compute first");
+    return cov_point_blocks(b->cov, n, pts, out);
+}
+
+int stba_ba_covariance_release(stba_ba* b) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    return STBA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // dense SPD solver entry points
 // ---------------------------------------------------------------------------------------------
@@ -2246,6 +2302,46 @@ int stba_dense_solve(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_p
     GeneralDenseSteps S(opt, n_res, n);
     STBA_TRY(S.init());
     return dense_lm(S, fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
+}
+
+// (J^T J)^-1 at x: one evaluation of the callback, J^T J formed on the device by GeneralDenseSteps::linearize -- the normal
+// equations of the general dense solve -- and inverted by covariance.hip's cov_spd_inverse_packed
+int stba_dense_covariance(stba_residual_fn fn, void* user, int n_params, int n_local, int n_res, const double* x, double min_rcond,
+                          double* cov, double* rcond_out) {
+    if (!fn || !x || !cov || n_params <= 0 || n_local <= 0 || n_res <= 0)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_covariance: bad argument");
+    if (n_local > 4096 || (double)n_local * n_res > 2.7e8)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_covariance: limited to 4096 local parameters and 2.7e8 Jacobian entries");
+    STBA_TRY(require_device());
+    stba_lm_options opt;
+    default_options(&opt);
+    const int n = n_local;
+    GeneralDenseSteps S(opt, n_res, n);
+    STBA_TRY(S.init());
+    std::vector<double> xv(x, x + n_params);
+    if (fn(user, xv.data(), S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
+    for (int i = 0; i < n_res; ++i)
+        if (!std::isfinite(S.r[i])) return fail(STBA_ERR_CALLBACK, "stba_dense_covariance: non-finite residual");
+    STBA_TRY(S.linearize(0.0));
+    double* sig = nullptr;
+    STBA_TRY(dev_alloc(&sig, (size_t)n * (n + 1) / 2));
+    struct Guard { double*& p; ~Guard() { if (p) (void)hipFree(p); } } guard{sig};
+    double rc = 0.0;
+    int piv = 0;
+    STBA_TRY(cov_spd_inverse_packed(S.dH, n, n, nullptr, sig, &rc, &piv, S.w.st));
+    if (rcond_out) *rcond_out = rc;
+    if (piv) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "stba_dense_covariance: J^T J is not positive definite (pivot of row " + std::to_string(piv - 1) + ")");
+    if (!(rc >= min_rcond)) {
+        char buf[64];
+        snprintf(buf, sizeof buf, "%.3e", rc);
+        return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string("stba_dense_covariance: J^T J has a pivot ratio of ") + buf + ", below min_reciprocal_condition_number");
+    }
+    std::vector<double> packed((size_t)n * (n + 1) / 2);
+    STBA_TRY(download(packed.data(), sig, packed.size(), S.w.st));
+    STBA_HIP(hipStreamSynchronize(S.w.st));
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) cov[(size_t)i * n + j] = cov[(size_t)j * n + i] = packed[(size_t)i * (i + 1) / 2 + j];
+    return STBA_OK;
 }
 
 }  // extern "C"
