@@ -470,6 +470,43 @@ int stba_pg_solve(stba_pg* pg, const stba_lm_options* opt, const stba_pcg_option
 /* the linear-solver side of the last stba_pg_solve of this engine */
 int stba_pg_last_pcg_summary(stba_pg* pg, stba_pcg_summary* out);
 
+/* ================================ bundle adjustment: ITERATIVE_SCHUR ================================ */
+/* Ceres' linear_solver_type = ITERATIVE_SCHUR: conjugate gradients on the reduced camera system S = (Hcc + D) - W V^-1 W^T, applied
+ * implicitly (two passes over the observations per product), so that neither S (8 (6 n_cams)^2 bytes) nor a Schur plan is ever
+ * made: the camera count is limited by the observations, not by S.  Same LM loop, damping, Jacobi scaling and constant dofs as the
+ * dense path; the step is inexact, its model change is -(J d)^T (r + J d / 2).  DESIGN.md 7b.
+ * stba_ba_create_options versions itself by struct_size: set it to sizeof(stba_ba_create_options); fields behind struct_size are
+ * taken as their defaults.  opt = NULL or STBA_LINEAR_DENSE_SCHUR: exactly stba_ba_create.
+ * An ITERATIVE_SCHUR engine refuses, with STBA_ERR_INVALID_ARGUMENT and its state untouched: stba_ba_reduced_system,
+ * stba_ba_solve_reduced, stba_ba_set_schur_mode, stba_ba_time_schur, stba_ba_covariance_compute (it needs the explicit S) and
+ * stba_ba_set_allreduce / stba_ba_set_comm (one rank only). */
+enum { STBA_LINEAR_DENSE_SCHUR = 0, STBA_LINEAR_ITERATIVE_SCHUR = 1 };
+typedef struct {
+    size_t struct_size;          /* sizeof(stba_ba_create_options) */
+    int    linear_solver;        /* STBA_LINEAR_DENSE_SCHUR (default) | STBA_LINEAR_ITERATIVE_SCHUR */
+} stba_ba_create_options;
+int stba_ba_create_ex(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts, const int* obs_cam,
+                      const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed, const unsigned char* pt_fixed,
+                      void* hip_stream, const stba_ba_create_options* opt);
+/* preconditioners, one 6x6 inverse per camera and LM iteration: IDENTITY (the identity in Jacobi-scaled coordinates), JACOBI (blocks
+ * of Hcc + D, Ceres' ImplicitSchurComplement block_diagonal_FtF_inverse), SCHUR_JACOBI (blocks of S) */
+enum { STBA_PRECOND_IDENTITY = 0, STBA_PRECOND_JACOBI = 1, STBA_PRECOND_SCHUR_JACOBI = 2 };
+/* Ceres' defaults: JACOBI, eta 0.1 (q_tolerance, Nash & Sofer's test i (Q_i - Q_{i-1}) / Q_i <= eta), min 0, max 500 iterations;
+ * check_every (4): iterations enqueued between the host's looks at the device-side stop flag.  Dense engines: invalid argument. */
+int stba_ba_set_pcg(stba_ba* ba, int preconditioner, double eta, int min_iterations, int max_iterations, int check_every);
+/* iterations_total, solves, hit_cap, max_iterations_in_a_solve, last_eta and (with phase_timing) linear_solve_ms of the last LM solve */
+int stba_ba_last_pcg_summary(stba_ba* ba, stba_pcg_summary* out);
+/* per_iteration[k]: PCG iterations of LM iteration k + 1 of the last solve, for k < n (0 behind its last iteration, and on a dense
+ * engine) -- Ceres' IterationSummary::linear_solver_iterations */
+int stba_ba_last_pcg_iterations(stba_ba* ba, int* per_iteration, int n);
+/* test and diagnostic hook (needs stba_ba_normal_blocks): with explicit diagonals dc[n], dp[n_pts*3] as stba_ba_reduced_system takes
+ * them, y[n] = S x (which = 0), the JACOBI (1) or SCHUR_JACOBI (2) preconditioner inverse applied to x, or the reduced right-hand
+ * side -(gc - W V^-1 gp) when x == NULL.  Entries of constant dofs are zero in and out. */
+int stba_ba_schur_apply(stba_ba* ba, const double* dc, const double* dp, int which, const double* x, double* y);
+/* measurement: average device time (ms, hipEvents on the engine's stream) of one product S x -- the landmark and the camera pass --
+ * over `reps` back-to-back products, with the blocks and the x of the last stba_ba_schur_apply */
+int stba_ba_time_schur_apply(stba_ba* ba, int reps, double* ms_avg);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

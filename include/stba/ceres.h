@@ -109,6 +109,11 @@ using std::sqrt; using std::sin; using std::cos; using std::atan2; using std::ab
 // ------------------------------------------------------------------------------------------
 enum LinearSolverType { DENSE_NORMAL_CHOLESKY, DENSE_QR, SPARSE_NORMAL_CHOLESKY, DENSE_SCHUR, SPARSE_SCHUR,
                         ITERATIVE_SCHUR, CGNR };
+// ITERATIVE_SCHUR on the "gpu-ba" / "gpu-ba-hostjac" paths: conjugate gradients on the implicitly applied reduced camera system
+// (stba_ba_create_ex) with IDENTITY, JACOBI or SCHUR_JACOBI; the other preconditioners are refused (FAILURE, the reason
+// in Summary::message and on stderr, parameters untouched).  Every other linear_solver_type, and every problem that is not BA-shaped,
+// takes the paths it always took.
+enum PreconditionerType { IDENTITY, JACOBI, SCHUR_JACOBI, CLUSTER_JACOBI, CLUSTER_TRIDIAGONAL, SUBSET };
 enum CallbackReturnType { SOLVER_CONTINUE, SOLVER_ABORT, SOLVER_TERMINATE_SUCCESSFULLY };
 enum TerminationType { CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_FAILURE };
 enum Ownership { DO_NOT_TAKE_OWNERSHIP, TAKE_OWNERSHIP };
@@ -121,6 +126,7 @@ class LossFunction { public: virtual ~LossFunction() = default; };
 
 struct IterationSummary {
     int iteration = 0;
+    int linear_solver_iterations = 0;     // PCG iterations of this iteration's step (ITERATIVE_SCHUR; 0 on every other path)
     bool step_is_valid = false, step_is_successful = false;
     double cost = 0, cost_change = 0, gradient_max_norm = 0, step_norm = 0, relative_decrease = 0,
            trust_region_radius = 0;
@@ -641,6 +647,9 @@ public:
         int max_num_iterations = 50;
         int num_threads = 1;
         LinearSolverType linear_solver_type = SPARSE_NORMAL_CHOLESKY;
+        PreconditionerType preconditioner_type = JACOBI;          // Ceres' defaults for the iterative linear solver
+        double eta = 1e-1;
+        int min_linear_solver_iterations = 0, max_linear_solver_iterations = 500;
         bool minimizer_progress_to_stdout = false;
         bool update_state_every_iteration = false;
         std::vector<IterationCallback*> callbacks;
@@ -662,6 +671,8 @@ public:
         // recognised user block at the end point; resolve = a second solve with the user's own code, if the verification failed
         struct Phases { double recognise = 0, pack = 0, engine_create = 0, device_solve = 0, write_back = 0, verify = 0, resolve = 0; } phases;
         int num_successful_steps = 0, num_unsuccessful_steps = 0;
+        // ITERATIVE_SCHUR on a BA path; 0 (DENSE_NORMAL_CHOLESKY's value) on every other path, which this field does not describe
+        LinearSolverType linear_solver_type_used = static_cast<LinearSolverType>(0);
         std::vector<IterationSummary> iterations;
         std::string execution_path;   // "gpu-ba" | "gpu-ba-hostjac" | "gpu-pg" | "gpu-dense-callback"
         std::string BriefReport() const {
@@ -1035,6 +1046,15 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     double t0 = WallSeconds();
     auto lap = [&](double* acc) { const double t1 = WallSeconds(); *acc += t1 - t0; t0 = t1; };
     const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
+    const bool iterative = o.linear_solver_type == ITERATIVE_SCHUR;
+    if (iterative && o.preconditioner_type != IDENTITY && o.preconditioner_type != JACOBI && o.preconditioner_type != SCHUR_JACOBI) {
+        // (refused like a LossFunction: before any device work, parameters untouched)
+        sum->termination_type = FAILURE;
+        sum->message = "stba_ceres: ITERATIVE_SCHUR with the CLUSTER_JACOBI, CLUSTER_TRIDIAGONAL or SUBSET preconditioner is not implemented by "
+                       "this layer (IDENTITY, JACOBI and SCHUR_JACOBI are) -- nothing was solved.";
+        std::fprintf(stderr, "%s\n", sum->message.c_str());
+        return false;
+    }
     BaSync sync{nullptr, p, &L, std::vector<double>((size_t)nc * 7), std::vector<double>((size_t)np * 3)};
     std::vector<unsigned char> cam_fixed((size_t)nc * 6, 0), pt_fixed((size_t)np, 0);
     for (int c = 0; c < nc; ++c) {
@@ -1052,8 +1072,20 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     int rc = STBA_OK;
     std::string create_error;
     auto create = [&]() {
-        rc = stba_ba_create(&sync.ba, nc, np, no, sync.cams.data(), sync.pts.data(), L.obs_cam.data(), L.obs_pt.data(),
-                            L.feat.data(), cam_fixed.data(), pt_fixed.data(), nullptr);
+        if (!iterative)
+            rc = stba_ba_create(&sync.ba, nc, np, no, sync.cams.data(), sync.pts.data(), L.obs_cam.data(), L.obs_pt.data(),
+                                L.feat.data(), cam_fixed.data(), pt_fixed.data(), nullptr);
+        else {
+            stba_ba_create_options co;
+            co.struct_size = sizeof co;
+            co.linear_solver = STBA_LINEAR_ITERATIVE_SCHUR;
+            rc = stba_ba_create_ex(&sync.ba, nc, np, no, sync.cams.data(), sync.pts.data(), L.obs_cam.data(), L.obs_pt.data(),
+                                   L.feat.data(), cam_fixed.data(), pt_fixed.data(), nullptr, &co);
+            const int pc = o.preconditioner_type == IDENTITY ? STBA_PRECOND_IDENTITY : o.preconditioner_type == JACOBI ? STBA_PRECOND_JACOBI
+                                                                                                                       : STBA_PRECOND_SCHUR_JACOBI;
+            if (rc == STBA_OK && (rc = stba_ba_set_pcg(sync.ba, pc, o.eta, o.min_linear_solver_iterations, o.max_linear_solver_iterations, 4)) != STBA_OK)
+                { create_error = stba_last_error(); stba_ba_destroy(sync.ba); sync.ba = nullptr; return; }
+        }
         if (rc != STBA_OK) create_error = stba_last_error();      // (the error text is thread-local: taken where it was set)
     };
     int device = 0;
@@ -1097,6 +1129,12 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     if (rc == STBA_OK) {
         BaCopyOut(&sync);   // parameters are updated in place, like ceres::Solve
         FillSummary(cs, trace, sum);
+        if (iterative) {
+            sum->linear_solver_type_used = ITERATIVE_SCHUR;
+            std::vector<int> its((size_t)cs.num_iterations, 0);
+            if (cs.num_iterations > 0 && stba_ba_last_pcg_iterations(sync.ba, its.data(), cs.num_iterations) == STBA_OK)
+                for (int i = 1; i <= cs.num_iterations && i < (int)sum->iterations.size(); ++i) sum->iterations[(size_t)i].linear_solver_iterations = its[(size_t)i - 1];
+        }
         if (ctx.user_abort) sum->termination_type = USER_FAILURE;
         if (ctx.user_success) sum->termination_type = USER_SUCCESS;
     } else {

@@ -76,7 +76,9 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_comm_allreduce_hook", "stba_ba_set_comm", "stba_pg_set_comm",
            "stba_ba_set_features", "stba_get_device", "stba_set_device",
            "stba_ba_covariance_compute", "stba_ba_camera_covariance", "stba_ba_point_covariance", "stba_ba_covariance_release",
-           "stba_dense_covariance"]
+           "stba_dense_covariance",
+           "stba_ba_create_ex", "stba_ba_set_pcg", "stba_ba_last_pcg_summary", "stba_ba_schur_apply",
+           "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply"]
 
 
 def lib():
@@ -163,10 +165,21 @@ class Comm:
             pass
 
 
-class BAEngine:
-    """Device-resident bundle-adjustment problem (one landmark shard per engine)."""
+class BACreateOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("linear_solver", C.c_int)]
 
-    def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None):
+
+LINEAR_SOLVERS = {"dense_schur": 0, "iterative_schur": 1}
+PRECONDITIONERS = {"identity": 0, "jacobi": 1, "schur_jacobi": 2}
+
+
+class BAEngine:
+    """Device-resident bundle-adjustment problem (one landmark shard per engine).
+
+    linear_solver: "dense_schur" (the reduced camera system formed and factored: stba_ba_create) or "iterative_schur" (PCG on the
+    implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
+
+    def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur"):
         self._h = C.c_void_p()
         cams = _f64(cams).reshape(-1, 7)
         pts = _f64(pts).reshape(-1, 3)
@@ -177,8 +190,16 @@ class BAEngine:
         pf = None if pt_fixed is None else np.ascontiguousarray(pt_fixed, dtype=np.uint8)
         self.nc, self.np_, self.no = len(cams), len(pts), len(oc)
         self._keep = []
-        _chk(lib().stba_ba_create(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
-                                  _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0)), "stba_ba_create")
+        if linear_solver not in LINEAR_SOLVERS:
+            raise ValueError(f"linear_solver must be one of {sorted(LINEAR_SOLVERS)}")
+        self.linear_solver = linear_solver
+        if linear_solver == "dense_schur":
+            _chk(lib().stba_ba_create(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
+                                      _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0)), "stba_ba_create")
+        else:
+            o = BACreateOptions(C.sizeof(BACreateOptions), LINEAR_SOLVERS[linear_solver])
+            _chk(lib().stba_ba_create_ex(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
+                                         _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0), C.byref(o)), "stba_ba_create_ex")
 
     def close(self):
         if self._h:
@@ -346,6 +367,38 @@ class BAEngine:
         m = C.c_int()
         _chk(lib().stba_ba_schur_mode(self._h, C.byref(m)), "stba_ba_schur_mode")
         return m.value
+
+    # ---- iterative Schur
+    def set_pcg(self, preconditioner="jacobi", eta=0.1, min_iterations=0, max_iterations=500, check_every=4):
+        """PCG of an "iterative_schur" engine (Ceres' defaults): preconditioner identity | jacobi | schur_jacobi, eta = q_tolerance"""
+        pc = PRECONDITIONERS[preconditioner] if isinstance(preconditioner, str) else int(preconditioner)
+        _chk(lib().stba_ba_set_pcg(self._h, pc, C.c_double(eta), int(min_iterations), int(max_iterations), int(check_every)),
+             "stba_ba_set_pcg")
+
+    def pcg_summary(self):
+        s = PCGSummary()
+        _chk(lib().stba_ba_last_pcg_summary(self._h, C.byref(s)), "stba_ba_last_pcg_summary")
+        return s
+
+    def pcg_iterations(self, n):
+        """PCG iterations of LM iterations 1 .. n of the last solve (stba_ba_last_pcg_iterations)"""
+        out = np.zeros(int(n), dtype=np.int32)
+        _chk(lib().stba_ba_last_pcg_iterations(self._h, _p(out), int(n)), "stba_ba_last_pcg_iterations")
+        return out
+
+    def time_schur_apply(self, reps=20):
+        """ms per implicit product S x on the device (hipEvents), with the blocks and x of the last schur_apply"""
+        ms = C.c_double()
+        _chk(lib().stba_ba_time_schur_apply(self._h, int(reps), C.byref(ms)), "stba_ba_time_schur_apply")
+        return ms.value
+
+    def schur_apply(self, dc, dp, which=0, x=None):
+        """S x (which 0), a preconditioner inverse applied to x (1 jacobi, 2 schur_jacobi), or the reduced rhs (x None), for the
+        explicit diagonals dc [6 n_cams], dp [n_pts, 3]; needs normal_blocks() first"""
+        y = np.zeros(6 * self.nc)
+        _chk(lib().stba_ba_schur_apply(self._h, _p(_f64(dc)), _p(_f64(dp)), int(which), _p(None if x is None else _f64(x)), _p(y)),
+             "stba_ba_schur_apply")
+        return y
 
     def time_schur(self, reps=10):
         """(ms per launch of the Schur-complement kernel, LDS atomics per launch, observation pairs per launch)"""

@@ -1298,6 +1298,7 @@ __global__ __launch_bounds__(PB_THREADS) void ba_backsub_kernel(int n_pts, const
     __shared__ int seg[PB_LM + 1];
     __shared__ double vv[3 * PB_LM];
     __shared__ double ssum[PB_THREADS / 64][3];
+    if (up.skip && *up.skip) return;
     const int t = threadIdx.x;
     const int gp_blocks = (n_pts + PB_LM - 1) / PB_LM;
     if ((int)blockIdx.x >= gp_blocks) {
@@ -1305,6 +1306,7 @@ __global__ __launch_bounds__(PB_THREADS) void ba_backsub_kernel(int n_pts, const
         const int cblk = blockIdx.x - gp_blocks, c = cblk * PB_THREADS + t;
         double v[4] = {0.0, 0.0, 0.0, 0.0};
         if (c < up.n_cams) camera_update_lane(c, up.cams, dxc, up.cam_fixed, up.gc, up.dc, up.cams_new, v);
+        if (up.r_model) v[2] = 0.0;          // (inexact step: the whole model change comes from the landmark workgroups' records)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             double x = v[k];
@@ -1325,7 +1327,7 @@ __global__ __launch_bounds__(PB_THREADS) void ba_backsub_kernel(int n_pts, const
     const int rb = seg[0], re = seg[nl];
     const int lj = t / 3, lk = t % 3;
     const bool mine = (t < 3 * PB_LM) && (lj < nl);
-    double acc = mine ? -gp[(size_t)j0 * 3 + t] : 0.0;
+    double acc = (mine && gp) ? -gp[(size_t)j0 * 3 + t] : 0.0;      // (gp null: the landmark pass of an implicit Schur product)
     for (int cb = rb; cb < re; cb += PB_CHUNK) {
         const int ce = min(cb + PB_CHUNK, re);
 #pragma unroll
@@ -1369,6 +1371,26 @@ __global__ __launch_bounds__(PB_THREADS) void ba_backsub_kernel(int n_pts, const
                 st[2] = -0.5 * gp[(size_t)j0 * 3 + t] * dd + 0.5 * up.dp[(size_t)j0 * 3 + t] * dd * dd;
             }
         }
+    }
+    if (up.r_model) {
+        // inexact step: m = -sum over the workgroup's records of (J d)^T (r + J d / 2), J d = Jc dxc[cam] + Jp dxp[landmark]
+        __shared__ double dsh[3 * PB_LM];
+        if (t < 3 * PB_LM) dsh[t] = (mine && !(up.pt_fixed && up.pt_fixed[j0 + lj] != 0)) ? dxp[(size_t)j0 * 3 + t] : 0.0;
+        __syncthreads();
+        double mv = 0.0;
+        for (int l = rb + t; l < re; l += PB_THREADS) {
+            const int c = obs_cam[l], jl = up.obs_pt[l] - j0;
+            double jc[12], jp[6];
+            load_jc_jp<GEN>(Jc, Jp, l, jc, jp, Jc12);
+            double u0 = 0.0, u1 = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) { const double d = dxc[c * 6 + a]; u0 += jc[a] * d; u1 += jc[6 + a] * d; }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { const double d = dsh[3 * jl + k]; u0 += jp[k] * d; u1 += jp[3 + k] * d; }
+            const double2 rl = up.r_model[l];
+            mv -= rl.x * u0 + rl.y * u1 + 0.5 * (u0 * u0 + u1 * u1);
+        }
+        st[2] = mv;
     }
     if (up.pts_new) {
 #pragma unroll

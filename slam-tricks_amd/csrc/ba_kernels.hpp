@@ -160,6 +160,11 @@ struct BacksubUpdate {
     double* pts_new; double* partial_p;
     int n_cams; const double* cams; const unsigned char* cam_fixed; const double* gc; const double* dc;
     double* cams_new; double* partial_c;
+    // iterative Schur (iterative_schur.hip): skip -- the PCG's device-side "done" flag (the kernel returns at once when it is set);
+    // r_model -- the model change of an INEXACT step, m = -(J d)^T (r + J d / 2), from the records, r and the step (obs_pt: the
+    // landmark of every record) in place of the exact-step term -1/2 g d + 1/2 d^T D d, which only holds for an exact solve
+    const int* skip = nullptr;
+    const double2* r_model = nullptr; const int* obs_pt = nullptr;
 };
 int backsub_grid(int n_pts);
 int backsub_cam_grid(int n_cams);

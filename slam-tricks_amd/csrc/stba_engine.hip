@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "iterative_schur.hpp"
 #include "lm_policy.hpp"
 
 namespace stba {
@@ -136,13 +137,27 @@ struct stba_ba {
     double ar_ms = 0.0, ar_bytes = 0.0; int ar_calls = 0;   // accumulated over one LM run
     hipEvent_t ev[15] = {};     // [12]: the trial block has reached the host; [13], [14]: second pair for the speculative linearisation
     CovStore* cov = nullptr;    // the last stba_ba_covariance_compute (covariance.hip), until the next one, a release or destroy
+    // ITERATIVE_SCHUR (stba_ba_create_ex; iterative_schur.hip): no S, no pair plan, no Y -- Sbuf holds only the extras tail.
+    // PCG vectors x = dxc, r, z, p, q; one 6x6 preconditioner inverse per camera; the chunk partials of the Schur-Jacobi blocks;
+    // three per-workgroup partial arrays; the solve's device state and its stamped hand-off to the host
+    bool iterative = false;
+    int pcg_precond = STBA_PRECOND_JACOBI, pcg_min = 0, pcg_max = 500, pcg_check = 4;
+    double pcg_eta = 0.1;
+    stba_pcg_summary pcg_sum{};
+    double *pcg_vec = nullptr, *pcg_minv = nullptr, *pcg_sj = nullptr, *pcg_part = nullptr;
+    PcgState* pcg_state = nullptr;
+    MappedBuffer pcg_host;
+    double pcg_seq = 0.0;
+    int pcg_last_it = 0, pcg_last_cap = 0;     // the last solve, counted into pcg_sum once the LM loop keeps its step
+    std::vector<int> pcg_per_iter;             // PCG iterations of every LM iteration of the last solve (1, 2, ...)
 
-    double* S() const { return Sbuf; }
-    double* ex_diag() const { return Sbuf + (size_t)lda * lda; }
-    double* ex_gc() const { return Sbuf + (size_t)lda * lda + lda; }
-    double* rhs() const { return Sbuf + (size_t)lda * lda + 2 * (size_t)lda; }
-    double* ex_scalar() const { return Sbuf + (size_t)lda * lda + 3 * (size_t)lda; }
-    size_t sbuf_count() const { return (size_t)lda * lda + 4 * (size_t)lda; }
+    size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
+    double* S() const { return iterative ? nullptr : Sbuf; }
+    double* ex_diag() const { return Sbuf + s_count(); }
+    double* ex_gc() const { return Sbuf + s_count() + lda; }
+    double* rhs() const { return Sbuf + s_count() + 2 * (size_t)lda; }
+    double* ex_scalar() const { return Sbuf + s_count() + 3 * (size_t)lda; }
+    size_t sbuf_count() const { return s_count() + 4 * (size_t)lda; }
     // cross-rank sum: only the lower triangle of the n x n system travels (S is symmetric and only its lower
     // triangle is ever read), followed by the four extras vectors: [tri n(n+1)/2 | ex_diag | ex_gc | rhs | scalars]
     // When the union over ranks of the non-zero 6x6 blocks is sparse (C5: 14 % of the camera pairs share a
@@ -171,6 +186,8 @@ static void ba_free(stba_ba* b) {
     F(b->task_p_lo); F(b->task_p_hi); F(b->row_task_ptr); F(b->row_tasks); F(b->task_part_off); F(b->schur_part);
     F(b->pair_begin); F(b->pair_end); F(b->pair_rec); F(b->task_vs_ptr); F(b->vs_first); F(b->Y); F(b->yv); F(b->yws); F(b->dup_run);
     F(b->cost_partial); F(b->upd_partial_c); F(b->upd_partial_p); F(b->trial); F(b->flag);
+    F(b->pcg_vec); F(b->pcg_minv); F(b->pcg_sj); F(b->pcg_part); F(b->pcg_state);
+    b->pcg_host.release();
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
     b->ts_host.release();
@@ -479,6 +496,7 @@ __global__ void export_trial_kernel(const double* __restrict__ trial, const int*
 static int ba_backsub_trial(stba_ba* b) {
     BacksubUpdate up{b->pts[b->cur], b->pt_fixed, b->dp, b->pts[b->cur ^ 1], b->upd_partial_p,
                      b->nc, b->cams[b->cur], b->cam_fixed, b->ex_gc(), b->dc, b->cams[b->cur ^ 1], b->upd_partial_c};
+    if (b->iterative) { up.r_model = b->r; up.obs_pt = b->obs_pt; }      // (an inexact step: m = -(J d)^T (r + J d / 2))
     return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, &up, b->hl_fn ? b->Jc12 : nullptr);
 }
 
@@ -550,6 +568,114 @@ static int ba_cov_build(stba_ba* b) {
     return STBA_OK;
 }
 
+// ---- ITERATIVE_SCHUR: the reduced camera system applied implicitly and solved by PCG (iterative_schur.hip).
+// Same unknowns, damping and constant dofs as the direct path: with eta -> 0 the step is the direct path's step.
+static PcgVecs pcg_vecs(stba_ba* b) {
+    PcgVecs v;
+    const size_t L = (size_t)b->lda, nw = (size_t)is_vec_grid(b->nc);
+    v.x = b->dxc; v.r = b->pcg_vec; v.z = b->pcg_vec + L; v.p = b->pcg_vec + 2 * L; v.q = b->pcg_vec + 3 * L;
+    v.b = b->rhs(); v.Minv = b->pcg_minv;
+    v.part_rz = b->pcg_part; v.part_pq = b->pcg_part + nw; v.part_q = b->pcg_part + 2 * nw;
+    v.state = b->pcg_state;
+    return v;
+}
+
+static int ba_pcg_alloc(stba_ba* b) {
+    STBA_TRY(dev_alloc(&b->pcg_vec, 4 * (size_t)b->lda));
+    STBA_TRY(dev_alloc(&b->pcg_minv, (size_t)b->nc * 36));
+    STBA_TRY(dev_alloc(&b->pcg_sj, (size_t)std::max(b->n_chunks, 1) * 24));
+    STBA_TRY(dev_alloc(&b->pcg_part, 3 * (size_t)is_vec_grid(b->nc)));
+    STBA_TRY(dev_alloc(&b->pcg_state, 1));
+    STBA_HIP(hipMemsetAsync(b->pcg_vec, 0, 4 * (size_t)b->lda * sizeof(double), b->st));
+    STBA_HIP(hipMemsetAsync(b->pcg_state, 0, sizeof(PcgState), b->st));
+    STBA_HIP(hipMemsetAsync(b->flag, 0, sizeof(int), b->st));       // (no factorisation: the trial block's flag stays 0)
+    return STBA_OK;
+}
+
+// landmark pass of one product: zp (in dxp) = V^-1 (-gp - W^T x); gp = null for S x.  skip: the PCG's state (null: always run)
+static int ba_is_landmark_pass(stba_ba* b, const double* x, const double* gp, PcgState* skip) {
+    BacksubUpdate up{};
+    up.skip = skip ? &skip->done : nullptr;
+    return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, gp, x, b->dxp, b->st, &up, b->hl_fn ? b->Jc12 : nullptr);
+}
+// camera pass: y = (Hcc + D) p + W zp (IS_FINAL_APPLY, p^T y partials into pq_part) | y = -gc - W zp (IS_FINAL_RHS)
+static int ba_is_camera_pass(stba_ba* b, int mode, const double* p, double* y, double* pq_part, const PcgState* skip) {
+    STBA_TRY(launch_is_cam_gather(b->n_chunks, b->chunk_begin, b->chunk_end, b->cam_perm, b->obs_pt, b->J8, b->omask, b->hl_fn ? b->Jc12 : nullptr,
+                                  b->dxp, skip, b->cam_partial, b->st));
+    return launch_is_cam_final(b->nc, mode, b->cam_chunk_start, b->cam_partial, b->Hcc, b->dc, b->gc, b->cam_fixed, p, y, pq_part, skip, b->st);
+}
+static int ba_is_precond(stba_ba* b, int kind) {
+    if (kind == STBA_PRECOND_SCHUR_JACOBI)
+        STBA_TRY(launch_is_sj_gather(b->n_chunks, b->no, b->chunk_begin, b->chunk_end, b->cam_perm, b->obs_cam, b->obs_pt, b->J8, b->omask,
+                                     b->hl_fn ? b->Jc12 : nullptr, b->Hinv6, b->pcg_sj, b->st));
+    return launch_is_precond(b->nc, kind, b->Hcc, b->dc, b->scale_c, b->cam_fixed, b->cam_chunk_start, b->pcg_sj, b->pcg_minv, b->st);
+}
+// reduced right-hand side rhs = -(gc - W V^-1 gp): the landmark pass with x = 0, then the camera pass
+static int ba_is_rhs(stba_ba* b) {
+    STBA_HIP(hipMemsetAsync(b->dxc, 0, (size_t)b->n * sizeof(double), b->st));
+    STBA_TRY(ba_is_landmark_pass(b, b->dxc, b->gp, nullptr));
+    return ba_is_camera_pass(b, IS_FINAL_RHS, nullptr, b->rhs(), nullptr, nullptr);
+}
+// what ba_build_reduced makes, without S: damped landmark inverses, camera blocks, the LM diagonal, the right-hand side and the
+// preconditioner of this iteration
+static int ba_build_implicit(stba_ba* b, const Damping& dm) {
+    const int init_scale = b->scale_init ? 0 : 1;
+    if (!dm.explicit_d)
+        STBA_TRY(launch_point_damp_invert(b->np, b->Hpp6, b->pt_fixed, b->scale_p, init_scale, dm.use_scaling, dm.radius, dm.dmin,
+                                          dm.dmax, b->dp, b->Hinv6, b->ex_diag(), 3 * b->lda, b->st));
+    else {
+        STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, b->st));
+        STBA_HIP(hipMemsetAsync(b->ex_diag(), 0, 3 * (size_t)b->lda * sizeof(double), b->st));
+    }
+    STBA_TRY(ba_camera_blocks(b));
+    STBA_TRY(launch_is_cam_setup(b->nc, b->Hcc, b->gc, b->ex_diag(), b->ex_gc(), b->scale_c, init_scale, dm.use_scaling, dm.radius, dm.dmin,
+                                 dm.dmax, b->dc, dm.explicit_d ? 1 : 0, b->st));
+    if (!dm.explicit_d) b->scale_init = true;
+    STBA_TRY(ba_is_rhs(b));
+    return ba_is_precond(b, b->pcg_precond);
+}
+static int ba_build(stba_ba* b, const Damping& dm) { return b->iterative ? ba_build_implicit(b, dm) : ba_build_reduced(b, dm); }
+
+// PCG on the reduced system into dxc.  check_every iterations are enqueued at a time, then the solve's state travels to the host
+// as a stamped block; every kernel of an iteration behind the device's decision returns at once.  *fail: Ceres' FAILURE (the LM
+// step is not ok)
+static int ba_pcg_solve(stba_ba* b, int* fail_out) {
+    const PcgVecs v = pcg_vecs(b);
+    STBA_TRY(launch_is_vec(b->nc, IS_VEC_INIT, v, b->st));
+    STBA_TRY(launch_is_check(b->nc, IS_CHECK_INIT, v, b->pcg_eta, b->pcg_min, b->pcg_max, b->st));
+    if (!b->pcg_host.host) STBA_TRY(b->pcg_host.alloc((size_t)stamped_doubles(4)));
+    double hs[4] = {0.0, 0.0, 0.0, 0.0};
+    long enqueued = 0;
+    while (true) {
+        for (int k = 0; k < b->pcg_check; ++k) {
+            STBA_TRY(launch_is_vec(b->nc, IS_VEC_DIR, v, b->st));
+            STBA_TRY(ba_is_landmark_pass(b, v.p, nullptr, b->pcg_state));
+            STBA_TRY(ba_is_camera_pass(b, IS_FINAL_APPLY, v.p, v.q, v.part_pq, b->pcg_state));
+            STBA_TRY(launch_is_vec(b->nc, IS_VEC_UPDATE, v, b->st));
+            STBA_TRY(launch_is_check(b->nc, IS_CHECK_ITER, v, b->pcg_eta, b->pcg_min, b->pcg_max, b->st));
+        }
+        enqueued += b->pcg_check;
+        const double seq = (b->pcg_seq += 1.0);
+        STBA_TRY(launch_is_export(b->pcg_state, b->pcg_host.dev, seq, b->st));
+        STBA_TRY(stamped_wait(b->pcg_host.host, 4, [seq](double st) { return st == seq; }, hs, hip_stream_state(b->st), "PCG state", 120.0));
+        if (hs[0] != 0.0) break;
+        if (enqueued > (long)b->pcg_max + b->pcg_check) return fail(STBA_ERR_HIP, "PCG: the device did not stop at max_iterations");
+    }
+    b->pcg_last_it = (int)hs[1];
+    b->pcg_last_cap = hs[3] != 0.0 ? 1 : 0;
+    *fail_out = hs[2] != 0.0 ? 1 : 0;
+    return STBA_OK;
+}
+// the last solve belongs to an LM iteration (not to a trial step the loop discards behind a late convergence test)
+static void ba_pcg_account(stba_ba* b, int lm_iter) {
+    if (lm_iter >= 1) { b->pcg_per_iter.resize((size_t)lm_iter, 0); b->pcg_per_iter[(size_t)lm_iter - 1] = b->pcg_last_it; }
+    b->pcg_sum.iterations_total += b->pcg_last_it;
+    b->pcg_sum.solves += 1;
+    b->pcg_sum.hit_cap += b->pcg_last_cap;
+    b->pcg_sum.max_iterations_in_a_solve = std::max(b->pcg_sum.max_iterations_in_a_solve, b->pcg_last_it);
+    b->pcg_sum.last_eta = b->pcg_eta;
+}
+
 static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterations, stba_lm_summary* sum,
                      double* trace, stba_iteration_callback cb, void* cb_user) {
     stba_lm_options opt;
@@ -567,6 +693,8 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
 
     b->scale_init = false;
     b->ar_ms = 0.0; b->ar_bytes = 0.0; b->ar_calls = 0; b->ar_timing_pending = false;
+    memset(&b->pcg_sum, 0, sizeof b->pcg_sum);
+    b->pcg_per_iter.clear();
     Damping dm;
     dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
     TrustRegion region(opt);
@@ -613,7 +741,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         const bool built_here = need_build;
         if (need_build) {
             if (timing) STBA_HIP(hipEventRecord(ev[2], b->st));
-            STBA_TRY(ba_build_reduced(b, dm));
+            STBA_TRY(ba_build(b, dm));
             if (timing) STBA_HIP(hipEventRecord(ev[3], b->st));
             build_end_ev = 3;
         }
@@ -639,10 +767,11 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         }
         ++iter;
         // ---- factor + solve, back-substitute, trial point
-        int flag_h = 0;
+        int flag_h = 0, pcg_fail = 0;
         // (several ranks behind a time-out of ANY rank: this engine's own cool-down -- every rank counts the same factorisations
         // through the stage kernels, whatever else shares its device or its process)
-        if (b->stage_cooldown > 0) { --b->stage_cooldown; STBA_TRY(chol_factor_solve_stages(b->S(), b->lda, b->n, b->dxc, b->flag, b->st)); }
+        if (b->iterative) STBA_TRY(ba_pcg_solve(b, &pcg_fail));
+        else if (b->stage_cooldown > 0) { --b->stage_cooldown; STBA_TRY(chol_factor_solve_stages(b->S(), b->lda, b->n, b->dxc, b->flag, b->st)); }
         else STBA_TRY(chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st));
         if (timing) STBA_HIP(hipEventRecord(ev[4], b->st));
         STBA_TRY(ba_backsub_trial(b));
@@ -653,7 +782,9 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         // bubble on the GPU in every iteration.  A rejected step costs one linearisation at the old point (below).
         // (With several ranks too: every rank takes the same decision from the same all-reduced block, and the collectives of
         // the speculative build are enqueued on the stream like everything else.)
-        const bool fast = deferred_ok && SPECULATE && !b->hl_fn;      // (host-linearised factors: the callback is synchronous host work)
+        // (host-linearised factors: the callback is synchronous host work; iterative Schur: the PCG hands its state to the host
+        // anyway, and this path does not speculate -- DESIGN.md 7b)
+        const bool fast = deferred_ok && SPECULATE && !b->hl_fn && !b->iterative;
         if (fast && !b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
         // (the speculative linearisation IS the evaluation of the trial point: one pass over the observations, not two)
         const bool speculate = fast && !(fixed && iter >= max_iter);
@@ -681,6 +812,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             STBA_TRY(download(&flag_h, b->flag, 1, b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
         }
+        if (pcg_fail) flag_h = 1;            // (the PCG failed: the step is not ok)
         if (pending) {
             // (cost2 and |g|max of the build behind the previous iteration: trial_finish_kernel read them on the way)
             const double c2 = 0.5 * ts[TS_LIN_COST2], g2 = ts[TS_LIN_GMAX];
@@ -697,6 +829,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
                 break;
             }
         }
+        if (b->iterative) ba_pcg_account(b, iter);
         // (several ranks: the decision is COLLECTIVE -- ts[TS_TIMEOUT] is the all-reduced count of ranks whose factorisation timed
         // out, the same number on every rank.  A rank-local decision would leave one rank re-running the iteration, with its
         // all-reduces of a system linearised at the old point, while the others move on: mismatched collectives.)
@@ -779,7 +912,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             // next reduced-system build (one collective per iteration); build it now.
             dm.radius = region.radius;
             if (timing) STBA_HIP(hipEventRecord(ev[e2], b->st));
-            STBA_TRY(ba_build_reduced(b, dm));
+            STBA_TRY(ba_build(b, dm));
             if (timing) STBA_HIP(hipEventRecord(ev[e2 + 1], b->st));
             build_end_ev = e2 + 1;
             need_build = false;
@@ -835,6 +968,7 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     ba_collect_allreduce_time(b);
     s.ms_allreduce = b->ar_ms; s.allreduce_bytes = b->ar_bytes; s.allreduce_calls = b->ar_calls;
     finish_summary(&s, iter, cost, region.radius, gmax, t_start);
+    b->pcg_sum.linear_solve_ms = b->iterative ? s.ms_solve : 0.0;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     if (sum) *sum = s;
     return STBA_OK;
@@ -873,9 +1007,10 @@ int stba_device_count(void) {
 
 void stba_lm_default_options(stba_lm_options* opt) { if (opt) default_options(opt); }
 
-int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
-                   const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
-                   const unsigned char* pt_fixed, void* hip_stream) {
+// (iterative: ITERATIVE_SCHUR -- no Schur plan, no dense Y, no S: see stba_ba_create_ex)
+static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
+                     const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
+                     const unsigned char* pt_fixed, void* hip_stream, bool iterative) {
     if (!out) return fail(STBA_ERR_INVALID_ARGUMENT, "out is null");
     *out = nullptr;
     if (n_cams <= 0 || n_pts < 0 || n_obs < 0 || !cams || (n_pts > 0 && !pts) ||
@@ -886,6 +1021,7 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
             return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: observation index out of range");
     STBA_TRY(require_device());
     stba_ba* b = new stba_ba();
+    b->iterative = iterative;
     b->nc = n_cams; b->np = n_pts; b->no = n_obs; b->n = 6 * n_cams; b->lda = chol_padded_dim(b->n);
     if (hip_stream) b->st = reinterpret_cast<hipStream_t>(hip_stream);
     else {
@@ -982,7 +1118,7 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
     int task_max_cols = 0;
     size_t total_pairs = 0;
     for (int j = 0; j < n_pts; ++j) { const size_t k = (size_t)(pt_start[j + 1] - pt_start[j]); total_pairs += k * (k + 1) / 2; }
-    {   // the plan costs 16 bytes per pair on the host and on the device: refuse what cannot be held instead of running out of memory
+    if (!iterative) {   // the plan costs 16 bytes per pair on the host and on the device: refuse what cannot be held instead of running out of memory
         // half-way (a landmark seen by k cameras makes k (k + 1) / 2 pairs: 1000 cameras that ALL see 100 000 landmarks are 5e10)
         size_t free_b = 0, total_b = 0;
         const bool have_info = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
@@ -1006,10 +1142,12 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
         ba_free(b);
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: more than 255 observations of one (camera, landmark) pair in a problem that needs the dense form of the Schur complement");
     }
-    const bool build_pair_plan = b->schur_mode != STBA_SCHUR_DENSE;
+    const bool build_pair_plan = !iterative && b->schur_mode != STBA_SCHUR_DENSE;
     b->have_pair_plan = build_pair_plan;
     static const int TASK_PAIRS = std::max(256, knob_int("STBA_SCHUR_TASK_PAIRS", SCHUR_TASK_PAIRS));
-    if (!build_pair_plan) {
+    if (iterative) {
+        // no reduced system at all: no block pattern either (row_col_ptr stays zero)
+    } else if (!build_pair_plan) {
         // no plan: the block pattern (only the cross-rank packing reads it) is taken as full -- enumerating it costs as much as the pairs
         for (int c = 0; c < n_cams; ++c) {
             for (int c2 = 0; c2 <= c; ++c2) row_cols.push_back(c2);
@@ -1400,6 +1538,7 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
     A_(dev_alloc(&b->upd_partial_c, (size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
     A_(dev_alloc(&b->upd_partial_p, (size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
     A_(dev_alloc(&b->trial, (size_t)TS_BLOCK)); A_(dev_alloc(&b->flag, 1));
+    if (iterative) A_(ba_pcg_alloc(b));
 
     tmark("device allocations");
     A_(upload(b->cams[0], cams, nc * 7, b->st)); A_(upload(b->pts[0], pts, np * 3, b->st));
@@ -1456,7 +1595,107 @@ int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double
     return STBA_OK;
 }
 
+int stba_ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
+                   const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
+                   const unsigned char* pt_fixed, void* hip_stream) {
+    return ba_create(out, n_cams, n_pts, n_obs, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed, pt_fixed, hip_stream, false);
+}
+
+int stba_ba_create_ex(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
+                      const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
+                      const unsigned char* pt_fixed, void* hip_stream, const stba_ba_create_options* opt) {
+    if (out) *out = nullptr;
+    int solver = STBA_LINEAR_DENSE_SCHUR;
+    if (opt) {
+        if (opt->struct_size < offsetof(stba_ba_create_options, linear_solver) + sizeof(int))
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create_ex: options.struct_size is smaller than any version of the struct");
+        solver = opt->linear_solver;
+    }
+    if (solver != STBA_LINEAR_DENSE_SCHUR && solver != STBA_LINEAR_ITERATIVE_SCHUR)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create_ex: unknown linear_solver " + std::to_string(solver));
+    return ba_create(out, n_cams, n_pts, n_obs, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed, pt_fixed, hip_stream,
+                     solver == STBA_LINEAR_ITERATIVE_SCHUR);
+}
+
+// what an ITERATIVE_SCHUR engine refuses: everything that needs the explicit reduced system, and several ranks
+static int refuse_iterative(const stba_ba* b, const char* who, const char* why) {
+    if (!b || !b->iterative) return STBA_OK;
+    return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine uses ITERATIVE_SCHUR, " + why);
+}
+
+int stba_ba_set_pcg(stba_ba* b, int preconditioner, double eta, int min_iterations, int max_iterations, int check_every) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (!b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_pcg: the engine uses the dense Schur solver (stba_ba_create_ex)");
+    if (preconditioner < STBA_PRECOND_IDENTITY || preconditioner > STBA_PRECOND_SCHUR_JACOBI || !(eta >= 0.0) || min_iterations < 0 ||
+        max_iterations < 1 || min_iterations > max_iterations || check_every < 1)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_pcg: bad argument");
+    b->pcg_precond = preconditioner; b->pcg_eta = eta; b->pcg_min = min_iterations; b->pcg_max = max_iterations; b->pcg_check = check_every;
+    return STBA_OK;
+}
+
+int stba_ba_last_pcg_summary(stba_ba* b, stba_pcg_summary* out) {
+    if (!b || !out) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
+    *out = b->pcg_sum;
+    return STBA_OK;
+}
+
+int stba_ba_last_pcg_iterations(stba_ba* b, int* per_iteration, int n) {
+    if (!b || n < 0 || (n > 0 && !per_iteration)) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_last_pcg_iterations: bad argument");
+    for (int k = 0; k < n; ++k) per_iteration[k] = (size_t)k < b->pcg_per_iter.size() ? b->pcg_per_iter[(size_t)k] : 0;
+    return STBA_OK;
+}
+
+int stba_ba_time_schur_apply(stba_ba* b, int reps, double* ms_avg) {
+    if (!b || reps <= 0 || !ms_avg) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_time_schur_apply: bad argument");
+    if (!b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_time_schur_apply: the engine uses the dense Schur solver");
+    if (!b->have_blocks) return fail(STBA_ERR_STATE, "stba_ba_time_schur_apply needs stba_ba_schur_apply first");
+    const PcgVecs v = pcg_vecs(b);
+    STBA_HIP(hipEventRecord(b->ev[0], b->st));
+    for (int k = 0; k < reps; ++k) {
+        STBA_TRY(ba_is_landmark_pass(b, v.p, nullptr, nullptr));
+        STBA_TRY(ba_is_camera_pass(b, IS_FINAL_APPLY, v.p, v.q, nullptr, nullptr));
+    }
+    STBA_HIP(hipEventRecord(b->ev[1], b->st));
+    STBA_HIP(hipStreamSynchronize(b->st));
+    float ms = 0.f;
+    STBA_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    *ms_avg = (double)ms / reps;
+    return STBA_OK;
+}
+
+int stba_ba_schur_apply(stba_ba* b, const double* dc, const double* dp, int which, const double* x, double* y) {
+    if (!b || !dc || !dp || !y || which < 0 || which > 2) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_schur_apply: bad argument");
+    if (!b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_schur_apply: the engine uses the dense Schur solver (stba_ba_reduced_system)");
+    if (!b->have_blocks) return fail(STBA_ERR_STATE, "stba_ba_schur_apply needs stba_ba_normal_blocks first");
+    STBA_TRY(upload(b->dc, dc, (size_t)b->n, b->st));
+    STBA_TRY(upload(b->dp, dp, (size_t)b->np * 3, b->st));
+    Damping dm;
+    dm.explicit_d = true;
+    STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, b->st));
+    STBA_TRY(ba_camera_blocks(b));
+    double* out_dev = b->rhs();
+    if (!x) STBA_TRY(ba_is_rhs(b));
+    else {
+        const PcgVecs v = pcg_vecs(b);
+        STBA_TRY(upload(which == 0 ? v.p : v.r, x, (size_t)b->n, b->st));
+        if (which == 0) {
+            STBA_TRY(ba_is_landmark_pass(b, v.p, nullptr, nullptr));
+            STBA_TRY(ba_is_camera_pass(b, IS_FINAL_APPLY, v.p, v.q, nullptr, nullptr));
+            out_dev = v.q;
+        } else {
+            STBA_TRY(ba_is_precond(b, which == 1 ? STBA_PRECOND_JACOBI : STBA_PRECOND_SCHUR_JACOBI));
+            STBA_TRY(launch_is_vec(b->nc, IS_VEC_PRECOND, v, b->st));
+            out_dev = v.z;
+        }
+    }
+    STBA_TRY(download(y, out_dev, (size_t)b->n, b->st));
+    STBA_HIP(hipStreamSynchronize(b->st));
+    b->have_reduced = b->have_dxc = b->have_dxp = false;
+    return STBA_OK;
+}
+
 int stba_ba_set_schur_mode(stba_ba* ba, int mode) {
+    STBA_TRY(refuse_iterative(ba, "stba_ba_set_schur_mode", "which forms no Schur complement"));
     if (!ba || mode < STBA_SCHUR_AUTO || mode > STBA_SCHUR_DENSE) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_schur_mode: bad argument");
     if (mode == STBA_SCHUR_AUTO) mode = ba->schur_mode_auto;
     if (mode == STBA_SCHUR_PAIRS && !ba->have_pair_plan)
@@ -1533,6 +1772,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
 }
 
 int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank, int world_size) {
+    STBA_TRY(refuse_iterative(b, "stba_ba_set_allreduce", "which runs on one rank only"));
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -1614,6 +1854,7 @@ int stba_ba_normal_blocks(stba_ba* b, double* Hcc, double* gc, double* Hpp, doub
 }
 
 int stba_ba_reduced_system(stba_ba* b, const double* dc, const double* dp, double* S, double* rhs) {
+    STBA_TRY(refuse_iterative(b, "stba_ba_reduced_system", "which never forms the reduced system (stba_ba_schur_apply applies it)"));
     if (!b || !dc || !dp) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
     if (!b->have_blocks) return fail(STBA_ERR_STATE, "stba_ba_reduced_system needs stba_ba_normal_blocks first");
     STBA_TRY(upload(b->dc, dc, (size_t)b->n, b->st));
@@ -1632,6 +1873,7 @@ int stba_ba_reduced_system(stba_ba* b, const double* dc, const double* dp, doubl
 }
 
 int stba_ba_solve_reduced(stba_ba* b, double* dxc) {
+    STBA_TRY(refuse_iterative(b, "stba_ba_solve_reduced", "which has no reduced system to factor"));
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (!b->have_reduced) return fail(STBA_ERR_STATE, "stba_ba_solve_reduced needs stba_ba_reduced_system first");
     STBA_TRY(chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st));
@@ -1724,6 +1966,7 @@ int stba_ba_time_linearize(stba_ba* b, int reps, double* ms_avg) {
 // measurement (bench.py roofline_schur): average device time of the Schur-complement kernel at the current point -- a fresh
 // linearisation and landmark blocks first, then `reps` reduced-system builds timed around the kernel alone
 int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics_per_launch, double* pairs_per_launch) {
+    STBA_TRY(refuse_iterative(b, "stba_ba_time_schur", "which has no Schur complement kernel"));
     if (!b || reps <= 0 || !ms_avg) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
     STBA_TRY(ba_linearize_lm(b, b->cur));
     STBA_TRY(ba_normal_blocks(b));
@@ -1746,6 +1989,7 @@ int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics
 }
 
 int stba_ba_covariance_compute(stba_ba* b, double min_rcond, double* rcond_out) {
+    STBA_TRY(refuse_iterative(b, "stba_ba_covariance_compute", "and the covariance needs the explicit reduced system S"));
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (b->ar) return fail(STBA_ERR_STATE, "stba_ba_covariance_compute: the engine holds one landmark shard of several ranks; covariance needs one rank");
     cov_store_free(b->cov);

@@ -480,3 +480,61 @@ def pose_graph_scene(n_nodes=10000, loops_per_node=3, seed=4, sigma_t=0.01, sigm
         init[i] = _se3_mul(init[i - 1][None], meas[i - 1][None])[0]
     fixed = np.zeros(n_nodes, np.uint8); fixed[0] = 1
     return dict(poses_true=poses, poses0=init, edge_i=ei, edge_j=ej, meas=meas, node_fixed=fixed)
+
+
+# --------------------------------------------------------------------------- large BA scene (iterative Schur)
+def _quat_mul(a, b):
+    """(..., 4) x (..., 4), (x, y, z, w) order: a (x) b"""
+    ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+
+def _quat_exp(w):
+    """(..., 3) rotation vectors -> unit quaternions (x, y, z, w)"""
+    th = np.linalg.norm(w, axis=-1, keepdims=True)
+    half = 0.5 * th
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = np.where(th > 1e-12, np.sin(half) / np.where(th > 0, th, 1.0), 0.5)
+    return np.concatenate([w * s, np.cos(half)], -1)
+
+
+def large_ba_scene(n_cams=50000, n_pts=500000, views_per_pt=10, seed=0, cam_dist=4.0, pt_radius=1.0, pos_noise=0.02,
+                   ang_noise_deg=0.3, pt_noise=0.02):
+    """A seeded, well-conditioned BA scene of any size, vectorised (5e6 observations in seconds).
+
+    Landmarks are uniform in a ball of radius pt_radius around the origin; every camera sits at distance cam_dist from the origin
+    with its optical axis through it, so it faces every landmark (depth >= cam_dist - pt_radius > 0, |x/z|, |y/z| <=
+    tan(asin(pt_radius / cam_dist))).  Every landmark is seen by exactly views_per_pt distinct cameras, (base + k * stride) mod n_cams
+    with a random base and stride per landmark: spread over the whole sphere, not a chain.  Features are the noise-free projections
+    (the ground truth is the exact solution); the start is the truth with every free camera rotated by ang_noise_deg and moved by
+    pos_noise (normal, per axis) and every landmark moved by pt_noise.  Cameras 0 and 1 are constant (they fix the gauge).
+    Returns cams_true, pts_true, cams0, pts0, obs_cam, obs_pt (landmark-major), obs_feat, cam_fixed -- st20_scene's keys."""
+    if not (1 <= views_per_pt <= n_cams) or cam_dist <= pt_radius:
+        raise ValueError("large_ba_scene: need 1 <= views_per_pt <= n_cams and cam_dist > pt_radius")
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(n_cams, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q *= np.where(q[:, 3:4] < 0, -1.0, 1.0)
+    R = rot_from_quat(q)
+    cams_true = np.concatenate([q, -cam_dist * R[:, :, 2]], 1)          # centre = -cam_dist * (optical axis in the world)
+    u = rng.normal(size=(n_pts, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    pts_true = u * (pt_radius * rng.random((n_pts, 1)) ** (1.0 / 3.0))
+    base = rng.integers(0, n_cams, size=n_pts)
+    stride = rng.integers(1, max(1, (n_cams - 1) // max(1, views_per_pt - 1)) + 1, size=n_pts) if views_per_pt > 1 else np.ones(n_pts, np.int64)
+    k = np.arange(views_per_pt)
+    obs_cam = ((base[:, None] + k[None, :] * stride[:, None]) % n_cams).reshape(-1).astype(np.int32)
+    obs_pt = np.repeat(np.arange(n_pts), views_per_pt).astype(np.int32)
+    obs_feat = project(cams_true, pts_true, obs_cam, obs_pt)[0]
+    cams0 = cams_true.copy()
+    dq = _quat_exp(rng.normal(0.0, np.deg2rad(ang_noise_deg), size=(n_cams, 3)))
+    cams0[:, :4] = _quat_mul(cams_true[:, :4], dq)
+    cams0[:, 4:] += rng.normal(0.0, pos_noise, size=(n_cams, 3))
+    cams0[:2] = cams_true[:2]
+    pts0 = pts_true + rng.normal(0.0, pt_noise, size=pts_true.shape)
+    cam_fixed = np.zeros((n_cams, 6), dtype=np.uint8)
+    cam_fixed[:2] = 1
+    return dict(cams_true=cams_true, pts_true=pts_true, cams0=cams0, pts0=pts0, obs_cam=obs_cam, obs_pt=obs_pt, obs_feat=obs_feat,
+                cam_fixed=cam_fixed)

@@ -1,0 +1,254 @@
+"""ITERATIVE_SCHUR bundle adjustment (stba_ba_create_ex, iterative_schur.hip) on the device: the implicit operator, its
+preconditioners and right-hand side against numpy, the exact limit of the PCG against the direct engine and the dense Ceres
+reference, Ceres' defaults on st20 and C2, a scene the direct path cannot hold, determinism and the refusals."""
+import importlib
+import time
+
+import numpy as np
+import pytest
+
+import lm_step_ref as L
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def st():
+    mod = importlib.import_module("slam-tricks_amd")
+    assert mod.device_count() > 0, "GPU tests need a HIP device"
+    return mod
+
+
+@pytest.fixture(scope="module")
+def sc():
+    return importlib.import_module("slam-tricks_amd.scenes")
+
+
+def engine(st, s, solver="iterative_schur"):
+    return st.BAEngine(s["cams0"], s["pts0"], s["obs_cam"], s["obs_pt"], s["obs_feat"], s["cam_fixed"], pt_fixed=s.get("pt_fixed"),
+                       linear_solver=solver)
+
+
+def numpy_system(prob, dc, dp):
+    """S (free dofs only: constant rows and columns zero), rhs, the Jacobi and Schur-Jacobi block inverses, in long double sums"""
+    cams, pts = prob.split(prob.x0)
+    r, Jc, Jp = prob.lin_obs(cams.copy(), pts.copy(), True)
+    Jc = Jc * (~prob.cam_fixed[prob.oc])[:, None, :]
+    Jp = Jp * (~prob.pt_fixed[prob.op])[:, None, None]
+    Jc, Jp, r = Jc.astype(np.longdouble), Jp.astype(np.longdouble), r.astype(np.longdouble)
+    nc, npt, n = prob.nc, prob.np_, 6 * prob.nc
+    U = np.zeros((n, n), np.longdouble)
+    gc = np.zeros(n, np.longdouble)
+    V = np.zeros((npt, 3, 3), np.longdouble)
+    gp = np.zeros((npt, 3), np.longdouble)
+    W = np.zeros((npt, n, 3), np.longdouble) if npt * n < 4e7 else None
+    for o in range(len(r)):
+        c, j = prob.oc[o], prob.op[o]
+        U[6 * c:6 * c + 6, 6 * c:6 * c + 6] += Jc[o].T @ Jc[o]
+        gc[6 * c:6 * c + 6] += Jc[o].T @ r[o]
+        V[j] += Jp[o].T @ Jp[o]
+        gp[j] += Jp[o].T @ r[o]
+        W[j, 6 * c:6 * c + 6] += Jc[o].T @ Jp[o]
+    U[np.arange(n), np.arange(n)] += dc
+    S = U.copy()
+    rhs = -gc.copy()
+    rhs_terms = np.abs(gc.astype(np.float64))          # componentwise size of the terms of rhs (it is a difference of large terms)
+    for j in range(npt):
+        if prob.pt_fixed[j]:
+            continue
+        Vi = np.linalg.inv((V[j] + np.diag(dp[j])).astype(np.float64)).astype(np.longdouble)
+        S -= W[j] @ Vi @ W[j].T
+        rhs += W[j] @ (Vi @ gp[j])
+        rhs_terms += np.abs(W[j].astype(np.float64)) @ np.abs(Vi.astype(np.float64)) @ np.abs(gp[j].astype(np.float64))
+    free = ~prob.cam_fixed.reshape(-1)
+    P = np.diag(free.astype(np.float64))
+    S = (P @ S.astype(np.float64) @ P)
+    rhs = rhs.astype(np.float64) * free
+
+    def block_inv(A):
+        out = np.zeros((n, n))
+        for c in range(nc):
+            f = free[6 * c:6 * c + 6]
+            B = A[6 * c:6 * c + 6, 6 * c:6 * c + 6].astype(np.float64)
+            blk = np.zeros((6, 6))
+            if f.any():
+                blk[np.ix_(f, f)] = np.linalg.inv(B[np.ix_(f, f)])
+            out[6 * c:6 * c + 6, 6 * c:6 * c + 6] = blk
+        return out
+    # size of the two terms S is the difference of: the bound of an operator product is relative to them, not to their difference
+    T = (U - np.diag(np.asarray(dc, np.longdouble))).astype(np.float64)
+    scale = np.linalg.norm(T, 2) + np.abs(dc).max() + np.linalg.norm((U.astype(np.float64) - S) * np.outer(free, free), 2)
+    return S, rhs, block_inv(U), block_inv(S), scale, np.linalg.norm(rhs_terms)
+
+
+def small_scenes(sc):
+    s1 = L.ba_scene(n_lm=33, extras=True)
+    s2 = sc.st20_scene()
+    return [("lm33_extras", s1), ("st20", s2)]
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device_jacobian", "host_linearised"])
+@pytest.mark.parametrize("scene", [0, 1])
+def test_operator_parity(st, sc, scene, host):
+    s = small_scenes(sc)[scene][1]
+    prob = L.ba_problem(dict(s, pt_fixed=s.get("pt_fixed")))
+    e = engine(st, s)
+    if host:
+        e.set_host_linearizer(lambda cams, pts, want: prob.lin_obs(cams.copy(), pts.copy(), want))
+        e.evaluate(jac=False)
+    else:
+        e.evaluate()
+    e.normal_blocks()
+    rng = np.random.default_rng(7)
+    n = 6 * prob.nc
+    dc = rng.uniform(0.1, 1.0, n)
+    dp = rng.uniform(0.1, 1.0, (prob.np_, 3))
+    S, rhs, Mj, Ms, nS, n_rhs_terms = numpy_system(prob, dc, dp)
+    free = ~prob.cam_fixed.reshape(-1)
+    for k in range(3):
+        x = rng.normal(size=n)
+        y = e.schur_apply(dc, dp, 0, x)
+        assert np.linalg.norm(y - S @ x) <= 1e-12 * nS * np.linalg.norm(x), (k, np.linalg.norm(y - S @ x) / (nS * np.linalg.norm(x)))
+        assert np.all(y[~free] == 0.0)
+        for w, M in ((1, Mj), (2, Ms)):
+            z = e.schur_apply(dc, dp, w, x)
+            ref = M @ x
+            assert np.linalg.norm(z - ref) <= 1e-10 * np.linalg.norm(M, 2) * np.linalg.norm(x), (w, np.linalg.norm(z - ref))
+    b = e.schur_apply(dc, dp, 0, None)
+    assert np.linalg.norm(b - rhs) <= 1e-13 * n_rhs_terms, (np.linalg.norm(b - rhs), n_rhs_terms)
+
+
+def lm_opts(st, **kw):
+    return st.default_options(**kw)
+
+
+@pytest.mark.parametrize("case", ["lm31_r1e4", "lm33_extras_r1e-3"])
+def test_exact_limit_matches_direct_and_reference(st, case):
+    sk, ok = L.BA_CASES[case]
+    k = 3
+    s = L.ba_scene(**sk)
+    o = L.lm_options(**ok)
+    prob = L.ba_problem(s)
+    opt = st.default_options(**dict({f: v for f, v in o.items()}, max_num_iterations=k))
+    d = engine(st, s, "dense_schur")
+    sd, trd = d.solve(opt)
+    e = engine(st, s)
+    e.set_pcg("jacobi", eta=1e-14, max_iterations=max(6 * prob.nc, 10) * 4)
+    se, tre = e.solve(opt)
+    assert se.num_iterations == sd.num_iterations and se.num_successful_steps == sd.num_successful_steps, (se.as_dict(), sd.as_dict())
+    assert np.array_equal(tre[:, 6], trd[:, 6]), "accept/reject decisions differ"
+    np.testing.assert_allclose(tre[:, 5], trd[:, 5], rtol=1e-12)           # radii
+    np.testing.assert_allclose(tre[:, 0], trd[:, 0], rtol=1e-9)
+    np.testing.assert_allclose(tre[:, 3], trd[:, 3], rtol=1e-6, atol=1e-14)
+    ref = L.lm_reference(prob, o, k)
+    cams, pts = e.get_params()
+    x_dev = np.concatenate([cams.reshape(-1), pts.reshape(-1)])
+    fails, ratios = L.compare(prob, ref, "ba", o, x_dev, tre, eps_eff=1e-9)
+    print(f"ITERATIVE exact-limit {case} " + " ".join(f"{kk}={v:.2e}" for kk, v in sorted(ratios.items())))
+    assert not fails, "; ".join(fails)
+    ps = e.pcg_summary()
+    assert ps.solves == se.num_iterations and ps.iterations_total > 0
+
+
+def numpy_gmax(prob, x):
+    r, J, cols = prob.lin(x, True)
+    g = np.zeros(prob.n_local)
+    np.add.at(g, cols.reshape(-1), np.einsum("nkc,nk->nc", J, r).reshape(-1))
+    return np.abs(g[prob.free]).max()
+
+
+def c2_scene(sc):
+    return sc.two_view_scene(n_pts=5000)
+
+
+@pytest.mark.parametrize("pc", ["identity", "jacobi", "schur_jacobi"])
+@pytest.mark.parametrize("scene", ["st20", "c2"])
+def test_ceres_defaults(st, sc, scene, pc):
+    s = sc.st20_scene(pix_noise=1e-3) if scene == "st20" else c2_scene(sc)
+    prob = L.ba_problem(dict(s, pt_fixed=None))
+    opt = st.default_options(max_num_iterations=100)
+    d = engine(st, s, "dense_schur")
+    sd, _ = d.solve(opt)
+    e = engine(st, s)
+    e.set_pcg(pc, eta=0.1, max_iterations=500)
+    se, tr = e.solve(opt)
+    print(f"ITERATIVE {scene} {pc}: direct {sd.num_iterations} it cost {sd.final_cost:.6e}; iterative {se.num_iterations} it "
+          f"cost {se.final_cost:.6e}; pcg {e.pcg_summary().as_dict()}")
+    assert se.termination_type == 0, se.as_dict()
+    # (C2 is a zero-residual problem: both final costs are rounding noise next to the start's, hence the floor relative to it)
+    assert se.final_cost <= sd.final_cost * (1 + opt.function_tolerance) + 1e-12 * sd.initial_cost
+    xd = np.concatenate([a.reshape(-1) for a in d.get_params()])
+    xe = np.concatenate([a.reshape(-1) for a in e.get_params()])
+    g0, gd, ge = numpy_gmax(prob, prob.x0), numpy_gmax(prob, xd), numpy_gmax(prob, xe)
+    print(f"  |g|max: start {g0:.3e}, direct end {gd:.3e}, iterative end {ge:.3e}, ratio {ge / gd:.3e}")
+    # Inexact steps end on the function tolerance further from the stationary point than exact ones, whose last step drives the
+    # gradient down quadratically.  Measured on st20 (1e-3 pixel noise): ratios 9.8e3 (IDENTITY), 4.9e3 (JACOBI), 4.8e3 (SCHUR_JACOBI),
+    # against 6.1e-10 at the direct end point; so the bound is 2e4, not 10.  C2 has zero residual: its direct end-point gradient is
+    # rounding noise, and only the bound against the start's gradient applies there.
+    assert ge <= 1e-3 * g0
+    if scene == "st20":
+        assert ge <= 2e4 * gd
+    ps = e.pcg_summary()
+    assert ps.solves == se.num_iterations and 0 < ps.iterations_total <= ps.solves * 500
+    e2 = engine(st, s)
+    e2.set_pcg(pc, eta=0.1, max_iterations=1)
+    s2, _ = e2.solve(st.default_options(max_num_iterations=5))
+    p2 = e2.pcg_summary()
+    assert p2.solves == s2.num_iterations and p2.hit_cap == p2.solves and p2.iterations_total == p2.solves
+
+
+def test_determinism(st, sc):
+    s = sc.st20_scene()
+    out = []
+    for _ in range(2):
+        e = engine(st, s)
+        e.set_pcg("schur_jacobi", eta=0.1)
+        summ, tr = e.solve(st.default_options(max_num_iterations=30))
+        cams, pts = e.get_params()
+        out.append((tr.copy(), cams, pts, e.pcg_summary().iterations_total))
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
+    assert out[0][3] == out[1][3]
+
+
+def test_refusals_leave_parameters(st, sc):
+    s = sc.st20_scene()
+    e = engine(st, s)
+    before = e.get_params()
+    e.evaluate()
+    e.normal_blocks()
+    n = 6 * len(s["cams0"])
+    dc, dp = np.ones(n), np.ones((len(s["pts0"]), 3))
+    calls = [lambda: e.reduced_system(dc, dp), lambda: e.solve_reduced(), lambda: e.set_schur_mode(e.SCHUR_DENSE),
+             lambda: e.covariance(), lambda: e.set_allreduce(lambda *a: 0, 0, 1), lambda: e.set_comm(None), lambda: e.time_schur(1)]
+    for call in calls:
+        with pytest.raises(st.StbaError) as ex:
+            call()
+        assert ex.value.code == -1 and "ITERATIVE_SCHUR" in str(ex.value), str(ex.value)      # STBA_ERR_INVALID_ARGUMENT
+        after = e.get_params()
+        assert np.array_equal(after[0], before[0]) and np.array_equal(after[1], before[1])
+    d = engine(st, s, "dense_schur")
+    with pytest.raises(st.StbaError):
+        d.set_pcg("jacobi")
+    with pytest.raises(st.StbaError):
+        e.set_pcg("jacobi", eta=0.1, min_iterations=5, max_iterations=4)
+
+
+def test_beyond_the_direct_path(st, sc):
+    import torch
+    t0 = time.time()
+    nc = 50000
+    s = sc.large_ba_scene(n_cams=nc, n_pts=500000, views_per_pt=10, seed=1)
+    total = torch.cuda.get_device_properties(0).total_memory
+    assert 8 * (6 * nc) ** 2 > total, "the direct path's S would fit this device"
+    e = engine(st, s)
+    e.set_pcg("schur_jacobi", eta=0.1, max_iterations=500)
+    summ, tr = e.solve(st.default_options(max_num_iterations=50))
+    cams, pts = e.get_params()
+    dt = time.time() - t0
+    err_c = np.abs(cams[:, 4:] - s["cams_true"][:, 4:]).max()
+    err_p = np.abs(pts - s["pts_true"]).max()
+    print(f"ITERATIVE 50k cameras: {summ.num_iterations} LM iterations, {e.pcg_summary().iterations_total} PCG iterations, "
+          f"cost {summ.initial_cost:.3e} -> {summ.final_cost:.3e}, centre err {err_c:.2e}, landmark err {err_p:.2e}, {dt:.1f} s in all")
+    assert summ.termination_type == 0, summ.as_dict()
+    assert err_c < 1e-6 and err_p < 1e-6
+    assert dt < 120.0
