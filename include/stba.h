@@ -507,6 +507,30 @@ int stba_ba_schur_apply(stba_ba* ba, const double* dc, const double* dp, int whi
  * over `reps` back-to-back products, with the blocks and the x of the last stba_ba_schur_apply */
 int stba_ba_time_schur_apply(stba_ba* ba, int reps, double* ms_avg);
 
+/* ================================ bundle adjustment: DOGLEG ================================ */
+/* Ceres' trust_region_strategy_type = DOGLEG, dogleg_type = TRADITIONAL_DOGLEG (Powell's dogleg).  The reduced camera system is
+ * built and factored ONCE per linearisation, at a small regularisation mu (1e-8, raised tenfold while a pivot fails and lowered
+ * after every accepted step); the Gauss-Newton and the Cauchy step are kept, and a rejected step only halves the radius and mixes
+ * the two again -- no Schur build, no factorisation, no back-substitution.  Same Jacobi scaling, LM diagonal bounds, constant dofs,
+ * tolerances and trace as the LM loop; the trace's radius column and stba_lm_summary::final_radius carry the dogleg radius.
+ * stba_ba_solve follows the engine's strategy; stba_ba_lm_iterations (the benchmark's unit) always runs LM.  DESIGN.md 7c.
+ * Refused with STBA_ERR_INVALID_ARGUMENT, the state untouched: DOGLEG on an ITERATIVE_SCHUR engine (Ceres: "DOGLEG only supports
+ * exact factorization based linear solvers"), DOGLEG on an engine with an all-reduce hook or communicator, stba_ba_set_allreduce /
+ * stba_ba_set_comm on a DOGLEG engine (one rank only), an unknown strategy.  STBA_VERSION is unchanged: test for the symbols. */
+enum { STBA_TR_LEVENBERG_MARQUARDT = 0, STBA_TR_TRADITIONAL_DOGLEG = 1 };
+int stba_ba_set_trust_region(stba_ba* ba, int strategy);      /* default LM; stba_ba_solve follows it */
+typedef struct {
+    size_t struct_size;          /* sizeof(stba_dogleg_summary); fields behind struct_size are not written */
+    int    factorizations;       /* factorisations of the reduced system (one per linearisation, plus one per mu escalation) */
+    int    gauss_newton_solves;  /* Gauss-Newton steps computed (each behind a factorisation) */
+    int    reused_steps;         /* steps that re-used the directions of the linearisation (every step behind a rejection) */
+    int    invalid_steps;        /* steps without a valid Gauss-Newton step or with a model change that is not positive */
+    int    steps_by_case[3];     /* trial steps: [0] the Gauss-Newton step, [1] the Cauchy step cut at the radius, [2] interpolated */
+    double final_mu;             /* mu at the end of the solve */
+} stba_dogleg_summary;
+/* the last stba_ba_solve of this engine (all zero if it ran LM) */
+int stba_ba_last_dogleg_summary(stba_ba* ba, stba_dogleg_summary* out);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

@@ -114,6 +114,12 @@ enum LinearSolverType { DENSE_NORMAL_CHOLESKY, DENSE_QR, SPARSE_NORMAL_CHOLESKY,
 // in Summary::message and on stderr, parameters untouched).  Every other linear_solver_type, and every problem that is not BA-shaped,
 // takes the paths it always took.
 enum PreconditionerType { IDENTITY, JACOBI, SCHUR_JACOBI, CLUSTER_JACOBI, CLUSTER_TRIDIAGONAL, SUBSET };
+// DOGLEG (TRADITIONAL_DOGLEG) on the "gpu-ba" / "gpu-ba-hostjac" paths with the dense Schur solver: Powell's dogleg, one factorisation
+// per linearisation (stba_ba_set_trust_region).  Refused before any device work (FAILURE, the reason in Summary::message
+// and on stderr, parameters untouched): SUBSPACE_DOGLEG, DOGLEG with ITERATIVE_SCHUR (Ceres' own rule), and DOGLEG on a problem that
+// takes "gpu-pg" or "gpu-dense-callback".
+enum TrustRegionStrategyType { LEVENBERG_MARQUARDT, DOGLEG };
+enum DoglegType { TRADITIONAL_DOGLEG, SUBSPACE_DOGLEG };
 enum CallbackReturnType { SOLVER_CONTINUE, SOLVER_ABORT, SOLVER_TERMINATE_SUCCESSFULLY };
 enum TerminationType { CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_FAILURE };
 enum Ownership { DO_NOT_TAKE_OWNERSHIP, TAKE_OWNERSHIP };
@@ -648,6 +654,8 @@ public:
         int num_threads = 1;
         LinearSolverType linear_solver_type = SPARSE_NORMAL_CHOLESKY;
         PreconditionerType preconditioner_type = JACOBI;          // Ceres' defaults for the iterative linear solver
+        TrustRegionStrategyType trust_region_strategy_type = LEVENBERG_MARQUARDT;
+        DoglegType dogleg_type = TRADITIONAL_DOGLEG;
         double eta = 1e-1;
         int min_linear_solver_iterations = 0, max_linear_solver_iterations = 500;
         bool minimizer_progress_to_stdout = false;
@@ -673,6 +681,9 @@ public:
         int num_successful_steps = 0, num_unsuccessful_steps = 0;
         // ITERATIVE_SCHUR on a BA path; 0 (DENSE_NORMAL_CHOLESKY's value) on every other path, which this field does not describe
         LinearSolverType linear_solver_type_used = static_cast<LinearSolverType>(0);
+        // the strategy that ran: DOGLEG / TRADITIONAL_DOGLEG where a BA path ran it, LEVENBERG_MARQUARDT on every other path
+        TrustRegionStrategyType trust_region_strategy_type = LEVENBERG_MARQUARDT;
+        DoglegType dogleg_type = TRADITIONAL_DOGLEG;
         std::vector<IterationSummary> iterations;
         std::string execution_path;   // "gpu-ba" | "gpu-ba-hostjac" | "gpu-pg" | "gpu-dense-callback"
         std::string BriefReport() const {
@@ -1120,6 +1131,12 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
         stba_ba_destroy(sync.ba);
         return false;
     }
+    const bool dogleg = o.trust_region_strategy_type == DOGLEG;
+    if (dogleg && (rc = stba_ba_set_trust_region(sync.ba, STBA_TR_TRADITIONAL_DOGLEG)) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_trust_region: ") + stba_last_error();
+        stba_ba_destroy(sync.ba);
+        return false;
+    }
     stba_lm_options co = ToC(o);
     stba_lm_summary cs;
     std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
@@ -1129,6 +1146,7 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     if (rc == STBA_OK) {
         BaCopyOut(&sync);   // parameters are updated in place, like ceres::Solve
         FillSummary(cs, trace, sum);
+        if (dogleg) { sum->trust_region_strategy_type = DOGLEG; sum->dogleg_type = TRADITIONAL_DOGLEG; }
         if (iterative) {
             sum->linear_solver_type_used = ITERATIVE_SCHUR;
             std::vector<int> its((size_t)cs.num_iterations, 0);
@@ -1351,6 +1369,21 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
                            "not implemented by this layer (the reference passes nullptr: test_ceres.h:120) -- nothing was solved.";
         std::fprintf(stderr, "%s\n", summary->message.c_str());
         return;
+    }
+    if (options.trust_region_strategy_type == DOGLEG) {
+        // (refused like a LossFunction: before any device work, parameters untouched)
+        const char* why = nullptr;
+        BaLayout shape_only;
+        if (options.dogleg_type != TRADITIONAL_DOGLEG) why = "SUBSPACE_DOGLEG is not implemented by this layer (TRADITIONAL_DOGLEG is)";
+        else if (options.linear_solver_type == ITERATIVE_SCHUR) why = "DOGLEG only supports exact factorization based linear solvers, not ITERATIVE_SCHUR";
+        else if (!DetectBa(*problem, &shape_only, false))
+            why = "DOGLEG is implemented for bundle adjustment (gpu-ba, gpu-ba-hostjac) only, not for problems that take gpu-pg or gpu-dense-callback";
+        if (why) {
+            summary->termination_type = FAILURE;
+            summary->message = std::string("stba_ceres: ") + why + " -- nothing was solved.";
+            std::fprintf(stderr, "%s\n", summary->message.c_str());
+            return;
+        }
     }
     BaLayout L;
     // CONTRACT of the recognition (DetectBa): a user cost function is replaced by the built-in device factor if

@@ -78,7 +78,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_covariance_compute", "stba_ba_camera_covariance", "stba_ba_point_covariance", "stba_ba_covariance_release",
            "stba_dense_covariance",
            "stba_ba_create_ex", "stba_ba_set_pcg", "stba_ba_last_pcg_summary", "stba_ba_schur_apply",
-           "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply"]
+           "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply",
+           "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary"]
 
 
 def lib():
@@ -169,7 +170,18 @@ class BACreateOptions(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("linear_solver", C.c_int)]
 
 
+class DoglegSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("factorizations", C.c_int), ("gauss_newton_solves", C.c_int), ("reused_steps", C.c_int),
+                ("invalid_steps", C.c_int), ("steps_by_case", C.c_int * 3), ("final_mu", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "steps_by_case"}
+        d["steps_by_case"] = list(self.steps_by_case)
+        return d
+
+
 LINEAR_SOLVERS = {"dense_schur": 0, "iterative_schur": 1}
+TRUST_REGIONS = {"lm": 0, "dogleg": 1}
 PRECONDITIONERS = {"identity": 0, "jacobi": 1, "schur_jacobi": 2}
 
 
@@ -385,6 +397,22 @@ class BAEngine:
         out = np.zeros(int(n), dtype=np.int32)
         _chk(lib().stba_ba_last_pcg_iterations(self._h, _p(out), int(n)), "stba_ba_last_pcg_iterations")
         return out
+
+    # ---- trust-region strategy
+    def set_trust_region(self, strategy):
+        """"lm" (Levenberg-Marquardt, the default) | "dogleg" (Powell's dogleg, Ceres' TRADITIONAL_DOGLEG): what solve() runs
+        (stba_ba_set_trust_region; lm_iterations always runs LM).  DOGLEG needs the dense Schur solver and one rank."""
+        if isinstance(strategy, str) and strategy not in TRUST_REGIONS:
+            raise ValueError(f"trust region strategy must be one of {sorted(TRUST_REGIONS)}, not {strategy!r}")
+        code = TRUST_REGIONS[strategy] if isinstance(strategy, str) else int(strategy)
+        _chk(lib().stba_ba_set_trust_region(self._h, code), "stba_ba_set_trust_region")
+
+    def dogleg_summary(self):
+        """factorisations, Gauss-Newton solves, re-used and invalid steps, steps per case and the final mu of the last solve"""
+        s = DoglegSummary()
+        s.struct_size = C.sizeof(DoglegSummary)
+        _chk(lib().stba_ba_last_dogleg_summary(self._h, C.byref(s)), "stba_ba_last_dogleg_summary")
+        return s
 
     def time_schur_apply(self, reps=20):
         """ms per implicit product S x on the device (hipEvents), with the blocks and x of the last schur_apply"""

@@ -50,6 +50,32 @@ struct TrustRegion {
     bool below_min(const stba_lm_options& o) const { return radius < o.min_trust_region_radius; }
 };
 
+// DoglegStrategy's state (TRADITIONAL_DOGLEG): the radius Delta, which lives in the dogleg coordinates z = d .* y,
+// the regularisation mu of the Gauss-Newton solve (J^T J + mu diag(d^2)) y_gn = -g, which persists across iterations, and whether
+// the next step re-uses the directions of this linearisation
+struct DoglegRegion {
+    static constexpr double kMinMu = 1e-8, kMaxMu = 1.0, kMuIncrease = 10.0;
+    double radius, mu = kMinMu;
+    bool reuse = false;
+    explicit DoglegRegion(const stba_lm_options& o) : radius(o.initial_trust_region_radius) {}
+    // z_norm: |z| of the accepted step
+    void accept(double rho, double z_norm, const stba_lm_options& o) {
+        if (rho > 0.75) radius = std::max(radius, 3.0 * z_norm);
+        else if (rho < 0.25) radius *= 0.5;
+        radius = std::min(o.max_trust_region_radius, radius);
+        mu = std::max(kMinMu, 2.0 * mu / kMuIncrease);
+        reuse = false;
+    }
+    void reject() { radius *= 0.5; reuse = true; }
+    // a step that is not valid: no Gauss-Newton step at any mu, or a model change that is not positive and finite
+    void invalid() { mu *= kMuIncrease; reuse = false; }
+    // the factorisation failed (a pivot that is not positive, or a Gauss-Newton step that is not finite): true if it runs again
+    // at the larger mu, false if no mu below kMaxMu is left (the step is invalid)
+    bool escalate() { mu *= kMuIncrease; return mu < kMaxMu; }
+    bool can_factor() const { return mu < kMaxMu; }
+    bool below_min(const stba_lm_options& o) const { return radius < o.min_trust_region_radius; }
+};
+
 struct StepVerdict {
     double cost_change = 0.0, rho = 0.0;
     bool accepted = false;       // (also on a function-tolerance stop that takes the step)

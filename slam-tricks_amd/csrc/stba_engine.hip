@@ -13,6 +13,7 @@
 
 #include "ba_kernels.hpp"
 #include "iterative_schur.hpp"
+#include "dogleg.hpp"
 #include "lm_policy.hpp"
 
 namespace stba {
@@ -150,6 +151,13 @@ struct stba_ba {
     double pcg_seq = 0.0;
     int pcg_last_it = 0, pcg_last_cap = 0;     // the last solve, counted into pcg_sum once the LM loop keeps its step
     std::vector<int> pcg_per_iter;             // PCG iterations of every LM iteration of the last solve (1, 2, ...)
+    // DOGLEG (stba_ba_set_trust_region; dogleg.hip): s .* u of cameras and landmarks, the terms kernel's partials, the six scalars,
+    // the step's stamped block for the host; the summary of the last solve
+    int trust_region = STBA_TR_LEVENBERG_MARQUARDT;
+    double *dl_uc = nullptr, *dl_up = nullptr, *dl_part = nullptr, *dl_sc = nullptr;
+    MappedBuffer dl_host;
+    double dl_seq = 0.0;
+    stba_dogleg_summary dl_sum{};
 
     size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
     double* S() const { return iterative ? nullptr : Sbuf; }
@@ -188,6 +196,8 @@ static void ba_free(stba_ba* b) {
     F(b->cost_partial); F(b->upd_partial_c); F(b->upd_partial_p); F(b->trial); F(b->flag);
     F(b->pcg_vec); F(b->pcg_minv); F(b->pcg_sj); F(b->pcg_part); F(b->pcg_state);
     b->pcg_host.release();
+    F(b->dl_uc); F(b->dl_up); F(b->dl_part); F(b->dl_sc);
+    b->dl_host.release();
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
     b->ts_host.release();
@@ -969,6 +979,243 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     s.ms_allreduce = b->ar_ms; s.allreduce_bytes = b->ar_bytes; s.allreduce_calls = b->ar_calls;
     finish_summary(&s, iter, cost, region.radius, gmax, t_start);
     b->pcg_sum.linear_solve_ms = b->iterative ? s.ms_solve : 0.0;
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    if (sum) *sum = s;
+    return STBA_OK;
+}
+
+// ---- DOGLEG (Ceres' TrustRegionMinimizer + DoglegStrategy, TRADITIONAL_DOGLEG).  One rank, the dense Schur path.
+// Per linearisation: the reduced system at radius 1/mu (ba_build), the persistent Cholesky, the Gauss-Newton back-substitution and
+// the terms kernel.  Per trial step: the step kernel at Delta and the trial evaluation, whose stamped block is the host's one wait;
+// a rejected step is nothing else.  No speculative linearisation: a rejection re-uses the linearisation, which a speculation at the
+// trial point would have overwritten.  The cost and |g|max of a new linearisation arrive with its first trial block (as in
+// ba_run_lm), unless somebody watches the iterations.
+static int ba_dogleg_alloc(stba_ba* b) {
+    if (b->dl_sc) return STBA_OK;
+    STBA_TRY(dev_alloc(&b->dl_uc, (size_t)std::max(b->n, 1)));
+    STBA_TRY(dev_alloc(&b->dl_up, (size_t)std::max(b->np, 1) * 3));
+    STBA_TRY(dev_alloc(&b->dl_part, dogleg_partial_doubles(b->nc, b->np)));
+    STBA_TRY(dev_alloc(&b->dl_sc, 8));
+    return b->dl_host.alloc((size_t)stamped_doubles(DL_BLOCK));
+}
+
+// the Gauss-Newton side of a linearisation: factor, back-substitute, the six scalars (the reduced system is built)
+static int ba_dogleg_gauss_newton(stba_ba* b, const Damping& dm) {
+    STBA_TRY(chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st));
+    STBA_TRY(launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, nullptr,
+                            b->hl_fn ? b->Jc12 : nullptr));
+    DoglegArgs a;
+    a.n_cams = b->nc; a.n_pts = b->np;
+    a.pt_start = b->pt_start; a.obs_cam = b->obs_cam; a.obs_pt = b->obs_pt;
+    a.J8 = b->J8; a.omask = b->omask; a.Jc12 = b->hl_fn ? b->Jc12 : nullptr;
+    a.cam_fixed = b->cam_fixed; a.pt_fixed = b->pt_fixed;
+    a.hc = b->ex_diag(); a.gc = b->ex_gc(); a.scale_c = b->scale_c;
+    a.Hpp6 = b->Hpp6; a.gp = b->gp; a.scale_p = b->scale_p;
+    a.dmin = dm.dmin; a.dmax = dm.dmax;
+    a.dxc = b->dxc; a.dxp = b->dxp; a.uc = b->dl_uc; a.up = b->dl_up;
+    a.partial = b->dl_part; a.scalars = b->dl_sc;
+    return launch_dogleg_terms(a, b->st);
+}
+
+static int ba_dogleg_step(stba_ba* b, double radius, double seq) {
+    DoglegStepArgs a;
+    a.n_cams = b->nc; a.n_pts = b->np;
+    a.scalars = b->dl_sc; a.uc = b->dl_uc; a.up = b->dl_up; a.dxc = b->dxc; a.dxp = b->dxp;
+    a.cams = b->cams[b->cur]; a.pts = b->pts[b->cur]; a.cam_fixed = b->cam_fixed; a.pt_fixed = b->pt_fixed;
+    a.cams_new = b->cams[b->cur ^ 1]; a.pts_new = b->pts[b->cur ^ 1];
+    a.partial_c = b->upd_partial_c; a.partial_p = b->upd_partial_p;
+    a.host_out = b->dl_host.dev; a.seq = seq;
+    return launch_dogleg_step(a, radius, b->st);
+}
+
+constexpr int kMaxConsecutiveInvalidSteps = 5;      // Ceres' Solver::Options::max_num_consecutive_invalid_steps
+
+static int ba_run_dogleg(stba_ba* b, const stba_lm_options* opt_in, stba_lm_summary* sum, double* trace, stba_iteration_callback cb,
+                         void* cb_user) {
+    stba_lm_options opt;
+    if (opt_in) opt = *opt_in; else default_options(&opt);
+    stba_lm_summary s;
+    memset(&s, 0, sizeof s);
+    const double t_start = wall_s();
+    const int max_iter = opt.max_num_iterations;
+    STBA_TRY(ba_dogleg_alloc(b));
+    if (!b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
+    b->scale_init = false;
+    b->ar_ms = 0.0; b->ar_bytes = 0.0; b->ar_calls = 0; b->ar_timing_pending = false; b->ar_timing_on = false;
+    memset(&b->pcg_sum, 0, sizeof b->pcg_sum);
+    b->pcg_per_iter.clear();
+    stba_dogleg_summary ds{};
+    ds.struct_size = sizeof ds;
+    Damping dm;
+    dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
+    DoglegRegion region(opt);
+    double cost = 0.0, gmax = 0.0;
+
+    STBA_TRY(ba_linearize_lm(b, b->cur));
+    STBA_TRY(ba_normal_blocks(b));
+    STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
+    const bool deferred_ok = (cb == nullptr) && !opt.minimizer_progress_to_stdout;
+    bool need_build = true, need_gn = true, first = true, pending = false, pending_accepted = false;
+    int pending_iter = 0, iter = 0, chol_timeouts = 0, invalid_in_a_row = 0;
+    s.termination_type = STBA_NO_CONVERGENCE;
+    s.termination_reason = STBA_TERM_MAX_ITER;
+    double hd[DL_BLOCK] = {0.0};
+
+    while (true) {
+        if (!first) {
+            if (iter >= max_iter) break;
+            if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
+        }
+        if (need_build) {
+            dm.radius = 1.0 / region.mu;
+            STBA_TRY(ba_build(b, dm));
+            need_build = false;
+        }
+        if (first) {
+            STBA_TRY(ba_read_linear_scalars(b, &cost, &gmax));
+            s.initial_cost = cost;
+            trace_start(trace, cost, gmax, region.radius);
+            first = false;
+            if (opt.minimizer_progress_to_stdout) progress_start(cost, gmax, region.radius);
+            if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; break; }
+            if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
+            if (max_iter <= 0) break;
+        }
+        ++iter;
+        // ---- the Gauss-Newton side, once per linearisation (and per mu escalation); mu >= 1: no solve, the step is invalid
+        bool have_gn = true, reused = !need_gn;
+        if (need_gn) {
+            if (region.can_factor()) {
+                STBA_TRY(ba_dogleg_gauss_newton(b, dm));
+                ++ds.factorizations; ++ds.gauss_newton_solves;
+                need_gn = false;
+            } else have_gn = false;
+        }
+        int flag_h = 0;
+        const double* ts = b->ts_vals;
+        if (have_gn) {
+            // ---- the trial step: the step kernel at Delta and the trial evaluation, read through the trial block (the one wait)
+            const double dseq = (b->dl_seq += 1.0), seq = (b->ts_seq += 1.0);
+            STBA_TRY(ba_dogleg_step(b, region.radius, dseq));
+            STBA_TRY(ba_trial(b, b->ts_host.dev, true, false, seq));
+            STBA_TRY(stamped_wait(b->ts_host.host, TS_BLOCK, [seq](double x) { return x == seq; }, b->ts_vals, hip_stream_state(b->st),
+                                  "trial point", 120.0));
+            // (the step kernel wrote its block before the trial evaluation began: it is there)
+            STBA_TRY(stamped_wait(b->dl_host.host, DL_BLOCK, [dseq](double x) { return x == dseq; }, hd, hip_stream_state(b->st),
+                                  "dogleg step", 120.0));
+            flag_h = (int)ts[TS_SPEC_COST2];
+            if (flag_h == CHOL_FLAG_TIMEOUT) {
+                // the persistent factorisation gave up (the device is shared): S is rebuilt and factored again through the stage
+                // kernels, as in ba_run_lm
+                chol_note_timeout();
+                if (++chol_timeouts > 8) return fail(STBA_ERR_HIP, "dense Cholesky: the persistent program timed out repeatedly");
+                --ds.factorizations; --ds.gauss_newton_solves;
+                need_build = need_gn = true;
+                --iter;
+                continue;
+            }
+            chol_timeouts = 0;
+            if (pending) {
+                // cost and |g|max of the linearisation behind the previous iteration (trial_finish_kernel read them on the way)
+                gmax = ts[TS_LIN_GMAX];
+                if (pending_accepted) cost = 0.5 * ts[TS_LIN_COST2];
+                if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = gmax;
+                pending = false;
+                if (pending_accepted && gmax <= opt.gradient_tolerance) {
+                    --iter;           // converged at the previous iteration: this trial step is discarded
+                    s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
+                    break;
+                }
+            }
+            if (flag_h != 0 || (int)hd[DL_KASE] == DOGLEG_INVALID_GN) {
+                // no Gauss-Newton step at this mu: the same linearisation again at 10 mu
+                if (region.escalate()) { need_build = need_gn = true; --iter; continue; }
+                have_gn = false;
+            }
+        }
+        const double new_cost = have_gn ? 0.5 * ts[TS_COST2] : cost;
+        const double step_norm = have_gn ? std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]) : 0.0;
+        const double x_norm = have_gn ? std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]) : 0.0;
+        const double model_change = have_gn ? ts[TS_MODEL] + ts[TS_CAM + 2] : 0.0;
+        // a step without a Gauss-Newton step, or whose model change is not positive and finite, is invalid; a trial point whose cost
+        // is not finite is rejected.  Neither is judged (row [cost, 0, ., 0, 0], no stop test).
+        const bool valid = have_gn && model_change > 0.0 && std::isfinite(model_change);
+        const bool step_ok = valid && std::isfinite(new_cost);
+        if (have_gn) {
+            const int kase = (int)hd[DL_KASE];
+            if (kase >= 0 && kase < 3) ++ds.steps_by_case[kase];
+            if (reused) ++ds.reused_steps;
+        }
+        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, true);
+        const bool accepted = v.accepted;
+        if (accepted) {
+            b->cur ^= 1;
+            cost = new_cost;
+            ++s.num_successful_steps;
+        }
+        trace_step(trace, iter, step_ok, cost, new_cost, v, gmax, step_norm, region.radius);
+        if (v.stop) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
+            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0);
+            break;
+        }
+        if (accepted) region.accept(v.rho, hd[DL_ZNORM], opt);
+        else {
+            ++s.num_unsuccessful_steps;
+            if (!valid) { region.invalid(); ++ds.invalid_steps; need_build = need_gn = true; }
+            else region.reject();
+        }
+        invalid_in_a_row = valid ? 0 : invalid_in_a_row + 1;
+        if (invalid_in_a_row >= kMaxConsecutiveInvalidSteps) {
+            // Ceres' max_num_consecutive_invalid_steps (5): mu has only grown, and nothing lowers it but an accepted step
+            s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL;
+            break;
+        }
+        if (accepted) {
+            // a new linearisation: the next iteration builds and factors it at the new mu
+            STBA_TRY(ba_linearize_lm(b, b->cur));
+            STBA_TRY(ba_normal_blocks(b));
+            STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
+            need_build = need_gn = true;
+            if (deferred_ok) {
+                pending = true; pending_accepted = true; pending_iter = iter;
+            } else {
+                dm.radius = 1.0 / region.mu;
+                STBA_TRY(ba_build(b, dm));
+                need_build = false;
+                double c2, g2;
+                STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
+                gmax = g2;
+                cost = c2;
+            }
+        }
+        if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
+        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
+        if (cb && cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0) != 0) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER;
+            break;
+        }
+        if (!pending && accepted && gmax <= opt.gradient_tolerance) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
+            break;
+        }
+    }
+    STBA_HIP(hipStreamSynchronize(b->st));
+    if (pending) {      // the loop ended (iteration / radius limit) before the last linearisation's scalars were read
+        double c2, g2;
+        if (need_build) { dm.radius = 1.0 / region.mu; STBA_TRY(ba_build(b, dm)); }
+        STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
+        gmax = g2;
+        cost = c2;
+        if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
+        if (g2 <= opt.gradient_tolerance &&
+            (s.termination_reason == STBA_TERM_MAX_ITER || s.termination_reason == STBA_TERM_MIN_RADIUS)) {
+            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
+        }
+    }
+    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
+    ds.final_mu = region.mu;
+    b->dl_sum = ds;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     if (sum) *sum = s;
     return STBA_OK;
@@ -1773,6 +2020,8 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
 
 int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank, int world_size) {
     STBA_TRY(refuse_iterative(b, "stba_ba_set_allreduce", "which runs on one rank only"));
+    if (b && b->trust_region == STBA_TR_TRADITIONAL_DOGLEG)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine uses DOGLEG, which runs on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -1930,7 +2179,34 @@ int stba_ba_apply_step(stba_ba* b, int accept, double* new_cost) {
 int stba_ba_solve(stba_ba* b, const stba_lm_options* opt, stba_lm_summary* summary, double* trace,
                   stba_iteration_callback cb, void* cb_user) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    b->dl_sum = stba_dogleg_summary{};
+    if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return ba_run_dogleg(b, opt, summary, trace, cb, cb_user);
     return ba_run_lm(b, opt, 0, summary, trace, cb, cb_user);
+}
+
+int stba_ba_set_trust_region(stba_ba* b, int strategy) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (strategy != STBA_TR_LEVENBERG_MARQUARDT && strategy != STBA_TR_TRADITIONAL_DOGLEG)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: unknown strategy " + std::to_string(strategy));
+    if (strategy == STBA_TR_TRADITIONAL_DOGLEG) {
+        if (b->iterative)
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG only supports exact factorization based linear solvers "
+                        "(this engine uses ITERATIVE_SCHUR)");
+        if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG runs on one rank only (an all-reduce hook is set)");
+    }
+    b->trust_region = strategy;
+    return STBA_OK;
+}
+
+int stba_ba_last_dogleg_summary(stba_ba* b, stba_dogleg_summary* out) {
+    if (!b || !out) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t want = out->struct_size;
+    if (want < offsetof(stba_dogleg_summary, factorizations) + sizeof(int))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_last_dogleg_summary: out->struct_size is smaller than any version of the struct");
+    stba_dogleg_summary s = b->dl_sum;
+    s.struct_size = want;
+    memcpy(out, &s, std::min(want, sizeof s));
+    return STBA_OK;
 }
 
 int stba_ba_lm_iterations(stba_ba* b, const stba_lm_options* opt, int iterations, stba_lm_summary* summary,
