@@ -531,6 +531,40 @@ typedef struct {
 /* the last stba_ba_solve of this engine (all zero if it ran LM) */
 int stba_ba_last_dogleg_summary(stba_ba* ba, stba_dogleg_summary* out);
 
+/* ================================ bundle adjustment: inner iterations ================================ */
+/* Ceres' Solver::Options::use_inner_iterations: after every valid trust-region step of stba_ba_solve / stba_ba_lm_iterations (LM,
+ * dense Schur or ITERATIVE_SCHUR), one coordinate-descent sweep moves the trial point x+ to x*: the groups of the ordering in
+ * ascending id, every block of a group solved on its own -- all other blocks held fixed -- by a Levenberg-Marquardt solve with
+ * Ceres' DEFAULT options over the residuals that touch it.  The model cost change grows by cost(x+) - cost(x*), the step is
+ * accepted if cost(x*) < cost(x) or rho > min_relative_decrease, and the trace / callback report x*.  Once a sweep improves the
+ * trial cost by a relative 1 - cost(x*) / cost(x+) <= tolerance, sweeps stop for the rest of the solve.  DESIGN.md 7d.
+ * Blocks: a camera's rotation (dofs 0..2) and position (dofs 3..5), and every landmark.  cam_rot_group[n_cams], cam_pos_group[n_cams],
+ * pt_group[n_pts]: the group id of each (>= 0), -1 = not swept (held fixed by the sweeps); equal rotation and position ids make the
+ * camera ONE 6-dof block.  All three NULL: the default ordering {cameras as 6-dof blocks}, {landmarks}; one NULL among the others:
+ * none of that kind is swept.  Constant blocks (every dof of the part constant) are ignored.
+ * Refused with STBA_ERR_INVALID_ARGUMENT (stba_last_error names the offending pair), the state untouched: a group that is not an
+ * independent set (a camera and a landmark it observes), a negative tolerance, an engine with an all-reduce hook or communicator or a
+ * host lineariser (and those setters on an engine with inner iterations).  stba_ba_solve on a DOGLEG engine with inner iterations:
+ * STBA_ERR_INVALID_ARGUMENT before any device work.  enable = 0: off (exactly the engine that never enabled them).
+ * STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_inner_iterations(stba_ba* ba, int enable, double tolerance, const int* cam_rot_group, const int* cam_pos_group,
+                                 const int* pt_group);
+/* one sweep at the current point (the ordering set above, or the default one), which moves the engine's parameters.
+ * iterations_per_block (nullable) [2 n_cams + n_pts]: the inner LM iterations (trust-region steps) of every rotation block, then
+ * every position block, then every landmark, in the caller's order; a 6-dof camera block reports its count in both entries, a
+ * block that is not swept 0.  cost_before / cost_after (nullable): 1/2 |r|^2 before and after the sweep. */
+int stba_ba_inner_sweep(stba_ba* ba, double* cost_before, double* cost_after, int* iterations_per_block);
+#define STBA_INNER_MAX_GROUPS_REPORTED 16
+typedef struct {
+    size_t struct_size;          /* sizeof(stba_inner_summary); fields behind struct_size are not written */
+    int    sweeps;               /* sweeps run by the last solve (or by the last stba_ba_inner_sweep) */
+    int    disabled_at_iteration;/* the iteration whose sweep switched inner iterations off, or -1 */
+    double sweep_ms;             /* device time of the sweeps (stba_lm_options::phase_timing; else 0) */
+    int    num_groups;           /* groups of the ordering used */
+    int    group_size[STBA_INNER_MAX_GROUPS_REPORTED];   /* blocks of every group, ascending id (the first 16) */
+} stba_inner_summary;
+int stba_ba_last_inner_summary(stba_ba* ba, stba_inner_summary* out);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

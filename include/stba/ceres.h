@@ -645,6 +645,65 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------
+// ParameterBlockOrdering (Ceres' OrderedGroups<double*>): parameter blocks in groups with integer ids >= 0, the order of the
+// inner iterations' sweep (Solver::Options::inner_iteration_ordering)
+// ------------------------------------------------------------------------------------------
+class ParameterBlockOrdering {
+public:
+    bool AddElementToGroup(double* element, int group) {
+        if (group < 0) return false;
+        auto it = element_to_group_.find(element);
+        if (it != element_to_group_.end()) {
+            if (it->second == group) return true;
+            Erase(element, it->second);
+        }
+        element_to_group_[element] = group;
+        group_to_elements_[group].insert(element);
+        return true;
+    }
+    int Remove(double* element) {
+        auto it = element_to_group_.find(element);
+        if (it == element_to_group_.end()) return 0;
+        Erase(element, it->second);
+        element_to_group_.erase(element);
+        return 1;
+    }
+    bool IsMember(double* element) const { return element_to_group_.count(element) != 0; }
+    int GroupId(double* element) const {
+        auto it = element_to_group_.find(element);
+        return it == element_to_group_.end() ? -1 : it->second;
+    }
+    int NumElements() const { return (int)element_to_group_.size(); }
+    int NumGroups() const { return (int)group_to_elements_.size(); }
+    int GroupSize(int group) const {
+        auto it = group_to_elements_.find(group);
+        return it == group_to_elements_.end() ? 0 : (int)it->second.size();
+    }
+    // Ceres' Reverse: the last group keeps its id, the others follow it in reverse order with ids one larger each
+    void Reverse() {
+        if (group_to_elements_.empty()) return;
+        auto it = group_to_elements_.rbegin();
+        std::map<int, std::set<double*>> out;
+        out[it->first] = it->second;
+        int id = it->first + 1;
+        for (++it; it != group_to_elements_.rend(); ++it, ++id)
+            for (double* e : it->second) { out[id].insert(e); element_to_group_[e] = id; }
+        group_to_elements_.swap(out);
+    }
+    void Clear() { element_to_group_.clear(); group_to_elements_.clear(); }
+    const std::map<int, std::set<double*>>& group_to_elements() const { return group_to_elements_; }
+
+private:
+    void Erase(double* element, int group) {
+        auto g = group_to_elements_.find(group);
+        g->second.erase(element);
+        if (g->second.empty()) group_to_elements_.erase(g);
+    }
+    std::map<double*, int> element_to_group_;
+    std::map<int, std::set<double*>> group_to_elements_;
+};
+
+// ------------------------------------------------------------------------------------------
 // Solver
 // ------------------------------------------------------------------------------------------
 class Solver {
@@ -666,6 +725,15 @@ public:
                function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
         bool jacobi_scaling = true;
         bool force_callback_path = false;   // (not in Ceres) never replace user cost functions by the built-in device factor: see Solve()
+        // inner iterations on the "gpu-ba" path: a coordinate-descent sweep behind every valid step.  Default ordering:
+        // {every rotation block}, {every position block}, {every landmark} -- Ceres' choice between rotations and positions for the
+        // first group depends on hash order; this is its deterministic instance.  Refused before any device work (FAILURE, the reason
+        // in Summary::message and on stderr, parameters untouched): with DOGLEG, a negative tolerance, an ordering whose group is not an
+        // independent set (a camera's rotation and position, or a camera part and a landmark it observes) or that names a pointer
+        // that is not a parameter block, and on problems that take "gpu-ba-hostjac", "gpu-pg" or "gpu-dense-callback".
+        bool use_inner_iterations = false;
+        double inner_iteration_tolerance = 1e-3;
+        std::shared_ptr<ParameterBlockOrdering> inner_iteration_ordering;
     };
     struct Summary {
         TerminationType termination_type = FAILURE;
@@ -686,6 +754,12 @@ public:
         DoglegType dogleg_type = TRADITIONAL_DOGLEG;
         std::vector<IterationSummary> iterations;
         std::string execution_path;   // "gpu-ba" | "gpu-ba-hostjac" | "gpu-pg" | "gpu-dense-callback"
+        // inner iterations: asked for / run; group sizes of the ordering given (empty: none) and of the one used (constant blocks
+        // left out); sweeps run; their device time (-1: no sweep ran)
+        bool inner_iterations_given = false, inner_iterations_used = false;
+        std::vector<int> inner_iteration_ordering_given, inner_iteration_ordering_used;
+        int num_inner_iteration_steps = -1;
+        double inner_iteration_time_in_seconds = -1.0;
         std::string BriefReport() const {
             char buf[512];
             const char* t = termination_type == CONVERGENCE ? "CONVERGENCE" : termination_type == NO_CONVERGENCE ? "NO_CONVERGENCE"
@@ -1052,8 +1126,63 @@ inline double WallSeconds() { return std::chrono::duration<double>(std::chrono::
 // HERE, on the calling thread, while a helper thread creates the device engine (regrouping, Schur plan, uploads: ~50 ms at 10^6
 // observations, next to ~35 ms of user Evaluate calls); the features it finds go to the engine afterwards (stba_ba_set_features).
 // *blocks_ok = false: a block is not the reprojection factor -- nothing was solved, the engine is gone, the caller goes on.
+// the inner iterations' ordering in the engine's terms (stba_ba_set_inner_iterations): a group id per camera rotation, camera position
+// and landmark (-1: not swept), and the sizes of the groups used (constant blocks left out)
+struct InnerGroups {
+    std::vector<int> rot, pos, pt;
+    std::vector<int> sizes_given, sizes_used;
+};
+
+// Solver::Options::inner_iteration_ordering (or the default one) -> *out; false with *why if the ordering is refused
+inline bool MakeInnerGroups(const Solver::Options& o, Problem& p, const BaLayout& L, InnerGroups* out, std::string* why) {
+    const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size();
+    out->rot.assign((size_t)nc, -1); out->pos.assign((size_t)nc, -1); out->pt.assign((size_t)np, -1);
+    out->sizes_given.clear(); out->sizes_used.clear();
+    const auto& blk = p.blocks();
+    if (!o.inner_iteration_ordering) {
+        std::fill(out->rot.begin(), out->rot.end(), 0); std::fill(out->pos.begin(), out->pos.end(), 1); std::fill(out->pt.begin(), out->pt.end(), 2);
+    } else {
+        std::unordered_map<const double*, std::pair<int, int>> where;    // block pointer -> (0 rotation | 1 position | 2 landmark, index)
+        for (int c = 0; c < nc; ++c) { where[blk[L.rot_block[c]].ptr] = {0, c}; where[blk[L.pos_block[c]].ptr] = {1, c}; }
+        for (int j = 0; j < np; ++j) where[blk[L.pt_block[j]].ptr] = {2, j};
+        for (const auto& g : o.inner_iteration_ordering->group_to_elements()) {
+            out->sizes_given.push_back((int)g.second.size());
+            for (double* e : g.second) {
+                auto it = where.find(e);
+                if (it == where.end()) { *why = "the inner iteration ordering names a pointer that is not a parameter block of the problem"; return false; }
+                (it->second.first == 0 ? out->rot : it->second.first == 1 ? out->pos : out->pt)[(size_t)it->second.second] = g.first;
+            }
+        }
+    }
+    for (int c = 0; c < nc; ++c) {           // (constant blocks are ignored)
+        if (blk[L.rot_block[c]].constant) out->rot[(size_t)c] = -1;
+        if (blk[L.pos_block[c]].constant) out->pos[(size_t)c] = -1;
+        if (out->rot[(size_t)c] >= 0 && out->rot[(size_t)c] == out->pos[(size_t)c]) {
+            *why = "inner iteration ordering: group " + std::to_string(out->rot[(size_t)c]) + " is not an independent set (the rotation and the "
+                   "position of camera " + std::to_string(c) + " share residuals)";
+            return false;
+        }
+    }
+    for (int j = 0; j < np; ++j) if (blk[L.pt_block[j]].constant) out->pt[(size_t)j] = -1;
+    for (size_t i = 0; i < L.obs_cam.size(); ++i) {
+        const int c = L.obs_cam[i], j = L.obs_pt[i], g = out->pt[(size_t)j];
+        if (g >= 0 && (g == out->rot[(size_t)c] || g == out->pos[(size_t)c])) {
+            *why = "inner iteration ordering: group " + std::to_string(g) + " is not an independent set (camera " + std::to_string(c) +
+                   " and landmark " + std::to_string(j) + " share a residual)";
+            return false;
+        }
+    }
+    std::map<int, int> used;
+    for (int v : out->rot) if (v >= 0) ++used[v];
+    for (int v : out->pos) if (v >= 0) ++used[v];
+    for (int v : out->pt) if (v >= 0) ++used[v];
+    for (const auto& u : used) out->sizes_used.push_back(u.second);
+    return true;
+}
+
 inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Solver::Summary* sum, bool host_jacobians = false,
-                    BaLayout* blocks_layout = nullptr, bool* blocks_ok = nullptr, std::thread* destroyer = nullptr) {
+                    BaLayout* blocks_layout = nullptr, bool* blocks_ok = nullptr, std::thread* destroyer = nullptr,
+                    const InnerGroups* inner = nullptr) {
     double t0 = WallSeconds();
     auto lap = [&](double* acc) { const double t1 = WallSeconds(); *acc += t1 - t0; t0 = t1; };
     const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
@@ -1137,7 +1266,14 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
         stba_ba_destroy(sync.ba);
         return false;
     }
+    if (inner && (rc = stba_ba_set_inner_iterations(sync.ba, 1, o.inner_iteration_tolerance, inner->rot.data(), inner->pos.data(),
+                                                    inner->pt.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_inner_iterations: ") + stba_last_error();
+        stba_ba_destroy(sync.ba);
+        return false;
+    }
     stba_lm_options co = ToC(o);
+    if (inner) co.phase_timing = 1;          // (the sweeps' device time for Summary::inner_iteration_time_in_seconds)
     stba_lm_summary cs;
     std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
     CallbackCtx ctx{&o, sum, &BaCopyOut, &sync};
@@ -1147,6 +1283,14 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
         BaCopyOut(&sync);   // parameters are updated in place, like ceres::Solve
         FillSummary(cs, trace, sum);
         if (dogleg) { sum->trust_region_strategy_type = DOGLEG; sum->dogleg_type = TRADITIONAL_DOGLEG; }
+        stba_inner_summary is{};
+        is.struct_size = sizeof is;
+        if (inner && stba_ba_last_inner_summary(sync.ba, &is) == STBA_OK) {
+            sum->inner_iterations_used = true;
+            sum->inner_iteration_ordering_used = inner->sizes_used;
+            sum->num_inner_iteration_steps = is.sweeps;
+            sum->inner_iteration_time_in_seconds = is.sweep_ms * 1e-3;
+        }
         if (iterative) {
             sum->linear_solver_type_used = ITERATIVE_SCHUR;
             std::vector<int> its((size_t)cs.num_iterations, 0);
@@ -1385,6 +1529,32 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
             return;
         }
     }
+    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
+    const bool force_cb = options.force_callback_path || (fe && *fe && *fe != '0');
+    summary->inner_iterations_given = options.use_inner_iterations;
+    InnerGroups inner;
+    if (options.use_inner_iterations) {
+        // (refused like a LossFunction: before any device work, parameters untouched)
+        std::string why;
+        BaLayout shape_only;
+        bool shape = DetectBa(*problem, &shape_only, false);
+        if (shape)
+            for (int rb : shape_only.rot_block) shape = shape && UsesQuaternionRightPlus(problem->blocks()[rb].local);
+        if (options.trust_region_strategy_type == DOGLEG) why = "inner iterations are not implemented with DOGLEG";
+        else if (!(options.inner_iteration_tolerance >= 0.0)) why = "inner_iteration_tolerance must be >= 0";
+        else if (!shape)
+            why = "inner iterations are implemented for bundle adjustment on the gpu-ba path only, not for problems that take gpu-pg or gpu-dense-callback";
+        else if (force_cb) why = "inner iterations are implemented on the gpu-ba path only, not on gpu-ba-hostjac (force_callback_path)";
+        else MakeInnerGroups(options, *problem, shape_only, &inner, &why);
+        if (options.inner_iteration_ordering)
+            for (const auto& g : options.inner_iteration_ordering->group_to_elements()) summary->inner_iteration_ordering_given.push_back((int)g.second.size());
+        if (!why.empty()) {
+            summary->termination_type = FAILURE;
+            summary->message = "stba_ceres: " + why + " -- nothing was solved.";
+            std::fprintf(stderr, "%s\n", summary->message.c_str());
+            return;
+        }
+    }
     BaLayout L;
     // CONTRACT of the recognition (DetectBa): a user cost function is replaced by the built-in device factor if
     //   * the first block of its C++ type equals proj(conj(q)(L - t)) - feature at four generic probe points, one of them behind the
@@ -1398,13 +1568,28 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
     // NOTE for callers with IterationCallbacks: if the end-point check fails, the callbacks have already fired for the discarded
     // device solve and fire again for the second one (the summary's message says that a second solve ran; its iterations are the
     // ones reported, the time of both is in total_time_in_seconds, the first one's under phases.resolve's complement).
-    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
-    const bool force_cb = options.force_callback_path || (fe && *fe && *fe != '0');
     double t0 = WallSeconds();
     bool ba = !force_cb && DetectBa(*problem, &L, true, options.num_threads, true);      // (the per-block half: inside SolveBa)
     if (ba)
         for (int rb : L.rot_block) ba = ba && UsesQuaternionRightPlus(problem->blocks()[rb].local);
     summary->phases.recognise = WallSeconds() - t0;
+    if (options.use_inner_iterations) {
+        // (gpu-ba only: every block must be the reprojection factor -- the per-block half of the recognition runs here, before any
+        // device work, instead of next to the engine's creation)
+        std::string why;
+        t0 = WallSeconds();
+        if (!ba || (L.n_user && !DetectBaBlocks(*problem, &L, options.num_threads)))
+            why = "inner iterations are implemented on the gpu-ba path only: this problem's cost functions are not the reprojection factor "
+                  "(gpu-ba-hostjac)";
+        else if (!MakeInnerGroups(options, *problem, L, &inner, &why)) {}
+        summary->phases.recognise += WallSeconds() - t0;
+        if (!why.empty()) {
+            summary->termination_type = FAILURE;
+            summary->message = "stba_ceres: " + why + " -- nothing was solved.";
+            std::fprintf(stderr, "%s\n", summary->message.c_str());
+            return;
+        }
+    }
     std::string carried;
     std::vector<double> saved;
     bool still_factor = true;
@@ -1414,7 +1599,10 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         bool blocks_ok = true;
         std::thread destroyer;
         JoinOnExit destroyer_guard{&destroyer};
-        SolveBa(options, problem, L, summary, false, L.n_user ? &L : nullptr, &blocks_ok, L.n_user ? &destroyer : nullptr);
+        if (options.use_inner_iterations)      // (the blocks were checked above)
+            SolveBa(options, problem, L, summary, false, nullptr, &blocks_ok, L.n_user ? &destroyer : nullptr, &inner);
+        else
+            SolveBa(options, problem, L, summary, false, L.n_user ? &L : nullptr, &blocks_ok, L.n_user ? &destroyer : nullptr);
         if (!blocks_ok) { ba = false; summary->execution_path.clear(); }       // a block is not the factor: on to the other paths, nothing was touched
         t0 = WallSeconds();
         still_factor = !ba || summary->termination_type == FAILURE || VerifyRecognisedBlocks(*problem, L, options.num_threads);
@@ -1431,9 +1619,16 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         size_t o = 0;
         for (auto& b : problem->blocks()) { std::copy(saved.begin() + o, saved.begin() + o + b.size, b.ptr); o += (size_t)b.size; }
         const Solver::Summary::Phases first = summary->phases;
+        const std::vector<int> given = summary->inner_iteration_ordering_given;
         *summary = Solver::Summary();
         summary->phases = first;
         carried = "a user cost function taken for the reprojection factor differs from it at the solution: solved again with the user's Evaluate.";
+        if (options.use_inner_iterations) {
+            // (the second solve takes gpu-ba-hostjac, which has no inner iterations: it runs without them)
+            summary->inner_iterations_given = true;
+            summary->inner_iteration_ordering_given = given;
+            carried += " The second solve ran without inner iterations (gpu-ba-hostjac has none).";
+        }
     }
     const double t_resolve = WallSeconds();
     // a pose graph: every residual block a RelativePoseFactor between two 7-double pose blocks with the SE3 right-plus chart
@@ -1450,7 +1645,9 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
     if (shape) {
         summary->execution_path = "gpu-ba-hostjac";
         Solver::Summary::Phases ph = summary->phases;
-        SolveBa(options, problem, L2, summary, true);
+        Solver::Options o2 = options;
+        o2.use_inner_iterations = false;           // (only the end-point re-solve gets here with inner iterations asked for)
+        SolveBa(o2, problem, L2, summary, true);
         if (!carried.empty()) { summary->phases = ph; summary->phases.resolve = WallSeconds() - t_resolve; }
     }
     else { summary->execution_path = "gpu-dense-callback"; SolveDense(options, problem, summary); }

@@ -79,7 +79,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_dense_covariance",
            "stba_ba_create_ex", "stba_ba_set_pcg", "stba_ba_last_pcg_summary", "stba_ba_schur_apply",
            "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply",
-           "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary"]
+           "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary",
+           "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary"]
 
 
 def lib():
@@ -178,6 +179,39 @@ class DoglegSummary(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "steps_by_case"}
         d["steps_by_case"] = list(self.steps_by_case)
         return d
+
+
+INNER_MAX_GROUPS_REPORTED = 16
+
+
+class InnerSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("sweeps", C.c_int), ("disabled_at_iteration", C.c_int), ("sweep_ms", C.c_double),
+                ("num_groups", C.c_int), ("group_size", C.c_int * INNER_MAX_GROUPS_REPORTED)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "group_size"}
+        d["group_size"] = list(self.group_size)[: min(self.num_groups, INNER_MAX_GROUPS_REPORTED)]
+        return d
+
+
+def inner_ordering(n_cams, n_pts, tolerance=1e-3, rot_group=None, pos_group=None, pt_group=None):
+    """checks the arguments of BAEngine.set_inner_iterations and returns (tolerance, rot, pos, pt) as the C ABI takes them (int32
+    arrays or None).  Group ids are integers >= -1 (-1: not swept); all three None: the default ordering."""
+    tol = float(tolerance)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"inner iteration tolerance must be finite and >= 0, not {tolerance!r}")
+    out = []
+    for name, g, n in (("rot_group", rot_group, n_cams), ("pos_group", pos_group, n_cams), ("pt_group", pt_group, n_pts)):
+        if g is None:
+            out.append(None)
+            continue
+        a = np.asarray(g)
+        if a.shape != (n,):
+            raise ValueError(f"{name} must have shape ({n},), not {a.shape}")
+        if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < -1):
+            raise ValueError(f"{name} must hold integer group ids >= -1")
+        out.append(np.ascontiguousarray(a, dtype=np.int32))
+    return (tol, *out)
 
 
 LINEAR_SOLVERS = {"dense_schur": 0, "iterative_schur": 1}
@@ -412,6 +446,31 @@ class BAEngine:
         s = DoglegSummary()
         s.struct_size = C.sizeof(DoglegSummary)
         _chk(lib().stba_ba_last_dogleg_summary(self._h, C.byref(s)), "stba_ba_last_dogleg_summary")
+        return s
+
+    # ---- inner iterations (Ceres' use_inner_iterations; include/stba.h)
+    def set_inner_iterations(self, enable=True, tolerance=1e-3, rot_group=None, pos_group=None, pt_group=None):
+        """a coordinate-descent sweep behind every valid step of solve() / lm_iterations().  rot_group, pos_group [n_cams] and
+        pt_group [n_pts]: group id of every camera rotation, camera position and landmark (-1: not swept; equal rotation and
+        position ids: one 6-dof camera block); all None: {cameras}, {landmarks}.  enable=False: off"""
+        tol, r, q, p = inner_ordering(self.nc, self.np_, tolerance, rot_group, pos_group, pt_group)
+        _chk(lib().stba_ba_set_inner_iterations(self._h, int(bool(enable)), C.c_double(tol), _p(r), _p(q), _p(p)),
+             "stba_ba_set_inner_iterations")
+
+    def inner_sweep(self):
+        """one sweep at the current point, which moves the parameters: (cost before, cost after, inner LM iterations per block as
+        a dict of int arrays rot [n_cams], pos [n_cams], pt [n_pts])"""
+        c0, c1 = C.c_double(), C.c_double()
+        it = np.zeros(2 * self.nc + self.np_, dtype=np.int32)
+        _chk(lib().stba_ba_inner_sweep(self._h, C.byref(c0), C.byref(c1), _p(it)), "stba_ba_inner_sweep")
+        return c0.value, c1.value, {"rot": it[: self.nc].copy(), "pos": it[self.nc: 2 * self.nc].copy(), "pt": it[2 * self.nc:].copy()}
+
+    def inner_summary(self):
+        """sweeps, the iteration that switched inner iterations off (-1: none), sweep device time (phase_timing) and group sizes
+        of the last solve or sweep"""
+        s = InnerSummary()
+        s.struct_size = C.sizeof(InnerSummary)
+        _chk(lib().stba_ba_last_inner_summary(self._h, C.byref(s)), "stba_ba_last_inner_summary")
         return s
 
     def time_schur_apply(self, reps=20):

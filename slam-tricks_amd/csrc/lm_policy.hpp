@@ -84,8 +84,10 @@ struct StepVerdict {
 
 // ok: the step was computed and its trial point evaluated -- what counts as that is the caller's.  A step that is not ok is
 // rejected with cost_change = rho = 0 and no test runs.  tests = false (the BA engine's fixed-iteration mode): no stop.
+// inner_useful (the BA engine's inner iterations): the sweep brought the candidate below the current cost -- the step
+// is taken whatever rho (Ceres IsStepSuccessful); new_cost, model_change and step_norm are then the sweep's
 inline StepVerdict judge_step(const stba_lm_options& o, double cost, bool ok, double new_cost, double model_change, double step_norm,
-                              double x_norm, bool tests = true) {
+                              double x_norm, bool tests = true, bool inner_useful = false) {
     StepVerdict v;
     if (!ok) return v;
     v.cost_change = cost - new_cost;
@@ -97,12 +99,12 @@ inline StepVerdict judge_step(const stba_lm_options& o, double cost, bool ok, do
         }
         if (std::fabs(v.cost_change) <= o.function_tolerance * cost) {
             // (function_tolerance_takes_step, stba.h: 1 = the decreasing step is taken before convergence is reported; 0 = not)
-            v.accepted = o.function_tolerance_takes_step && v.rho > o.min_relative_decrease;
+            v.accepted = o.function_tolerance_takes_step && (inner_useful || v.rho > o.min_relative_decrease);
             v.stop = STBA_TERM_FUNCTION;
             return v;
         }
     }
-    v.accepted = v.rho > o.min_relative_decrease;
+    v.accepted = inner_useful || v.rho > o.min_relative_decrease;
     return v;
 }
 

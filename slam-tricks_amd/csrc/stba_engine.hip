@@ -14,6 +14,7 @@
 #include "ba_kernels.hpp"
 #include "iterative_schur.hpp"
 #include "dogleg.hpp"
+#include "inner_iterations.hpp"
 #include "lm_policy.hpp"
 
 namespace stba {
@@ -158,6 +159,20 @@ struct stba_ba {
     MappedBuffer dl_host;
     double dl_seq = 0.0;
     stba_dogleg_summary dl_sum{};
+    // inner iterations (stba_ba_set_inner_iterations; inner_iterations.hip): the ordering as per-group ranges of a
+    // camera list (with each entry's dof mask) and a landmark list, in ascending group id; the entries' iteration counts; the gate of
+    // the sweep behind a trial point, its two scalars {cost2 at x*, |x - x*|^2} and the partials of the latter
+    bool inner_on = false;
+    double inner_tol = 1e-3;
+    struct InnerGroup { int cam_lo, cam_hi, pt_lo, pt_hi; };
+    std::vector<InnerGroup> inner_groups;
+    std::vector<int> inner_cam_h, inner_pt_h;
+    std::vector<unsigned char> inner_mask_h, inner_kind_h;   // kind: 1 rotation, 2 position, 3 both (a 6-dof block)
+    int *inner_cam = nullptr, *inner_pt = nullptr, *inner_it = nullptr, *inner_gate = nullptr;
+    unsigned char* inner_mask = nullptr;
+    double *inner_sc = nullptr, *inner_part = nullptr;
+    hipEvent_t inner_ev[2] = {};
+    stba_inner_summary inner_sum{};
 
     size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
     double* S() const { return iterative ? nullptr : Sbuf; }
@@ -198,6 +213,8 @@ static void ba_free(stba_ba* b) {
     b->pcg_host.release();
     F(b->dl_uc); F(b->dl_up); F(b->dl_part); F(b->dl_sc);
     b->dl_host.release();
+    F(b->inner_cam); F(b->inner_pt); F(b->inner_it); F(b->inner_gate); F(b->inner_mask); F(b->inner_sc); F(b->inner_part);
+    for (auto& e : b->inner_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
     b->ts_host.release();
@@ -686,6 +703,49 @@ static void ba_pcg_account(stba_ba* b, int lm_iter) {
     b->pcg_sum.last_eta = b->pcg_eta;
 }
 
+// ---- inner iterations (Solver::Options::use_inner_iterations; inner_iterations.hip)
+static InnerObs inner_obs_args(const stba_ba* b) {
+    InnerObs o;
+    o.n_cams = b->nc; o.n_pts = b->np;
+    o.pt_start = b->pt_start; o.obs_cam = b->obs_cam; o.obs_pt = b->obs_pt; o.feat = b->feat;
+    o.cam_perm = b->cam_perm; o.chunk_begin = b->chunk_begin; o.chunk_end = b->chunk_end; o.cam_chunk_start = b->cam_chunk_start;
+    return o;
+}
+// one sweep of the ordering over parameter buffer `which`, in place: the groups in ascending id, in each the camera blocks, then the
+// landmarks (a group is an independent set: the two launches see nothing of each other's blocks).  gate: null, or the device's
+// verdict on the trial point (0: every workgroup returns at once)
+static int ba_inner_sweep_enqueue(stba_ba* b, int which, const int* gate) {
+    const InnerObs o = inner_obs_args(b);
+    const int n_cam_entries = (int)b->inner_cam_h.size();
+    for (const auto& g : b->inner_groups) {
+        STBA_TRY(launch_inner_cameras(o, g.cam_hi - g.cam_lo, b->inner_cam + g.cam_lo, b->inner_mask + g.cam_lo, b->cams[which],
+                                      b->pts[which], b->inner_it + g.cam_lo, gate, b->st));
+        STBA_TRY(launch_inner_points(o, g.pt_hi - g.pt_lo, b->inner_pt + g.pt_lo, b->cams[which], b->pts[which],
+                                     b->inner_it + n_cam_entries + g.pt_lo, gate, b->st));
+    }
+    return STBA_OK;
+}
+// behind the trial point x+ in buffer cur ^ 1 (enqueued before the host reads the trial block): the gate, the sweep x+ -> x*, the
+// cost at x* by the trial pass's residual kernel -> inner_sc[0] (cost2), and the ambient |x - x*|^2 -> inner_sc[1]
+static int ba_inner_after_trial(stba_ba* b) {
+    const int cur = b->cur, nxt = cur ^ 1;
+    STBA_TRY(launch_inner_gate(b->trial, b->flag, TS_COST2, TS_MODEL, TS_CAM + 2, b->inner_gate, b->st));
+    STBA_TRY(ba_inner_sweep_enqueue(b, nxt, b->inner_gate));
+    STBA_TRY(ba_cost_only(b, nxt, b->inner_sc));
+    STBA_TRY(launch_inner_step2(b->nc, b->np, b->cams[cur], b->pts[cur], b->cams[nxt], b->pts[nxt], b->inner_part, b->st));
+    return launch_sum_partials(b->inner_part, inner_step_grid(b->nc, b->np), 1, 1, b->inner_sc + 1, b->st);
+}
+static void inner_summary_reset(stba_ba* b) {
+    b->inner_sum = stba_inner_summary{};
+    b->inner_sum.struct_size = sizeof(stba_inner_summary);
+    b->inner_sum.disabled_at_iteration = -1;
+    b->inner_sum.num_groups = (int)b->inner_groups.size();
+    for (int g = 0; g < b->inner_sum.num_groups && g < STBA_INNER_MAX_GROUPS_REPORTED; ++g) {
+        const auto& r = b->inner_groups[(size_t)g];
+        b->inner_sum.group_size[g] = (r.cam_hi - r.cam_lo) + (r.pt_hi - r.pt_lo);
+    }
+}
+
 static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterations, stba_lm_summary* sum,
                      double* trace, stba_iteration_callback cb, void* cb_user) {
     stba_lm_options opt;
@@ -709,6 +769,12 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
     TrustRegion region(opt);
     double cost = 0.0, gmax = 0.0;
+    // inner iterations: on while the engine has them and no sweep has switched them off (rule 6)
+    bool inner_active = b->inner_on;
+    if (b->inner_on) {
+        inner_summary_reset(b);
+        if (timing) for (auto& e : b->inner_ev) if (!e) STBA_HIP(hipEventCreate(&e));
+    }
 
     // ---- iteration 0: linearise at the start point
     if (timing) STBA_HIP(hipEventRecord(ev[0], b->st));
@@ -794,13 +860,20 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         // the speculative build are enqueued on the stream like everything else.)
         // (host-linearised factors: the callback is synchronous host work; iterative Schur: the PCG hands its state to the host
         // anyway, and this path does not speculate -- DESIGN.md 7b)
-        const bool fast = deferred_ok && SPECULATE && !b->hl_fn && !b->iterative;
+        // (inner iterations: the sweep moves the trial point before anything is linearised there -- no speculation)
+        const bool fast = deferred_ok && SPECULATE && !b->hl_fn && !b->iterative && !inner_active;
         if (fast && !b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
         // (the speculative linearisation IS the evaluation of the trial point: one pass over the observations, not two)
         const bool speculate = fast && !(fixed && iter >= max_iter);
         const double seq = fast ? (b->ts_seq += 1.0) : 0.0;
         STBA_TRY(ba_trial(b, fast ? b->ts_host.dev : nullptr, true, speculate, seq));
         if (timing) STBA_HIP(hipEventRecord(ev[6], b->st));
+        double isc[2] = {0.0, 0.0};
+        if (inner_active) {
+            if (timing) STBA_HIP(hipEventRecord(b->inner_ev[0], b->st));
+            STBA_TRY(ba_inner_after_trial(b));
+            if (timing) STBA_HIP(hipEventRecord(b->inner_ev[1], b->st));
+        }
         const double* ts = b->ts_vals;
         bool speculated = false;
         if (fast) {
@@ -820,7 +893,9 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         } else {
             STBA_TRY(download(b->ts_vals, b->trial, TS_BLOCK, b->st));
             STBA_TRY(download(&flag_h, b->flag, 1, b->st));
+            if (inner_active) STBA_TRY(download(isc, b->inner_sc, 2, b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
+            if (inner_active && timing && hipEventElapsedTime(&ms, b->inner_ev[0], b->inner_ev[1]) == hipSuccess) b->inner_sum.sweep_ms += ms;
         }
         if (pcg_fail) flag_h = 1;            // (the PCG failed: the step is not ok)
         if (pending) {
@@ -879,14 +954,26 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         chol_timeouts = 0;
 
         bool step_ok = (flag_h == 0);
-        const double new_cost = 0.5 * ts[TS_COST2];
-        const double step_norm = std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]);
+        double new_cost = 0.5 * ts[TS_COST2];
+        double step_norm = std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]);
         x_norm = std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]);
-        const double model_change = ts[TS_MODEL] + ts[TS_CAM + 2];
+        double model_change = ts[TS_MODEL] + ts[TS_CAM + 2];
         // (a non-finite trial cost makes the step not ok: row [cost, 0, ., 0, 0], no stop test)
         if (step_ok && (!(model_change > 0.0) || !std::isfinite(model_change) || !std::isfinite(new_cost)))
             step_ok = false;
-        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, !fixed);
+        bool inner_useful = false;
+        if (inner_active && step_ok) {
+            // the sweep ran (its gate saw the same valid step): the candidate becomes x* (Ceres DoInnerIterationsIfNeeded)
+            const double inner_cost = 0.5 * isc[0];
+            ++b->inner_sum.sweeps;
+            model_change += new_cost - inner_cost;
+            inner_useful = inner_cost < cost;
+            const double progress = 1.0 - inner_cost / new_cost;
+            new_cost = inner_cost;
+            step_norm = std::sqrt(isc[1]);
+            if (!(progress > b->inner_tol)) { inner_active = false; b->inner_sum.disabled_at_iteration = iter; }
+        }
+        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, !fixed, inner_useful);
         const bool accepted = v.accepted;
         if (accepted) {
             b->cur ^= 1;
@@ -2012,6 +2099,7 @@ int stba_ba_get_params(stba_ba* b, double* cams, double* pts) {
 
 int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (fn && b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has inner iterations (device residuals only)");
     if (fn && !b->Jc12) STBA_TRY(dev_alloc(&b->Jc12, (size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
@@ -2022,6 +2110,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
     STBA_TRY(refuse_iterative(b, "stba_ba_set_allreduce", "which runs on one rank only"));
     if (b && b->trust_region == STBA_TR_TRADITIONAL_DOGLEG)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine uses DOGLEG, which runs on one rank only");
+    if (b && b->inner_on && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has inner iterations, which run on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -2180,7 +2270,10 @@ int stba_ba_solve(stba_ba* b, const stba_lm_options* opt, stba_lm_summary* summa
                   stba_iteration_callback cb, void* cb_user) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     b->dl_sum = stba_dogleg_summary{};
-    if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return ba_run_dogleg(b, opt, summary, trace, cb, cb_user);
+    if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) {
+        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_solve: inner iterations are not supported with DOGLEG");
+        return ba_run_dogleg(b, opt, summary, trace, cb, cb_user);
+    }
     return ba_run_lm(b, opt, 0, summary, trace, cb, cb_user);
 }
 
@@ -2206,6 +2299,146 @@ int stba_ba_last_dogleg_summary(stba_ba* b, stba_dogleg_summary* out) {
     stba_dogleg_summary s = b->dl_sum;
     s.struct_size = want;
     memcpy(out, &s, std::min(want, sizeof s));
+    return STBA_OK;
+}
+
+int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const int* cam_rot_group, const int* cam_pos_group,
+                                 const int* pt_group) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (!enable) {
+        b->inner_on = false;
+        return STBA_OK;
+    }
+    if (!(tolerance >= 0.0) || !std::isfinite(tolerance))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: the tolerance must be finite and >= 0");
+    if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: inner iterations run on one rank only (an all-reduce hook is set)");
+    if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: not with a host lineariser");
+    const int nc = b->nc, np = b->np, no = b->no;
+    // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
+    std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
+    if (b->cam_fixed) STBA_TRY(download(cf.data(), b->cam_fixed, (size_t)nc, b->st));
+    if (b->pt_fixed) STBA_TRY(download(pf.data(), b->pt_fixed, (size_t)np, b->st));
+    std::vector<int> oc((size_t)no), op((size_t)no);
+    STBA_TRY(download(oc.data(), b->obs_cam, (size_t)no, b->st));
+    STBA_TRY(download(op.data(), b->obs_pt, (size_t)no, b->st));
+    STBA_HIP(hipStreamSynchronize(b->st));
+    const bool dflt = !cam_rot_group && !cam_pos_group && !pt_group;
+    // group of every part (-1: not swept); constant parts are ignored
+    std::vector<int> gr((size_t)nc, -1), gq((size_t)nc, -1), gp((size_t)np, -1);
+    for (int c = 0; c < nc; ++c) {
+        const bool rot_const = (cf[(size_t)c] & 7u) == 7u, pos_const = (cf[(size_t)c] & 56u) == 56u;
+        const int r = dflt ? 0 : (cam_rot_group ? cam_rot_group[c] : -1), q = dflt ? 0 : (cam_pos_group ? cam_pos_group[c] : -1);
+        if (r < -1 || q < -1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: camera " + std::to_string(c) + ": a group id below -1");
+        gr[(size_t)c] = rot_const ? -1 : r;
+        gq[(size_t)c] = pos_const ? -1 : q;
+    }
+    for (int j = 0; j < np; ++j) {
+        const int g = dflt ? 1 : (pt_group ? pt_group[j] : -1);
+        if (g < -1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: landmark " + std::to_string(j) + ": a group id below -1");
+        gp[(size_t)j] = pf[(size_t)j] ? -1 : g;
+    }
+    // independence: a residual touches one camera and one landmark, so a group is independent unless it holds a part of a camera and
+    // a landmark that camera observes (a camera's rotation and position in one group are one 6-dof block)
+    for (int i = 0; i < no; ++i) {
+        const int c = oc[(size_t)i], j = op[(size_t)i], g = gp[(size_t)j];
+        if (g >= 0 && (g == gr[(size_t)c] || g == gq[(size_t)c]))
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: group " + std::to_string(g) + " is not an independent set: camera " +
+                        std::to_string(c) + " and landmark " + std::to_string(j) + " share a residual");
+    }
+    std::vector<int> ids;
+    for (int c = 0; c < nc; ++c) { if (gr[(size_t)c] >= 0) ids.push_back(gr[(size_t)c]); if (gq[(size_t)c] >= 0) ids.push_back(gq[(size_t)c]); }
+    for (int j = 0; j < np; ++j) if (gp[(size_t)j] >= 0) ids.push_back(gp[(size_t)j]);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    std::vector<stba_ba::InnerGroup> groups;
+    std::vector<int> cam_l, pt_l;
+    std::vector<unsigned char> mask_l, kind_l;
+    for (const int g : ids) {
+        stba_ba::InnerGroup r;
+        r.cam_lo = (int)cam_l.size(); r.pt_lo = (int)pt_l.size();
+        for (int c = 0; c < nc; ++c) {
+            const unsigned kind = (gr[(size_t)c] == g ? 1u : 0u) | (gq[(size_t)c] == g ? 2u : 0u);
+            if (!kind) continue;
+            const unsigned m = (((kind & 1u) ? 7u : 0u) | ((kind & 2u) ? 56u : 0u)) & ~(unsigned)cf[(size_t)c];
+            cam_l.push_back(c); mask_l.push_back((unsigned char)m); kind_l.push_back((unsigned char)kind);
+        }
+        for (int j = 0; j < np; ++j) if (gp[(size_t)j] == g) pt_l.push_back(j);
+        r.cam_hi = (int)cam_l.size(); r.pt_hi = (int)pt_l.size();
+        groups.push_back(r);
+    }
+    // device lists: the new ones are allocated and filled first and swapped in only when all of them are there, so that a failed
+    // allocation leaves the engine's state (and an earlier ordering) as it was
+    const size_t n_it = std::max<size_t>(cam_l.size() + pt_l.size(), 1);
+    int *n_cam = nullptr, *n_pt = nullptr, *n_itb = nullptr, *n_gate = nullptr;
+    unsigned char* n_mask = nullptr;
+    double *n_sc = nullptr, *n_part = nullptr;
+    auto F = [](void* p) { if (p) (void)hipFree(p); };
+    auto drop = [&]() { F(n_cam); F(n_pt); F(n_itb); F(n_mask); F(n_gate); F(n_sc); F(n_part); };
+    int rc = STBA_OK;
+    if ((rc = dev_alloc(&n_cam, std::max<size_t>(cam_l.size(), 1))) != STBA_OK || (rc = dev_alloc(&n_mask, std::max<size_t>(mask_l.size(), 1))) != STBA_OK ||
+        (rc = dev_alloc(&n_pt, std::max<size_t>(pt_l.size(), 1))) != STBA_OK || (rc = dev_alloc(&n_itb, n_it)) != STBA_OK ||
+        (!b->inner_gate && (rc = dev_alloc(&n_gate, 1)) != STBA_OK) || (!b->inner_sc && (rc = dev_alloc(&n_sc, 4)) != STBA_OK) ||
+        (!b->inner_part && (rc = dev_alloc(&n_part, (size_t)inner_step_grid(nc, np))) != STBA_OK)) { drop(); return rc; }
+    if ((!cam_l.empty() && ((rc = upload(n_cam, cam_l.data(), cam_l.size(), b->st)) != STBA_OK ||
+                            (rc = upload(n_mask, mask_l.data(), mask_l.size(), b->st)) != STBA_OK)) ||
+        (!pt_l.empty() && (rc = upload(n_pt, pt_l.data(), pt_l.size(), b->st)) != STBA_OK) ||
+        hipMemsetAsync(n_itb, 0, n_it * sizeof(int), b->st) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) {
+        drop();
+        return rc != STBA_OK ? rc : fail(STBA_ERR_HIP, "stba_ba_set_inner_iterations: upload failed");
+    }
+    F(b->inner_cam); F(b->inner_pt); F(b->inner_it); F(b->inner_mask);
+    b->inner_cam = n_cam; b->inner_pt = n_pt; b->inner_it = n_itb; b->inner_mask = n_mask;
+    if (n_gate) b->inner_gate = n_gate;
+    if (n_sc) b->inner_sc = n_sc;
+    if (n_part) b->inner_part = n_part;
+    b->inner_groups = std::move(groups);
+    b->inner_cam_h = std::move(cam_l); b->inner_pt_h = std::move(pt_l);
+    b->inner_mask_h = std::move(mask_l); b->inner_kind_h = std::move(kind_l);
+    b->inner_tol = tolerance;
+    b->inner_on = true;
+    inner_summary_reset(b);
+    return STBA_OK;
+}
+
+int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int* iterations_per_block) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
+    if (b->ar || b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: one rank, device residuals only");
+    const bool was_on = b->inner_on;
+    if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
+    STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
+    STBA_TRY(ba_inner_sweep_enqueue(b, b->cur, nullptr));
+    STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc));
+    double sc[3];
+    STBA_TRY(download(sc, b->inner_sc, 3, b->st));
+    const size_t ncl = b->inner_cam_h.size(), npl = b->inner_pt_h.size();
+    std::vector<int> it(ncl + npl);
+    if (!it.empty()) STBA_TRY(download(it.data(), b->inner_it, it.size(), b->st));
+    STBA_HIP(hipStreamSynchronize(b->st));
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    inner_summary_reset(b);
+    b->inner_sum.sweeps = 1;
+    b->inner_on = was_on;
+    if (cost_before) *cost_before = 0.5 * sc[2];
+    if (cost_after) *cost_after = 0.5 * sc[0];
+    if (iterations_per_block) {
+        const int nc = b->nc;
+        memset(iterations_per_block, 0, sizeof(int) * ((size_t)2 * nc + b->np));
+        for (size_t k = 0; k < ncl; ++k) {
+            const int c = b->inner_cam_h[k];
+            if (b->inner_kind_h[k] & 1u) iterations_per_block[c] = it[k];
+            if (b->inner_kind_h[k] & 2u) iterations_per_block[nc + c] = it[k];
+        }
+        for (size_t k = 0; k < npl; ++k) iterations_per_block[2 * nc + b->inner_pt_h[k]] = it[ncl + k];
+    }
+    return STBA_OK;
+}
+
+int stba_ba_last_inner_summary(stba_ba* b, stba_inner_summary* out) {
+    if (!b || !out || out->struct_size < offsetof(stba_inner_summary, sweeps) + sizeof(int)) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_last_inner_summary: bad argument");
+    const size_t n = std::min(out->struct_size, sizeof(stba_inner_summary));
+    stba_inner_summary s = b->inner_sum;
+    s.struct_size = out->struct_size;
+    memcpy(out, &s, n);
     return STBA_OK;
 }
 
