@@ -470,6 +470,48 @@ int stba_pg_solve(stba_pg* pg, const stba_lm_options* opt, const stba_pcg_option
 /* the linear-solver side of the last stba_pg_solve of this engine */
 int stba_pg_last_pcg_summary(stba_pg* pg, stba_pcg_summary* out);
 
+/* --- pose-graph covariance ---------------------------------------------------------------- */
+/* C = (J^T J)^-1 of the undamped, unscaled problem at the engine's current poses, in the engine's tangent coordinates (per node
+ * [rho, theta] of T <- T exp(delta)); not multiplied by a residual variance (the definition of stba_ba_covariance_compute); constant
+ * nodes have zero rows and columns.  The columns of the requested nodes are solved 64 at a time by a batched preconditioned
+ * conjugate gradient on the device (pg_covariance.hip): memory is O(6 n_nodes x 64) whatever is asked for.  Both entry
+ * points re-linearise, run on the engine's stream and leave the LM state alone: a later stba_pg_solve gives the same bits as
+ * one without the call.
+ * Refused, with the reason in stba_last_error() and nothing written to out:
+ *   STBA_ERR_NOT_POSITIVE_DEFINITE  before any device work: a connected component of the graph without a constant node (J^T J is
+ *                                   singular; the message names the component's size and first node -- stba_pg_gauge_check);
+ *                                   during the solve: p^T H p <= 0, or max_iterations reached with the TRUE relative residual
+ *                                   |e - H x| / |e| of a column above relative_tolerance (the message gives it and the iterations)
+ *   STBA_ERR_INVALID_ARGUMENT       a node index out of range
+ *   STBA_ERR_STATE                  an all-reduce hook or communicator is set (several ranks)
+ * STBA_VERSION is unchanged: test for the symbols. */
+typedef struct {
+    size_t struct_size;          /* sizeof(stba_pg_covariance_options); fields behind struct_size are taken as their defaults */
+    double relative_tolerance;   /* 1e-12, on the true residual |e - H x| / |e| of every column */
+    int    max_iterations;       /* 0: 6 x the number of free nodes (the dimension of the system), per batch */
+    int    check_every;          /* 4: iterations enqueued between the host's looks at the device-side flag */
+} stba_pg_covariance_options;
+void stba_pg_covariance_default_options(stba_pg_covariance_options* o);
+typedef struct {
+    size_t struct_size;          /* sizeof(stba_pg_covariance_summary); fields behind struct_size are not written */
+    int    batches;              /* batches of up to 64 columns */
+    int    columns;              /* columns solved (6 per distinct free node) */
+    int    iterations_total;     /* PCG iterations over all batches */
+    int    max_iterations_in_a_batch;
+    double max_relative_residual;/* largest true |e - H x| / |e| over all columns */
+    double device_ms;            /* hipEvents on the engine's stream around the whole computation */
+} stba_pg_covariance_summary;
+/* out[n_pairs*36]: the 6x6 row-major block C[node_a[k], node_b[k]] per pair; solves for the distinct node_b; a pair that names a
+ * constant node gets zeros.  opt and summary may be NULL. */
+int stba_pg_covariance(stba_pg* pg, int n_pairs, const int* node_a, const int* node_b, const stba_pg_covariance_options* opt,
+                       double* out, stba_pg_covariance_summary* summary);
+/* out[6*n_nodes*6] row-major: the six whole columns of C that belong to `node` -- its covariance with every pose of the graph */
+int stba_pg_covariance_columns(stba_pg* pg, int node, const stba_pg_covariance_options* opt, double* out,
+                               stba_pg_covariance_summary* summary);
+/* the gauge check both run first, on the host and without a device: STBA_OK, or STBA_ERR_NOT_POSITIVE_DEFINITE if a connected
+ * component of the graph holds no constant node (node_fixed may be NULL: no constant node at all) */
+int stba_pg_gauge_check(int n_nodes, int n_edges, const int* edge_i, const int* edge_j, const unsigned char* node_fixed);
+
 /* ================================ bundle adjustment: ITERATIVE_SCHUR ================================ */
 /* Ceres' linear_solver_type = ITERATIVE_SCHUR: conjugate gradients on the reduced camera system S = (Hcc + D) - W V^-1 W^T, applied
  * implicitly (two passes over the observations per product), so that neither S (8 (6 n_cams)^2 bytes) nor a Schur plan is ever

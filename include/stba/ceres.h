@@ -1455,11 +1455,19 @@ inline bool SolveDense(const Solver::Options& o, Problem* p, Solver::Summary* su
 
 // ---- path 3: pose graph on the device engine (stba_pg_*) -------------------------------------
 // returns false WITHOUT touching the summary if the problem is not a pose graph of built-in factors
-inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary* sum) {
+// the recognition, shared by Solve and Covariance: every residual block a RelativePoseFactor on two distinct 7-double blocks with the
+// SE3RightPlus chart and no bounds.  Nodes are numbered in the order the residual blocks first name them.
+struct PoseGraphLayout {
+    std::map<int, int> node_of;            // parameter block index -> node
+    std::vector<int> node_block, ei, ej;   // node -> parameter block index; the edges
+    std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
+    std::vector<unsigned char> fixed;      // [n]
+};
+inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
     if (p->residuals().empty()) return false;
-    std::map<int, int> node_of;
-    std::vector<int> node_block, ei, ej;
-    std::vector<double> meas;
+    auto& node_of = L->node_of;
+    auto& node_block = L->node_block; auto& ei = L->ei; auto& ej = L->ej;
+    auto& meas = L->meas;
     for (auto& r : p->residuals()) {
         auto* f = dynamic_cast<RelativePoseFactor*>(r.cost);
         if (!f || r.blocks.size() != 2 || r.blocks[0] == r.blocks[1]) return false;
@@ -1474,13 +1482,21 @@ inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary
         ei.push_back(ends[0]); ej.push_back(ends[1]);
         meas.insert(meas.end(), f->measurement(), f->measurement() + 7);
     }
-    const int n = (int)node_block.size(), m = (int)ei.size();
-    std::vector<double> poses((size_t)n * 7);
-    std::vector<unsigned char> fixed((size_t)n, 0);
+    const int n = (int)node_block.size();
+    L->poses.assign((size_t)n * 7, 0.0);
+    L->fixed.assign((size_t)n, 0);
     for (int k = 0; k < n; ++k) {
-        std::memcpy(&poses[(size_t)k * 7], p->blocks()[node_block[k]].ptr, 7 * sizeof(double));
-        fixed[k] = p->blocks()[node_block[k]].constant ? 1 : 0;
+        std::memcpy(&L->poses[(size_t)k * 7], p->blocks()[node_block[k]].ptr, 7 * sizeof(double));
+        L->fixed[k] = p->blocks()[node_block[k]].constant ? 1 : 0;
     }
+    return true;
+}
+inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary* sum) {
+    PoseGraphLayout L;
+    if (!DetectPoseGraph(p, &L)) return false;
+    auto& node_block = L.node_block; auto& ei = L.ei; auto& ej = L.ej;
+    auto& meas = L.meas; auto& poses = L.poses; auto& fixed = L.fixed;
+    const int n = (int)node_block.size(), m = (int)ei.size();
     sum->execution_path = "gpu-pg";
     stba_pg* pg = nullptr;
     int rc = stba_pg_create(&pg, n, m, poses.data(), ei.data(), ej.data(), meas.data(), fixed.data(), nullptr);
@@ -1672,6 +1688,10 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
 //   * "gpu-ba": every residual block is the reprojection factor (built-in, or a user cost function recognised as it at the current
 //     point, as Solve recognises it) -> stba_ba_covariance_compute with device Jacobians;
 //   * "gpu-ba-hostjac": BA-shaped with another factor -> the same with the user's cost functions as the host lineariser;
+//   * "gpu-pg": a pose graph as Solve recognises it (every residual block a RelativePoseFactor on two SE3RightPlus blocks) ->
+//     stba_pg_covariance, a batched conjugate gradient on the device engine's matrix-free J^T J: any size the engine takes.  A
+//     requested pair is any two pose blocks of the graph; a connected component without a constant block makes J^T J singular and
+//     Compute return false (the message names the component), before any device work;
 //   * "gpu-dense": anything else within the dense solve's limits -> stba_dense_covariance.
 // On the BA routes a requested pair must be two camera blocks (rotation / position, of one camera or of two) or one landmark with
 // itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: no robust losses (refused
@@ -1727,7 +1747,7 @@ public:
         std::copy(it->second.begin(), it->second.end(), cov);
         return true;
     }
-    const std::string& execution_path() const { return path_; }      // "gpu-ba" | "gpu-ba-hostjac" | "gpu-dense" (empty: none ran)
+    const std::string& execution_path() const { return path_; }      // "gpu-ba" | "gpu-ba-hostjac" | "gpu-pg" | "gpu-dense" (empty: none ran)
     const std::string& message() const { return message_; }
 
 private:
@@ -1775,7 +1795,39 @@ private:
             if (host) for (int rb : L.rot_block) host = host && UsesQuaternionRightPlus(p->blocks()[rb].local);
         }
         if (ba || host) return ComputeBa(pairs, p, L, index, host);
+        PoseGraphLayout G;
+        if (DetectPoseGraph(p, &G)) return ComputePoseGraph(pairs, G, index);
         return ComputeDense(pairs, p, index);
+    }
+
+    bool ComputePoseGraph(const std::vector<std::pair<const double*, const double*>>& pairs, const internal::PoseGraphLayout& G,
+                          const std::unordered_map<const double*, int>& index) {
+        const int n = (int)G.node_block.size(), m = (int)G.ei.size();
+        std::vector<int> na, nb;
+        for (size_t k = 0; k < pairs.size(); ++k) {
+            const auto a = G.node_of.find(index.at(pairs[k].first)), b = G.node_of.find(index.at(pairs[k].second));
+            if (a == G.node_of.end() || b == G.node_of.end()) return Fail(PairName(k) + " names a parameter block that no residual block of the pose graph uses");
+            na.push_back(a->second); nb.push_back(b->second);
+        }
+        path_ = "gpu-pg";
+        if (pairs.empty()) return true;
+        // (the gauge check of stba_pg_covariance, here so that a graph it refuses never needs a device)
+        if (stba_pg_gauge_check(n, m, G.ei.data(), G.ej.data(), G.fixed.data()) != STBA_OK) return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
+        stba_pg* pg = nullptr;
+        if (stba_pg_create(&pg, n, m, G.poses.data(), G.ei.data(), G.ej.data(), G.meas.data(), G.fixed.data(), nullptr) != STBA_OK)
+            return Fail(std::string("stba_pg_create: ") + stba_last_error());
+        struct Destroy { stba_pg* g; ~Destroy() { stba_pg_destroy(g); } } destroy{pg};
+        std::vector<double> blk(pairs.size() * 36);
+        if (stba_pg_covariance(pg, (int)pairs.size(), na.data(), nb.data(), nullptr, blk.data(), nullptr) != STBA_OK)
+            return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
+        for (size_t k = 0; k < pairs.size(); ++k)
+            Store(pairs[k].first, pairs[k].second, 6, 6, std::vector<double>(blk.begin() + (ptrdiff_t)k * 36, blk.begin() + (ptrdiff_t)(k + 1) * 36));
+        // (the columns of C come from separate conjugate-gradient solves, so C[a, b] and C[b, a]^T differ in their last bits: Store's
+        // transpose serves the swapped pair nobody asked for, and every REQUESTED pair -- a diagonal one, or both orders of one --
+        // keeps the block that was computed for it)
+        for (size_t k = 0; k < pairs.size(); ++k)
+            tangent_[{pairs[k].first, pairs[k].second}].assign(blk.begin() + (ptrdiff_t)k * 36, blk.begin() + (ptrdiff_t)(k + 1) * 36);
+        return true;
     }
 
     bool ComputeBa(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p, const internal::BaLayout& L,

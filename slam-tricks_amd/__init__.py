@@ -80,7 +80,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_create_ex", "stba_ba_set_pcg", "stba_ba_last_pcg_summary", "stba_ba_schur_apply",
            "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply",
            "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary",
-           "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary"]
+           "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary",
+           "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check"]
 
 
 def lib():
@@ -511,6 +512,33 @@ class PCGSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PGCovarianceOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("relative_tolerance", C.c_double), ("max_iterations", C.c_int), ("check_every", C.c_int)]
+
+
+class PGCovarianceSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("batches", C.c_int), ("columns", C.c_int), ("iterations_total", C.c_int),
+                ("max_iterations_in_a_batch", C.c_int), ("max_relative_residual", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+def pg_covariance_options(**kw):
+    o = PGCovarianceOptions()
+    lib().stba_pg_covariance_default_options(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def pg_gauge_check(n_nodes, edge_i, edge_j, node_fixed=None):
+    """raises StbaError(STBA_ERR_NOT_POSITIVE_DEFINITE) if a connected component of the graph holds no constant node; host only"""
+    ei = np.ascontiguousarray(edge_i, dtype=np.int32); ej = np.ascontiguousarray(edge_j, dtype=np.int32)
+    nf = None if node_fixed is None else np.ascontiguousarray(node_fixed, dtype=np.uint8)
+    _chk(lib().stba_pg_gauge_check(int(n_nodes), len(ei), _p(ei), _p(ej), _p(nf)), "stba_pg_gauge_check")
+
+
 class PGEngine:
     """Device-resident pose graph (BASELINE config C4, build-defined)."""
 
@@ -587,6 +615,25 @@ class PGEngine:
         _chk(lib().stba_pg_solve(self._h, C.byref(opt), C.byref(pcg), C.byref(summ), _p(trace), C.byref(total)),
              "stba_pg_solve")
         return summ, trace[: summ.num_iterations + 1], total.value
+
+    def covariance(self, pairs, **opt):
+        """(n_pairs, 6, 6): the blocks C[a, b] of (J^T J)^-1 at the current poses, tangent [rho, theta]; and the summary as a dict.
+        opt: relative_tolerance, max_iterations, check_every (stba_pg_covariance_options)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a = np.ascontiguousarray(pairs[:, 0]); b = np.ascontiguousarray(pairs[:, 1])
+        out = np.zeros((len(pairs), 6, 6))
+        summ = PGCovarianceSummary(struct_size=C.sizeof(PGCovarianceSummary))
+        o = pg_covariance_options(**opt)
+        _chk(lib().stba_pg_covariance(self._h, len(pairs), _p(a), _p(b), C.byref(o), _p(out), C.byref(summ)), "stba_pg_covariance")
+        return out, summ.as_dict()
+
+    def covariance_columns(self, node, **opt):
+        """(6 n, 6): the six columns of (J^T J)^-1 that belong to `node` -- its covariance with every pose; and the summary as a dict"""
+        out = np.zeros((6 * self.n, 6))
+        summ = PGCovarianceSummary(struct_size=C.sizeof(PGCovarianceSummary))
+        o = pg_covariance_options(**opt)
+        _chk(lib().stba_pg_covariance_columns(self._h, int(node), C.byref(o), _p(out), C.byref(summ)), "stba_pg_covariance_columns")
+        return out, summ.as_dict()
 
 
 def cholesky_factor(A, stream=None):

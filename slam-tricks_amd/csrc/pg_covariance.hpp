@@ -1,0 +1,38 @@
+// pg_covariance.hpp -- what pg_covariance.hip needs from the pose-graph engine (pg_engine.hip), and the host-side gauge check.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+
+struct stba_pg;
+
+namespace stba {
+
+// the graph as the caller gave it (host copies kept by the engine) -- enough to refuse a request before any device work
+struct PgCovGraph {
+    int n = 0, m = 0;
+    const int* ei = nullptr; const int* ej = nullptr;      // [m]
+    const unsigned char* fixed = nullptr;                  // [n] or null
+    bool several_ranks = false;                            // an all-reduce hook or communicator is set
+};
+void pg_cov_graph(const stba_pg* g, PgCovGraph* out);
+
+// the linearisation at the engine's current poses, on the device.  pg_cov_linearize re-linearises and sums the diagonal blocks; it
+// writes only buffers that every stba_pg_solve overwrites before it reads them (residuals, Jacobians, gradient, diagonal blocks).
+struct PgCovDevice {
+    hipStream_t st = nullptr;
+    const int* node_start = nullptr;       // [n + 1]: the edge ends of every node (CSR)
+    const int* end_code = nullptr;         // [2 m]: 2 * edge + side at a CSR position
+    const int* end_rem = nullptr;          // [2 m]: the node at the other end
+    const double* Ji = nullptr; const double* Jj = nullptr;      // [36][m] component-major, zero for constant nodes
+    const double* Hd = nullptr;            // [n][36] diagonal blocks of J^T J
+    const unsigned char* fixed = nullptr;  // device, or null
+};
+int pg_cov_linearize(stba_pg* g, PgCovDevice* out);
+
+// union-find over the edges: the first connected component without a constant node.  true: every component has one.
+// Otherwise *size and *first_node describe the offending component (the one whose smallest node index is smallest).
+bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, int* size, int* first_node);
+
+}  // namespace stba

@@ -36,6 +36,7 @@
 
 #include "ba_kernels.hpp"
 #include "lm_policy.hpp"
+#include "pg_covariance.hpp"
 
 namespace stba {
 namespace {
@@ -1348,6 +1349,9 @@ struct stba_pg {
     hipEvent_t ev_t[2] = {nullptr, nullptr};      // stba_lm_options::phase_timing: around the linear solve
     bool job_in_flight = false, job_reads_pending = false, ac0_valid = false;
     stba_pcg_summary last_pcg;
+    // host copies of the graph for stba_pg_covariance's gauge check (pg_covariance.hip), which runs before any device work
+    std::vector<int> h_ei, h_ej;
+    std::vector<unsigned char> h_fixed;
 };
 
 namespace stba {
@@ -1411,6 +1415,24 @@ int pg_sum_ranks(stba_pg* g, double* v) {
     return STBA_OK;
 }
 }  // namespace
+
+// ---- what pg_covariance.hip sees of the engine (pg_covariance.hpp)
+void pg_cov_graph(const stba_pg* g, PgCovGraph* out) {
+    out->n = g->n; out->m = g->m;
+    out->ei = g->h_ei.data(); out->ej = g->h_ej.data();
+    out->fixed = g->h_fixed.empty() ? nullptr : g->h_fixed.data();
+    out->several_ranks = g->ar != nullptr || g->world > 1;
+}
+int pg_cov_linearize(stba_pg* g, PgCovDevice* out) {
+    // (a coarse inverse of the last solve may still be reading the diagonal blocks on the second stream)
+    if (g->st2 && g->job_in_flight) STBA_HIP(hipStreamSynchronize(g->st2));
+    STBA_TRY(pg_linearize(g, g->cur, true));
+    hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->node_start, g->end_code, g->contrib, g->g, g->Hd);
+    STBA_HIP(hipGetLastError());
+    out->st = g->st; out->node_start = g->node_start; out->end_code = g->end_code; out->end_rem = g->end_rem;
+    out->Ji = g->Ji; out->Jj = g->Jj; out->Hd = g->Hd; out->fixed = g->fixed;
+    return STBA_OK;
+}
 }  // namespace stba
 
 // ---- coarse space: sizes and buffers for a group size (lazily: the group size is an option of the solve)
@@ -1501,6 +1523,8 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
     STBA_TRY(require_device());
     stba_pg* g = new stba_pg();
     g->n = n_nodes; g->m = n_edges;
+    g->h_ei.assign(edge_i, edge_i + n_edges); g->h_ej.assign(edge_j, edge_j + n_edges);
+    if (node_fixed) g->h_fixed.assign(node_fixed, node_fixed + n_nodes);
     if (hip_stream) g->st = reinterpret_cast<hipStream_t>(hip_stream);
     else { if (hipStreamCreate(&g->st) != hipSuccess) { delete g; return fail(STBA_ERR_HIP, "hipStreamCreate"); } g->own = true; }
     g->nb_nodes = (n_nodes + 255) / 256; g->nb_vec = (6 * n_nodes + 255) / 256; g->nb_edges = (n_edges + 255) / 256;
