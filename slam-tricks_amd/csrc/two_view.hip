@@ -22,28 +22,6 @@ namespace {
 
 constexpr int QR_THREADS = 128;
 
-// fold the row a (9 entries) into the packed upper-triangular R (row k holds R[k][k..8])
-__host__ __device__ inline void givens_fold(double (&R)[45], double (&a)[9]) {
-    int idx = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const double ak = a[k];
-        if (ak != 0.0) {
-            const double d = R[idx];
-            const double r = sqrt(d * d + ak * ak);
-            const double c = d / r, s = ak / r;
-            R[idx] = r;
-#pragma unroll
-            for (int j = k + 1; j < 9; ++j) {
-                const double x = R[idx + j - k], y = a[j];
-                R[idx + j - k] = c * x + s * y;
-                a[j] = c * y - s * x;
-            }
-        }
-        idx += 9 - k;
-    }
-}
-
 __global__ __launch_bounds__(QR_THREADS) void tv_qr_kernel(int n, const double* __restrict__ f1, const double* __restrict__ f2,
                                                            double* __restrict__ Rout) {
     __shared__ double sh[QR_THREADS][45];

@@ -1,0 +1,210 @@
+"""The host closed forms of slam-tricks_amd/csrc/small_linalg.hpp -- smallest_right_singular_vector, svd3 and the Givens row fold
+that two_view.hip shares with its kernel -- compiled with g++ into tests/cpp/small_linalg_driver.cpp and compared with a 50-digit
+reference (tests/two_view_ref.py).  No device.
+
+Bounds.  A null vector is held to 64 EPS sigma_1 / sigma_(n-1): EPS sigma_1 / sigma_(n-1) is the first-order perturbation bound
+of the null vector of a matrix known to one rounding, 64 the ceiling for a backward-stable method (a few dozen rotations touch
+every entry).  svd3 is held to 8 EPS, as orthogonality and as a relative residual."""
+import json
+import os
+import subprocess
+
+import mpmath as mp
+import numpy as np
+import pytest
+
+import mp_ref as M
+import two_view_cases as TC
+import two_view_ref as TR
+import zhang_init as Z
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+EPS = TR.EPS
+C_NULL = 64.0               # the derived ceiling, see above
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("small_linalg") / "small_linalg_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "tests", "cpp", "small_linalg_driver.cpp"), "-o", exe])
+
+    def run(cmd, *mats):
+        """one command; the matrices go over as %a hex doubles and the answer comes back the same way"""
+        text = cmd + "\n" + "\n".join(" ".join(float(x).hex() for x in np.asarray(m, dtype=float).ravel()) for m in mats) + "\n"
+        p = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
+        assert p.returncode == 0, (cmd, p.returncode, p.stderr[-500:])
+        return np.array([float.fromhex(w) for w in p.stdout.split()])
+    return run
+
+
+def _err_up_to_sign(v, ref):
+    ref = TR.f64(ref)
+    return np.abs(np.sign(v @ ref) * v - ref).max()
+
+
+def _null_unit(sig):
+    """EPS sigma_1 / sigma_(n-1)"""
+    return EPS * float(sig[0] / sig[-2])
+
+
+# ---------------------------------------------------------------- smallest_right_singular_vector
+def _small_ids():
+    return [c for c in TC.f_case_ids() if int(c.partition("-")[0][1:]) <= 513]
+
+
+@pytest.mark.parametrize("cid", _small_ids())
+def test_null_vector_of_the_epipolar_system(driver, cid):
+    c = TC.f_case(cid)
+    A = TC.system(c["f1"], c["f2"])
+    ref, sig = TR.null_vector(A)
+    u = _null_unit(sig)
+    assert EPS * float(sig[0] / sig[-2]) ** 2 >= 100 * C_NULL * u, "the case cannot tell a normal-equations method from this one"
+    Ap = np.vstack([A, np.zeros((max(0, 9 - len(A)), 9))])          # the Jacobi wants m >= n: eight rows get a ninth of zeros
+    v = driver(f"srsv {len(Ap)} 9", Ap)
+    err = _err_up_to_sign(v, ref)
+    print(f"{cid}: srsv error {err / u:.3g} u, u = EPS s1/s8 = {u:.3g}")
+    assert err <= C_NULL * u, f"{cid}: {err / u:.3g} u > {C_NULL} u"
+    # the path two_view.hip takes: fold the rows into the triangular factor, then the null vector of that factor
+    out = driver(f"fold {len(A)}", A)
+    err = _err_up_to_sign(out[45:], ref)
+    print(f"{cid}: fold + srsv error {err / u:.3g} u")
+    assert err <= C_NULL * u, f"{cid}: fold + srsv {err / u:.3g} u > {C_NULL} u"
+
+
+@pytest.fixture(scope="module")
+def calib():
+    with open(os.path.join(GOLDEN, "known_answers.json")) as f:
+        ka = json.load(f)["st3_calibration"]
+    return Z.read_corners(os.path.join(GOLDEN, "st3_calib"), ka["board_square_m"])
+
+
+def _homography_system(img, obj):
+    """calib_io.cpp, stba_zhang_init: rows [x y 1 0 0 0 -ux -uy -u], [0 0 0 x y 1 -vx -vy -v]"""
+    n = len(img)
+    A = np.zeros((2 * n, 9))
+    x, y, u, v = obj[:, 0], obj[:, 1], img[:, 0], img[:, 1]
+    A[0::2, 0] = x; A[0::2, 1] = y; A[0::2, 2] = 1; A[0::2, 6] = -u * x; A[0::2, 7] = -u * y; A[0::2, 8] = -u
+    A[1::2, 3] = x; A[1::2, 4] = y; A[1::2, 5] = 1; A[1::2, 6] = -v * x; A[1::2, 7] = -v * y; A[1::2, 8] = -v
+    return A
+
+
+def _intrinsics_system(Hs):
+    """the 2V x 5 system of the zero-skew image of the absolute conic (calib.cpp:95-140)"""
+    def cof(H, i, j):
+        hi, hj = H[:, i], H[:, j]
+        return np.array([hi[0] * hj[0], hi[2] * hj[0] + hi[0] * hj[2], hi[1] * hj[1], hi[2] * hj[1] + hi[1] * hj[2], hi[2] * hj[2]])
+    C = []
+    for H in Hs:
+        C.append(cof(H, 0, 1))
+        C.append(cof(H, 0, 0) - cof(H, 1, 1))
+    return np.array(C)
+
+
+def test_null_vectors_of_the_calibration_systems(driver, calib):
+    """measured corners: sigma_n is not zero here, and what bounds the null vector's error is the GAP, so the unit is
+    EPS sigma_1 sigma_(n-1) / (sigma_(n-1)^2 - sigma_n^2) -- which is EPS sigma_1 / sigma_(n-1) wherever sigma_n is small"""
+    obj, img = calib
+    Hs = []
+    for v in range(len(obj)):
+        A = _homography_system(img[v], obj[v])
+        ref, sig = TR.null_vector(A)
+        u = EPS * float(sig[0] * sig[-2] / (sig[-2] ** 2 - sig[-1] ** 2))
+        h = driver(f"srsv {len(A)} 9", A)
+        err = _err_up_to_sign(h, ref)
+        print(f"view {v}: homography error {err / u:.3g} u, u = {u:.3g}, s9/s8 = {float(sig[-1] / sig[-2]):.3g}")
+        assert err <= C_NULL * u, f"view {v}: {err / u:.3g} u"
+        Hs.append(h.reshape(3, 3))
+    C = _intrinsics_system(Hs)
+    ref, sig = TR.null_vector(C)
+    u = EPS * float(sig[0] * sig[-2] / (sig[-2] ** 2 - sig[-1] ** 2))
+    b = driver(f"srsv {len(C)} 5", C)
+    err = _err_up_to_sign(b, ref)
+    print(f"intrinsics: error {err / u:.3g} u, u = {u:.3g}")
+    assert err <= C_NULL * u, f"intrinsics: {err / u:.3g} u"
+
+
+# ---------------------------------------------------------------- svd3
+def _essential(rng, s3=0.0):
+    """U diag(1, 1, s3) V^T built at 50 digits from two random rotations, rounded to doubles"""
+    U = M.so3_exp(M.axis_angle(rng, rng.uniform(0.1, 3.0)))
+    V = M.so3_exp(M.axis_angle(rng, rng.uniform(0.1, 3.0)))
+    S = [[mp.mpf(1), 0, 0], [0, mp.mpf(1) if s3 is not None else 0, 0], [0, 0, mp.mpf(s3 or 0)]]
+    return TR.f64(M.mm(M.mm(U, S), M.tr(V)))
+
+
+def _svd3_inputs():
+    rng = np.random.default_rng(3)
+    out = [(f"random{i}", rng.normal(size=(3, 3)), None) for i in range(4)]
+    out += [(f"rank2_{i}", _essential(rng), "rank2") for i in range(4)]
+    out += [("s3_1e-11", _essential(rng, 1e-11), None), ("s3_1e-13", _essential(rng, 1e-13), "rank2")]
+    a, b = rng.normal(size=3), rng.normal(size=3)
+    out += [("rank1", np.outer(a, b), None), ("rank1_exact", np.outer([1.0, 2.0, 2.0], [0.0, 0.0, 3.0]), None), ("zero", np.zeros((3, 3)), None)]
+    out += [("random_1e+150", rng.normal(size=(3, 3)) * 1e150, None), ("random_1e-150", rng.normal(size=(3, 3)) * 1e-150, None)]
+    out += [("rank2_1e+150", _essential(rng) * 1e150, "rank2"), ("rank2_1e-150", _essential(rng) * 1e-150, "rank2")]
+    return out
+
+
+@pytest.mark.parametrize("name,mat,kind", _svd3_inputs(), ids=[x[0] for x in _svd3_inputs()])
+def test_svd3(driver, name, mat, kind):
+    out = driver("svd3", mat)
+    U, s, V = out[:9].reshape(3, 3), out[9:12], out[12:].reshape(3, 3)
+    assert np.all(np.isfinite(out))
+    assert s[0] >= s[1] >= s[2] >= 0.0, s
+    eV, eU = np.abs(V.T @ V - np.eye(3)).max(), np.abs(U.T @ U - np.eye(3)).max()
+    nM = np.linalg.norm(mat)
+    res = np.abs((U * s) @ V.T - mat).max()
+    print(f"{name}: V^T V - I = {eV / EPS:.3g} EPS, U^T U - I = {eU / EPS:.3g} EPS, residual {res / (EPS * nM) if nM else 0:.3g} EPS |M|")
+    assert eV <= 8 * EPS and eU <= 8 * EPS
+    assert res <= 8 * EPS * nM
+    if kind == "rank2":
+        # t of the two-view decomposition is this column: against the left null vector of the 50-digit SVD.  Its first-order
+        # perturbation bound is EPS s1 / s2 (= EPS here, s1 = s2); 8 as above
+        Ur, sr, _ = TR.svd3(mat.tolist())
+        u3 = TR.f64([Ur[r][2] for r in range(3)])
+        err = np.abs(np.sign(u3 @ U[:, 2]) * U[:, 2] - u3).max()
+        print(f"{name}: s3/s1 = {s[2] / s[0]:.3g} ({'cross-product' if not s[2] > 1e-12 * s[0] else 'Jacobi'} branch), u3 error {err / EPS:.3g} EPS")
+        assert err <= 8 * EPS * float(sr[0] / sr[1]), f"u3 off by {err / EPS:.3g} EPS"
+
+
+# ---------------------------------------------------------------- the fold
+def _unpack(R45):
+    R = np.zeros((9, 9))
+    R[np.triu_indices(9)] = R45
+    return R
+
+
+@pytest.mark.parametrize("cid", ["n9", "n129", "n513", "n513-K2"])
+def test_fold_gives_the_cholesky_factor(driver, cid):
+    """R of the fold against the Cholesky factor of A^T A at 50 digits, row by row up to sign.  Rows 0..7 are the factor of
+    the first eight columns and of the part of the ninth they explain; the bound is the one of the null vector, relative to
+    the largest entry of R.  R[8][8] is sigma_9-sized and carries no digits: it is held to the same ABSOLUTE bound only."""
+    c = TC.f_case(cid)
+    A = TC.system(c["f1"], c["f2"])
+    G = TR.gram(A)
+    _, sig = TR._null_and_sigmas(G, 9)
+    Rref = TR.f64(TR.cholesky_upper(G))
+    R = _unpack(driver(f"fold {len(A)}", A)[:45])
+    sgn = np.sign(np.diag(R)); sgn[sgn == 0] = 1.0
+    err = np.abs(sgn[:, None] * R - Rref).max()
+    bound = C_NULL * _null_unit(sig) * np.abs(Rref).max()
+    print(f"{cid}: fold vs Cholesky {err / (bound / C_NULL):.3g} u |R|")
+    assert err <= bound, f"{cid}: {err / (bound / C_NULL):.3g} u |R| > {C_NULL}"
+
+
+def test_fold_ignores_zero_rows_and_takes_rows_with_zeros(driver, calib):
+    obj, img = calib
+    A = _homography_system(img[0], obj[0])          # every row has three exact zeros
+    G = TR.gram(A)
+    _, sig = TR._null_and_sigmas(G, 9)
+    Rref = TR.f64(TR.cholesky_upper(G))
+    out = driver(f"fold {len(A)}", A)
+    R = _unpack(out[:45])
+    sgn = np.sign(np.diag(R)); sgn[sgn == 0] = 1.0
+    u = EPS * float(sig[0] * sig[-2] / (sig[-2] ** 2 - sig[-1] ** 2))
+    assert np.abs(sgn[:, None] * R - Rref).max() <= C_NULL * u * np.abs(Rref).max()
+    # all-zero rows, first, last and in between: not one bit changes
+    Z0 = np.zeros((1, 9))
+    B = np.vstack([Z0, A[:5], Z0, Z0, A[5:], Z0])
+    assert np.array_equal(driver(f"fold {len(B)}", B), out)
+    assert np.array_equal(driver("fold 3", np.zeros((3, 9)))[:45], np.zeros(45))
