@@ -470,6 +470,36 @@ int stba_pg_solve(stba_pg* pg, const stba_lm_options* opt, const stba_pcg_option
 /* the linear-solver side of the last stba_pg_solve of this engine */
 int stba_pg_last_pcg_summary(stba_pg* pg, stba_pcg_summary* out);
 
+/* --- pose-graph edge information matrices --------------------------------------------------- */
+/* An engine as created weights every edge by the identity: cost = 1/2 sum |r_e|^2.  With per-edge weights the cost is
+ * 1/2 sum |W_e r_e|^2 = 1/2 sum r_e^T Omega_e r_e, Omega_e = W_e^T W_e; W_e (6 x 6, the square-root information) multiplies the
+ * residual and both Jacobians of the edge inside the linearisation kernel, so everything behind it works on the weighted problem:
+ *   stba_pg_evaluate               hands back the WHITENED r = W r, Ji = W Ji, Jj = W Jj and the weighted cost;
+ *   stba_pg_solve                  minimises the weighted cost;
+ *   stba_pg_covariance[_columns]   return (J^T Omega J)^-1;
+ *   stba_pg_time_kernels           times the whitening linearisation.
+ * Rows and columns are in the tangent order of the residual, [rho(3), theta(3)].
+ * CONVENTION of the information form: Omega = L L^T (Cholesky, L lower triangular) and W = L^T, so that W^T W = Omega.  This is
+ * NOT the matrixL() habit of Ceres' pose_graph_3d example (residual <- L r, whose cost is r^T L^T L r); the two agree only for
+ * a diagonal Omega.  A caller who wants that cost passes L to stba_pg_set_sqrt_information.
+ *   stba_pg_set_information       information[m*36]: a symmetric positive definite 6x6 per edge, row-major, in the order of
+ *                                 stba_pg_create's edges (of THIS engine's edge shard where the edges are sharded); the lower
+ *                                 triangle is factored on the device, in double-double arithmetic, so that W is the correctly
+ *                                 rounded factor of the matrix given.  An edge whose matrix has a pivot that is not positive, or
+ *                                 any entry that is not finite: STBA_ERR_NOT_POSITIVE_DEFINITE, stba_last_error() names the
+ *                                 smallest such edge.
+ *   stba_pg_set_sqrt_information  sqrt_information[m*36]: any finite W per edge, row-major (it need be neither triangular nor
+ *                                 symmetric).  An entry that is not finite: STBA_ERR_INVALID_ARGUMENT, the edge named likewise.
+ *   NULL for either               back to the identity: the array is released and the engine is bit for bit the one that never
+ *                                 had weights (it runs the kernel without the whitening).
+ *   stba_pg_has_information       *has = 1 while the engine holds weights.
+ * A call that fails leaves the engine with the weights it had.  A call that succeeds invalidates the current linearisation: the
+ * next solve, evaluation or covariance starts from a fresh one.  Both setters are allowed with an all-reduce hook or communicator
+ * set.  STBA_VERSION is unchanged: test for the symbols. */
+int stba_pg_set_information(stba_pg* pg, const double* information);
+int stba_pg_set_sqrt_information(stba_pg* pg, const double* sqrt_information);
+int stba_pg_has_information(const stba_pg* pg, int* has);
+
 /* --- pose-graph covariance ---------------------------------------------------------------- */
 /* C = (J^T J)^-1 of the undamped, unscaled problem at the engine's current poses, in the engine's tangent coordinates (per node
  * [rho, theta] of T <- T exp(delta)); not multiplied by a residual variance (the definition of stba_ba_covariance_compute); constant

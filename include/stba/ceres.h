@@ -477,8 +477,17 @@ public:
 class RelativePoseFactor : public SizedCostFunction<6, 7, 7> {
 public:
     explicit RelativePoseFactor(const double* measurement) { std::memcpy(z_, measurement, sizeof z_); }
+    // sqrt_information: W, 6 x 6 row-major in the tangent order [rho, theta] of the residual -- the edge becomes r = W log(...), its
+    // cost 1/2 r^T (W^T W) r.  Any finite W; for an information matrix Omega = L L^T the device engine's convention is W = L^T
+    // (stba_pg_set_information in include/stba.h)
+    RelativePoseFactor(const double* measurement, const double* sqrt_information) : has_w_(true) {
+        std::memcpy(z_, measurement, sizeof z_);
+        std::memcpy(w_, sqrt_information, sizeof w_);
+    }
     static RelativePoseFactor* Create(const double* measurement) { return new RelativePoseFactor(measurement); }
+    static RelativePoseFactor* Create(const double* measurement, const double* sqrt_information) { return new RelativePoseFactor(measurement, sqrt_information); }
     const double* measurement() const { return z_; }
+    const double* sqrt_information() const { return has_w_ ? w_ : nullptr; }      // nullptr: made without one (identity)
     template <typename T>
     bool operator()(const T* Ti, const T* Tj, T* r) const {
         T Z[7], Zi[7], Tii[7], A[7], E[7];
@@ -488,7 +497,14 @@ public:
         se3::Compose(Tii, Tj, A);
         se3::Compose(Zi, A, E);
         if (E[3] < T(0.0)) for (int k = 0; k < 4; ++k) E[k] = -E[k];       // shortest rotation
-        se3::Log(E, r);
+        if (!has_w_) { se3::Log(E, r); return true; }
+        T xi[6];
+        se3::Log(E, xi);
+        for (int a = 0; a < 6; ++a) {
+            T s = T(0.0);
+            for (int k = 0; k < 6; ++k) s = s + T(w_[a * 6 + k]) * xi[k];
+            r[a] = s;
+        }
         return true;
     }
     bool Evaluate(double const* const* p, double* residuals, double** jacobians) const override {
@@ -506,6 +522,8 @@ public:
     }
 private:
     double z_[7];
+    double w_[36] = {0};
+    bool has_w_ = false;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1462,6 +1480,7 @@ struct PoseGraphLayout {
     std::vector<int> node_block, ei, ej;   // node -> parameter block index; the edges
     std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
     std::vector<unsigned char> fixed;      // [n]
+    std::vector<double> sqrt_info;         // [m][36] the factors' W, the identity for a factor without one; EMPTY if no factor has one
 };
 inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
     if (p->residuals().empty()) return false;
@@ -1481,6 +1500,16 @@ inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
         }
         ei.push_back(ends[0]); ej.push_back(ends[1]);
         meas.insert(meas.end(), f->measurement(), f->measurement() + 7);
+        if (f->sqrt_information() && L->sqrt_info.empty()) {       // the first weighted factor: identity for every edge before it
+            L->sqrt_info.assign(ei.size() * 36, 0.0);
+            for (size_t e = 0; e < ei.size(); ++e) for (int a = 0; a < 6; ++a) L->sqrt_info[e * 36 + a * 7] = 1.0;
+            std::memcpy(&L->sqrt_info[(ei.size() - 1) * 36], f->sqrt_information(), 36 * sizeof(double));
+        } else if (!L->sqrt_info.empty()) {
+            const size_t at = L->sqrt_info.size();
+            L->sqrt_info.resize(at + 36, 0.0);
+            if (f->sqrt_information()) std::memcpy(&L->sqrt_info[at], f->sqrt_information(), 36 * sizeof(double));
+            else for (int a = 0; a < 6; ++a) L->sqrt_info[at + a * 7] = 1.0;
+        }
     }
     const int n = (int)node_block.size();
     L->poses.assign((size_t)n * 7, 0.0);
@@ -1501,6 +1530,11 @@ inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary
     stba_pg* pg = nullptr;
     int rc = stba_pg_create(&pg, n, m, poses.data(), ei.data(), ej.data(), meas.data(), fixed.data(), nullptr);
     if (rc != STBA_OK) { sum->termination_type = FAILURE; sum->message = std::string("stba_pg_create: ") + stba_last_error(); return true; }
+    if (!L.sqrt_info.empty() && (rc = stba_pg_set_sqrt_information(pg, L.sqrt_info.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_pg_set_sqrt_information: ") + stba_last_error();
+        stba_pg_destroy(pg);
+        return true;
+    }
     stba_lm_options co = ToC(o);
     stba_lm_summary cs;
     std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
@@ -1817,6 +1851,8 @@ private:
         if (stba_pg_create(&pg, n, m, G.poses.data(), G.ei.data(), G.ej.data(), G.meas.data(), G.fixed.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_pg_create: ") + stba_last_error());
         struct Destroy { stba_pg* g; ~Destroy() { stba_pg_destroy(g); } } destroy{pg};
+        if (!G.sqrt_info.empty() && stba_pg_set_sqrt_information(pg, G.sqrt_info.data()) != STBA_OK)
+            return Fail(std::string("stba_pg_set_sqrt_information: ") + stba_last_error());
         std::vector<double> blk(pairs.size() * 36);
         if (stba_pg_covariance(pg, (int)pairs.size(), na.data(), nb.data(), nullptr, blk.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_pg_covariance: ") + stba_last_error());

@@ -81,7 +81,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply",
            "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary",
            "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary",
-           "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check"]
+           "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check",
+           "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information"]
 
 
 def lib():
@@ -542,15 +543,47 @@ def pg_gauge_check(n_nodes, edge_i, edge_j, node_fixed=None):
 class PGEngine:
     """Device-resident pose graph (BASELINE config C4, build-defined)."""
 
-    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None):
+    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None, information=None, sqrt_information=None):
+        """information / sqrt_information: (m, 6, 6) per-edge weights (set_information / set_sqrt_information); at most one of them"""
         self._h = C.c_void_p()
+        if information is not None and sqrt_information is not None:
+            raise ValueError("PGEngine: give information or sqrt_information, not both")
         poses = _f64(poses).reshape(-1, 7)
         ei = np.ascontiguousarray(edge_i, dtype=np.int32); ej = np.ascontiguousarray(edge_j, dtype=np.int32)
         meas = _f64(meas).reshape(-1, 7)
         nf = None if node_fixed is None else np.ascontiguousarray(node_fixed, dtype=np.uint8)
         self.n, self.m = len(poses), len(ei)
+        weights = None if information is None and sqrt_information is None else \
+            self._edge_blocks(information if information is not None else sqrt_information)
         _chk(lib().stba_pg_create(C.byref(self._h), self.n, self.m, _p(poses), _p(ei), _p(ej), _p(meas), _p(nf),
                                   C.c_void_p(stream or 0)), "stba_pg_create")
+        if information is not None:
+            self.set_information(weights)
+        elif sqrt_information is not None:
+            self.set_sqrt_information(weights)
+
+    def _edge_blocks(self, a):
+        a = _f64(a)
+        if a.size != self.m * 36 or a.shape[0] != self.m:
+            raise ValueError(f"PGEngine: per-edge weights must have shape ({self.m}, 6, 6), got {a.shape}")
+        return a.reshape(self.m, 36)
+
+    def set_information(self, information):
+        """per-edge information matrices Omega (m, 6, 6), symmetric positive definite, tangent order [rho, theta]: the cost becomes
+        1/2 sum r^T Omega r.  Factored on the device as Omega = L L^T, W = L^T (include/stba.h).  None: back to the identity."""
+        a = None if information is None else self._edge_blocks(information)
+        _chk(lib().stba_pg_set_information(self._h, _p(a)), "stba_pg_set_information")
+
+    def set_sqrt_information(self, sqrt_information):
+        """per-edge square-root information W (m, 6, 6), any finite matrices: the cost becomes 1/2 sum |W r|^2.  None: identity."""
+        a = None if sqrt_information is None else self._edge_blocks(sqrt_information)
+        _chk(lib().stba_pg_set_sqrt_information(self._h, _p(a)), "stba_pg_set_sqrt_information")
+
+    @property
+    def has_information(self):
+        has = C.c_int()
+        _chk(lib().stba_pg_has_information(self._h, C.byref(has)), "stba_pg_has_information")
+        return bool(has.value)
 
     def close(self):
         if self._h:

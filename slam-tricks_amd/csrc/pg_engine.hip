@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <functional>
 #include <vector>
 
@@ -161,13 +162,33 @@ struct PcgState {
 enum { PX_RR0 = 0, PX_RR = 1, PX_ITERS = 2, PX_DONE = 3, PX_HIT_CAP = 4, PX_COUNT = 5 };
 
 // ---------------------------------------------------------------- kernels
+// x <- W x for `cols` columns of a 6-row matrix held row-major with row stride `ld` (a 6-vector: cols = ld = 1): one column at a
+// time through a 6-vector of temporaries, so that the product needs W (36) and six doubles on top of what is whitened in place
+__device__ inline void pg_whiten_cols(const double* W, double* x, int cols, int ld) {
+    for (int c = 0; c < cols; ++c) {
+        double t[6];
+        for (int a = 0; a < 6; ++a) {
+            double s = 0.0;
+            for (int k = 0; k < 6; ++k) s += W[a * 6 + k] * x[k * ld + c];
+            t[a] = s;
+        }
+        for (int a = 0; a < 6; ++a) x[a * ld + c] = t[a];
+    }
+}
+
+// INFO = false: every edge weighted by the identity -- the kernel as it was before edges had information matrices; Winfo is not
+// read.  INFO = true: the residual and both Jacobians are whitened by the edge's square-root information W_e (Winfo[k * n_edges + e],
+// laid out like Ji) right behind pg_edge: cost, stores, the constant-node zeroing and the contrib block below all see W r, W Ji,
+// W Jj, and so does every consumer of what this kernel writes.  Two instantiations and not a runtime branch: an engine without
+// weights runs the instruction stream it ran before.
+template <bool INFO>
 __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const double* __restrict__ poses,
                                                            const int* __restrict__ ei, const int* __restrict__ ej,
                                                            const double* __restrict__ meas,
                                                            const unsigned char* __restrict__ fixed, int with_jac,
                                                            double* __restrict__ r, double* __restrict__ Ji,
                                                            double* __restrict__ Jj, double* __restrict__ partial,
-                                                           double* __restrict__ contrib) {
+                                                           double* __restrict__ contrib, const double* __restrict__ Winfo) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     double c = 0.0;
     if (e < n_edges) {
@@ -175,6 +196,12 @@ __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const do
         double Ti[7], Tj[7], Z[7], re[6], ji[36], jj[36];
         for (int k = 0; k < 7; ++k) { Ti[k] = poses[(size_t)i * 7 + k]; Tj[k] = poses[(size_t)j * 7 + k]; Z[k] = meas[(size_t)e * 7 + k]; }
         pg_edge(Ti, Tj, Z, re, with_jac ? ji : nullptr, jj);
+        if (INFO) {
+            double We[36];
+            for (int k = 0; k < 36; ++k) We[k] = Winfo[(size_t)k * n_edges + e];
+            pg_whiten_cols(We, re, 1, 1);
+            if (with_jac) { pg_whiten_cols(We, ji, 6, 6); pg_whiten_cols(We, jj, 6, 6); }
+        }
         for (int k = 0; k < 6; ++k) c += re[k] * re[k];
         if (r) for (int k = 0; k < 6; ++k) r[(size_t)e * 6 + k] = re[k];
         if (with_jac) {
@@ -207,6 +234,78 @@ __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const do
     double out2[2];
     block_sum2(c, 0.0, out2);
     if (threadIdx.x == 0) partial[blockIdx.x] = out2[0];
+}
+
+// ---- per-edge weights: what the caller gives ([m][36] row-major) -> the component-major array the linearisation reads
+// Double-double arithmetic (a value as an unevaluated sum hi + lo) for the Cholesky factor below: the factor is made once per call of
+// stba_pg_set_information and is a 6 x 6 per edge, so its cost does not matter, while an FP64 factorisation loses
+// about cond(Omega) eps in its last pivots -- an error the caller could not tell from one of the solver's.
+struct dd { double hi, lo; };
+__device__ inline dd dd_make(double a, double b) { const double s = a + b; return {s, b - (s - a)}; }      // |a| >= |b|
+__device__ inline dd dd_add(dd x, dd y) {
+    const double s = x.hi + y.hi, bb = s - x.hi;
+    const double e = ((x.hi - (s - bb)) + (y.hi - bb)) + (x.lo + y.lo);
+    return dd_make(s, e);
+}
+__device__ inline dd dd_neg(dd x) { return {-x.hi, -x.lo}; }
+__device__ inline dd dd_mul(dd x, dd y) {
+    const double p = x.hi * y.hi;
+    const double e = fma(x.hi, y.hi, -p) + (x.hi * y.lo + x.lo * y.hi);
+    return dd_make(p, e);
+}
+__device__ inline dd dd_div(dd x, dd y) {
+    const double q1 = x.hi / y.hi;
+    dd r = dd_add(x, dd_neg(dd_mul(y, dd{q1, 0.0})));
+    const double q2 = r.hi / y.hi;
+    r = dd_add(r, dd_neg(dd_mul(y, dd{q2, 0.0})));
+    const double q3 = r.hi / y.hi;
+    return dd_add(dd_make(q1, q2), dd{q3, 0.0});
+}
+__device__ inline dd dd_sqrt(dd x) {           // x.hi > 0
+    const double s = sqrt(x.hi);
+    const double p = s * s;
+    const dd r = dd_add(x, dd{-p, -fma(s, s, -p)});
+    return dd_make(s, r.hi / (2.0 * s));
+}
+
+// One edge per lane.  sqrt_form = 0: `in` holds an information matrix Omega_e (symmetric positive definite; the lower triangle is
+// factored), Omega = L L^T by an unblocked Cholesky in double-double, W_e = L^T rounded to FP64.  sqrt_form = 1: `in` holds W_e itself,
+// which is only transposed into the component-major array.  A non-finite entry anywhere in the 36, or a pivot that is not a positive
+// finite number, refuses the edge: the smallest such edge index ends up in *bad (which the host set to INT_MAX), and the host
+// throws the whole array away.
+__global__ __launch_bounds__(256) void pg_information_kernel(int n_edges, const double* __restrict__ in, int sqrt_form,
+                                                             double* __restrict__ Wout, int* __restrict__ bad) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    double A[36];
+    bool ok = true;
+    for (int k = 0; k < 36; ++k) { A[k] = in[(size_t)e * 36 + k]; ok = ok && isfinite(A[k]); }
+    double Wl[36];
+    if (sqrt_form) {
+        for (int k = 0; k < 36; ++k) Wl[k] = A[k];
+    } else {
+        dd L[21];                                  // lower triangle, row a at a (a + 1) / 2
+        for (int k = 0; k < 21; ++k) L[k] = dd{0.0, 0.0};
+        for (int k = 0; k < 36; ++k) Wl[k] = 0.0;
+        for (int c = 0; c < 6 && ok; ++c) {
+            dd d = dd{A[c * 7], 0.0};
+            for (int k = 0; k < c; ++k) d = dd_add(d, dd_neg(dd_mul(L[c * (c + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
+            if (!(d.hi > 0.0) || !isfinite(d.hi)) { ok = false; break; }
+            const dd lcc = dd_sqrt(d);
+            L[c * (c + 1) / 2 + c] = lcc;
+            Wl[c * 7] = lcc.hi;
+            for (int a = c + 1; a < 6; ++a) {
+                dd v = dd{A[a * 6 + c], 0.0};
+                for (int k = 0; k < c; ++k) v = dd_add(v, dd_neg(dd_mul(L[a * (a + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
+                v = dd_div(v, lcc);
+                L[a * (a + 1) / 2 + c] = v;
+                Wl[c * 6 + a] = v.hi;              // W = L^T
+            }
+        }
+        for (int k = 0; k < 36; ++k) ok = ok && isfinite(Wl[k]);
+    }
+    if (!ok) { atomicMin(bad, e); return; }
+    for (int k = 0; k < 36; ++k) Wout[(size_t)k * n_edges + e] = Wl[k];
 }
 
 // gradient and diagonal blocks: g_i += Ji^T r, Hd_i += Ji^T Ji (same for j), FP64 atomics
@@ -1352,6 +1451,9 @@ struct stba_pg {
     // host copies of the graph for stba_pg_covariance's gauge check (pg_covariance.hip), which runs before any device work
     std::vector<int> h_ei, h_ej;
     std::vector<unsigned char> h_fixed;
+    // per-edge square-root information W_e, component-major [36][m] like Ji (stba_pg_set_information / _sqrt_information); NULL: every
+    // edge weighted by the identity, and pg_linearize launches the kernel without the whitening
+    double* Winfo = nullptr;
 };
 
 namespace stba {
@@ -1363,7 +1465,7 @@ void pg_free(stba_pg* g) {
     F(g->part_b); F(g->part_c); F(g->part_d); F(g->fixed); F(g->scalar); F(g->node_start); F(g->end_code); F(g->u);
     F(g->end_node); F(g->AdP); F(g->Ac0); F(g->W); F(g->Ainv); F(g->inv_work); F(g->rc_part); F(g->zc); F(g->part_cz); F(g->part_u);
     F(g->scal_dev); F(g->cflag); F(g->state); F(g->contrib); F(g->Dc);
-    F(g->end_pos); F(g->end_rem); F(g->Bend); F(g->ubuf); F(g->pbuf); F(g->ustamp); F(g->pstamp);
+    F(g->end_pos); F(g->end_rem); F(g->Bend); F(g->ubuf); F(g->pbuf); F(g->ustamp); F(g->pstamp); F(g->Winfo);
     if (g->st2) { (void)hipStreamSynchronize(g->st2); chol_forget_stream(g->st2); (void)hipStreamDestroy(g->st2); }
     if (g->ev_in) (void)hipEventDestroy(g->ev_in);
     if (g->ev_read) (void)hipEventDestroy(g->ev_read);
@@ -1386,8 +1488,15 @@ double host_sum(hipStream_t st, const double* dev, int n, int stride, int off, s
 }
 
 int pg_linearize(stba_pg* g, int which, bool jac) {
-    hipLaunchKernelGGL(pg_linearize_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
-                       g->meas, g->fixed, jac ? 1 : 0, jac ? g->r : nullptr, g->Ji, g->Jj, g->part_e, jac ? g->contrib : nullptr);
+    // (an engine that holds square-root information runs the whitening instantiation, every other one the kernel without it)
+    if (g->Winfo)
+        hipLaunchKernelGGL(pg_linearize_kernel<true>, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
+                           g->meas, g->fixed, jac ? 1 : 0, jac ? g->r : nullptr, g->Ji, g->Jj, g->part_e, jac ? g->contrib : nullptr,
+                           (const double*)g->Winfo);
+    else
+        hipLaunchKernelGGL(pg_linearize_kernel<false>, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
+                           g->meas, g->fixed, jac ? 1 : 0, jac ? g->r : nullptr, g->Ji, g->Jj, g->part_e, jac ? g->contrib : nullptr,
+                           (const double*)nullptr);
     STBA_HIP(hipGetLastError());
     if (jac) g->bend_valid = false;
     return STBA_OK;
@@ -2104,6 +2213,54 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
             ps.coarse_failures = cf;
     }
     g->last_pcg = ps;
+    return STBA_OK;
+}
+
+// the two setters of the per-edge weights: `in` [m][36] -> a NEW component-major array on the device; only a call that succeeds
+// swaps it in (a refused one leaves the engine with the weights it had), NULL releases the array
+static int pg_set_weights(stba_pg* g, const double* in, int sqrt_form, const char* who) {
+    if (!g) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
+    double* Wnew = nullptr;
+    if (in) {
+        const size_t cnt = (size_t)g->m * 36;
+        double* stage = nullptr;
+        int* bad = nullptr;
+        int bad_h = INT_MAX;
+        auto F = [](void* p) { if (p) (void)hipFree(p); };
+        int rc = dev_alloc(&Wnew, cnt);
+        if (rc == STBA_OK) rc = dev_alloc(&stage, cnt);
+        if (rc == STBA_OK) rc = dev_alloc(&bad, 1);
+        if (rc == STBA_OK &&
+            (hipMemcpyAsync(stage, in, cnt * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
+             hipMemcpyAsync(bad, &bad_h, sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess))
+            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
+        if (rc == STBA_OK) {
+            hipLaunchKernelGGL(pg_information_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, (const double*)stage, sqrt_form, Wnew, bad);
+            if (hipGetLastError() != hipSuccess ||
+                hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, g->st) != hipSuccess ||
+                hipStreamSynchronize(g->st) != hipSuccess)
+                rc = fail(STBA_ERR_HIP, std::string(who) + ": the conversion kernel failed");
+        }
+        F(stage); F(bad);
+        if (rc == STBA_OK && bad_h != INT_MAX)
+            rc = sqrt_form ? fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": edge " + std::to_string(bad_h) + ": the square-root information has an entry that is not finite")
+                           : fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string(who) + ": edge " + std::to_string(bad_h) + ": the information matrix is not positive definite (or has an entry that is not finite)");
+        if (rc != STBA_OK) { F(Wnew); return rc; }
+    }
+    // (nothing of the engine may still be reading the old array or what was linearised with it)
+    STBA_HIP(hipStreamSynchronize(g->st));
+    if (g->st2) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; g->job_reads_pending = false; }
+    if (g->Winfo) (void)hipFree(g->Winfo);
+    g->Winfo = Wnew;
+    g->bend_valid = false; g->coarse_valid = false; g->ac0_valid = false;      // what pg_linearize and the solve's linearisation reset
+    return STBA_OK;
+}
+
+int stba_pg_set_information(stba_pg* g, const double* information) { return pg_set_weights(g, information, 0, "stba_pg_set_information"); }
+int stba_pg_set_sqrt_information(stba_pg* g, const double* sqrt_information) { return pg_set_weights(g, sqrt_information, 1, "stba_pg_set_sqrt_information"); }
+int stba_pg_has_information(const stba_pg* g, int* has) {
+    if (!g || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
+    *has = g->Winfo ? 1 : 0;
     return STBA_OK;
 }
 

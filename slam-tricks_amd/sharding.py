@@ -48,6 +48,9 @@ def make_pg_shard(scene, rank, world):
     out = dict(scene)
     for k in ("edge_i", "edge_j", "meas"):
         out[k] = scene[k][lo:hi]
+    for k in ("information", "sqrt_information"):      # per-edge weights travel with their edges
+        if scene.get(k) is not None:
+            out[k] = scene[k][lo:hi]
     out["lo"], out["hi"] = lo, hi
     return out
 
