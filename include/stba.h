@@ -500,6 +500,42 @@ int stba_pg_set_information(stba_pg* pg, const double* information);
 int stba_pg_set_sqrt_information(stba_pg* pg, const double* sqrt_information);
 int stba_pg_has_information(const stba_pg* pg, int* has);
 
+/* --- pose-graph robust loss functions ------------------------------------------------------- */
+/* Per edge a loss rho_e: cost = 1/2 sum rho_e(s_e), s_e = |W_e r_e|^2 (W_e the edge's square-root information, the identity without
+ * one).  The kinds are Ceres' (loss_function.h), with Ceres' rho, rho', rho'' and its lower clamp of rho' by DBL_MIN:
+ *   TRIVIAL          rho = s
+ *   HUBER(a)         s for s <= a^2, else 2 a sqrt(s) - a^2
+ *   SOFTLONE(a)      2 a^2 (sqrt(1 + s / a^2) - 1)
+ *   CAUCHY(a)        a^2 log(1 + s / a^2)
+ *   ARCTAN(a)        a atan2(s, a)
+ *   TOLERANT(a, b)   b log(1 + e^((s - a) / b)) - b log(1 + e^(-a / b)); s - a - b log(1 + e^(-a / b)) once (s - a) / b > 36.7
+ *   TUKEY(a)         (a^2 / 3) (1 - (1 - s / a^2)^3) for s <= a^2, else a^2 / 3 (rho' = rho'' = 0)
+ * and scale_e multiplies rho, rho' and rho'' (Ceres' ScaledLoss).  The linearisation kernel applies Ceres' corrector to the residual
+ * and both Jacobians of the edge behind the whitening, so everything behind it works on the robustified problem:
+ *   stba_pg_evaluate               hands back the CORRECTED r' and J' (Ceres' Problem::Evaluate with apply_loss_function = true:
+ *                                  J'^T r' = rho' J^T r) and the cost 1/2 sum rho;
+ *   stba_pg_solve                  minimises 1/2 sum rho;
+ *   stba_pg_covariance[_columns]   return (J'^T J')^-1, as Ceres' Covariance does;
+ *   stba_pg_time_kernels           times the correcting linearisation.
+ *   stba_pg_set_loss   kind[m] (STBA_LOSS_*), a[m], b[m], scale[m] in the order of stba_pg_create's edges (of THIS engine's edge shard
+ *                      where the edges are sharded).  b may be NULL if no edge is TOLERANT, a may be NULL if every edge is TRIVIAL,
+ *                      scale == NULL means 1 for every edge.  Entries of a and b that the edge's kind does not use are not read.
+ *                      Checked before anything is replaced: an unknown kind, an a (or, for TOLERANT, b) that is not finite and
+ *                      positive, a scale that is not finite or is negative: STBA_ERR_INVALID_ARGUMENT, stba_last_error() names the
+ *                      smallest such edge, and the engine keeps the table it had.
+ *                      kind == NULL removes the table: the engine is bit for bit the one that never had a loss (it runs the
+ *                      kernel without the corrector).  An edge of kind TRIVIAL and scale 1 is left untouched by the corrector.
+ *   stba_pg_has_loss   *has = 1 while the engine holds a table.
+ * A call that succeeds invalidates the current linearisation.  Allowed with an all-reduce hook or communicator set.  TUKEY can give
+ * every edge of a node the weight zero: the solve is covered by its damping; a covariance at such a point is refused by the
+ * conjugate gradient's own guards (STBA_ERR_NOT_POSITIVE_DEFINITE, or its iteration cap), the structural gauge check does not see it.  STBA_VERSION is unchanged: test for the symbols. */
+enum {
+    STBA_LOSS_TRIVIAL = 0, STBA_LOSS_HUBER = 1, STBA_LOSS_SOFTLONE = 2, STBA_LOSS_CAUCHY = 3, STBA_LOSS_ARCTAN = 4,
+    STBA_LOSS_TOLERANT = 5, STBA_LOSS_TUKEY = 6
+};
+int stba_pg_set_loss(stba_pg* pg, const int* kind, const double* a, const double* b, const double* scale);
+int stba_pg_has_loss(const stba_pg* pg, int* has);
+
 /* --- pose-graph covariance ---------------------------------------------------------------- */
 /* C = (J^T J)^-1 of the undamped, unscaled problem at the engine's current poses, in the engine's tangent coordinates (per node
  * [rho, theta] of T <- T exp(delta)); not multiplied by a residual variance (the definition of stba_ba_covariance_compute); constant

@@ -40,12 +40,14 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -125,10 +127,156 @@ enum TerminationType { CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_
 enum Ownership { DO_NOT_TAKE_OWNERSHIP, TAKE_OWNERSHIP };
 constexpr int DYNAMIC = -1;
 
-// The reference only passes nullptr (test_ceres.h:120, solver.hpp:267).  Robust losses are NOT implemented: a Problem that holds a
-// residual block with a non-null LossFunction is REFUSED by Solve() (FAILURE, parameters untouched, the reason in Summary::message and
-// on stderr) instead of being solved unweighted.
+// The reference only passes nullptr (test_ceres.h:120, solver.hpp:267).  Robust losses are implemented for POSE GRAPHS only: a Problem
+// that takes the "gpu-pg" route (every residual block a RelativePoseFactor) and whose losses are all the built-in classes below
+// (recognised by dynamic_cast) is solved with them -- the per-edge table goes to stba_pg_set_loss (include/stba.h), which applies Ceres'
+// corrector inside the device's linearisation kernel; Covariance on such a problem returns (J'^T J')^-1 as Ceres does.  Everything
+// else that holds a non-null LossFunction -- a bare LossFunction or a user subclass (this base class has no Evaluate to call), any
+// loss on a problem that takes a bundle-adjustment or the dense-callback route -- is REFUSED by Solve() and Covariance::Compute
+// (FAILURE, parameters untouched, the reason in Summary::message and on stderr) instead of being solved without the loss.
+// Not provided: ComposedLoss, LossFunctionWrapper; ScaledLoss wraps a built-in (or nullptr) one level deep.
 class LossFunction { public: virtual ~LossFunction() = default; };
+
+// Ceres' loss functions (loss_function.h): Evaluate(s, rho) gives rho(s), rho'(s), rho''(s) at s = |r|^2, the formulas of the device
+// kernel (pg_engine.hip) on the host.  The classes are final: a dynamic_cast to one of them means exactly that loss.
+class TrivialLoss final : public LossFunction {
+public:
+    void Evaluate(double s, double rho[3]) const { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }
+};
+class HuberLoss final : public LossFunction {
+public:
+    explicit HuberLoss(double a) : a_(a), b_(a * a) {}
+    void Evaluate(double s, double rho[3]) const {
+        if (s > b_) {
+            const double r = std::sqrt(s);
+            rho[0] = 2.0 * a_ * r - b_; rho[1] = std::max(DBL_MIN, a_ / r); rho[2] = -rho[1] / (2.0 * s);
+        } else { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }
+    }
+    double a() const { return a_; }
+private:
+    const double a_, b_;
+};
+class SoftLOneLoss final : public LossFunction {
+public:
+    explicit SoftLOneLoss(double a) : a_(a), b_(a * a), c_(1.0 / b_) {}
+    void Evaluate(double s, double rho[3]) const {
+        const double sum = 1.0 + s * c_, tmp = std::sqrt(sum);
+        rho[0] = 2.0 * b_ * (tmp - 1.0); rho[1] = std::max(DBL_MIN, 1.0 / tmp); rho[2] = -(c_ * rho[1]) / (2.0 * sum);
+    }
+    double a() const { return a_; }
+private:
+    const double a_, b_, c_;
+};
+class CauchyLoss final : public LossFunction {
+public:
+    explicit CauchyLoss(double a) : a_(a), b_(a * a), c_(1.0 / b_) {}
+    void Evaluate(double s, double rho[3]) const {
+        const double sum = 1.0 + s * c_, inv = 1.0 / sum;
+        rho[0] = b_ * std::log(sum); rho[1] = std::max(DBL_MIN, inv); rho[2] = -c_ * (inv * inv);
+    }
+    double a() const { return a_; }
+private:
+    const double a_, b_, c_;
+};
+class ArctanLoss final : public LossFunction {
+public:
+    explicit ArctanLoss(double a) : a_(a), b_(1.0 / (a * a)) {}
+    void Evaluate(double s, double rho[3]) const {
+        const double sum = 1.0 + s * s * b_, inv = 1.0 / sum;
+        rho[0] = a_ * std::atan2(s, a_); rho[1] = std::max(DBL_MIN, inv); rho[2] = -2.0 * s * b_ * (inv * inv);
+    }
+    double a() const { return a_; }
+private:
+    const double a_, b_;
+};
+class TolerantLoss final : public LossFunction {
+public:
+    TolerantLoss(double a, double b) : a_(a), b_(b), c_(b * std::log(1.0 + std::exp(-a / b))) {}
+    void Evaluate(double s, double rho[3]) const {
+        const double x = (s - a_) / b_;
+        if (x > 36.7) { rho[0] = s - a_ - c_; rho[1] = 1.0; rho[2] = 0.0; }       // log(2^53): e^x + 1 == e^x from here on
+        else {
+            const double e_x = std::exp(x);
+            rho[0] = b_ * std::log(1.0 + e_x) - c_; rho[1] = std::max(DBL_MIN, e_x / (1.0 + e_x)); rho[2] = 0.5 / (b_ * (1.0 + std::cosh(x)));
+        }
+    }
+    double a() const { return a_; }
+    double b() const { return b_; }
+private:
+    const double a_, b_, c_;
+};
+class TukeyLoss final : public LossFunction {
+public:
+    explicit TukeyLoss(double a) : a_(a), a_squared_(a * a) {}
+    void Evaluate(double s, double rho[3]) const {
+        if (s <= a_squared_) {
+            const double value = 1.0 - s / a_squared_, value_sq = value * value;
+            rho[0] = a_squared_ / 3.0 * (1.0 - value_sq * value); rho[1] = value_sq; rho[2] = -2.0 / a_squared_ * value;
+        } else { rho[0] = a_squared_ / 3.0; rho[1] = 0.0; rho[2] = 0.0; }
+    }
+    double a() const { return a_; }
+private:
+    const double a_, a_squared_;
+};
+
+namespace internal {
+// the STBA_LOSS_* row of a built-in loss; false for anything else (a bare LossFunction, a user subclass, a ScaledLoss)
+inline bool BuiltinLossRow(const LossFunction* l, int* kind, double* a, double* b) {
+    *a = 1.0; *b = 1.0;
+    if (dynamic_cast<const TrivialLoss*>(l)) { *kind = STBA_LOSS_TRIVIAL; return true; }
+    if (auto* h = dynamic_cast<const HuberLoss*>(l)) { *kind = STBA_LOSS_HUBER; *a = h->a(); return true; }
+    if (auto* h = dynamic_cast<const SoftLOneLoss*>(l)) { *kind = STBA_LOSS_SOFTLONE; *a = h->a(); return true; }
+    if (auto* h = dynamic_cast<const CauchyLoss*>(l)) { *kind = STBA_LOSS_CAUCHY; *a = h->a(); return true; }
+    if (auto* h = dynamic_cast<const ArctanLoss*>(l)) { *kind = STBA_LOSS_ARCTAN; *a = h->a(); return true; }
+    if (auto* h = dynamic_cast<const TolerantLoss*>(l)) { *kind = STBA_LOSS_TOLERANT; *a = h->a(); *b = h->b(); return true; }
+    if (auto* h = dynamic_cast<const TukeyLoss*>(l)) { *kind = STBA_LOSS_TUKEY; *a = h->a(); return true; }
+    return false;
+}
+}  // namespace internal
+
+// a * rho(s) (rho', rho'' likewise) of a built-in loss, or a * s for a null one.  ONE level: a ScaledLoss around anything that is not one
+// of the classes above (another ScaledLoss, a user's loss) is not a built-in loss and is refused like a user's.
+class ScaledLoss final : public LossFunction {
+public:
+    ScaledLoss(const LossFunction* rho, double a, Ownership ownership) : rho_(rho), a_(a), ownership_(ownership) {}
+    ScaledLoss(const ScaledLoss&) = delete;
+    ScaledLoss& operator=(const ScaledLoss&) = delete;
+    ~ScaledLoss() override { if (ownership_ == TAKE_OWNERSHIP) delete rho_; }
+    void Evaluate(double s, double rho[3]) const {
+        int kind; double a, b;
+        if (!rho_) { rho[0] = a_ * s; rho[1] = a_; rho[2] = 0.0; return; }
+        if (!internal::BuiltinLossRow(rho_, &kind, &a, &b)) { rho[0] = rho[1] = rho[2] = std::numeric_limits<double>::quiet_NaN(); return; }
+        switch (kind) {
+        case STBA_LOSS_TRIVIAL: static_cast<const TrivialLoss*>(rho_)->Evaluate(s, rho); break;
+        case STBA_LOSS_HUBER: static_cast<const HuberLoss*>(rho_)->Evaluate(s, rho); break;
+        case STBA_LOSS_SOFTLONE: static_cast<const SoftLOneLoss*>(rho_)->Evaluate(s, rho); break;
+        case STBA_LOSS_CAUCHY: static_cast<const CauchyLoss*>(rho_)->Evaluate(s, rho); break;
+        case STBA_LOSS_ARCTAN: static_cast<const ArctanLoss*>(rho_)->Evaluate(s, rho); break;
+        case STBA_LOSS_TOLERANT: static_cast<const TolerantLoss*>(rho_)->Evaluate(s, rho); break;
+        default: static_cast<const TukeyLoss*>(rho_)->Evaluate(s, rho); break;
+        }
+        for (int k = 0; k < 3; ++k) rho[k] *= a_;
+    }
+    const LossFunction* inner() const { return rho_; }
+    double scale() const { return a_; }
+private:
+    const LossFunction* rho_;
+    const double a_;
+    const Ownership ownership_;
+};
+
+namespace internal {
+// kind, a, b, scale of a loss this layer knows: a built-in, or a ScaledLoss around a built-in or nullptr
+inline bool KnownLossRow(const LossFunction* l, int* kind, double* a, double* b, double* scale) {
+    *scale = 1.0;
+    if (auto* sl = dynamic_cast<const ScaledLoss*>(l)) {
+        *scale = sl->scale();
+        if (!sl->inner()) { *kind = STBA_LOSS_TRIVIAL; *a = 1.0; *b = 1.0; return true; }
+        return BuiltinLossRow(sl->inner(), kind, a, b);
+    }
+    return BuiltinLossRow(l, kind, a, b);
+}
+}  // namespace internal
 
 struct IterationSummary {
     int iteration = 0;
@@ -565,6 +713,7 @@ public:
     void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* const* blocks, size_t n_blocks) {
         Residual r;
         r.cost = cost;
+        r.loss = loss;
         const auto& sizes = cost->parameter_block_sizes();
         if (sizes.size() != n_blocks) { std::fprintf(stderr, "stba_ceres: block count mismatch\n"); std::abort(); }
         r.blocks.pool = &block_pool_; r.blocks.off = (int)block_pool_.size(); r.blocks.n = (int)n_blocks;
@@ -575,7 +724,7 @@ public:
         if (options_.cost_function_ownership == TAKE_OWNERSHIP && !cost->owned_by_problem_) { cost->owned_by_problem_ = true; owned_costs_.push_back(cost); }
         if (loss) { owned_losses_.insert(loss); ++num_loss_functions_; }
     }
-    int NumLossFunctions() const { return num_loss_functions_; }   // residual blocks added with a non-null LossFunction (Solve refuses them)
+    int NumLossFunctions() const { return num_loss_functions_; }   // residual blocks added with a non-null LossFunction (Solve takes them on gpu-pg only)
     void SetParameterBlockConstant(double* values) { find(values).constant = true; }
     void SetParameterBlockVariable(double* values) { find(values).constant = false; }
     void SetParameterLowerBound(double* values, int index, double lower) { Block& b = find(values); b.ensure_bounds(); b.lower[index] = lower; }
@@ -601,7 +750,7 @@ public:
         const int* begin() const { return pool->data() + off; }
         const int* end() const { return pool->data() + off + n; }
     };
-    struct Residual { CostFunction* cost = nullptr; BlockList blocks; };
+    struct Residual { CostFunction* cost = nullptr; LossFunction* loss = nullptr; BlockList blocks; };
     std::vector<Block>& blocks() { return blocks_; }
     std::vector<Residual>& residuals() { return residuals_; }
 
@@ -1481,6 +1630,11 @@ struct PoseGraphLayout {
     std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
     std::vector<unsigned char> fixed;      // [n]
     std::vector<double> sqrt_info;         // [m][36] the factors' W, the identity for a factor without one; EMPTY if no factor has one
+    // [m] each, the residual blocks' losses as stba_pg_set_loss takes them (TRIVIAL, scale 1 for a block without one); EMPTY if no
+    // block has a loss.  losses_known: every loss is a built-in (KnownLossRow)
+    std::vector<int> loss_kind;
+    std::vector<double> loss_a, loss_b, loss_scale;
+    bool losses_known = true;
 };
 inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
     if (p->residuals().empty()) return false;
@@ -1510,6 +1664,16 @@ inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
             if (f->sqrt_information()) std::memcpy(&L->sqrt_info[at], f->sqrt_information(), 36 * sizeof(double));
             else for (int a = 0; a < 6; ++a) L->sqrt_info[at + a * 7] = 1.0;
         }
+        if (r.loss && L->loss_kind.empty()) {                       // the first block with a loss: no loss for every edge before it
+            L->loss_kind.assign(ei.size() - 1, STBA_LOSS_TRIVIAL);
+            L->loss_a.assign(ei.size() - 1, 1.0); L->loss_b.assign(ei.size() - 1, 1.0); L->loss_scale.assign(ei.size() - 1, 1.0);
+        }
+        if (r.loss || !L->loss_kind.empty()) {
+            int kind = STBA_LOSS_TRIVIAL;
+            double a = 1.0, b = 1.0, scale = 1.0;
+            if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) L->losses_known = false;
+            L->loss_kind.push_back(kind); L->loss_a.push_back(a); L->loss_b.push_back(b); L->loss_scale.push_back(scale);
+        }
     }
     const int n = (int)node_block.size();
     L->poses.assign((size_t)n * 7, 0.0);
@@ -1535,6 +1699,11 @@ inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary
         stba_pg_destroy(pg);
         return true;
     }
+    if (!L.loss_kind.empty() && (rc = stba_pg_set_loss(pg, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_pg_set_loss: ") + stba_last_error();
+        stba_pg_destroy(pg);
+        return true;
+    }
     stba_lm_options co = ToC(o);
     stba_lm_summary cs;
     std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
@@ -1555,9 +1724,21 @@ inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary
 }  // namespace internal
 
 namespace internal {
+// a problem with losses is let through only if it is a pose graph (DetectPoseGraph) and every loss is a built-in; Solve asks in
+// addition for what SolveDispatch asks before it calls SolvePoseGraph: no forced callback path, no iteration callbacks
+inline bool PoseGraphWithKnownLosses(Problem* problem) {
+    PoseGraphLayout G;
+    return DetectPoseGraph(problem, &G) && G.losses_known;
+}
+inline bool LossesGoToPoseGraph(const Solver::Options& options, Problem* problem) {
+    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
+    if (options.force_callback_path || (fe && *fe && *fe != '0') || !options.callbacks.empty()) return false;
+    return PoseGraphWithKnownLosses(problem);
+}
 inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
-    if (problem->NumLossFunctions() > 0) {
-        // (Ceres would apply the loss; this layer has none to apply -- an unweighted solve would be a silently different problem)
+    if (problem->NumLossFunctions() > 0 && !LossesGoToPoseGraph(options, problem)) {
+        // (Ceres would apply the loss; outside the pose-graph route this layer has none to apply -- a solve without it would be a
+        // silently different problem)
         summary->termination_type = FAILURE;
         summary->message = "stba_ceres: " + std::to_string(problem->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are "
                            "not implemented by this layer (the reference passes nullptr: test_ceres.h:120) -- nothing was solved.";
@@ -1728,8 +1909,8 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
 //     Compute return false (the message names the component), before any device work;
 //   * "gpu-dense": anything else within the dense solve's limits -> stba_dense_covariance.
 // On the BA routes a requested pair must be two camera blocks (rotation / position, of one camera or of two) or one landmark with
-// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: no robust losses (refused
-// as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
+// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: robust losses on "gpu-pg" only,
+// where the result is (J'^T J')^-1 of the corrected Jacobian as in Ceres (refused elsewhere as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
 // factorisations (stba.h, stba_ba_covariance_compute) -- not a condition number estimate.  algorithm_type and num_threads are
 // accepted for source compatibility and do not change the computation.
 // (not in Ceres) execution_path() and message(): which route ran, and why Compute returned false.
@@ -1803,7 +1984,7 @@ private:
 
     bool ComputeImpl(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p) {
         using namespace internal;
-        if (p->NumLossFunctions() > 0)
+        if (p->NumLossFunctions() > 0 && !PoseGraphWithKnownLosses(p))
             return Fail(std::to_string(p->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are not implemented by this layer -- no covariance computed");
         if (options_.null_space_rank != 0)
             return Fail("null_space_rank = " + std::to_string(options_.null_space_rank) + ": this layer has no pseudo-inverse (only 0 is supported)");
@@ -1853,6 +2034,9 @@ private:
         struct Destroy { stba_pg* g; ~Destroy() { stba_pg_destroy(g); } } destroy{pg};
         if (!G.sqrt_info.empty() && stba_pg_set_sqrt_information(pg, G.sqrt_info.data()) != STBA_OK)
             return Fail(std::string("stba_pg_set_sqrt_information: ") + stba_last_error());
+        // (apply_loss_function = false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
+        if (options_.apply_loss_function && !G.loss_kind.empty() && stba_pg_set_loss(pg, G.loss_kind.data(), G.loss_a.data(), G.loss_b.data(), G.loss_scale.data()) != STBA_OK)
+            return Fail(std::string("stba_pg_set_loss: ") + stba_last_error());
         std::vector<double> blk(pairs.size() * 36);
         if (stba_pg_covariance(pg, (int)pairs.size(), na.data(), nb.data(), nullptr, blk.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_pg_covariance: ") + stba_last_error());

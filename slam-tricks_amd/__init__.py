@@ -82,7 +82,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_set_trust_region", "stba_ba_last_dogleg_summary",
            "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary",
            "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check",
-           "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information"]
+           "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information",
+           "stba_pg_set_loss", "stba_pg_has_loss"]
 
 
 def lib():
@@ -540,11 +541,48 @@ def pg_gauge_check(n_nodes, edge_i, edge_j, node_fixed=None):
     _chk(lib().stba_pg_gauge_check(int(n_nodes), len(ei), _p(ei), _p(ej), _p(nf)), "stba_pg_gauge_check")
 
 
+# robust loss kinds of the pose graph: the STBA_LOSS_* of include/stba.h by name (None and "trivial": no loss on that edge)
+LOSS_KINDS = {None: 0, "trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tolerant": 5, "tukey": 6}
+
+
+def pg_loss_table(m, kind, a=None, b=None, scale=None):
+    """the per-edge table stba_pg_set_loss takes, from one spec for all m edges or per-edge sequences: kind a name of LOSS_KINDS (or
+    its integer), a / b / scale numbers; each may be a scalar or have length m.  Returns (kind int32[m], a, b, scale float64[m]);
+    a and b default to 1 where the kind does not use them, scale to 1.  Raises ValueError on an unknown name or a wrong length."""
+    def code(k):
+        if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+            return int(k)
+        key = k.lower() if isinstance(k, str) else k
+        if key not in LOSS_KINDS:
+            raise ValueError(f"PGEngine: unknown loss kind {k!r} (one of {sorted(x for x in LOSS_KINDS if x)} or None)")
+        return LOSS_KINDS[key]
+
+    if kind is None or isinstance(kind, (str, int, np.integer)):
+        kinds = np.full(m, code(kind), np.int32)
+    else:
+        kinds = np.array([code(k) for k in kind], np.int32)
+        if kinds.shape != (m,):
+            raise ValueError(f"PGEngine: per-edge loss kinds must have length {m}, got {kinds.shape}")
+
+    def column(v, name):
+        if v is None:
+            return np.ones(m)
+        v = np.asarray(v, np.float64)
+        if v.ndim == 0:
+            return np.full(m, float(v))
+        if v.shape != (m,):
+            raise ValueError(f"PGEngine: per-edge loss parameter {name} must be a number or have length {m}, got {v.shape}")
+        return np.ascontiguousarray(v)
+
+    return kinds, column(a, "a"), column(b, "b"), column(scale, "scale")
+
+
 class PGEngine:
     """Device-resident pose graph (BASELINE config C4, build-defined)."""
 
-    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None, information=None, sqrt_information=None):
-        """information / sqrt_information: (m, 6, 6) per-edge weights (set_information / set_sqrt_information); at most one of them"""
+    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None, information=None, sqrt_information=None, loss=None):
+        """information / sqrt_information: (m, 6, 6) per-edge weights (set_information / set_sqrt_information); at most one of them.
+        loss: a kind name ("huber" uses a = 1), a tuple (kind, a[, b[, scale]]) or a dict of set_loss's arguments"""
         self._h = C.c_void_p()
         if information is not None and sqrt_information is not None:
             raise ValueError("PGEngine: give information or sqrt_information, not both")
@@ -555,8 +593,11 @@ class PGEngine:
         self.n, self.m = len(poses), len(ei)
         weights = None if information is None and sqrt_information is None else \
             self._edge_blocks(information if information is not None else sqrt_information)
+        table = None if loss is None else self._loss_table(loss)
         _chk(lib().stba_pg_create(C.byref(self._h), self.n, self.m, _p(poses), _p(ei), _p(ej), _p(meas), _p(nf),
                                   C.c_void_p(stream or 0)), "stba_pg_create")
+        if table is not None:
+            self._set_loss_table(table)
         if information is not None:
             self.set_information(weights)
         elif sqrt_information is not None:
@@ -583,6 +624,33 @@ class PGEngine:
     def has_information(self):
         has = C.c_int()
         _chk(lib().stba_pg_has_information(self._h, C.byref(has)), "stba_pg_has_information")
+        return bool(has.value)
+
+    def _loss_table(self, loss):
+        if isinstance(loss, dict):
+            return pg_loss_table(self.m, **loss)
+        if isinstance(loss, tuple):
+            return pg_loss_table(self.m, *loss)
+        return pg_loss_table(self.m, loss)
+
+    def _set_loss_table(self, table):
+        kind, a, b, scale = table
+        _chk(lib().stba_pg_set_loss(self._h, _p(kind), _p(a), _p(b), _p(scale)), "stba_pg_set_loss")
+
+    def set_loss(self, kind, a=None, b=None, scale=None):
+        """robust losses (Ceres' kinds, LOSS_KINDS): the cost becomes 1/2 sum rho_e(|W_e r_e|^2).  One spec for all edges --
+        set_loss("cauchy", 0.5) -- or per-edge sequences of length m: set_loss(["huber", None, ...], a_array).  b is TolerantLoss'
+        second parameter; scale multiplies the loss (ScaledLoss).  evaluate() then returns the corrected r and J, covariance()
+        (J'^T J')^-1 (include/stba.h).  set_loss(None): no loss, the engine as it was."""
+        if kind is None and a is None and b is None and scale is None:
+            _chk(lib().stba_pg_set_loss(self._h, None, None, None, None), "stba_pg_set_loss")
+            return
+        self._set_loss_table(pg_loss_table(self.m, kind, a, b, scale))
+
+    @property
+    def has_loss(self):
+        has = C.c_int()
+        _chk(lib().stba_pg_has_loss(self._h, C.byref(has)), "stba_pg_has_loss")
         return bool(has.value)
 
     def close(self):

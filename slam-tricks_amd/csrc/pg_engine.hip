@@ -31,7 +31,9 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cfloat>
 #include <climits>
+#include <cmath>
 #include <functional>
 #include <vector>
 
@@ -176,19 +178,87 @@ __device__ inline void pg_whiten_cols(const double* W, double* x, int cols, int 
     }
 }
 
+// rho(s), rho'(s), rho''(s) of one edge's robust loss, Ceres' definitions; kind is an STBA_LOSS_* of include/stba.h
+// other than TRIVIAL.  rho' is clamped from below by DBL_MIN where Ceres clamps it.
+__device__ inline void pg_loss(int kind, double a, double b, double s, double* rho) {
+    const double b2 = a * a;
+    switch (kind) {
+    case STBA_LOSS_HUBER:
+        if (s > b2) {
+            const double q = sqrt(s);
+            rho[0] = 2.0 * a * q - b2; rho[1] = fmax(DBL_MIN, a / q); rho[2] = -rho[1] / (2.0 * s);
+        } else { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }
+        break;
+    case STBA_LOSS_SOFTLONE: {
+        const double c = 1.0 / b2, sum = 1.0 + s * c, t = sqrt(sum);
+        rho[0] = 2.0 * b2 * (t - 1.0); rho[1] = fmax(DBL_MIN, 1.0 / t); rho[2] = -(c * rho[1]) / (2.0 * sum);
+        break;
+    }
+    case STBA_LOSS_CAUCHY: {
+        const double c = 1.0 / b2, sum = 1.0 + s * c, inv = 1.0 / sum;
+        rho[0] = b2 * log(sum); rho[1] = fmax(DBL_MIN, inv); rho[2] = -c * (inv * inv);
+        break;
+    }
+    case STBA_LOSS_ARCTAN: {
+        const double c = 1.0 / b2, sum = 1.0 + s * s * c, inv = 1.0 / sum;
+        rho[0] = a * atan2(s, a); rho[1] = fmax(DBL_MIN, inv); rho[2] = -2.0 * s * c * (inv * inv);
+        break;
+    }
+    case STBA_LOSS_TOLERANT: {
+        const double c = b * log(1.0 + exp(-a / b)), x = (s - a) / b;
+        if (x > 36.7) { rho[0] = s - a - c; rho[1] = 1.0; rho[2] = 0.0; }      // (36.7 = log(2^53): e^x + 1 == e^x from here on)
+        else {
+            const double ex = exp(x);
+            rho[0] = b * log(1.0 + ex) - c; rho[1] = fmax(DBL_MIN, ex / (1.0 + ex)); rho[2] = 0.5 / (b * (1.0 + cosh(x)));
+        }
+        break;
+    }
+    case STBA_LOSS_TUKEY:
+        if (s <= b2) {
+            const double v = 1.0 - s / b2, v2 = v * v;
+            rho[0] = b2 / 3.0 * (1.0 - v2 * v); rho[1] = v2; rho[2] = -2.0 / b2 * v;
+        } else { rho[0] = b2 / 3.0; rho[1] = 0.0; rho[2] = 0.0; }
+        break;
+    default:                                    // TRIVIAL with a scale
+        rho[0] = s; rho[1] = 1.0; rho[2] = 0.0;
+    }
+}
+
+// J <- sqrt(rho') (J - k r (r^T J)) for the 6 x 6 row-major J of one edge end, one column at a time (k = alpha / s of Ceres' corrector;
+// k == 0: the scaling alone)
+__device__ inline void pg_correct_cols(const double* re, double* J, double sq, double k) {
+    for (int c = 0; c < 6; ++c) {
+        if (k != 0.0) {
+            double t = 0.0;
+            for (int a = 0; a < 6; ++a) t += re[a] * J[a * 6 + c];
+            t *= k;
+            for (int a = 0; a < 6; ++a) J[a * 6 + c] = sq * (J[a * 6 + c] - re[a] * t);
+        } else {
+            for (int a = 0; a < 6; ++a) J[a * 6 + c] = sq * J[a * 6 + c];
+        }
+    }
+}
+
 // INFO = false: every edge weighted by the identity -- the kernel as it was before edges had information matrices; Winfo is not
 // read.  INFO = true: the residual and both Jacobians are whitened by the edge's square-root information W_e (Winfo[k * n_edges + e],
 // laid out like Ji) right behind pg_edge: cost, stores, the constant-node zeroing and the contrib block below all see W r, W Ji,
 // W Jj, and so does every consumer of what this kernel writes.  Two instantiations and not a runtime branch: an engine without
 // weights runs the instruction stream it ran before.
-template <bool INFO>
+// ROBUST = false: no edge has a loss, the kernel as it was before (lkind, la, lb, lscale are not read).  ROBUST = true: behind the
+// whitening the edge's loss (lkind[e], la[e], lb[e], lscale[e]: read by edge index) is evaluated at s = |r|^2 and Ceres' corrector
+// turns r and both Jacobians into r', J' with J'^T r' = rho' J^T r and J'^T J' the Triggs approximation of the robustified Hessian;
+// the edge's cost term is rho(s).  Every store and the contrib block see r', J'.  An edge of kind TRIVIAL and scale 1 is left alone:
+// what it stores compares == to the ROBUST = false kernel's.  The kind is a runtime switch: lanes of a wave may differ.
+template <bool INFO, bool ROBUST>
 __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const double* __restrict__ poses,
                                                            const int* __restrict__ ei, const int* __restrict__ ej,
                                                            const double* __restrict__ meas,
                                                            const unsigned char* __restrict__ fixed, int with_jac,
                                                            double* __restrict__ r, double* __restrict__ Ji,
                                                            double* __restrict__ Jj, double* __restrict__ partial,
-                                                           double* __restrict__ contrib, const double* __restrict__ Winfo) {
+                                                           double* __restrict__ contrib, const double* __restrict__ Winfo,
+                                                           const int* __restrict__ lkind, const double* __restrict__ la,
+                                                           const double* __restrict__ lb, const double* __restrict__ lscale) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     double c = 0.0;
     if (e < n_edges) {
@@ -203,6 +273,26 @@ __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const do
             if (with_jac) { pg_whiten_cols(We, ji, 6, 6); pg_whiten_cols(We, jj, 6, 6); }
         }
         for (int k = 0; k < 6; ++k) c += re[k] * re[k];
+        if (ROBUST) {
+            const int kind = lkind[e];
+            const double sc = lscale[e];
+            if (kind != STBA_LOSS_TRIVIAL || sc != 1.0) {
+                const double s = c;
+                double rho[3];
+                pg_loss(kind, la[e], lb[e], s, rho);
+                for (int k = 0; k < 3; ++k) rho[k] *= sc;
+                c = rho[0];
+                const double sq = sqrt(rho[1]);
+                double rs = sq, ak = 0.0;                     // residual scaling, alpha / s
+                if (s != 0.0 && rho[2] > 0.0) {
+                    const double alpha = 1.0 - sqrt(1.0 + 2.0 * s * rho[2] / rho[1]);
+                    rs = sq / (1.0 - alpha);
+                    ak = alpha / s;
+                }
+                if (with_jac) { pg_correct_cols(re, ji, sq, ak); pg_correct_cols(re, jj, sq, ak); }
+                for (int k = 0; k < 6; ++k) re[k] *= rs;
+            }
+        }
         if (r) for (int k = 0; k < 6; ++k) r[(size_t)e * 6 + k] = re[k];
         if (with_jac) {
             const bool fi = fixed && fixed[i], fj = fixed && fixed[j];
@@ -1454,6 +1544,10 @@ struct stba_pg {
     // per-edge square-root information W_e, component-major [36][m] like Ji (stba_pg_set_information / _sqrt_information); NULL: every
     // edge weighted by the identity, and pg_linearize launches the kernel without the whitening
     double* Winfo = nullptr;
+    // per-edge robust losses (stba_pg_set_loss): kind (STBA_LOSS_*), a, b, scale, each [m]; all NULL: no edge has a loss, and
+    // pg_linearize launches a kernel without the corrector
+    int* loss_kind = nullptr;
+    double *loss_a = nullptr, *loss_b = nullptr, *loss_scale = nullptr;
 };
 
 namespace stba {
@@ -1466,6 +1560,7 @@ void pg_free(stba_pg* g) {
     F(g->end_node); F(g->AdP); F(g->Ac0); F(g->W); F(g->Ainv); F(g->inv_work); F(g->rc_part); F(g->zc); F(g->part_cz); F(g->part_u);
     F(g->scal_dev); F(g->cflag); F(g->state); F(g->contrib); F(g->Dc);
     F(g->end_pos); F(g->end_rem); F(g->Bend); F(g->ubuf); F(g->pbuf); F(g->ustamp); F(g->pstamp); F(g->Winfo);
+    F(g->loss_kind); F(g->loss_a); F(g->loss_b); F(g->loss_scale);
     if (g->st2) { (void)hipStreamSynchronize(g->st2); chol_forget_stream(g->st2); (void)hipStreamDestroy(g->st2); }
     if (g->ev_in) (void)hipEventDestroy(g->ev_in);
     if (g->ev_read) (void)hipEventDestroy(g->ev_read);
@@ -1488,15 +1583,17 @@ double host_sum(hipStream_t st, const double* dev, int n, int stride, int off, s
 }
 
 int pg_linearize(stba_pg* g, int which, bool jac) {
-    // (an engine that holds square-root information runs the whitening instantiation, every other one the kernel without it)
-    if (g->Winfo)
-        hipLaunchKernelGGL(pg_linearize_kernel<true>, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
+    // (an engine that holds square-root information runs a whitening instantiation, one that holds a loss table a robust one, every
+    // other one the kernel without either)
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
                            g->meas, g->fixed, jac ? 1 : 0, jac ? g->r : nullptr, g->Ji, g->Jj, g->part_e, jac ? g->contrib : nullptr,
-                           (const double*)g->Winfo);
-    else
-        hipLaunchKernelGGL(pg_linearize_kernel<false>, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->poses[which], g->ei, g->ej,
-                           g->meas, g->fixed, jac ? 1 : 0, jac ? g->r : nullptr, g->Ji, g->Jj, g->part_e, jac ? g->contrib : nullptr,
-                           (const double*)nullptr);
+                           (const double*)g->Winfo, (const int*)g->loss_kind, (const double*)g->loss_a, (const double*)g->loss_b,
+                           (const double*)g->loss_scale);
+    };
+    if (g->loss_kind) { if (g->Winfo) launch(pg_linearize_kernel<true, true>); else launch(pg_linearize_kernel<false, true>); }
+    else if (g->Winfo) launch(pg_linearize_kernel<true, false>);
+    else launch(pg_linearize_kernel<false, false>);
     STBA_HIP(hipGetLastError());
     if (jac) g->bend_valid = false;
     return STBA_OK;
@@ -2261,6 +2358,57 @@ int stba_pg_set_sqrt_information(stba_pg* g, const double* sqrt_information) { r
 int stba_pg_has_information(const stba_pg* g, int* has) {
     if (!g || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
     *has = g->Winfo ? 1 : 0;
+    return STBA_OK;
+}
+
+// the per-edge loss table: checked on the host BEFORE anything is replaced (a refused call leaves the engine with the table it had),
+// then uploaded into NEW arrays that are swapped in; kind == NULL releases the table
+int stba_pg_set_loss(stba_pg* g, const int* kind, const double* a, const double* b, const double* scale) {
+    const char* who = "stba_pg_set_loss";
+    if (!g) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
+    int* k_new = nullptr;
+    double *a_new = nullptr, *b_new = nullptr, *s_new = nullptr;
+    if (kind) {
+        const size_t m = (size_t)g->m;
+        std::vector<double> ha(m, 1.0), hb(m, 1.0), hs(m, 1.0);
+        for (size_t e = 0; e < m; ++e) {
+            const int kd = kind[e];
+            std::string why;
+            if (kd < STBA_LOSS_TRIVIAL || kd > STBA_LOSS_TUKEY) why = "unknown loss kind " + std::to_string(kd);
+            else if (kd != STBA_LOSS_TRIVIAL && (!a || !std::isfinite(a[e]) || !(a[e] > 0.0))) why = "the loss parameter a must be finite and positive";
+            else if (kd == STBA_LOSS_TOLERANT && (!b || !std::isfinite(b[e]) || !(b[e] > 0.0))) why = "the loss parameter b must be finite and positive";
+            else if (scale && (!std::isfinite(scale[e]) || !(scale[e] >= 0.0))) why = "the loss scale must be finite and not negative";
+            if (!why.empty()) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": edge " + std::to_string(e) + ": " + why);
+            if (kd != STBA_LOSS_TRIVIAL) ha[e] = a[e];
+            if (kd == STBA_LOSS_TOLERANT) hb[e] = b[e];
+            if (scale) hs[e] = scale[e];
+        }
+        auto F = [](void* p) { if (p) (void)hipFree(p); };
+        int rc = dev_alloc(&k_new, m);
+        if (rc == STBA_OK) rc = dev_alloc(&a_new, m);
+        if (rc == STBA_OK) rc = dev_alloc(&b_new, m);
+        if (rc == STBA_OK) rc = dev_alloc(&s_new, m);
+        if (rc == STBA_OK &&
+            (hipMemcpyAsync(k_new, kind, m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
+             hipMemcpyAsync(a_new, ha.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
+             hipMemcpyAsync(b_new, hb.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
+             hipMemcpyAsync(s_new, hs.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
+             hipStreamSynchronize(g->st) != hipSuccess))
+            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
+        if (rc != STBA_OK) { F(k_new); F(a_new); F(b_new); F(s_new); return rc; }
+    }
+    // (nothing of the engine may still be reading the old table or what was linearised with it)
+    STBA_HIP(hipStreamSynchronize(g->st));
+    if (g->st2) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; g->job_reads_pending = false; }
+    for (void* p : {(void*)g->loss_kind, (void*)g->loss_a, (void*)g->loss_b, (void*)g->loss_scale}) if (p) (void)hipFree(p);
+    g->loss_kind = k_new; g->loss_a = a_new; g->loss_b = b_new; g->loss_scale = s_new;
+    g->bend_valid = false; g->coarse_valid = false; g->ac0_valid = false;
+    return STBA_OK;
+}
+
+int stba_pg_has_loss(const stba_pg* g, int* has) {
+    if (!g || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "null argument");
+    *has = g->loss_kind ? 1 : 0;
     return STBA_OK;
 }
 

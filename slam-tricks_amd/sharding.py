@@ -51,6 +51,8 @@ def make_pg_shard(scene, rank, world):
     for k in ("information", "sqrt_information"):      # per-edge weights travel with their edges
         if scene.get(k) is not None:
             out[k] = scene[k][lo:hi]
+    if scene.get("loss") is not None:                   # a dict of PGEngine.set_loss's arguments: per-edge entries travel too, one spec for all edges stays
+        out["loss"] = {k: (v[lo:hi] if (not isinstance(v, str) and np.ndim(v) == 1 and len(v) == m) else v) for k, v in scene["loss"].items()}
     out["lo"], out["hi"] = lo, hi
     return out
 
