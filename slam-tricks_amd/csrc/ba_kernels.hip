@@ -680,7 +680,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, GEN ? 2 : 4) void ba_schur_pairs_ker
     // deep.  (Two pairs in flight per lane -- the second pair's gathers requested before the first is computed -- was
     // measured 7 % slower: the kernel is not bound by the gather latency.)
     // Every wave walks ITS OWN list: the host dealt the task's blocks (parts of heavy blocks) to the eight waves, so all the LDS
-    // adds that meet in one address come from one wave, in program order -- S is bitwise reproducible (see stba_ba_create).
+    // adds that meet in one address come from one wave, in program order -- S is bitwise reproducible (see plan_pair_records, schur_plan.hpp).
     // a.mode 1 (round 5, second form): ONE list per task walked by all 512 lanes as until round 4 (lane t takes pair t + 512 trip),
     // and the eight waves add their contributions of a trip IN WAVE ORDER: a token in LDS -- wave w of trip n waits for 8 n + w,
     // adds, waits for its LDS operations, passes 8 n + w + 1 on.  Same order of additions into every address in every run.

@@ -1,12 +1,12 @@
 // ba_kernels.hpp -- launch wrappers of the BA hot-path kernels (definitions in ba_kernels.hip)
 #pragma once
 #include "common.hpp"
+#include "schur_plan.hpp"      // CAM_CHUNK and the SCHUR_* constants that the host-side plan shares with the kernels
 
 namespace stba {
 
 constexpr int LIN_THREADS = 1024;              // observations per workgroup tile
 constexpr int LIN_MAX_LDS = 160 * 1024 - 512;  // dynamic LDS budget of the linearize kernel
-constexpr int CAM_CHUNK = 256;                 // observations per camera-side reduction chunk
 
 struct LinArgs {
     int n_obs, n_cams;
@@ -91,19 +91,13 @@ int launch_point_damp_invert(int n_pts, const double* Hpp6, const unsigned char*
 int launch_point_invert(int n_pts, const double* Hpp6, const double* dp, const unsigned char* pt_fixed,
                         double* Hinv6, hipStream_t st);
 // Schur complement of the landmark blocks, row-wise with LDS accumulation (plan built on the host at create time:
-// stba_ba_create).  SCHUR_SPLIT_COLS: non-zero blocks one task accumulates in LDS (two workgroups per CU);
-// SCHUR_TASK_PAIRS: most (i, l) observation pairs per task (unlimited: smaller tasks measured slower).
-constexpr int SCHUR_PLAN_DEFAULT = 3;                       // SchurArgs::mode of the product build
-constexpr int SCHUR_MAX_SLOTS = 256;                        // LDS accumulator slots of a task: two workgroups of 81.5 KB per CU
-constexpr int SCHUR_SPLIT_COLS = SCHUR_MAX_SLOTS - 8;       // blocks per task; a heavy block takes up to one extra slot per wave (parts)
-constexpr int SCHUR_TASK_PAIRS = 1 << 30;
+// build_schur_plan, schur_plan.hpp, which also holds SCHUR_MAX_SLOTS, SCHUR_SPLIT_COLS, SCHUR_TASK_PAIRS and SCHUR_THREADS).
 // LDS stride of one 6x6 accumulator block, in doubles: odd, so that the same entry of different blocks falls
 // into different bank pairs (36 = 72 dwords = 8 mod 64 gave 8-way conflicts on every ds_add_f64: measured,
 // the kernel was bound by them)
 constexpr int SCHUR_BLK_LD = 37;
 constexpr int SCHUR_CAM_LD = 56;      // per wave of a diagonal slice: 21 + 6 sums of the camera block, 21 + 6 of the pairs (i, i), padded
 constexpr int SCHUR_ROTS = 6;        // column rotations of the Schur kernel's lanes (dealt per pair by the host: bits 16..18 of the record), see its pair loop
-constexpr int SCHUR_THREADS = 512;    // 8 waves per task, two tasks per CU: 16 waves hide the L2 gathers
 struct SchurArgs {
     const int* task_cam; const int* cam_start;       // camera row of the task; the camera's range of cam_perm
     const int* task_col_lo; const int* task_col_hi;  // the task's slice of its row's column list

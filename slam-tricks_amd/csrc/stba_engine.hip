@@ -60,15 +60,8 @@ enum { TS_COST2 = 0, TS_STEP2 = 1, TS_X2 = 2, TS_MODEL = 3, TS_TIMEOUT = 4, TS_C
 
 using namespace stba;
 
-// host-side plan construction runs on a few threads (the camera rows / Schur tasks are independent)
-template <typename F>
-static void host_parallel_for(int n, F fn) {
-    const int nt = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), n / 64}));
-    if (nt <= 1) { fn(0, n, 0); return; }
-    std::vector<std::thread> th;
-    for (int k = 0; k < nt; ++k) th.emplace_back([=] { fn((int)((long)n * k / nt), (int)((long)n * (k + 1) / nt), k); });
-    for (auto& t : th) t.join();
-}
+static_assert(sizeof(PairRec) == sizeof(int4) && alignof(int4) % alignof(PairRec) == 0, "the Schur kernel reads a pair record as one int4");
+static_assert(SCHUR_FORM_PAIRS == STBA_SCHUR_PAIRS && SCHUR_FORM_DENSE == STBA_SCHUR_DENSE, "schur_plan.hpp mirrors include/stba.h");
 
 struct stba_ba {
     int nc = 0, np = 0, no = 0, n = 0, lda = 0;
@@ -83,17 +76,18 @@ struct stba_ba {
     int *obs_cam = nullptr, *obs_pt = nullptr, *pt_start = nullptr;
     int *cam_perm = nullptr, *chunk_begin = nullptr, *chunk_end = nullptr, *cam_chunk_start = nullptr;
     int n_chunks = 0;
-    // Schur plan: task = (camera row, slice [lo, hi) of the row's column list), see stba_ba_create
+    // Schur plan: task = (camera row, slice [lo, hi) of the row's column list), see build_schur_plan (schur_plan.hpp)
     int *task_cam = nullptr, *cam_start = nullptr, *row_col_ptr = nullptr, *row_cols = nullptr;
     int *task_col_lo = nullptr, *task_col_hi = nullptr;
     int n_tasks = 0, max_cols = 0;
     // round 6, FEW camera rows (landmark-heavy problems): a task = (camera row, a RANGE of the camera's observation list), all columns of
-    // the row; the slices of a row write partial blocks, ba_schur_reduce_slices_kernel adds them in order (see stba_ba_create)
+    // the row; the slices of a row write partial blocks, ba_schur_reduce_slices_kernel adds them in order (see plan_rows, schur_plan.hpp)
     int *task_p_lo = nullptr, *task_p_hi = nullptr, *row_task_ptr = nullptr, *row_tasks = nullptr;
     long long* task_part_off = nullptr;
     double* schur_part = nullptr;
     bool lm_slices = false;
-    std::shared_ptr<void> create_leftovers;     // the host-side temporaries of stba_ba_create, kept until the engine goes (see there)
+    std::shared_ptr<SchurPlan> create_leftovers;     // the host-side plan of ba_create, kept until the engine goes (see there)
+    std::vector<unsigned char> create_omask;         // (the host copy of omask: kept, and freed, with it)
     // pair plan of the Schur kernel (see ba_schur_pairs_kernel)
     int *pair_begin = nullptr, *pair_end = nullptr;      // per (task, wave)
     int *task_vs_ptr = nullptr, *vs_first = nullptr;     // per task: first accumulator slot of every block of its slice (+ the slot count)
@@ -198,7 +192,8 @@ struct stba_ba {
 namespace stba {
 
 static void ba_free(stba_ba* b) {
-    b->create_leftovers.reset();                        // (what stba_ba_create's plan left on the host)
+    b->create_leftovers.reset();                        // (what ba_create's plan left on the host)
+    std::vector<unsigned char>().swap(b->create_omask);
     cov_store_free(b->cov);
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
@@ -1385,442 +1380,32 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cu = prop.multiProcessorCount;
     tmark("events, device properties");
 
-    // ---- landmark-major regrouping (stable counting sort) and the camera-side permutation
-    std::vector<int> pt_start(n_pts + 1, 0);
-    for (int i = 0; i < n_obs; ++i) ++pt_start[obs_pt[i] + 1];
-    for (int j = 0; j < n_pts; ++j) pt_start[j + 1] += pt_start[j];
-    b->perm.resize(n_obs);
-    {
-        std::vector<int> fill(pt_start.begin(), pt_start.end() - 1);
-        for (int i = 0; i < n_obs; ++i) b->perm[fill[obs_pt[i]]++] = i;
-    }
-    std::vector<int> s_cam(n_obs), s_pt(n_obs);
-    std::vector<double> s_feat((size_t)n_obs * 2);
-    for (int p = 0; p < n_obs; ++p) {
-        const int i = b->perm[p];
-        s_cam[p] = obs_cam[i]; s_pt[p] = obs_pt[i];
-        s_feat[2 * (size_t)p] = obs_feat[2 * (size_t)i]; s_feat[2 * (size_t)p + 1] = obs_feat[2 * (size_t)i + 1];
-    }
-    std::vector<int> cam_start(n_cams + 1, 0);
-    for (int p = 0; p < n_obs; ++p) ++cam_start[s_cam[p] + 1];
-    for (int c = 0; c < n_cams; ++c) cam_start[c + 1] += cam_start[c];
-    std::vector<int> cam_perm(n_obs);
-    {
-        std::vector<int> fill(cam_start.begin(), cam_start.end() - 1);
-        for (int p = 0; p < n_obs; ++p) cam_perm[fill[s_cam[p]]++] = p;
-    }
-    std::vector<int> chunk_begin, chunk_end, cam_chunk_start(n_cams + 1, 0);
-    for (int c = 0; c < n_cams; ++c) {
-        cam_chunk_start[c] = (int)chunk_begin.size();
-        for (int s0 = cam_start[c]; s0 < cam_start[c + 1]; s0 += CAM_CHUNK) {
-            chunk_begin.push_back(s0);
-            chunk_end.push_back(std::min(s0 + CAM_CHUNK, cam_start[c + 1]));
-        }
-    }
-    cam_chunk_start[n_cams] = (int)chunk_begin.size();
-    b->n_chunks = (int)chunk_begin.size();
-    // Several observations of one (camera, landmark) pair -- stereo residuals on one pose block, two factors on one pair through the
-    // host-linearised path: in a camera's list (landmarks ascending) they are neighbours.  The pair plan treats them like any other
-    // pair of observations; the dense form writes ONE block of Y per (camera, landmark) and must sum them (ba_schur_dense_chunk_kernel).
-    std::vector<unsigned char> dup_run;
-    size_t n_dup = 0;
-    for (int c = 0; c < n_cams; ++c)
-        for (int q = cam_start[c]; q < cam_start[c + 1];) {
-            int e = q + 1;
-            while (e < cam_start[c + 1] && s_pt[cam_perm[e]] == s_pt[cam_perm[q]]) ++e;
-            if (e - q > 1) {
-                // (the run table is one byte per observation and only the DENSE form reads it: a longer run is refused where that form
-                // is chosen, not here -- the pair plan handles any number of observations of one pair; advisor, round 5)
-                if (e - q > 255) b->dup_overflow = true;
-                if (dup_run.empty()) dup_run.assign((size_t)n_obs, 0);
-                dup_run[(size_t)q] = (unsigned char)std::min(254, e - q - 1);
-                for (int k = q + 1; k < e; ++k) dup_run[(size_t)k] = 255;
-                n_dup += (size_t)(e - q - 1);
-            }
-            q = e;
-        }
-    tmark("regroup observations");
-    // ---- Schur plan.  Camera row c of the reduced system has one non-zero 6x6 block per partner camera c2 <= c it shares a
-    // landmark with; every (observation i of c, observation l of the same landmark with camera(l) <= c) PAIR contributes to
-    // one of them.  A task = (camera row, a slice of the row's sorted column list): it owns its blocks alone (one writer per
-    // block of S, no atomics on S, and the task zeroes its own stretch of the six matrix rows).  A slice holds at most
-    // SCHUR_SPLIT_COLS blocks (the LDS accumulator: two workgroups per CU) and at most SCHUR_TASK_PAIRS pairs (no limit
-    // by default: see the task order below).  The pairs of every task are enumerated here once (the structure is static).
-    std::vector<int> row_col_ptr(n_cams + 1, 0), row_cols, task_cam, task_col_lo, task_col_hi, task_p_lo, task_p_hi;
-    std::vector<size_t> task_pairs;
-    std::vector<std::vector<int>> cnt_of;       // per camera row: pairs of every non-zero block (without the pairs (i, i))
-    int task_max_cols = 0;
-    size_t total_pairs = 0;
-    for (int j = 0; j < n_pts; ++j) { const size_t k = (size_t)(pt_start[j + 1] - pt_start[j]); total_pairs += k * (k + 1) / 2; }
-    if (!iterative) {   // the plan costs 16 bytes per pair on the host and on the device: refuse what cannot be held instead of running out of memory
-        // half-way (a landmark seen by k cameras makes k (k + 1) / 2 pairs: 1000 cameras that ALL see 100 000 landmarks are 5e10)
-        size_t free_b = 0, total_b = 0;
-        const bool have_info = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-        const size_t cap = std::min<size_t>((size_t)1 << 30, have_info ? free_b / 2 / 16 : ((size_t)1 << 30));
-        // dense visibility: the Schur complement as one symmetric product on the matrix cores instead (ba_kernels.hip): no plan
-        const double visibility = (n_pts > 0 && n_cams > 0) ? (double)((size_t)n_obs - n_dup) / ((double)n_pts * n_cams) : 0.0;   // (distinct pairs)
-        const size_t y_bytes = (size_t)b->lda * (((size_t)3 * n_pts + 31) / 16 * 16) * sizeof(double);
-        const bool y_fits = !have_info || y_bytes < free_b / 2;
-        if (total_pairs > cap && !y_fits) {
-            ba_free(b);
-            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: " + std::to_string(total_pairs) + " observation pairs (sum over landmarks of k (k + 1) / 2, "
-                        "k = cameras that see the landmark) need a Schur plan of " + std::to_string(total_pairs * 16 / (1 << 20)) + " MiB; the limit here is " +
-                        std::to_string(cap) + " pairs (2^30, or half of the free device memory) -- and the dense form needs " +
-                        std::to_string(y_bytes / (1 << 20)) + " MiB, which the device does not have free either");
-        }
-        // (measured, tools/dense_schur_time.py, 59 % visibility: 29 x 600 -- 94 k pairs -- 0.053 ms either way; 60 x 12 000 -- 7.8 M pairs --
-        // 1.30 ms by the plan, 0.30 ms as a product; 100 x 8000 -- 14 M -- 1.53 against 0.37 ms)
-        if (total_pairs > cap || (total_pairs > ((size_t)1 << 20) && visibility >= 0.3 && y_fits)) b->schur_mode = b->schur_mode_auto = STBA_SCHUR_DENSE;
-    }
-    if (b->schur_mode == STBA_SCHUR_DENSE && b->dup_overflow) {
-        ba_free(b);
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: more than 255 observations of one (camera, landmark) pair in a problem that needs the dense form of the Schur complement");
-    }
-    const bool build_pair_plan = !iterative && b->schur_mode != STBA_SCHUR_DENSE;
-    b->have_pair_plan = build_pair_plan;
-    static const int TASK_PAIRS = std::max(256, knob_int("STBA_SCHUR_TASK_PAIRS", SCHUR_TASK_PAIRS));
-    if (iterative) {
-        // no reduced system at all: no block pattern either (row_col_ptr stays zero)
-    } else if (!build_pair_plan) {
-        // no plan: the block pattern (only the cross-rank packing reads it) is taken as full -- enumerating it costs as much as the pairs
-        for (int c = 0; c < n_cams; ++c) {
-            for (int c2 = 0; c2 <= c; ++c2) row_cols.push_back(c2);
-            row_col_ptr[c + 1] = (int)row_cols.size();
-        }
-    } else {
-        std::vector<std::vector<int>> cols_of((size_t)n_cams);
-        cnt_of.assign((size_t)n_cams, std::vector<int>());
-        host_parallel_for(n_cams, [&](int c_lo, int c_hi, int) {
-            std::vector<int> stamp(n_cams, -1), slot_of((size_t)n_cams, 0);
-            for (int c = c_lo; c < c_hi; ++c) {
-                std::vector<int>& tmp = cols_of[(size_t)c];
-                for (int p = cam_start[c]; p < cam_start[c + 1]; ++p) {
-                    const int j = s_pt[cam_perm[p]];
-                    for (int l = pt_start[j]; l < pt_start[j + 1]; ++l) {
-                        const int c2 = s_cam[l];
-                        if (c2 <= c && stamp[c2] != c) { stamp[c2] = c; tmp.push_back(c2); }
-                    }
-                }
-                std::sort(tmp.begin(), tmp.end());
-                for (size_t q = 0; q < tmp.size(); ++q) slot_of[(size_t)tmp[q]] = (int)q;
-                std::vector<int>& cnt = cnt_of[(size_t)c];
-                cnt.assign(tmp.size(), 0);
-                for (int p = cam_start[c]; p < cam_start[c + 1]; ++p) {
-                    const int j = s_pt[cam_perm[p]];
-                    for (int l = pt_start[j]; l < pt_start[j + 1]; ++l)
-                        if (s_cam[l] <= c && l != cam_perm[p]) ++cnt[(size_t)slot_of[(size_t)s_cam[l]]];     // (not the pair (i, i): below)
-                }
-            }
-        });
-        // FEW camera rows (round 5; the landmark-heavy scenes, e.g. 100 cameras x 1 000 000 landmarks): a task per row leaves most of the
-        // 512 workgroup slots empty, so the rows are cut into slices by pair count, about two per row -- measured on 100 x 1 000 000
-        // (45 M pairs): one slice per row 10.8 ms, two 4.7, three 5.8, four 6.9 (every further slice walks the camera's observation
-        // list once more and finds fewer of a landmark's pairs side by side); on one eighth of it 1.30 / 0.48 / 0.56 ms
-        const bool two_slices = n_cams <= 256 && total_pairs > ((size_t)1 << 20) && TASK_PAIRS == SCHUR_TASK_PAIRS;
-        // ROUND 6: with few camera rows whose blocks all fit ONE task's accumulator (<= SCHUR_SPLIT_COLS columns), a row is cut by
-        // LANDMARK RANGE instead: a task = (row, a contiguous range of the camera's observation list, all columns).  Cutting by columns
-        // (above) makes every slice gather the camera's own records again and finds fewer of a landmark's pairs side by side, so more
-        // than ~two slices per row lost (4.7 / 5.8 / 6.9 ms at two / three / four); by landmark range a slice touches only its own
-        // stretch of the list, any number of slices balances, and a thousand tasks fill the 512 workgroup slots twice over.  The
-        // slices of a row write PARTIAL blocks (plus their share of the camera block, the gradient and the right-hand side); a
-        // second, small kernel adds them in slice order -- no atomics on S, bitwise reproducible.
-        bool lm_slices = two_slices && knob_int("STBA_SCHUR_LM_SLICES", 1) != 0;
-        for (int c = 0; c < n_cams && lm_slices; ++c) if ((int)cols_of[(size_t)c].size() > SCHUR_SPLIT_COLS) lm_slices = false;
-        b->lm_slices = lm_slices;
-        if (lm_slices) {
-            const size_t cap = std::max<size_t>(8192, total_pairs / 1024 + 1);
-            for (int c = 0; c < n_cams; ++c) {
-                const std::vector<int>& tmp = cols_of[(size_t)c];
-                row_cols.insert(row_cols.end(), tmp.begin(), tmp.end());
-                row_col_ptr[c + 1] = (int)row_cols.size();
-                const int ncols_c = (int)tmp.size();
-                task_max_cols = std::max(task_max_cols, ncols_c);
-                // pairs behind every observation of the camera's list: partners l of the same landmark with camera(l) <= c, l != i
-                const int p0 = cam_start[c], p1 = cam_start[c + 1];
-                size_t row_pairs = 0;
-                for (int q : cnt_of[(size_t)c]) row_pairs += (size_t)q;
-                const int n_sl = (int)std::min<size_t>(64, std::max<size_t>(1, (row_pairs + cap - 1) / cap));
-                const size_t per = (row_pairs + (size_t)n_sl - 1) / (size_t)n_sl;
-                int lo = p0, made = 0;
-                size_t acc = 0;
-                auto push = [&](int hi) {
-                    task_cam.push_back(c); task_col_lo.push_back(0); task_col_hi.push_back(ncols_c);
-                    task_p_lo.push_back(lo); task_p_hi.push_back(hi); task_pairs.push_back(acc);
-                    ++made; lo = hi; acc = 0;
-                };
-                for (int p = p0; p < p1; ++p) {
-                    const int i = cam_perm[p];
-                    const int j = s_pt[i];
-                    size_t w = 0;
-                    for (int l = pt_start[j]; l < pt_start[j + 1]; ++l) if (s_cam[l] <= c && l != i) ++w;
-                    if (acc > 0 && acc + w > per && made < n_sl - 1) push(p);
-                    acc += w;
-                }
-                push(p1);          // (the last slice; a camera without observations gets one empty task)
-            }
-        } else
-        for (int c = 0; c < n_cams; ++c) {
-            const std::vector<int>& tmp = cols_of[(size_t)c];
-            const std::vector<int>& cnt = cnt_of[(size_t)c];
-            // (ONE cap for all rows, 0.58 of the mean pairs per row: most rows fall into two slices, a heavy row into three, and no task is
-            // longer than the cap -- the kernel ends with its longest task.  450 k pairs per row: 4.7 ms against 5.5 for equal halves of
-            // every row and 6.5 for 58 / 42 of every row; 56 k per row -- one rank's share at eight ranks -- 0.48 ms against 1.30 uncut)
-            const size_t row_cap = two_slices ? std::max<size_t>(4096, (size_t)(0.58 * (double)total_pairs / (double)n_cams) + 1) : (size_t)TASK_PAIRS;
-            row_cols.insert(row_cols.end(), tmp.begin(), tmp.end());
-            row_col_ptr[c + 1] = (int)row_cols.size();
-            const int ncols_c = (int)tmp.size();
-            int lo = 0;
-            size_t acc = 0;
-            for (int q = 0; q <= ncols_c; ++q) {
-                // close the slice in front of column q when it is full, and at the end of the row (a camera without
-                // observations still gets one empty task: it zeroes its rows and writes its zero camera block)
-                const bool end = q == ncols_c;
-                const bool full = !end && q > lo && (acc + (size_t)cnt[(size_t)q] > row_cap || q - lo >= SCHUR_SPLIT_COLS);
-                if (full || end) {
-                    task_cam.push_back(c); task_col_lo.push_back(lo); task_col_hi.push_back(q); task_pairs.push_back(acc);
-                    task_max_cols = std::max(task_max_cols, q - lo);
-                    lo = q; acc = 0;
-                }
-                if (!end) acc += (size_t)cnt[(size_t)q];
-            }
-        }
-        // Task order: heaviest first (most pairs), for a short tail.  (Measured against it in round 3, C5, Schur kernel
-        // 0.324 ms: the cameras in trajectory order 0.39 ms; cut into eight contiguous ranges walked by one XCD each, so that
-        // the workgroups side by side on an XCD gather the same records, 0.39-0.40 ms in camera order and 0.323 ms heaviest
-        // first inside every range: the L2 hits bring nothing.  Slices cut to 3072 / 4096 / 6144 / 8192 pairs: 0.49 / 0.37 / 0.34 / 0.34 ms: a task's fixed costs --
-        // zeroing its accumulator and its rows, the block stores -- outweigh the better balance.)
-        std::vector<int> order(task_cam.size());
-        for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return task_pairs[(size_t)x] > task_pairs[(size_t)y]; });
-        auto permute = [&](auto& v) { auto t = v; for (size_t k = 0; k < order.size(); ++k) v[k] = t[(size_t)order[k]]; };
-        permute(task_cam); permute(task_col_lo); permute(task_col_hi); permute(task_pairs);
-        if (lm_slices) { permute(task_p_lo); permute(task_p_hi); }
-    }
-    tmark("row plan");
-    b->n_tasks = (int)task_cam.size();
-    // Pair records (i, l, landmark, accumulator slot | flags) of every task.  RUN-TO-RUN REPRODUCIBILITY (round 5): every LDS
-    // accumulator slot of a task is added to by ONE wave of the task's workgroup, so the ds_add_f64 that meet in an LDS address are
-    // all issued by the same wave, in program order, and S comes out bit-identical from launch to launch (with the pairs dealt to
-    // all 512 lanes in list order, as until round 4, the eight waves raced for the blocks and the sums differed in their last
-    // bits: 34 distinct final costs in 48 long LM runs).
-    // How the slots are dealt matters for speed.  A first version gave every 6 x 6 block to one wave (heaviest first): correct, and
-    // 0.340 instead of 0.257 ms -- a wave's 64 lanes then hold pairs of 64 different landmarks (a landmark's partners are different
-    // cameras, i.e. different blocks, i.e. different waves), so the own record J_i and the inverse landmark block are requested 64
-    // times per instruction instead of ~12, and a wave that owns a heavy block adds to the same addresses in most of its lanes.
-    // So: the camera's observation list (landmarks ascending) is cut into EIGHT RANGES of equal pair count, one per wave; a heavy
-    // block gets up to eight PARTS -- accumulator slots of its own, consecutive, added in order when the block is written -- one per
-    // range (or per two / four ranges), and part k goes to a wave of its ranges.  A wave's list is then, for the blocks that hold
-    // most of the pairs, exactly the pairs of the landmarks of its range in the old order: the same coalescing and the same mix of
-    // blocks per instruction as before.  Light blocks (one part) are dealt to the least loaded wave.
-    constexpr int NW = SCHUR_THREADS / 64;
-    // (debug builds: STBA_SCHUR_PLAN = 1: one list per task, the waves add in turn (token); 2: one list, arrival order -- the round-4 kernel)
-    const int plan_knob = std::min(3, std::max(0, knob_int("STBA_SCHUR_PLAN", SCHUR_PLAN_DEFAULT)));
-    const bool plan_stripes = plan_knob == 3;
-    const bool plan_runs = knob_int("STBA_SCHUR_RUNS", 1) != 0;
-    const bool rot_by_rank = knob_int("STBA_SCHUR_ROT_RANK", 1) != 0;
-    const int plan_mode = plan_stripes ? 0 : plan_knob;
-    b->schur_plan_mode = plan_mode;
-    std::vector<int> pair_begin, pair_end, task_vs_ptr, vs_first;
-    // (not a std::vector: its resize() would write 72 MB of zeros at C5, on one thread, in front of the threads that fill it)
-    std::unique_ptr<int4[]> pair_rec;
-    size_t n_pair_rec = 0;
-    std::vector<size_t> diag_pairs_thr(64, 0);
-    int max_slots = 0;
-    if (build_pair_plan) {
-        const int ntask = (int)task_cam.size();
-        pair_begin.resize((size_t)ntask * NW); pair_end.resize((size_t)ntask * NW);
-        std::vector<size_t> cnt((size_t)ntask + 1, 0);
-        task_vs_ptr.assign((size_t)ntask + 1, 0);
-        for (int k = 0; k < ntask; ++k) {
-            cnt[(size_t)k + 1] = cnt[(size_t)k] + task_pairs[(size_t)k];
-            task_vs_ptr[(size_t)k + 1] = task_vs_ptr[(size_t)k] + (task_col_hi[(size_t)k] - task_col_lo[(size_t)k]) + 1;
-        }
-        n_pair_rec = cnt[(size_t)ntask];
-        pair_rec.reset(new int4[std::max<size_t>(n_pair_rec, 1)]);
-        vs_first.assign((size_t)task_vs_ptr[(size_t)ntask], 0);
-        std::vector<int> max_slots_thr(64, 0);
-        host_parallel_for(ntask, [&](int k_lo, int k_hi, int tix) {
-            std::vector<int> slot_of((size_t)n_cams, 0);
-            std::vector<int> nparts, wave_of, order, cntR, bcl, rank_of;
-            std::vector<unsigned char> range_of;
-            const bool lm = b->lm_slices;
-            for (int k = k_lo; k < k_hi; ++k) {
-                const int c = task_cam[(size_t)k];
-                const int* cb = row_cols.data() + row_col_ptr[c];
-                const int nco = row_col_ptr[c + 1] - row_col_ptr[c];
-                for (int q = 0; q < nco; ++q) slot_of[(size_t)cb[q]] = q;
-                const int slo = task_col_lo[(size_t)k], shi = task_col_hi[(size_t)k], ncols = shi - slo;
-                const size_t total = task_pairs[(size_t)k];
-                int* vsf = vs_first.data() + task_vs_ptr[(size_t)k];
-                // ---- pass 1: the range of every observation of the camera (equal shares of THIS task's pairs), pairs per (block, range)
-                // (a landmark-range slice walks its own stretch of the camera's list only)
-                const int p0 = lm ? task_p_lo[(size_t)k] : cam_start[c], p1 = lm ? task_p_hi[(size_t)k] : cam_start[c + 1];
-                range_of.assign((size_t)(p1 - p0), 0);
-                cntR.assign((size_t)ncols * NW, 0);
-                {
-                    size_t before = 0;
-                    for (int p = p0; p < p1; ++p) {
-                        const int i = cam_perm[p];
-                        const int j = s_pt[i];
-                        // (plan 3: STRIPES -- the list dealt to the waves in runs of ~64 pairs, round robin, so that at any moment the eight
-                        // waves work side by side in one stretch of the list as they did with the shared list)
-                        const int w = plan_stripes ? (int)((before / 64) % NW) : total > 0 ? (int)std::min<size_t>(NW - 1, before * NW / total) : 0;
-                        range_of[(size_t)(p - p0)] = (unsigned char)w;
-                        for (int l = pt_start[j]; l < pt_start[j + 1]; ++l) {
-                            const int c2 = s_cam[l];
-                            if (c2 > c || l == i) continue;
-                            const int sl = slot_of[(size_t)c2];
-                            if (sl < slo || sl >= shi) continue;
-                            ++cntR[(size_t)(sl - slo) * NW + w];
-                            ++before;
-                        }
-                    }
-                }
-                // ---- parts per block.  A pair whose block has one part is handled by the block's wave whatever landmark it belongs to: its
-                // own record and inverse landmark block are then requested by a lane of their own instead of by the handful of neighbouring
-                // lanes that hold the same landmark's other pairs (~25 instead of ~12 cache lines per gather instruction).  With P parts the
-                // share of such FOREIGN pairs of a block of m pairs is 1 - P / 8, so every accumulator slot spent on a block makes m / 8 of
-                // its pairs local, whatever P: the blocks are upgraded heaviest first, to eight parts each, while slots last.
-                // pairs per block of the slice (a landmark-range slice counts its own: the row's table covers the whole list)
-                const int* bc = cnt_of[(size_t)c].data() + slo;
-                if (lm) {
-                    bcl.assign((size_t)ncols, 0);
-                    for (int q = 0; q < ncols; ++q) for (int w2 = 0; w2 < NW; ++w2) bcl[(size_t)q] += cntR[(size_t)q * NW + w2];
-                    bc = bcl.data();
-                }
-                nparts.assign((size_t)ncols, 1);
-                int nvs = ncols;
-                if (plan_mode == 0) {
-                    order.resize((size_t)ncols);
-                    for (int q = 0; q < ncols; ++q) order[(size_t)q] = q;
-                    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return bc[x] > bc[y]; });
-                    for (int q : order) {
-                        if (bc[q] < 16) break;                              // (nothing to gain below a couple of pairs per wave)
-                        const int np_ = (SCHUR_MAX_SLOTS - nvs >= 7) ? 8 : (SCHUR_MAX_SLOTS - nvs >= 3) ? 4 : (SCHUR_MAX_SLOTS - nvs >= 1) ? 2 : 1;
-                        if (np_ == 1) break;
-                        nparts[(size_t)q] = np_;
-                        nvs += np_ - 1;
-                    }
-                }
-                nvs = 0;
-                for (int q = 0; q < ncols; ++q) { vsf[q] = nvs; nvs += nparts[(size_t)q]; }
-                vsf[ncols] = nvs;
-                max_slots_thr[(size_t)(tix & 63)] = std::max(max_slots_thr[(size_t)(tix & 63)], nvs);
-                // ---- slots -> waves: a part goes to the least loaded wave among the ranges it covers; blocks heaviest first
-                order.resize((size_t)ncols);
-                for (int q = 0; q < ncols; ++q) order[(size_t)q] = q;
-                std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return bc[x] > bc[y]; });
-                size_t load[NW] = {0};
-                wave_of.assign((size_t)nvs, 0);
-                for (int q : order) {
-                    const int np_ = nparts[(size_t)q], span = NW / np_;
-                    if (np_ == 1 && plan_mode == 0 && plan_runs) continue;        // (light blocks: in column runs, below)
-                    for (int part = 0; part < np_; ++part) {
-                        size_t pc = 0;
-                        for (int w = part * span; w < (part + 1) * span; ++w) pc += (size_t)cntR[(size_t)q * NW + w];
-                        int best = part * span;
-                        for (int w = part * span + 1; w < (part + 1) * span; ++w) if (load[w] < load[best]) best = w;
-                        if (plan_mode != 0) best = 0;       // one list per task (the kernel's modes 1 and 2): everything in wave 0's range of the table
-                        wave_of[(size_t)(vsf[q] + part)] = best;
-                        load[best] += pc;
-                    }
-                }
-                if (plan_mode == 0 && plan_runs) {
-                    // Light blocks (one part) in RUNS of consecutive columns: the cameras next to each other in the column list see the same
-                    // landmarks, so a landmark's pairs in light blocks mostly fall to one wave, side by side in its list -- and share the
-                    // requests for the landmark's own record and inverse block again.  The runs fill the waves up to an equal share.
-                    const size_t target = (total + NW - 1) / NW;
-                    int cw = 0;
-                    for (int q = 0; q < ncols; ++q) {
-                        if (nparts[(size_t)q] != 1) continue;
-                        while (cw < NW - 1 && load[cw] >= target) ++cw;
-                        wave_of[(size_t)vsf[q]] = cw;
-                        load[cw] += (size_t)bc[q];
-                    }
-                }
-                size_t wpos[NW];
-                {
-                    size_t off = cnt[(size_t)k];
-                    for (int w2 = 0; w2 < NW; ++w2) {
-                        pair_begin[(size_t)k * NW + w2] = (int)off; wpos[w2] = off;
-                        off += load[w2];
-                        pair_end[(size_t)k * NW + w2] = (int)off;
-                    }
-                }
-                // ---- pass 2: the records, every wave's list in landmark-major order
-                for (int p = p0; p < p1; ++p) {
-                    const int i = cam_perm[p];
-                    const int j = s_pt[i];
-                    const int w = range_of[(size_t)(p - p0)];
-                    for (int l = pt_start[j]; l < pt_start[j + 1]; ++l) {
-                        const int c2 = s_cam[l];
-                        // (the pairs (i, i) -- an observation's own term of the diagonal block and of the right-hand side -- are
-                        // made by the camera-block pass of the Schur kernel in registers, not here)
-                        if (c2 > c || l == i) continue;
-                        const int sl = slot_of[(size_t)c2];
-                        if (sl < slo || sl >= shi) continue;
-                        const int q = sl - slo;
-                        const int v = vsf[q] + w / (NW / nparts[(size_t)q]);
-                        pair_rec[wpos[wave_of[(size_t)v]]++] = make_int4(i, l, j, v | (c2 == c ? 0x8000 : 0));
-                        if (c2 == c) ++diag_pairs_thr[(size_t)(tix & 63)];
-                    }
-                }
-                // ---- the COLUMN ROTATION of every pair (bits 16..18 of its fourth word).  The 64 pairs of one wave instruction that add
-                // to the SAME block are served one after the other by ds_add_f64 unless they meet in different addresses: the kernel
-                // lets a lane walk the six columns of its block starting at column `rotation`.  Round 6: the rotation is the pair's RANK
-                // among the pairs of its trip that share its accumulator slot (mod 6) -- the host knows who meets whom.  Until then
-                // it was lane mod 3, which does nothing where a landmark has 9 or 12 partners: the lanes that meet -- the same partner
-                // camera, consecutive landmarks -- are then 9 or 12 lanes apart.
-                {
-                    rank_of.assign((size_t)nvs, 0);
-                    const size_t t_lo = cnt[(size_t)k], t_hi = cnt[(size_t)k + 1];
-                    for (int w2 = 0; w2 < NW; ++w2) {
-                        const size_t lb = (size_t)pair_begin[(size_t)k * NW + w2], le = (size_t)pair_end[(size_t)k * NW + w2];
-                        (void)t_lo; (void)t_hi;
-                        for (size_t x0 = lb; x0 < le; x0 += 64) {
-                            const size_t x1 = std::min(le, x0 + 64);
-                            for (size_t x = x0; x < x1; ++x) {
-                                const int v = pair_rec[x].w & 0x3fff;
-                                const int rot = rot_by_rank ? rank_of[(size_t)v]++ % 6 : 2 * (int)((x - x0) % 3);
-                                pair_rec[x].w |= rot << 16;
-                            }
-                            if (rot_by_rank) for (size_t x = x0; x < x1; ++x) rank_of[(size_t)(pair_rec[x].w & 0x3fff)] = 0;
-                        }
-                    }
-                }
-            }
-        });
-        for (int v : max_slots_thr) max_slots = std::max(max_slots, v);
-    }
-    b->max_cols = std::max(task_max_cols, max_slots);       // accumulator slots of the largest task (blocks + extra parts)
-    {   // LDS atomics of one launch: 36 per pair (21 in a diagonal block)
-        double at = 0.0;
-        size_t n_diag = 0;
-        for (size_t v : diag_pairs_thr) n_diag += v;
-        at = 36.0 * (double)(n_pair_rec - n_diag) + 21.0 * (double)n_diag;
-        b->schur_pairs = (double)n_pair_rec; b->schur_lds_atomics = at;
-    }
-    // landmark-range slices: where every task writes its partial blocks, and every row's tasks in list order (the order of the sum)
-    std::vector<long long> task_part_off;
-    std::vector<int> row_task_ptr, row_tasks;
-    size_t part_doubles = 0;
-    if (b->lm_slices) {
-        const int ntask = (int)task_cam.size();
-        task_part_off.resize((size_t)ntask);
-        for (int k = 0; k < ntask; ++k) {
-            task_part_off[(size_t)k] = (long long)part_doubles;
-            part_doubles += (size_t)(task_col_hi[(size_t)k] - task_col_lo[(size_t)k]) * 36 + 64;
-        }
-        std::vector<std::vector<std::pair<int, int>>> by_row((size_t)n_cams);
-        for (int k = 0; k < ntask; ++k) by_row[(size_t)task_cam[(size_t)k]].push_back({task_p_lo[(size_t)k], k});
-        row_task_ptr.assign((size_t)n_cams + 1, 0);
-        for (int c = 0; c < n_cams; ++c) {
-            std::sort(by_row[(size_t)c].begin(), by_row[(size_t)c].end());
-            for (auto& pr : by_row[(size_t)c]) row_tasks.push_back(pr.second);
-            row_task_ptr[(size_t)c + 1] = (int)row_tasks.size();
-        }
-    }
-    tmark("pair plan");
+    SchurPlanOptions popt;
+    popt.iterative = iterative;
+    popt.lda = b->lda;
+    size_t total_b = 0;
+    if (!iterative) popt.have_mem_info = hipMemGetInfo(&popt.free_bytes, &total_b) == hipSuccess;
+    static const int TASK_PAIRS = knob_int("STBA_SCHUR_TASK_PAIRS", SCHUR_TASK_PAIRS);
+    popt.task_pairs = TASK_PAIRS;
+    popt.plan_knob = knob_int("STBA_SCHUR_PLAN", SCHUR_PLAN_DEFAULT);
+    popt.plan_runs = knob_int("STBA_SCHUR_RUNS", 1) != 0;
+    popt.rot_by_rank = knob_int("STBA_SCHUR_ROT_RANK", 1) != 0;
+    popt.lm_slices_allowed = knob_int("STBA_SCHUR_LM_SLICES", 1) != 0;
+    popt.phase = tmark;
+    // the whole host-side plan (schur_plan.hpp); the engine keeps it until it is destroyed, see the end of this function
+    auto plan = std::make_shared<SchurPlan>();
+    std::string why;
+    if (build_schur_plan(n_cams, n_pts, n_obs, obs_cam, obs_pt, obs_feat, popt, plan.get(), &why) != 0)
+        return bail(fail(STBA_ERR_INVALID_ARGUMENT, why));
+    const SchurPlan& P = *plan;
+    b->n_chunks = (int)P.chunk_begin.size();
+    b->dup_overflow = P.dup_overflow;
+    b->schur_mode = b->schur_mode_auto = P.schur_mode;
+    b->have_pair_plan = P.have_pair_plan;
+    b->lm_slices = P.lm_slices;
+    b->n_tasks = P.n_tasks; b->max_cols = P.max_cols;
+    b->schur_plan_mode = P.plan_mode;
+    b->schur_pairs = (double)P.pairs; b->schur_lds_atomics = P.lds_atomics;
     std::vector<unsigned char> cmask;
     if (cam_fixed) {
         cmask.resize(n_cams);
@@ -1843,23 +1428,23 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     A_(dev_alloc(&b->pt_start, np + 1)); A_(dev_alloc(&b->cam_perm, no));
     A_(dev_alloc(&b->chunk_begin, (size_t)b->n_chunks)); A_(dev_alloc(&b->chunk_end, (size_t)b->n_chunks));
     A_(dev_alloc(&b->cam_chunk_start, nc + 1));
-    A_(dev_alloc(&b->task_cam, std::max<size_t>(task_cam.size(), 1))); A_(dev_alloc(&b->cam_start, nc + 1));
-    A_(dev_alloc(&b->task_col_lo, std::max<size_t>(task_cam.size(), 1))); A_(dev_alloc(&b->task_col_hi, std::max<size_t>(task_cam.size(), 1)));
-    A_(dev_alloc(&b->row_col_ptr, nc + 1)); A_(dev_alloc(&b->row_cols, std::max<size_t>(row_cols.size(), 1)));
-    A_(dev_alloc(&b->pair_begin, std::max<size_t>(pair_begin.size(), 1))); A_(dev_alloc(&b->pair_end, std::max<size_t>(pair_end.size(), 1)));
-    A_(dev_alloc(&b->pair_rec, std::max<size_t>(n_pair_rec, 1)));
-    A_(dev_alloc(&b->task_vs_ptr, std::max<size_t>(task_vs_ptr.size(), 1))); A_(dev_alloc(&b->vs_first, std::max<size_t>(vs_first.size(), 1)));
+    A_(dev_alloc(&b->task_cam, P.task_cam.size())); A_(dev_alloc(&b->cam_start, nc + 1));
+    A_(dev_alloc(&b->task_col_lo, P.task_cam.size())); A_(dev_alloc(&b->task_col_hi, P.task_cam.size()));
+    A_(dev_alloc(&b->row_col_ptr, nc + 1)); A_(dev_alloc(&b->row_cols, P.row_cols.size()));
+    A_(dev_alloc(&b->pair_begin, P.pair_begin.size())); A_(dev_alloc(&b->pair_end, P.pair_end.size()));
+    A_(dev_alloc(&b->pair_rec, P.pairs));
+    A_(dev_alloc(&b->task_vs_ptr, P.task_vs_ptr.size())); A_(dev_alloc(&b->vs_first, P.vs_first.size()));
     if (cam_fixed) A_(dev_alloc(&b->cam_fixed, nc));
     if (pt_fixed) A_(dev_alloc(&b->pt_fixed, np));
     if (b->lm_slices) {
-        A_(dev_alloc(&b->task_p_lo, task_p_lo.size())); A_(dev_alloc(&b->task_p_hi, task_p_hi.size())); A_(dev_alloc(&b->task_part_off, task_part_off.size()));
-        A_(dev_alloc(&b->row_task_ptr, row_task_ptr.size())); A_(dev_alloc(&b->row_tasks, std::max<size_t>(row_tasks.size(), 1)));
-        A_(dev_alloc(&b->schur_part, std::max<size_t>(part_doubles, 1)));
-        A_(upload(b->task_p_lo, task_p_lo.data(), task_p_lo.size(), b->st)); A_(upload(b->task_p_hi, task_p_hi.data(), task_p_hi.size(), b->st));
-        A_(upload(b->task_part_off, task_part_off.data(), task_part_off.size(), b->st));
-        A_(upload(b->row_task_ptr, row_task_ptr.data(), row_task_ptr.size(), b->st)); A_(upload(b->row_tasks, row_tasks.data(), row_tasks.size(), b->st));
+        A_(dev_alloc(&b->task_p_lo, P.task_p_lo.size())); A_(dev_alloc(&b->task_p_hi, P.task_p_hi.size())); A_(dev_alloc(&b->task_part_off, P.task_part_off.size()));
+        A_(dev_alloc(&b->row_task_ptr, P.row_task_ptr.size())); A_(dev_alloc(&b->row_tasks, P.row_tasks.size()));
+        A_(dev_alloc(&b->schur_part, P.part_doubles));
+        A_(upload(b->task_p_lo, P.task_p_lo.data(), P.task_p_lo.size(), b->st)); A_(upload(b->task_p_hi, P.task_p_hi.data(), P.task_p_hi.size(), b->st));
+        A_(upload(b->task_part_off, P.task_part_off.data(), P.task_part_off.size(), b->st));
+        A_(upload(b->row_task_ptr, P.row_task_ptr.data(), P.row_task_ptr.size(), b->st)); A_(upload(b->row_tasks, P.row_tasks.data(), P.row_tasks.size(), b->st));
     }
-    if (!dup_run.empty()) { A_(dev_alloc(&b->dup_run, no)); A_(upload(b->dup_run, dup_run.data(), no, b->st)); }
+    if (!P.dup_run.empty()) { A_(dev_alloc(&b->dup_run, no)); A_(upload(b->dup_run, P.dup_run.data(), no, b->st)); }
     A_(dev_alloc(&b->r, no)); A_(dev_alloc(&b->J8, no * 8));
     if (cam_fixed || pt_fixed) A_(dev_alloc(&b->omask, no));
     A_(dev_alloc(&b->Hpp6, np * 6)); A_(dev_alloc(&b->gp, np * 3)); A_(dev_alloc(&b->Hinv6, np * 6));
@@ -1876,28 +1461,28 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
 
     tmark("device allocations");
     A_(upload(b->cams[0], cams, nc * 7, b->st)); A_(upload(b->pts[0], pts, np * 3, b->st));
-    A_(upload(reinterpret_cast<double*>(b->feat), s_feat.data(), no * 2, b->st));
-    A_(upload(b->obs_cam, s_cam.data(), no, b->st)); A_(upload(b->obs_pt, s_pt.data(), no, b->st));
-    A_(upload(b->pt_start, pt_start.data(), np + 1, b->st)); A_(upload(b->cam_perm, cam_perm.data(), no, b->st));
-    A_(upload(b->chunk_begin, chunk_begin.data(), (size_t)b->n_chunks, b->st));
-    A_(upload(b->chunk_end, chunk_end.data(), (size_t)b->n_chunks, b->st));
-    A_(upload(b->cam_chunk_start, cam_chunk_start.data(), nc + 1, b->st));
-    A_(upload(b->task_cam, task_cam.data(), task_cam.size(), b->st));
-    A_(upload(b->cam_start, cam_start.data(), nc + 1, b->st));
-    A_(upload(b->task_col_lo, task_col_lo.data(), task_cam.size(), b->st));
-    A_(upload(b->task_col_hi, task_col_hi.data(), task_cam.size(), b->st));
-    b->h_row_col_ptr = row_col_ptr; b->h_row_cols = row_cols;
-    A_(upload(b->row_col_ptr, row_col_ptr.data(), nc + 1, b->st));
-    if (!row_cols.empty()) A_(upload(b->row_cols, row_cols.data(), row_cols.size(), b->st));
-    A_(upload(b->pair_begin, pair_begin.data(), pair_begin.size(), b->st)); A_(upload(b->pair_end, pair_end.data(), pair_end.size(), b->st));
-    if (n_pair_rec > 0) A_(upload(b->pair_rec, pair_rec.get(), n_pair_rec, b->st));
-    A_(upload(b->task_vs_ptr, task_vs_ptr.data(), task_vs_ptr.size(), b->st)); A_(upload(b->vs_first, vs_first.data(), vs_first.size(), b->st));
+    A_(upload(reinterpret_cast<double*>(b->feat), P.s_feat.data(), no * 2, b->st));
+    A_(upload(b->obs_cam, P.s_cam.data(), no, b->st)); A_(upload(b->obs_pt, P.s_pt.data(), no, b->st));
+    A_(upload(b->pt_start, P.pt_start.data(), np + 1, b->st)); A_(upload(b->cam_perm, P.cam_perm.data(), no, b->st));
+    A_(upload(b->chunk_begin, P.chunk_begin.data(), (size_t)b->n_chunks, b->st));
+    A_(upload(b->chunk_end, P.chunk_end.data(), (size_t)b->n_chunks, b->st));
+    A_(upload(b->cam_chunk_start, P.cam_chunk_start.data(), nc + 1, b->st));
+    A_(upload(b->task_cam, P.task_cam.data(), P.task_cam.size(), b->st));
+    A_(upload(b->cam_start, P.cam_start.data(), nc + 1, b->st));
+    A_(upload(b->task_col_lo, P.task_col_lo.data(), P.task_cam.size(), b->st));
+    A_(upload(b->task_col_hi, P.task_col_hi.data(), P.task_cam.size(), b->st));
+    b->h_row_col_ptr = P.row_col_ptr; b->h_row_cols = P.row_cols;
+    A_(upload(b->row_col_ptr, P.row_col_ptr.data(), nc + 1, b->st));
+    if (!P.row_cols.empty()) A_(upload(b->row_cols, P.row_cols.data(), P.row_cols.size(), b->st));
+    A_(upload(b->pair_begin, P.pair_begin.data(), P.pair_begin.size(), b->st)); A_(upload(b->pair_end, P.pair_end.data(), P.pair_end.size(), b->st));
+    if (P.pairs > 0) A_(upload(b->pair_rec, reinterpret_cast<const int4*>(P.pair_rec.get()), P.pairs, b->st));
+    A_(upload(b->task_vs_ptr, P.task_vs_ptr.data(), P.task_vs_ptr.size(), b->st)); A_(upload(b->vs_first, P.vs_first.data(), P.vs_first.size(), b->st));
     if (cam_fixed) A_(upload(b->cam_fixed, cmask.data(), nc, b->st));
-    std::vector<unsigned char> omask;
+    std::vector<unsigned char>& omask = b->create_omask;
     if (b->omask) {
         omask.resize(no);
         for (size_t p2 = 0; p2 < no; ++p2)
-            omask[p2] = (unsigned char)((cam_fixed ? cmask[(size_t)s_cam[p2]] : 0u) | ((pt_fixed && pt_fixed[(size_t)s_pt[p2]]) ? 64u : 0u));
+            omask[p2] = (unsigned char)((cam_fixed ? cmask[(size_t)P.s_cam[p2]] : 0u) | ((pt_fixed && pt_fixed[(size_t)P.s_pt[p2]]) ? 64u : 0u));
         A_(upload(b->omask, omask.data(), no, b->st));
     }
     if (pt_fixed) A_(upload(b->pt_fixed, pt_fixed, np, b->st));
@@ -1912,19 +1497,8 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     // the caller gets its engine that much sooner, and the operator API destroys its engine on a helper thread next to its end-point
     // check anyway.  (Freed by a thread of their own right here: 10 ms off this function as well, but 2 ms ON a drop-in Solve() -- the
     // munmap of 110 MB holds the process's address-space lock while the calling thread faults pages in.)
-    {
-        struct Garbage {
-            std::unique_ptr<int4[]> pair_rec;
-            std::vector<int> a, b2, c, d, e, f;
-            std::vector<double> g;
-            std::vector<unsigned char> h, i;
-            std::vector<std::vector<int>> j;
-        };
-        Garbage* gb = new (std::nothrow) Garbage{std::move(pair_rec), std::move(s_cam), std::move(s_pt), std::move(cam_perm), std::move(pt_start),
-                                                 std::move(vs_first), std::move(row_cols), std::move(s_feat), std::move(dup_run), std::move(omask),
-                                                 std::move(cnt_of)};
-        if (gb) b->create_leftovers = std::shared_ptr<void>(gb, [](void* q) { delete static_cast<Garbage*>(q); });
-    }
+    b->perm = std::move(plan->perm);
+    b->create_leftovers = std::move(plan);
     *out = b;
     return STBA_OK;
 }
