@@ -1599,6 +1599,17 @@ int pg_linearize(stba_pg* g, int which, bool jac) {
     return STBA_OK;
 }
 
+// the all-reduce hook over `count` doubles at `buf`, on the engine's stream (one rank: nothing)
+int pg_hook(stba_pg* g, double* buf, size_t count) {
+    if (g->ar && g->ar(g->ar_user, buf, count, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
+    return STBA_OK;
+}
+
+// gradient | diagonal blocks of the last pg_linearize(jac), gathered per node
+void pg_gather_blocks(stba_pg* g) {
+    hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->node_start, g->end_code, g->contrib, g->g, g->Hd);
+}
+
 // q = (J^T J [+ D]) v.  Sharded: every rank applies its edges, rank 0 alone adds the diagonal term, and the
 // hook sums the 6n-vector (the only data-path collective of a PCG iteration: every other vector operation
 // is replicated and bit-identical on all ranks).
@@ -1607,15 +1618,14 @@ int pg_apply(stba_pg* g, const double* v, double* q, bool with_d) {
                        (with_d && g->rank == 0) ? 1 : 0);
     hipLaunchKernelGGL(pg_matvec_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, v, q);
     STBA_HIP(hipGetLastError());
-    if (g->ar && g->ar(g->ar_user, q, (size_t)6 * g->n, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-    return STBA_OK;
+    return pg_hook(g, q, (size_t)6 * g->n);
 }
 
 // sum of a host scalar across ranks (through one device double and the hook)
 int pg_sum_ranks(stba_pg* g, double* v) {
     if (!g->ar) return STBA_OK;
     STBA_HIP(hipMemcpyAsync(g->scalar, v, sizeof(double), hipMemcpyHostToDevice, g->st));
-    if (g->ar(g->ar_user, g->scalar, 1, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
+    STBA_TRY(pg_hook(g, g->scalar, 1));
     STBA_HIP(hipMemcpyAsync(v, g->scalar, sizeof(double), hipMemcpyDeviceToHost, g->st));
     STBA_HIP(hipStreamSynchronize(g->st));
     return STBA_OK;
@@ -1633,13 +1643,18 @@ int pg_cov_linearize(stba_pg* g, PgCovDevice* out) {
     // (a coarse inverse of the last solve may still be reading the diagonal blocks on the second stream)
     if (g->st2 && g->job_in_flight) STBA_HIP(hipStreamSynchronize(g->st2));
     STBA_TRY(pg_linearize(g, g->cur, true));
-    hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->node_start, g->end_code, g->contrib, g->g, g->Hd);
+    pg_gather_blocks(g);
     STBA_HIP(hipGetLastError());
     out->st = g->st; out->node_start = g->node_start; out->end_code = g->end_code; out->end_rem = g->end_rem;
     out->Ji = g->Ji; out->Jj = g->Jj; out->Hd = g->Hd; out->fixed = g->fixed;
     return STBA_OK;
 }
 }  // namespace stba
+
+// the dynamic LDS of pg_coarse_build_kernel: six coarse columns and the edge ends of the largest group; what a launch may ask for
+// at the most (+ 20 KB static in the kernel)
+static constexpr size_t PG_COARSE_BUILD_LDS_MAX = 136 * 1024;
+static size_t pg_coarse_build_lds(int nc, int max_group_ends) { return (size_t)6 * nc * sizeof(double) + (size_t)4 * max_group_ends * sizeof(int); }
 
 // ---- coarse space: sizes and buffers for a group size (lazily: the group size is an option of the solve)
 static int pg_setup_coarse(stba_pg* g, int group_opt) {
@@ -1655,7 +1670,7 @@ static int pg_setup_coarse(stba_pg* g, int group_opt) {
     int max_ends = 0;
     for (int a = 0; a < na; ++a)
         max_ends = std::max(max_ends, g->h_node_start[(size_t)std::min(g->n, (a + 1) * agg)] - g->h_node_start[(size_t)std::min(g->n, a * agg)]);
-    if ((size_t)6 * nc * sizeof(double) + (size_t)4 * max_ends * sizeof(int) > 136 * 1024)       // (+ 20 KB static in pg_coarse_build_kernel)
+    if (pg_coarse_build_lds(nc, max_ends) > PG_COARSE_BUILD_LDS_MAX)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_solve: coarse space too large for this group size");
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     if (g->st2) STBA_HIP(hipStreamSynchronize(g->st2));       // (a job of the last solve may still be writing W / an inverse)
@@ -1669,7 +1684,7 @@ static int pg_setup_coarse(stba_pg* g, int group_opt) {
     STBA_HIP(hipMemsetAsync(g->rc_part, 0, (size_t)na * parts * 6 * sizeof(double), g->st));
     static DeviceOnce attr;
     STBA_TRY(attr.run([]() -> int {
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_coarse_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_coarse_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PG_COARSE_BUILD_LDS_MAX));
         return STBA_OK;
     }));
     g->agg = agg; g->na = na; g->nc = nc; g->np = np; g->parts = parts; g->max_group_ends = max_ends;
@@ -1697,6 +1712,387 @@ static int pg_wait_if_pending(hipStream_t st, hipEvent_t ev) {
     STBA_HIP(hipStreamWaitEvent(st, ev, 0));
     return STBA_OK;
 }
+
+// ---- stba_pg_solve's steps.  PgSolve is the state of ONE call; what outlives a call (job_in_flight, job_reads_pending, bend_valid,
+// ac0_valid, coarse_valid, pp_base, pp_disabled, seq) stays in stba_pg.  No step captures anything; every launch is written once.
+namespace {
+struct PgSolve {
+    stba_lm_options opt;
+    stba_pcg_options pcg;
+    // derived once
+    bool coarse = false, async_inv = false, build_on_st2 = false, multi = false, forcing = false, pp_ok = false, timing = false;
+    int chunk = 1;
+    // the loop
+    TrustRegion region;
+    double cost = 0.0, gmax = 0.0, g2 = 0.0, eta = 0.0;
+    double last_rel_decrease = 1.0;      // of the last accepted step: (cost before - cost after) / cost before
+    int iter = 0, jobs = 0, since_refresh = 0;
+    bool scale_init = false;
+    bool head_done = false;              // the preconditioner and the job's head of the NEXT iteration are already on their way
+    stba_pcg_summary ps;
+    PgSolve(const stba_lm_options& o, const stba_pcg_options& p) : opt(o), pcg(p), region(o) { memset(&ps, 0, sizeof ps); }
+};
+
+// the rest of a second-stream job, for whoever enqueues it: the buffer of the pair it writes, and whether its head is already out
+struct PgJob { int wbuf = 0; bool head_was_done = false; };
+// what pg_coarse_refresh leaves to the iteration: the inverse its PCG reads, and a job that is still to be enqueued
+struct PgCoarseUse { const double* Ainv = nullptr; bool job_deferred = false; PgJob job; };
+
+void pg_precond(stba_pg* g, PgSolve& sv) {
+    hipLaunchKernelGGL(pg_precond_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->Hd, g->scale, sv.scale_init ? 0 : 1,
+                       sv.opt.jacobi_scaling, sv.region.radius, sv.opt.min_lm_diagonal, sv.opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
+    sv.scale_init = true;
+}
+
+void pg_offdiag_if_stale(stba_pg* g) {
+    if (g->bend_valid) return;
+    hipLaunchKernelGGL(pg_offdiag_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->Ji, g->Jj, g->end_pos, g->Bend);
+    g->bend_valid = true;
+}
+
+// the coarse matrix P^T J^T J P from the blocks; add_nodes: with the diagonal blocks' part (several ranks: rank 0 alone)
+void pg_coarse_build(stba_pg* g, hipStream_t st, int add_nodes) {
+    hipLaunchKernelGGL(pg_coarse_build_kernel, dim3(g->na), dim3(256), pg_coarse_build_lds(g->nc, g->max_group_ends), st, g->n, g->agg, g->nc,
+                       add_nodes, g->node_start, g->end_node, g->end_rem, g->Bend, g->Hd, g->AdP, g->Ac0);
+}
+
+// its damping term P^T D P, and W = the padded sum of the two
+void pg_coarse_damped(stba_pg* g, hipStream_t st) {
+    const size_t cnt = (size_t)3 * g->np * g->np;
+    hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->na), dim3(256), 0, st, g->n, g->agg, g->AdP, g->d, g->Dc);
+    hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g->nc, g->np, g->Ac0, g->Dc, g->W);
+}
+
+// W^-1 -> Aout
+int pg_coarse_invert(stba_pg* g, hipStream_t st, double* Aout) {
+    STBA_TRY(chol_spd_inverse_dev(g->W, 2 * g->np, g->np, g->nc, g->cflag, g->inv_work, st));
+    hipLaunchKernelGGL(pg_coarse_finish_kernel, dim3((unsigned)(((size_t)g->nc * g->nc + 255) / 256)), dim3(256), 0, st, g->nc, g->np, g->W, Aout,
+                       g->cflag, g->cflag + 1);
+    return STBA_OK;
+}
+
+// the tail of the two finish kernels.  One rank: the kernel has written the stamped block itself.  Several: it wrote g->scal_dev, the
+// hook sums the first n_summed scalars and a kernel exports the n_payload of them with the stamp.  Then the host reads g->fin_vals.
+int pg_read_block(stba_pg* g, int n_summed, int n_payload) {
+    if (g->ar) {
+        STBA_TRY(pg_hook(g, g->scal_dev, (size_t)n_summed));
+        hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, n_payload, g->scal_dev, g->fin.dev, g->seq);
+    }
+    STBA_HIP(hipGetLastError());
+    const double seq = g->seq;
+    return stamped_wait(g->fin.host, n_payload, [seq](double st) { return st == seq; }, g->fin_vals, hip_stream_state(g->st), "pose graph", 120.0);
+}
+
+// (the job of the second stream reads the blocks, the coarse basis and the damping of the linearisation it belongs to: whatever
+// overwrites them -- the next linearisation, or the preconditioner kernel -- waits until it has: an event that has long fired by then)
+int pg_wait_for_job_reads(stba_pg* g) {
+    if (g->job_reads_pending) { STBA_TRY(pg_wait_if_pending(g->st, g->ev_read)); g->job_reads_pending = false; }
+    return STBA_OK;
+}
+
+// the PCG solve as one kernel: one rank, a coarse space whose groups fit a workgroup (<= 64 nodes, all their edge-end products
+// in LDS) and are all resident at once (one per CU)
+bool pg_one_kernel_eligible(stba_pg* g, const PgSolve& sv) {
+    bool pp_ok = sv.pcg.one_kernel_solve != 0 && !sv.multi && sv.coarse && g->agg <= 64 && g->na <= 256 && g->nc <= PP_NCMAX &&
+                 pp_lds_bytes(g->na, g->nc) <= (size_t)160 * 1024 - 64;
+    if (pp_ok) {
+        int dev = 0, cus = 0, lds_max = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g->na > cus) pp_ok = false;
+        // (the LDS a workgroup may opt in to is a property of the device and the driver: asked, not assumed -- advisor, round 5)
+        if (pp_ok && (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || pp_lds_bytes(g->na, g->nc) > (size_t)std::max(0, lds_max - 64))) pp_ok = false;
+        if (g->max_group_ends > PP_VCAP) pp_ok = false;
+    }
+    if (pp_ok) {
+        static DeviceOnce attr;
+        // a device that refuses the attribute takes the launch path; that is not a failed solve
+        if (attr.run([]() -> int {
+                STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_pcg_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+                return STBA_OK;
+            }) != STBA_OK) { pp_ok = false; g->pp_disabled = true; (void)hipGetLastError(); }
+    }
+    return pp_ok;
+}
+
+// ---- set-up of a solve: the coarse space for this group size, the second stream, the flags derived once
+int pg_solve_begin(stba_pg* g, PgSolve& sv) {
+    const stba_pcg_options& pcg = sv.pcg;
+    STBA_TRY(pg_setup_coarse(g, pcg.coarse_group));
+    sv.coarse = g->agg > 0;
+    // the second stream of the coarse inverse (pg_coarse_refresh); a job of the previous solve may still be in flight: it is awaited here,
+    // where it costs nothing, instead of at the end of that solve, where it would have been the last 0.3 ms of its wall time
+    sv.async_inv = sv.coarse && pcg.coarse_async != 0;
+    if (sv.async_inv) {
+        STBA_TRY(pg_second_stream(g));
+        if (g->job_in_flight) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; }
+        g->job_reads_pending = false;
+    }
+    sv.build_on_st2 = sv.async_inv && !g->ar;
+    if (sv.coarse) STBA_HIP(hipMemsetAsync(g->cflag + 1, 0, sizeof(int), g->st));      // this solve's count of failed coarse operators
+    sv.multi = (g->ar != nullptr);
+    sv.chunk = std::max(1, pcg.check_every);
+    sv.forcing = pcg.forcing_eta0 > 0.0;
+    sv.eta = pcg.forcing_eta0;
+    sv.ps.coarse_dim = sv.coarse ? g->nc : 0;
+    sv.pp_ok = pg_one_kernel_eligible(g, sv);
+    // (stba_lm_options::phase_timing: hipEvents around the linear solve -- the persistent kernel, or the launches of the PCG loop --
+    // for bench.py's roofline of the C4 line; an event is a packet of its own on the queue, so only on request)
+    sv.timing = sv.opt.phase_timing != 0;
+    return STBA_OK;
+}
+
+// ---- linearisation at the current point: residuals, Jacobians, gradient | diagonal blocks, the coarse basis and matrix
+int pg_linearize_enqueue(stba_pg* g, const PgSolve& sv) {
+    STBA_TRY(pg_wait_for_job_reads(g));
+    STBA_TRY(pg_linearize(g, g->cur, true));
+    pg_gather_blocks(g);
+    STBA_TRY(pg_hook(g, g->g, (size_t)g->n * 42));
+    hipLaunchKernelGGL(pg_gnorm_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, 6 * g->n, g->g, g->part_c);
+    if (sv.coarse) {
+        hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->agg, g->poses[g->cur], g->fixed, g->AdP);
+        pg_offdiag_if_stale(g);
+        // (one rank with the coarse inverse on its second stream: the coarse MATRIX is only read by that job, and is built there --
+        // 55 us of every LM iteration off the critical path; several ranks sum it with the hook, on the engine's stream)
+        if (!sv.build_on_st2) {
+            pg_coarse_build(g, g->st, (!g->ar || g->rank == 0) ? 1 : 0);
+            STBA_TRY(pg_hook(g, g->Ac0, (size_t)g->nc * g->nc));
+        }
+        g->coarse_valid = false;
+        g->ac0_valid = false;
+    }
+    STBA_HIP(hipGetLastError());
+    return STBA_OK;
+}
+
+// cost and |g|_inf of that linearisation: one kernel sums, the host reads mapped memory (several ranks: the cost goes over the hook)
+int pg_linearize_finish(stba_pg* g, double* cost, double* gmax, double* g2) {
+    g->seq += 1.0;
+    hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->ar ? g->scal_dev : g->fin.dev, g->seq);
+    STBA_TRY(pg_read_block(g, 1, 3));
+    *cost = 0.5 * g->fin_vals[0]; *gmax = g->fin_vals[1]; *g2 = g->fin_vals[2];
+    return STBA_OK;
+}
+
+// the HEAD of the second stream's job (one rank): everything the inverse needs -- the coarse matrix from the blocks, the diagonal
+// blocks and the basis of THIS linearisation, its damping term, the workspace; READ_k tells the first stream when its next
+// linearisation / preconditioner kernel may overwrite those inputs.  Three launches: behind an accepted step they are enqueued
+// at once (the preconditioner kernel in front of them), so that they run under the host's wait for the new point's scalars
+// instead of at the start of the PCG kernel, with which the inversion then competes for CUs.
+int pg_job_head(stba_pg* g) {
+    STBA_HIP(hipStreamWaitEvent(g->st2, g->ev_in, 0));
+    if (!g->ac0_valid) {
+        pg_coarse_build(g, g->st2, 1);
+        g->ac0_valid = true;
+    }
+    pg_coarse_damped(g, g->st2);
+    STBA_HIP(hipEventRecord(g->ev_read, g->st2));
+    g->job_reads_pending = true;
+    g->job_in_flight = true;
+    return STBA_OK;
+}
+
+// THE JOB: ~ 30 launches on the second stream.  Enqueueing them takes the HOST ~ 250 us -- so when the iteration does not
+// wait for them (the usual case), the PCG kernel is launched FIRST and the job is enqueued while it runs: with the job in
+// front, the kernel timeline showed the first stream idle for 277 us of every 760 us iteration, waiting for the host
+// (profiles/r6_c4_iter_trace.txt)
+int pg_job_rest(stba_pg* g, const PgSolve& sv, const PgJob& job) {
+    if (!job.head_was_done) { if (sv.build_on_st2) STBA_TRY(pg_job_head(g)); else STBA_HIP(hipStreamWaitEvent(g->st2, g->ev_in, 0)); }
+    STBA_TRY(pg_coarse_invert(g, g->st2, job.wbuf ? g->Ainv2 : g->Ainv));
+    STBA_HIP(hipEventRecord(g->ev_job[job.wbuf], g->st2));
+    g->job_in_flight = true;
+    return STBA_OK;
+}
+
+// does this iteration's PCG wait for the inverse of its OWN operator (or take the one made an LM iteration earlier)?
+// The first solve(s) wait (coarse_async = 2: not with a forcing sequence; coarse_async_after: how many LM iterations do -- the
+// operator changes most in the first iterations) -- and every solve that follows a LONG step: the operator is stale by exactly the
+// step that was just taken.  At C4 (profiles/r6_c4_async.txt) the steps of the first three iterations take 98 %, 97 % and 45 % off
+// the cost, the later ones 1 % and less; preconditioning iteration 3 with iteration 2's operator ends 3.9e-5 from the exact-step
+// poses, iterations 4 .. 9 with their predecessors' 2.9e-6 (in line: 2.5e-6).  Rule: lag only behind a step that took at most
+// coarse_async_decrease (0.5) off the cost.
+// (also measured, profiles/r6_c4_async_coarse_tolerance_behind_long_steps.txt: not waiting behind a long step either and
+// giving THAT solve a tolerance on the coarse residual instead -- 3e-4 is what the poses need (2.4e-6), and then the extra
+// PCG iterations cost more than the wait: 1323 against 1411 LM it/s)
+bool pg_waits_for_own_inverse(const stba_pcg_options& pcg, bool forcing, int jobs, int iter, double last_rel_decrease) {
+    const bool long_step = iter <= pcg.coarse_async_after || last_rel_decrease > pcg.coarse_async_decrease;
+    return (jobs == 0 && (!forcing || pcg.coarse_async != 2)) || (pcg.coarse_async != 2 && long_step);
+}
+
+// ---- coarse operator (P^T (J^T J + D) P)^-1 of an LM iteration
+int pg_coarse_refresh(stba_pg* g, PgSolve& sv, bool head_was_done, PgCoarseUse* use) {
+    use->Ainv = g->Ainv;
+    use->job_deferred = false;
+    if (sv.coarse && sv.async_inv) {
+        // ROUND 6: off the critical path.  The inversion (eight panels of a ~45 us chain on a handful of CUs: 0.39 of a 0.92 ms LM
+        // iteration at C4) runs on a SECOND stream, next to this iteration's PCG kernel (157 workgroups on 256 CUs), and is applied one LM
+        // iteration LATE: iteration k preconditions with the inverse of iteration k - 1's operator -- an inverse made at the
+        // previous linearisation / damping still is a preconditioner, only a weaker one (coarse_refresh_every = 2 had measured
+        // + 9 % PCG iterations).  The very first solve has no predecessor: it waits for its own inverse (coarse_async = 2 with a
+        // forcing sequence: it runs on block Jacobi alone, Ainv = 0 -- 3 PCG iterations at eta_0 = 0.1, but a first step that
+        // leaves the cost at 1021 where the two-level step leaves 258 and the exact one 48: the whole trajectory moves).
+        // Everything is ordered by events, so the result does not depend on timing: run to run the same bits.
+        //   stream 1: precond_k | wait job_{k-1} | record IN_k | PCG_k (Ainv of job_{k-1}) | trial | wait READ_k | linearise ...
+        //   stream 2:                              wait IN_k   | coarse matrix, Dc_k, assemble W_k | record READ_k | invert -> Ainv[k & 1] | record job_k
+        // (several ranks: coarse matrix -- summed by the hook --, Dc_k and W_k stay on stream 1, IN_k is recorded behind them)
+        const int wbuf = sv.jobs & 1;
+        double* Aw = wbuf ? g->Ainv2 : g->Ainv;
+        double* Ar = wbuf ? g->Ainv : g->Ainv2;        // written by the previous job (or zeroed below)
+        if (sv.jobs == 0) STBA_HIP(hipMemsetAsync(Ar, 0, (size_t)g->nc * g->nc * sizeof(double), g->st));
+        else STBA_TRY(pg_wait_if_pending(g->st, g->ev_job[(sv.jobs - 1) & 1]));
+        const bool own = pg_waits_for_own_inverse(sv.pcg, sv.forcing, sv.jobs, sv.iter, sv.last_rel_decrease);
+        if (!sv.build_on_st2) pg_coarse_damped(g, g->st);
+        if (!head_was_done) STBA_HIP(hipEventRecord(g->ev_in, g->st));
+        use->job.wbuf = wbuf;
+        use->job.head_was_done = head_was_done;
+        use->Ainv = Ar;
+        if (own) {
+            STBA_TRY(pg_job_rest(g, sv, use->job));
+            STBA_HIP(hipStreamWaitEvent(g->st, g->ev_job[wbuf], 0));
+            use->Ainv = Aw;
+        } else use->job_deferred = true;
+        ++sv.jobs;
+        g->coarse_valid = true;
+        ++sv.ps.coarse_refreshes;
+    } else if (sv.coarse && (sv.ps.coarse_refreshes < 2 || sv.since_refresh >= std::max(1, sv.pcg.coarse_refresh_every))) {
+        // (synchronous form, coarse_async = 0) rebuilt when the linearisation or (every coarse_refresh_every-th time) the damping changed
+        // (the inverse is a preconditioner: one made at an earlier linearisation / damping still is one, only weaker -- with
+        // coarse_refresh_every = k it is re-made every k-th LM iteration; the first two iterations always make theirs)
+        pg_coarse_damped(g, g->st);
+        STBA_TRY(pg_coarse_invert(g, g->st, g->Ainv));
+        g->coarse_valid = true;
+        sv.since_refresh = 0;
+        ++sv.ps.coarse_refreshes;
+    }
+    ++sv.since_refresh;
+    return STBA_OK;
+}
+
+// ---- PCG on (J^T J + D) x = -g, stopped on the device at |r| <= eta_k |g|: four launches per iteration, watched by the host
+int pg_pcg_by_launches(stba_pg* g, const PgSolve& sv, const double* Ainv_use, double eta_k) {
+    const stba_pcg_options& pcg = sv.pcg;
+    const bool coarse = sv.coarse;
+    const double* AdP = coarse ? g->AdP : nullptr;
+    // (every kernel of the previous solve has finished -- the host has read the trial block behind them -- so the exported
+    // block can be taken back: the wait below must not see the previous solve's tick count and `done`)
+    g->exp.zero();
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    hipLaunchKernelGGL(pg_pcg_init4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, g->g, g->Minv, AdP, g->x, g->rr, g->z,
+                       g->rc_part, g->part_a);
+    if (coarse)
+        hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, (const PcgState*)nullptr, Ainv_use, g->rc_part,
+                           g->zc, g->part_cz);
+    hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
+                       g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+    STBA_HIP(hipGetLastError());
+    int enq = 0;
+    bool pcg_done = false;
+    double px[PX_COUNT];
+    STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [](double st) { return st >= 1.0; }, px, hip_stream_state(g->st), "pose graph",
+                          120.0));          // (also: the previous solve's ticks are gone)
+    if (px[PX_DONE] != 0.0) pcg_done = true;
+    while (!pcg_done && enq < pcg.max_iterations) {
+        const int todo = std::min(sv.chunk, pcg.max_iterations - enq);
+        for (int c = 0; c < todo; ++c, ++enq) {
+            const int slot = enq & 1;
+            if (!sv.multi) {
+                hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u,
+                                   g->part_c, g->state);
+                hipLaunchKernelGGL(pg_pcg_update4_kernel<true>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_edges,
+                                   g->part_c, g->nb_nodes4, g->part_d, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, (const double*)nullptr,
+                                   g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
+            } else {
+                STBA_TRY(pg_apply(g, g->p, g->q, true));
+                hipLaunchKernelGGL(pg_dot_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, 6 * g->n, g->p, g->q, g->part_c);
+                hipLaunchKernelGGL(pg_pcg_update4_kernel<false>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_vec,
+                                   g->part_c, 0, (const double*)nullptr, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, g->q,
+                                   g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
+            }
+            if (coarse)
+                hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, g->state, Ainv_use, g->rc_part, g->zc,
+                                   g->part_cz);
+            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, slot, 0, eta_k, pcg.max_iterations, g->state,
+                               g->exp.dev, g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+        }
+        STBA_HIP(hipGetLastError());
+        // one rank: the host looks at the chunk BEFORE the one it has just enqueued (the stream never runs dry; the kernels of a
+        // chunk enqueued past convergence return at once).  Several ranks: every rank must enqueue the same collectives, so the
+        // decision waits for the chunk itself -- the solve state is replicated and every rank sees the same `done`.
+        const double want = 1 + (sv.multi ? enq : enq - todo);
+        STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [want](double st) { return st >= want; }, px, hip_stream_state(g->st), "pose graph",
+                              120.0));
+        if (px[PX_DONE] != 0.0) pcg_done = true;
+    }
+    return STBA_OK;
+}
+
+// the same solve as ONE kernel (see pg_pcg_persistent_kernel): nothing for the host to watch, the trial point follows on the stream
+int pg_pcg_one_kernel(stba_pg* g, const PgSolve& sv, const double* Ainv_use, double eta_k) {
+    const stba_pcg_options& pcg = sv.pcg;
+    pg_offdiag_if_stale(g);
+    if (g->pp_base > (1 << 30)) {        // (stamps only grow; long before they wrap they are taken back to zero)
+        STBA_HIP(hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
+        STBA_HIP(hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
+        g->pp_base = 0;
+    }
+    PpArgs a;
+    a.n = g->n; a.agg = g->agg; a.log2agg = 0; while ((1 << a.log2agg) < g->agg) ++a.log2agg;
+    a.na = g->na; a.nc = g->nc; a.base = g->pp_base; a.max_iters = pcg.max_iterations; a.eta = eta_k;
+    a.node_start = g->node_start; a.end_rem = g->end_rem; a.Bend = g->Bend; a.Hd = g->Hd; a.d = g->d; a.Minv = g->Minv; a.AdP = g->AdP;
+    a.Ainv = Ainv_use; a.g = g->g; a.x = g->x; a.ubuf = g->ubuf; a.pbuf = g->pbuf; a.ustamp = g->ustamp; a.pstamp = g->pstamp;
+    a.state = g->state; a.spin_limit = pcg.one_kernel_solve == 2 ? 0 : 25000000ll;      // (a quarter of a second of wall_clock64 ticks; 2: the test of the way back)
+    a.fences = pcg.one_kernel_solve == 3 ? 1 : 0;
+    a.eta_c = sv.forcing ? pcg.coarse_eta : 0.0;
+    a.tdbg = nullptr;
+#ifdef STBA_DEBUG_KNOBS
+    static long long* tdbg_dev = nullptr;
+    if (knob_int("STBA_PP_TIMING", 0)) {
+        if (!tdbg_dev) { STBA_HIP(hipMalloc(&tdbg_dev, 8 * sizeof(long long))); STBA_HIP(hipMemset(tdbg_dev, 0, 8 * sizeof(long long))); }
+        a.tdbg = tdbg_dev;
+    }
+#endif
+    hipLaunchKernelGGL(pg_pcg_persistent_kernel, dim3(g->na), dim3(PP_T), pp_lds_bytes(g->na, g->nc), g->st, a);
+#ifdef STBA_DEBUG_KNOBS
+    if (a.tdbg) {
+        long long h[8];
+        STBA_HIP(hipMemcpyAsync(h, tdbg_dev, sizeof h, hipMemcpyDeviceToHost, g->st)); STBA_HIP(hipStreamSynchronize(g->st));
+        fprintf(stderr, "pp phases (x 10 ns, cumulative): publish %lld | ends %lld | w+sum9 %lld | all-gather %lld | scalars+update %lld | coarse+u %lld | loop top %lld\n",
+                h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
+    }
+#endif
+    STBA_HIP(hipGetLastError());
+    g->pp_base += pcg.max_iterations + 8;
+    return STBA_OK;
+}
+
+// ---- model change, trial point: |J x|^2 from the edge kernel (its |t_e|^2 sums), g.x and the step norms from the update kernel;
+// the trial block (cost, x^T H x, g.x, |step|^2, |x|^2, PCG iterations, capped / timed out, |r_0|^2) comes home in g->fin_vals
+int pg_trial_point(stba_pg* g) {
+    const int nxt = g->cur ^ 1;
+    hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->x, g->u, g->part_b,
+                       (const PcgState*)nullptr);
+    hipLaunchKernelGGL(pg_update4_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->poses[g->cur], g->x, g->g, g->fixed, g->poses[nxt], g->part_u);
+    STBA_TRY(pg_linearize(g, nxt, false));
+    g->seq += 1.0;
+    hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
+                       g->state, g->ar ? g->scal_dev : g->fin.dev, g->seq);
+    return pg_read_block(g, 2, 8);      // (several ranks: cost and |J x|^2 summed over the edge shards)
+}
+
+// forcing sequence (Eisenstat & Walker, choice 2) behind an accepted step: eta_{k+1} = 0.9 (|g_{k+1}| / |g_k|)^2 with their
+// safeguard, kept in [eta_min, eta0]; after a rejected step the gradient has not moved and eta stays
+double pg_next_eta(const stba_pcg_options& pcg, const stba_lm_options& opt, double eta, double g2, double g2_new, double cost_change,
+                   double new_cost) {
+    if (!(pcg.forcing_eta0 > 0.0 && g2 > 0.0 && std::isfinite(g2_new))) return eta;
+    double e2 = 0.9 * g2_new / g2;
+    if (0.9 * eta * eta > 0.1) e2 = std::max(e2, 0.9 * eta * eta);
+    eta = std::min(pcg.forcing_eta0, std::max(pcg.forcing_eta_min, e2));
+    // (round 6) about to converge -- the step just taken changed the cost by less than 100 x the function tolerance: the
+    // error of the LAST inexact step is what the converged poses keep (about eta x its length; on C4 the last step still
+    // moves poses by 3.6e-3, and Eisenstat & Walker leave eta ~ 1e-2 there: 4e-5 in the poses, north_star asks for 1e-5)
+    if (pcg.forcing_eta_final > 0.0 && cost_change <= 100.0 * opt.function_tolerance * (new_cost + cost_change))
+        eta = std::max(pcg.forcing_eta_min, std::min(eta, pcg.forcing_eta_final));
+    return eta;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1886,347 +2282,48 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
     stba_lm_summary s;
     memset(&s, 0, sizeof s);
     const double t0 = wall_s();
-    const int N = 6 * g->n;
-    STBA_TRY(pg_setup_coarse(g, pcg.coarse_group));
-    const bool coarse = g->agg > 0;
-    // the second stream of the coarse inverse (see the loop); a job of the previous solve may still be in flight: it is awaited here,
-    // where it costs nothing, instead of at the end of that solve, where it would have been the last 0.3 ms of its wall time
-    const bool async_inv = coarse && pcg.coarse_async != 0;
-    if (async_inv) {
-        STBA_TRY(pg_second_stream(g));
-        if (g->job_in_flight) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; }
-        g->job_reads_pending = false;
-    }
-    const bool build_on_st2 = async_inv && !g->ar;
-    if (coarse) STBA_HIP(hipMemsetAsync(g->cflag + 1, 0, sizeof(int), g->st));      // this solve's count of failed coarse operators
-    const bool multi = (g->ar != nullptr);
-    const int chunk = std::max(1, pcg.check_every);
-    const bool forcing = pcg.forcing_eta0 > 0.0;
-    stba_pcg_summary ps;
-    memset(&ps, 0, sizeof ps);
-    ps.coarse_dim = coarse ? g->nc : 0;
-    double* fin = g->fin_vals;          // (the validated copy of the mapped block g->fin)
-    // the PCG solve as one kernel: one rank, a coarse space whose groups fit a workgroup (<= 64 nodes, all their edge-end products
-    // in LDS) and are all resident at once (one per CU)
-    bool pp_ok = pcg.one_kernel_solve != 0 && !multi && coarse && g->agg <= 64 && g->na <= 256 && g->nc <= PP_NCMAX &&
-                 pp_lds_bytes(g->na, g->nc) <= (size_t)160 * 1024 - 64;
-    if (pp_ok) {
-        int dev = 0, cus = 0, lds_max = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g->na > cus) pp_ok = false;
-        // (the LDS a workgroup may opt in to is a property of the device and the driver: asked, not assumed -- advisor, round 5)
-        if (pp_ok && (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || pp_lds_bytes(g->na, g->nc) > (size_t)std::max(0, lds_max - 64))) pp_ok = false;
-        if (g->max_group_ends > PP_VCAP) pp_ok = false;
-    }
-    if (pp_ok) {
-        static DeviceOnce attr;
-        // a device that refuses the attribute takes the launch path; that is not a failed solve
-        if (attr.run([]() -> int {
-                STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_pcg_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-                return STBA_OK;
-            }) != STBA_OK) { pp_ok = false; g->pp_disabled = true; (void)hipGetLastError(); }
-    }
+    // ---- options and set-up
+    PgSolve sv(opt, pcg);
+    STBA_TRY(pg_solve_begin(g, sv));
+    stba_pcg_summary& ps = sv.ps;
+    TrustRegion& region = sv.region;
+    const double* fin = g->fin_vals;          // (the validated copy of the mapped block g->fin)
 
-    // ---- linearisation at the current point: residuals, Jacobians, gradient | diagonal blocks, the coarse basis and matrix
-    auto linearize_enqueue = [&]() -> int {
-        // (the job of the second stream reads the blocks, the coarse basis and the damping of the linearisation it belongs to: the next
-        // linearisation waits until it has -- an event that has long fired by then)
-        if (g->job_reads_pending) { STBA_TRY(pg_wait_if_pending(g->st, g->ev_read)); g->job_reads_pending = false; }
-        STBA_TRY(pg_linearize(g, g->cur, true));
-        hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->node_start, g->end_code, g->contrib, g->g, g->Hd);
-        if (g->ar && g->ar(g->ar_user, g->g, (size_t)g->n * 42, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-        hipLaunchKernelGGL(pg_gnorm_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, N, g->g, g->part_c);
-        if (coarse) {
-            hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->agg, g->poses[g->cur], g->fixed, g->AdP);
-            if (!g->bend_valid) {
-                hipLaunchKernelGGL(pg_offdiag_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->Ji, g->Jj, g->end_pos, g->Bend);
-                g->bend_valid = true;
-            }
-            // (one rank with the coarse inverse on its second stream: the coarse MATRIX is only read by that job, and is built there --
-            // 55 us of every LM iteration off the critical path; several ranks sum it with the hook, on the engine's stream)
-            if (!build_on_st2) {
-                hipLaunchKernelGGL(pg_coarse_build_kernel, dim3(g->na), dim3(256), (size_t)6 * g->nc * sizeof(double) + (size_t)4 * g->max_group_ends * sizeof(int), g->st, g->n, g->agg, g->nc,
-                                   (!g->ar || g->rank == 0) ? 1 : 0, g->node_start, g->end_node, g->end_rem, g->Bend, g->Hd, g->AdP, g->Ac0);
-                if (g->ar && g->ar(g->ar_user, g->Ac0, (size_t)g->nc * g->nc, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-            }
-            g->coarse_valid = false;
-            g->ac0_valid = false;
-        }
-        STBA_HIP(hipGetLastError());
-        return STBA_OK;
-    };
-    // cost and |g|_inf of that linearisation: one kernel sums, the host reads mapped memory (several ranks: the cost goes over the hook)
-    auto linearize_finish = [&](double* cost, double* gmax, double* g2) -> int {
-        g->seq += 1.0;
-        if (!multi) {
-            hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->fin.dev, g->seq);
-        } else {
-            hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->scal_dev, g->seq);
-            if (g->ar(g->ar_user, g->scal_dev, 1, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-            hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 3, g->scal_dev, g->fin.dev, g->seq);
-        }
-        STBA_HIP(hipGetLastError());
-        const double seq = g->seq;
-        STBA_TRY(stamped_wait(g->fin.host, 3, [seq](double st) { return st == seq; }, fin, hip_stream_state(g->st), "pose graph", 120.0));
-        *cost = 0.5 * fin[0]; *gmax = fin[1]; *g2 = fin[2];
-        return STBA_OK;
-    };
-
-    // the HEAD of the second stream's job (one rank): everything the inverse needs -- the coarse matrix from the blocks, the diagonal
-    // blocks and the basis of THIS linearisation, its damping term, the workspace; READ_k tells the first stream when its next
-    // linearisation / preconditioner kernel may overwrite those inputs.  Three launches: behind an accepted step they are enqueued
-    // at once (the preconditioner kernel in front of them), so that they run under the host's wait for the new point's scalars
-    // instead of at the start of the PCG kernel, with which the inversion then competes for CUs.
-    bool head_done = false;
-    auto job_head = [&]() -> int {
-        const size_t cnt = (size_t)3 * g->np * g->np;
-        STBA_HIP(hipStreamWaitEvent(g->st2, g->ev_in, 0));
-        if (!g->ac0_valid) {
-            hipLaunchKernelGGL(pg_coarse_build_kernel, dim3(g->na), dim3(256), (size_t)6 * g->nc * sizeof(double) + (size_t)4 * g->max_group_ends * sizeof(int), g->st2, g->n, g->agg, g->nc,
-                               1, g->node_start, g->end_node, g->end_rem, g->Bend, g->Hd, g->AdP, g->Ac0);
-            g->ac0_valid = true;
-        }
-        hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->na), dim3(256), 0, g->st2, g->n, g->agg, g->AdP, g->d, g->Dc);
-        hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g->st2, g->nc, g->np, g->Ac0, g->Dc, g->W);
-        STBA_HIP(hipEventRecord(g->ev_read, g->st2));
-        g->job_reads_pending = true;
-        g->job_in_flight = true;
-        return STBA_OK;
-    };
-
-    double cost = 0.0, gmax = 0.0, g2 = 0.0;
-    STBA_TRY(linearize_enqueue());
-    STBA_TRY(linearize_finish(&cost, &gmax, &g2));
-    s.initial_cost = cost;
-    TrustRegion region(opt);
-    bool scale_init = false;
-    int iter = 0;
-    double eta = pcg.forcing_eta0;
-    trace_start(trace, cost, gmax, region.radius);
+    // ---- first linearisation
+    STBA_TRY(pg_linearize_enqueue(g, sv));
+    STBA_TRY(pg_linearize_finish(g, &sv.cost, &sv.gmax, &sv.g2));
+    s.initial_cost = sv.cost;
+    trace_start(trace, sv.cost, sv.gmax, region.radius);
     s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
-    bool done = gmax <= opt.gradient_tolerance;
+    bool done = sv.gmax <= opt.gradient_tolerance;
     if (done) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; }
-    if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }   // (Ceres: initial evaluation failed, see stba_ba_solve)
-    int since_refresh = 0, jobs = 0;
-    double last_rel_decrease = 1.0;      // of the last accepted step: (cost before - cost after) / cost before
+    if (!std::isfinite(sv.cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }   // (Ceres: initial evaluation failed, see stba_ba_solve)
     while (!done) {
-        if (iter >= opt.max_num_iterations) break;
+        if (sv.iter >= opt.max_num_iterations) break;
         if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
-        ++iter;
-        const bool head_was_done = head_done;       // (behind an accepted step the preconditioner and the job's head are already on their way)
-        if (!head_done) {
-            if (g->job_reads_pending) { STBA_TRY(pg_wait_if_pending(g->st, g->ev_read)); g->job_reads_pending = false; }    // (a rejected step: no linearisation in between)
-            hipLaunchKernelGGL(pg_precond_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->Hd, g->scale, scale_init ? 0 : 1,
-                               opt.jacobi_scaling, region.radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
-            scale_init = true;
+        ++sv.iter;
+        // ---- preconditioner (behind an accepted step it and the job's head are already on their way)
+        const bool head_was_done = sv.head_done;
+        if (!sv.head_done) {
+            STBA_TRY(pg_wait_for_job_reads(g));      // (a rejected step: no linearisation in between)
+            pg_precond(g, sv);
         }
-        head_done = false;
-        // ---- coarse operator (P^T (J^T J + D) P)^-1
-        const double* Ainv_use = g->Ainv;
-        std::function<int()> job;
-        bool job_deferred = false;
-        if (coarse && async_inv) {
-            // ROUND 6: off the critical path.  The inversion (eight panels of a ~45 us chain on a handful of CUs: 0.39 of a 0.92 ms LM
-            // iteration at C4) runs on a SECOND stream, next to this iteration's PCG kernel (157 workgroups on 256 CUs), and is applied one LM
-            // iteration LATE: iteration k preconditions with the inverse of iteration k - 1's operator -- an inverse made at the
-            // previous linearisation / damping still is a preconditioner, only a weaker one (coarse_refresh_every = 2 had measured
-            // + 9 % PCG iterations).  The very first solve has no predecessor: it waits for its own inverse (coarse_async = 2 with a
-            // forcing sequence: it runs on block Jacobi alone, Ainv = 0 -- 3 PCG iterations at eta_0 = 0.1, but a first step that
-            // leaves the cost at 1021 where the two-level step leaves 258 and the exact one 48: the whole trajectory moves).
-            // Everything is ordered by events, so the result does not depend on timing: run to run the same bits.
-            //   stream 1: precond_k | wait job_{k-1} | record IN_k | PCG_k (Ainv of job_{k-1}) | trial | wait READ_k | linearise ...
-            //   stream 2:                              wait IN_k   | coarse matrix, Dc_k, assemble W_k | record READ_k | invert -> Ainv[k & 1] | record job_k
-            // (several ranks: coarse matrix -- summed by the hook --, Dc_k and W_k stay on stream 1, IN_k is recorded behind them)
-            const int wbuf = jobs & 1;
-            double* Aw = wbuf ? g->Ainv2 : g->Ainv;
-            const double* Ar = wbuf ? g->Ainv : g->Ainv2;        // written by the previous job (or zeroed below)
-            if (jobs == 0) STBA_HIP(hipMemsetAsync(const_cast<double*>(Ar), 0, (size_t)g->nc * g->nc * sizeof(double), g->st));
-            else STBA_TRY(pg_wait_if_pending(g->st, g->ev_job[(jobs - 1) & 1]));
-            // the first solve(s) wait for their own inverse (coarse_async = 2: not with a forcing sequence; coarse_async_after: how many
-            // LM iterations do -- the operator changes most in the first iterations)
-            // -- and every solve that follows a LONG step: the operator is stale by exactly the step that was just taken.  At C4
-            // (profiles/r6_c4_async.txt) the steps of the first three iterations take 98 %, 97 % and 45 % off the cost, the later ones
-            // 1 % and less; preconditioning iteration 3 with iteration 2's operator ends 3.9e-5 from the exact-step poses,
-            // iterations 4 .. 9 with their predecessors' 2.9e-6 (in line: 2.5e-6).  Rule: lag only behind a step that took at most
-            // coarse_async_decrease (0.5) off the cost.
-            // (also measured, profiles/r6_c4_async_coarse_tolerance_behind_long_steps.txt: not waiting behind a long step either and
-            // giving THAT solve a tolerance on the coarse residual instead -- 3e-4 is what the poses need (2.4e-6), and then the extra
-            // PCG iterations cost more than the wait: 1323 against 1411 LM it/s)
-            const bool long_step = iter <= pcg.coarse_async_after || last_rel_decrease > pcg.coarse_async_decrease;
-            const bool own = (jobs == 0 && (!forcing || pcg.coarse_async != 2)) || (pcg.coarse_async != 2 && long_step);
-            const size_t cnt = (size_t)3 * g->np * g->np;
-            if (!build_on_st2) {
-                hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->na), dim3(256), 0, g->st, g->n, g->agg, g->AdP, g->d, g->Dc);
-                hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g->st, g->nc, g->np, g->Ac0, g->Dc, g->W);
-            }
-            if (!head_was_done) STBA_HIP(hipEventRecord(g->ev_in, g->st));
-            // THE JOB: ~ 30 launches on the second stream.  Enqueueing them takes the HOST ~ 250 us -- so when this iteration does not
-            // wait for them (the usual case), the PCG kernel is launched FIRST and the job is enqueued while it runs: with the job in
-            // front, the kernel timeline showed the first stream idle for 277 us of every 760 us iteration, waiting for the host
-            // (profiles/r6_c4_iter_trace.txt)
-            job = [=, &job_head]() -> int {
-                if (!head_was_done) { if (build_on_st2) STBA_TRY(job_head()); else STBA_HIP(hipStreamWaitEvent(g->st2, g->ev_in, 0)); }
-                STBA_TRY(chol_spd_inverse_dev(g->W, 2 * g->np, g->np, g->nc, g->cflag, g->inv_work, g->st2));
-                hipLaunchKernelGGL(pg_coarse_finish_kernel, dim3((unsigned)(((size_t)g->nc * g->nc + 255) / 256)), dim3(256), 0, g->st2, g->nc, g->np, g->W, Aw,
-                                   g->cflag, g->cflag + 1);
-                STBA_HIP(hipEventRecord(g->ev_job[wbuf], g->st2));
-                g->job_in_flight = true;
-                return STBA_OK;
-            };
-            Ainv_use = Ar;
-            if (own) {
-                STBA_TRY(job());
-                STBA_HIP(hipStreamWaitEvent(g->st, g->ev_job[wbuf], 0));
-                Ainv_use = Aw;
-            } else job_deferred = true;
-            ++jobs;
-            g->coarse_valid = true;
-            ++ps.coarse_refreshes;
-        } else
-        // (synchronous form, coarse_async = 0) rebuilt when the linearisation or (every coarse_refresh_every-th time) the damping changed
-        // (the inverse is a preconditioner: one made at an earlier linearisation / damping still is one, only weaker -- with
-        // coarse_refresh_every = k it is re-made every k-th LM iteration; the first two iterations always make theirs)
-        if (coarse && (ps.coarse_refreshes < 2 || since_refresh >= std::max(1, pcg.coarse_refresh_every))) {
-            const size_t cnt = (size_t)3 * g->np * g->np;
-            hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->na), dim3(256), 0, g->st, g->n, g->agg, g->AdP, g->d, g->Dc);
-            hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g->st, g->nc, g->np, g->Ac0, g->Dc, g->W);
-            STBA_TRY(chol_spd_inverse_dev(g->W, 2 * g->np, g->np, g->nc, g->cflag, g->inv_work, g->st));
-            hipLaunchKernelGGL(pg_coarse_finish_kernel, dim3((unsigned)(((size_t)g->nc * g->nc + 255) / 256)), dim3(256), 0, g->st, g->nc, g->np, g->W, g->Ainv,
-                               g->cflag, g->cflag + 1);
-            g->coarse_valid = true;
-            since_refresh = 0;
-            ++ps.coarse_refreshes;
-        }
-        ++since_refresh;
-        // ---- PCG on (J^T J + D) x = -g, stopped on the device at |r| <= eta |g|
-        const double eta_k = forcing ? eta : pcg.relative_tolerance;
-        const double* AdP = coarse ? g->AdP : nullptr;
+        sv.head_done = false;
+        PgCoarseUse cu;
+        STBA_TRY(pg_coarse_refresh(g, sv, head_was_done, &cu));
+        // ---- PCG and trial point.  A deferred job goes BEHIND the launch of the one-kernel PCG, so that the host enqueues it while
+        // the kernel runs, but in FRONT of the launch path's, which talks to the host all along (pg_job_rest: the measured reason)
+        const double eta_k = sv.forcing ? sv.eta : pcg.relative_tolerance;
         const int nxt = g->cur ^ 1;
-        auto pcg_by_launches = [&]() -> int {
-            // (every kernel of the previous solve has finished -- the host has read the trial block behind them -- so the exported
-            // block can be taken back: the wait below must not see the previous solve's tick count and `done`)
-            g->exp.zero();
-            std::atomic_thread_fence(std::memory_order_seq_cst);
-            hipLaunchKernelGGL(pg_pcg_init4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, g->g, g->Minv, AdP, g->x, g->rr, g->z,
-                               g->rc_part, g->part_a);
-            if (coarse)
-                hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, (const PcgState*)nullptr, Ainv_use, g->rc_part,
-                                   g->zc, g->part_cz);
-            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
-                               g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
-            STBA_HIP(hipGetLastError());
-            int enq = 0;
-            bool pcg_done = false;
-            double px[PX_COUNT];
-            STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [](double st) { return st >= 1.0; }, px, hip_stream_state(g->st), "pose graph",
-                                  120.0));          // (also: the previous solve's ticks are gone)
-            if (px[PX_DONE] != 0.0) pcg_done = true;
-            while (!pcg_done && enq < pcg.max_iterations) {
-                const int todo = std::min(chunk, pcg.max_iterations - enq);
-                for (int c = 0; c < todo; ++c, ++enq) {
-                    const int slot = enq & 1;
-                    if (!multi) {
-                        hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u,
-                                           g->part_c, g->state);
-                        hipLaunchKernelGGL(pg_pcg_update4_kernel<true>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_edges,
-                                           g->part_c, g->nb_nodes4, g->part_d, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, (const double*)nullptr,
-                                           g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
-                    } else {
-                        STBA_TRY(pg_apply(g, g->p, g->q, true));
-                        hipLaunchKernelGGL(pg_dot_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, N, g->p, g->q, g->part_c);
-                        hipLaunchKernelGGL(pg_pcg_update4_kernel<false>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_vec,
-                                           g->part_c, 0, (const double*)nullptr, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, g->q,
-                                           g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
-                    }
-                    if (coarse)
-                        hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, g->state, Ainv_use, g->rc_part, g->zc,
-                                           g->part_cz);
-                    hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, slot, 0, eta_k, pcg.max_iterations, g->state,
-                                       g->exp.dev, g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
-                }
-                STBA_HIP(hipGetLastError());
-                // one rank: the host looks at the chunk BEFORE the one it has just enqueued (the stream never runs dry; the kernels of a
-                // chunk enqueued past convergence return at once).  Several ranks: every rank must enqueue the same collectives, so the
-                // decision waits for the chunk itself -- the solve state is replicated and every rank sees the same `done`.
-                const double want = 1 + (multi ? enq : enq - todo);
-                STBA_TRY(stamped_wait(g->exp.host, PX_COUNT, [want](double st) { return st >= want; }, px, hip_stream_state(g->st), "pose graph",
-                                      120.0));
-                if (px[PX_DONE] != 0.0) pcg_done = true;
-            }
-            return STBA_OK;
-        };
-        // the same solve as ONE kernel (see pg_pcg_persistent_kernel): nothing for the host to watch, the trial point follows on the stream
-        auto pcg_one_kernel = [&]() -> int {
-            if (!g->bend_valid) {
-                hipLaunchKernelGGL(pg_offdiag_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->Ji, g->Jj, g->end_pos, g->Bend);
-                g->bend_valid = true;
-            }
-            if (g->pp_base > (1 << 30)) {        // (stamps only grow; long before they wrap they are taken back to zero)
-                STBA_HIP(hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
-                STBA_HIP(hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
-                g->pp_base = 0;
-            }
-            PpArgs a;
-            a.n = g->n; a.agg = g->agg; a.log2agg = 0; while ((1 << a.log2agg) < g->agg) ++a.log2agg;
-            a.na = g->na; a.nc = g->nc; a.base = g->pp_base; a.max_iters = pcg.max_iterations; a.eta = eta_k;
-            a.node_start = g->node_start; a.end_rem = g->end_rem; a.Bend = g->Bend; a.Hd = g->Hd; a.d = g->d; a.Minv = g->Minv; a.AdP = g->AdP;
-            a.Ainv = Ainv_use; a.g = g->g; a.x = g->x; a.ubuf = g->ubuf; a.pbuf = g->pbuf; a.ustamp = g->ustamp; a.pstamp = g->pstamp;
-            a.state = g->state; a.spin_limit = pcg.one_kernel_solve == 2 ? 0 : 25000000ll;      // (a quarter of a second of wall_clock64 ticks; 2: the test of the way back)
-            a.fences = pcg.one_kernel_solve == 3 ? 1 : 0;
-            a.eta_c = forcing ? pcg.coarse_eta : 0.0;
-            a.tdbg = nullptr;
-#ifdef STBA_DEBUG_KNOBS
-            static long long* tdbg_dev = nullptr;
-            if (knob_int("STBA_PP_TIMING", 0)) {
-                if (!tdbg_dev) { STBA_HIP(hipMalloc(&tdbg_dev, 8 * sizeof(long long))); STBA_HIP(hipMemset(tdbg_dev, 0, 8 * sizeof(long long))); }
-                a.tdbg = tdbg_dev;
-            }
-#endif
-            hipLaunchKernelGGL(pg_pcg_persistent_kernel, dim3(g->na), dim3(PP_T), pp_lds_bytes(g->na, g->nc), g->st, a);
-#ifdef STBA_DEBUG_KNOBS
-            if (a.tdbg) {
-                long long h[8];
-                STBA_HIP(hipMemcpyAsync(h, tdbg_dev, sizeof h, hipMemcpyDeviceToHost, g->st)); STBA_HIP(hipStreamSynchronize(g->st));
-                fprintf(stderr, "pp phases (x 10 ns, cumulative): publish %lld | ends %lld | w+sum9 %lld | all-gather %lld | scalars+update %lld | coarse+u %lld | loop top %lld\n",
-                        h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-            }
-#endif
-            STBA_HIP(hipGetLastError());
-            g->pp_base += pcg.max_iterations + 8;
-            return STBA_OK;
-        };
-        auto trial_point = [&]() -> int {
-            // ---- model change, trial point: |J x|^2 from the edge kernel (its |t_e|^2 sums), g.x and the step norms from the update kernel
-            hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->x, g->u, g->part_b,
-                               (const PcgState*)nullptr);
-            hipLaunchKernelGGL(pg_update4_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->poses[g->cur], g->x, g->g, g->fixed, g->poses[nxt], g->part_u);
-            STBA_TRY(pg_linearize(g, nxt, false));
-            g->seq += 1.0;
-            if (!multi) {
-                hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
-                                   g->state, g->fin.dev, g->seq);
-            } else {
-                hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
-                                   g->state, g->scal_dev, g->seq);
-                if (g->ar(g->ar_user, g->scal_dev, 2, g->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");      // cost and |J x|^2 over the edge shards
-                hipLaunchKernelGGL(pg_export_kernel, dim3(1), dim3(64), 0, g->st, 8, g->scal_dev, g->fin.dev, g->seq);
-            }
-            STBA_HIP(hipGetLastError());
-            const double seq = g->seq;
-            STBA_TRY(stamped_wait(g->fin.host, 8, [seq](double st) { return st == seq; }, fin, hip_stream_state(g->st), "pose graph", 120.0));
-            return STBA_OK;
-        };
-        const bool one_kernel = pp_ok && !g->pp_disabled;
-        // (stba_lm_options::phase_timing: hipEvents around the linear solve -- the persistent kernel, or the launches of the PCG loop --
-        // for bench.py's roofline of the C4 line; an event is a packet of its own on the queue, so only on request)
-        const bool timing = opt.phase_timing != 0;
-        if (timing && !g->ev_t[0]) { STBA_HIP(hipEventCreate(&g->ev_t[0])); STBA_HIP(hipEventCreate(&g->ev_t[1])); }
-        if (timing) STBA_HIP(hipEventRecord(g->ev_t[0], g->st));
-        if (!one_kernel && job_deferred) { STBA_TRY(job()); job_deferred = false; }      // (the launch path talks to the host all along: the job goes first)
-        if (one_kernel) STBA_TRY(pcg_one_kernel()); else STBA_TRY(pcg_by_launches());
-        if (timing) STBA_HIP(hipEventRecord(g->ev_t[1], g->st));
-        if (job_deferred) { STBA_TRY(job()); job_deferred = false; }
-        STBA_TRY(trial_point());
-        if (timing) {
+        const bool one_kernel = sv.pp_ok && !g->pp_disabled;
+        if (sv.timing && !g->ev_t[0]) { STBA_HIP(hipEventCreate(&g->ev_t[0])); STBA_HIP(hipEventCreate(&g->ev_t[1])); }
+        if (sv.timing) STBA_HIP(hipEventRecord(g->ev_t[0], g->st));
+        if (!one_kernel && cu.job_deferred) { STBA_TRY(pg_job_rest(g, sv, cu.job)); cu.job_deferred = false; }
+        if (one_kernel) STBA_TRY(pg_pcg_one_kernel(g, sv, cu.Ainv, eta_k)); else STBA_TRY(pg_pcg_by_launches(g, sv, cu.Ainv, eta_k));
+        if (sv.timing) STBA_HIP(hipEventRecord(g->ev_t[1], g->st));
+        if (cu.job_deferred) { STBA_TRY(pg_job_rest(g, sv, cu.job)); cu.job_deferred = false; }
+        STBA_TRY(pg_trial_point(g));
+        if (sv.timing) {
             float ms = 0.f;
             STBA_HIP(hipEventSynchronize(g->ev_t[1]));
             STBA_HIP(hipEventElapsedTime(&ms, g->ev_t[0], g->ev_t[1]));
@@ -2237,9 +2334,10 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
             // a stamp never came: the workgroups were not all resident (another process on the device).  Once is enough: this
             // engine solves with launches from here on, starting with this very iteration.
             g->pp_disabled = true;
-            STBA_TRY(pcg_by_launches());
-            STBA_TRY(trial_point());
+            STBA_TRY(pg_pcg_by_launches(g, sv, cu.Ainv, eta_k));
+            STBA_TRY(pg_trial_point(g));
         }
+        // ---- verdict
         const double new_cost = 0.5 * fin[0], xhx = fin[1], gx = fin[2], step2 = fin[3], x2 = fin[4];
         const int k = (int)fin[5];
         const bool capped = fin[6] != 0.0;
@@ -2250,61 +2348,48 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
         const double model_change = -gx - 0.5 * xhx;
         const double step_norm = std::sqrt(step2), x_norm = std::sqrt(x2);
         ok = ok && model_change > 0.0 && std::isfinite(model_change) && std::isfinite(new_cost);
-        const StepVerdict v = judge_step(opt, cost, ok, new_cost, model_change, step_norm, x_norm);
-        trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
+        const StepVerdict v = judge_step(opt, sv.cost, ok, new_cost, model_change, step_norm, x_norm);
+        trace_step(trace, sv.iter, ok, sv.cost, new_cost, v, sv.gmax, step_norm, region.radius);
         if (v.stop) {        // (no progress line)
             s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
-            if (v.accepted) { g->cur = nxt; cost = new_cost; ++s.num_successful_steps; g->coarse_valid = false; }
+            if (v.accepted) { g->cur = nxt; sv.cost = new_cost; ++s.num_successful_steps; g->coarse_valid = false; }
             break;
         }
         if (v.accepted) {
             g->cur = nxt;
             ++s.num_successful_steps;
-            last_rel_decrease = cost > 0.0 ? v.cost_change / cost : 1.0;
+            sv.last_rel_decrease = sv.cost > 0.0 ? v.cost_change / sv.cost : 1.0;
             region.accept(v.rho, opt);
-            double c2, g2_new = 0.0;
-            STBA_TRY(linearize_enqueue());
-            if (async_inv && build_on_st2) {        // the next iteration's preconditioner kernel and the head of its job, at once (job_head)
-                hipLaunchKernelGGL(pg_precond_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->Hd, g->scale, scale_init ? 0 : 1,
-                                   opt.jacobi_scaling, region.radius, opt.min_lm_diagonal, opt.max_lm_diagonal, g->fixed, g->d, g->Minv);
-                scale_init = true;
+            double g2_new = 0.0;
+            STBA_TRY(pg_linearize_enqueue(g, sv));
+            if (sv.async_inv && sv.build_on_st2) {        // the next iteration's preconditioner kernel and the head of its job, at once (pg_job_head)
+                pg_precond(g, sv);
                 STBA_HIP(hipEventRecord(g->ev_in, g->st));
-                STBA_TRY(job_head());
-                head_done = true;
+                STBA_TRY(pg_job_head(g));
+                sv.head_done = true;
             }
-            STBA_TRY(linearize_finish(&c2, &gmax, &g2_new));
-            cost = c2;
-            // forcing sequence (Eisenstat & Walker, choice 2): eta_{k+1} = 0.9 (|g_{k+1}| / |g_k|)^2 with their safeguard, kept in
-            // [eta_min, eta0]; after a rejected step the gradient has not moved and eta stays
-            if (forcing && g2 > 0.0 && std::isfinite(g2_new)) {
-                double e2 = 0.9 * g2_new / g2;
-                if (0.9 * eta * eta > 0.1) e2 = std::max(e2, 0.9 * eta * eta);
-                eta = std::min(pcg.forcing_eta0, std::max(pcg.forcing_eta_min, e2));
-                // (round 6) about to converge -- the step just taken changed the cost by less than 100 x the function tolerance: the
-                // error of the LAST inexact step is what the converged poses keep (about eta x its length; on C4 the last step still
-                // moves poses by 3.6e-3, and Eisenstat & Walker leave eta ~ 1e-2 there: 4e-5 in the poses, north_star asks for 1e-5)
-                if (pcg.forcing_eta_final > 0.0 && v.cost_change <= 100.0 * opt.function_tolerance * (cost + v.cost_change))
-                    eta = std::max(pcg.forcing_eta_min, std::min(eta, pcg.forcing_eta_final));
-            }
-            g2 = g2_new;
-            if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
+            STBA_TRY(pg_linearize_finish(g, &sv.cost, &sv.gmax, &g2_new));
+            sv.eta = pg_next_eta(pcg, opt, sv.eta, sv.g2, g2_new, v.cost_change, sv.cost);
+            sv.g2 = g2_new;
+            if (trace) { trace[(size_t)sv.iter * STBA_TRACE_COLS + 2] = sv.gmax; trace[(size_t)sv.iter * STBA_TRACE_COLS + 5] = region.radius; }
             // (the gradient is tested here, before the progress line: none is printed for the converging iteration)
-            if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
+            if (sv.gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
         } else {
             ++s.num_unsuccessful_steps;
             region.reject();
-            if (trace) trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius;
+            if (trace) trace[(size_t)sv.iter * STBA_TRACE_COLS + 5] = region.radius;
         }
         if (opt.minimizer_progress_to_stdout) {
             char tail[64];
             snprintf(tail, sizeof tail, "  pcg %d eta %.1e%s", k, eta_k, capped ? " CAP" : "");
-            progress_step(iter, cost, v, gmax, step_norm, region.radius, tail);
+            progress_step(sv.iter, sv.cost, v, sv.gmax, step_norm, region.radius, tail);
         }
     }
-    finish_summary(&s, iter, cost, region.radius, gmax, t0);
+    // ---- summary
+    finish_summary(&s, sv.iter, sv.cost, region.radius, sv.gmax, t0);
     if (summary) *summary = s;
     if (pcg_iterations_total) *pcg_iterations_total = ps.iterations_total;
-    if (coarse) {        // (how many coarse operators could not be factored: counted on the device, read once per solve)
+    if (sv.coarse) {        // (how many coarse operators could not be factored: counted on the device, read once per solve)
         int cf = 0;
         if (hipMemcpyAsync(&cf, g->cflag + 1, sizeof(int), hipMemcpyDeviceToHost, g->st) == hipSuccess && hipStreamSynchronize(g->st) == hipSuccess)
             ps.coarse_failures = cf;

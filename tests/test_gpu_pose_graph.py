@@ -68,6 +68,106 @@ def test_pg_exact_steps_follow_the_dense_oracle(st, O, scenes, group):
     assert (ps.coarse_dim > 0) == (group >= 0)
 
 
+@pytest.fixture(scope="module")
+def small(O, scenes):
+    """the 150-node graph of the test above (19 groups of 8 nodes: both PCG paths and the coarse space are live) and the dense
+    oracle's solve of it, made once for the option cases below"""
+    s = scenes.pose_graph_scene(n_nodes=150, loops_per_node=3, seed=4, sigma_t=0.02, sigma_r=0.004, turns=6)
+    o = O.PG(s["poses0"], s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
+    so, tro = o.solve()
+    return s, so, tro, o.poses.copy()
+
+
+def small_engine(st, small):
+    s = small[0]
+    return st.PGEngine(s["poses0"], s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
+
+
+def follows_the_oracle(e, small, summ, tr):
+    """test_pg_exact_steps_follow_the_dense_oracle's own checks and tolerances"""
+    _, so, tro, poses_o = small
+    assert summ.termination_type == 0 and summ.num_iterations == so.num_iterations
+    n = min(len(tr), len(tro))
+    assert np.allclose(tr[:n, 0], tro[:n, 0], rtol=1e-7)
+    assert np.all(tr[:n, 6] == tro[:n, 6])
+    assert pose_diff(e.get_poses(), poses_o) < 1e-6
+    assert e.pcg_summary().hit_cap == 0
+
+
+@pytest.mark.parametrize("every", [2, 3])
+def test_pg_inline_coarse_inverse_refreshed_every_kth_iteration(st, small, every):
+    """coarse_async = 0 with coarse_refresh_every = k: the first two LM iterations make their inverse, then every k-th does; an older
+    inverse is a weaker preconditioner and must not change the answer"""
+    e = small_engine(st, small)
+    summ, tr, _ = e.solve(pcg=e.pcg_options(forcing_eta0=0.0, coarse_async=0, coarse_refresh_every=every))
+    follows_the_oracle(e, small, summ, tr)
+    n = summ.num_iterations
+    assert e.pcg_summary().coarse_refreshes == min(n, 2) + max(0, n - 2) // every
+
+
+def test_pg_one_kernel_solve_with_fences(st, small):
+    """one_kernel_solve = 3: the persistent kernel with its fences, every solve of the run"""
+    e = small_engine(st, small)
+    summ, tr, _ = e.solve(pcg=e.pcg_options(forcing_eta0=0.0, one_kernel_solve=3))
+    follows_the_oracle(e, small, summ, tr)
+    ps = e.pcg_summary()
+    assert ps.one_kernel_solves == ps.solves > 0
+
+
+def test_pg_phase_timing_leaves_the_arithmetic_alone(st, small):
+    """phase_timing = 1 puts events around the linear solve: a time comes back, and trace and poses keep their bits"""
+    res = []
+    for timing in (0, 1):
+        e = small_engine(st, small)
+        summ, tr, _ = e.solve(phase_timing=timing, pcg=e.pcg_options(forcing_eta0=0.0))
+        res.append((tr, e.get_poses(), e.pcg_summary().linear_solve_ms))
+    assert res[1][2] > 0
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+
+
+def test_pg_solves_on_one_engine_with_other_coarse_groups(st, O, small):
+    """a second and a third solve on one engine with another group size: the solve waits for the coarse job the last one left in
+    flight, and the coarse space's buffers are made again.  The oracle takes the same three solves: an LM that starts again (initial
+    radius) behind two iterations stops 4.2e-5 from where the uninterrupted solve stops, the oracle's as the engine's."""
+    s = small[0]
+    e = small_engine(st, small)
+    dims = []
+    poses_o = s["poses0"]
+    for kw, group in ((dict(max_num_iterations=2), 0), ({}, 16), ({}, -1)):
+        e.solve(pcg=e.pcg_options(forcing_eta0=0.0, coarse_group=group), **kw)
+        dims.append(e.pcg_summary().coarse_dim)
+        o = O.PG(poses_o, s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
+        o.solve(**kw)
+        poses_o = o.poses.copy()
+    assert pose_diff(e.get_poses(), poses_o) < 1e-6
+    assert dims[0] > 0 and dims[1] > 0 and dims[2] == 0
+
+
+@pytest.mark.parametrize("kw", [dict(coarse_async=2), dict(coarse_async=2, coarse_async_after=0, coarse_async_decrease=1.0)],
+                         ids=["mode2", "mode2-always-late"])
+def test_pg_late_coarse_inverse_with_exact_steps(st, small, kw):
+    """coarse_async = 2 without a forcing sequence (the first solve waits for its own inverse), and with every later inverse
+    applied one LM iteration late: exact steps do not depend on the preconditioner"""
+    e = small_engine(st, small)
+    summ, tr, _ = e.solve(pcg=e.pcg_options(forcing_eta0=0.0, **kw))
+    follows_the_oracle(e, small, summ, tr)
+
+
+def test_pg_forcing_eta_final_reaches_the_oracles_answer(st, O, scenes):
+    """the production forcing sequence with forcing_eta_final = 1e-3 (a tighter last step): the scene and the tolerances of
+    test_pg_inexact_steps_reach_the_oracles_answer"""
+    s = scenes.pose_graph_scene(n_nodes=300, loops_per_node=3, seed=11, sigma_t=0.02, sigma_r=0.004, turns=6)
+    e = st.PGEngine(s["poses0"], s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
+    o = O.PG(s["poses0"], s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
+    tight = dict(function_tolerance=1e-12, parameter_tolerance=1e-11)
+    summ, tr, pcg_total = e.solve(pcg=e.pcg_options(forcing_eta_final=1e-3), **tight)
+    so, tro, _, _ = o.solve_sparse(**tight)
+    assert summ.termination_type == 0 and so.termination_type == 0
+    assert abs(summ.final_cost - so.final_cost) <= 1e-6 * so.final_cost
+    assert pose_diff(e.get_poses(), o.poses) < 1e-5
+    assert e.pcg_summary().hit_cap == 0
+
+
 def test_pg_coarse_space_cuts_the_pcg_iterations(st, scenes):
     """the point of the two-level preconditioner: on a 3 000-node spiral the same exact-step solve needs several times fewer
     PCG iterations with the rigid-body coarse space than with block Jacobi alone"""

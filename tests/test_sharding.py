@@ -192,9 +192,12 @@ def test_two_shards_on_one_gpu(scenes, O, n_cams, n_pts, max_obs, sparse):
 
 
 @pytest.mark.gpu
-def test_pose_graph_two_edge_shards_on_one_gpu(scenes):
+@pytest.mark.parametrize("options", [{}, dict(coarse_async=0), dict(one_kernel_solve=0, coarse_group=-1)],
+                         ids=["defaults", "inline-coarse-inverse", "launches-no-coarse-space"])
+def test_pose_graph_two_edge_shards_on_one_gpu(scenes, options):
     """BASELINE C4 sharded: two engines hold half of the edges each (all nodes replicated); the hook sums
-    gradient | diagonal blocks, every PCG matrix-vector product and the costs.  Must follow the single engine."""
+    gradient | diagonal blocks, every PCG matrix-vector product and the costs.  Must follow the single engine --
+    with the default options, with the coarse inverse in line, and without a coarse space."""
     import torch
     st = importlib.import_module("slam-tricks_amd")
     sharding = importlib.import_module("slam-tricks_amd.sharding")
@@ -225,7 +228,7 @@ def test_pose_graph_two_edge_shards_on_one_gpu(scenes):
         e.set_allreduce(make_hook(rank), rank, world)
         # (exact LM steps, so that the traces can be compared digit for digit: with the production forcing sequence the
         # one-rank and the sharded PCG stop on different sides of the threshold now and then)
-        summ, tr, npcg = e.solve(max_num_iterations=6, pcg=e.pcg_options(forcing_eta0=0.0))
+        summ, tr, npcg = e.solve(max_num_iterations=6, pcg=e.pcg_options(forcing_eta0=0.0, **options))
         out[rank] = (summ, tr, npcg, e.get_poses())
 
     th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
@@ -235,7 +238,7 @@ def test_pose_graph_two_edge_shards_on_one_gpu(scenes):
         t.join(timeout=300)
     assert all(o is not None for o in out)
     e1 = st.PGEngine(s["poses0"], s["edge_i"], s["edge_j"], s["meas"], s["node_fixed"])
-    s1, tr1, n1 = e1.solve(max_num_iterations=6, pcg=e1.pcg_options(forcing_eta0=0.0))
+    s1, tr1, n1 = e1.solve(max_num_iterations=6, pcg=e1.pcg_options(forcing_eta0=0.0, **options))
     p1 = e1.get_poses()
     for rank in range(world):
         summ, tr, npcg, poses = out[rank]
