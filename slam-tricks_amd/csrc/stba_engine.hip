@@ -55,6 +55,12 @@ enum { SC_COST2 = 0, SC_GPMAX0 = 8, SC_MAX_WORLD = 64 };
 // iteration late -- outside the summed prefix, and equal on every rank (both come from the all-reduced extras).
 enum { TS_COST2 = 0, TS_STEP2 = 1, TS_X2 = 2, TS_MODEL = 3, TS_TIMEOUT = 4, TS_CAM = 5, TS_COUNT = 8,
        TS_SPEC_COST2 = 8, TS_LIN_COST2 = 9, TS_LIN_GMAX = 10, TS_BLOCK = 11 };
+// phase-timing events of a BA solve (stba_ba::ev; recorded only with stba_lm_options::phase_timing).  A pair is {X, X + 1}:
+// the linearisation and the build the loop reads in the same iteration; the ends of the solve, the back-substitution and the trial
+// evaluation; the two pairs the speculative linearisation alternates between; the build whose pair is read one solve later
+// (ba_step_events).  stba_ba_time_linearize / _schur / _schur_apply borrow the first pair.
+enum { EV_LIN = 0, EV_LIN_END, EV_BUILD, EV_BUILD_END, EV_SOLVE_END, EV_BACKSUB_END, EV_TRIAL_END,
+       EV_SPEC_A, EV_SPEC_A_END, EV_SPEC_B, EV_SPEC_B_END, EV_DBUILD, EV_DBUILD_END, EV_COUNT };
 
 }  // namespace stba
 
@@ -131,7 +137,7 @@ struct stba_ba {
     hipEvent_t ev_ar[2] = {};   // around the cross-rank sum of the reduced system (several ranks only)
     bool ar_timing_pending = false, ar_timing_on = false;
     double ar_ms = 0.0, ar_bytes = 0.0; int ar_calls = 0;   // accumulated over one LM run
-    hipEvent_t ev[15] = {};     // [12]: the trial block has reached the host; [13], [14]: second pair for the speculative linearisation
+    hipEvent_t ev[EV_COUNT] = {};   // phase timing of a solve (the EV_ enum)
     CovStore* cov = nullptr;    // the last stba_ba_covariance_compute (covariance.hip), until the next one, a release or destroy
     // ITERATIVE_SCHUR (stba_ba_create_ex; iterative_schur.hip): no S, no pair plan, no Y -- Sbuf holds only the extras tail.
     // PCG vectors x = dxc, r, z, p, q; one 6x6 preconditioner inverse per camera; the chunk partials of the Schur-Jacobi blocks;
@@ -741,145 +747,331 @@ static void inner_summary_reset(stba_ba* b) {
     }
 }
 
-static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterations, stba_lm_summary* sum,
-                     double* trace, stba_iteration_callback cb, void* cb_user) {
+// ---- the steps of a BA solve (ba_run_lm, ba_run_dogleg).  BaSolve is the state of ONE call; what outlives a call (the parameter
+// buffers and which is current, the Jacobi scale, the stage cool-down, the stamped blocks' sequence numbers, the events, the PCG,
+// dogleg and inner summaries) stays in stba_ba.  The two strategies share steps, not a loop: each keeps its trust region and its
+// own order of enqueues.  No step captures anything.
+struct BaPending {             // (cost, |g|max) of the linearisation behind iteration `iter`: they arrive with the next trial block
+    bool on = false, accepted = false;
+    int iter = 0, lin_ev = EV_SPEC_A;     // lin_ev: the event pair around that linearisation
+};
+struct BaSolve {
     stba_lm_options opt;
-    if (opt_in) opt = *opt_in; else default_options(&opt);
-    if (b->world > SC_MAX_WORLD) return fail(STBA_ERR_INVALID_ARGUMENT, "world size too large");
+    // derived once
+    bool fixed = false, timing = false;
+    bool deferred_ok = false;   // deferred read of (cost, |g|max) of a freshly linearised point: only when nobody watches the iterations
+    int max_iter = 0;
+    Damping dm;
     stba_lm_summary s;
-    memset(&s, 0, sizeof s);
-    const double t_start = wall_s();
-    const bool fixed = fixed_iterations > 0;
-    const int max_iter = fixed ? fixed_iterations : opt.max_num_iterations;
-    float ms = 0.f;
-    hipEvent_t* ev = b->ev;
-    const bool timing = opt.phase_timing != 0;       // (see stba_lm_options: every event costs ~5 us of idle GPU)
-    b->ar_timing_on = timing;
+    double t_start = 0.0;
+    // the loop
+    double cost = 0.0, gmax = 0.0;
+    int iter = 0, chol_timeouts = 0;
+    bool need_build = true;      // reduced system must be (re)built before the next solve
+    BaPending pending;
+    // phase timing: is the start point's linearisation pair still to be read, the speculation's pair of this iteration, and
+    // the end event of the last build (the start of the solve that follows it)
+    bool lin_timing_pending = true;
+    int spec_ev = EV_SPEC_B, build_end_ev = EV_BUILD_END;
+    double* trace = nullptr;
+    stba_iteration_callback cb = nullptr;
+    void* cb_user = nullptr;
+};
+struct TrialScalars { double new_cost = 0.0, step_norm = 0.0, x_norm = 0.0, model_change = 0.0; };
 
+static void stop(BaSolve& sv, int type, int reason) { sv.s.termination_type = type; sv.s.termination_reason = reason; }
+
+// (see stba_lm_options::phase_timing: every event costs ~5 us of idle GPU -- with timing off none is enqueued)
+static int ba_stamp(stba_ba* b, bool on, int ev) {
+    if (on) STBA_HIP(hipEventRecord(b->ev[ev], b->st));
+    return STBA_OK;
+}
+static void ba_add_ms(stba_ba* b, int ev_begin, int ev_end, double* total) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, b->ev[ev_begin], b->ev[ev_end]) == hipSuccess) *total += ms;
+}
+
+// options, summary, the per-solve resets of the engine, the damping's constants.  timed: the strategy has phase events at all
+static void ba_solve_begin(stba_ba* b, BaSolve& sv, const stba_lm_options* opt_in, int fixed_iterations, bool timed, double* trace,
+                           stba_iteration_callback cb, void* cb_user) {
+    if (opt_in) sv.opt = *opt_in; else default_options(&sv.opt);
+    memset(&sv.s, 0, sizeof sv.s);
+    stop(sv, STBA_NO_CONVERGENCE, STBA_TERM_MAX_ITER);
+    sv.t_start = wall_s();
+    sv.fixed = fixed_iterations > 0;
+    sv.max_iter = sv.fixed ? fixed_iterations : sv.opt.max_num_iterations;
+    sv.timing = timed && sv.opt.phase_timing != 0;
+    sv.deferred_ok = (cb == nullptr) && !sv.opt.minimizer_progress_to_stdout;
+    sv.trace = trace; sv.cb = cb; sv.cb_user = cb_user;
+    b->ar_timing_on = sv.timing;
     b->scale_init = false;
     b->ar_ms = 0.0; b->ar_bytes = 0.0; b->ar_calls = 0; b->ar_timing_pending = false;
     memset(&b->pcg_sum, 0, sizeof b->pcg_sum);
     b->pcg_per_iter.clear();
-    Damping dm;
-    dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
+    sv.dm.dmin = sv.opt.min_lm_diagonal; sv.dm.dmax = sv.opt.max_lm_diagonal; sv.dm.use_scaling = sv.opt.jacobi_scaling;
+}
+
+// linearisation at parameter buffer `which`: residuals + Jacobians, the landmark blocks, and the cost -> *cost_slot with the
+// scalar slots.  jac_done: a with_jac trial pass has made the residuals and Jacobians there already (the speculation).
+// timed: the pair ev_pair, ev_pair + 1 is recorded around everything but the scalar fill
+static int ba_linearize_point(stba_ba* b, int which, double* cost_slot, bool timed = false, int ev_pair = EV_LIN, bool jac_done = false) {
+    STBA_TRY(ba_stamp(b, timed, ev_pair));
+    if (!jac_done) STBA_TRY(ba_linearize_lm(b, which));
+    STBA_TRY(ba_normal_blocks(b));
+    STBA_TRY(ba_stamp(b, timed, ev_pair + 1));
+    return ba_fill_scalar_slots(b, cost_slot);
+}
+
+// the reduced system at `radius`, inside the event pair ev_pair when the solve is timed
+static int ba_build_at(stba_ba* b, BaSolve& sv, double radius, int ev_pair = EV_BUILD) {
+    sv.dm.radius = radius;
+    STBA_TRY(ba_stamp(b, sv.timing, ev_pair));
+    STBA_TRY(ba_build(b, sv.dm));
+    STBA_TRY(ba_stamp(b, sv.timing, ev_pair + 1));
+    sv.build_end_ev = ev_pair + 1;
+    sv.need_build = false;
+    return STBA_OK;
+}
+
+// the start point, behind its first build: cost and |g|max, row 0, the header.  *go = false: the solve ends here
+static int ba_first_point(stba_ba* b, BaSolve& sv, double radius, bool* go) {
+    *go = false;
+    STBA_TRY(ba_read_linear_scalars(b, &sv.cost, &sv.gmax));
+    sv.s.initial_cost = sv.cost;
+    trace_start(sv.trace, sv.cost, sv.gmax, radius);
+    if (sv.opt.minimizer_progress_to_stdout) progress_start(sv.cost, sv.gmax, radius);     // (the BA loops alone print a header)
+    // Ceres: a residual block that returns a non-finite value fails its evaluation, and a failed evaluation of the START
+    // point ends the solve as FAILURE before any step ("Initial residual and Jacobian evaluation failed"); at a trial
+    // point it is an unsuccessful step -- the rho test rejects a non-finite cost.  (oracle.c: orc_ba_solve)
+    if (!std::isfinite(sv.cost)) stop(sv, STBA_FAILURE, STBA_TERM_SOLVER_FAIL);
+    else if (!sv.fixed && sv.gmax <= sv.opt.gradient_tolerance) stop(sv, STBA_CONVERGENCE, STBA_TERM_GRADIENT);
+    else *go = sv.max_iter > 0;
+    return STBA_OK;
+}
+
+// the pending read: (cost, |g|max) of the linearisation behind iteration pending.iter have arrived.  true: that iteration had
+// converged on its gradient -- the test comes first, whatever the loop has done since
+static bool ba_take_pending(BaSolve& sv, double cost, double gmax) {
+    sv.gmax = gmax;
+    if (sv.pending.accepted) sv.cost = cost;
+    if (sv.trace) sv.trace[(size_t)sv.pending.iter * STBA_TRACE_COLS + 2] = gmax;
+    sv.pending.on = false;
+    return sv.pending.accepted && !sv.fixed && gmax <= sv.opt.gradient_tolerance;
+}
+// behind the loop (the stream is idle): the loop ended (iteration / radius limit) before the last linearisation's scalars were read
+static int ba_take_pending_at_end(stba_ba* b, BaSolve& sv) {
+    if (!sv.pending.on) return STBA_OK;
+    double c2, g2;
+    STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
+    if (ba_take_pending(sv, c2, g2) && (sv.s.termination_reason == STBA_TERM_MAX_ITER || sv.s.termination_reason == STBA_TERM_MIN_RADIUS))
+        stop(sv, STBA_CONVERGENCE, STBA_TERM_GRADIENT);
+    return STBA_OK;
+}
+
+static TrialScalars trial_scalars(const double* ts) {
+    return {0.5 * ts[TS_COST2], std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]), std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]), ts[TS_MODEL] + ts[TS_CAM + 2]};
+}
+
+// The persistent factorisation gave up waiting for a dependency: some of its workgroups were not resident (the
+// device is shared with another process).  S is half factored; it is rebuilt from the blocks -- the engine owns
+// them -- and this iteration runs again, the factorisation through the stage kernels, which need nothing
+// resident (chol_note_timeout: so do the next ones on this device).
+// relinearize: a speculative linearisation overwrote the current point's residuals, Jacobians and blocks
+static int ba_on_chol_timeout(stba_ba* b, BaSolve& sv, int flag_h, bool relinearize) {
+    // One rank: the DEVICE is marked (it is shared with somebody: the next 64 factorisations of anybody on it take the stage
+    // kernels).  Several ranks: every rank -- the one that gave up and its peers -- starts the same cool-down of ITS ENGINE, so
+    // that all of them factor the identical system with the identical schedule for the same 64 factorisations (the two
+    // schedules differ in the last bits, and every rank must hold the same camera blocks); a counter in the shared
+    // per-device state (round 5) was decremented by whoever else factored on that device (advisor, round 5).
+    if (b->ar) { b->stage_cooldown = 64; if (flag_h == CHOL_FLAG_TIMEOUT) chol_count_timeout(); }
+    else chol_note_timeout();
+    // (a device that keeps timing out is shared for good: the cool-down is renewed every time, so a long run goes on through
+    // the stage kernels instead of failing; only time-outs that come back-to-back without a good iteration in between --
+    // the stage kernels cannot time out -- end the solve)
+    if (++sv.chol_timeouts > 8) return fail(STBA_ERR_HIP, "dense Cholesky: the persistent program timed out repeatedly");
+    if (relinearize) STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2));
+    sv.need_build = true;
+    --sv.iter;
+    return STBA_OK;
+}
+
+static int ba_notify(const BaSolve& sv, const StepVerdict& v, double step_norm, double radius) {
+    return sv.cb ? sv.cb(sv.cb_user, sv.iter, sv.cost, v.cost_change, sv.gmax, step_norm, radius, v.accepted ? 1 : 0) : 0;
+}
+// a judged step: the accepted point becomes the current one; the iteration's trace row (its |g|max and radius follow, ba_end_iteration).
+// true: the step ended the solve on the parameter or the function tolerance (the callback hears of it; its answer no longer matters)
+static bool ba_apply_verdict(stba_ba* b, BaSolve& sv, const StepVerdict& v, bool step_ok, const TrialScalars& t, double radius) {
+    if (v.accepted) {
+        b->cur ^= 1;
+        sv.cost = t.new_cost;
+        ++sv.s.num_successful_steps;
+    }
+    trace_step(sv.trace, sv.iter, step_ok, sv.cost, t.new_cost, v, sv.gmax, t.step_norm, radius);
+    if (!v.stop) return false;
+    stop(sv, STBA_CONVERGENCE, v.stop);
+    (void)ba_notify(sv, v, t.step_norm, radius);
+    return true;
+}
+// the iteration's row is complete: |g|max and the new radius into it, the progress line, the callback.  true: the solve ends here
+static bool ba_end_iteration(BaSolve& sv, const StepVerdict& v, double step_norm, double radius) {
+    if (sv.trace) { sv.trace[(size_t)sv.iter * STBA_TRACE_COLS + 2] = sv.gmax; sv.trace[(size_t)sv.iter * STBA_TRACE_COLS + 5] = radius; }
+    if (sv.opt.minimizer_progress_to_stdout) progress_step(sv.iter, sv.cost, v, sv.gmax, step_norm, radius);
+    if (ba_notify(sv, v, step_norm, radius) != 0) { stop(sv, STBA_CONVERGENCE, STBA_TERM_USER); return true; }
+    if (!sv.pending.on && v.accepted && !sv.fixed && sv.gmax <= sv.opt.gradient_tolerance) {
+        stop(sv, STBA_CONVERGENCE, STBA_TERM_GRADIENT);
+        return true;
+    }
+    return false;
+}
+
+static int ba_solve_end(stba_ba* b, BaSolve& sv, double radius, stba_lm_summary* sum) {
+    STBA_HIP(hipStreamSynchronize(b->st));
+    STBA_TRY(ba_take_pending_at_end(b, sv));
+    ba_collect_allreduce_time(b);
+    sv.s.ms_allreduce = b->ar_ms; sv.s.allreduce_bytes = b->ar_bytes; sv.s.allreduce_calls = b->ar_calls;
+    finish_summary(&sv.s, sv.iter, sv.cost, radius, sv.gmax, sv.t_start);
+    b->pcg_sum.linear_solve_ms = b->iterative ? sv.s.ms_solve : 0.0;
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    if (sum) *sum = sv.s;
+    return STBA_OK;
+}
+
+// ---- ba_run_lm's own steps
+// factor + solve into dxc: the PCG (*pcg_fail: the step is not ok), or the dense Cholesky -- the persistent program, or the stage kernels
+static int ba_factor_solve(stba_ba* b, int* pcg_fail) {
+    if (b->iterative) return ba_pcg_solve(b, pcg_fail);
+    // (several ranks behind a time-out of ANY rank: this engine's own cool-down -- every rank counts the same factorisations
+    // through the stage kernels, whatever else shares its device or its process)
+    if (b->stage_cooldown > 0) { --b->stage_cooldown; return chol_factor_solve_stages(b->S(), b->lda, b->n, b->dxc, b->flag, b->st); }
+    return chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st);
+}
+
+// the sweep ran behind a valid step (its gate saw the same valid step): the candidate becomes x* (Ceres DoInnerIterationsIfNeeded),
+// isc = {cost2 at x*, |x - x*|^2}.  Returns whether the sweep brought the candidate below the current cost
+static bool ba_inner_verdict(stba_ba* b, const BaSolve& sv, const double* isc, TrialScalars& t, bool* inner_active) {
+    const double inner_cost = 0.5 * isc[0];
+    ++b->inner_sum.sweeps;
+    t.model_change += t.new_cost - inner_cost;
+    const double progress = 1.0 - inner_cost / t.new_cost;
+    t.new_cost = inner_cost;
+    t.step_norm = std::sqrt(isc[1]);
+    if (!(progress > b->inner_tol)) { *inner_active = false; b->inner_sum.disabled_at_iteration = sv.iter; }
+    return inner_cost < sv.cost;
+}
+
+// Which event pairs the linearisation and the build behind a judged step belong to.  Watched, the loop reads both at once: its
+// own pairs.  Deferred, the host reads them one solve later, with the next trial block: the build has a pair of its own, and the
+// linearisation's is the pair the speculation used LAST -- recorded by the speculation itself if the step it ran ahead of was
+// accepted, by the re-linearisation otherwise; the next iteration's speculation records into the other one, so the pair is
+// still intact when the host reads it.
+struct BaStepEvents { int lin, build; };
+static BaStepEvents ba_step_events(const BaSolve& sv) {
+    return sv.deferred_ok ? BaStepEvents{sv.spec_ev, EV_DBUILD} : BaStepEvents{EV_LIN, EV_BUILD};
+}
+
+// everything behind a judged step that has not ended the solve: the linearisation at the (new) current point -- unless the stream
+// has done so already --, the reduced system at the new radius, and the pending or immediate read of its cost and |g|max
+static int ba_advance(stba_ba* b, BaSolve& sv, double radius, bool accepted, bool speculated) {
+    sv.need_build = true;
+    if ((accepted || sv.fixed) && !(sv.fixed && sv.iter >= sv.max_iter)) {
+        const BaStepEvents e = ba_step_events(sv);
+        if (!(speculated && accepted)) STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2, sv.timing, e.lin));
+        // gradient of the new point is needed for the convergence test: it arrives with the
+        // next reduced-system build (one collective per iteration); build it now.
+        STBA_TRY(ba_build_at(b, sv, radius, e.build));
+        sv.lin_timing_pending = false;
+        if (sv.deferred_ok) {
+            // (cost, |g|max) of the new point arrive with the next iteration's trial block
+            sv.pending.on = true; sv.pending.accepted = accepted; sv.pending.iter = sv.iter; sv.pending.lin_ev = e.lin;
+        } else {
+            double c2, g2;
+            STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
+            if (sv.timing) { ba_add_ms(b, e.lin, e.lin + 1, &sv.s.ms_linearize); ba_add_ms(b, e.build, e.build + 1, &sv.s.ms_schur); }
+            sv.gmax = g2;
+            if (accepted) sv.cost = c2;   // same value as new_cost up to summation order
+        }
+    } else if (speculated && !accepted) {
+        // the speculative linearisation overwrote the residuals, Jacobians and blocks of the current point
+        STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2));
+    }
+    return STBA_OK;
+}
+
+static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterations, stba_lm_summary* sum,
+                     double* trace, stba_iteration_callback cb, void* cb_user) {
+    if (b->world > SC_MAX_WORLD) return fail(STBA_ERR_INVALID_ARGUMENT, "world size too large");
+    BaSolve sv;
+    ba_solve_begin(b, sv, opt_in, fixed_iterations, true, trace, cb, cb_user);
+    const stba_lm_options& opt = sv.opt;
+    stba_lm_summary& s = sv.s;
     TrustRegion region(opt);
-    double cost = 0.0, gmax = 0.0;
     // inner iterations: on while the engine has them and no sweep has switched them off (rule 6)
     bool inner_active = b->inner_on;
     if (b->inner_on) {
         inner_summary_reset(b);
-        if (timing) for (auto& e : b->inner_ev) if (!e) STBA_HIP(hipEventCreate(&e));
+        if (sv.timing) for (auto& e : b->inner_ev) if (!e) STBA_HIP(hipEventCreate(&e));
     }
+    static const bool SPECULATE = knob_int("STBA_LM_SPECULATE", 1) != 0;
 
     // ---- iteration 0: linearise at the start point
-    if (timing) STBA_HIP(hipEventRecord(ev[0], b->st));
-    STBA_TRY(ba_linearize_lm(b, b->cur));
-    STBA_TRY(ba_normal_blocks(b));
-    if (timing) STBA_HIP(hipEventRecord(ev[1], b->st));
-    STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-    bool need_build = true;      // reduced system must be (re)built before the next solve
-    bool lin_timing_pending = true;
-
-    static const bool SPECULATE = knob_int("STBA_LM_SPECULATE", 1) != 0;
-    // deferred read of (cost, |g|max) of a freshly linearised point: only when nobody watches the iterations
-    const bool deferred_ok = (cb == nullptr) && !opt.minimizer_progress_to_stdout;
-    bool pending = false, pending_accepted = false;
-    int pending_iter = 0, pending_lin_ev = 8, spec_ev = 13;
-
-    int iter = 0, chol_timeouts = 0, build_end_ev = 3;
-    s.termination_type = STBA_NO_CONVERGENCE;
-    s.termination_reason = STBA_TERM_MAX_ITER;
+    STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2, sv.timing, EV_LIN));
     bool first = true;
-    double x_norm = 0.0;
-
     while (true) {
         if (!first) {
-            if (iter >= max_iter) {
-                s.termination_type = fixed ? STBA_CONVERGENCE : STBA_NO_CONVERGENCE;
-                s.termination_reason = fixed ? STBA_TERM_FIXED : STBA_TERM_MAX_ITER;
+            if (sv.iter >= sv.max_iter) {
+                stop(sv, sv.fixed ? STBA_CONVERGENCE : STBA_NO_CONVERGENCE, sv.fixed ? STBA_TERM_FIXED : STBA_TERM_MAX_ITER);
                 break;
             }
-            if (!fixed && region.below_min(opt)) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS;
-                break;
-            }
+            if (!sv.fixed && region.below_min(opt)) { stop(sv, STBA_CONVERGENCE, STBA_TERM_MIN_RADIUS); break; }
         }
         // ---- reduced system for the current radius
         // (an event record is a packet of its own on the queue, ~5 us of idle GPU between two kernels: none is recorded that
         // is not needed -- when the system was built behind the previous iteration, that build's end event is the start of
         // this solve)
-        dm.radius = region.radius;
-        const bool built_here = need_build;
-        if (need_build) {
-            if (timing) STBA_HIP(hipEventRecord(ev[2], b->st));
-            STBA_TRY(ba_build(b, dm));
-            if (timing) STBA_HIP(hipEventRecord(ev[3], b->st));
-            build_end_ev = 3;
-        }
-        const int solve_start_ev = build_end_ev;
+        const bool built_here = sv.need_build;
+        if (sv.need_build) STBA_TRY(ba_build_at(b, sv, region.radius));
+        const int solve_start_ev = sv.build_end_ev;
         if (first) {
-            STBA_TRY(ba_read_linear_scalars(b, &cost, &gmax));
-            s.initial_cost = cost;
-            trace_start(trace, cost, gmax, region.radius);
+            bool go = false;
             first = false;
-            if (opt.minimizer_progress_to_stdout) progress_start(cost, gmax, region.radius);     // (the only loop with a header)
-            // Ceres: a residual block that returns a non-finite value fails its evaluation, and a failed evaluation of the START
-            // point ends the solve as FAILURE before any step ("Initial residual and Jacobian evaluation failed"); at a trial
-            // point it is an unsuccessful step -- the rho test rejects a non-finite cost.  (oracle.c: orc_ba_solve)
-            if (!std::isfinite(cost)) {
-                s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL;
-                break;
-            }
-            if (!fixed && gmax <= opt.gradient_tolerance) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
-                break;
-            }
-            if (max_iter <= 0) break;
+            STBA_TRY(ba_first_point(b, sv, region.radius, &go));
+            if (!go) break;
         }
-        ++iter;
+        ++sv.iter;
         // ---- factor + solve, back-substitute, trial point
         int flag_h = 0, pcg_fail = 0;
-        // (several ranks behind a time-out of ANY rank: this engine's own cool-down -- every rank counts the same factorisations
-        // through the stage kernels, whatever else shares its device or its process)
-        if (b->iterative) STBA_TRY(ba_pcg_solve(b, &pcg_fail));
-        else if (b->stage_cooldown > 0) { --b->stage_cooldown; STBA_TRY(chol_factor_solve_stages(b->S(), b->lda, b->n, b->dxc, b->flag, b->st)); }
-        else STBA_TRY(chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st));
-        if (timing) STBA_HIP(hipEventRecord(ev[4], b->st));
+        STBA_TRY(ba_factor_solve(b, &pcg_fail));
+        STBA_TRY(ba_stamp(b, sv.timing, EV_SOLVE_END));
         STBA_TRY(ba_backsub_trial(b));
-        if (timing) STBA_HIP(hipEventRecord(ev[5], b->st));
+        STBA_TRY(ba_stamp(b, sv.timing, EV_BACKSUB_END));
         // Nobody watches the iterations and there is one rank: the host learns the trial point's scalars through a stamped
         // block in mapped memory, and meanwhile the stream already linearises AT THE TRIAL POINT -- a step is accepted far
         // more often than not, and the host's round trip (wake-up, decision, enqueue: ~35 us) would otherwise be a
-        // bubble on the GPU in every iteration.  A rejected step costs one linearisation at the old point (below).
+        // bubble on the GPU in every iteration.  A rejected step costs one linearisation at the old point (ba_advance).
         // (With several ranks too: every rank takes the same decision from the same all-reduced block, and the collectives of
         // the speculative build are enqueued on the stream like everything else.)
         // (host-linearised factors: the callback is synchronous host work; iterative Schur: the PCG hands its state to the host
         // anyway, and this path does not speculate -- DESIGN.md 7b)
         // (inner iterations: the sweep moves the trial point before anything is linearised there -- no speculation)
-        const bool fast = deferred_ok && SPECULATE && !b->hl_fn && !b->iterative && !inner_active;
+        const bool fast = sv.deferred_ok && SPECULATE && !b->hl_fn && !b->iterative && !inner_active;
         if (fast && !b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
         // (the speculative linearisation IS the evaluation of the trial point: one pass over the observations, not two)
-        const bool speculate = fast && !(fixed && iter >= max_iter);
+        const bool speculate = fast && !(sv.fixed && sv.iter >= sv.max_iter);
         const double seq = fast ? (b->ts_seq += 1.0) : 0.0;
         STBA_TRY(ba_trial(b, fast ? b->ts_host.dev : nullptr, true, speculate, seq));
-        if (timing) STBA_HIP(hipEventRecord(ev[6], b->st));
+        STBA_TRY(ba_stamp(b, sv.timing, EV_TRIAL_END));
         double isc[2] = {0.0, 0.0};
         if (inner_active) {
-            if (timing) STBA_HIP(hipEventRecord(b->inner_ev[0], b->st));
+            if (sv.timing) STBA_HIP(hipEventRecord(b->inner_ev[0], b->st));
             STBA_TRY(ba_inner_after_trial(b));
-            if (timing) STBA_HIP(hipEventRecord(b->inner_ev[1], b->st));
+            if (sv.timing) STBA_HIP(hipEventRecord(b->inner_ev[1], b->st));
         }
         const double* ts = b->ts_vals;
-        bool speculated = false;
         if (fast) {
             if (speculate) {
-                // (its own pair of events, alternating: the previous linearisation's pair is read behind the synchronisation below)
-                spec_ev = (spec_ev == 8) ? 13 : 8;
-                if (timing) STBA_HIP(hipEventRecord(ev[spec_ev], b->st));
-                STBA_TRY(ba_normal_blocks(b));
-                if (timing) STBA_HIP(hipEventRecord(ev[spec_ev + 1], b->st));
-                STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_SPEC_COST2));
-                speculated = true;
+                // (its own pair of events, alternating: the previous linearisation's pair is read behind the wait below)
+                sv.spec_ev = (sv.spec_ev == EV_SPEC_A) ? EV_SPEC_B : EV_SPEC_A;
+                STBA_TRY(ba_linearize_point(b, b->cur ^ 1, b->trial + TS_SPEC_COST2, sv.timing, sv.spec_ev, true));
             }
             // (a polled stamped block, no event: a record between two kernels costs the GPU ~5 us, and the stream goes straight on)
             STBA_TRY(stamped_wait(b->ts_host.host, TS_BLOCK, [seq](double st) { return st == seq; }, b->ts_vals, hip_stream_state(b->st),
@@ -890,180 +1082,60 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
             STBA_TRY(download(&flag_h, b->flag, 1, b->st));
             if (inner_active) STBA_TRY(download(isc, b->inner_sc, 2, b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
-            if (inner_active && timing && hipEventElapsedTime(&ms, b->inner_ev[0], b->inner_ev[1]) == hipSuccess) b->inner_sum.sweep_ms += ms;
+            if (inner_active && sv.timing) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, b->inner_ev[0], b->inner_ev[1]) == hipSuccess) b->inner_sum.sweep_ms += ms;
+            }
         }
         if (pcg_fail) flag_h = 1;            // (the PCG failed: the step is not ok)
-        if (pending) {
+        if (sv.pending.on) {
             // (cost2 and |g|max of the build behind the previous iteration: trial_finish_kernel read them on the way)
-            const double c2 = 0.5 * ts[TS_LIN_COST2], g2 = ts[TS_LIN_GMAX];
-            if (timing && hipEventElapsedTime(&ms, ev[pending_lin_ev], ev[pending_lin_ev + 1]) == hipSuccess) s.ms_linearize += ms;
-            if (timing && hipEventElapsedTime(&ms, ev[10], ev[11]) == hipSuccess) s.ms_schur += ms;
-            gmax = g2;
-            if (pending_accepted) cost = c2;
-            if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
-            pending = false;
-            if (pending_accepted && !fixed && g2 <= opt.gradient_tolerance) {
+            if (sv.timing) {
+                ba_add_ms(b, sv.pending.lin_ev, sv.pending.lin_ev + 1, &s.ms_linearize);
+                ba_add_ms(b, EV_DBUILD, EV_DBUILD_END, &s.ms_schur);
+            }
+            if (ba_take_pending(sv, 0.5 * ts[TS_LIN_COST2], ts[TS_LIN_GMAX])) {
                 // converged at the previous iteration: the trial step just computed is discarded
-                --iter;
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
+                --sv.iter;
+                stop(sv, STBA_CONVERGENCE, STBA_TERM_GRADIENT);
                 break;
             }
         }
-        if (b->iterative) ba_pcg_account(b, iter);
+        if (b->iterative) ba_pcg_account(b, sv.iter);
         // (several ranks: the decision is COLLECTIVE -- ts[TS_TIMEOUT] is the all-reduced count of ranks whose factorisation timed
         // out, the same number on every rank.  A rank-local decision would leave one rank re-running the iteration, with its
         // all-reduces of a system linearised at the old point, while the others move on: mismatched collectives.)
         if (flag_h == CHOL_FLAG_TIMEOUT || ts[TS_TIMEOUT] > 0.0) {
-            // The persistent factorisation gave up waiting for a dependency: some of its workgroups were not resident (the
-            // device is shared with another process).  S is half factored; it is rebuilt from the blocks -- the engine owns
-            // them -- and this iteration runs again, the factorisation through the stage kernels, which need nothing
-            // resident (chol_note_timeout: so do the next ones on this device).
-            // One rank: the DEVICE is marked (it is shared with somebody: the next 64 factorisations of anybody on it take the stage
-            // kernels).  Several ranks: every rank -- the one that gave up and its peers -- starts the same cool-down of ITS ENGINE, so
-            // that all of them factor the identical system with the identical schedule for the same 64 factorisations (the two
-            // schedules differ in the last bits, and every rank must hold the same camera blocks); a counter in the shared
-            // per-device state (round 5) was decremented by whoever else factored on that device (advisor, round 5).
-            if (b->ar) { b->stage_cooldown = 64; if (flag_h == CHOL_FLAG_TIMEOUT) chol_count_timeout(); }
-            else chol_note_timeout();
-            // (a device that keeps timing out is shared for good: the cool-down is renewed every time, so a long run goes on through
-            // the stage kernels instead of failing; only time-outs that come back-to-back without a good iteration in between --
-            // the stage kernels cannot time out -- end the solve)
-            if (++chol_timeouts > 8) return fail(STBA_ERR_HIP, "dense Cholesky: the persistent program timed out repeatedly");
-            if (speculated) {       // (the speculative linearisation overwrote the current point's residuals, Jacobians and blocks)
-                STBA_TRY(ba_linearize_lm(b, b->cur));
-                STBA_TRY(ba_normal_blocks(b));
-                STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-            }
-            need_build = true;
-            --iter;
+            STBA_TRY(ba_on_chol_timeout(b, sv, flag_h, speculate));
             continue;
         }
-        if (timing) {
-            if (lin_timing_pending) { (void)hipEventElapsedTime(&ms, ev[0], ev[1]); s.ms_linearize += ms; }
-            if (built_here) { (void)hipEventElapsedTime(&ms, ev[2], ev[3]); s.ms_schur += ms; }
-            (void)hipEventElapsedTime(&ms, ev[solve_start_ev], ev[4]); s.ms_solve += ms;
-            (void)hipEventElapsedTime(&ms, ev[4], ev[5]); s.ms_backsub += ms;
-            (void)hipEventElapsedTime(&ms, ev[5], ev[6]); s.ms_cost += ms;
+        if (sv.timing) {
+            if (sv.lin_timing_pending) ba_add_ms(b, EV_LIN, EV_LIN_END, &s.ms_linearize);
+            if (built_here) ba_add_ms(b, EV_BUILD, EV_BUILD_END, &s.ms_schur);
+            ba_add_ms(b, solve_start_ev, EV_SOLVE_END, &s.ms_solve);
+            ba_add_ms(b, EV_SOLVE_END, EV_BACKSUB_END, &s.ms_backsub);
+            // (a polled trial block can reach the host before the event recorded behind its kernel has fired: wait for that one)
+            if (fast) (void)hipEventSynchronize(b->ev[EV_TRIAL_END]);
+            ba_add_ms(b, EV_BACKSUB_END, EV_TRIAL_END, &s.ms_cost);
         }
-        lin_timing_pending = false;
-        chol_timeouts = 0;
+        sv.lin_timing_pending = false;
+        sv.chol_timeouts = 0;
 
-        bool step_ok = (flag_h == 0);
-        double new_cost = 0.5 * ts[TS_COST2];
-        double step_norm = std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]);
-        x_norm = std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]);
-        double model_change = ts[TS_MODEL] + ts[TS_CAM + 2];
+        TrialScalars t = trial_scalars(ts);
         // (a non-finite trial cost makes the step not ok: row [cost, 0, ., 0, 0], no stop test)
-        if (step_ok && (!(model_change > 0.0) || !std::isfinite(model_change) || !std::isfinite(new_cost)))
-            step_ok = false;
-        bool inner_useful = false;
-        if (inner_active && step_ok) {
-            // the sweep ran (its gate saw the same valid step): the candidate becomes x* (Ceres DoInnerIterationsIfNeeded)
-            const double inner_cost = 0.5 * isc[0];
-            ++b->inner_sum.sweeps;
-            model_change += new_cost - inner_cost;
-            inner_useful = inner_cost < cost;
-            const double progress = 1.0 - inner_cost / new_cost;
-            new_cost = inner_cost;
-            step_norm = std::sqrt(isc[1]);
-            if (!(progress > b->inner_tol)) { inner_active = false; b->inner_sum.disabled_at_iteration = iter; }
-        }
-        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, !fixed, inner_useful);
-        const bool accepted = v.accepted;
-        if (accepted) {
-            b->cur ^= 1;
-            cost = new_cost;
-            ++s.num_successful_steps;
-        }
-        trace_step(trace, iter, step_ok, cost, new_cost, v, gmax, step_norm, region.radius);
-        if (v.stop) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
-            if (accepted) b->have_lin = b->have_blocks = false;
-            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0);
-            break;
-        }
-        if (accepted) region.accept(v.rho, opt);
+        const bool step_ok = flag_h == 0 && t.model_change > 0.0 && std::isfinite(t.model_change) && std::isfinite(t.new_cost);
+        const bool inner_useful = inner_active && step_ok && ba_inner_verdict(b, sv, isc, t, &inner_active);
+        const StepVerdict v = judge_step(opt, sv.cost, step_ok, t.new_cost, t.model_change, t.step_norm, t.x_norm, !sv.fixed, inner_useful);
+        if (ba_apply_verdict(b, sv, v, step_ok, t, region.radius)) break;
+        if (v.accepted) region.accept(v.rho, opt);
         else {
             ++s.num_unsuccessful_steps;
             region.reject();
         }
-        need_build = true;
-        if ((accepted || fixed) && !(fixed && iter >= max_iter)) {
-            // re-linearise at the (new) current point -- unless the stream has done so already
-            // (event pair of a non-speculated re-linearisation: the pair the speculation used LAST -- the next iteration's
-            // speculation records into the other one, so the pair is still intact when the host reads it one solve later)
-            const int e0 = deferred_ok ? spec_ev : 0, e2 = deferred_ok ? 10 : 2;
-            if (!(speculated && accepted)) {
-                if (timing) STBA_HIP(hipEventRecord(ev[e0], b->st));
-                STBA_TRY(ba_linearize_lm(b, b->cur));
-                STBA_TRY(ba_normal_blocks(b));
-                if (timing) STBA_HIP(hipEventRecord(ev[e0 + 1], b->st));
-                STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-            }
-            // gradient of the new point is needed for the convergence test: it arrives with the
-            // next reduced-system build (one collective per iteration); build it now.
-            dm.radius = region.radius;
-            if (timing) STBA_HIP(hipEventRecord(ev[e2], b->st));
-            STBA_TRY(ba_build(b, dm));
-            if (timing) STBA_HIP(hipEventRecord(ev[e2 + 1], b->st));
-            build_end_ev = e2 + 1;
-            need_build = false;
-            lin_timing_pending = false;
-            if (deferred_ok) {
-                // (cost, |g|max) of the new point arrive with the next iteration's trial block
-                pending = true; pending_accepted = accepted; pending_iter = iter;
-                pending_lin_ev = spec_ev;
-                if (accepted) cost = new_cost;
-            } else {
-                double c2, g2;
-                STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
-                if (timing) {
-                    (void)hipEventElapsedTime(&ms, ev[0], ev[1]); s.ms_linearize += ms;
-                    (void)hipEventElapsedTime(&ms, ev[2], ev[3]); s.ms_schur += ms;
-                }
-                gmax = g2;
-                if (accepted) cost = c2;   // same value as new_cost up to summation order
-            }
-        }
-        else if (speculated && !accepted) {
-            // the speculative linearisation overwrote the residuals, Jacobians and blocks of the current point
-            STBA_TRY(ba_linearize_lm(b, b->cur));
-            STBA_TRY(ba_normal_blocks(b));
-            STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-        }
-        if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
-        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
-        if (cb) {
-            if (cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0) != 0) {
-                s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER;
-                break;
-            }
-        }
-        if (!pending && accepted && !fixed && gmax <= opt.gradient_tolerance) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
-            break;
-        }
+        STBA_TRY(ba_advance(b, sv, region.radius, v.accepted, speculate));
+        if (ba_end_iteration(sv, v, t.step_norm, region.radius)) break;
     }
-    STBA_HIP(hipStreamSynchronize(b->st));
-    if (pending) {      // the loop ended (iteration / radius limit) before the last linearisation's scalars were read
-        double c2, g2;
-        STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
-        gmax = g2;
-        if (pending_accepted) cost = c2;
-        if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
-        if (pending_accepted && !fixed && g2 <= opt.gradient_tolerance &&
-            (s.termination_reason == STBA_TERM_MAX_ITER || s.termination_reason == STBA_TERM_MIN_RADIUS)) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;   // the test comes first
-        }
-        pending = false;
-    }
-    ba_collect_allreduce_time(b);
-    s.ms_allreduce = b->ar_ms; s.allreduce_bytes = b->ar_bytes; s.allreduce_calls = b->ar_calls;
-    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
-    b->pcg_sum.linear_solve_ms = b->iterative ? s.ms_solve : 0.0;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    if (sum) *sum = s;
-    return STBA_OK;
+    return ba_solve_end(b, sv, region.radius, sum);
 }
 
 // ---- DOGLEG (Ceres' TrustRegionMinimizer + DoglegStrategy, TRADITIONAL_DOGLEG).  One rank, the dense Schur path.
@@ -1114,66 +1186,43 @@ constexpr int kMaxConsecutiveInvalidSteps = 5;      // Ceres' Solver::Options::m
 
 static int ba_run_dogleg(stba_ba* b, const stba_lm_options* opt_in, stba_lm_summary* sum, double* trace, stba_iteration_callback cb,
                          void* cb_user) {
-    stba_lm_options opt;
-    if (opt_in) opt = *opt_in; else default_options(&opt);
-    stba_lm_summary s;
-    memset(&s, 0, sizeof s);
-    const double t_start = wall_s();
-    const int max_iter = opt.max_num_iterations;
     STBA_TRY(ba_dogleg_alloc(b));
     if (!b->ts_host.host) STBA_TRY(b->ts_host.alloc((size_t)stamped_doubles(TS_BLOCK)));
-    b->scale_init = false;
-    b->ar_ms = 0.0; b->ar_bytes = 0.0; b->ar_calls = 0; b->ar_timing_pending = false; b->ar_timing_on = false;
-    memset(&b->pcg_sum, 0, sizeof b->pcg_sum);
-    b->pcg_per_iter.clear();
+    BaSolve sv;
+    ba_solve_begin(b, sv, opt_in, 0, false, trace, cb, cb_user);
+    const stba_lm_options& opt = sv.opt;
+    stba_lm_summary& s = sv.s;
     stba_dogleg_summary ds{};
     ds.struct_size = sizeof ds;
-    Damping dm;
-    dm.dmin = opt.min_lm_diagonal; dm.dmax = opt.max_lm_diagonal; dm.use_scaling = opt.jacobi_scaling;
     DoglegRegion region(opt);
-    double cost = 0.0, gmax = 0.0;
 
-    STBA_TRY(ba_linearize_lm(b, b->cur));
-    STBA_TRY(ba_normal_blocks(b));
-    STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-    const bool deferred_ok = (cb == nullptr) && !opt.minimizer_progress_to_stdout;
-    bool need_build = true, need_gn = true, first = true, pending = false, pending_accepted = false;
-    int pending_iter = 0, iter = 0, chol_timeouts = 0, invalid_in_a_row = 0;
-    s.termination_type = STBA_NO_CONVERGENCE;
-    s.termination_reason = STBA_TERM_MAX_ITER;
+    STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2));
+    bool need_gn = true, first = true;
+    int invalid_in_a_row = 0;
     double hd[DL_BLOCK] = {0.0};
 
     while (true) {
         if (!first) {
-            if (iter >= max_iter) break;
-            if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
+            if (sv.iter >= sv.max_iter) break;
+            if (region.below_min(opt)) { stop(sv, STBA_CONVERGENCE, STBA_TERM_MIN_RADIUS); break; }
         }
-        if (need_build) {
-            dm.radius = 1.0 / region.mu;
-            STBA_TRY(ba_build(b, dm));
-            need_build = false;
-        }
+        if (sv.need_build) STBA_TRY(ba_build_at(b, sv, 1.0 / region.mu));
         if (first) {
-            STBA_TRY(ba_read_linear_scalars(b, &cost, &gmax));
-            s.initial_cost = cost;
-            trace_start(trace, cost, gmax, region.radius);
+            bool go = false;
             first = false;
-            if (opt.minimizer_progress_to_stdout) progress_start(cost, gmax, region.radius);
-            if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; break; }
-            if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
-            if (max_iter <= 0) break;
+            STBA_TRY(ba_first_point(b, sv, region.radius, &go));
+            if (!go) break;
         }
-        ++iter;
+        ++sv.iter;
         // ---- the Gauss-Newton side, once per linearisation (and per mu escalation); mu >= 1: no solve, the step is invalid
         bool have_gn = true, reused = !need_gn;
         if (need_gn) {
             if (region.can_factor()) {
-                STBA_TRY(ba_dogleg_gauss_newton(b, dm));
+                STBA_TRY(ba_dogleg_gauss_newton(b, sv.dm));
                 ++ds.factorizations; ++ds.gauss_newton_solves;
                 need_gn = false;
             } else have_gn = false;
         }
-        int flag_h = 0;
         const double* ts = b->ts_vals;
         if (have_gn) {
             // ---- the trial step: the step kernel at Delta and the trial evaluation, read through the trial block (the one wait)
@@ -1185,121 +1234,70 @@ static int ba_run_dogleg(stba_ba* b, const stba_lm_options* opt_in, stba_lm_summ
             // (the step kernel wrote its block before the trial evaluation began: it is there)
             STBA_TRY(stamped_wait(b->dl_host.host, DL_BLOCK, [dseq](double x) { return x == dseq; }, hd, hip_stream_state(b->st),
                                   "dogleg step", 120.0));
-            flag_h = (int)ts[TS_SPEC_COST2];
+            const int flag_h = (int)ts[TS_SPEC_COST2];
             if (flag_h == CHOL_FLAG_TIMEOUT) {
                 // the persistent factorisation gave up (the device is shared): S is rebuilt and factored again through the stage
                 // kernels, as in ba_run_lm
-                chol_note_timeout();
-                if (++chol_timeouts > 8) return fail(STBA_ERR_HIP, "dense Cholesky: the persistent program timed out repeatedly");
+                STBA_TRY(ba_on_chol_timeout(b, sv, flag_h, false));
                 --ds.factorizations; --ds.gauss_newton_solves;
-                need_build = need_gn = true;
-                --iter;
+                need_gn = true;
                 continue;
             }
-            chol_timeouts = 0;
-            if (pending) {
-                // cost and |g|max of the linearisation behind the previous iteration (trial_finish_kernel read them on the way)
-                gmax = ts[TS_LIN_GMAX];
-                if (pending_accepted) cost = 0.5 * ts[TS_LIN_COST2];
-                if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = gmax;
-                pending = false;
-                if (pending_accepted && gmax <= opt.gradient_tolerance) {
-                    --iter;           // converged at the previous iteration: this trial step is discarded
-                    s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
-                    break;
-                }
+            sv.chol_timeouts = 0;
+            // cost and |g|max of the linearisation behind the previous iteration (trial_finish_kernel read them on the way)
+            if (sv.pending.on && ba_take_pending(sv, 0.5 * ts[TS_LIN_COST2], ts[TS_LIN_GMAX])) {
+                --sv.iter;           // converged at the previous iteration: this trial step is discarded
+                stop(sv, STBA_CONVERGENCE, STBA_TERM_GRADIENT);
+                break;
             }
             if (flag_h != 0 || (int)hd[DL_KASE] == DOGLEG_INVALID_GN) {
                 // no Gauss-Newton step at this mu: the same linearisation again at 10 mu
-                if (region.escalate()) { need_build = need_gn = true; --iter; continue; }
+                if (region.escalate()) { sv.need_build = need_gn = true; --sv.iter; continue; }
                 have_gn = false;
             }
         }
-        const double new_cost = have_gn ? 0.5 * ts[TS_COST2] : cost;
-        const double step_norm = have_gn ? std::sqrt(ts[TS_STEP2] + ts[TS_CAM + 0]) : 0.0;
-        const double x_norm = have_gn ? std::sqrt(ts[TS_X2] + ts[TS_CAM + 1]) : 0.0;
-        const double model_change = have_gn ? ts[TS_MODEL] + ts[TS_CAM + 2] : 0.0;
+        const TrialScalars t = have_gn ? trial_scalars(ts) : TrialScalars{sv.cost, 0.0, 0.0, 0.0};
         // a step without a Gauss-Newton step, or whose model change is not positive and finite, is invalid; a trial point whose cost
         // is not finite is rejected.  Neither is judged (row [cost, 0, ., 0, 0], no stop test).
-        const bool valid = have_gn && model_change > 0.0 && std::isfinite(model_change);
-        const bool step_ok = valid && std::isfinite(new_cost);
+        const bool valid = have_gn && t.model_change > 0.0 && std::isfinite(t.model_change);
+        const bool step_ok = valid && std::isfinite(t.new_cost);
         if (have_gn) {
             const int kase = (int)hd[DL_KASE];
             if (kase >= 0 && kase < 3) ++ds.steps_by_case[kase];
             if (reused) ++ds.reused_steps;
         }
-        const StepVerdict v = judge_step(opt, cost, step_ok, new_cost, model_change, step_norm, x_norm, true);
-        const bool accepted = v.accepted;
-        if (accepted) {
-            b->cur ^= 1;
-            cost = new_cost;
-            ++s.num_successful_steps;
-        }
-        trace_step(trace, iter, step_ok, cost, new_cost, v, gmax, step_norm, region.radius);
-        if (v.stop) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
-            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0);
-            break;
-        }
-        if (accepted) region.accept(v.rho, hd[DL_ZNORM], opt);
+        const StepVerdict v = judge_step(opt, sv.cost, step_ok, t.new_cost, t.model_change, t.step_norm, t.x_norm, true);
+        if (ba_apply_verdict(b, sv, v, step_ok, t, region.radius)) break;
+        if (v.accepted) region.accept(v.rho, hd[DL_ZNORM], opt);
         else {
             ++s.num_unsuccessful_steps;
-            if (!valid) { region.invalid(); ++ds.invalid_steps; need_build = need_gn = true; }
+            if (!valid) { region.invalid(); ++ds.invalid_steps; sv.need_build = need_gn = true; }
             else region.reject();
         }
         invalid_in_a_row = valid ? 0 : invalid_in_a_row + 1;
         if (invalid_in_a_row >= kMaxConsecutiveInvalidSteps) {
             // Ceres' max_num_consecutive_invalid_steps (5): mu has only grown, and nothing lowers it but an accepted step
-            s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL;
+            stop(sv, STBA_FAILURE, STBA_TERM_SOLVER_FAIL);
             break;
         }
-        if (accepted) {
+        if (v.accepted) {
             // a new linearisation: the next iteration builds and factors it at the new mu
-            STBA_TRY(ba_linearize_lm(b, b->cur));
-            STBA_TRY(ba_normal_blocks(b));
-            STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
-            need_build = need_gn = true;
-            if (deferred_ok) {
-                pending = true; pending_accepted = true; pending_iter = iter;
+            STBA_TRY(ba_linearize_point(b, b->cur, b->trial + TS_COST2));
+            sv.need_build = need_gn = true;
+            if (sv.deferred_ok) {
+                sv.pending.on = true; sv.pending.accepted = true; sv.pending.iter = sv.iter;
             } else {
-                dm.radius = 1.0 / region.mu;
-                STBA_TRY(ba_build(b, dm));
-                need_build = false;
-                double c2, g2;
-                STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
-                gmax = g2;
-                cost = c2;
+                STBA_TRY(ba_build_at(b, sv, 1.0 / region.mu));
+                STBA_TRY(ba_read_linear_scalars(b, &sv.cost, &sv.gmax));
             }
         }
-        if (trace) { trace[(size_t)iter * STBA_TRACE_COLS + 2] = gmax; trace[(size_t)iter * STBA_TRACE_COLS + 5] = region.radius; }
-        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
-        if (cb && cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, accepted ? 1 : 0) != 0) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER;
-            break;
-        }
-        if (!pending && accepted && gmax <= opt.gradient_tolerance) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
-            break;
-        }
+        if (ba_end_iteration(sv, v, t.step_norm, region.radius)) break;
     }
-    STBA_HIP(hipStreamSynchronize(b->st));
-    if (pending) {      // the loop ended (iteration / radius limit) before the last linearisation's scalars were read
-        double c2, g2;
-        if (need_build) { dm.radius = 1.0 / region.mu; STBA_TRY(ba_build(b, dm)); }
-        STBA_TRY(ba_read_linear_scalars(b, &c2, &g2));
-        gmax = g2;
-        cost = c2;
-        if (trace) trace[(size_t)pending_iter * STBA_TRACE_COLS + 2] = g2;
-        if (g2 <= opt.gradient_tolerance &&
-            (s.termination_reason == STBA_TERM_MAX_ITER || s.termination_reason == STBA_TERM_MIN_RADIUS)) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT;
-        }
-    }
-    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
+    // (a pending read behind the loop needs the reduced system of the last linearisation: the gradient comes with its build)
+    if (sv.pending.on && sv.need_build) STBA_TRY(ba_build_at(b, sv, 1.0 / region.mu));
+    STBA_TRY(ba_solve_end(b, sv, region.radius, sum));
     ds.final_mu = region.mu;
     b->dl_sum = ds;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    if (sum) *sum = s;
     return STBA_OK;
 }
 
@@ -1558,15 +1556,15 @@ int stba_ba_time_schur_apply(stba_ba* b, int reps, double* ms_avg) {
     if (!b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_time_schur_apply: the engine uses the dense Schur solver");
     if (!b->have_blocks) return fail(STBA_ERR_STATE, "stba_ba_time_schur_apply needs stba_ba_schur_apply first");
     const PcgVecs v = pcg_vecs(b);
-    STBA_HIP(hipEventRecord(b->ev[0], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN], b->st));
     for (int k = 0; k < reps; ++k) {
         STBA_TRY(ba_is_landmark_pass(b, v.p, nullptr, nullptr));
         STBA_TRY(ba_is_camera_pass(b, IS_FINAL_APPLY, v.p, v.q, nullptr, nullptr));
     }
-    STBA_HIP(hipEventRecord(b->ev[1], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN_END], b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     float ms = 0.f;
-    STBA_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    STBA_HIP(hipEventElapsedTime(&ms, b->ev[EV_LIN], b->ev[EV_LIN_END]));
     *ms_avg = (double)ms / reps;
     return STBA_OK;
 }
@@ -2035,12 +2033,12 @@ int stba_ba_time_linearize(stba_ba* b, int reps, double* ms_avg) {
     if (!b || reps <= 0 || !ms_avg) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
     LinArgs a = lin_args(b, b->cur, true);
     STBA_TRY(launch_linearize(a, true, b->lin_grid, b->st));   // warm
-    STBA_HIP(hipEventRecord(b->ev[0], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN], b->st));
     for (int k = 0; k < reps; ++k) STBA_TRY(launch_linearize(a, true, b->lin_grid, b->st));
-    STBA_HIP(hipEventRecord(b->ev[1], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN_END], b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     float ms = 0.f;
-    STBA_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    STBA_HIP(hipEventElapsedTime(&ms, b->ev[EV_LIN], b->ev[EV_LIN_END]));
     *ms_avg = (double)ms / reps;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     return STBA_OK;
@@ -2058,12 +2056,12 @@ int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics
     STBA_TRY(launch_point_damp_invert(b->np, b->Hpp6, b->pt_fixed, b->scale_p, b->scale_init ? 0 : 1, dm.use_scaling, dm.radius, dm.dmin,
                                       dm.dmax, b->dp, b->Hinv6, b->Sbuf + (size_t)b->lda * b->lda, 3 * b->lda, b->st));
     STBA_TRY(ba_schur_step(b));      // warm
-    STBA_HIP(hipEventRecord(b->ev[0], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN], b->st));
     for (int k = 0; k < reps; ++k) STBA_TRY(ba_schur_step(b));
-    STBA_HIP(hipEventRecord(b->ev[1], b->st));
+    STBA_HIP(hipEventRecord(b->ev[EV_LIN_END], b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     float ms = 0.f;
-    STBA_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+    STBA_HIP(hipEventElapsedTime(&ms, b->ev[EV_LIN], b->ev[EV_LIN_END]));
     *ms_avg = (double)ms / reps;
     if (lds_atomics_per_launch) *lds_atomics_per_launch = b->schur_lds_atomics;
     if (pairs_per_launch) *pairs_per_launch = b->schur_pairs;

@@ -40,8 +40,8 @@ def x_of(e):
     return np.concatenate([cams.reshape(-1), pts.reshape(-1)])
 
 
-def run(st, e, o, k):
-    summ, tr = e.solve(st.default_options(**dict(o, max_num_iterations=k)))
+def run(st, e, o, k, callback=None):
+    summ, tr = e.solve(st.default_options(**dict(o, max_num_iterations=k)), callback=callback)
     assert summ.num_iterations == k and len(tr) == k + 1, summ.as_dict()
     return summ, tr
 
@@ -69,7 +69,8 @@ def test_reference_trace_covers_every_case():
 PARITY = [(sc, k) for sc in SCENES for k in ((1, 3, 10) if sc == "jitter3_r1" else (1, 3, 5))]
 
 
-@pytest.mark.parametrize("form", ["pairs", "dense", "host"])
+# (watched: the pair plan with an iteration callback -- the loop reads every new linearisation's scalars at once)
+@pytest.mark.parametrize("form", ["pairs", "dense", "host", "watched"])
 @pytest.mark.parametrize("scene,k", PARITY)
 def test_parity_with_reference(st, scene, form, k):
     sk, ok = SCENES[scene]
@@ -82,7 +83,7 @@ def test_parity_with_reference(st, scene, form, k):
         e.set_schur_mode(e.SCHUR_DENSE)
     elif form == "host":
         e.set_host_linearizer(lambda cams, pts, want: prob.lin_obs(cams.copy(), pts.copy(), want))
-    _, tr = run(st, e, o, k)
+    _, tr = run(st, e, o, k, callback=(lambda *a: 0) if form == "watched" else None)
     check(prob, ref, o, e, tr, f"{scene} {form} k={k}")
     ds = e.dogleg_summary()
     assert list(ds.steps_by_case) == [sum(1 for it in ref if it["case"] == c) for c in range(3)], ds.as_dict()
@@ -120,6 +121,59 @@ def test_bitwise_reproducible(st):
         _, tr = run(st, e, o, 10)
         out.append((x_of(e).tobytes(), tr.tobytes()))
     assert out[0] == out[1]
+
+
+def test_two_solves_on_one_engine(st):
+    """the second solve of an engine is the solve of a fresh engine at the same point (what a solve resets, it resets per solve)"""
+    sk, ok = SCENES["jitter3_r1"]
+    s = L.ba_scene(**sk)
+    e = engine(st, s)
+    e.solve(st.default_options(**dict(ok, max_num_iterations=2)))
+    cams, pts = e.get_params()
+    sa, ta = e.solve(st.default_options(**ok))
+    f = st.BAEngine(cams, pts, s["obs_cam"], s["obs_pt"], s["obs_feat"], s["cam_fixed"], pt_fixed=s["pt_fixed"])
+    f.set_trust_region("dogleg")
+    sb, tb = f.solve(st.default_options(**ok))
+    print("DOGLEG two solves", sa.as_dict(), e.dogleg_summary().as_dict())
+    assert sa.num_iterations == sb.num_iterations and sa.termination_reason == sb.termination_reason, (sa.as_dict(), sb.as_dict())
+    assert e.dogleg_summary().as_dict() == f.dogleg_summary().as_dict()
+    assert ta.tobytes() == tb.tobytes() and x_of(e).tobytes() == x_of(f).tobytes()
+
+
+def test_watched_equals_unwatched(st):
+    """to convergence at the library's defaults: the deferred read of a new linearisation's scalars against the immediate one"""
+    sk, ok = SCENES["jitter3_r1"]
+    s = L.ba_scene(**sk)
+    out = []
+    for cb in (None, lambda *a: 0):
+        e = engine(st, s)
+        summ, tr = e.solve(st.default_options(**ok), callback=cb)
+        out.append((summ, tr, x_of(e), e.dogleg_summary().as_dict()))
+    (su, tu, xu, du), (sw, tw, xw, dw) = out
+    print("DOGLEG watched/unwatched", su.as_dict(), du, "max|d trace|", np.abs(tu - tw).max() if tu.shape == tw.shape else None)
+    assert su.termination_type == 0
+    assert (su.num_iterations, su.termination_reason, su.num_successful_steps, su.num_unsuccessful_steps) == \
+           (sw.num_iterations, sw.termination_reason, sw.num_successful_steps, sw.num_unsuccessful_steps)
+    assert du == dw and np.array_equal(tu[:, 6], tw[:, 6])
+    assert tu.tobytes() == tw.tobytes() and xu.tobytes() == xw.tobytes()
+
+
+def test_progress_text(st, capfd):
+    """minimizer_progress_to_stdout: the header, then one row per trace row, numbered 0 .. num_iterations"""
+    import ctypes
+    sk, ok = SCENES["jitter3_r1"]
+    s = L.ba_scene(**sk)
+    e = engine(st, s)
+    libc = ctypes.CDLL(None)
+    libc.fflush(None)
+    capfd.readouterr()
+    summ, tr = e.solve(st.default_options(**dict(L.lm_options(**ok), max_num_iterations=5, minimizer_progress_to_stdout=1)))
+    libc.fflush(None)
+    lines = capfd.readouterr().out.splitlines()
+    assert summ.num_iterations == 5 and len(tr) == 6
+    assert lines[0].split()[:2] == ["iter", "cost"], lines
+    assert len(lines) == 1 + len(tr), lines
+    assert [int(ln.split()[0]) for ln in lines[1:]] == list(range(summ.num_iterations + 1))
 
 
 def test_switching_back_to_lm_is_lm(st):

@@ -185,6 +185,23 @@ def test_bitwise_reproducible(st):
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
+def test_phase_timing_leaves_the_arithmetic_alone(st):
+    """phase_timing = 1 with inner iterations: the same trace and parameters bit for bit, and the sweeps' device time reported"""
+    s = L.ba_scene()
+    outs = []
+    for timing in (0, 1):
+        e = engine(st, s)
+        e.set_inner_iterations(True)
+        summ, tr = e.solve(st.default_options(**dict(L.lm_options(), max_num_iterations=4, phase_timing=timing)))
+        outs.append((summ, tr, x_of(e), e.inner_summary()))
+    (s0, t0, x0, i0), (s1, t1, x1, i1) = outs
+    print(f"INNER phase timing: sweep_ms {i1.sweep_ms:.4f}, sweeps {i1.sweeps}, {s1.as_dict()}")
+    assert s0.num_iterations == s1.num_iterations == 4 and i0.sweeps == i1.sweeps >= 1
+    assert np.array_equal(t0, t1) and np.array_equal(x0, x1)
+    assert i0.sweep_ms == 0.0 and i1.sweep_ms > 0.0
+    assert all(getattr(s1, f) > 0.0 for f in ("ms_linearize", "ms_schur", "ms_solve", "ms_backsub", "ms_cost")), s1.as_dict()
+
+
 @pytest.mark.parametrize("solver", ["dense_schur", "iterative_schur"])
 def test_off_path_is_bitwise_unchanged(st, solver):
     s = st20()

@@ -150,6 +150,29 @@ def test_exact_limit_matches_direct_and_reference(st, case):
     assert ps.solves == se.num_iterations and ps.iterations_total > 0
 
 
+@pytest.mark.parametrize("watched", [False, True], ids=["unwatched", "watched"])
+def test_phase_timing_leaves_the_arithmetic_alone(st, watched):
+    """phase_timing = 1 on the PCG path: the same trace and parameters bit for bit, and the linear solve's device time reported"""
+    sk, ok = L.BA_CASES["lm31_r1e4"]
+    s = L.ba_scene(**sk)
+    out = []
+    for timing in (0, 1):
+        e = engine(st, s)
+        e.set_pcg("schur_jacobi", eta=0.1)
+        summ, tr = e.solve(st.default_options(**dict(L.lm_options(**ok), max_num_iterations=4, phase_timing=timing)),
+                           callback=(lambda *a: 0) if watched else None)
+        cams, pts = e.get_params()
+        out.append((summ, tr, cams, pts, e.pcg_summary()))
+    (s0, t0, c0, p0, q0), (s1, t1, c1, p1, q1) = out
+    print(f"ITERATIVE phase timing: linear_solve_ms {q1.linear_solve_ms:.4f} ms_solve {s1.ms_solve:.4f} pcg {q1.as_dict()}")
+    assert s0.num_iterations == s1.num_iterations == 4
+    assert t0.tobytes() == t1.tobytes() and c0.tobytes() == c1.tobytes() and p0.tobytes() == p1.tobytes()
+    assert (q0.iterations_total, q0.solves) == (q1.iterations_total, q1.solves) and q1.solves == 4
+    assert q0.linear_solve_ms == 0.0 and s0.ms_solve == 0.0
+    assert q1.linear_solve_ms > 0.0 and q1.linear_solve_ms == s1.ms_solve
+    assert all(getattr(s1, f) > 0.0 for f in ("ms_linearize", "ms_schur", "ms_solve", "ms_backsub", "ms_cost")), s1.as_dict()
+
+
 def numpy_gmax(prob, x):
     r, J, cols = prob.lin(x, True)
     g = np.zeros(prob.n_local)
