@@ -673,6 +673,41 @@ typedef struct {
 } stba_inner_summary;
 int stba_ba_last_inner_summary(stba_ba* ba, stba_inner_summary* out);
 
+/* ================================ bundle adjustment: robust loss functions ================================ */
+/* A loss rho_i per observation, the kinds and parameters of the pose graph's table above (STBA_LOSS_*, Ceres' rho, rho', rho'' and
+ * ScaledLoss): the engine then minimises 1/2 sum_i rho_i(|r_i|^2).  A linearisation kernel of its own evaluates the loss at
+ * s = |r|^2 and applies Ceres' corrector to the residual and to both Jacobian blocks of the observation; it writes them in the
+ * general form that host-linearised factors use (the 2x6 camera block stored, not re-derived from the projection), so every stage
+ * behind it works on the robustified problem:
+ *   stba_ba_evaluate              hands back the CORRECTED r', Jc', Jp' (columns of constant dofs zero) and the cost 1/2 sum rho --
+ *                                 Ceres' Problem::Evaluate with apply_loss_function = true;
+ *   stba_ba_solve / _lm_iterations  LM or DOGLEG, dense Schur (both forms) or ITERATIVE_SCHUR: the step solves
+ *                                 (J'^T J' + D) d = -J'^T r', the model change is that of (r', J'), the gain ratio divides the change
+ *                                 of 1/2 sum rho by it;
+ *   stba_ba_covariance_compute    gives (J'^T J')^-1, as Ceres' Covariance does;
+ *   the stage entry points and stba_ba_time_linearize work on / time the correcting linearisation.
+ *   stba_ba_set_loss   kind[n_obs] (STBA_LOSS_*), a[n_obs], b[n_obs], scale[n_obs] in the CALLER's observation order (that of
+ *                      stba_ba_create).  b may be NULL if no observation is TOLERANT, a may be NULL if every one is TRIVIAL,
+ *                      scale == NULL means 1 for every observation.  Entries of a and b that the observation's kind does not use are
+ *                      not read.  Checked before anything is replaced: an unknown kind, an a (or, for TOLERANT, b) that is not finite
+ *                      and positive, a scale that is not finite or is negative: STBA_ERR_INVALID_ARGUMENT, stba_last_error() names
+ *                      the smallest such observation, and the engine keeps the table it had.
+ *                      kind == NULL removes the table: the engine is bit for bit the one that never had a loss (it runs the
+ *                      lossless kernels on the compact Jacobian record).  An observation of kind TRIVIAL and scale 1 is left
+ *                      untouched by the corrector: what stba_ba_evaluate returns for it compares == with the lossless engine's.
+ *   stba_ba_has_loss   *has = 1 while the engine holds a table.
+ *   stba_ba_loss_kernel_geometry   DIAGNOSTIC, NOT A STABLE INTERFACE (the tests derive their scenes from it; the figures belong to
+ *                      this build's kernel and may change or go with it; every pointer nullable): observations per workgroup tile of
+ *                      the correcting kernel, whether THIS engine's cameras are staged in its LDS, the largest camera count that is.
+ * A call that succeeds invalidates the current linearisation and releases a held covariance.  Refused with
+ * STBA_ERR_INVALID_ARGUMENT, the state untouched, in both orders: a table on an engine with a host lineariser, with inner iterations,
+ * or with an all-reduce hook / communicator (and those setters on an engine with a table).  TUKEY can give every observation of a
+ * landmark the weight zero: the solve is covered by its damping (the landmark does not move); a covariance at such a point meets a
+ * singular landmark block.  STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_loss(stba_ba* ba, const int* kind, const double* a, const double* b, const double* scale);  /* [n_obs], caller's observation order */
+int stba_ba_has_loss(const stba_ba* ba, int* has);
+int stba_ba_loss_kernel_geometry(const stba_ba* ba, int* tile_observations, int* cameras_in_lds, int* max_cameras_in_lds);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

@@ -134,6 +134,12 @@ constexpr int DYNAMIC = -1;
 // else that holds a non-null LossFunction -- a bare LossFunction or a user subclass (this base class has no Evaluate to call), any
 // loss on a problem that takes a bundle-adjustment or the dense-callback route -- is REFUSED by Solve() and Covariance::Compute
 // (FAILURE, parameters untouched, the reason in Summary::message and on stderr) instead of being solved without the loss.
+// OPT-IN for bundle adjustment (an extension of this layer, like force_callback_path; the default stays the refusal):
+// Solver::Options::bundle_adjustment_losses / Covariance::Options::bundle_adjustment_losses = true let a problem with losses through
+// if, without them, it takes "gpu-ba" (device residuals: not "gpu-ba-hostjac", not the callback path), use_inner_iterations is off and
+// every loss is one of the built-in classes (ScaledLoss one level deep included).  The per-observation table (kind 0, scale 1 for a
+// block without a loss) then goes to stba_ba_set_loss before the solve (include/stba.h); any linear_solver_type and
+// trust-region strategy "gpu-ba" accepts is accepted; Covariance returns (J'^T J')^-1.  Everything else is refused as before.
 // Not provided: ComposedLoss, LossFunctionWrapper; ScaledLoss wraps a built-in (or nullptr) one level deep.
 class LossFunction { public: virtual ~LossFunction() = default; };
 
@@ -724,7 +730,7 @@ public:
         if (options_.cost_function_ownership == TAKE_OWNERSHIP && !cost->owned_by_problem_) { cost->owned_by_problem_ = true; owned_costs_.push_back(cost); }
         if (loss) { owned_losses_.insert(loss); ++num_loss_functions_; }
     }
-    int NumLossFunctions() const { return num_loss_functions_; }   // residual blocks added with a non-null LossFunction (Solve takes them on gpu-pg only)
+    int NumLossFunctions() const { return num_loss_functions_; }   // residual blocks added with a non-null LossFunction (Solve takes them on gpu-pg, and on gpu-ba with bundle_adjustment_losses)
     void SetParameterBlockConstant(double* values) { find(values).constant = true; }
     void SetParameterBlockVariable(double* values) { find(values).constant = false; }
     void SetParameterLowerBound(double* values, int index, double lower) { Block& b = find(values); b.ensure_bounds(); b.lower[index] = lower; }
@@ -892,6 +898,9 @@ public:
                function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
         bool jacobi_scaling = true;
         bool force_callback_path = false;   // (not in Ceres) never replace user cost functions by the built-in device factor: see Solve()
+        // (not in Ceres) let built-in LossFunctions through on a problem that takes "gpu-ba": see the comment above class LossFunction.
+        // Off by default: without it a loss on a bundle-adjustment problem is refused, as it always was.
+        bool bundle_adjustment_losses = false;
         // inner iterations on the "gpu-ba" path: a coordinate-descent sweep behind every valid step.  Default ordering:
         // {every rotation block}, {every position block}, {every landmark} -- Ceres' choice between rotations and positions for the
         // first group depends on hash order; this is its deterministic instance.  Refused before any device work (FAILURE, the reason
@@ -1127,6 +1136,10 @@ template <class F> inline void ParallelRanges(size_t n, int threads, F fn) {
 
 // ---- path 1: every residual block is the reprojection factor (built-in or recognised) --------
 struct BaLayout {
+    // [n_obs] each, the residual blocks' losses as stba_ba_set_loss takes them (TRIVIAL, scale 1 for a block without one), in the
+    // order of the residual blocks, which is the order of obs_cam / obs_pt / feat; EMPTY if no block has a loss (BaLossTable)
+    std::vector<int> loss_kind;
+    std::vector<double> loss_a, loss_b, loss_scale;
     std::vector<int> rot_block, pos_block;   // per camera: Problem block indices
     std::vector<int> pt_block;               // per landmark
     std::vector<int> obs_cam, obs_pt;
@@ -1347,6 +1360,28 @@ inline bool MakeInnerGroups(const Solver::Options& o, Problem& p, const BaLayout
     return true;
 }
 
+// the per-observation loss table of a BA-shaped problem -> L (as DetectPoseGraph builds the per-edge one); false if a loss is not a
+// built-in (KnownLossRow)
+inline bool BaLossTable(Problem& p, BaLayout* L) {
+    L->loss_kind.clear(); L->loss_a.clear(); L->loss_b.clear(); L->loss_scale.clear();
+    if (p.NumLossFunctions() == 0) return true;
+    bool known = true;
+    for (const auto& r : p.residuals()) {
+        int kind = STBA_LOSS_TRIVIAL;
+        double a = 1.0, b = 1.0, scale = 1.0;
+        if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) known = false;
+        L->loss_kind.push_back(kind); L->loss_a.push_back(a); L->loss_b.push_back(b); L->loss_scale.push_back(scale);
+    }
+    return known;
+}
+// a problem with losses that, without them, takes "gpu-ba" -- every block the reprojection factor (the per-block half of the
+// recognition included), quaternion right-plus charts -- and whose losses are all built-ins; *L gets the layout and the table
+inline bool BaWithKnownLosses(Problem* problem, int threads, BaLayout* L) {
+    bool ba = DetectBa(*problem, L, true, threads);
+    if (ba) for (int rb : L->rot_block) ba = ba && UsesQuaternionRightPlus(problem->blocks()[rb].local);
+    return ba && BaLossTable(*problem, L);
+}
+
 inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Solver::Summary* sum, bool host_jacobians = false,
                     BaLayout* blocks_layout = nullptr, bool* blocks_ok = nullptr, std::thread* destroyer = nullptr,
                     const InnerGroups* inner = nullptr) {
@@ -1421,6 +1456,11 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     }
     lap(&sum->phases.engine_create);
     if (rc != STBA_OK) { sum->termination_type = FAILURE; sum->message = std::string("stba_ba_create: ") + create_error; return false; }
+    if (!L.loss_kind.empty() && (rc = stba_ba_set_loss(sync.ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_loss: ") + stba_last_error();
+        stba_ba_destroy(sync.ba);
+        return false;
+    }
     BaHostCtx hctx{p, &L, o.num_threads};
     if (host_jacobians && (rc = stba_ba_set_host_linearizer(sync.ba, &BaHostLinearize, &hctx)) != STBA_OK) {
         sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_host_linearizer: ") + stba_last_error();
@@ -1735,8 +1775,16 @@ inline bool LossesGoToPoseGraph(const Solver::Options& options, Problem* problem
     if (options.force_callback_path || (fe && *fe && *fe != '0') || !options.callbacks.empty()) return false;
     return PoseGraphWithKnownLosses(problem);
 }
+// Solver::Options::bundle_adjustment_losses: the problem, without its losses, takes "gpu-ba" and every loss is a built-in
+inline bool LossesGoToBa(const Solver::Options& options, Problem* problem) {
+    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
+    if (!options.bundle_adjustment_losses || options.force_callback_path || (fe && *fe && *fe != '0') || options.use_inner_iterations) return false;
+    BaLayout L;
+    return BaWithKnownLosses(problem, options.num_threads, &L);
+}
 inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
-    if (problem->NumLossFunctions() > 0 && !LossesGoToPoseGraph(options, problem)) {
+    const bool ba_losses = problem->NumLossFunctions() > 0 && !LossesGoToPoseGraph(options, problem) && LossesGoToBa(options, problem);
+    if (problem->NumLossFunctions() > 0 && !ba_losses && !LossesGoToPoseGraph(options, problem)) {
         // (Ceres would apply the loss; outside the pose-graph route this layer has none to apply -- a solve without it would be a
         // silently different problem)
         summary->termination_type = FAILURE;
@@ -1803,6 +1851,7 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
     bool ba = !force_cb && DetectBa(*problem, &L, true, options.num_threads, true);      // (the per-block half: inside SolveBa)
     if (ba)
         for (int rb : L.rot_block) ba = ba && UsesQuaternionRightPlus(problem->blocks()[rb].local);
+    if (ba && ba_losses) BaLossTable(*problem, &L);
     summary->phases.recognise = WallSeconds() - t0;
     if (options.use_inner_iterations) {
         // (gpu-ba only: every block must be the reprojection factor -- the per-block half of the recognition runs here, before any
@@ -1849,6 +1898,15 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         }
         size_t o = 0;
         for (auto& b : problem->blocks()) { std::copy(saved.begin() + o, saved.begin() + o + b.size, b.ptr); o += (size_t)b.size; }
+        if (ba_losses) {
+            // (the second solve would take gpu-ba-hostjac, which has no losses: refused, the parameters as they were)
+            *summary = Solver::Summary();
+            summary->termination_type = FAILURE;
+            summary->message = "stba_ceres: a user cost function taken for the reprojection factor differs from it at the solution, and robust losses are "
+                               "not implemented on the gpu-ba-hostjac path (LossFunction) -- nothing was solved.";
+            std::fprintf(stderr, "%s\n", summary->message.c_str());
+            return;
+        }
         const Solver::Summary::Phases first = summary->phases;
         const std::vector<int> given = summary->inner_iteration_ordering_given;
         *summary = Solver::Summary();
@@ -1909,8 +1967,8 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
 //     Compute return false (the message names the component), before any device work;
 //   * "gpu-dense": anything else within the dense solve's limits -> stba_dense_covariance.
 // On the BA routes a requested pair must be two camera blocks (rotation / position, of one camera or of two) or one landmark with
-// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: robust losses on "gpu-pg" only,
-// where the result is (J'^T J')^-1 of the corrected Jacobian as in Ceres (refused elsewhere as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
+// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: robust losses on "gpu-pg", and on "gpu-ba"
+// with Options::bundle_adjustment_losses set, where the result is (J'^T J')^-1 of the corrected Jacobian as in Ceres (refused elsewhere as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
 // factorisations (stba.h, stba_ba_covariance_compute) -- not a condition number estimate.  algorithm_type and num_threads are
 // accepted for source compatibility and do not change the computation.
 // (not in Ceres) execution_path() and message(): which route ran, and why Compute returned false.
@@ -1924,6 +1982,7 @@ public:
         int null_space_rank = 0;
         int num_threads = 1;
         bool apply_loss_function = true;
+        bool bundle_adjustment_losses = false;   // (not in Ceres) as Solver::Options::bundle_adjustment_losses: built-in losses on "gpu-ba"
     };
     explicit Covariance(const Options& options) : options_(options) {}
 
@@ -1984,7 +2043,9 @@ private:
 
     bool ComputeImpl(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p) {
         using namespace internal;
-        if (p->NumLossFunctions() > 0 && !PoseGraphWithKnownLosses(p))
+        BaLayout LL;
+        const bool ba_losses = p->NumLossFunctions() > 0 && options_.bundle_adjustment_losses && BaWithKnownLosses(p, options_.num_threads, &LL);
+        if (p->NumLossFunctions() > 0 && !ba_losses && !PoseGraphWithKnownLosses(p))
             return Fail(std::to_string(p->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are not implemented by this layer -- no covariance computed");
         if (options_.null_space_rank != 0)
             return Fail("null_space_rank = " + std::to_string(options_.null_space_rank) + ": this layer has no pseudo-inverse (only 0 is supported)");
@@ -2009,6 +2070,7 @@ private:
             host = DetectBa(*p, &L, false);
             if (host) for (int rb : L.rot_block) host = host && UsesQuaternionRightPlus(p->blocks()[rb].local);
         }
+        if (ba && ba_losses && options_.apply_loss_function) BaLossTable(*p, &L);      // (false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
         if (ba || host) return ComputeBa(pairs, p, L, index, host);
         PoseGraphLayout G;
         if (DetectPoseGraph(p, &G)) return ComputePoseGraph(pairs, G, index);
@@ -2082,6 +2144,8 @@ private:
                            pt_fixed.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_ba_create: ") + stba_last_error());
         struct Destroy { stba_ba* b; ~Destroy() { stba_ba_destroy(b); } } destroy{ba};
+        if (!host && !L.loss_kind.empty() && stba_ba_set_loss(ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
+            return Fail(std::string("stba_ba_set_loss: ") + stba_last_error());
         BaHostCtx hctx{p, &L, options_.num_threads};
         if (host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, &hctx) != STBA_OK) return Fail(std::string("stba_ba_set_host_linearizer: ") + stba_last_error());
         double rc = 0.0;

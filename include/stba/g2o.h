@@ -86,8 +86,33 @@ protected:
     T _backup{};
 };
 
+// g2o's robust kernels (robust_kernel.h, robust_kernel_impl.h): rho(e2) of the edge's squared error e2.  RobustKernelHuber(delta):
+// e2 for sqrt(e2) <= delta, else 2 delta sqrt(e2) - delta^2; RobustKernelCauchy(delta): delta^2 log(1 + e2 / delta^2) -- Ceres'
+// HuberLoss(delta) and CauchyLoss(delta) (include/stba.h, STBA_LOSS_HUBER / STBA_LOSS_CAUCHY with a = delta).  Both have rho'' <= 0,
+// so g2o's weighting of error and Jacobian by sqrt(rho') is the first branch of Ceres' corrector, which the engine applies
+// (stba_ba_set_loss).  The classes are final: SparseOptimizer::optimize recognises exactly these two by dynamic_cast
+// and refuses any other RobustKernel subclass the way it refuses a foreign edge type.  delta defaults to 1 as in g2o.
+class RobustKernel {
+public:
+    RobustKernel() = default;
+    explicit RobustKernel(number_t delta) : _delta(delta) {}
+    virtual ~RobustKernel() = default;
+    virtual void setDelta(number_t delta) { _delta = delta; }
+    number_t delta() const { return _delta; }
+protected:
+    number_t _delta = 1.0;
+};
+class RobustKernelHuber final : public RobustKernel { public: using RobustKernel::RobustKernel; };
+class RobustKernelCauchy final : public RobustKernel { public: using RobustKernel::RobustKernel; };
+
 struct Edge {
-    virtual ~Edge() = default;
+    virtual ~Edge() { delete _robust; }
+    Edge() = default;
+    Edge(const Edge&) = delete;
+    Edge& operator=(const Edge&) = delete;
+    // the edge owns its kernel, as in g2o (a second call deletes the first kernel; nullptr removes it)
+    void setRobustKernel(RobustKernel* k) { if (k != _robust) delete _robust; _robust = k; }
+    RobustKernel* robustKernel() const { return _robust; }
     virtual int dimension() const = 0;
     virtual void computeError() = 0;
     virtual void error_raw(double* out) const = 0;
@@ -96,6 +121,7 @@ struct Edge {
     const std::vector<Vertex*>& vertices() const { return _vertices; }
 protected:
     std::vector<Vertex*> _vertices;
+    RobustKernel* _robust = nullptr;
 };
 
 template <int D, typename E, typename VertexXi, typename VertexXj>
@@ -157,8 +183,20 @@ public:
         const int no = (int)_edges.size();
         std::vector<int> oc(no), op(no);
         std::vector<double> feat((size_t)no * 2);
+        // the edges' robust kernels as the per-observation table of stba_ba_set_loss (kind TRIVIAL for an edge without one); used only if
+        // some edge has a kernel
+        std::vector<int> lkind((size_t)no, STBA_LOSS_TRIVIAL);
+        std::vector<double> la((size_t)no, 1.0);
+        bool any_kernel = false;
         for (int k = 0; k < no; ++k) {
             Edge* e = _edges[k];
+            if (const RobustKernel* rk = e->robustKernel()) {
+                if (dynamic_cast<const RobustKernelHuber*>(rk)) lkind[(size_t)k] = STBA_LOSS_HUBER;
+                else if (dynamic_cast<const RobustKernelCauchy*>(rk)) lkind[(size_t)k] = STBA_LOSS_CAUCHY;
+                else { _message = "edge " + std::to_string(k) + ": unsupported robust kernel (only RobustKernelHuber and RobustKernelCauchy run on the device)"; return 0; }
+                la[(size_t)k] = rk->delta();
+                any_kernel = true;
+            }
             if (e->dimension() != 2 || e->vertices().size() != 2) { _message = "unsupported edge (only binary 2-residual projection edges)"; return 0; }
             const int a = vidx(e->vertices()[0]), b = vidx(e->vertices()[1]);
             if (a < 0 || b < 0 || cam_of[a] < 0 || pt_of[b] < 0) { _message = "edge does not connect (pose, landmark)"; return 0; }
@@ -185,6 +223,11 @@ public:
             _message = std::string("stba_ba_create: ") + stba_last_error();
             return 0;
         }
+        if (any_kernel && stba_ba_set_loss(ba, lkind.data(), la.data(), nullptr, nullptr) != STBA_OK) {
+            _message = std::string("stba_ba_set_loss: ") + stba_last_error();      // (a delta that is not finite and positive: the edge is named)
+            stba_ba_destroy(ba);
+            return 0;
+        }
         stba_lm_options o;
         stba_lm_default_options(&o);
         o.max_num_iterations = iterations;
@@ -208,7 +251,7 @@ public:
                     stba_ba_destroy(ba);
                     return 0;
                 }
-            _chi2 = 2.0 * s.final_cost;   // g2o reports chi^2 = sum r^2, Ceres 1/2 sum r^2
+            _chi2 = 2.0 * s.final_cost;   // g2o reports chi^2 = sum r^2 (sum rho with robust kernels), Ceres 1/2 of it
             done = s.num_iterations;
             if (_verbose)
                 for (int i = 0; i <= s.num_iterations; ++i)

@@ -83,7 +83,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_set_inner_iterations", "stba_ba_inner_sweep", "stba_ba_last_inner_summary",
            "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check",
            "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information",
-           "stba_pg_set_loss", "stba_pg_has_loss"]
+           "stba_pg_set_loss", "stba_pg_has_loss",
+           "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry"]
 
 
 def lib():
@@ -228,7 +229,10 @@ class BAEngine:
     linear_solver: "dense_schur" (the reduced camera system formed and factored: stba_ba_create) or "iterative_schur" (PCG on the
     implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
 
-    def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur"):
+    def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur",
+                 loss=None):
+        """loss: per-observation robust losses as PGEngine takes them -- a kind name, a tuple (kind, a[, b[, scale]]) or a dict of
+        set_loss's arguments"""
         self._h = C.c_void_p()
         cams = _f64(cams).reshape(-1, 7)
         pts = _f64(pts).reshape(-1, 3)
@@ -242,6 +246,7 @@ class BAEngine:
         if linear_solver not in LINEAR_SOLVERS:
             raise ValueError(f"linear_solver must be one of {sorted(LINEAR_SOLVERS)}")
         self.linear_solver = linear_solver
+        table = None if loss is None else self._loss_table(loss)
         if linear_solver == "dense_schur":
             _chk(lib().stba_ba_create(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
                                       _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0)), "stba_ba_create")
@@ -249,6 +254,8 @@ class BAEngine:
             o = BACreateOptions(C.sizeof(BACreateOptions), LINEAR_SOLVERS[linear_solver])
             _chk(lib().stba_ba_create_ex(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
                                          _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0), C.byref(o)), "stba_ba_create_ex")
+        if table is not None:
+            self._set_loss_table(table)
 
     def close(self):
         if self._h:
@@ -276,6 +283,43 @@ class BAEngine:
         cams = np.zeros((self.nc, 7)); pts = np.zeros((self.np_, 3))
         _chk(lib().stba_ba_get_params(self._h, _p(cams), _p(pts)), "stba_ba_get_params")
         return cams, pts
+
+    # ---- robust losses
+    def _loss_table(self, loss):
+        kw = dict(who="BAEngine", what="observation")
+        if isinstance(loss, dict):
+            return pg_loss_table(self.no, **loss, **kw)
+        if isinstance(loss, tuple):
+            return pg_loss_table(self.no, *loss, **kw)
+        return pg_loss_table(self.no, loss, **kw)
+
+    def _set_loss_table(self, table):
+        kind, a, b, scale = table
+        _chk(lib().stba_ba_set_loss(self._h, _p(kind), _p(a), _p(b), _p(scale)), "stba_ba_set_loss")
+
+    def set_loss(self, kind, a=None, b=None, scale=None):
+        """robust losses (Ceres' kinds, LOSS_KINDS), per observation in the order given at creation: the cost becomes
+        1/2 sum rho_i(|r_i|^2).  One spec for all observations -- set_loss("cauchy", 0.05) -- or sequences of length n_obs:
+        set_loss(["huber", None, ...], a_array).  b is TolerantLoss' second parameter; scale multiplies the loss (ScaledLoss).
+        evaluate() then returns the corrected r, Jc, Jp, covariance() (J'^T J')^-1 (include/stba.h).  set_loss(None): no loss, the
+        engine as it was."""
+        if kind is None and a is None and b is None and scale is None:
+            _chk(lib().stba_ba_set_loss(self._h, None, None, None, None), "stba_ba_set_loss")
+            return
+        self._set_loss_table(pg_loss_table(self.no, kind, a, b, scale, who="BAEngine", what="observation"))
+
+    @property
+    def has_loss(self):
+        has = C.c_int()
+        _chk(lib().stba_ba_has_loss(self._h, C.byref(has)), "stba_ba_has_loss")
+        return bool(has.value)
+
+    def loss_kernel_geometry(self):
+        """(observations per workgroup tile of the correcting linearisation kernel, whether this engine's cameras are staged in its
+        LDS, the largest camera count that still is): stba_ba_loss_kernel_geometry"""
+        t, c, m = C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().stba_ba_loss_kernel_geometry(self._h, C.byref(t), C.byref(c), C.byref(m)), "stba_ba_loss_kernel_geometry")
+        return t.value, bool(c.value), m.value
 
     def set_allreduce(self, fn, rank, world):
         cb = ALLREDUCE_FN(fn)
@@ -545,7 +589,7 @@ def pg_gauge_check(n_nodes, edge_i, edge_j, node_fixed=None):
 LOSS_KINDS = {None: 0, "trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tolerant": 5, "tukey": 6}
 
 
-def pg_loss_table(m, kind, a=None, b=None, scale=None):
+def pg_loss_table(m, kind, a=None, b=None, scale=None, who="PGEngine", what="edge"):
     """the per-edge table stba_pg_set_loss takes, from one spec for all m edges or per-edge sequences: kind a name of LOSS_KINDS (or
     its integer), a / b / scale numbers; each may be a scalar or have length m.  Returns (kind int32[m], a, b, scale float64[m]);
     a and b default to 1 where the kind does not use them, scale to 1.  Raises ValueError on an unknown name or a wrong length."""
@@ -554,7 +598,7 @@ def pg_loss_table(m, kind, a=None, b=None, scale=None):
             return int(k)
         key = k.lower() if isinstance(k, str) else k
         if key not in LOSS_KINDS:
-            raise ValueError(f"PGEngine: unknown loss kind {k!r} (one of {sorted(x for x in LOSS_KINDS if x)} or None)")
+            raise ValueError(f"{who}: unknown loss kind {k!r} (one of {sorted(x for x in LOSS_KINDS if x)} or None)")
         return LOSS_KINDS[key]
 
     if kind is None or isinstance(kind, (str, int, np.integer)):
@@ -562,7 +606,7 @@ def pg_loss_table(m, kind, a=None, b=None, scale=None):
     else:
         kinds = np.array([code(k) for k in kind], np.int32)
         if kinds.shape != (m,):
-            raise ValueError(f"PGEngine: per-edge loss kinds must have length {m}, got {kinds.shape}")
+            raise ValueError(f"{who}: per-{what} loss kinds must have length {m}, got {kinds.shape}")
 
     def column(v, name):
         if v is None:
@@ -571,7 +615,7 @@ def pg_loss_table(m, kind, a=None, b=None, scale=None):
         if v.ndim == 0:
             return np.full(m, float(v))
         if v.shape != (m,):
-            raise ValueError(f"PGEngine: per-edge loss parameter {name} must be a number or have length {m}, got {v.shape}")
+            raise ValueError(f"{who}: per-{what} loss parameter {name} must be a number or have length {m}, got {v.shape}")
         return np.ascontiguousarray(v)
 
     return kinds, column(a, "a"), column(b, "b"), column(scale, "scale")

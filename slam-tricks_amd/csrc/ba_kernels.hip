@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "ba_kernels.hpp"
+#include "robust_loss.hpp"
 
 namespace stba {
 
@@ -131,6 +132,180 @@ int launch_linearize(const LinArgs& a, bool with_jac, int grid, hipStream_t st) 
         hipLaunchKernelGGL((ba_linearize_kernel<false, true>), dim3(grid), dim3(LIN_THREADS), lds, st, a);
     else
         hipLaunchKernelGGL((ba_linearize_kernel<false, false>), dim3(grid), dim3(LIN_THREADS), lds, st, a);
+    STBA_HIP(hipGetLastError());
+    return STBA_OK;
+}
+
+// ===========================================================================================
+// residual + Jacobian with a per-observation robust loss (stba_ba_set_loss).  The geometry is ba_linearize_kernel's:
+// one observation per lane, cameras staged in LDS when they fit, every global store 16 B per lane and contiguous across the wave.
+// Behind the projection the observation's loss (kind[i], a[i], b[i], scale[i]: read by observation index) is evaluated at
+// s = |r|^2 and Ceres' corrector turns r and both Jacobian blocks into r', J' (J'^T r' = rho' J^T r, J'^T J' the Triggs
+// approximation of the robustified Hessian).  The corrected camera block q A hat(p) is no function of (xn, yn) any more, so the
+// kernel writes the GENERAL form that host-linearised factors use: J8 = {0, 0, Jp'}, Jc12 = Jc' (2 x 6 row-major, unmasked; the
+// constant-dof mask is applied where the blocks are loaded, load_jc_jp<true>).  The cost partial is sum rho(s), also when
+// WITH_JAC = false (the LM trial point).  An observation of kind TRIVIAL and scale 1 skips the corrector, and its camera block is
+// written with the very expressions of load_jc_jp<false>: what it stores compares == to the lossless engine's.
+// The tile is LIN_ROBUST_THREADS = 512 observations: 8 + 12 doubles per lane (rows padded to 9 and 13, odd strides) are 88 KB, staged
+// in ONE pass next to the cameras; at 1024 lanes they would not fit into 160 KB, and 8 waves per workgroup leave 256 VGPRs per lane.
+// ===========================================================================================
+template <bool CAMS_IN_LDS, bool WITH_JAC>
+__global__ __launch_bounds__(LIN_ROBUST_THREADS) void ba_linearize_robust_kernel(LinArgs a, LinLoss l) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int T = LIN_ROBUST_THREADS;
+    double* s_j8 = smem;                                  // [T][9]
+    double* s_jc = smem + T * 9;                          // [T][13]
+    double* s_cam = smem + (WITH_JAC ? T * (9 + 13) : 0);   // [n_cams][7]
+    const int tid = threadIdx.x;
+    if (CAMS_IN_LDS) {
+        for (int i = tid; i < a.n_cams * 7; i += T) s_cam[i] = a.cams[i];
+        __syncthreads();
+    }
+    double cost = 0.0;
+    const int n_tiles = (a.n_obs + T - 1) / T;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int base = tile * T;
+        const int i = base + tid;
+        if (i < a.n_obs) {
+            const double2 f = a.feat[i];
+            const int c = a.obs_cam[i], j = a.obs_pt[i];
+            const int kind = l.kind[i];
+            const double la = l.a[i], lb = l.b[i], sc = l.scale[i];
+            const double* cam = CAMS_IN_LDS ? (s_cam + c * 7) : (a.cams + (size_t)c * 7);
+            double q[4] = {cam[0], cam[1], cam[2], cam[3]};
+            const double t0 = cam[4], t1 = cam[5], t2 = cam[6];
+            const double* L = a.pts + (size_t)j * 3;
+            const double d0 = L[0] - t0, d1 = L[1] - t1, d2 = L[2] - t2;
+            double R[9];
+            quat_to_rot(q, R);
+            const double x = R[0] * d0 + R[3] * d1 + R[6] * d2;   // R^T (L - t)
+            const double y = R[1] * d0 + R[4] * d1 + R[7] * d2;
+            const double z = R[2] * d0 + R[5] * d1 + R[8] * d2;
+            const double iz = 1.0 / z;
+            const double xn = x * iz, yn = y * iz;
+            double r0 = xn - f.x, r1 = yn - f.y;
+            const double s = r0 * r0 + r1 * r1;
+            double jc[12], jp[6];
+            if (WITH_JAC) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {                     // P = A R^T, as ba_linearize_kernel has it
+                    jp[k] = iz * (R[k * 3 + 0] - xn * R[k * 3 + 2]);
+                    jp[3 + k] = iz * (R[k * 3 + 1] - yn * R[k * 3 + 2]);
+                }
+                jc[0] = xn * yn;                                  // [A hat(pInC) | -P], as load_jc_jp<false> has it
+                jc[1] = -(1.0 + xn * xn);
+                jc[2] = yn;
+                jc[6] = 1.0 + yn * yn;
+                jc[7] = -xn * yn;
+                jc[8] = -xn;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { jc[3 + k] = -jp[k]; jc[9 + k] = -jp[3 + k]; }
+            }
+            double rho0 = s;
+            if (kind != STBA_LOSS_TRIVIAL || sc != 1.0) {
+                double rho[3];
+                robust_loss(kind, la, lb, s, rho);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) rho[k] *= sc;
+                rho0 = rho[0];
+                const double sq = sqrt(rho[1]);
+                double rs = sq, ak = 0.0;                         // residual scaling, alpha / s of Ceres' corrector
+                if (s != 0.0 && rho[2] > 0.0) {
+                    const double alpha = 1.0 - sqrt(1.0 + 2.0 * s * rho[2] / rho[1]);
+                    rs = sq / (1.0 - alpha);
+                    ak = alpha / s;
+                }
+                if (WITH_JAC) {
+                    // J <- sqrt(rho') (J - (alpha / s) r (r^T J)), one column at a time (ak == 0: the scaling alone)
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) {
+                        double& u = k < 6 ? jc[k] : jp[k - 6];
+                        double& v = k < 6 ? jc[6 + k] : jp[k - 3];
+                        if (ak != 0.0) {
+                            const double t = (r0 * u + r1 * v) * ak;
+                            u = sq * (u - r0 * t);
+                            v = sq * (v - r1 * t);
+                        } else {
+                            u = sq * u;
+                            v = sq * v;
+                        }
+                    }
+                }
+                r0 *= rs; r1 *= rs;
+            }
+            if (a.r) a.r[i] = make_double2(r0, r1);
+            cost += rho0;
+            if (WITH_JAC) {
+                double* j8 = s_j8 + tid * 9;
+                double* j12 = s_jc + tid * 13;
+                j8[0] = 0.0; j8[1] = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) j8[2 + k] = jp[k];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) j12[k] = jc[k];
+            }
+        }
+        if (WITH_JAC) {
+            __syncthreads();
+            const int n_here = min(T, a.n_obs - base);
+            double* gj = a.J8 + (size_t)base * 8;
+            for (int e = tid; e < n_here * 4; e += T) {
+                const int o = e >> 2, k = (e & 3) * 2;
+                const double* sj = s_j8 + o * 9 + k;
+                *reinterpret_cast<double2*>(gj + 2 * (size_t)e) = make_double2(sj[0], sj[1]);
+            }
+            double* gc = l.Jc12 + (size_t)base * 12;
+            for (int e = tid; e < n_here * 6; e += T) {
+                const int o = e / 6, k = (e - o * 6) * 2;
+                const double* sj = s_jc + o * 13 + k;
+                *reinterpret_cast<double2*>(gc + 2 * (size_t)e) = make_double2(sj[0], sj[1]);
+            }
+            __syncthreads();
+        }
+    }
+    // deterministic block reduction of the cost
+    __shared__ double s_red[T / 64];
+    for (int off = 32; off > 0; off >>= 1) cost += __shfl_down(cost, off, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = cost;
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int w = 0; w < T / 64; ++w) sum += s_red[w];
+        a.cost_partial[blockIdx.x] = sum;
+    }
+}
+
+size_t lin_robust_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac) {
+    size_t d = 0;
+    if (with_jac) d += (size_t)LIN_ROBUST_THREADS * (9 + 13);
+    if (cams_in_lds) d += (size_t)n_cams * 7;
+    return d * sizeof(double) + 16;
+}
+
+// (decided once per engine, from the full linearisation: the residual-only launch of the trial point takes the same variant)
+bool lin_robust_cams_in_lds(int n_cams) { return lin_robust_lds_bytes(n_cams, true, true) <= (size_t)LIN_MAX_LDS; }
+
+int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st) {
+    const bool in_lds = lin_robust_cams_in_lds(a.n_cams);
+    const size_t lds = lin_robust_lds_bytes(a.n_cams, in_lds, with_jac);
+    static DeviceOnce attr;
+    STBA_TRY(attr.run([]() -> int {
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, false>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<false, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
+        return STBA_OK;
+    }));
+    if (in_lds && with_jac)
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, true>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+    else if (in_lds)
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, false>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+    else if (with_jac)
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, true>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+    else
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, false>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
@@ -295,8 +470,23 @@ __global__ __launch_bounds__(256) void ba_expand_jacobian_kernel(int n_obs, cons
     if (Jc) for (int k = 0; k < 12; ++k) Jc[(size_t)i * 12 + k] = jc[k];
     if (Jp) for (int k = 0; k < 6; ++k) Jp[(size_t)i * 6 + k] = jp[k];
 }
-int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st) {
-    if (n_obs > 0) hipLaunchKernelGGL(ba_expand_jacobian_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, st, n_obs, J8, omask, Jc, Jp);
+// (the general form: camera blocks from Jc12, J8 = {0, 0, Jp}; the masks applied as everywhere)
+__global__ __launch_bounds__(256) void ba_expand_jacobian_gen_kernel(int n_obs, const double* __restrict__ J8,
+                                                                     const unsigned char* __restrict__ omask,
+                                                                     const double* __restrict__ Jc12, double* __restrict__ Jc,
+                                                                     double* __restrict__ Jp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_obs) return;
+    double jc[12], jp[6];
+    load_jc_jp<true>(J8, omask, i, jc, jp, Jc12);
+    if (Jc) for (int k = 0; k < 12; ++k) Jc[(size_t)i * 12 + k] = jc[k];
+    if (Jp) for (int k = 0; k < 6; ++k) Jp[(size_t)i * 6 + k] = jp[k];
+}
+int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st,
+                           const double* Jc12) {
+    if (n_obs > 0 && Jc12)
+        hipLaunchKernelGGL(ba_expand_jacobian_gen_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, st, n_obs, J8, omask, Jc12, Jc, Jp);
+    else if (n_obs > 0) hipLaunchKernelGGL(ba_expand_jacobian_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, st, n_obs, J8, omask, Jc, Jp);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }

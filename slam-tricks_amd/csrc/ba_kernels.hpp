@@ -66,11 +66,26 @@ __device__ inline void load_jc_jp(const double* __restrict__ J8, const unsigned 
 
 size_t lin_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac);
 int launch_linearize(const LinArgs& a, bool with_jac, int grid, hipStream_t st);
+// with a per-observation robust loss (stba_ba_set_loss): the table in the engine's observation order, and where the corrected camera
+// blocks go -- the kernel writes the general form J8 = {0, 0, Jp'}, Jc12 = Jc' (ba_linearize_robust_kernel, ba_kernels.hip)
+constexpr int LIN_ROBUST_THREADS = 512;        // observations per workgroup tile of the robust kernel
+struct LinLoss {
+    const int* kind;                 // [n_obs] STBA_LOSS_*
+    const double* a;                 // [n_obs]
+    const double* b;                 // [n_obs]
+    const double* scale;             // [n_obs]
+    double* Jc12;                    // [n_obs][12]
+};
+size_t lin_robust_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac);
+bool lin_robust_cams_in_lds(int n_cams);
+int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st);
 int launch_sum_partials(const double* partial, int n, int stride, int K, double* out, hipStream_t st);
 int launch_absmax(const double* v, size_t n, const double* v2, size_t n2, double* out, double* partial, int n_partial,
                   hipStream_t st);
 // (J8: compact Jacobian [n_obs][8]; omask: per-observation mask byte of constant dofs / landmarks, or null)
-int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st);
+// (Jc12: the camera blocks of the general form -- host-linearised factors, robust losses -- or null)
+int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st,
+                           const double* Jc12 = nullptr);
 // (gpmax_partial: optional, one max |gp| per workgroup of 256 landmarks, finished by launch_linear_finish)
 int point_blocks_grid(int n_pts);      // workgroups of the landmark-block kernel = entries of its gpmax partial array
 int launch_point_blocks(int n_pts, const int* pt_start, const double* J8, const unsigned char* omask, const double2* r,

@@ -117,6 +117,11 @@ struct stba_ba {
     void* hl_user = nullptr;
     double* Jc12 = nullptr;          // [n_obs][12]
     std::vector<double> hl_cams, hl_pts, hl_r, hl_jc, hl_jp, hl_stage, hl_cost_stage;   // host staging (caller order | engine order)
+    // per-observation robust losses (stba_ba_set_loss): kind (STBA_LOSS_*), a, b, scale, each [n_obs] in the engine's
+    // order; all null: no table.  With one, ba_linearize_robust_kernel writes the corrected r', J8 = {0, 0, Jp'} and Jc12 = Jc', and
+    // everything behind the linearisation runs its general form on them, as for host-linearised factors
+    int* loss_kind = nullptr;
+    double *loss_a = nullptr, *loss_b = nullptr, *loss_scale = nullptr;
     unsigned char* omask = nullptr;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
     double *Hpp6 = nullptr, *gp = nullptr, *Hinv6 = nullptr, *dp = nullptr, *scale_p = nullptr;
     double *Hcc = nullptr, *gc = nullptr, *cam_partial = nullptr, *dc = nullptr, *scale_c = nullptr;
@@ -204,7 +209,7 @@ static void ba_free(stba_ba* b) {
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
     F(b->pt_start); F(b->cam_perm); F(b->chunk_begin); F(b->chunk_end); F(b->cam_chunk_start); F(b->cam_fixed);
-    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->dp); F(b->scale_p);
+    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->dp); F(b->scale_p);
     F(b->Hcc); F(b->gc); F(b->cam_partial); F(b->dc); F(b->scale_c); F(b->Sbuf); F(b->Spack); F(b->pk_blocks); F(b->dxc); F(b->dxp);
     F(b->task_cam); F(b->cam_start); F(b->task_col_lo); F(b->task_col_hi); F(b->row_col_ptr); F(b->row_cols);
     F(b->task_p_lo); F(b->task_p_hi); F(b->row_task_ptr); F(b->row_tasks); F(b->task_part_off); F(b->schur_part);
@@ -277,17 +282,28 @@ static int ba_host_linearize(stba_ba* b, int which, bool with_jac) {
     return STBA_OK;
 }
 
+// the camera blocks of the GENERAL form (J8 = {0, 0, Jp}, Jc12 = the 2 x 6 blocks), which every kernel behind the linearisation
+// takes in its GEN instantiation: host-linearised factors and engines with a loss table; null: the compact record
+static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind) ? b->Jc12 : nullptr; }
+
+// THE linearisation at parameter buffer `which`: the host's callback, the robust kernel (a loss table is set) or the lossless
+// kernel.  The cost partials (sum r^2, or sum rho with a table) are left in cost_partial; with_jac: r, J8 (and Jc12) are stored
+static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
+    if (b->hl_fn) return ba_host_linearize(b, which, with_jac);
+    const LinArgs a = lin_args(b, which, with_jac);
+    if (b->loss_kind) return launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12}, with_jac, b->lin_grid, b->st);
+    return launch_linearize(a, with_jac, b->lin_grid, b->st);
+}
+
 // residuals + Jacobians at parameter buffer `which`; sum r^2 -> *cost2_dev
 static int ba_linearize(stba_ba* b, int which, double* cost2_dev) {
-    if (b->hl_fn) STBA_TRY(ba_host_linearize(b, which, true));
-    else STBA_TRY(launch_linearize(lin_args(b, which, true), true, b->lin_grid, b->st));
+    STBA_TRY(ba_linearize_dispatch(b, which, true));
     return launch_sum_partials(b->cost_partial, b->lin_grid, 1, 1, cost2_dev, b->st);
 }
 
 // residual-only kernel (nothing stored): sum r^2 -> *cost2_dev
 static int ba_cost_only(stba_ba* b, int which, double* cost2_dev) {
-    if (b->hl_fn) STBA_TRY(ba_host_linearize(b, which, false));
-    else STBA_TRY(launch_linearize(lin_args(b, which, false), false, b->lin_grid, b->st));
+    STBA_TRY(ba_linearize_dispatch(b, which, false));
     return launch_sum_partials(b->cost_partial, b->lin_grid, 1, 1, cost2_dev, b->st);
 }
 
@@ -300,12 +316,11 @@ static int ba_normal_blocks(stba_ba* b) {
 // residuals + Jacobians of the LM loop: the cost partial sums stay in cost_partial and are added up by
 // ba_fill_scalar_slots behind the landmark blocks (one launch less than ba_linearize)
 static int ba_linearize_lm(stba_ba* b, int which) {
-    if (b->hl_fn) return ba_host_linearize(b, which, true);
-    return launch_linearize(lin_args(b, which, true), true, b->lin_grid, b->st);
+    return ba_linearize_dispatch(b, which, true);
 }
 static int ba_camera_blocks(stba_ba* b) {
     return launch_camera_blocks(b->nc, b->n_chunks, b->chunk_begin, b->chunk_end, b->cam_chunk_start, b->cam_perm,
-                                b->J8, b->omask, b->hl_fn ? b->Jc12 : nullptr, b->r, b->cam_partial, b->Hcc, b->gc, b->st);
+                                b->J8, b->omask, ba_general_jc(b), b->r, b->cam_partial, b->Hcc, b->gc, b->st);
 }
 
 struct Damping {
@@ -424,7 +439,7 @@ static int ba_schur_step(stba_ba* b) {
         da.n_cams = b->nc; da.n_chunks = b->n_chunks;
         da.chunk_begin = b->chunk_begin; da.chunk_end = b->chunk_end; da.cam_chunk_start = b->cam_chunk_start; da.cam_perm = b->cam_perm;
         da.obs_cam = b->obs_cam; da.obs_pt = b->obs_pt;
-        da.J8 = b->J8; da.omask = b->omask; da.Jc12 = b->hl_fn ? b->Jc12 : nullptr; da.r = b->r; da.Hinv6 = b->Hinv6; da.gp = b->gp;
+        da.J8 = b->J8; da.omask = b->omask; da.Jc12 = ba_general_jc(b); da.r = b->r; da.Hinv6 = b->Hinv6; da.gp = b->gp;
         da.Y = b->Y; da.ldy = b->ldy; da.kcols = b->ykcols; da.partial = b->yv; da.ws = b->yws; da.dup_run = b->dup_run;
         da.S = b->S(); da.lda = b->lda; da.rhs = b->rhs(); da.Hcc = b->Hcc; da.gc = b->gc;
         return launch_schur_dense(da, b->st);
@@ -432,7 +447,7 @@ static int ba_schur_step(stba_ba* b) {
     SchurArgs sa;
     sa.task_cam = b->task_cam; sa.cam_start = b->cam_start; sa.task_col_lo = b->task_col_lo; sa.task_col_hi = b->task_col_hi;
     sa.row_col_ptr = b->row_col_ptr; sa.row_cols = b->row_cols; sa.max_cols = b->max_cols; sa.cam_perm = b->cam_perm;
-    sa.J8 = b->J8; sa.omask = b->omask; sa.Jc12 = b->hl_fn ? b->Jc12 : nullptr; sa.r = b->r; sa.Hinv6 = b->Hinv6; sa.gp = b->gp;
+    sa.J8 = b->J8; sa.omask = b->omask; sa.Jc12 = ba_general_jc(b); sa.r = b->r; sa.Hinv6 = b->Hinv6; sa.gp = b->gp;
     sa.S = b->S(); sa.lda = b->lda; sa.rhs = b->rhs(); sa.Hcc = b->Hcc; sa.gc = b->gc;
     sa.obs_pt = b->obs_pt; sa.pair_begin = b->pair_begin; sa.pair_end = b->pair_end; sa.pair_rec = b->pair_rec;
     sa.task_vs_ptr = b->task_vs_ptr; sa.vs_first = b->vs_first; sa.mode = b->schur_plan_mode;
@@ -525,7 +540,7 @@ static int ba_backsub_trial(stba_ba* b) {
     BacksubUpdate up{b->pts[b->cur], b->pt_fixed, b->dp, b->pts[b->cur ^ 1], b->upd_partial_p,
                      b->nc, b->cams[b->cur], b->cam_fixed, b->ex_gc(), b->dc, b->cams[b->cur ^ 1], b->upd_partial_c};
     if (b->iterative) { up.r_model = b->r; up.obs_pt = b->obs_pt; }      // (an inexact step: m = -(J d)^T (r + J d / 2))
-    return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, &up, b->hl_fn ? b->Jc12 : nullptr);
+    return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, &up, ba_general_jc(b));
 }
 
 // trial point: both manifold updates (one launch), the residual-only kernel, and ONE launch that finishes every sum of
@@ -546,8 +561,7 @@ static int ba_trial(stba_ba* b, double* host_out, bool updated = false, bool wit
     static_assert(TS_COST2 == 0 && TS_STEP2 == 1 && TS_X2 == 2 && TS_MODEL == 3 && TS_TIMEOUT == 4 && TS_CAM == 5 && TS_COUNT == 8 &&
                   TS_SPEC_COST2 == 8 && TS_LIN_COST2 == 9 && TS_LIN_GMAX == 10 && TS_BLOCK == 11, "trial_finish_kernel writes this layout");
     if (with_jac) STBA_TRY(ba_linearize_lm(b, nxt));
-    else if (b->hl_fn) STBA_TRY(ba_host_linearize(b, nxt, false));
-    else STBA_TRY(launch_linearize(lin_args(b, nxt, false), false, b->lin_grid, b->st));
+    else STBA_TRY(ba_linearize_dispatch(b, nxt, false));
     STBA_TRY(launch_trial_finish(b->cost_partial, b->lin_grid, b->upd_partial_p, b->np > 0 ? pb : 0, b->upd_partial_c, cb, b->flag,
                                  b->ex_scalar() + SC_COST2, b->ex_scalar() + SC_GPMAX0, b->world, b->ex_gc(), b->n, b->trial,
                                  b->ar ? nullptr : host_out, host_seq, b->st));
@@ -624,18 +638,18 @@ static int ba_pcg_alloc(stba_ba* b) {
 static int ba_is_landmark_pass(stba_ba* b, const double* x, const double* gp, PcgState* skip) {
     BacksubUpdate up{};
     up.skip = skip ? &skip->done : nullptr;
-    return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, gp, x, b->dxp, b->st, &up, b->hl_fn ? b->Jc12 : nullptr);
+    return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, gp, x, b->dxp, b->st, &up, ba_general_jc(b));
 }
 // camera pass: y = (Hcc + D) p + W zp (IS_FINAL_APPLY, p^T y partials into pq_part) | y = -gc - W zp (IS_FINAL_RHS)
 static int ba_is_camera_pass(stba_ba* b, int mode, const double* p, double* y, double* pq_part, const PcgState* skip) {
-    STBA_TRY(launch_is_cam_gather(b->n_chunks, b->chunk_begin, b->chunk_end, b->cam_perm, b->obs_pt, b->J8, b->omask, b->hl_fn ? b->Jc12 : nullptr,
+    STBA_TRY(launch_is_cam_gather(b->n_chunks, b->chunk_begin, b->chunk_end, b->cam_perm, b->obs_pt, b->J8, b->omask, ba_general_jc(b),
                                   b->dxp, skip, b->cam_partial, b->st));
     return launch_is_cam_final(b->nc, mode, b->cam_chunk_start, b->cam_partial, b->Hcc, b->dc, b->gc, b->cam_fixed, p, y, pq_part, skip, b->st);
 }
 static int ba_is_precond(stba_ba* b, int kind) {
     if (kind == STBA_PRECOND_SCHUR_JACOBI)
         STBA_TRY(launch_is_sj_gather(b->n_chunks, b->no, b->chunk_begin, b->chunk_end, b->cam_perm, b->obs_cam, b->obs_pt, b->J8, b->omask,
-                                     b->hl_fn ? b->Jc12 : nullptr, b->Hinv6, b->pcg_sj, b->st));
+                                     ba_general_jc(b), b->Hinv6, b->pcg_sj, b->st));
     return launch_is_precond(b->nc, kind, b->Hcc, b->dc, b->scale_c, b->cam_fixed, b->cam_chunk_start, b->pcg_sj, b->pcg_minv, b->st);
 }
 // reduced right-hand side rhs = -(gc - W V^-1 gp): the landmark pass with x = 0, then the camera pass
@@ -1157,11 +1171,11 @@ static int ba_dogleg_alloc(stba_ba* b) {
 static int ba_dogleg_gauss_newton(stba_ba* b, const Damping& dm) {
     STBA_TRY(chol_factor_solve_dev(b->S(), b->lda, b->n, b->dxc, b->flag, b->st));
     STBA_TRY(launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, nullptr,
-                            b->hl_fn ? b->Jc12 : nullptr));
+                            ba_general_jc(b)));
     DoglegArgs a;
     a.n_cams = b->nc; a.n_pts = b->np;
     a.pt_start = b->pt_start; a.obs_cam = b->obs_cam; a.obs_pt = b->obs_pt;
-    a.J8 = b->J8; a.omask = b->omask; a.Jc12 = b->hl_fn ? b->Jc12 : nullptr;
+    a.J8 = b->J8; a.omask = b->omask; a.Jc12 = ba_general_jc(b);
     a.cam_fixed = b->cam_fixed; a.pt_fixed = b->pt_fixed;
     a.hc = b->ex_diag(); a.gc = b->ex_gc(); a.scale_c = b->scale_c;
     a.Hpp6 = b->Hpp6; a.gp = b->gp; a.scale_p = b->scale_p;
@@ -1672,9 +1686,83 @@ int stba_ba_get_params(stba_ba* b, double* cams, double* pts) {
 int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (fn && b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has inner iterations (device residuals only)");
+    if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
     if (fn && !b->Jc12) STBA_TRY(dev_alloc(&b->Jc12, (size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    return STBA_OK;
+}
+
+// the per-observation loss table: checked on the host BEFORE anything is replaced (a refused call leaves the engine with the table it
+// had), permuted into the engine's landmark-major order, uploaded into NEW arrays that are swapped in; kind == NULL releases the table
+int stba_ba_set_loss(stba_ba* b, const int* kind, const double* a, const double* lb, const double* scale) {
+    const char* who = "stba_ba_set_loss";
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
+    int* k_new = nullptr;
+    double *a_new = nullptr, *b_new = nullptr, *s_new = nullptr, *jc_new = nullptr;
+    if (kind) {
+        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has a host lineariser (losses need device residuals; not supported together)");
+        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has inner iterations (inner iterations with losses are not supported)");
+        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and losses run on one rank only");
+        const size_t m = (size_t)b->no;
+        std::vector<double> ha(m, 1.0), hb(m, 1.0), hs(m, 1.0);
+        for (size_t e = 0; e < m; ++e) {
+            const int kd = kind[e];
+            std::string why;
+            if (kd < STBA_LOSS_TRIVIAL || kd > STBA_LOSS_TUKEY) why = "unknown loss kind " + std::to_string(kd);
+            else if (kd != STBA_LOSS_TRIVIAL && (!a || !std::isfinite(a[e]) || !(a[e] > 0.0))) why = "the loss parameter a must be finite and positive";
+            else if (kd == STBA_LOSS_TOLERANT && (!lb || !std::isfinite(lb[e]) || !(lb[e] > 0.0))) why = "the loss parameter b must be finite and positive";
+            else if (scale && (!std::isfinite(scale[e]) || !(scale[e] >= 0.0))) why = "the loss scale must be finite and not negative";
+            if (!why.empty()) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": observation " + std::to_string(e) + ": " + why);
+            if (kd != STBA_LOSS_TRIVIAL) ha[e] = a[e];
+            if (kd == STBA_LOSS_TOLERANT) hb[e] = lb[e];
+            if (scale) hs[e] = scale[e];
+        }
+        std::vector<int> pk(m);
+        std::vector<double> pa(m), pb(m), ps(m);
+        for (size_t p = 0; p < m; ++p) {                    // the engine's order: b->perm = position -> the caller's index
+            const size_t i = (size_t)b->perm[p];
+            pk[p] = kind[i]; pa[p] = ha[i]; pb[p] = hb[i]; ps[p] = hs[i];
+        }
+        auto F = [](void* p) { if (p) (void)hipFree(p); };
+        const size_t ma = std::max<size_t>(m, 1);
+        int rc = dev_alloc(&k_new, ma);
+        if (rc == STBA_OK) rc = dev_alloc(&a_new, ma);
+        if (rc == STBA_OK) rc = dev_alloc(&b_new, ma);
+        if (rc == STBA_OK) rc = dev_alloc(&s_new, ma);
+        if (rc == STBA_OK && !b->Jc12) rc = dev_alloc(&jc_new, ma * 12);
+        if (rc == STBA_OK && m > 0 &&
+            (hipMemcpyAsync(k_new, pk.data(), m * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(a_new, pa.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(b_new, pb.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(s_new, ps.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipStreamSynchronize(b->st) != hipSuccess))
+            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
+        if (rc != STBA_OK) { F(k_new); F(a_new); F(b_new); F(s_new); F(jc_new); return rc; }
+    }
+    // (nothing of the engine may still be reading the old table or what was linearised with it)
+    STBA_HIP(hipStreamSynchronize(b->st));
+    for (void* p : {(void*)b->loss_kind, (void*)b->loss_a, (void*)b->loss_b, (void*)b->loss_scale}) if (p) (void)hipFree(p);
+    b->loss_kind = k_new; b->loss_a = a_new; b->loss_b = b_new; b->loss_scale = s_new;
+    if (jc_new) b->Jc12 = jc_new;
+    if (!kind && !b->hl_fn && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }      // (96 B per observation nobody reads any more)
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    return STBA_OK;
+}
+
+int stba_ba_has_loss(const stba_ba* b, int* has) {
+    if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_loss: null argument");
+    *has = b->loss_kind ? 1 : 0;
+    return STBA_OK;
+}
+
+int stba_ba_loss_kernel_geometry(const stba_ba* b, int* tile_observations, int* cameras_in_lds, int* max_cameras_in_lds) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_loss_kernel_geometry: null engine");
+    if (tile_observations) *tile_observations = LIN_ROBUST_THREADS;
+    if (cameras_in_lds) *cameras_in_lds = lin_robust_cams_in_lds(b->nc) ? 1 : 0;
+    if (max_cameras_in_lds) *max_cameras_in_lds = (int)(((size_t)LIN_MAX_LDS - lin_robust_lds_bytes(0, true, true)) / (7 * sizeof(double)));
     return STBA_OK;
 }
 
@@ -1684,6 +1772,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine uses DOGLEG, which runs on one rank only");
     if (b && b->inner_on && (fn || world_size > 1))
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has inner iterations, which run on one rank only");
+    if (b && b->loss_kind && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has a loss table, and losses run on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -1716,7 +1806,7 @@ int stba_ba_evaluate(stba_ba* b, double* cost, double* r, double* Jc, double* Jp
     if (Jc || Jp) {
         if (Jc) STBA_TRY(dev_alloc(&djc, no * 12));
         if (Jp) STBA_TRY(dev_alloc(&djp, no * 6));
-        STBA_TRY(launch_expand_jacobian(b->no, b->J8, b->omask, djc, djp, b->st));
+        STBA_TRY(launch_expand_jacobian(b->no, b->J8, b->omask, djc, djp, b->st, ba_general_jc(b)));
         if (Jc) { tjc.resize(no * 12); STBA_TRY(download(tjc.data(), djc, no * 12, b->st)); }
         if (Jp) { tjp.resize(no * 6); STBA_TRY(download(tjp.data(), djp, no * 6, b->st)); }
     }
@@ -1816,7 +1906,7 @@ int stba_ba_solve_reduced(stba_ba* b, double* dxc) {
 int stba_ba_back_substitute(stba_ba* b, double* dxp) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (!b->have_dxc) return fail(STBA_ERR_STATE, "stba_ba_back_substitute needs stba_ba_solve_reduced first");
-    STBA_TRY(launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, nullptr, b->hl_fn ? b->Jc12 : nullptr));
+    STBA_TRY(launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, nullptr, ba_general_jc(b)));
     if (dxp) STBA_TRY(download(dxp, b->dxp, (size_t)b->np * 3, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     b->have_dxp = true;
@@ -1885,6 +1975,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: the tolerance must be finite and >= 0");
     if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: inner iterations run on one rank only (an all-reduce hook is set)");
     if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: not with a host lineariser");
+    if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has a loss table (inner iterations with losses are not supported)");
     const int nc = b->nc, np = b->np, no = b->no;
     // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
     std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
@@ -1975,6 +2066,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
 int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int* iterations_per_block) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (b->ar || b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: one rank, device residuals only");
+    if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has a loss table (inner iterations with losses are not supported)");
     const bool was_on = b->inner_on;
     if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
     STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
@@ -2031,10 +2123,9 @@ int stba_ba_triangulate(stba_ba* b, int max_iter) {
 
 int stba_ba_time_linearize(stba_ba* b, int reps, double* ms_avg) {
     if (!b || reps <= 0 || !ms_avg) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    LinArgs a = lin_args(b, b->cur, true);
-    STBA_TRY(launch_linearize(a, true, b->lin_grid, b->st));   // warm
+    STBA_TRY(ba_linearize_dispatch(b, b->cur, true));   // warm
     STBA_HIP(hipEventRecord(b->ev[EV_LIN], b->st));
-    for (int k = 0; k < reps; ++k) STBA_TRY(launch_linearize(a, true, b->lin_grid, b->st));
+    for (int k = 0; k < reps; ++k) STBA_TRY(ba_linearize_dispatch(b, b->cur, true));
     STBA_HIP(hipEventRecord(b->ev[EV_LIN_END], b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     float ms = 0.f;
@@ -2078,7 +2169,7 @@ int stba_ba_covariance_compute(stba_ba* b, double min_rcond, double* rcond_out) 
     STBA_TRY(ba_cov_build(b));
     BaCovInputs in;
     in.nc = b->nc; in.np = b->np; in.no = b->no; in.n = b->n; in.lda = b->lda; in.st = b->st;
-    in.pt_start = b->pt_start; in.obs_cam = b->obs_cam; in.J8 = b->J8; in.Jc12 = b->hl_fn ? b->Jc12 : nullptr;
+    in.pt_start = b->pt_start; in.obs_cam = b->obs_cam; in.J8 = b->J8; in.Jc12 = ba_general_jc(b);
     in.omask = b->omask; in.cam_fixed = b->cam_fixed; in.pt_fixed = b->pt_fixed;
     in.Hpp6 = b->Hpp6; in.Hinv6 = b->Hinv6; in.S = b->S();
     return cov_compute(in, min_rcond, &b->cov, rcond_out);
