@@ -708,6 +708,43 @@ int stba_ba_set_loss(stba_ba* ba, const int* kind, const double* a, const double
 int stba_ba_has_loss(const stba_ba* ba, int* has);
 int stba_ba_loss_kernel_geometry(const stba_ba* ba, int* tile_observations, int* cameras_in_lds, int* max_cameras_in_lds);
 
+/* ================================ bundle adjustment: per-observation information matrices ================================ */
+/* A 2 x 2 square-root information W_i per observation (row-major; the identity where none is given), the pose graph's semantics
+ * above restated for BA: the cost is 1/2 sum_i rho_i(s_i) with s_i = |W_i r_i|^2 = r_i^T Omega_i r_i, Omega_i = W_i^T W_i.
+ * Whitening comes FIRST -- r <- W r, Jc <- W Jc, Jp <- W Jp -- and Ceres' corrector then runs on the whitened triple if the
+ * observation has a loss (stba_ba_set_loss; the two combine freely, in either order, and each is removed on its own).  The kernel
+ * that applies the losses does the whitening (its INFO form) and writes the general Jacobian form, so:
+ *   stba_ba_evaluate              hands back the WHITENED (and corrected) r, Jc, Jp and the cost above;
+ *   stba_ba_solve / _lm_iterations  minimise that cost (LM or DOGLEG, both dense Schur forms, ITERATIVE_SCHUR);
+ *   stba_ba_covariance_compute    gives (J^T Omega J)^-1, with losses (J'^T J')^-1;
+ *   stba_ba_triangulate           STAYS the unweighted per-landmark refinement (identity weights, no loss), as it does with losses.
+ *   stba_ba_set_information       information[n_obs*4]: a symmetric positive definite 2 x 2 per observation in the CALLER's observation
+ *                      order; the lower triangle (a, b, c) = ([0], [2], [3]) is factored on the host, Omega = L L^T, W = L^T (the
+ *                      upper off-diagonal entry [1] must be finite and is otherwise IGNORED: a matrix that is not symmetric is
+ *                      taken for the symmetric one of its lower triangle, without a message):
+ *                      l11 = sqrt(a), l21 = b / l11, l22 = sqrt(c - b^2 / a), the pivot c - b^2 / a formed with error-free (FMA)
+ *                      products directly from a, b, c, so that every entry of W is within 4 eps (eps = 2^-52) of the exact factor of
+ *                      the matrix given, up to cond(Omega) = 1e12.  A pivot that is not positive or an entry that is not finite:
+ *                      STBA_ERR_NOT_POSITIVE_DEFINITE, stba_last_error() names the smallest such observation, the old weights stay.
+ *   stba_ba_set_sqrt_information   sqrt_information[n_obs*4]: any finite W (it need not be triangular or symmetric); an entry that
+ *                      is not finite: STBA_ERR_INVALID_ARGUMENT, the observation named likewise.
+ *                      NULL to either setter goes back to the identity and releases the array: an engine that then has no loss table
+ *                      either is bit for bit one that never had weights or losses (it runs the lossless kernels).  An array whose
+ *                      every W is exactly the identity (for the information form: every factor) is taken the same way: no array is
+ *                      held and stba_ba_has_information reports 0.  An observation
+ *                      whose W is exactly the identity is not whitened: without a loss (or TRIVIAL with scale 1) what stba_ba_evaluate
+ *                      returns for it compares == with the lossless engine's.
+ *   stba_ba_has_information   *has = 1 while the engine holds weights.
+ *   stba_ba_get_sqrt_information   out[n_obs*4]: the W the engine holds, in the caller's order; identity rows if it holds none.
+ * A setter that succeeds invalidates the current linearisation and releases a held covariance.  Refused with
+ * STBA_ERR_INVALID_ARGUMENT, the state untouched, in both orders: weights on an engine with a host lineariser (the callback's
+ * factors whiten themselves), with inner iterations, or with an all-reduce hook / communicator / world_size > 1 (and those setters on
+ * an engine with weights).  STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_information(stba_ba* ba, const double* information);            /* [n_obs*4], caller's observation order, or NULL */
+int stba_ba_set_sqrt_information(stba_ba* ba, const double* sqrt_information);  /* [n_obs*4], caller's observation order, or NULL */
+int stba_ba_has_information(const stba_ba* ba, int* has);
+int stba_ba_get_sqrt_information(stba_ba* ba, double* out);                     /* [n_obs*4] */
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

@@ -53,6 +53,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <typeindex>
 #include <typeinfo>
 #include <cstdint>
@@ -481,9 +482,20 @@ public:
 class ReprojectionFactor : public SizedCostFunction<2, 4, 3, 3> {
 public:
     ReprojectionFactor(double fx, double fy) : fx_(fx), fy_(fy) {}
+    // sqrt_information: W, 2 x 2 row-major -- the factor becomes r = W (proj(R^T (L - t)) - feature), its cost 1/2 r^T W^T W r.  The
+    // factor whitens itself (operator() and, through the Jets, Evaluate's Jacobians), so every host route sees the weighted factor;
+    // on "gpu-ba" the W of all blocks go to stba_ba_set_sqrt_information
+    // (a template over the pointer type so that ReprojectionFactor(0, 0) stays the (double, double) constructor: literal zeros deduce
+    // int, which is no pointer)
+    template <class P, class = typename std::enable_if<std::is_pointer<P>::value && std::is_convertible<P, const double*>::value>::type>
+    ReprojectionFactor(P feature, const double* sqrt_information) : fx_(feature[0]), fy_(feature[1]), has_w_(true) {
+        std::memcpy(w_, sqrt_information, sizeof w_);
+    }
     static ReprojectionFactor* Create(const double* feature) { return new ReprojectionFactor(feature[0], feature[1]); }
+    static ReprojectionFactor* Create(const double* feature, const double* sqrt_information) { return new ReprojectionFactor(feature, sqrt_information); }
     double fx() const { return fx_; }
     double fy() const { return fy_; }
+    const double* sqrt_information() const { return has_w_ ? w_ : nullptr; }      // nullptr: made without one (identity)
     template <typename T>
     bool operator()(const T* q, const T* t, const T* L, T* r) const {
         // conj(q) * (L - t) with Eigen's v + 2w(u x v) + 2 u x (u x v), u = -q.xyz
@@ -495,6 +507,11 @@ public:
         const T z = v2 + w * a2 + (u0 * a1 - u1 * a0);
         r[0] = x / z - T(fx_);
         r[1] = y / z - T(fy_);
+        if (has_w_) {
+            const T e0 = r[0], e1 = r[1];
+            r[0] = T(w_[0]) * e0 + T(w_[1]) * e1;
+            r[1] = T(w_[2]) * e0 + T(w_[3]) * e1;
+        }
         return true;
     }
     bool Evaluate(double const* const* p, double* residuals, double** jacobians) const override {
@@ -514,6 +531,8 @@ public:
     }
 private:
     double fx_, fy_;
+    bool has_w_ = false;
+    double w_[4] = {1.0, 0.0, 0.0, 1.0};
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1144,6 +1163,9 @@ struct BaLayout {
     std::vector<int> pt_block;               // per landmark
     std::vector<int> obs_cam, obs_pt;
     std::vector<double> feat;
+    // [n_obs][4], the built-in factors' square-root information as stba_ba_set_sqrt_information takes it (the identity for a factor
+    // made without one), gathered next to feat; EMPTY if no factor has one
+    std::vector<double> sqrt_info;
     std::vector<unsigned char> user;         // per residual block: 1 = a user cost function taken over (0: the built-in factor)
     size_t n_user = 0;
 };
@@ -1193,6 +1215,7 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
     // ---- structure: one pass, flat tables (block index -> camera / landmark)
     std::vector<int> cam_of_rot(blk.size(), -1), cam_of_pos(blk.size(), -1), pt_of(blk.size(), -1);
     L->obs_cam.resize(nr); L->obs_pt.resize(nr); L->feat.assign(2 * nr, 0.0); L->user.assign(nr, 0); L->n_user = 0;
+    L->sqrt_info.clear();
     const std::type_info* last_type = nullptr;
     bool last_builtin = false;
     std::vector<std::pair<const std::type_info*, const CostFunction*>> first_of_type;
@@ -1208,7 +1231,16 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
                 for (auto& ft : first_of_type) seen = seen || (*ft.first == ti);
                 if (!seen) first_of_type.emplace_back(&ti, last_builtin ? nullptr : r.cost);
             }
-            if (last_builtin) { auto* f = static_cast<const ReprojectionFactor*>(r.cost); L->feat[2 * k] = f->fx(); L->feat[2 * k + 1] = f->fy(); }
+            if (last_builtin) {
+                auto* f = static_cast<const ReprojectionFactor*>(r.cost); L->feat[2 * k] = f->fx(); L->feat[2 * k + 1] = f->fy();
+                if (const double* w = f->sqrt_information()) {
+                    if (L->sqrt_info.empty()) {                         // the first weighted factor: the identity for every other block
+                        L->sqrt_info.assign(4 * nr, 0.0);
+                        for (size_t i = 0; i < nr; ++i) L->sqrt_info[4 * i] = L->sqrt_info[4 * i + 3] = 1.0;
+                    }
+                    std::memcpy(&L->sqrt_info[4 * k], w, 4 * sizeof(double));
+                }
+            }
             else { L->user[k] = 1; ++L->n_user; }
         }
         const int b0 = r.blocks[0], b1 = r.blocks[1], b2 = r.blocks[2];
@@ -1456,6 +1488,12 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     }
     lap(&sum->phases.engine_create);
     if (rc != STBA_OK) { sum->termination_type = FAILURE; sum->message = std::string("stba_ba_create: ") + create_error; return false; }
+    // (weighted ReprojectionFactors; with host Jacobians the factors whiten themselves)
+    if (!host_jacobians && !L.sqrt_info.empty() && (rc = stba_ba_set_sqrt_information(sync.ba, L.sqrt_info.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_sqrt_information: ") + stba_last_error();
+        stba_ba_destroy(sync.ba);
+        return false;
+    }
     if (!L.loss_kind.empty() && (rc = stba_ba_set_loss(sync.ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
         sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_loss: ") + stba_last_error();
         stba_ba_destroy(sync.ba);
@@ -1861,6 +1899,8 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         if (!ba || (L.n_user && !DetectBaBlocks(*problem, &L, options.num_threads)))
             why = "inner iterations are implemented on the gpu-ba path only: this problem's cost functions are not the reprojection factor "
                   "(gpu-ba-hostjac)";
+        else if (!L.sqrt_info.empty())
+            why = "inner iterations with weighted ReprojectionFactors (sqrt_information) are not implemented";
         else if (!MakeInnerGroups(options, *problem, L, &inner, &why)) {}
         summary->phases.recognise += WallSeconds() - t0;
         if (!why.empty()) {
@@ -2144,6 +2184,8 @@ private:
                            pt_fixed.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_ba_create: ") + stba_last_error());
         struct Destroy { stba_ba* b; ~Destroy() { stba_ba_destroy(b); } } destroy{ba};
+        if (!host && !L.sqrt_info.empty() && stba_ba_set_sqrt_information(ba, L.sqrt_info.data()) != STBA_OK)
+            return Fail(std::string("stba_ba_set_sqrt_information: ") + stba_last_error());
         if (!host && !L.loss_kind.empty() && stba_ba_set_loss(ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
             return Fail(std::string("stba_ba_set_loss: ") + stba_last_error());
         BaHostCtx hctx{p, &L, options_.num_threads};

@@ -23,10 +23,12 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iosfwd>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <typeinfo>
 #include <utility>
 #include <vector>
@@ -117,6 +119,11 @@ struct Edge {
     virtual void computeError() = 0;
     virtual void error_raw(double* out) const = 0;
     virtual void measurement_raw(double* out) const = 0;
+    // the edge's information matrix Omega, dimension() x dimension() row-major (the identity unless setInformation said otherwise)
+    virtual void information_raw(double* out) const {
+        const int d = dimension();
+        for (int i = 0; i < d; ++i) for (int j = 0; j < d; ++j) out[i * d + j] = i == j ? 1.0 : 0.0;
+    }
     void setVertex(size_t i, Vertex* v) { if (_vertices.size() <= i) _vertices.resize(i + 1, nullptr); _vertices[i] = v; }
     const std::vector<Vertex*>& vertices() const { return _vertices; }
 protected:
@@ -128,11 +135,16 @@ template <int D, typename E, typename VertexXi, typename VertexXj>
 class BaseBinaryEdge : public Edge {
 public:
     static const int Dimension = D;
-    BaseBinaryEdge() { _vertices.resize(2, nullptr); }
+    BaseBinaryEdge() { _vertices.resize(2, nullptr); set_information(1.0, std::true_type()); }
     int dimension() const override { return D; }
     void setMeasurement(const E& m) { _measurement = m; }
     const E& measurement() const { return _measurement; }
-    template <class M> void setInformation(const M&) {}   // the reference sets identity (test_g2o.h:129)
+    // Omega of the edge, chi2 = rho(e^T Omega e): a number m means m I, anything else is read through m(i, j), i, j < D (Eigen's
+    // spelling).  The reference sets the identity (test_g2o.h:129); optimize() hands the matrices to stba_ba_set_information if one
+    // of them is not the identity
+    template <class M> void setInformation(const M& m) { set_information(m, std::is_arithmetic<M>()); }
+    const double* information() const { return _information; }          // D x D row-major
+    void information_raw(double* out) const override { for (int k = 0; k < D * D; ++k) out[k] = _information[k]; }
     void error_raw(double* out) const override { Traits<E>::get(_error, out); }
     void measurement_raw(double* out) const override { Traits<E>::get(_measurement, out); }
     virtual bool read(istream& is) = 0;
@@ -140,6 +152,14 @@ public:
 protected:
     E _measurement{};
     E _error{};
+private:
+    template <class M> void set_information(const M& m, std::true_type) {
+        for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) _information[i * D + j] = i == j ? (double)m : 0.0;
+    }
+    template <class M> void set_information(const M& m, std::false_type) {
+        for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) _information[i * D + j] = (double)m(i, j);
+    }
+    double _information[D * D];
 };
 
 // ---- solver scaffolding (types only: the engine replaces what they would configure) --------
@@ -188,6 +208,10 @@ public:
         std::vector<int> lkind((size_t)no, STBA_LOSS_TRIVIAL);
         std::vector<double> la((size_t)no, 1.0);
         bool any_kernel = false;
+        // the edges' information matrices as the array of stba_ba_set_information; used only if one of them is not the identity (a graph
+        // that only ever passes the identity calls no setter and runs the lossless kernels)
+        std::vector<double> info((size_t)no * 4);
+        bool any_information = false;
         for (int k = 0; k < no; ++k) {
             Edge* e = _edges[k];
             if (const RobustKernel* rk = e->robustKernel()) {
@@ -202,6 +226,9 @@ public:
             if (a < 0 || b < 0 || cam_of[a] < 0 || pt_of[b] < 0) { _message = "edge does not connect (pose, landmark)"; return 0; }
             oc[k] = cam_of[a]; op[k] = pt_of[b];
             e->measurement_raw(&feat[(size_t)k * 2]);
+            double* om = &info[(size_t)k * 4];
+            e->information_raw(om);
+            if (!(om[0] == 1.0 && om[1] == 0.0 && om[2] == 0.0 && om[3] == 1.0)) any_information = true;
             // EVERY edge must be the reprojection residual (a graph with one edge of another type must not be treated as pure
             // bundle adjustment): one computeError per edge at its current estimates, host work, no device involved
             if (!probe_edge(e, k)) return 0;
@@ -221,6 +248,15 @@ public:
         stba_ba* ba = nullptr;
         if (stba_ba_create(&ba, nc, np, no, c7.data(), p3.data(), oc.data(), op.data(), feat.data(), cfix.data(), pfix.data(), nullptr) != STBA_OK) {
             _message = std::string("stba_ba_create: ") + stba_last_error();
+            return 0;
+        }
+        if (any_information && stba_ba_set_information(ba, info.data()) != STBA_OK) {
+            // (an Omega that is not positive definite or not finite: the engine's message names the row as "observation <index>:", and
+            // the observation's index is the edge's; ba_set_weights in stba_engine.hip carries a note that this text is read here)
+            const std::string why = stba_last_error();
+            const size_t at = why.find("observation ");
+            _message = (at == std::string::npos ? std::string() : "edge " + std::to_string(std::atoi(why.c_str() + at + 12)) + ": ") + why;
+            stba_ba_destroy(ba);
             return 0;
         }
         if (any_kernel && stba_ba_set_loss(ba, lkind.data(), la.data(), nullptr, nullptr) != STBA_OK) {
@@ -251,7 +287,7 @@ public:
                     stba_ba_destroy(ba);
                     return 0;
                 }
-            _chi2 = 2.0 * s.final_cost;   // g2o reports chi^2 = sum r^2 (sum rho with robust kernels), Ceres 1/2 of it
+            _chi2 = 2.0 * s.final_cost;   // g2o reports chi^2 = sum rho(e^T Omega e) (rho the identity without a kernel), Ceres 1/2 of it
             done = s.num_iterations;
             if (_verbose)
                 for (int i = 0; i <= s.num_iterations; ++i)

@@ -84,7 +84,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check",
            "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information",
            "stba_pg_set_loss", "stba_pg_has_loss",
-           "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry"]
+           "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry",
+           "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information"]
 
 
 def lib():
@@ -230,9 +231,12 @@ class BAEngine:
     implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
 
     def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur",
-                 loss=None):
+                 loss=None, information=None, sqrt_information=None):
         """loss: per-observation robust losses as PGEngine takes them -- a kind name, a tuple (kind, a[, b[, scale]]) or a dict of
-        set_loss's arguments"""
+        set_loss's arguments.  information / sqrt_information (one of the two): per-observation 2 x 2 weights, the shapes that
+        set_information takes"""
+        if information is not None and sqrt_information is not None:
+            raise ValueError("BAEngine: give information or sqrt_information, not both")
         self._h = C.c_void_p()
         cams = _f64(cams).reshape(-1, 7)
         pts = _f64(pts).reshape(-1, 3)
@@ -247,6 +251,11 @@ class BAEngine:
             raise ValueError(f"linear_solver must be one of {sorted(LINEAR_SOLVERS)}")
         self.linear_solver = linear_solver
         table = None if loss is None else self._loss_table(loss)
+        weights = None
+        if information is not None:
+            weights = ("stba_ba_set_information", self._weight_array(information, "information"))
+        elif sqrt_information is not None:
+            weights = ("stba_ba_set_sqrt_information", self._weight_array(sqrt_information, "sqrt_information"))
         if linear_solver == "dense_schur":
             _chk(lib().stba_ba_create(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
                                       _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0)), "stba_ba_create")
@@ -254,6 +263,8 @@ class BAEngine:
             o = BACreateOptions(C.sizeof(BACreateOptions), LINEAR_SOLVERS[linear_solver])
             _chk(lib().stba_ba_create_ex(C.byref(self._h), self.nc, self.np_, self.no, _p(cams), _p(pts), _p(oc), _p(op),
                                          _p(of), _p(cf), _p(pf), C.c_void_p(stream or 0), C.byref(o)), "stba_ba_create_ex")
+        if weights is not None:
+            _chk(getattr(lib(), weights[0])(self._h, _p(weights[1])), weights[0])
         if table is not None:
             self._set_loss_table(table)
 
@@ -313,6 +324,53 @@ class BAEngine:
         has = C.c_int()
         _chk(lib().stba_ba_has_loss(self._h, C.byref(has)), "stba_ba_has_loss")
         return bool(has.value)
+
+    # ---- per-observation information matrices
+    def _weight_array(self, w, name):
+        """(n_obs, 4) float64 from a (2, 2) for all observations, an (n_obs, 2, 2), or a scalar / an (n_obs,) array w_i meaning
+        w_i * I (for the information form: g2o's invSigma2)"""
+        w = np.asarray(w, np.float64)
+        if w.ndim == 0:
+            w = np.full(self.no, float(w))
+        if w.ndim == 1:
+            if w.shape != (self.no,):
+                raise ValueError(f"BAEngine: per-observation {name} must be a number or have length {self.no}, got {w.shape}")
+            out = np.zeros((self.no, 4))
+            out[:, 0] = w
+            out[:, 3] = w
+            return out
+        if w.shape == (2, 2):
+            return np.ascontiguousarray(np.broadcast_to(w.reshape(1, 4), (self.no, 4)))
+        if w.shape != (self.no, 2, 2):
+            raise ValueError(f"BAEngine: per-observation {name} must have shape (2, 2) or ({self.no}, 2, 2), got {w.shape}")
+        return np.ascontiguousarray(w.reshape(self.no, 4))
+
+    def set_information(self, information):
+        """per-observation 2 x 2 information matrices Omega_i (symmetric positive definite), in the order given at creation: the
+        cost becomes 1/2 sum rho_i(r_i^T Omega_i r_i).  A (2, 2) for all observations, an (n_obs, 2, 2), or a scalar / an (n_obs,)
+        array w_i meaning w_i * I.  evaluate() then returns the whitened r, Jc, Jp (W_i = L_i^T, Omega_i = L_i L_i^T), covariance()
+        (J^T Omega J)^-1 (include/stba.h).  set_information(None), or weights that are all exactly the identity: no weights, the
+        engine as it was (has_information is False)."""
+        arr = None if information is None else self._weight_array(information, "information")
+        _chk(lib().stba_ba_set_information(self._h, _p(arr)), "stba_ba_set_information")
+
+    def set_sqrt_information(self, sqrt_information):
+        """as set_information, from square-root information matrices W_i (any finite 2 x 2, Omega_i = W_i^T W_i); a scalar or an
+        (n_obs,) array means w_i * I as W.  None: the identity."""
+        arr = None if sqrt_information is None else self._weight_array(sqrt_information, "sqrt_information")
+        _chk(lib().stba_ba_set_sqrt_information(self._h, _p(arr)), "stba_ba_set_sqrt_information")
+
+    @property
+    def has_information(self):
+        has = C.c_int()
+        _chk(lib().stba_ba_has_information(self._h, C.byref(has)), "stba_ba_has_information")
+        return bool(has.value)
+
+    def sqrt_information(self):
+        """(n_obs, 2, 2): the W_i the engine holds, in the order given at creation (identities if it holds none)"""
+        out = np.empty((self.no, 2, 2))
+        _chk(lib().stba_ba_get_sqrt_information(self._h, _p(out)), "stba_ba_get_sqrt_information")
+        return out
 
     def loss_kernel_geometry(self):
         """(observations per workgroup tile of the correcting linearisation kernel, whether this engine's cameras are staged in its

@@ -148,8 +148,13 @@ int launch_linearize(const LinArgs& a, bool with_jac, int grid, hipStream_t st) 
 // written with the very expressions of load_jc_jp<false>: what it stores compares == to the lossless engine's.
 // The tile is LIN_ROBUST_THREADS = 512 observations: 8 + 12 doubles per lane (rows padded to 9 and 13, odd strides) are 88 KB, staged
 // in ONE pass next to the cameras; at 1024 lanes they would not fit into 160 KB, and 8 waves per workgroup leave 256 VGPRs per lane.
+// INFO (stba_ba_set_information / _sqrt_information): the observation's square-root information W (winfo[i], 2 x 2
+// row-major, two 16 B loads per lane) whitens the triple FIRST -- r <- W r, and each of the nine columns of [Jc | Jp] <- W column, in
+// registers -- and s = |W r|^2 is what the loss sees.  A W that is exactly the identity skips the products, so that what such an
+// observation stores is what the kernel without INFO stores.  LOSS = false (weights only) reads no loss table and runs no corrector:
+// <., ., false, true> is the loss-only kernel of 7h, <., ., true, false> whitens only, <., ., true, true> does both.
 // ===========================================================================================
-template <bool CAMS_IN_LDS, bool WITH_JAC>
+template <bool CAMS_IN_LDS, bool WITH_JAC, bool INFO, bool LOSS>
 __global__ __launch_bounds__(LIN_ROBUST_THREADS) void ba_linearize_robust_kernel(LinArgs a, LinLoss l) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int T = LIN_ROBUST_THREADS;
@@ -169,8 +174,14 @@ __global__ __launch_bounds__(LIN_ROBUST_THREADS) void ba_linearize_robust_kernel
         if (i < a.n_obs) {
             const double2 f = a.feat[i];
             const int c = a.obs_cam[i], j = a.obs_pt[i];
-            const int kind = l.kind[i];
-            const double la = l.a[i], lb = l.b[i], sc = l.scale[i];
+            const int kind = LOSS ? l.kind[i] : (int)STBA_LOSS_TRIVIAL;
+            const double la = LOSS ? l.a[i] : 1.0, lb = LOSS ? l.b[i] : 1.0, sc = LOSS ? l.scale[i] : 1.0;
+            double w[4] = {1.0, 0.0, 0.0, 1.0};
+            if (INFO) {
+                const double2* wi = reinterpret_cast<const double2*>(l.winfo) + 2 * (size_t)i;
+                const double2 w01 = wi[0], w23 = wi[1];
+                w[0] = w01.x; w[1] = w01.y; w[2] = w23.x; w[3] = w23.y;
+            }
             const double* cam = CAMS_IN_LDS ? (s_cam + c * 7) : (a.cams + (size_t)c * 7);
             double q[4] = {cam[0], cam[1], cam[2], cam[3]};
             const double t0 = cam[4], t1 = cam[5], t2 = cam[6];
@@ -184,7 +195,7 @@ __global__ __launch_bounds__(LIN_ROBUST_THREADS) void ba_linearize_robust_kernel
             const double iz = 1.0 / z;
             const double xn = x * iz, yn = y * iz;
             double r0 = xn - f.x, r1 = yn - f.y;
-            const double s = r0 * r0 + r1 * r1;
+            double s = r0 * r0 + r1 * r1;
             double jc[12], jp[6];
             if (WITH_JAC) {
 #pragma unroll
@@ -201,8 +212,25 @@ __global__ __launch_bounds__(LIN_ROBUST_THREADS) void ba_linearize_robust_kernel
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { jc[3 + k] = -jp[k]; jc[9 + k] = -jp[3 + k]; }
             }
+            if (INFO && (w[0] != 1.0 || w[1] != 0.0 || w[2] != 0.0 || w[3] != 1.0)) {
+                // whitening: the two-term product W (u, v)^T on r and on each column of [Jc | Jp]
+                const double t = w[0] * r0 + w[1] * r1;
+                r1 = w[2] * r0 + w[3] * r1;
+                r0 = t;
+                s = r0 * r0 + r1 * r1;
+                if (WITH_JAC) {
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) {
+                        double& u = k < 6 ? jc[k] : jp[k - 6];
+                        double& v = k < 6 ? jc[6 + k] : jp[k - 3];
+                        const double tu = w[0] * u + w[1] * v;
+                        v = w[2] * u + w[3] * v;
+                        u = tu;
+                    }
+                }
+            }
             double rho0 = s;
-            if (kind != STBA_LOSS_TRIVIAL || sc != 1.0) {
+            if (LOSS && (kind != STBA_LOSS_TRIVIAL || sc != 1.0)) {
                 double rho[3];
                 robust_loss(kind, la, lb, s, rho);
 #pragma unroll
@@ -285,29 +313,38 @@ size_t lin_robust_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac) {
 // (decided once per engine, from the full linearisation: the residual-only launch of the trial point takes the same variant)
 bool lin_robust_cams_in_lds(int n_cams) { return lin_robust_lds_bytes(n_cams, true, true) <= (size_t)LIN_MAX_LDS; }
 
-int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st) {
+// (one of the twelve instantiations: CAMS_IN_LDS x WITH_JAC from the geometry, INFO x LOSS from what the engine holds)
+template <bool INFO, bool LOSS>
+static int launch_linearize_robust_as(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st) {
     const bool in_lds = lin_robust_cams_in_lds(a.n_cams);
     const size_t lds = lin_robust_lds_bytes(a.n_cams, in_lds, with_jac);
     static DeviceOnce attr;
     STBA_TRY(attr.run([]() -> int {
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, true>),
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, true, INFO, LOSS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, false>),
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<true, false, INFO, LOSS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<false, true>),
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_robust_kernel<false, true, INFO, LOSS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, LIN_MAX_LDS));
         return STBA_OK;
     }));
     if (in_lds && with_jac)
-        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, true>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, true, INFO, LOSS>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
     else if (in_lds)
-        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, false>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<true, false, INFO, LOSS>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
     else if (with_jac)
-        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, true>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, true, INFO, LOSS>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
     else
-        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, false>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
+        hipLaunchKernelGGL((ba_linearize_robust_kernel<false, false, INFO, LOSS>), dim3(grid), dim3(LIN_ROBUST_THREADS), lds, st, a, l);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
+}
+
+int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st) {
+    if (l.winfo && l.kind) return launch_linearize_robust_as<true, true>(a, l, with_jac, grid, st);
+    if (l.winfo) return launch_linearize_robust_as<true, false>(a, l, with_jac, grid, st);
+    if (l.kind) return launch_linearize_robust_as<false, true>(a, l, with_jac, grid, st);
+    return fail(STBA_ERR_INVALID_ARGUMENT, "launch_linearize_robust: neither a loss table nor weights");
 }
 
 // ===========================================================================================

@@ -75,7 +75,9 @@ struct LinLoss {
     const double* b;                 // [n_obs]
     const double* scale;             // [n_obs]
     double* Jc12;                    // [n_obs][12]
+    const double* winfo;             // [n_obs][4] square-root information, 2 x 2 row-major; null: the identity
 };
+// (kind == null with winfo set: weights only, the table is not read)
 size_t lin_robust_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac);
 bool lin_robust_cams_in_lds(int n_cams);
 int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st);

@@ -122,6 +122,9 @@ struct stba_ba {
     // everything behind the linearisation runs its general form on them, as for host-linearised factors
     int* loss_kind = nullptr;
     double *loss_a = nullptr, *loss_b = nullptr, *loss_scale = nullptr;
+    // per-observation square-root information W_i (stba_ba_set_information / _sqrt_information): [n_obs][4], 2 x 2
+    // row-major in the engine's order; null: the identity.  With it the same kernel whitens r, Jc, Jp in front of the corrector
+    double* winfo = nullptr;
     unsigned char* omask = nullptr;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
     double *Hpp6 = nullptr, *gp = nullptr, *Hinv6 = nullptr, *dp = nullptr, *scale_p = nullptr;
     double *Hcc = nullptr, *gc = nullptr, *cam_partial = nullptr, *dc = nullptr, *scale_c = nullptr;
@@ -209,7 +212,7 @@ static void ba_free(stba_ba* b) {
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
     F(b->pt_start); F(b->cam_perm); F(b->chunk_begin); F(b->chunk_end); F(b->cam_chunk_start); F(b->cam_fixed);
-    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->dp); F(b->scale_p);
+    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->winfo); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->dp); F(b->scale_p);
     F(b->Hcc); F(b->gc); F(b->cam_partial); F(b->dc); F(b->scale_c); F(b->Sbuf); F(b->Spack); F(b->pk_blocks); F(b->dxc); F(b->dxp);
     F(b->task_cam); F(b->cam_start); F(b->task_col_lo); F(b->task_col_hi); F(b->row_col_ptr); F(b->row_cols);
     F(b->task_p_lo); F(b->task_p_hi); F(b->row_task_ptr); F(b->row_tasks); F(b->task_part_off); F(b->schur_part);
@@ -283,15 +286,16 @@ static int ba_host_linearize(stba_ba* b, int which, bool with_jac) {
 }
 
 // the camera blocks of the GENERAL form (J8 = {0, 0, Jp}, Jc12 = the 2 x 6 blocks), which every kernel behind the linearisation
-// takes in its GEN instantiation: host-linearised factors and engines with a loss table; null: the compact record
-static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind) ? b->Jc12 : nullptr; }
+// takes in its GEN instantiation: host-linearised factors and engines with a loss table or weights; null: the compact record
+static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind || b->winfo) ? b->Jc12 : nullptr; }
 
-// THE linearisation at parameter buffer `which`: the host's callback, the robust kernel (a loss table is set) or the lossless
-// kernel.  The cost partials (sum r^2, or sum rho with a table) are left in cost_partial; with_jac: r, J8 (and Jc12) are stored
+// THE linearisation at parameter buffer `which`: the host's callback, the robust kernel (a loss table and / or weights are set: its
+// INFO / LOSS pair follows from which of the two the engine holds) or the lossless kernel.  The cost partials (sum r^2, or sum rho with a table) are left in cost_partial; with_jac: r, J8 (and Jc12) are stored
 static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
     if (b->hl_fn) return ba_host_linearize(b, which, with_jac);
     const LinArgs a = lin_args(b, which, with_jac);
-    if (b->loss_kind) return launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12}, with_jac, b->lin_grid, b->st);
+    if (b->loss_kind || b->winfo)
+        return launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12, b->winfo}, with_jac, b->lin_grid, b->st);
     return launch_linearize(a, with_jac, b->lin_grid, b->st);
 }
 
@@ -1687,6 +1691,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (fn && b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has inner iterations (device residuals only)");
     if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
+    if (fn && b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has information matrices (the callback's factors whiten themselves; not supported together)");
     if (fn && !b->Jc12) STBA_TRY(dev_alloc(&b->Jc12, (size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
@@ -1745,10 +1750,110 @@ int stba_ba_set_loss(stba_ba* b, const int* kind, const double* a, const double*
     for (void* p : {(void*)b->loss_kind, (void*)b->loss_a, (void*)b->loss_b, (void*)b->loss_scale}) if (p) (void)hipFree(p);
     b->loss_kind = k_new; b->loss_a = a_new; b->loss_b = b_new; b->loss_scale = s_new;
     if (jc_new) b->Jc12 = jc_new;
-    if (!kind && !b->hl_fn && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }      // (96 B per observation nobody reads any more)
+    if (!kind && !b->hl_fn && !b->winfo && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }      // (96 B per observation nobody reads any more)
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     cov_store_free(b->cov);
     b->cov = nullptr;
+    return STBA_OK;
+}
+
+// Omega = L L^T, W = L^T of ONE symmetric 2 x 2 from its lower triangle (a, b, c) = (in[0], in[2], in[3]): l11 = sqrt(a), l21 = b / l11,
+// l22 = sqrt(c - b^2 / a).  The pivot is formed directly from a, b, c with error-free products: t = fl(b / a), t b = p + e and
+// b - t a = rem exactly (FMA), c - p = sum + err exactly (two-sum), so pivot = sum + (err - e - rem b / a) carries one rounding where
+// c - l21^2 would carry kappa(Omega) of them: every entry of W is within 4 eps of the exact factor of the matrix given.
+// false: an entry that is not finite, or a pivot that is not a positive finite number.
+static bool ba_information_factor(const double* in, double* W) {
+    const double a = in[0], bb = in[2], c = in[3];
+    if (!std::isfinite(a) || !std::isfinite(in[1]) || !std::isfinite(bb) || !std::isfinite(c) || !(a > 0.0)) return false;
+    const double l11 = std::sqrt(a);
+    const double t = bb / a;
+    const double p = t * bb, e = std::fma(t, bb, -p);
+    const double rem = std::fma(-t, a, bb);
+    const double sum = c - p, z = sum - c;
+    const double err = (c - (sum - z)) + (-p - z);
+    const double pivot = sum + ((err - e) - rem * bb / a);
+    if (!(pivot > 0.0) || !std::isfinite(pivot)) return false;
+    W[0] = l11; W[1] = bb / l11; W[2] = 0.0; W[3] = std::sqrt(pivot);
+    return std::isfinite(W[0]) && std::isfinite(W[1]) && std::isfinite(W[3]);
+}
+
+// the per-observation weights: checked (and, for the information form, factored) on the host BEFORE anything is replaced, permuted
+// into the engine's landmark-major order, uploaded into a NEW array that is swapped in; in == NULL, or an array whose every W is
+// exactly the identity, goes back to the identity (no array held)
+static int ba_set_weights(stba_ba* b, const double* in, bool sqrt_form, const char* who) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
+    double *w_new = nullptr, *jc_new = nullptr;
+    const size_t m = (size_t)b->no;
+    std::vector<double> hw;
+    if (in) {
+        // (the messages below name the row as "observation <index>:" -- include/stba/g2o.h reads the index out of that text to name the
+        // edge; keep the wording)
+        hw.resize(m * 4);
+        bool all_identity = true;
+        for (size_t e = 0; e < m; ++e) {
+            if (sqrt_form) {
+                for (int k = 0; k < 4; ++k) {
+                    if (!std::isfinite(in[e * 4 + k]))
+                        return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": observation " + std::to_string(e) + ": the square-root information has an entry that is not finite");
+                    hw[e * 4 + k] = in[e * 4 + k];
+                }
+            } else if (!ba_information_factor(in + e * 4, &hw[e * 4])) {
+                return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string(who) + ": observation " + std::to_string(e) + ": the information matrix is not positive definite (or has an entry that is not finite)");
+            }
+            const double* w = &hw[e * 4];
+            all_identity = all_identity && w[0] == 1.0 && w[1] == 0.0 && w[2] == 0.0 && w[3] == 1.0;
+        }
+        // every W exactly the identity IS the engine without weights: the array is not held (as for NULL), the lossless kernels run
+        if (all_identity) in = nullptr;
+    }
+    if (in) {
+        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has a host lineariser (the callback's factors whiten themselves; not supported together)");
+        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has inner iterations (inner iterations with information matrices are not supported)");
+        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and information matrices run on one rank only");
+        std::vector<double> pw(m * 4);
+        for (size_t p = 0; p < m; ++p) memcpy(&pw[p * 4], &hw[(size_t)b->perm[p] * 4], 4 * sizeof(double));   // the engine's order
+        auto F = [](void* p) { if (p) (void)hipFree(p); };
+        const size_t ma = std::max<size_t>(m, 1);
+        int rc = dev_alloc(&w_new, ma * 4);
+        if (rc == STBA_OK && !b->Jc12) rc = dev_alloc(&jc_new, ma * 12);
+        if (rc == STBA_OK && m > 0 &&
+            (hipMemcpyAsync(w_new, pw.data(), m * 4 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipStreamSynchronize(b->st) != hipSuccess))
+            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
+        if (rc != STBA_OK) { F(w_new); F(jc_new); return rc; }
+    }
+    // (nothing of the engine may still be reading the old array or what was linearised with it)
+    STBA_HIP(hipStreamSynchronize(b->st));
+    if (b->winfo) (void)hipFree(b->winfo);
+    b->winfo = w_new;
+    if (jc_new) b->Jc12 = jc_new;
+    if (!in && !b->hl_fn && !b->loss_kind && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    return STBA_OK;
+}
+
+int stba_ba_set_information(stba_ba* b, const double* information) { return ba_set_weights(b, information, false, "stba_ba_set_information"); }
+int stba_ba_set_sqrt_information(stba_ba* b, const double* sqrt_information) { return ba_set_weights(b, sqrt_information, true, "stba_ba_set_sqrt_information"); }
+
+int stba_ba_has_information(const stba_ba* b, int* has) {
+    if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_information: null argument");
+    *has = b->winfo ? 1 : 0;
+    return STBA_OK;
+}
+
+int stba_ba_get_sqrt_information(stba_ba* b, double* out) {
+    if (!b || !out) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_get_sqrt_information: null argument");
+    const size_t m = (size_t)b->no;
+    if (!b->winfo) {
+        for (size_t e = 0; e < m; ++e) { out[e * 4] = 1.0; out[e * 4 + 1] = 0.0; out[e * 4 + 2] = 0.0; out[e * 4 + 3] = 1.0; }
+        return STBA_OK;
+    }
+    std::vector<double> pw(m * 4);
+    if (m > 0) STBA_TRY(download(pw.data(), b->winfo, m * 4, b->st));
+    STBA_HIP(hipStreamSynchronize(b->st));
+    for (size_t p = 0; p < m; ++p) memcpy(&out[(size_t)b->perm[p] * 4], &pw[p * 4], 4 * sizeof(double));
     return STBA_OK;
 }
 
@@ -1774,6 +1879,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has inner iterations, which run on one rank only");
     if (b && b->loss_kind && (fn || world_size > 1))
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has a loss table, and losses run on one rank only");
+    if (b && b->winfo && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has information matrices, which run on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -1976,6 +2083,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: inner iterations run on one rank only (an all-reduce hook is set)");
     if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: not with a host lineariser");
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has a loss table (inner iterations with losses are not supported)");
+    if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has information matrices (inner iterations with information matrices are not supported)");
     const int nc = b->nc, np = b->np, no = b->no;
     // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
     std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
@@ -2067,6 +2175,7 @@ int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (b->ar || b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: one rank, device residuals only");
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has a loss table (inner iterations with losses are not supported)");
+    if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has information matrices (inner iterations with information matrices are not supported)");
     const bool was_on = b->inner_on;
     if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
     STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
