@@ -276,6 +276,17 @@ int stba_ba_camera_covariance(stba_ba* ba, int n_pairs, const int* cam_a, const 
 /* out[n*9]: the 3x3 marginal covariance of landmarks pts[0..n) (pts = NULL: all n_pts landmarks in order, n = n_pts):
  * V_j^-1 + sum over pairs of its observations F_a^T Sigma_cc[a, b] F_b, F_a = E_{a,j} V_j^-1 (covariance.hip) */
 int stba_ba_point_covariance(stba_ba* ba, int n, const int* pts, double* out);
+/* The off-diagonal blocks of the full inverse, from what the compute left on the device (nothing more is inverted; F_i = Jc_i^T Jp_i
+ * V_j^-1 per observation i of landmark j, sums over observations):
+ *   Sigma[a, j] = - sum_{i in obs(j)} Sigma_cc[a, cam(i)] F_i,   Sigma[j, k] = sum_{x in obs(j), y in obs(k)} F_x^T Sigma_cc[cam(x), cam(y)] F_y  (j != k)
+ * Both need a preceding stba_ba_covariance_compute (STBA_ERR_STATE otherwise).  An index out of range, or a null array with
+ * n_pairs > 0: STBA_ERR_INVALID_ARGUMENT (stba_last_error() names the position), nothing written.  n_pairs == 0: STBA_OK.  Constant
+ * dofs and constant landmarks give zero rows and columns.  Sigma[k, j] is bitwise the transpose of Sigma[j, k].  STBA_VERSION is
+ * unchanged: test for the symbols. */
+/* out[n_pairs*18]: the 6 x 3 row-major block Sigma[cam[k], pt[k]] (rows [dtheta(3), dt(3)], columns the landmark's coordinates) */
+int stba_ba_camera_point_covariance(stba_ba* ba, int n_pairs, const int* cam, const int* pt, double* out);
+/* out[n_pairs*9]: the 3 x 3 row-major block Sigma[pt_a[k], pt_b[k]]; pt_a == pt_b gives the marginal of stba_ba_point_covariance, bit for bit */
+int stba_ba_point_pair_covariance(stba_ba* ba, int n_pairs, const int* pt_a, const int* pt_b, double* out);
 int stba_ba_covariance_release(stba_ba* ba);
 
 /* ================================ dense SPD solver ======================================== */

@@ -2006,8 +2006,11 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
 //     requested pair is any two pose blocks of the graph; a connected component without a constant block makes J^T J singular and
 //     Compute return false (the message names the component), before any device work;
 //   * "gpu-dense": anything else within the dense solve's limits -> stba_dense_covariance.
-// On the BA routes a requested pair must be two camera blocks (rotation / position, of one camera or of two) or one landmark with
-// itself; anything else is refused before any device work.  Constant blocks give zero blocks.  Limits: robust losses on "gpu-pg", and on "gpu-ba"
+// On the BA routes a requested pair is two camera blocks (rotation / position, of one camera or of two) or one landmark with
+// itself; with Options::bundle_adjustment_cross_blocks = true (an extension of this layer, off by default: tests/cpp/test_covariance.cpp
+// pins the refusal) it is any two of the rotation blocks, position blocks and landmarks, as in Ceres: also camera-landmark blocks
+// (either way round) and the blocks of two different landmarks (stba_ba_camera_point_covariance, stba_ba_point_pair_covariance).
+// Without the option those pairs are refused before any device work.  Constant blocks give zero blocks.  Limits: robust losses on "gpu-pg", and on "gpu-ba"
 // with Options::bundle_adjustment_losses set, where the result is (J'^T J')^-1 of the corrected Jacobian as in Ceres (refused elsewhere as Solve refuses them), no pseudo-inverse (null_space_rank must be 0), and the rank test is the pivot ratio of the Cholesky
 // factorisations (stba.h, stba_ba_covariance_compute) -- not a condition number estimate.  algorithm_type and num_threads are
 // accepted for source compatibility and do not change the computation.
@@ -2023,6 +2026,7 @@ public:
         int num_threads = 1;
         bool apply_loss_function = true;
         bool bundle_adjustment_losses = false;   // (not in Ceres) as Solver::Options::bundle_adjustment_losses: built-in losses on "gpu-ba"
+        bool bundle_adjustment_cross_blocks = false;   // (not in Ceres) camera-landmark pairs and pairs of different landmarks on the BA routes (off: refused, the default this layer has had)
     };
     explicit Covariance(const Options& options) : options_(options) {}
 
@@ -2161,13 +2165,20 @@ private:
         std::vector<int> cam_of(blk.size(), -1), off_of(blk.size(), 0), pt_of(blk.size(), -1);
         for (int c = 0; c < nc; ++c) { cam_of[L.rot_block[c]] = c; cam_of[L.pos_block[c]] = c; off_of[L.pos_block[c]] = 3; }
         for (int j = 0; j < np; ++j) pt_of[L.pt_block[j]] = j;
-        std::vector<int> ca, cb, pj;
+        // four kinds of pair, one C-ABI call each: camera-camera, a landmark's marginal, camera-landmark (a (landmark, camera) pair
+        // is asked for as (camera, landmark) and transposed), landmark-landmark
+        std::vector<int> ca, cb, pj, xc, xp, la, lb;
         for (size_t k = 0; k < pairs.size(); ++k) {
             const int a = index.at(pairs[k].first), b = index.at(pairs[k].second);
             if (cam_of[a] >= 0 && cam_of[b] >= 0) { ca.push_back(cam_of[a]); cb.push_back(cam_of[b]); }
             else if (pt_of[a] >= 0 && a == b) pj.push_back(pt_of[a]);
-            else return Fail(PairName(k) + " is neither two camera blocks nor one landmark with itself: the bundle-adjustment route has no "
-                             "camera-landmark or landmark-landmark blocks");
+            else if (!options_.bundle_adjustment_cross_blocks)
+                return Fail(PairName(k) + " is neither two camera blocks nor one landmark with itself: camera-landmark and landmark-landmark "
+                            "blocks of the bundle-adjustment route need Covariance::Options::bundle_adjustment_cross_blocks = true");
+            else if (cam_of[a] >= 0 && pt_of[b] >= 0) { xc.push_back(cam_of[a]); xp.push_back(pt_of[b]); }
+            else if (pt_of[a] >= 0 && cam_of[b] >= 0) { xc.push_back(cam_of[b]); xp.push_back(pt_of[a]); }
+            else if (pt_of[a] >= 0 && pt_of[b] >= 0) { la.push_back(pt_of[a]); lb.push_back(pt_of[b]); }
+            else return Fail(PairName(k) + " names a parameter block that no residual block of the bundle adjustment uses");
         }
         path_ = host ? "gpu-ba-hostjac" : "gpu-ba";
         std::vector<double> cams((size_t)nc * 7), pts((size_t)np * 3);
@@ -2193,19 +2204,27 @@ private:
         double rc = 0.0;
         if (stba_ba_covariance_compute(ba, options_.min_reciprocal_condition_number, &rc) != STBA_OK)
             return Fail(std::string("stba_ba_covariance_compute: ") + stba_last_error());
-        std::vector<double> cblk(ca.size() * 36), pblk(pj.size() * 9);
+        std::vector<double> cblk(ca.size() * 36), pblk(pj.size() * 9), xblk(xc.size() * 18), lblk(la.size() * 9);
         if (stba_ba_camera_covariance(ba, (int)ca.size(), ca.data(), cb.data(), cblk.data()) != STBA_OK ||
-            stba_ba_point_covariance(ba, (int)pj.size(), pj.data(), pblk.data()) != STBA_OK)
+            stba_ba_point_covariance(ba, (int)pj.size(), pj.data(), pblk.data()) != STBA_OK ||
+            stba_ba_camera_point_covariance(ba, (int)xc.size(), xc.data(), xp.data(), xblk.data()) != STBA_OK ||
+            stba_ba_point_pair_covariance(ba, (int)la.size(), la.data(), lb.data(), lblk.data()) != STBA_OK)
             return Fail(std::string("covariance blocks: ") + stba_last_error());
-        size_t kc = 0, kp = 0;
+        size_t kc = 0, kp = 0, kx = 0, kl = 0;
         for (auto& pr : pairs) {
             const int a = index.at(pr.first), b = index.at(pr.second);
-            std::vector<double> t;
+            std::vector<double> t(9);
             if (cam_of[a] >= 0 && cam_of[b] >= 0) {
                 const double* s6 = &cblk[kc++ * 36];
-                t.resize(9);
                 for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) t[(size_t)r * 3 + c] = s6[(size_t)(off_of[a] + r) * 6 + off_of[b] + c];
-            } else { const double* s3 = &pblk[kp++ * 9]; t.assign(s3, s3 + 9); }
+            } else if (pt_of[a] >= 0 && a == b) { const double* s3 = &pblk[kp++ * 9]; t.assign(s3, s3 + 9); }
+            else if (cam_of[a] >= 0) {              // (rotation | position, landmark): rows off .. off + 3 of the 6 x 3 block
+                const double* s = &xblk[kx++ * 18] + (size_t)off_of[a] * 3;
+                t.assign(s, s + 9);
+            } else if (cam_of[b] >= 0) {            // (landmark, rotation | position): the transpose
+                const double* s = &xblk[kx++ * 18] + (size_t)off_of[b] * 3;
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) t[(size_t)r * 3 + c] = s[(size_t)c * 3 + r];
+            } else { const double* s3 = &lblk[kl++ * 9]; t.assign(s3, s3 + 9); }
             Store(pr.first, pr.second, 3, 3, std::move(t));
         }
         return true;

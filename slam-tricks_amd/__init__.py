@@ -76,6 +76,7 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_comm_allreduce_hook", "stba_ba_set_comm", "stba_pg_set_comm",
            "stba_ba_set_features", "stba_get_device", "stba_set_device",
            "stba_ba_covariance_compute", "stba_ba_camera_covariance", "stba_ba_point_covariance", "stba_ba_covariance_release",
+           "stba_ba_camera_point_covariance", "stba_ba_point_pair_covariance",
            "stba_dense_covariance",
            "stba_ba_create_ex", "stba_ba_set_pcg", "stba_ba_last_pcg_summary", "stba_ba_schur_apply",
            "stba_ba_last_pcg_iterations", "stba_ba_time_schur_apply",
@@ -487,6 +488,27 @@ class BAEngine:
         pb = np.zeros((m, 3, 3))
         _chk(L.stba_ba_point_covariance(self._h, m, _p(pts), _p(pb)), "stba_ba_point_covariance")
         return cam, pb, rc.value
+
+    def cross_covariance(self, cam_points=(), point_pairs=(), min_rcond=1e-14, recompute=True):
+        """off-diagonal blocks of the same covariance: returns (cp [k,6,3], pp [m,3,3], rcond).  cam_points: (camera, landmark)
+        pairs -> Sigma[camera, landmark] (rows [rot(3), pos(3)]); point_pairs: (j, k) landmark pairs -> Sigma[j, k] ((j, j): the
+        marginal covariance() gives; (k, j) is bitwise the transpose of (j, k)).  recompute=False takes the blocks from what the
+        last covariance() or cross_covariance() left on the device (StbaError -6 if nothing is held); rcond is then None."""
+        L = lib()
+        rcond = None
+        if recompute:
+            rc = C.c_double()
+            _chk(L.stba_ba_covariance_compute(self._h, C.c_double(min_rcond), C.byref(rc)), "stba_ba_covariance_compute")
+            rcond = rc.value
+        cpr = np.asarray(cam_points, dtype=np.int32).reshape(-1, 2)
+        ca, pj = np.ascontiguousarray(cpr[:, 0]), np.ascontiguousarray(cpr[:, 1])
+        cp = np.zeros((len(ca), 6, 3))
+        _chk(L.stba_ba_camera_point_covariance(self._h, len(ca), _p(ca), _p(pj), _p(cp)), "stba_ba_camera_point_covariance")
+        ppr = np.asarray(point_pairs, dtype=np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(ppr[:, 0]), np.ascontiguousarray(ppr[:, 1])
+        pp = np.zeros((len(pa), 3, 3))
+        _chk(L.stba_ba_point_pair_covariance(self._h, len(pa), _p(pa), _p(pb), _p(pp)), "stba_ba_point_pair_covariance")
+        return cp, pp, rcond
 
     def covariance_release(self):
         _chk(lib().stba_ba_covariance_release(self._h), "stba_ba_covariance_release")

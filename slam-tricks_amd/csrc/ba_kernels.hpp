@@ -211,6 +211,10 @@ void cov_store_free(CovStore* c);
 int cov_compute(const BaCovInputs& in, double min_rcond, CovStore** out, double* rcond_out);
 int cov_camera_blocks(const CovStore* c, int n_pairs, const int* cam_a, const int* cam_b, double* out);
 int cov_point_blocks(const CovStore* c, int n, const int* pts, double* out);
+// the off-diagonal blocks of the full inverse: Sigma[cam[k], pt[k]] (6 x 3) and Sigma[pt_a[k], pt_b[k]] (3 x 3; pt_a == pt_b: the
+// marginal of cov_point_blocks).  An index out of range: STBA_ERR_INVALID_ARGUMENT with the position named, nothing written
+int cov_cam_point_blocks(const CovStore* c, int n_pairs, const int* cam, const int* pt, double* out);
+int cov_point_pair_blocks(const CovStore* c, int n_pairs, const int* pt_a, const int* pt_b, double* out);
 // inverse of the SPD matrix whose lower triangle is A (n x n, leading dimension lda, device) -> packed lower triangle sig (device,
 // row i at i (i + 1) / 2); *rcond = smallest / largest Cholesky pivot over the rows that are not constant dofs (cam_fixed: bit a of
 // byte i / 6 marks row i; may be null); *pivot_row = 0, or row + 1 of the first pivot that is not positive

@@ -6,6 +6,9 @@
 //   Sigma_jj = V_j^-1 + sum_{a, b in cams(j)} F_a^T Sigma_cc[a, b] F_b,   F_a = E_{a,j} V_j^-1
 // E_{a,j} is a sum over the observations of landmark j by camera a, so the double sum runs over PAIRS OF OBSERVATIONS of the
 // landmark (F_i = Jc_i^T Jp_i V_j^-1 per observation): a camera that sees the landmark twice is the sum of its two terms.
+// The off-diagonal blocks of the full inverse are made of the same pieces, nothing more is inverted:
+//   Sigma[a, j] (6 x 3) = - sum_{i in obs(j)} Sigma_cc[a, cam(i)] F_i
+//   Sigma[j, k] (3 x 3) =   sum_{x in obs(j)} sum_{y in obs(k)} F_x^T Sigma_cc[cam(x), cam(y)] F_y              (j != k)
 //
 //   cov_spd_inverse_packed   S (or a dense J^T J) -> W = [S . ; I 0] -> chol_spd_inverse_dev (dense_chol.hip) -> the lower
 //                            triangle of S^-1, packed (row i at i (i + 1) / 2: 144 MB at 6000 unknowns), and the pivot ratio
@@ -14,6 +17,9 @@
 //                            6 x 6 blocks of Sigma_cc read straight from the packed triangle, one pair of observations per lane
 //                            and trip, a fixed order and a fixed shuffle reduction: bitwise reproducible, no atomics
 //   cov_camera_kernel        6 x 6 blocks (a, b) of Sigma_cc, constant dofs zeroed
+//   cov_cam_point_kernel     camera-landmark blocks: one wave per pair, one observation of the landmark per lane, F in registers
+//   cov_point_pair_kernel    landmark-landmark blocks: one wave per pair, the staging and the per-pair product of cov_point_kernel
+//                            (cov_form_F, cov_Ft_sigma_F), smaller index first and the transpose for a swapped request
 // The pivot ratio (smallest pivot / largest pivot of the Cholesky factorisation) is a cheap stand-in for a reciprocal condition
 // number, not an estimate of one: a ratio above the threshold does not prove the matrix well conditioned.
 #include <algorithm>
@@ -175,6 +181,51 @@ __global__ __launch_bounds__(256) void cov_camera_kernel(const double* __restric
 // triangle (288 B: the whole triangle is 144 MB at C5 and stays in the Infinity Cache), 162 FMAs.
 constexpr int CV_CHUNK = 32, CV_LD = 19;      // (odd stride: the 18 doubles of neighbouring observations start in different banks)
 
+// what the three block kernels share.  F = Jc^T Jp V^-1 (6 x 3 row-major) of observation i, Vf = V^-1 of its landmark as a full 3 x 3
+template <bool GEN>
+__device__ __forceinline__ void cov_form_F(const double* __restrict__ J8, const unsigned char* __restrict__ omask, const double* __restrict__ Jc12,
+                                           int i, const double Vf[9], double* F) {
+    double jc[12], jp[6];
+    load_jc_jp<GEN>(J8, omask, i, jc, jp, Jc12);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        const double e0 = jc[r] * jp[0] + jc[6 + r] * jp[3];
+        const double e1 = jc[r] * jp[1] + jc[6 + r] * jp[4];
+        const double e2 = jc[r] * jp[2] + jc[6 + r] * jp[5];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) F[r * 3 + k] = e0 * Vf[k] + e1 * Vf[3 + k] + e2 * Vf[6 + k];
+    }
+}
+
+// T (6 x 3) = Sigma_cc[rows rx .. rx + 6, columns ry .. ry + 6] F_y, the block read straight from the packed triangle
+__device__ __forceinline__ void cov_sigma_F(const double* __restrict__ sig, int rx, int ry, const double* Fy, double T[18]) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const double s = packed_at(sig, rx + r, ry + c);
+            t0 += s * Fy[c * 3]; t1 += s * Fy[c * 3 + 1]; t2 += s * Fy[c * 3 + 2];
+        }
+        T[r * 3] = t0; T[r * 3 + 1] = t1; T[r * 3 + 2] = t2;
+    }
+}
+
+// X (3 x 3) = F_x^T Sigma_cc[rx .., ry ..] F_y
+__device__ __forceinline__ void cov_Ft_sigma_F(const double* __restrict__ sig, const double* Fx, int rx, const double* Fy, int ry, double X[9]) {
+    double T[18];
+    cov_sigma_F(sig, rx, ry, Fy, T);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            double s = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) s += Fx[r * 3 + k] * T[r * 3 + l];
+            X[k * 3 + l] = s;
+        }
+}
+
 template <bool GEN>
 __global__ __launch_bounds__(64) void cov_point_kernel(const int* __restrict__ req, const int* __restrict__ pt_start, const int* __restrict__ obs_cam,
                                                        const double* __restrict__ J8, const unsigned char* __restrict__ omask,
@@ -199,17 +250,7 @@ __global__ __launch_bounds__(64) void cov_point_kernel(const int* __restrict__ r
                 const int half = t >> 5, lt = t & 31;
                 const int o = (half ? ib : ia) * CV_CHUNK + lt;
                 if (o < m) {
-                    double jc[12], jp[6];
-                    load_jc_jp<GEN>(J8, omask, o0 + o, jc, jp, Jc12);
-                    double* F = sf[half] + lt * CV_LD;
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) {
-                        const double e0 = jc[r] * jp[0] + jc[6 + r] * jp[3];
-                        const double e1 = jc[r] * jp[1] + jc[6 + r] * jp[4];
-                        const double e2 = jc[r] * jp[2] + jc[6 + r] * jp[5];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) F[r * 3 + k] = e0 * Vf[k] + e1 * Vf[3 + k] + e2 * Vf[6 + k];
-                    }
+                    cov_form_F<GEN>(J8, omask, Jc12, o0 + o, Vf, sf[half] + lt * CV_LD);
                     sc[half][lt] = obs_cam[o0 + o];
                 }
             }
@@ -228,27 +269,8 @@ __global__ __launch_bounds__(64) void cov_point_kernel(const int* __restrict__ r
                 const double* Fx = sf[0] + x * CV_LD;
                 const double* Fy = sf[same ? 0 : 1] + y * CV_LD;
                 const int rx = 6 * sc[0][x], ry = 6 * sc[same ? 0 : 1][y];
-                double T[18];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) {
-                    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        const double s = packed_at(sig, rx + r, ry + c);
-                        t0 += s * Fy[c * 3]; t1 += s * Fy[c * 3 + 1]; t2 += s * Fy[c * 3 + 2];
-                    }
-                    T[r * 3] = t0; T[r * 3 + 1] = t1; T[r * 3 + 2] = t2;
-                }
                 double X[9];
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) s += Fx[r * 3 + k] * T[r * 3 + l];
-                        X[k * 3 + l] = s;
-                    }
+                cov_Ft_sigma_F(sig, Fx, rx, Fy, ry, X);
                 if (same && x == y) {
                     acc[0] += X[0]; acc[1] += X[1]; acc[2] += X[2]; acc[3] += X[4]; acc[4] += X[5]; acc[5] += X[8];
                 } else {
@@ -266,6 +288,108 @@ __global__ __launch_bounds__(64) void cov_point_kernel(const int* __restrict__ r
         o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
         o[3] = s[1]; o[4] = s[3]; o[5] = s[4];
         o[6] = s[2]; o[7] = s[4]; o[8] = s[5];
+    }
+}
+
+// Landmark-landmark blocks Sigma[j, k] = sum_{x in obs(j), y in obs(k)} F_x^T Sigma_cc[c_x, c_y] F_y (j != k: no V^-1 term, no
+// symmetry), one wave per requested pair.  It is the two-different-chunks case of cov_point_kernel: lanes 0..31 stage a chunk of
+// the first landmark with its V^-1, lanes 32..63 a chunk of the second with its own, then one pair of observations per lane and
+// trip.  The pair is computed with the smaller landmark index first and written transposed for a swapped request, so that
+// Sigma[k, j] is bitwise Sigma[j, k]^T.  A constant landmark (V^-1 = 0) gives exact zeros.  (j == k never gets here: the host sends
+// it through cov_point_kernel.)
+template <bool GEN>
+__global__ __launch_bounds__(64) void cov_point_pair_kernel(const int* __restrict__ req_a, const int* __restrict__ req_b, const int* __restrict__ pt_start,
+                                                            const int* __restrict__ obs_cam, const double* __restrict__ J8,
+                                                            const unsigned char* __restrict__ omask, const double* __restrict__ Jc12,
+                                                            const double* __restrict__ vinv6, const double* __restrict__ sig, double* __restrict__ out) {
+    __shared__ double sf[2][CV_CHUNK * CV_LD];
+    __shared__ int sc[2][CV_CHUNK];
+    const int t = threadIdx.x, half = t >> 5, lt = t & 31;
+    const int ra = req_a[blockIdx.x], rb = req_b[blockIdx.x];
+    const bool swapped = ra > rb;
+    const int j = swapped ? rb : ra, k = swapped ? ra : rb;
+    double Vj[6], Vk[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { Vj[q] = vinv6[(size_t)j * 6 + q]; Vk[q] = vinv6[(size_t)k * 6 + q]; }
+    const bool constant = (Vj[0] == 0.0 && Vj[3] == 0.0 && Vj[5] == 0.0) || (Vk[0] == 0.0 && Vk[3] == 0.0 && Vk[5] == 0.0);
+    double V[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) V[q] = half ? Vk[q] : Vj[q];
+    const double Vf[9] = {V[0], V[1], V[2], V[1], V[3], V[4], V[2], V[4], V[5]};
+    const int oj = pt_start[j], mj = pt_start[j + 1] - oj, ok = pt_start[k], mk = pt_start[k + 1] - ok;
+    const int o0 = half ? ok : oj, m = half ? mk : mj;            // (the landmark whose chunk this lane stages)
+    const int nca = constant ? 0 : (mj + CV_CHUNK - 1) / CV_CHUNK, ncb = (mk + CV_CHUNK - 1) / CV_CHUNK;
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int ia = 0; ia < nca; ++ia)
+        for (int ib = 0; ib < ncb; ++ib) {
+            __syncthreads();                 // (the previous pair of chunks has been read)
+            {
+                const int o = (half ? ib : ia) * CV_CHUNK + lt;
+                if (o < m) {
+                    cov_form_F<GEN>(J8, omask, Jc12, o0 + o, Vf, sf[half] + lt * CV_LD);
+                    sc[half][lt] = obs_cam[o0 + o];
+                }
+            }
+            __syncthreads();
+            const int na = min(CV_CHUNK, mj - ia * CV_CHUNK), nb = min(CV_CHUNK, mk - ib * CV_CHUNK);
+            for (int p = t; p < na * nb; p += 64) {
+                const int x = p / nb, y = p % nb;
+                double X[9];
+                cov_Ft_sigma_F(sig, sf[0] + x * CV_LD, 6 * sc[0][x], sf[1] + y * CV_LD, 6 * sc[1][y], X);
+#pragma unroll
+                for (int q = 0; q < 9; ++q) acc[q] += X[q];
+            }
+        }
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+    if (t == 0) {
+        double* o = out + (size_t)blockIdx.x * 9;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[swapped ? c * 3 + r : r * 3 + c] = acc[r * 3 + c];
+    }
+}
+
+// Camera-landmark blocks Sigma[a, j] = - sum_{i in obs(j)} Sigma_cc[a, c_i] F_i (6 x 3), one wave per requested pair, one
+// observation of the landmark per lane in trips of 64: F_i in registers, times the 6 x 6 block of the packed triangle; the 18 sums
+// go through the same butterfly.  Rows of constant dofs of camera a are written as zero (the packed triangle is not zero there),
+// a constant landmark gives exact zeros.
+template <bool GEN>
+__global__ __launch_bounds__(64) void cov_cam_point_kernel(const int* __restrict__ req_cam, const int* __restrict__ req_pt, const int* __restrict__ pt_start,
+                                                           const int* __restrict__ obs_cam, const double* __restrict__ J8,
+                                                           const unsigned char* __restrict__ omask, const double* __restrict__ Jc12,
+                                                           const double* __restrict__ vinv6, const double* __restrict__ sig,
+                                                           const unsigned char* __restrict__ cam_fixed, double* __restrict__ out) {
+    const int t = threadIdx.x;
+    const int a = req_cam[blockIdx.x], j = req_pt[blockIdx.x];
+    double V[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) V[q] = vinv6[(size_t)j * 6 + q];
+    const double Vf[9] = {V[0], V[1], V[2], V[1], V[3], V[4], V[2], V[4], V[5]};
+    const int o0 = pt_start[j], m = pt_start[j + 1] - o0;
+    const bool constant = V[0] == 0.0 && V[3] == 0.0 && V[5] == 0.0;
+    double acc[18];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) acc[q] = 0.0;
+    for (int o = t; o < (constant ? 0 : m); o += 64) {
+        double F[18], T[18];
+        cov_form_F<GEN>(J8, omask, Jc12, o0 + o, Vf, F);
+        cov_sigma_F(sig, 6 * a, 6 * obs_cam[o0 + o], F, T);
+#pragma unroll
+        for (int q = 0; q < 18; ++q) acc[q] += T[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 18; ++q)
+        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+    if (t == 0) {
+        double* o = out + (size_t)blockIdx.x * 18;
+        const unsigned fx = cam_fixed ? cam_fixed[a] : 0u;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[r * 3 + c] = ((fx >> r) & 1u) ? 0.0 : 0.0 - acc[r * 3 + c];
     }
 }
 
@@ -373,6 +497,65 @@ int cov_point_blocks(const CovStore* c, int n, const int* pts, double* out) {
     STBA_HIP(hipGetLastError());
     STBA_HIP(hipMemcpyAsync(out, dout, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, c->st));
     STBA_HIP(hipStreamSynchronize(c->st));
+    return STBA_OK;
+}
+
+int cov_cam_point_blocks(const CovStore* c, int n_pairs, const int* cam, const int* pt, double* out) {
+    if (n_pairs <= 0) return STBA_OK;
+    for (int k = 0; k < n_pairs; ++k) {
+        if (cam[k] < 0 || cam[k] >= c->nc)
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_point_covariance: camera index out of range in pair " + std::to_string(k));
+        if (pt[k] < 0 || pt[k] >= c->np)
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_point_covariance: landmark index out of range in pair " + std::to_string(k));
+    }
+    int *da = nullptr, *db = nullptr;
+    double* dout = nullptr;
+    struct Guard { int *&a, *&b; double*& o; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (o) (void)hipFree(o); } } guard{da, db, dout};
+    STBA_TRY(dev_alloc(&da, (size_t)n_pairs)); STBA_TRY(dev_alloc(&db, (size_t)n_pairs)); STBA_TRY(dev_alloc(&dout, (size_t)n_pairs * 18));
+    STBA_HIP(hipMemcpyAsync(da, cam, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
+    STBA_HIP(hipMemcpyAsync(db, pt, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
+    if (c->Jc12)
+        hipLaunchKernelGGL(cov_cam_point_kernel<true>, dim3(n_pairs), dim3(64), 0, c->st, da, db, c->pt_start, c->obs_cam, c->J8, c->omask, c->Jc12, c->vinv6, c->sig, c->cam_fixed, dout);
+    else
+        hipLaunchKernelGGL(cov_cam_point_kernel<false>, dim3(n_pairs), dim3(64), 0, c->st, da, db, c->pt_start, c->obs_cam, c->J8, c->omask, c->Jc12, c->vinv6, c->sig, c->cam_fixed, dout);
+    STBA_HIP(hipGetLastError());
+    STBA_HIP(hipMemcpyAsync(out, dout, (size_t)n_pairs * 18 * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    STBA_HIP(hipStreamSynchronize(c->st));
+    return STBA_OK;
+}
+
+int cov_point_pair_blocks(const CovStore* c, int n_pairs, const int* pt_a, const int* pt_b, double* out) {
+    if (n_pairs <= 0) return STBA_OK;
+    for (int k = 0; k < n_pairs; ++k)
+        if (pt_a[k] < 0 || pt_a[k] >= c->np || pt_b[k] < 0 || pt_b[k] >= c->np)
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_point_pair_covariance: landmark index out of range in pair " + std::to_string(k));
+    // a landmark with itself is the marginal (it has the V_j^-1 term): those go through cov_point_kernel, the rest in one launch here
+    std::vector<int> off_pos, off_a, off_b, diag_pos, diag_pt;
+    for (int k = 0; k < n_pairs; ++k) {
+        if (pt_a[k] == pt_b[k]) { diag_pos.push_back(k); diag_pt.push_back(pt_a[k]); }
+        else { off_pos.push_back(k); off_a.push_back(pt_a[k]); off_b.push_back(pt_b[k]); }
+    }
+    const int n_off = (int)off_pos.size(), n_diag = (int)diag_pos.size();
+    std::vector<double> res((size_t)n_pairs * 9);          // (out is written only once everything has come home)
+    if (n_off > 0) {
+        int *da = nullptr, *db = nullptr;
+        double* dout = nullptr;
+        struct Guard { int *&a, *&b; double*& o; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (o) (void)hipFree(o); } } guard{da, db, dout};
+        STBA_TRY(dev_alloc(&da, (size_t)n_off)); STBA_TRY(dev_alloc(&db, (size_t)n_off)); STBA_TRY(dev_alloc(&dout, (size_t)n_off * 9));
+        STBA_HIP(hipMemcpyAsync(da, off_a.data(), (size_t)n_off * sizeof(int), hipMemcpyHostToDevice, c->st));
+        STBA_HIP(hipMemcpyAsync(db, off_b.data(), (size_t)n_off * sizeof(int), hipMemcpyHostToDevice, c->st));
+        if (c->Jc12)
+            hipLaunchKernelGGL(cov_point_pair_kernel<true>, dim3(n_off), dim3(64), 0, c->st, da, db, c->pt_start, c->obs_cam, c->J8, c->omask, c->Jc12, c->vinv6, c->sig, dout);
+        else
+            hipLaunchKernelGGL(cov_point_pair_kernel<false>, dim3(n_off), dim3(64), 0, c->st, da, db, c->pt_start, c->obs_cam, c->J8, c->omask, c->Jc12, c->vinv6, c->sig, dout);
+        STBA_HIP(hipGetLastError());
+        STBA_HIP(hipMemcpyAsync(res.data(), dout, (size_t)n_off * 9 * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        STBA_HIP(hipStreamSynchronize(c->st));
+    }
+    if (n_diag > 0) STBA_TRY(cov_point_blocks(c, n_diag, diag_pt.data(), res.data() + (size_t)n_off * 9));
+    for (int q = 0; q < n_off; ++q) std::copy(res.begin() + (size_t)q * 9, res.begin() + (size_t)(q + 1) * 9, out + (size_t)off_pos[q] * 9);
+    for (int q = 0; q < n_diag; ++q)
+        std::copy(res.begin() + (size_t)(n_off + q) * 9, res.begin() + (size_t)(n_off + q + 1) * 9, out + (size_t)diag_pos[q] * 9);
     return STBA_OK;
 }
 

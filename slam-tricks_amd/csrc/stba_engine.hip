@@ -2296,6 +2296,18 @@ int stba_ba_point_covariance(stba_ba* b, int n, const int* pts, double* out) {
     return cov_point_blocks(b->cov, n, pts, out);
 }
 
+int stba_ba_camera_point_covariance(stba_ba* b, int n_pairs, const int* cam, const int* pt, double* out) {
+    if (!b || n_pairs < 0 || (n_pairs > 0 && (!cam || !pt || !out))) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_point_covariance: bad argument");
+    if (!b->cov) return fail(STBA_ERR_STATE, "stba_ba_camera_point_covariance needs stba_ba_covariance_compute first");
+    return cov_cam_point_blocks(b->cov, n_pairs, cam, pt, out);
+}
+
+int stba_ba_point_pair_covariance(stba_ba* b, int n_pairs, const int* pt_a, const int* pt_b, double* out) {
+    if (!b || n_pairs < 0 || (n_pairs > 0 && (!pt_a || !pt_b || !out))) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_point_pair_covariance: bad argument");
+    if (!b->cov) return fail(STBA_ERR_STATE, "stba_ba_point_pair_covariance needs stba_ba_covariance_compute first");
+    return cov_point_pair_blocks(b->cov, n_pairs, pt_a, pt_b, out);
+}
+
 int stba_ba_covariance_release(stba_ba* b) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     cov_store_free(b->cov);
