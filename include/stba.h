@@ -756,6 +756,45 @@ int stba_ba_set_sqrt_information(stba_ba* ba, const double* sqrt_information);  
 int stba_ba_has_information(const stba_ba* ba, int* has);
 int stba_ba_get_sqrt_information(stba_ba* ba, double* out);                     /* [n_obs*4] */
 
+/* ================================ bundle adjustment: camera pose priors ================================ */
+/* A prior k names a camera c_k, a prior pose (qh_k, th_k) -- camera to world, [qx, qy, qz, qw, tx, ty, tz] like the engine's cameras --
+ * and a 6 x 6 square-root information W_k (row-major):
+ *     r_k = [ Log(qh_k^-1 (x) q_c) ; t_c - th_k ]      order [rot(3), pos(3)]: that of cam_fixed and of Jc's columns, NOT the pose
+ *                                                      graph's [rho, theta]
+ *     J_k = d r_k / d[dtheta, dt] = blockdiag(Jr^-1(r_theta), I)   under the engine's chart q <- q (x) exp(dtheta), t <- t + dt
+ *     cost += 1/2 |W_k r_k|^2
+ * Log takes the short way round (q and -q give the same bits), is exact at angle 0 and usable up to the neighbourhood of pi; Jr^-1
+ * is the closed form of SO(3) (a series below 0.1 rad).  GPS / INS / odometry knowledge of a pose, the gauge of a problem that fixes
+ * no camera (two priors make stba_ba_covariance_compute well defined), the prior a marginalised window leaves behind.  Any number of
+ * priors, several on one camera.  Columns of a camera's constant dofs (cam_fixed) are exactly 0: a constant camera's prior adds to
+ * the cost only.
+ *   stba_ba_set_pose_priors   cam[n], pose[n*7], and at most ONE of information[n*36] (symmetric positive definite; the lower triangle
+ *                      is factored on the host, Omega = L L^T, W = L^T, in double-double arithmetic: every entry of W within 4 eps of
+ *                      the exact factor of the matrix given up to cond(Omega) = 1e12; else STBA_ERR_NOT_POSITIVE_DEFINITE) and
+ *                      sqrt_information[n*36] (any finite W, rank-deficient included: zero rotation rows give a position-only prior).
+ *                      Both NULL: the identity.  Quaternions are normalised on the host (one that is unit to 8 eps keeps its bits).
+ *                      n = 0 clears the priors: the engine then enqueues exactly what one that never had any enqueues.
+ *                      STBA_ERR_INVALID_ARGUMENT, stba_last_error() naming the smallest such prior, nothing changed: a camera index
+ *                      out of range, an entry that is not finite, a zero quaternion; also both weight arrays given.
+ *   stba_ba_pose_prior_count  *n = the number of priors held.
+ *   stba_ba_evaluate_pose_priors   at the current parameters: cost = 1/2 sum |W r|^2 of the priors alone, r[n*6] = W_k r_k,
+ *                      J[n*36] = W_k J_k (6 x 6 row-major), in the caller's order; any may be NULL.
+ *   stba_ba_pose_prior_kernel_geometry   DIAGNOSTIC, NOT A STABLE INTERFACE (the tests derive their scenes from it): cameras with
+ *                      priors per workgroup of the block kernel.
+ * With priors, stba_ba_evaluate's and stba_ba_cost's cost, the LM summary and trace and the gradient norm are those of the SUM,
+ * observations plus priors (r, Jc, Jp stay per observation); stba_ba_normal_blocks' Hcc, gc include the priors' J'^T J', J'^T r';
+ * stba_ba_solve / _lm_iterations (LM; PAIRS and DENSE), the stage entry points, stba_ba_covariance_compute and its getters run on
+ * the sum; losses and information matrices on the observations combine freely.  A setter that succeeds invalidates the current
+ * linearisation and releases a held covariance.  LIMITS, refused with STBA_ERR_INVALID_ARGUMENT, the state untouched, in both
+ * orders of the two calls: ITERATIVE_SCHUR engines (the inexact-step model term is summed from the observation records), DOGLEG
+ * (its |J g|^2 is too), inner iterations, a host lineariser, an all-reduce hook / communicator / world_size > 1.
+ * STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_pose_priors(stba_ba* ba, int n, const int* cam, const double* pose /*[n*7]*/,
+                            const double* information /*[n*36] or NULL*/, const double* sqrt_information /*[n*36] or NULL*/);
+int stba_ba_pose_prior_count(const stba_ba* ba, int* n);
+int stba_ba_evaluate_pose_priors(stba_ba* ba, double* cost, double* r /*[n*6]*/, double* J /*[n*36], 6x6 row-major*/);
+int stba_ba_pose_prior_kernel_geometry(const stba_ba* ba, int* cameras_per_workgroup);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

@@ -535,6 +535,92 @@ private:
     double w_[4] = {1.0, 0.0, 0.0, 1.0};
 };
 
+// A prior on a camera's pose, the host form of the device engine's pose-prior factor (stba_ba_set_pose_priors): blocks
+// {SO3 quaternion 4, POS 3} -> 6 residuals r = W [Log(qh^-1 (x) q); t - th], order [rot(3), pos(3)]; W the 6 x 6 row-major
+// square-root information (nullptr: the identity; zero rotation rows: a position-only prior).  The Jacobians are ambient (6 x 4 and
+// 6 x 3): the quaternion's is W[:, :3] Jr^-1(r_theta) P^+ with P = QuaternionRightPlus::ComputeJacobian(q) and P^+ = 4 P^T / |q|^2
+// its left inverse, so that composed with that chart it is W[:, :3] Jr^-1 -- the device factor's J under q <- q (x) exp(delta).
+// Same formulas as the device (slam-tricks_amd/csrc/ba_prior.hpp): the quaternion product with the cancelling products paired (a
+// prior AT the camera's pose has the rotation residual exactly 0 in a build without FMA contraction), theta = 2 atan2(|v|, w) behind
+// the sign choice w >= 0 (q and -q: the same residual), the hat^2 coefficient (1 - (theta / 2) cot(theta / 2)) / theta^2 with
+// cot(theta / 2) = w / |v| (no 0 / 0 at pi), its series below 0.1 rad.
+// On a problem that otherwise takes "gpu-ba", DetectBa sets these blocks aside and Solve / Covariance hand them to the device engine
+// (stba_ba_set_pose_priors), provided the two blocks are the rotation and the position block of ONE camera that some observation
+// names and the block has no LossFunction; otherwise, and on every other route, it is an ordinary host cost function.  With
+// ITERATIVE_SCHUR, DOGLEG or use_inner_iterations the solve is refused (FAILURE, parameters untouched, the reason in the message).
+class PosePriorFactor : public SizedCostFunction<6, 4, 3> {
+public:
+    PosePriorFactor(const double q[4], const double t[3], const double* sqrt_information = nullptr) {
+        // (normalised as stba_ba_set_pose_priors normalises: a quaternion that is unit to 8 eps keeps its bits)
+        const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+        const double sc = std::fabs(n2 - 1.0) <= 8 * 2.220446049250313e-16 ? 1.0 : 1.0 / std::sqrt(n2);
+        for (int k = 0; k < 4; ++k) pose_[k] = q[k] * sc;
+        for (int k = 0; k < 3; ++k) pose_[4 + k] = t[k];
+        for (int k = 0; k < 36; ++k) w_[k] = sqrt_information ? sqrt_information[k] : (k % 7 == 0 ? 1.0 : 0.0);
+        has_w_ = sqrt_information != nullptr;
+    }
+    static PosePriorFactor* Create(const double q[4], const double t[3], const double* sqrt_information = nullptr) {
+        return new PosePriorFactor(q, t, sqrt_information);
+    }
+    const double* pose() const { return pose_; }                                  // [qx qy qz qw tx ty tz], the quaternion normalised
+    const double* sqrt_information() const { return has_w_ ? w_ : nullptr; }      // nullptr: made without one (identity)
+    const double* weights() const { return w_; }                                  // the 36 entries either way
+    // the 6 unwhitened residuals at (q, t) and Jr^-1 of the rotation part (3 x 3 row-major; may be null)
+    void Residual(const double* q, const double* t, double* r, double* Jri) const {
+        const double ax = -pose_[0], ay = -pose_[1], az = -pose_[2], aw = pose_[3];
+        const double bx = q[0], by = q[1], bz = q[2], bw = q[3];
+        double x = (aw * bx + ax * bw) + (ay * bz - az * by);
+        double y = (aw * by + ay * bw) + (az * bx - ax * bz);
+        double z = (aw * bz + az * bw) + (ax * by - ay * bx);
+        double w = ((aw * bw - ax * bx) - ay * by) - az * bz;
+        const double lead = x != 0.0 ? x : (y != 0.0 ? y : z);
+        if (w < 0.0 || (w == 0.0 && lead < 0.0)) { x = -x; y = -y; z = -z; w = -w; }
+        const double n2 = (x * x + y * y) + z * z, n = std::sqrt(n2);
+        double k, cot = 0.0;
+        if (n2 < 1e-40) k = 2.0 / w;
+        else { k = 2.0 * std::atan2(n, w) / n; cot = w / n; }
+        r[0] = k * x; r[1] = k * y; r[2] = k * z;
+        for (int i = 0; i < 3; ++i) r[3 + i] = t[i] - pose_[4 + i];
+        if (!Jri) return;
+        const double th = k * n, t2 = th * th;
+        const double c = th < 0.1 ? 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 * (1.0 / 47900160.0))))
+                                  : (1.0 - (0.5 * th) * cot) / t2;
+        const double pp = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+        const double h[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                const double d = a == b ? 1.0 : 0.0;
+                Jri[a * 3 + b] = (d + 0.5 * h[a * 3 + b]) + c * (r[a] * r[b] - pp * d);
+            }
+    }
+    bool Evaluate(double const* const* p, double* residuals, double** jacobians) const override {
+        const double* q = p[0];
+        double r[6], Jri[9];
+        Residual(q, p[1], r, Jri);
+        for (int i = 0; i < 6; ++i) {
+            const double* wi = w_ + i * 6;
+            residuals[i] = ((((wi[0] * r[0] + wi[1] * r[1]) + wi[2] * r[2]) + wi[3] * r[3]) + wi[4] * r[4]) + wi[5] * r[5];
+        }
+        if (!jacobians) return true;
+        if (jacobians[0]) {
+            double P[12];
+            QuaternionRightPlus().ComputeJacobian(q, P);
+            const double s = 4.0 / (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            for (int i = 0; i < 6; ++i) {
+                double wj[3];       // row i of W[:, :3] Jr^-1
+                for (int a = 0; a < 3; ++a) wj[a] = (w_[i * 6] * Jri[a] + w_[i * 6 + 1] * Jri[3 + a]) + w_[i * 6 + 2] * Jri[6 + a];
+                for (int g = 0; g < 4; ++g) jacobians[0][i * 4 + g] = s * (wj[0] * P[g * 3] + wj[1] * P[g * 3 + 1] + wj[2] * P[g * 3 + 2]);
+            }
+        }
+        if (jacobians[1]) for (int i = 0; i < 6; ++i) for (int a = 0; a < 3; ++a) jacobians[1][i * 3 + a] = w_[i * 6 + 3 + a];
+        return true;
+    }
+private:
+    double pose_[7];
+    double w_[36];
+    bool has_w_ = false;
+};
+
 // ------------------------------------------------------------------------------------------
 // Pose graph through the same operator API (BASELINE config C4; build-defined: the reference has no pose-graph code, the
 // conventions are its Lie-group notes', st23-lie-group-v2/doc.tex:862-996).  A pose is ONE parameter block of 7 doubles
@@ -1168,18 +1254,23 @@ struct BaLayout {
     std::vector<double> sqrt_info;
     std::vector<unsigned char> user;         // per residual block: 1 = a user cost function taken over (0: the built-in factor)
     size_t n_user = 0;
+    // PosePriorFactor blocks, set aside: camera, pose [7], W [36] as stba_ba_set_pose_priors takes them, in the order of
+    // the residual blocks.  obs_res: observation index -> residual block index; EMPTY when the problem has no prior block -- then
+    // observation k IS residual block k, as it always was, and nothing below looks at this
+    std::vector<int> prior_cam, obs_res;
+    std::vector<double> prior_pose, prior_w;
+    const Problem::Residual& res_of(Problem& p, size_t k) const { return p.residuals()[obs_res.empty() ? k : (size_t)obs_res[k]]; }
 };
 
 // every recognised USER block evaluated at the parameter values its blocks hold right now (before the solve: DetectBa; after it: Solve)
 inline bool VerifyRecognisedBlocks(Problem& p, const BaLayout& L, int threads) {
     if (!L.n_user) return true;
-    auto& res = p.residuals();
     auto& blk = p.blocks();
     std::atomic<int> bad{0};
-    ParallelRanges(res.size(), threads, [&](size_t lo, size_t hi) {
+    ParallelRanges(L.obs_cam.size(), threads, [&](size_t lo, size_t hi) {
         for (size_t k = lo; k < hi; ++k) {
             if (!L.user[k]) continue;
-            const auto& r = res[k];
+            const auto& r = L.res_of(p, k);
             if (!ReprojectionValueAtData(r.cost, blk[r.blocks[0]].ptr, blk[r.blocks[1]].ptr, blk[r.blocks[2]].ptr, &L.feat[2 * k])) { bad.store(1); return; }
         }
     });
@@ -1190,13 +1281,12 @@ inline bool VerifyRecognisedBlocks(Problem& p, const BaLayout& L, int threads) {
 // data.  10^6 blocks = 2 x 10^6 calls of the user's Evaluate, on the calling thread (options.num_threads of them): the one part of the
 // recognition that costs time -- Solve runs it while a helper thread creates the device engine (SolveBa).
 inline bool DetectBaBlocks(Problem& p, BaLayout* L, int threads) {
-    auto& res = p.residuals();
     auto& blk = p.blocks();
     std::atomic<int> bad{0};
-    ParallelRanges(res.size(), threads, [&](size_t lo, size_t hi) {
+    ParallelRanges(L->obs_cam.size(), threads, [&](size_t lo, size_t hi) {
         for (size_t k = lo; k < hi; ++k) {
             if (!L->user[k]) continue;
-            const auto& r = res[k];
+            const auto& r = L->res_of(p, k);
             if (!CanonicalFeature(r.cost, &L->feat[2 * k]) ||
                 !ReprojectionValueAtData(r.cost, blk[r.blocks[0]].ptr, blk[r.blocks[1]].ptr, blk[r.blocks[2]].ptr, &L->feat[2 * k])) { bad.store(1); return; }
         }
@@ -1216,12 +1306,24 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
     std::vector<int> cam_of_rot(blk.size(), -1), cam_of_pos(blk.size(), -1), pt_of(blk.size(), -1);
     L->obs_cam.resize(nr); L->obs_pt.resize(nr); L->feat.assign(2 * nr, 0.0); L->user.assign(nr, 0); L->n_user = 0;
     L->sqrt_info.clear();
+    L->prior_cam.clear(); L->obs_res.clear(); L->prior_pose.clear(); L->prior_w.clear();
     const std::type_info* last_type = nullptr;
     bool last_builtin = false;
     std::vector<std::pair<const std::type_info*, const CostFunction*>> first_of_type;
-    for (size_t k = 0; k < nr; ++k) {
-        const auto& r = res[k];
-        if (r.blocks.size() != 3 || !IsReprojectionShape(r.cost)) return false;
+    // PosePriorFactor blocks are set aside (their residual block index and their two parameter blocks, resolved to a camera behind
+    // the loop): from the first one on, observation k (the index of every per-observation array) is no longer residual block kr
+    std::vector<size_t> prior_res;
+    size_t k = 0;
+    for (size_t kr = 0; kr < nr; ++kr) {
+        const auto& r = res[kr];
+        if (r.blocks.size() != 3 || !IsReprojectionShape(r.cost)) {
+            // (probe = false is the host-lineariser route, which has no priors: such a problem is not BA-shaped there, as before)
+            if (!probe || r.blocks.size() != 2 || r.loss || !dynamic_cast<const PosePriorFactor*>(r.cost)) return false;
+            if (prior_res.empty()) { L->obs_res.resize(k); for (size_t i = 0; i < k; ++i) L->obs_res[i] = (int)i; }
+            prior_res.push_back(kr);
+            continue;
+        }
+        if (!prior_res.empty()) L->obs_res.push_back((int)kr);
         if (probe) {
             const std::type_info& ti = typeid(*r.cost);
             if (!last_type || !(ti == *last_type)) {
@@ -1258,6 +1360,27 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
         int j = pt_of[b2];
         if (j < 0) { j = (int)L->pt_block.size(); pt_of[b2] = j; L->pt_block.push_back(b2); }
         L->obs_cam[k] = c; L->obs_pt[k] = j;
+        ++k;
+    }
+    if (!prior_res.empty()) {
+        const size_t no = k;
+        if (no == 0) return false;
+        L->obs_cam.resize(no); L->obs_pt.resize(no); L->feat.resize(2 * no); L->user.resize(no);
+        if (!L->sqrt_info.empty()) {
+            // (filled at 4 * observation index, but made for nr rows with the identity: cut to the observations)
+            L->sqrt_info.resize(4 * no);
+        }
+        for (size_t kr : prior_res) {
+            // a prior's two blocks must be the rotation and the position block of ONE camera that some observation names
+            const auto& r = res[kr];
+            const int b0 = r.blocks[0], b1 = r.blocks[1];
+            const int c = cam_of_rot[(size_t)b0];
+            if (c < 0 || L->pos_block[(size_t)c] != b1) return false;
+            auto* f = static_cast<const PosePriorFactor*>(r.cost);
+            L->prior_cam.push_back(c);
+            L->prior_pose.insert(L->prior_pose.end(), f->pose(), f->pose() + 7);
+            L->prior_w.insert(L->prior_w.end(), f->weights(), f->weights() + 36);
+        }
     }
     for (size_t c = 0; c < L->rot_block.size(); ++c)                // a block cannot be a rotation AND a landmark / position
         if (pt_of[(size_t)L->rot_block[c]] >= 0 || pt_of[(size_t)L->pos_block[c]] >= 0 || cam_of_pos[(size_t)L->rot_block[c]] >= 0) return false;
@@ -1398,7 +1521,9 @@ inline bool BaLossTable(Problem& p, BaLayout* L) {
     L->loss_kind.clear(); L->loss_a.clear(); L->loss_b.clear(); L->loss_scale.clear();
     if (p.NumLossFunctions() == 0) return true;
     bool known = true;
-    for (const auto& r : p.residuals()) {
+    const size_t no = L->obs_res.empty() ? p.residuals().size() : L->obs_res.size();      // (prior blocks carry no loss: DetectBa)
+    for (size_t k = 0; k < no; ++k) {
+        const auto& r = L->res_of(p, k);
         int kind = STBA_LOSS_TRIVIAL;
         double a = 1.0, b = 1.0, scale = 1.0;
         if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) known = false;
@@ -1496,6 +1621,14 @@ inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Sol
     }
     if (!L.loss_kind.empty() && (rc = stba_ba_set_loss(sync.ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
         sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_loss: ") + stba_last_error();
+        stba_ba_destroy(sync.ba);
+        return false;
+    }
+    // (PosePriorFactor blocks: the engine refuses them on an ITERATIVE_SCHUR engine here, and DOGLEG / inner iterations below refuse
+    // an engine that holds them -- each before any solve, the parameters untouched, the engine's reason in the message)
+    if (!L.prior_cam.empty() && (rc = stba_ba_set_pose_priors(sync.ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
+                                                              L.prior_w.data())) != STBA_OK) {
+        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_pose_priors: ") + stba_last_error();
         stba_ba_destroy(sync.ba);
         return false;
     }
@@ -1837,8 +1970,13 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         BaLayout shape_only;
         if (options.dogleg_type != TRADITIONAL_DOGLEG) why = "SUBSPACE_DOGLEG is not implemented by this layer (TRADITIONAL_DOGLEG is)";
         else if (options.linear_solver_type == ITERATIVE_SCHUR) why = "DOGLEG only supports exact factorization based linear solvers, not ITERATIVE_SCHUR";
-        else if (!DetectBa(*problem, &shape_only, false))
-            why = "DOGLEG is implemented for bundle adjustment (gpu-ba, gpu-ba-hostjac) only, not for problems that take gpu-pg or gpu-dense-callback";
+        else if (!DetectBa(*problem, &shape_only, false)) {
+            BaLayout with_priors;
+            if (DetectBa(*problem, &with_priors, true, 1, true) && !with_priors.prior_cam.empty())
+                why = "DOGLEG with PosePriorFactor blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)";
+            else
+                why = "DOGLEG is implemented for bundle adjustment (gpu-ba, gpu-ba-hostjac) only, not for problems that take gpu-pg or gpu-dense-callback";
+        }
         if (why) {
             summary->termination_type = FAILURE;
             summary->message = std::string("stba_ceres: ") + why + " -- nothing was solved.";
@@ -1857,8 +1995,11 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
         bool shape = DetectBa(*problem, &shape_only, false);
         if (shape)
             for (int rb : shape_only.rot_block) shape = shape && UsesQuaternionRightPlus(problem->blocks()[rb].local);
+        BaLayout with_priors;
         if (options.trust_region_strategy_type == DOGLEG) why = "inner iterations are not implemented with DOGLEG";
         else if (!(options.inner_iteration_tolerance >= 0.0)) why = "inner_iteration_tolerance must be >= 0";
+        else if (!shape && DetectBa(*problem, &with_priors, true, 1, true) && !with_priors.prior_cam.empty())
+            why = "inner iterations with PosePriorFactor blocks are not implemented";
         else if (!shape)
             why = "inner iterations are implemented for bundle adjustment on the gpu-ba path only, not for problems that take gpu-pg or gpu-dense-callback";
         else if (force_cb) why = "inner iterations are implemented on the gpu-ba path only, not on gpu-ba-hostjac (force_callback_path)";
@@ -2199,6 +2340,9 @@ private:
             return Fail(std::string("stba_ba_set_sqrt_information: ") + stba_last_error());
         if (!host && !L.loss_kind.empty() && stba_ba_set_loss(ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
             return Fail(std::string("stba_ba_set_loss: ") + stba_last_error());
+        if (!L.prior_cam.empty() && stba_ba_set_pose_priors(ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
+                                                            L.prior_w.data()) != STBA_OK)
+            return Fail(std::string("stba_ba_set_pose_priors: ") + stba_last_error());
         BaHostCtx hctx{p, &L, options_.num_threads};
         if (host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, &hctx) != STBA_OK) return Fail(std::string("stba_ba_set_host_linearizer: ") + stba_last_error());
         double rc = 0.0;

@@ -86,7 +86,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information",
            "stba_pg_set_loss", "stba_pg_has_loss",
            "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry",
-           "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information"]
+           "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information",
+           "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry"]
 
 
 def lib():
@@ -232,10 +233,10 @@ class BAEngine:
     implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
 
     def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur",
-                 loss=None, information=None, sqrt_information=None):
+                 loss=None, information=None, sqrt_information=None, pose_priors=None):
         """loss: per-observation robust losses as PGEngine takes them -- a kind name, a tuple (kind, a[, b[, scale]]) or a dict of
         set_loss's arguments.  information / sqrt_information (one of the two): per-observation 2 x 2 weights, the shapes that
-        set_information takes"""
+        set_information takes.  pose_priors: dict(cams=, poses=, information= | sqrt_information=), set_pose_priors' arguments"""
         if information is not None and sqrt_information is not None:
             raise ValueError("BAEngine: give information or sqrt_information, not both")
         self._h = C.c_void_p()
@@ -268,6 +269,8 @@ class BAEngine:
             _chk(getattr(lib(), weights[0])(self._h, _p(weights[1])), weights[0])
         if table is not None:
             self._set_loss_table(table)
+        if pose_priors is not None:
+            self.set_pose_priors(**pose_priors)
 
     def close(self):
         if self._h:
@@ -372,6 +375,56 @@ class BAEngine:
         out = np.empty((self.no, 2, 2))
         _chk(lib().stba_ba_get_sqrt_information(self._h, _p(out)), "stba_ba_get_sqrt_information")
         return out
+
+    # ---- camera pose priors
+    def set_pose_priors(self, cams, poses, information=None, sqrt_information=None):
+        """soft constraints on camera poses (stba_ba_set_pose_priors): prior k pulls camera cams[k] towards poses[k] = [qx, qy, qz, qw,
+        tx, ty, tz] (camera to world, like the engine's cameras) with cost 1/2 |W_k r_k|^2, r_k = [Log(qh^-1 q); t - th] in the order
+        [rot(3), pos(3)].  information: (n, 6, 6) symmetric positive definite (W = L^T of its Cholesky factor) or sqrt_information:
+        (n, 6, 6) any finite W (zero rotation rows: a position-only prior); a single (6, 6) is taken for every prior; neither: the
+        identity.  Several priors may name one camera.  cams empty (or None) clears the priors."""
+        if information is not None and sqrt_information is not None:
+            raise ValueError("BAEngine: give information or sqrt_information, not both")
+        c = np.ascontiguousarray([] if cams is None else cams, dtype=np.int32).reshape(-1)
+        n = len(c)
+        if n == 0:
+            _chk(lib().stba_ba_set_pose_priors(self._h, 0, None, None, None, None), "stba_ba_set_pose_priors")
+            return
+        ps = _f64(poses).reshape(-1, 7)
+        if len(ps) != n:
+            raise ValueError(f"BAEngine: {n} prior cameras but {len(ps)} prior poses")
+
+        def blocks(w, name):
+            if w is None:
+                return None
+            w = np.asarray(w, np.float64)
+            if w.shape == (6, 6):
+                w = np.broadcast_to(w, (n, 6, 6))
+            if w.shape != (n, 6, 6):
+                raise ValueError(f"BAEngine: pose-prior {name} must have shape (6, 6) or ({n}, 6, 6), got {w.shape}")
+            return np.ascontiguousarray(w)
+        om, w = blocks(information, "information"), blocks(sqrt_information, "sqrt_information")
+        _chk(lib().stba_ba_set_pose_priors(self._h, n, _p(c), _p(ps), _p(om), _p(w)), "stba_ba_set_pose_priors")
+
+    def pose_prior_count(self):
+        n = C.c_int()
+        _chk(lib().stba_ba_pose_prior_count(self._h, C.byref(n)), "stba_ba_pose_prior_count")
+        return n.value
+
+    def evaluate_pose_priors(self, jac=True):
+        """(cost, r [n, 6], J [n, 6, 6] | None) of the priors alone at the current parameters: whitened, in the order they were set"""
+        n = self.pose_prior_count()
+        cost = C.c_double()
+        r = np.zeros((n, 6))
+        J = np.zeros((n, 6, 6)) if jac else None
+        _chk(lib().stba_ba_evaluate_pose_priors(self._h, C.byref(cost), _p(r), _p(J)), "stba_ba_evaluate_pose_priors")
+        return cost.value, r, J
+
+    def pose_prior_kernel_geometry(self):
+        """cameras with priors per workgroup of the block kernel (a diagnostic: stba_ba_pose_prior_kernel_geometry)"""
+        k = C.c_int()
+        _chk(lib().stba_ba_pose_prior_kernel_geometry(self._h, C.byref(k)), "stba_ba_pose_prior_kernel_geometry")
+        return k.value
 
     def loss_kernel_geometry(self):
         """(observations per workgroup tile of the correcting linearisation kernel, whether this engine's cameras are staged in its

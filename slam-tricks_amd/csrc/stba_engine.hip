@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "ba_prior.hpp"
 #include "iterative_schur.hpp"
 #include "dogleg.hpp"
 #include "inner_iterations.hpp"
@@ -181,6 +182,18 @@ struct stba_ba {
     double *inner_sc = nullptr, *inner_part = nullptr;
     hipEvent_t inner_ev[2] = {};
     stba_inner_summary inner_sum{};
+    // camera pose priors (stba_ba_set_pose_priors; ba_prior.hip): grouped by camera -- CSR over the cameras that have
+    // any, inside a group the caller's order -- with the poses (quaternions normalised) and the 6 x 6 square-root informations in
+    // that order; prior_order: grouped position -> the caller's index.  With priors the cost partials carry ONE more slot behind
+    // the lineariser's lin_grid (n_cost), filled by the cost form at every linearisation; the block form adds to Hcc, gc behind the
+    // Schur step at lin_which, the parameter buffer the Jacobian records were last made at
+    int n_prior = 0, n_prior_groups = 0;
+    int *prior_ptr = nullptr, *prior_cam = nullptr;
+    double *prior_pose = nullptr, *prior_W = nullptr;
+    std::vector<int> prior_order;
+    int lin_which = 0;
+    int n_cost() const { return lin_grid + (n_prior ? 1 : 0); }
+    PriorArgs prior_args() const { return PriorArgs{n_prior_groups, prior_ptr, prior_cam, prior_pose, prior_W, cam_fixed}; }
 
     size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
     double* S() const { return iterative ? nullptr : Sbuf; }
@@ -222,6 +235,7 @@ static void ba_free(stba_ba* b) {
     b->pcg_host.release();
     F(b->dl_uc); F(b->dl_up); F(b->dl_part); F(b->dl_sc);
     b->dl_host.release();
+    F(b->prior_ptr); F(b->prior_cam); F(b->prior_pose); F(b->prior_W);
     F(b->inner_cam); F(b->inner_pt); F(b->inner_it); F(b->inner_gate); F(b->inner_mask); F(b->inner_sc); F(b->inner_part);
     for (auto& e : b->inner_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
@@ -294,21 +308,33 @@ static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->lo
 static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
     if (b->hl_fn) return ba_host_linearize(b, which, with_jac);
     const LinArgs a = lin_args(b, which, with_jac);
+    if (with_jac) b->lin_which = which;
     if (b->loss_kind || b->winfo)
-        return launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12, b->winfo}, with_jac, b->lin_grid, b->st);
-    return launch_linearize(a, with_jac, b->lin_grid, b->st);
+        STBA_TRY(launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12, b->winfo}, with_jac, b->lin_grid, b->st));
+    else
+        STBA_TRY(launch_linearize(a, with_jac, b->lin_grid, b->st));
+    // pose priors: their cost at the same parameters into the slot behind the lineariser's partials (one launch; n_cost counts it)
+    if (b->n_prior) STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[which], b->cost_partial + b->lin_grid, b->st));
+    return STBA_OK;
+}
+
+// pose priors: sum J'^T J' into Hcc and sum J'^T r' into gc, at the parameters the Jacobian records were made at (one launch; none
+// without priors).  Behind whatever has just WRITTEN the camera blocks: the Schur step or the camera-block kernel
+static int ba_prior_blocks(stba_ba* b) {
+    if (!b->n_prior) return STBA_OK;
+    return launch_prior_blocks(b->prior_args(), b->cams[b->lin_which], b->Hcc, b->gc, nullptr, nullptr, b->st);
 }
 
 // residuals + Jacobians at parameter buffer `which`; sum r^2 -> *cost2_dev
 static int ba_linearize(stba_ba* b, int which, double* cost2_dev) {
     STBA_TRY(ba_linearize_dispatch(b, which, true));
-    return launch_sum_partials(b->cost_partial, b->lin_grid, 1, 1, cost2_dev, b->st);
+    return launch_sum_partials(b->cost_partial, b->n_cost(), 1, 1, cost2_dev, b->st);
 }
 
 // residual-only kernel (nothing stored): sum r^2 -> *cost2_dev
 static int ba_cost_only(stba_ba* b, int which, double* cost2_dev) {
     STBA_TRY(ba_linearize_dispatch(b, which, false));
-    return launch_sum_partials(b->cost_partial, b->lin_grid, 1, 1, cost2_dev, b->st);
+    return launch_sum_partials(b->cost_partial, b->n_cost(), 1, 1, cost2_dev, b->st);
 }
 
 // landmark blocks Hpp, gp.  The CAMERA blocks Hcc, gc are made by the Schur kernel on the way (ba_build_reduced: the
@@ -476,6 +502,7 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm) {
     }
     // S is zeroed (pair plan) or overwritten (dense product) by the Schur step itself
     STBA_TRY(ba_schur_step(b));
+    STBA_TRY(ba_prior_blocks(b));
     if (!b->ar && !dm.explicit_d && b->n == 6 * b->nc) {
         // one rank: camera blocks, LM diagonal, damping and padding in one launch
         STBA_TRY(launch_reduced_finalize(b->nc, b->n, b->Hcc, b->gc, b->cam_fixed, b->S(), b->lda, b->rhs(), b->ex_diag(), b->ex_gc(),
@@ -525,7 +552,7 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm) {
 // (behind ba_linearize_lm + ba_normal_blocks: the cost of the linearisation point -> *cost2_dev and the cost slot, the
 // |gp| maxima of the landmark-block workgroups -> this rank's slot, the rest of the scalar block zeroed)
 static int ba_fill_scalar_slots(stba_ba* b, double* cost2_dev) {
-    return launch_linear_finish(b->cost_partial, b->lin_grid, b->upd_partial_p, point_blocks_grid(b->np), cost2_dev, b->ex_scalar(), b->lda,
+    return launch_linear_finish(b->cost_partial, b->n_cost(), b->upd_partial_p, point_blocks_grid(b->np), cost2_dev, b->ex_scalar(), b->lda,
                                 SC_COST2, SC_GPMAX0 + b->rank, b->st);
 }
 
@@ -566,7 +593,7 @@ static int ba_trial(stba_ba* b, double* host_out, bool updated = false, bool wit
                   TS_SPEC_COST2 == 8 && TS_LIN_COST2 == 9 && TS_LIN_GMAX == 10 && TS_BLOCK == 11, "trial_finish_kernel writes this layout");
     if (with_jac) STBA_TRY(ba_linearize_lm(b, nxt));
     else STBA_TRY(ba_linearize_dispatch(b, nxt, false));
-    STBA_TRY(launch_trial_finish(b->cost_partial, b->lin_grid, b->upd_partial_p, b->np > 0 ? pb : 0, b->upd_partial_c, cb, b->flag,
+    STBA_TRY(launch_trial_finish(b->cost_partial, b->n_cost(), b->upd_partial_p, b->np > 0 ? pb : 0, b->upd_partial_c, cb, b->flag,
                                  b->ex_scalar() + SC_COST2, b->ex_scalar() + SC_GPMAX0, b->world, b->ex_gc(), b->n, b->trial,
                                  b->ar ? nullptr : host_out, host_seq, b->st));
     if (b->ar) {
@@ -1469,7 +1496,7 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     A_(dev_alloc(&b->dc, nc * 6)); A_(dev_alloc(&b->scale_c, nc * 6));
     A_(dev_alloc(&b->Sbuf, b->sbuf_count()));
     A_(dev_alloc(&b->dxc, (size_t)b->lda)); A_(dev_alloc(&b->dxp, np * 3));
-    A_(dev_alloc(&b->cost_partial, (size_t)b->lin_grid));
+    A_(dev_alloc(&b->cost_partial, (size_t)b->lin_grid + 1));     // (+ 1: the pose priors' slot, see n_cost)
     A_(dev_alloc(&b->upd_partial_c, (size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
     A_(dev_alloc(&b->upd_partial_p, (size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
     A_(dev_alloc(&b->trial, (size_t)TS_BLOCK)); A_(dev_alloc(&b->flag, 1));
@@ -1692,6 +1719,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
     if (fn && b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has inner iterations (device residuals only)");
     if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
     if (fn && b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has information matrices (the callback's factors whiten themselves; not supported together)");
+    if (fn && b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has pose priors (priors need device residuals; not supported together)");
     if (fn && !b->Jc12) STBA_TRY(dev_alloc(&b->Jc12, (size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
@@ -1857,6 +1885,138 @@ int stba_ba_get_sqrt_information(stba_ba* b, double* out) {
     return STBA_OK;
 }
 
+// ---- camera pose priors.  Everything is checked -- and, for the information form, factored -- on the host BEFORE
+// anything is replaced; the priors are grouped by camera (a stable sort: inside a group the caller's order), uploaded into NEW arrays
+// that are swapped in.  n == 0 releases them: the engine then enqueues exactly what one that never had priors enqueues
+int stba_ba_set_pose_priors(stba_ba* b, int n, const int* cam, const double* pose, const double* information, const double* sqrt_information) {
+    const std::string who = "stba_ba_set_pose_priors";
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
+    if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
+    if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
+    int *ptr_new = nullptr, *cam_new = nullptr;
+    double *pose_new = nullptr, *w_new = nullptr;
+    std::vector<int> order;
+    int n_groups = 0;
+    if (n > 0) {
+        if (!cam || !pose) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null cam or pose array");
+        if (b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses ITERATIVE_SCHUR (its inexact-step model is summed from the observation records; pose priors are not supported)");
+        if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses DOGLEG (DOGLEG with pose priors is not supported)");
+        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has inner iterations (inner iterations with pose priors are not supported)");
+        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has a host lineariser (priors need device residuals; not supported together)");
+        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has an all-reduce hook, and pose priors run on one rank only");
+        const size_t m = (size_t)n;
+        std::vector<double> hp(m * 7), hw(m * 36);
+        for (size_t k = 0; k < m; ++k) {
+            const std::string at = who + ": prior " + std::to_string(k) + ": ";
+            if (cam[k] < 0 || cam[k] >= b->nc) return fail(STBA_ERR_INVALID_ARGUMENT, at + "camera index " + std::to_string(cam[k]) + " out of range");
+            for (int j = 0; j < 7; ++j)
+                if (!std::isfinite(pose[k * 7 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the pose has an entry that is not finite");
+            const double* q = pose + k * 7;
+            const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+            if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(STBA_ERR_INVALID_ARGUMENT, at + "zero quaternion");
+            // (a quaternion that is unit to rounding keeps its bits: a prior AT a camera's pose then has the residual exactly 0)
+            const double sc = std::fabs(n2 - 1.0) <= 8 * 2.220446049250313e-16 ? 1.0 : 1.0 / std::sqrt(n2);
+            for (int j = 0; j < 4; ++j) hp[k * 7 + j] = q[j] * sc;
+            for (int j = 4; j < 7; ++j) hp[k * 7 + j] = q[j];
+            if (sqrt_information) {
+                for (int j = 0; j < 36; ++j) {
+                    if (!std::isfinite(sqrt_information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the square-root information has an entry that is not finite");
+                    hw[k * 36 + j] = sqrt_information[k * 36 + j];
+                }
+            } else if (information) {
+                for (int j = 0; j < 36; ++j)
+                    if (!std::isfinite(information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the information matrix has an entry that is not finite");
+                if (!prior_information_factor(information + k * 36, &hw[k * 36]))
+                    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, at + "the information matrix is not positive definite");
+            } else {
+                for (int j = 0; j < 36; ++j) hw[k * 36 + j] = (j % 7 == 0) ? 1.0 : 0.0;
+            }
+        }
+        order.resize(m);
+        for (size_t k = 0; k < m; ++k) order[k] = (int)k;
+        std::stable_sort(order.begin(), order.end(), [cam](int x, int y) { return cam[x] < cam[y]; });
+        std::vector<int> gptr, gcam;
+        std::vector<double> gp(m * 7), gw(m * 36);
+        for (size_t p = 0; p < m; ++p) {
+            const size_t k = (size_t)order[p];
+            if (p == 0 || cam[k] != gcam.back()) { gptr.push_back((int)p); gcam.push_back(cam[k]); }
+            memcpy(&gp[p * 7], &hp[k * 7], 7 * sizeof(double));
+            memcpy(&gw[p * 36], &hw[k * 36], 36 * sizeof(double));
+        }
+        gptr.push_back(n);
+        n_groups = (int)gcam.size();
+        auto F = [](void* p) { if (p) (void)hipFree(p); };
+        int rc = dev_alloc(&ptr_new, gptr.size());
+        if (rc == STBA_OK) rc = dev_alloc(&cam_new, gcam.size());
+        if (rc == STBA_OK) rc = dev_alloc(&pose_new, m * 7);
+        if (rc == STBA_OK) rc = dev_alloc(&w_new, m * 36);
+        if (rc == STBA_OK &&
+            (hipMemcpyAsync(ptr_new, gptr.data(), gptr.size() * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(cam_new, gcam.data(), gcam.size() * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(pose_new, gp.data(), m * 7 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipMemcpyAsync(w_new, gw.data(), m * 36 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
+             hipStreamSynchronize(b->st) != hipSuccess))
+            rc = fail(STBA_ERR_HIP, who + ": upload failed");
+        if (rc != STBA_OK) { F(ptr_new); F(cam_new); F(pose_new); F(w_new); return rc; }
+    }
+    // (nothing of the engine may still be reading the old priors or what was linearised with them)
+    STBA_HIP(hipStreamSynchronize(b->st));
+    for (void* p : {(void*)b->prior_ptr, (void*)b->prior_cam, (void*)b->prior_pose, (void*)b->prior_W}) if (p) (void)hipFree(p);
+    b->prior_ptr = ptr_new; b->prior_cam = cam_new; b->prior_pose = pose_new; b->prior_W = w_new;
+    b->n_prior = n; b->n_prior_groups = n_groups;
+    b->prior_order = std::move(order);
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    return STBA_OK;
+}
+
+int stba_ba_pose_prior_count(const stba_ba* b, int* n) {
+    if (!b || !n) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_pose_prior_count: null argument");
+    *n = b->n_prior;
+    return STBA_OK;
+}
+
+int stba_ba_pose_prior_kernel_geometry(const stba_ba* b, int* cameras_per_workgroup) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_pose_prior_kernel_geometry: null engine");
+    if (cameras_per_workgroup) *cameras_per_workgroup = PRIOR_CAMS_PER_WG;
+    return STBA_OK;
+}
+
+// the whitened residuals and Jacobians of the priors at the current parameters, by the block kernel itself (no blocks written),
+// and their cost by the cost kernel; the caller's order.  The engine's linearisation state is not touched
+int stba_ba_evaluate_pose_priors(stba_ba* b, double* cost, double* r, double* J) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_evaluate_pose_priors: null engine");
+    if (cost) *cost = 0.0;
+    if (!b->n_prior) return STBA_OK;
+    const size_t m = (size_t)b->n_prior;
+    double *dr = nullptr, *dj = nullptr, *dcost = nullptr;
+    struct TmpGuard { double*& a; double*& c; double*& d; ~TmpGuard() { if (a) (void)hipFree(a); if (c) (void)hipFree(c); if (d) (void)hipFree(d); } } guard{dr, dj, dcost};
+    std::vector<double> hr, hj;
+    double c2 = 0.0;
+    if (r || J) {
+        STBA_TRY(dev_alloc(&dr, m * 6));
+        STBA_TRY(dev_alloc(&dj, m * 36));
+        STBA_TRY(launch_prior_blocks(b->prior_args(), b->cams[b->cur], nullptr, nullptr, dr, dj, b->st));
+        hr.resize(m * 6); hj.resize(m * 36);
+        STBA_TRY(download(hr.data(), dr, m * 6, b->st));
+        STBA_TRY(download(hj.data(), dj, m * 36, b->st));
+    }
+    if (cost) {
+        STBA_TRY(dev_alloc(&dcost, 1));
+        STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[b->cur], dcost, b->st));
+        STBA_TRY(download(&c2, dcost, 1, b->st));
+    }
+    STBA_HIP(hipStreamSynchronize(b->st));
+    if (cost) *cost = 0.5 * c2;
+    for (size_t p = 0; p < m && (r || J); ++p) {
+        const size_t k = (size_t)b->prior_order[p];
+        if (r) memcpy(r + k * 6, &hr[p * 6], 6 * sizeof(double));
+        if (J) memcpy(J + k * 36, &hj[p * 36], 36 * sizeof(double));
+    }
+    return STBA_OK;
+}
+
 int stba_ba_has_loss(const stba_ba* b, int* has) {
     if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_loss: null argument");
     *has = b->loss_kind ? 1 : 0;
@@ -1881,6 +2041,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has a loss table, and losses run on one rank only");
     if (b && b->winfo && (fn || world_size > 1))
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has information matrices, which run on one rank only");
+    if (b && b->n_prior && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has pose priors, which run on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -1945,6 +2107,7 @@ int stba_ba_normal_blocks(stba_ba* b, double* Hcc, double* gc, double* Hpp, doub
     if (!b->have_lin) return fail(STBA_ERR_STATE, "stba_ba_normal_blocks needs stba_ba_evaluate first");
     STBA_TRY(ba_normal_blocks(b));
     STBA_TRY(ba_camera_blocks(b));
+    STBA_TRY(ba_prior_blocks(b));
     std::vector<double> h6;
     if (Hcc) STBA_TRY(download(Hcc, b->Hcc, (size_t)b->nc * 36, b->st));
     if (gc) STBA_TRY(download(gc, b->gc, (size_t)b->nc * 6, b->st));
@@ -2055,6 +2218,7 @@ int stba_ba_set_trust_region(stba_ba* b, int strategy) {
             return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG only supports exact factorization based linear solvers "
                         "(this engine uses ITERATIVE_SCHUR)");
         if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG runs on one rank only (an all-reduce hook is set)");
+        if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: this engine has pose priors (DOGLEG with pose priors is not supported)");
     }
     b->trust_region = strategy;
     return STBA_OK;
@@ -2084,6 +2248,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: not with a host lineariser");
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has a loss table (inner iterations with losses are not supported)");
     if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has information matrices (inner iterations with information matrices are not supported)");
+    if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has pose priors (inner iterations with pose priors are not supported)");
     const int nc = b->nc, np = b->np, no = b->no;
     // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
     std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
@@ -2176,6 +2341,7 @@ int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int
     if (b->ar || b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: one rank, device residuals only");
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has a loss table (inner iterations with losses are not supported)");
     if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has information matrices (inner iterations with information matrices are not supported)");
+    if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has pose priors (inner iterations with pose priors are not supported)");
     const bool was_on = b->inner_on;
     if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
     STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
