@@ -505,15 +505,45 @@ void orc_ba_normal_blocks(const orc_ba_problem* p, const double* r, const double
     }
 }
 
+/* inverse of the SPD 3x3 A (row-major) as the device forms it (spd3_inverse, small_linalg.hpp): power-of-two scaling to a
+ * diagonal in [0.5, 2), Cholesky with the better determined of rows 1 and 2 taken second, the factor inverted by substitution,
+ * A^-1 = S L^-T L^-1 S.  Returns 1 (Ai untouched) where a pivot is below 16 eps of its diagonal entry. */
 static int inv3_sym(const double A[9], double Ai[9]) {
-    const double a = A[0], b = A[1], c = A[2], d = A[4], e = A[5], f = A[8];
-    const double C00 = d * f - e * e, C01 = c * e - b * f, C02 = b * e - c * d;
-    const double det = a * C00 + b * C01 + c * C02;
-    if (!(det > 0) || !isfinite(det)) return 1;
-    const double inv = 1.0 / det;
-    Ai[0] = C00 * inv; Ai[1] = C01 * inv; Ai[2] = C02 * inv;
-    Ai[3] = Ai[1]; Ai[4] = (a * f - c * c) * inv; Ai[5] = (b * c - a * e) * inv;
-    Ai[6] = Ai[2]; Ai[7] = Ai[5]; Ai[8] = (a * d - b * b) * inv;
+    const double tol = 16.0 * 2.220446049250313e-16;
+    if (!(A[0] > 0) || !(A[4] > 0) || !(A[8] > 0) || !(A[0] < 1e300) || !(A[4] < 1e300) || !(A[8] < 1e300)) return 1;
+    int e0, e1, e2;
+    frexp(A[0], &e0); frexp(A[4], &e1); frexp(A[8], &e2);
+    const double s0 = ldexp(1.0, -(e0 >> 1));
+    double s1 = ldexp(1.0, -(e1 >> 1)), s2 = ldexp(1.0, -(e2 >> 1));
+    const double b00 = A[0] * s0 * s0, b12 = A[5] * s1 * s2;
+    double b11 = A[4] * s1 * s1, b22 = A[8] * s2 * s2;
+    const double l00 = sqrt(b00), m00 = 1.0 / l00;
+    double l10 = (A[1] * s0 * s1) * m00, l20 = (A[2] * s0 * s2) * m00;
+    double d1 = b11 - l10 * l10;
+    const double d1alt = b22 - l20 * l20;
+    const int swap = d1alt * b11 > d1 * b22;
+    if (swap) {
+        double t;
+        t = s1; s1 = s2; s2 = t;
+        t = b11; b11 = b22; b22 = t;
+        t = l10; l10 = l20; l20 = t;
+        d1 = d1alt;
+    }
+    if (!(d1 > tol * b11)) return 1;
+    const double l11 = sqrt(d1), m11 = 1.0 / l11;
+    const double l21 = (b12 - l20 * l10) * m11;
+    const double d2 = (b22 - l20 * l20) - l21 * l21;
+    if (!(d2 > tol * b22)) return 1;
+    const double l22 = sqrt(d2), m22 = 1.0 / l22;
+    const double m10 = -(l10 * m00) * m11;
+    const double m21 = -(l21 * m11) * m22;
+    const double m20 = -(l20 * m00 + l21 * m10) * m22;
+    const double r00 = m00 * s0, r01 = m10 * s0, r02 = m20 * s0, r11 = m11 * s1, r12 = m21 * s1, r22 = m22 * s2;
+    const double i00 = r00 * r00 + r01 * r01 + r02 * r02, i01 = r01 * r11 + r02 * r12, i02 = r02 * r22;
+    const double i11 = r11 * r11 + r12 * r12, i12 = r12 * r22, i22 = r22 * r22;
+    Ai[0] = i00; Ai[1] = swap ? i02 : i01; Ai[2] = swap ? i01 : i02;
+    Ai[3] = Ai[1]; Ai[4] = swap ? i22 : i11; Ai[5] = i12;
+    Ai[6] = Ai[2]; Ai[7] = Ai[5]; Ai[8] = swap ? i11 : i22;
     return 0;
 }
 

@@ -23,6 +23,7 @@
 
 #include "ba_kernels.hpp"
 #include "robust_loss.hpp"
+#include "small_linalg.hpp"
 
 namespace stba {
 
@@ -779,24 +780,33 @@ int launch_lm_diagonal(int n, int bs, int bstride, int kind, const double* H, do
     return STBA_OK;
 }
 
+// the landmark's inverse block and its square root (spd3_inverse, small_linalg.hpp: the ONE inverse every consumer reads -- the
+// pair plan, the implicit product, back-substitution and the covariance Hinv6, the dense form Rinv9 with R R^T = Hinv); zero for
+// constant landmarks and for blocks that are not numerically positive definite
+__device__ __forceinline__ void point_inverse_store(const double H[6], bool fixed, size_t j, double* __restrict__ Hinv6,
+                                                    double* __restrict__ Rinv9) {
+    double Hi[6] = {0, 0, 0, 0, 0, 0}, R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!fixed) spd3_inverse(H, Hi, R);          // (false: Hi and R stay zero)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Hinv6[j * 6 + k] = Hi[k];
+    if (Rinv9) {          // (null: the caller's Schur step is not the dense form, nobody reads the root)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rinv9[j * 9 + k] = R[k];
+    }
+}
+
 // (Hpp + diag(dp))^-1 per landmark; zero for constant / degenerate landmarks
 __global__ __launch_bounds__(256) void ba_point_invert_kernel(int n_pts, const double* __restrict__ Hpp6,
                                                               const double* __restrict__ dp,
                                                               const unsigned char* __restrict__ pt_fixed,
-                                                              double* __restrict__ Hinv6) {
+                                                              double* __restrict__ Hinv6, double* __restrict__ Rinv9) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n_pts) return;
-    double H[6], Hi[6] = {0, 0, 0, 0, 0, 0};
+    double H[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) H[k] = Hpp6[(size_t)j * 6 + k];
     H[0] += dp[(size_t)j * 3]; H[3] += dp[(size_t)j * 3 + 1]; H[5] += dp[(size_t)j * 3 + 2];
-    const bool fixed = pt_fixed ? (pt_fixed[j] != 0) : false;
-    if (fixed || !inv3_sym6(H, Hi)) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) Hi[k] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Hinv6[(size_t)j * 6 + k] = Hi[k];
+    point_inverse_store(H, pt_fixed ? (pt_fixed[j] != 0) : false, (size_t)j, Hinv6, Rinv9);
 }
 
 // the same with the landmark's LM diagonal computed on the way (lm_diagonal_kernel, kind 1: diagonal of the packed 3x3
@@ -805,11 +815,12 @@ __global__ __launch_bounds__(256) void ba_point_damp_invert_kernel(int n_pts, co
                                                                    const unsigned char* __restrict__ pt_fixed,
                                                                    double* __restrict__ scale, int init_scale, int use_scaling,
                                                                    double radius, double dmin, double dmax, double* __restrict__ dp,
-                                                                   double* __restrict__ Hinv6, double* __restrict__ zero_buf, int zero_n) {
+                                                                   double* __restrict__ Hinv6, double* __restrict__ Rinv9,
+                                                                   double* __restrict__ zero_buf, int zero_n) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < zero_n) zero_buf[j] = 0.0;          // (the three extras vectors behind S: one memset launch less per iteration)
     if (j >= n_pts) return;
-    double H[6], Hi[6] = {0, 0, 0, 0, 0, 0};
+    double H[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) H[k] = Hpp6[(size_t)j * 6 + k];
     const int dg[3] = {0, 3, 5};
@@ -828,28 +839,22 @@ __global__ __launch_bounds__(256) void ba_point_damp_invert_kernel(int n_pts, co
         dp[i] = d;
         H[dg[k]] = h + d;
     }
-    const bool fixed = pt_fixed ? (pt_fixed[j] != 0) : false;
-    if (fixed || !inv3_sym6(H, Hi)) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) Hi[k] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Hinv6[(size_t)j * 6 + k] = Hi[k];
+    point_inverse_store(H, pt_fixed ? (pt_fixed[j] != 0) : false, (size_t)j, Hinv6, Rinv9);
 }
 
 int launch_point_damp_invert(int n_pts, const double* Hpp6, const unsigned char* pt_fixed, double* scale, int init_scale,
-                             int use_scaling, double radius, double dmin, double dmax, double* dp, double* Hinv6,
+                             int use_scaling, double radius, double dmin, double dmax, double* dp, double* Hinv6, double* Rinv9,
                              double* zero_buf, int zero_n, hipStream_t st) {
     hipLaunchKernelGGL(ba_point_damp_invert_kernel, dim3((std::max(n_pts, zero_n) + 255) / 256), dim3(256), 0, st, n_pts, Hpp6, pt_fixed, scale,
-                       init_scale, use_scaling, radius, dmin, dmax, dp, Hinv6, zero_buf, zero_n);
+                       init_scale, use_scaling, radius, dmin, dmax, dp, Hinv6, Rinv9, zero_buf, zero_n);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
 
 int launch_point_invert(int n_pts, const double* Hpp6, const double* dp, const unsigned char* pt_fixed,
-                        double* Hinv6, hipStream_t st) {
+                        double* Hinv6, double* Rinv9, hipStream_t st) {
     hipLaunchKernelGGL(ba_point_invert_kernel, dim3((n_pts + 255) / 256), dim3(256), 0, st, n_pts, Hpp6, dp,
-                       pt_fixed, Hinv6);
+                       pt_fixed, Hinv6, Rinv9);
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
@@ -1140,26 +1145,14 @@ __global__ __launch_bounds__(SCHUR_THREADS, GEN ? 2 : 4) void ba_schur_pairs_ker
 
 // ===========================================================================================
 // The same Schur complement for DENSE visibility (most cameras see most landmarks): per observation i of landmark j the 6 x 3 block
-// Y_i = (Jc_i^T Jp_i) R_j with R_j R_j^T = Hpp_j^-1 (Cholesky of the inverse landmark block), written into a dense matrix
+// Y_i = (Jc_i^T Jp_i) R_j with R_j R_j^T = Hpp_j^-1 (Rinv9: the root spd3_inverse hands out with the inverse -- factoring the ROUNDED inverse
+// again loses a column of Y where rounding has made it indefinite), written into a dense matrix
 // Y [6 n_cams padded] x [3 n_pts padded]; then S = -(Y Y^T) (lower triangle) is ONE symmetric rank-k product on the matrix cores
 // (chol_yyt_lower_dev) and rhs = Y v, v_j = R_j^T gp_j.  No pair plan: the pair formulation costs 16 B of plan and 36 LDS atomics
 // per pair of observations of a landmark -- k (k + 1) / 2 pairs for a landmark seen by k cameras; the product costs 6 C x 6 C x 3
 // multiply-adds per landmark whatever k is, and wins from k / C ~ 0.3 on.  The zero blocks of Y (camera does not see landmark)
 // are zeroed once, at the first launch: the visibility pattern is static.
 // ===========================================================================================
-__device__ inline void chol3_of_sym6(const double h[6], double R[6]) {
-    // h = (00, 01, 02, 11, 12, 22) of an SPD (or zero) 3 x 3 block; R = (r00, r10, r20, r11, r21, r22) lower triangular, R R^T = h
-    const double r00 = h[0] > 0.0 ? sqrt(h[0]) : 0.0;
-    const double i0 = r00 > 0.0 ? 1.0 / r00 : 0.0;
-    const double r10 = h[1] * i0, r20 = h[2] * i0;
-    const double d1 = h[3] - r10 * r10;
-    const double r11 = d1 > 0.0 ? sqrt(d1) : 0.0;
-    const double i1 = r11 > 0.0 ? 1.0 / r11 : 0.0;
-    const double r21 = (h[4] - r20 * r10) * i1;
-    const double d2 = h[5] - r20 * r20 - r21 * r21;
-    const double r22 = d2 > 0.0 ? sqrt(d2) : 0.0;
-    R[0] = r00; R[1] = r10; R[2] = r20; R[3] = r11; R[4] = r21; R[5] = r22;
-}
 // One WAVE per chunk of <= CAM_CHUNK observations of ONE camera (the camera-sorted permutation, landmarks ascending inside a camera:
 // the lanes of a wave write neighbouring 24-byte pieces of the camera's six rows of Y).  On the way the wave sums what else the
 // Schur step owes for its camera: the camera block Jc^T Jc (21), Jc^T r (6) and the right-hand side sum_i W_i Hpp^-1 gp (6); a
@@ -1171,7 +1164,7 @@ __global__ __launch_bounds__(256) void ba_schur_dense_chunk_kernel(int n_chunks,
                                                                    const int* __restrict__ obs_pt, const double* __restrict__ J8,
                                                                    const unsigned char* __restrict__ omask, const double* __restrict__ Jc12,
                                                                    const double2* __restrict__ r, const double* __restrict__ Hinv6,
-                                                                   const double* __restrict__ gp, double* __restrict__ Y, size_t ldy,
+                                                                   const double* __restrict__ Rinv9, const double* __restrict__ gp, double* __restrict__ Y, size_t ldy,
                                                                    double* __restrict__ partial, const unsigned char* __restrict__ dup_run) {
     const int lane = threadIdx.x & 63;
     const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1183,13 +1176,14 @@ __global__ __launch_bounds__(256) void ba_schur_dense_chunk_kernel(int n_chunks,
     for (int p = chunk_begin[ch] + lane; p < e; p += 64) {
         const int i = cam_perm[p];
         const int c = obs_cam[i], j = obs_pt[i];
-        double jc[12], jp[6], h[6], R[6];
+        double jc[12], jp[6], h[6], R[9];
         load_jc_jp<GEN>(J8, omask, i, jc, jp, Jc12);
         const double2 ri = r[i];
 #pragma unroll
         for (int k = 0; k < 6; ++k) h[k] = Hinv6[(size_t)j * 6 + k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rinv9[(size_t)j * 9 + k];
         const double g0 = gp[(size_t)j * 3], g1 = gp[(size_t)j * 3 + 1], g2 = gp[(size_t)j * 3 + 2];
-        chol3_of_sym6(h, R);
         const double t0 = h[0] * g0 + h[1] * g1 + h[2] * g2, t1 = h[1] * g0 + h[3] * g1 + h[4] * g2, t2 = h[2] * g0 + h[4] * g1 + h[5] * g2;
         int idx = 0;
         double wrow[DUP ? 18 : 1];
@@ -1201,9 +1195,9 @@ __global__ __launch_bounds__(256) void ba_schur_dense_chunk_kernel(int n_chunks,
             if constexpr (DUP) { wrow[q * 3] = w0; wrow[q * 3 + 1] = w1; wrow[q * 3 + 2] = w2; }
             else {
                 double* y = Y + (size_t)(c * 6 + q) * ldy + (size_t)j * 3;
-                y[0] = w0 * R[0] + w1 * R[1] + w2 * R[2];
-                y[1] = w1 * R[3] + w2 * R[4];
-                y[2] = w2 * R[5];
+                y[0] = w0 * R[0] + w1 * R[3] + w2 * R[6];
+                y[1] = w0 * R[1] + w1 * R[4] + w2 * R[7];
+                y[2] = w0 * R[2] + w1 * R[5] + w2 * R[8];
             }
 #pragma unroll
             for (int b = 0; b <= q; ++b) acc[idx++] += jc[q] * jc[b] + jc[6 + q] * jc[6 + b];
@@ -1231,9 +1225,9 @@ __global__ __launch_bounds__(256) void ba_schur_dense_chunk_kernel(int n_chunks,
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             double* y = Y + (size_t)(c * 6 + q) * ldy + (size_t)j * 3;
-            y[0] = wrow[q * 3] * R[0] + wrow[q * 3 + 1] * R[1] + wrow[q * 3 + 2] * R[2];
-            y[1] = wrow[q * 3 + 1] * R[3] + wrow[q * 3 + 2] * R[4];
-            y[2] = wrow[q * 3 + 2] * R[5];
+            y[0] = wrow[q * 3] * R[0] + wrow[q * 3 + 1] * R[3] + wrow[q * 3 + 2] * R[6];
+            y[1] = wrow[q * 3] * R[1] + wrow[q * 3 + 1] * R[4] + wrow[q * 3 + 2] * R[7];
+            y[2] = wrow[q * 3] * R[2] + wrow[q * 3 + 1] * R[5] + wrow[q * 3 + 2] * R[8];
         }
         }
     }
@@ -1271,7 +1265,7 @@ int launch_schur_dense(const SchurDenseArgs& a, hipStream_t st) {
     if (a.n_chunks > 0) {
         const dim3 grid((a.n_chunks + 3) / 4);
 #define STBA_DENSE_CHUNK(GEN_, DUP_) hipLaunchKernelGGL((ba_schur_dense_chunk_kernel<GEN_, DUP_>), grid, dim3(256), 0, st, a.n_chunks, a.chunk_begin, \
-            a.chunk_end, a.cam_perm, a.obs_cam, a.obs_pt, a.J8, a.omask, a.Jc12, a.r, a.Hinv6, a.gp, a.Y, a.ldy, a.partial, a.dup_run)
+            a.chunk_end, a.cam_perm, a.obs_cam, a.obs_pt, a.J8, a.omask, a.Jc12, a.r, a.Hinv6, a.Rinv9, a.gp, a.Y, a.ldy, a.partial, a.dup_run)
         if (a.Jc12) { if (a.dup_run) STBA_DENSE_CHUNK(true, true); else STBA_DENSE_CHUNK(true, false); }
         else { if (a.dup_run) STBA_DENSE_CHUNK(false, true); else STBA_DENSE_CHUNK(false, false); }
 #undef STBA_DENSE_CHUNK
@@ -1765,8 +1759,8 @@ __global__ __launch_bounds__(256) void ba_triangulate_kernel(int n_pts, const in
     for (int it = 0; it < max_iter; ++it) {
         double Hd[6] = {H[0] + lambda * (H[0] + 1e-12), H[1], H[2], H[3] + lambda * (H[3] + 1e-12), H[4],
                         H[5] + lambda * (H[5] + 1e-12)};
-        double Hi[6];
-        if (!inv3_sym6(Hd, Hi)) break;
+        double Hi[6], Rr[9];
+        if (!spd3_inverse(Hd, Hi, Rr)) break;
         const double d0 = Hi[0] * g[0] + Hi[1] * g[1] + Hi[2] * g[2];
         const double d1 = Hi[1] * g[0] + Hi[3] * g[1] + Hi[4] * g[2];
         const double d2 = Hi[2] * g[0] + Hi[4] * g[1] + Hi[5] * g[2];

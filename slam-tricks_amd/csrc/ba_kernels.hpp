@@ -103,10 +103,13 @@ int launch_camera_blocks(int n_cams, int n_chunks, const int* chunk_begin, const
 int launch_lm_diagonal(int n, int bs, int bstride, int kind, const double* H, double* scale, int init_scale,
                        int use_scaling, double radius, double dmin, double dmax, double* d, hipStream_t st);
 int launch_point_damp_invert(int n_pts, const double* Hpp6, const unsigned char* pt_fixed, double* scale, int init_scale,
-                             int use_scaling, double radius, double dmin, double dmax, double* dp, double* Hinv6,
+                             int use_scaling, double radius, double dmin, double dmax, double* dp, double* Hinv6, double* Rinv9,
                              double* zero_buf, int zero_n, hipStream_t st);
+// Hinv6 [n_pts][6] = (Hpp + diag(dp))^-1 packed, Rinv9 [n_pts][9] a root of it, R R^T = Hinv (row-major 3 x 3); both zero for a
+// constant landmark and for a block that is not numerically positive definite (spd3_inverse, small_linalg.hpp); Rinv9 may be null (only the
+// dense form of the Schur step reads it)
 int launch_point_invert(int n_pts, const double* Hpp6, const double* dp, const unsigned char* pt_fixed,
-                        double* Hinv6, hipStream_t st);
+                        double* Hinv6, double* Rinv9, hipStream_t st);
 // Schur complement of the landmark blocks, row-wise with LDS accumulation (plan built on the host at create time:
 // build_schur_plan, schur_plan.hpp, which also holds SCHUR_MAX_SLOTS, SCHUR_SPLIT_COLS, SCHUR_TASK_PAIRS and SCHUR_THREADS).
 // LDS stride of one 6x6 accumulator block, in doubles: odd, so that the same entry of different blocks falls
@@ -145,7 +148,7 @@ struct SchurDenseArgs {
     const int* chunk_begin; const int* chunk_end; const int* cam_chunk_start; const int* cam_perm;
     const int* obs_cam; const int* obs_pt;
     const double* J8; const unsigned char* omask; const double* Jc12; const double2* r;
-    const double* Hinv6; const double* gp;
+    const double* Hinv6; const double* Rinv9; const double* gp;
     double* Y; size_t ldy; size_t kcols;         // [lda][ldy], kcols = 3 n_pts rounded up to 16 (<= ldy); zero where nothing is observed
     double* partial;                              // schur_dense_partial_doubles(n_chunks)
     const unsigned char* dup_run;                 // per position of cam_perm: repeated (camera, landmark) pairs (null: none), see the chunk kernel

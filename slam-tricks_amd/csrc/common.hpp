@@ -383,16 +383,4 @@ __host__ __device__ inline void se3_left_update(const double* d, double* xi) {
     xi[3] = w[0]; xi[4] = w[1]; xi[5] = w[2];
 }
 
-// inverse of the symmetric 3x3 given as (xx,xy,xz,yy,yz,zz); returns false if not SPD-ish
-__host__ __device__ inline bool inv3_sym6(const double A[6], double Ai[6]) {
-    const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5];
-    const double C00 = d * f - e * e, C01 = c * e - b * f, C02 = b * e - c * d;
-    const double det = a * C00 + b * C01 + c * C02;
-    if (!(det > 0.0) || !(fabs(det) < 1e300)) return false;
-    const double inv = 1.0 / det;
-    Ai[0] = C00 * inv; Ai[1] = C01 * inv; Ai[2] = C02 * inv;
-    Ai[3] = (a * f - c * c) * inv; Ai[4] = (b * c - a * e) * inv; Ai[5] = (a * d - b * b) * inv;
-    return true;
-}
-
 }  // namespace stba

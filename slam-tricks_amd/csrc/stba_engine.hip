@@ -127,7 +127,7 @@ struct stba_ba {
     // row-major in the engine's order; null: the identity.  With it the same kernel whitens r, Jc, Jp in front of the corrector
     double* winfo = nullptr;
     unsigned char* omask = nullptr;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
-    double *Hpp6 = nullptr, *gp = nullptr, *Hinv6 = nullptr, *dp = nullptr, *scale_p = nullptr;
+    double *Hpp6 = nullptr, *gp = nullptr, *Hinv6 = nullptr, *Rinv9 = nullptr, *dp = nullptr, *scale_p = nullptr;
     double *Hcc = nullptr, *gc = nullptr, *cam_partial = nullptr, *dc = nullptr, *scale_c = nullptr;
     double* Sbuf = nullptr;   // [S lda*lda | ex_diag lda | ex_gc lda | rhs lda | ex_scalar lda]
     double *dxc = nullptr, *dxp = nullptr;
@@ -225,7 +225,7 @@ static void ba_free(stba_ba* b) {
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
     F(b->pt_start); F(b->cam_perm); F(b->chunk_begin); F(b->chunk_end); F(b->cam_chunk_start); F(b->cam_fixed);
-    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->winfo); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->dp); F(b->scale_p);
+    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->winfo); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->Rinv9); F(b->dp); F(b->scale_p);
     F(b->Hcc); F(b->gc); F(b->cam_partial); F(b->dc); F(b->scale_c); F(b->Sbuf); F(b->Spack); F(b->pk_blocks); F(b->dxc); F(b->dxp);
     F(b->task_cam); F(b->cam_start); F(b->task_col_lo); F(b->task_col_hi); F(b->row_col_ptr); F(b->row_cols);
     F(b->task_p_lo); F(b->task_p_hi); F(b->row_task_ptr); F(b->row_tasks); F(b->task_part_off); F(b->schur_part);
@@ -461,6 +461,9 @@ static int ba_dense_alloc(stba_ba* b) {
     return STBA_OK;
 }
 
+// where the landmark inversion in front of a Schur step puts the root of the inverse: only the dense form reads it
+static double* ba_rinv(stba_ba* b) { return b->schur_mode == STBA_SCHUR_DENSE ? b->Rinv9 : nullptr; }
+
 // S (lower triangle), rhs, Hcc, gc from the linearisation and the inverse landmark blocks: the pair plan or the dense product
 static int ba_schur_step(stba_ba* b) {
     if (b->schur_mode == STBA_SCHUR_DENSE) {
@@ -469,7 +472,7 @@ static int ba_schur_step(stba_ba* b) {
         da.n_cams = b->nc; da.n_chunks = b->n_chunks;
         da.chunk_begin = b->chunk_begin; da.chunk_end = b->chunk_end; da.cam_chunk_start = b->cam_chunk_start; da.cam_perm = b->cam_perm;
         da.obs_cam = b->obs_cam; da.obs_pt = b->obs_pt;
-        da.J8 = b->J8; da.omask = b->omask; da.Jc12 = ba_general_jc(b); da.r = b->r; da.Hinv6 = b->Hinv6; da.gp = b->gp;
+        da.J8 = b->J8; da.omask = b->omask; da.Jc12 = ba_general_jc(b); da.r = b->r; da.Hinv6 = b->Hinv6; da.Rinv9 = b->Rinv9; da.gp = b->gp;
         da.Y = b->Y; da.ldy = b->ldy; da.kcols = b->ykcols; da.partial = b->yv; da.ws = b->yws; da.dup_run = b->dup_run;
         da.S = b->S(); da.lda = b->lda; da.rhs = b->rhs(); da.Hcc = b->Hcc; da.gc = b->gc;
         return launch_schur_dense(da, b->st);
@@ -495,9 +498,9 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm) {
     double* extras = b->Sbuf + (size_t)b->lda * b->lda;
     if (!dm.explicit_d)
         STBA_TRY(launch_point_damp_invert(b->np, b->Hpp6, b->pt_fixed, b->scale_p, init_scale, dm.use_scaling, dm.radius, dm.dmin,
-                                          dm.dmax, b->dp, b->Hinv6, extras, 3 * b->lda, b->st));
+                                          dm.dmax, b->dp, b->Hinv6, ba_rinv(b), extras, 3 * b->lda, b->st));
     else {
-        STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, b->st));
+        STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, ba_rinv(b), b->st));
         STBA_HIP(hipMemsetAsync(extras, 0, 3 * (size_t)b->lda * sizeof(double), b->st));
     }
     // S is zeroed (pair plan) or overwritten (dense product) by the Schur step itself
@@ -695,9 +698,9 @@ static int ba_build_implicit(stba_ba* b, const Damping& dm) {
     const int init_scale = b->scale_init ? 0 : 1;
     if (!dm.explicit_d)
         STBA_TRY(launch_point_damp_invert(b->np, b->Hpp6, b->pt_fixed, b->scale_p, init_scale, dm.use_scaling, dm.radius, dm.dmin,
-                                          dm.dmax, b->dp, b->Hinv6, b->ex_diag(), 3 * b->lda, b->st));
+                                          dm.dmax, b->dp, b->Hinv6, nullptr, b->ex_diag(), 3 * b->lda, b->st));
     else {
-        STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, b->st));
+        STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, nullptr, b->st));
         STBA_HIP(hipMemsetAsync(b->ex_diag(), 0, 3 * (size_t)b->lda * sizeof(double), b->st));
     }
     STBA_TRY(ba_camera_blocks(b));
@@ -1490,7 +1493,7 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     if (!P.dup_run.empty()) { A_(dev_alloc(&b->dup_run, no)); A_(upload(b->dup_run, P.dup_run.data(), no, b->st)); }
     A_(dev_alloc(&b->r, no)); A_(dev_alloc(&b->J8, no * 8));
     if (cam_fixed || pt_fixed) A_(dev_alloc(&b->omask, no));
-    A_(dev_alloc(&b->Hpp6, np * 6)); A_(dev_alloc(&b->gp, np * 3)); A_(dev_alloc(&b->Hinv6, np * 6));
+    A_(dev_alloc(&b->Hpp6, np * 6)); A_(dev_alloc(&b->gp, np * 3)); A_(dev_alloc(&b->Hinv6, np * 6)); A_(dev_alloc(&b->Rinv9, np * 9));
     A_(dev_alloc(&b->dp, np * 3)); A_(dev_alloc(&b->scale_p, np * 3));
     A_(dev_alloc(&b->Hcc, nc * 36)); A_(dev_alloc(&b->gc, nc * 6)); A_(dev_alloc(&b->cam_partial, (size_t)b->n_chunks * 28));
     A_(dev_alloc(&b->dc, nc * 6)); A_(dev_alloc(&b->scale_c, nc * 6));
@@ -1622,7 +1625,7 @@ int stba_ba_schur_apply(stba_ba* b, const double* dc, const double* dp, int whic
     STBA_TRY(upload(b->dp, dp, (size_t)b->np * 3, b->st));
     Damping dm;
     dm.explicit_d = true;
-    STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, b->st));
+    STBA_TRY(launch_point_invert(b->np, b->Hpp6, b->dp, b->pt_fixed, b->Hinv6, nullptr, b->st));
     STBA_TRY(ba_camera_blocks(b));
     double* out_dev = b->rhs();
     if (!x) STBA_TRY(ba_is_rhs(b));
@@ -2420,7 +2423,7 @@ int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics
     STBA_TRY(ba_fill_scalar_slots(b, b->trial + TS_COST2));
     Damping dm;
     STBA_TRY(launch_point_damp_invert(b->np, b->Hpp6, b->pt_fixed, b->scale_p, b->scale_init ? 0 : 1, dm.use_scaling, dm.radius, dm.dmin,
-                                      dm.dmax, b->dp, b->Hinv6, b->Sbuf + (size_t)b->lda * b->lda, 3 * b->lda, b->st));
+                                      dm.dmax, b->dp, b->Hinv6, ba_rinv(b), b->Sbuf + (size_t)b->lda * b->lda, 3 * b->lda, b->st));
     STBA_TRY(ba_schur_step(b));      // warm
     STBA_HIP(hipEventRecord(b->ev[EV_LIN], b->st));
     for (int k = 0; k < reps; ++k) STBA_TRY(ba_schur_step(b));

@@ -29,6 +29,25 @@ def engine(st, s, solver="iterative_schur"):
                        linear_solver=solver)
 
 
+def inv3_longdouble(A):
+    """inverse of an SPD 3 x 3 in long double throughout (Cholesky, the factor inverted by substitution).  A float64 LAPACK inverse
+    here left S itself known to 1e-9 on the extras scene -- a landmark at depth 0.05 seen once: W V^-1 W^T cancels the camera
+    block to a thousandth -- which is a third of what test_operator_parity allows the DEVICE (measured against the 50-digit
+    reference of schur_elim_ref.py: 1.4e-9 of the 3.3e-9 bound)"""
+    A = np.asarray(A, np.longdouble)
+    Lc = np.zeros((3, 3), np.longdouble)
+    for i in range(3):
+        for k in range(i + 1):
+            t = A[i, k] - np.dot(Lc[i, :k], Lc[k, :k])
+            Lc[i, k] = np.sqrt(t) if i == k else t / Lc[k, k]
+    Mi = np.zeros((3, 3), np.longdouble)
+    for i in range(3):
+        Mi[i, i] = 1 / Lc[i, i]
+        for k in range(i):
+            Mi[i, k] = -np.dot(Lc[i, k:i], Mi[k:i, k]) / Lc[i, i]
+    return Mi.T @ Mi
+
+
 def numpy_system(prob, dc, dp):
     """S (free dofs only: constant rows and columns zero), rhs, the Jacobi and Schur-Jacobi block inverses, in long double sums"""
     cams, pts = prob.split(prob.x0)
@@ -56,7 +75,7 @@ def numpy_system(prob, dc, dp):
     for j in range(npt):
         if prob.pt_fixed[j]:
             continue
-        Vi = np.linalg.inv((V[j] + np.diag(dp[j])).astype(np.float64)).astype(np.longdouble)
+        Vi = inv3_longdouble(V[j] + np.diag(dp[j]))
         S -= W[j] @ Vi @ W[j].T
         rhs += W[j] @ (Vi @ gp[j])
         rhs_terms += np.abs(W[j].astype(np.float64)) @ np.abs(Vi.astype(np.float64)) @ np.abs(gp[j].astype(np.float64))

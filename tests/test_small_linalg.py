@@ -1,10 +1,11 @@
-"""The host closed forms of slam-tricks_amd/csrc/small_linalg.hpp -- smallest_right_singular_vector, svd3 and the Givens row fold
-that two_view.hip shares with its kernel -- compiled with g++ into tests/cpp/small_linalg_driver.cpp and compared with a 50-digit
+"""The host closed forms of slam-tricks_amd/csrc/small_linalg.hpp -- smallest_right_singular_vector, svd3, the Givens row fold
+that two_view.hip shares with its kernel and the SPD 3 x 3 inverse that the landmark kernels share (spd3_inverse) -- compiled with g++ into tests/cpp/small_linalg_driver.cpp and compared with a 50-digit
 reference (tests/two_view_ref.py).  No device.
 
 Bounds.  A null vector is held to 64 EPS sigma_1 / sigma_(n-1): EPS sigma_1 / sigma_(n-1) is the first-order perturbation bound
 of the null vector of a matrix known to one rounding, 64 the ceiling for a backward-stable method (a few dozen rotations touch
-every entry).  svd3 is held to 8 EPS, as orthogonality and as a relative residual."""
+every entry).  svd3 is held to 8 EPS, as orthogonality and as a relative residual.  spd3_inverse is held to C3 EPS lambda_1 /
+lambda_3 of the largest entry of the inverse, C3 = 8 times what LAPACK's potrf + potri reach on the same blocks (measured here)."""
 import json
 import os
 import subprocess
@@ -208,3 +209,81 @@ def test_fold_ignores_zero_rows_and_takes_rows_with_zeros(driver, calib):
     B = np.vstack([Z0, A[:5], Z0, Z0, A[5:], Z0])
     assert np.array_equal(driver(f"fold {len(B)}", B), out)
     assert np.array_equal(driver("fold 3", np.zeros((3, 9)))[:45], np.zeros(45))
+
+
+# ---------------------------------------------------------------- spd3_inverse
+SPD3_SPECTRA = [("1_.6_k", k, (1.0, 0.6, 1.0 / k)) for k in (1e6, 1e10, 1e13)] + [("1_k_k", k, (1.0, 1.0 / k, 1.0 / k)) for k in (1e4, 1e6, 1e8, 1e10, 1e13)]
+
+
+def _spd3_blocks(spectrum, orientation, n):
+    """n SPD blocks Q diag(spectrum) Q^T built at 50 digits and rounded to doubles: Q a random rotation, or a permutation with a
+    rotation of 1e-9 rad on top (eigenvectors on the coordinate axes to nine digits; an exact permutation is diagonal, no test)"""
+    rng = np.random.default_rng(int(-np.log10(spectrum[2])) + (100 if orientation == "axis" else 0))
+    out = []
+    for i in range(n):
+        Q = M.so3_exp(M.axis_angle(rng, rng.uniform(0.1, 3.0) if orientation == "random" else 1e-9))
+        d = [mp.mpf(x) for x in (np.roll(spectrum, i) if orientation == "axis" else spectrum)]
+        A = M.mm(M.mm(Q, [[d[0], 0, 0], [0, d[1], 0], [0, 0, d[2]]]), M.tr(Q))
+        A = TR.f64(A)
+        out.append(np.array([A[0, 0], 0.5 * (A[0, 1] + A[1, 0]), 0.5 * (A[0, 2] + A[2, 0]), A[1, 1], 0.5 * (A[1, 2] + A[2, 1]), A[2, 2]]))
+    return np.array(out)
+
+
+def _sym(p):
+    return np.array([[p[0], p[1], p[2]], [p[1], p[3], p[4]], [p[2], p[4], p[5]]])
+
+
+def _inv_mp(p):
+    return M.f64(mp.matrix(_sym(p).tolist()) ** -1)
+
+
+@pytest.mark.parametrize("orientation", ["random", "axis"])
+@pytest.mark.parametrize("name,kappa,spectrum", SPD3_SPECTRA, ids=[f"{n}{k:.0e}" for n, k, _ in SPD3_SPECTRA])
+def test_spd3_inverse(driver, name, kappa, spectrum, orientation):
+    from scipy.linalg import lapack
+    n = 100
+    blocks = _spd3_blocks(spectrum, orientation, n)
+    out = driver(f"inv3 {n}", blocks).reshape(n, 23)
+    e_new, e_old, e_lap, rejected_old, indefinite_old = 0.0, 0.0, 0.0, 0, 0
+    for p, o in zip(blocks, out):
+        X = _inv_mp(p)
+        sc = np.abs(X).max()
+        assert o[0] == 1.0, f"{name} kappa {kappa:.0e}: spd3_inverse rejected an SPD block"
+        Ai, R = _sym(o[1:7]), o[7:16].reshape(3, 3)
+        e_new = max(e_new, np.abs(Ai - X).max() / sc, np.abs(R @ R.T - X).max() / sc)
+        c, info = lapack.dpotrf(_sym(p), lower=1)
+        assert info == 0
+        Xl, info = lapack.dpotri(c, lower=1)
+        assert info == 0
+        e_lap = max(e_lap, np.abs(np.tril(Xl) - np.tril(X)).max() / sc)
+        if o[16] == 1.0:
+            e_old = max(e_old, np.abs(_sym(o[17:23]) - X).max() / sc)
+            indefinite_old += int(np.linalg.eigvalsh(_sym(o[17:23])).min() <= 0)
+        else:
+            rejected_old += 1
+    u = EPS * spectrum[0] / spectrum[2]
+    c3 = 8 * e_lap / u
+    print(f"{name} kappa {kappa:.0e} {orientation}: spd3_inverse {e_new / u:.3g} u, potrf+potri {e_lap / u:.3g} u (C3 = {c3:.3g}), "
+          f"cofactors {e_old / u:.3g} u = {e_old:.3g}, rejected {rejected_old}/{n}, not positive definite {indefinite_old}/{n}")
+    assert e_new <= c3 * u, f"{e_new / u:.3g} u > C3 = {c3:.3g}"
+    # packed: one number per symmetric pair, so the result is symmetric by construction; no entry may be non-finite
+    assert np.all(np.isfinite(out[:, 1:16]))
+
+
+def test_spd3_inverse_rejects_what_is_not_positive_definite(driver, calib):
+    """a rank-2 block J^T J of one observation (the landmark nobody else sees, undamped), zero, a negative diagonal, NaN: flag 0
+    and the outputs untouched"""
+    rng = np.random.default_rng(5)
+    J = rng.normal(size=(2000, 2, 3)) * np.exp(2 * rng.normal(size=(2000, 1, 3)))        # columns of very different sizes, some nearly parallel
+    V = np.einsum("nki,nkj->nij", J, J)
+    blocks = [[v[0, 0], v[0, 1], v[0, 2], v[1, 1], v[1, 2], v[2, 2]] for v in V]
+    blocks += [[0.0] * 6, [1.0, 0, 0, -1.0, 0, 1.0], [1.0, 0, 0, np.nan, 0, 1.0], [1.0, 2.0, 0, 1.0, 0, 1.0], [np.inf, 0, 0, 1.0, 0, 1.0]]
+    out = driver(f"inv3 {len(blocks)}", np.array(blocks)).reshape(len(blocks), 23)
+    assert np.all(out[:, 0] == 0.0) and np.all(out[:, 1:16] == 0.0)
+    # ... and scaling by powers of two changes nothing but the exponent: the decision and every bit of the mantissas
+    A = _spd3_blocks((1.0, 1e-6, 1e-10), "random", 8)
+    base = driver("inv3 8", A).reshape(8, 23)
+    for k in (-300, 300):
+        got = driver("inv3 8", A * 2.0 ** k).reshape(8, 23)
+        assert np.array_equal(got[:, 0], base[:, 0]) and np.array_equal(got[:, 1:7] * 2.0 ** k, base[:, 1:7])
+        assert np.array_equal(got[:, 7:16] * 2.0 ** (k // 2), base[:, 7:16])
