@@ -61,6 +61,10 @@ const char* stba_last_error(void);      /* thread-local detail of the last failu
 int stba_version(void);                 /* 6: stba_pcg_options grew coarse_async, forcing_step_accuracy (append-only); 5: stba_lm_options grew function_tolerance_takes_step */
 /* number of visible HIP devices (0 => every compute entry point returns STBA_ERR_NO_DEVICE) */
 int stba_device_count(void);
+/* device buffers the library's engines, stores and calls hold at this moment, process-wide (a count of allocations, not bytes).
+ * An engine's buffers go with stba_*_destroy, a call's temporaries when it returns: the count is then what it was before.  Not
+ * counted: the dense Cholesky's per-stream workspaces and the small dense step's pooled buffers, which live as long as the process */
+int stba_live_device_buffers(long long* count);
 
 /* ---- Levenberg-Marquardt options: the fields the reference sets plus Ceres' defaults --------
  * (solver.hpp:272-282, test_ceres.h:133-146; defaults: SURVEY.md 8c) */

@@ -87,7 +87,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_pg_set_loss", "stba_pg_has_loss",
            "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry",
            "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information",
-           "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry"]
+           "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry",
+           "stba_live_device_buffers"]
 
 
 def lib():
@@ -129,6 +130,13 @@ def _f64(a):
 
 def device_count():
     return lib().stba_device_count()
+
+
+def live_device_buffers():
+    """device buffers the library's engines, stores and calls hold right now (stba_live_device_buffers)"""
+    n = C.c_longlong(0)
+    _chk(lib().stba_live_device_buffers(C.byref(n)), "stba_live_device_buffers")
+    return n.value
 
 
 def default_options(**kw):

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -37,13 +38,57 @@ inline int fail(int code, const std::string& msg) {
 
 int require_device();   // STBA_OK or STBA_ERR_NO_DEVICE (there is no CPU fallback)
 
-// device buffer of `count` T (at least one)
+// ---- device memory: a buffer is freed by the object that holds it -------------------------
+// buffers obtained through DevBuf and not yet freed, process-wide (stba_live_device_buffers; the workspaces that dense_chol.hip and
+// small_dense.hip keep for the life of the process come from hipMalloc directly and are not counted)
+inline std::atomic<long long> g_live_device_buffers{0};
+
+// move-only owner of one device array.  Converts to T*, so launches, argument structs and pointer arithmetic read as with a raw
+// pointer; a conditional against nullptr needs get().  Never an object of static or thread storage duration: the destructor calls HIP.
 template <class T>
-inline int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) return fail(STBA_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+class DevBuf {
+    T* p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {          // (frees what the target held)
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // `count` T (at least one); what the buffer held is freed first.  On failure the buffer is empty
+    int alloc(size_t count) {
+        reset();
+        if (count == 0) count = 1;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), count * sizeof(T));
+        if (e != hipSuccess) { p_ = nullptr; return fail(STBA_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        g_live_device_buffers.fetch_add(1, std::memory_order_relaxed);
+        return STBA_OK;
+    }
+    void reset() {
+        if (!p_) return;
+        (void)hipFree(p_);
+        g_live_device_buffers.fetch_sub(1, std::memory_order_relaxed);
+        p_ = nullptr;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+
+// host <-> device copies on a stream (nothing is enqueued for count 0).  The device side is not deduced, so a DevBuf converts
+template <class T> struct same_as { using type = T; };
+template <class T>
+inline int upload(typename same_as<T>::type* dst, const T* src, size_t count, hipStream_t st) {
+    if (count == 0) return STBA_OK;
+    STBA_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return STBA_OK;
+}
+template <class T>
+inline int download(T* dst, const typename same_as<T>::type* src, size_t count, hipStream_t st) {
+    if (count == 0) return STBA_OK;
+    STBA_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, st));
     return STBA_OK;
 }
 

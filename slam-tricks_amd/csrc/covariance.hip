@@ -34,18 +34,17 @@ namespace stba {
 struct CovStore {
     int nc = 0, np = 0, n = 0;
     hipStream_t st = nullptr;
-    double* sig = nullptr;       // Sigma_cc, packed lower triangle
-    double* vinv6 = nullptr;     // [np][6] V_j^-1 (xx xy xz yy yz zz), zero for constant landmarks
-    double* J8 = nullptr;        // the linearisation the marginals are made from (a later solve overwrites the engine's)
-    double* Jc12 = nullptr;      // host-linearised factors only
+    DevBuf<double> sig;          // Sigma_cc, packed lower triangle
+    DevBuf<double> vinv6;        // [np][6] V_j^-1 (xx xy xz yy yz zz), zero for constant landmarks
+    DevBuf<double> J8;           // the linearisation the marginals are made from (a later solve overwrites the engine's)
+    DevBuf<double> Jc12;         // host-linearised factors only
     const int* pt_start = nullptr; const int* obs_cam = nullptr;          // the engine's (fixed at its creation)
     const unsigned char* omask = nullptr; const unsigned char* cam_fixed = nullptr;
 };
 
 void cov_store_free(CovStore* c) {
     if (!c) return;
-    if (c->st) (void)hipStreamSynchronize(c->st);
-    for (double* p : {c->sig, c->vinv6, c->J8, c->Jc12}) if (p) (void)hipFree(p);
+    if (c->st) (void)hipStreamSynchronize(c->st);      // (then the store: its buffers go with it)
     delete c;
 }
 
@@ -102,13 +101,12 @@ __global__ __launch_bounds__(256) void cov_pack_kernel(const double* __restrict_
 int cov_spd_inverse_packed(const double* A, int lda, int n, const unsigned char* cam_fixed, double* sig, double* rcond, int* pivot_row,
                            hipStream_t st) {
     const int np = (n + CHOL_NB - 1) / CHOL_NB * CHOL_NB, ldw = 2 * np;
-    double *W = nullptr, *work = nullptr, *piv = nullptr;
-    int* flag = nullptr;
-    struct Guard { double *&a, *&b, *&c; int*& f; ~Guard() { for (double* p : {a, b, c}) if (p) (void)hipFree(p); if (f) (void)hipFree(f); } } guard{W, work, piv, flag};
-    STBA_TRY(dev_alloc(&W, (size_t)ldw * ldw));
-    STBA_TRY(dev_alloc(&work, chol_spd_inverse_workspace_doubles(np)));
-    STBA_TRY(dev_alloc(&piv, 2));
-    STBA_TRY(dev_alloc(&flag, 1));
+    DevBuf<double> W, work, piv;
+    DevBuf<int> flag;
+    STBA_TRY(W.alloc((size_t)ldw * ldw));
+    STBA_TRY(work.alloc(chol_spd_inverse_workspace_doubles(np)));
+    STBA_TRY(piv.alloc(2));
+    STBA_TRY(flag.alloc(1));
     hipLaunchKernelGGL(cov_layout_kernel, dim3(ldw), dim3(256), 0, st, A, lda, n, np, W);
     STBA_HIP(hipGetLastError());
     STBA_TRY(chol_spd_inverse_dev(W, ldw, np, n, flag, work, st));
@@ -401,14 +399,14 @@ int cov_compute(const BaCovInputs& in, double min_rcond, CovStore** out, double*
     double rc_pts = 1.0;
     if (in.np > 0) {
         const int nb = (in.np + 255) / 256;
-        double* dpart = nullptr;
-        STBA_TRY(dev_alloc(&dpart, (size_t)nb * 3));
+        DevBuf<double> dpart;
+        STBA_TRY(dpart.alloc((size_t)nb * 3));
         std::vector<double> part((size_t)nb * 3);
         hipLaunchKernelGGL(cov_point_rcond_kernel, dim3(nb), dim3(256), 0, st, in.np, in.Hpp6, in.pt_fixed, min_rcond, dpart);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(part.data(), dpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(dpart);
+        dpart.reset();
         if (e != hipSuccess) return fail(STBA_ERR_HIP, std::string("covariance: landmark pivots: ") + hipGetErrorString(e));
         long bad = 0;
         int first = in.np;
@@ -429,7 +427,7 @@ int cov_compute(const BaCovInputs& in, double min_rcond, CovStore** out, double*
     c->pt_start = in.pt_start; c->obs_cam = in.obs_cam; c->omask = in.omask; c->cam_fixed = in.cam_fixed;
     double rc_s = 1.0;
     if (in.n > 0) {
-        STBA_TRY(dev_alloc(&c->sig, (size_t)in.n * (in.n + 1) / 2));
+        STBA_TRY(c->sig.alloc((size_t)in.n * (in.n + 1) / 2));
         int piv = 0;
         STBA_TRY(cov_spd_inverse_packed(in.S, in.lda, in.n, in.cam_fixed, c->sig, &rc_s, &piv, st));
         if (piv)
@@ -442,12 +440,12 @@ int cov_compute(const BaCovInputs& in, double min_rcond, CovStore** out, double*
                         ", below min_reciprocal_condition_number (is the gauge fixed?)");
         }
     }
-    STBA_TRY(dev_alloc(&c->vinv6, (size_t)std::max(in.np, 1) * 6));
-    STBA_TRY(dev_alloc(&c->J8, (size_t)std::max(in.no, 1) * 8));
+    STBA_TRY(c->vinv6.alloc((size_t)std::max(in.np, 1) * 6));
+    STBA_TRY(c->J8.alloc((size_t)std::max(in.no, 1) * 8));
     if (in.np) STBA_HIP(hipMemcpyAsync(c->vinv6, in.Hinv6, (size_t)in.np * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (in.no) STBA_HIP(hipMemcpyAsync(c->J8, in.J8, (size_t)in.no * 8 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (in.Jc12) {
-        STBA_TRY(dev_alloc(&c->Jc12, (size_t)std::max(in.no, 1) * 12));
+        STBA_TRY(c->Jc12.alloc((size_t)std::max(in.no, 1) * 12));
         if (in.no) STBA_HIP(hipMemcpyAsync(c->Jc12, in.Jc12, (size_t)in.no * 12 * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     STBA_HIP(hipStreamSynchronize(st));
@@ -461,10 +459,9 @@ int cov_camera_blocks(const CovStore* c, int n_pairs, const int* cam_a, const in
     for (int k = 0; k < n_pairs; ++k)
         if (cam_a[k] < 0 || cam_a[k] >= c->nc || cam_b[k] < 0 || cam_b[k] >= c->nc)
             return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_covariance: camera index out of range in pair " + std::to_string(k));
-    int *da = nullptr, *db = nullptr;
-    double* dout = nullptr;
-    struct Guard { int *&a, *&b; double*& o; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (o) (void)hipFree(o); } } guard{da, db, dout};
-    STBA_TRY(dev_alloc(&da, (size_t)n_pairs)); STBA_TRY(dev_alloc(&db, (size_t)n_pairs)); STBA_TRY(dev_alloc(&dout, (size_t)n_pairs * 36));
+    DevBuf<int> da, db;
+    DevBuf<double> dout;
+    STBA_TRY(da.alloc((size_t)n_pairs)); STBA_TRY(db.alloc((size_t)n_pairs)); STBA_TRY(dout.alloc((size_t)n_pairs * 36));
     STBA_HIP(hipMemcpyAsync(da, cam_a, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
     STBA_HIP(hipMemcpyAsync(db, cam_b, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
     const size_t ne = (size_t)n_pairs * 36;
@@ -482,14 +479,13 @@ int cov_point_blocks(const CovStore* c, int n, const int* pts, double* out) {
             if (pts[k] < 0 || pts[k] >= c->np)
                 return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_point_covariance: landmark index out of range at position " + std::to_string(k));
     if (!pts && n != c->np) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_point_covariance: pts = NULL asks for all n_pts landmarks");
-    int* dreq = nullptr;
-    double* dout = nullptr;
-    struct Guard { int*& r; double*& o; ~Guard() { if (r) (void)hipFree(r); if (o) (void)hipFree(o); } } guard{dreq, dout};
+    DevBuf<int> dreq;
+    DevBuf<double> dout;
     if (pts) {
-        STBA_TRY(dev_alloc(&dreq, (size_t)n));
+        STBA_TRY(dreq.alloc((size_t)n));
         STBA_HIP(hipMemcpyAsync(dreq, pts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->st));
     }
-    STBA_TRY(dev_alloc(&dout, (size_t)n * 9));
+    STBA_TRY(dout.alloc((size_t)n * 9));
     if (c->Jc12)
         hipLaunchKernelGGL(cov_point_kernel<true>, dim3(n), dim3(64), 0, c->st, dreq, c->pt_start, c->obs_cam, c->J8, c->omask, c->Jc12, c->vinv6, c->sig, dout);
     else
@@ -508,10 +504,9 @@ int cov_cam_point_blocks(const CovStore* c, int n_pairs, const int* cam, const i
         if (pt[k] < 0 || pt[k] >= c->np)
             return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_camera_point_covariance: landmark index out of range in pair " + std::to_string(k));
     }
-    int *da = nullptr, *db = nullptr;
-    double* dout = nullptr;
-    struct Guard { int *&a, *&b; double*& o; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (o) (void)hipFree(o); } } guard{da, db, dout};
-    STBA_TRY(dev_alloc(&da, (size_t)n_pairs)); STBA_TRY(dev_alloc(&db, (size_t)n_pairs)); STBA_TRY(dev_alloc(&dout, (size_t)n_pairs * 18));
+    DevBuf<int> da, db;
+    DevBuf<double> dout;
+    STBA_TRY(da.alloc((size_t)n_pairs)); STBA_TRY(db.alloc((size_t)n_pairs)); STBA_TRY(dout.alloc((size_t)n_pairs * 18));
     STBA_HIP(hipMemcpyAsync(da, cam, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
     STBA_HIP(hipMemcpyAsync(db, pt, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, c->st));
     if (c->Jc12)
@@ -538,10 +533,9 @@ int cov_point_pair_blocks(const CovStore* c, int n_pairs, const int* pt_a, const
     const int n_off = (int)off_pos.size(), n_diag = (int)diag_pos.size();
     std::vector<double> res((size_t)n_pairs * 9);          // (out is written only once everything has come home)
     if (n_off > 0) {
-        int *da = nullptr, *db = nullptr;
-        double* dout = nullptr;
-        struct Guard { int *&a, *&b; double*& o; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (o) (void)hipFree(o); } } guard{da, db, dout};
-        STBA_TRY(dev_alloc(&da, (size_t)n_off)); STBA_TRY(dev_alloc(&db, (size_t)n_off)); STBA_TRY(dev_alloc(&dout, (size_t)n_off * 9));
+        DevBuf<int> da, db;
+        DevBuf<double> dout;
+        STBA_TRY(da.alloc((size_t)n_off)); STBA_TRY(db.alloc((size_t)n_off)); STBA_TRY(dout.alloc((size_t)n_off * 9));
         STBA_HIP(hipMemcpyAsync(da, off_a.data(), (size_t)n_off * sizeof(int), hipMemcpyHostToDevice, c->st));
         STBA_HIP(hipMemcpyAsync(db, off_b.data(), (size_t)n_off * sizeof(int), hipMemcpyHostToDevice, c->st));
         if (c->Jc12)

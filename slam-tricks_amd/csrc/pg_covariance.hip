@@ -286,14 +286,12 @@ __global__ __launch_bounds__(256) void pgc_extract_kernel(int count, const long 
 
 // everything a call allocates, freed on every way out
 struct Workspace {
-    double *Jp = nullptr, *Minv = nullptr, *X = nullptr, *R = nullptr, *Z = nullptr, *P = nullptr, *Q = nullptr, *part = nullptr, *out = nullptr;
-    long long *src = nullptr, *dst = nullptr;
-    PgcCtrl* ctrl = nullptr;
+    DevBuf<double> Jp, Minv, X, R, Z, P, Q, part, out;
+    DevBuf<long long> src, dst;
+    DevBuf<PgcCtrl> ctrl;
     MappedBuffer exp;
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~Workspace() {
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        F(Jp); F(Minv); F(X); F(R); F(Z); F(P); F(Q); F(part); F(out); F(src); F(dst); F(ctrl);
         exp.release();
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     }
@@ -360,10 +358,10 @@ int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt
         Workspace ws;
         const size_t vec = (size_t)6 * n * PGC_K;
         const int nb = (n + PGC_NPW - 1) / PGC_NPW;
-        STBA_TRY(dev_alloc(&ws.Jp, (size_t)gr.m * 72)); STBA_TRY(dev_alloc(&ws.Minv, (size_t)n * 36));
-        STBA_TRY(dev_alloc(&ws.X, vec)); STBA_TRY(dev_alloc(&ws.R, vec)); STBA_TRY(dev_alloc(&ws.Z, vec)); STBA_TRY(dev_alloc(&ws.P, vec)); STBA_TRY(dev_alloc(&ws.Q, vec));
-        STBA_TRY(dev_alloc(&ws.part, (size_t)3 * nb * PGC_K)); STBA_TRY(dev_alloc(&ws.ctrl, 1));
-        if (!whole) { STBA_TRY(dev_alloc(&ws.out, out_count)); STBA_TRY(dev_alloc(&ws.src, (size_t)36 * rq.n_pairs)); STBA_TRY(dev_alloc(&ws.dst, (size_t)36 * rq.n_pairs)); }
+        STBA_TRY(ws.Jp.alloc((size_t)gr.m * 72)); STBA_TRY(ws.Minv.alloc((size_t)n * 36));
+        STBA_TRY(ws.X.alloc(vec)); STBA_TRY(ws.R.alloc(vec)); STBA_TRY(ws.Z.alloc(vec)); STBA_TRY(ws.P.alloc(vec)); STBA_TRY(ws.Q.alloc(vec));
+        STBA_TRY(ws.part.alloc((size_t)3 * nb * PGC_K)); STBA_TRY(ws.ctrl.alloc(1));
+        if (!whole) { STBA_TRY(ws.out.alloc(out_count)); STBA_TRY(ws.src.alloc((size_t)36 * rq.n_pairs)); STBA_TRY(ws.dst.alloc((size_t)36 * rq.n_pairs)); }
         STBA_TRY(ws.exp.alloc((size_t)stamped_doubles(CX_COUNT)));
         STBA_HIP(hipEventCreate(&ws.ev[0])); STBA_HIP(hipEventCreate(&ws.ev[1]));
         double* part_pq = ws.part; double* part_rz = ws.part + (size_t)nb * PGC_K; double* part_rr = ws.part + (size_t)2 * nb * PGC_K;

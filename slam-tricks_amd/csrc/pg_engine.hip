@@ -1446,39 +1446,37 @@ struct stba_pg {
     int n = 0, m = 0;
     hipStream_t st = nullptr;
     bool own = false;
-    double* poses[2] = {nullptr, nullptr};
+    DevBuf<double> poses[2];
     int cur = 0;
-    int *ei = nullptr, *ej = nullptr;
-    double *meas = nullptr, *r = nullptr, *Ji = nullptr, *Jj = nullptr, *g = nullptr, *Hd = nullptr, *Minv = nullptr,
-           *d = nullptr, *scale = nullptr, *x = nullptr, *rr = nullptr, *z = nullptr, *p = nullptr, *q = nullptr,
-           *part_e = nullptr, *part_a = nullptr, *part_b = nullptr, *part_c = nullptr, *part_d = nullptr;
-    unsigned char* fixed = nullptr;
+    DevBuf<int> ei, ej;
+    DevBuf<double> meas, r, Ji, Jj, g, Minv, d, scale, x, rr, z, p, q, part_e, part_a, part_b, part_c, part_d;
+    double* Hd = nullptr;               // (inside g)
+    DevBuf<unsigned char> fixed;
     int nb_nodes = 1, nb_vec = 1, nb_edges = 1;
     // one rank: the edge ends (edge * 2 + side) of every node as a CSR, and the per-edge products u = (Ji^T t | Jj^T t) [12][m]
-    int *node_start = nullptr, *end_code = nullptr;
-    double* u = nullptr;
+    DevBuf<int> node_start, end_code;
+    DevBuf<double> u;
     // multi-GPU: this engine holds one shard of the EDGES, all nodes are replicated; the hook sums the
     // gradient | diagonal blocks, every matrix-vector product and the cost across ranks
     stba_allreduce_fn ar = nullptr;
     void* ar_user = nullptr;
     int rank = 0, world = 1;
-    double* scalar = nullptr;           // one device double for the cost sums
+    DevBuf<double> scalar;              // one device double for the cost sums
     // ---- round 4: coarse space of the two-level preconditioner (see the header) and the device-side PCG control
     int agg = 0, na = 0, nc = 0, np = 0, parts = 1;      // nodes per group, groups, coarse unknowns, padded, workgroups per group
-    int* end_node = nullptr;                             // owner node of every edge end of the CSR
-    double *AdP = nullptr, *Ac0 = nullptr, *W = nullptr, *Ainv = nullptr, *inv_work = nullptr, *rc_part = nullptr, *zc = nullptr,
-           *part_cz = nullptr, *part_u = nullptr, *scal_dev = nullptr, *contrib = nullptr, *Dc = nullptr;
-    int* cflag = nullptr;            // [0]: pivot flag of the coarse factorisation, [1]: coarse operators that failed (this solve)
-    PcgState* state = nullptr;
+    DevBuf<int> end_node;                                // owner node of every edge end of the CSR
+    DevBuf<double> AdP, Ac0, W, Ainv, inv_work, rc_part, zc, part_cz, part_u, scal_dev, contrib, Dc;
+    DevBuf<int> cflag;               // [0]: pivot flag of the coarse factorisation, [1]: coarse operators that failed (this solve)
+    DevBuf<PcgState> state;
     MappedBuffer exp;                                    // the launch-path PCG's stamped block (PX_*)
     double fin_vals[8] = {0};                            // the host's validated copy of the last trial / linearisation block
     MappedBuffer fin;                                    // the trial / linearisation scalars' stamped block
     double seq = 0.0;
     int nb_nodes4 = 1;
     // ---- round 5: the PCG solve as one persistent kernel (pg_pcg_persistent_kernel)
-    int *end_pos = nullptr, *end_rem = nullptr;          // CSR position of the edge end 2 e + side | remote node of the end at a CSR position
-    double *Bend = nullptr, *ubuf = nullptr, *pbuf = nullptr;
-    int *ustamp = nullptr, *pstamp = nullptr;
+    DevBuf<int> end_pos, end_rem;                        // CSR position of the edge end 2 e + side | remote node of the end at a CSR position
+    DevBuf<double> Bend, ubuf, pbuf;
+    DevBuf<int> ustamp, pstamp;
     int max_group_ends = 0;                              // edge ends of the largest group of the coarse space
     int pp_base = 0;                                     // stamps only grow: the next solve starts behind the last one's
     bool bend_valid = false, pp_disabled = false;
@@ -1489,7 +1487,7 @@ struct stba_pg {
     // operator of LM iteration k while the first runs iteration k's PCG with the inverse made during iteration k - 1
     hipStream_t st2 = nullptr;
     hipEvent_t ev_in = nullptr, ev_read = nullptr, ev_job[2] = {nullptr, nullptr};
-    double* Ainv2 = nullptr;         // the second buffer of the pair (Ainv is the first)
+    DevBuf<double> Ainv2;            // the second buffer of the pair (Ainv is the first)
     hipEvent_t ev_t[2] = {nullptr, nullptr};      // stba_lm_options::phase_timing: around the linear solve
     bool job_in_flight = false, job_reads_pending = false, ac0_valid = false;
     stba_pcg_summary last_pcg;
@@ -1498,30 +1496,25 @@ struct stba_pg {
     std::vector<unsigned char> h_fixed;
     // per-edge square-root information W_e, component-major [36][m] like Ji (stba_pg_set_information / _sqrt_information); NULL: every
     // edge weighted by the identity, and pg_linearize launches the kernel without the whitening
-    double* Winfo = nullptr;
+    DevBuf<double> Winfo;
     // per-edge robust losses (stba_pg_set_loss): kind (STBA_LOSS_*), a, b, scale, each [m]; all NULL: no edge has a loss, and
     // pg_linearize launches a kernel without the corrector
-    int* loss_kind = nullptr;
-    double *loss_a = nullptr, *loss_b = nullptr, *loss_scale = nullptr;
+    DevBuf<int> loss_kind;
+    DevBuf<double> loss_a, loss_b, loss_scale;
 };
 
 namespace stba {
 namespace {
+// Everything of an engine that is not memory, then the engine: its DevBuf members free themselves in `delete`.  Both streams are
+// synchronised FIRST (nothing on the device reads a buffer that is about to go); then the Cholesky's per-stream cache forgets the
+// second one, then the events, the mapped blocks and the streams, and the buffers last.
 void pg_free(stba_pg* g) {
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    F(g->poses[0]); F(g->poses[1]); F(g->ei); F(g->ej); F(g->meas); F(g->r); F(g->Ji); F(g->Jj); F(g->g);
-    F(g->Minv); F(g->d); F(g->scale); F(g->x); F(g->rr); F(g->z); F(g->p); F(g->q); F(g->part_e); F(g->part_a);
-    F(g->part_b); F(g->part_c); F(g->part_d); F(g->fixed); F(g->scalar); F(g->node_start); F(g->end_code); F(g->u);
-    F(g->end_node); F(g->AdP); F(g->Ac0); F(g->W); F(g->Ainv); F(g->inv_work); F(g->rc_part); F(g->zc); F(g->part_cz); F(g->part_u);
-    F(g->scal_dev); F(g->cflag); F(g->state); F(g->contrib); F(g->Dc);
-    F(g->end_pos); F(g->end_rem); F(g->Bend); F(g->ubuf); F(g->pbuf); F(g->ustamp); F(g->pstamp); F(g->Winfo);
-    F(g->loss_kind); F(g->loss_a); F(g->loss_b); F(g->loss_scale);
+    if (g->st) (void)hipStreamSynchronize(g->st);
     if (g->st2) { (void)hipStreamSynchronize(g->st2); chol_forget_stream(g->st2); (void)hipStreamDestroy(g->st2); }
     if (g->ev_in) (void)hipEventDestroy(g->ev_in);
     if (g->ev_read) (void)hipEventDestroy(g->ev_read);
     for (auto& e : g->ev_job) if (e) (void)hipEventDestroy(e);
     for (auto& e : g->ev_t) if (e) (void)hipEventDestroy(e);
-    F(g->Ainv2);
     g->exp.release();
     g->fin.release();
     if (g->own && g->st) (void)hipStreamDestroy(g->st);
@@ -1627,15 +1620,13 @@ static int pg_setup_coarse(stba_pg* g, int group_opt) {
         max_ends = std::max(max_ends, g->h_node_start[(size_t)std::min(g->n, (a + 1) * agg)] - g->h_node_start[(size_t)std::min(g->n, a * agg)]);
     if (pg_coarse_build_lds(nc, max_ends) > PG_COARSE_BUILD_LDS_MAX)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_solve: coarse space too large for this group size");
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
     if (g->st2) STBA_HIP(hipStreamSynchronize(g->st2));       // (a job of the last solve may still be writing W / an inverse)
     g->job_in_flight = false;
-    F(g->AdP); F(g->Ac0); F(g->W); F(g->Ainv); F(g->Ainv2); F(g->inv_work); F(g->rc_part); F(g->zc); F(g->part_cz); F(g->Dc);
-    g->AdP = g->Ac0 = g->W = g->Ainv = g->Ainv2 = g->inv_work = g->rc_part = g->zc = g->part_cz = g->Dc = nullptr;
+    for (auto* buf : {&g->AdP, &g->Ac0, &g->W, &g->Ainv, &g->Ainv2, &g->inv_work, &g->rc_part, &g->zc, &g->part_cz, &g->Dc}) buf->reset();
     g->agg = 0;
-    STBA_TRY(dev_alloc(&g->AdP, (size_t)g->n * 36)); STBA_TRY(dev_alloc(&g->Ac0, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->W, (size_t)4 * np * np));
-    STBA_TRY(dev_alloc(&g->Ainv, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->Ainv2, (size_t)nc * nc)); STBA_TRY(dev_alloc(&g->Dc, (size_t)na * 36)); STBA_TRY(dev_alloc(&g->inv_work, chol_spd_inverse_workspace_doubles(np)));
-    STBA_TRY(dev_alloc(&g->rc_part, (size_t)na * parts * 6)); STBA_TRY(dev_alloc(&g->zc, (size_t)nc)); STBA_TRY(dev_alloc(&g->part_cz, (size_t)((nc + 3) / 4) * 2 + 2));
+    STBA_TRY(g->AdP.alloc((size_t)g->n * 36)); STBA_TRY(g->Ac0.alloc((size_t)nc * nc)); STBA_TRY(g->W.alloc((size_t)4 * np * np));
+    STBA_TRY(g->Ainv.alloc((size_t)nc * nc)); STBA_TRY(g->Ainv2.alloc((size_t)nc * nc)); STBA_TRY(g->Dc.alloc((size_t)na * 36)); STBA_TRY(g->inv_work.alloc(chol_spd_inverse_workspace_doubles(np)));
+    STBA_TRY(g->rc_part.alloc((size_t)na * parts * 6)); STBA_TRY(g->zc.alloc((size_t)nc)); STBA_TRY(g->part_cz.alloc((size_t)((nc + 3) / 4) * 2 + 2));
     STBA_HIP(hipMemsetAsync(g->rc_part, 0, (size_t)na * parts * 6 * sizeof(double), g->st));
     static DeviceOnce attr;
     STBA_TRY(attr.run([]() -> int {
@@ -2068,6 +2059,67 @@ void stba_pcg_default_options(stba_pcg_options* o) {
     o->coarse_async_decrease = 0.5;
 }
 
+// everything of stba_pg_create behind the engine object and its stream: the buffers and their contents.  A failure leaves a partly
+// filled engine, which stba_pg_create frees
+static int pg_fill(stba_pg* g, int n_nodes, int n_edges, const double* poses, const int* edge_i, const int* edge_j, const double* meas,
+                   const unsigned char* node_fixed) {
+    const size_t n = (size_t)n_nodes, m = (size_t)n_edges;
+    STBA_TRY(g->poses[0].alloc(n * 7)); STBA_TRY(g->poses[1].alloc(n * 7)); STBA_TRY(g->ei.alloc(m)); STBA_TRY(g->ej.alloc(m));
+    STBA_TRY(g->meas.alloc(m * 7)); STBA_TRY(g->r.alloc(m * 6)); STBA_TRY(g->Ji.alloc(m * 36)); STBA_TRY(g->Jj.alloc(m * 36));
+    STBA_TRY(g->g.alloc(n * 42)); g->Hd = g->g + n * 6;      // [gradient 6n | diagonal blocks 36n]: one cross-rank sum
+    STBA_TRY(g->Minv.alloc(n * 36)); STBA_TRY(g->d.alloc(n * 6)); STBA_TRY(g->scalar.alloc(1));
+    STBA_TRY(g->scale.alloc(n * 6)); STBA_TRY(g->x.alloc(n * 6)); STBA_TRY(g->rr.alloc(n * 6)); STBA_TRY(g->z.alloc(n * 6));
+    STBA_TRY(g->p.alloc(n * 6)); STBA_TRY(g->q.alloc(n * 6));
+    const size_t np_ = (size_t)std::max(g->nb_vec, std::max(g->nb_nodes, g->nb_edges)) * 2 + 2;
+    STBA_TRY(g->part_e.alloc(np_)); STBA_TRY(g->part_a.alloc(np_)); STBA_TRY(g->part_b.alloc(np_)); STBA_TRY(g->part_c.alloc(np_));
+    STBA_TRY(g->part_d.alloc(np_));
+    if (node_fixed) STBA_TRY(g->fixed.alloc(n));
+    STBA_TRY(g->node_start.alloc(n + 1)); STBA_TRY(g->end_code.alloc(2 * m)); STBA_TRY(g->u.alloc(12 * m));
+    STBA_TRY(g->end_node.alloc(2 * m)); STBA_TRY(g->contrib.alloc(2 * m * 28));
+    STBA_TRY(g->end_pos.alloc(2 * m)); STBA_TRY(g->end_rem.alloc(2 * m)); STBA_TRY(g->Bend.alloc(72 * m)); STBA_TRY(g->ubuf.alloc(12 * n));
+    STBA_TRY(g->pbuf.alloc((size_t)2 * 256 * PP_SLOT)); STBA_TRY(g->ustamp.alloc((size_t)256 * PP_STAMP)); STBA_TRY(g->pstamp.alloc((size_t)256 * PP_STAMP));
+    if (hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess ||
+        hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess)
+        return fail(STBA_ERR_HIP, "stba_pg_create: memset");
+    g->nb_nodes4 = (n_nodes + PG_NPW - 1) / PG_NPW;
+    STBA_TRY(g->part_u.alloc((size_t)g->nb_nodes * 4 + 4)); STBA_TRY(g->scal_dev.alloc(16)); STBA_TRY(g->state.alloc(1)); STBA_TRY(g->cflag.alloc(2));
+    if (g->exp.alloc((size_t)stamped_doubles(PX_COUNT)) != STBA_OK || g->fin.alloc(16) != STBA_OK)
+        return fail(STBA_ERR_ALLOC, "stba_pg_create: mapped host memory");
+    memset(&g->last_pcg, 0, sizeof g->last_pcg);
+    {   // edge ends sorted by node (counting sort; stable: a node's ends in edge order)
+        std::vector<int> start((size_t)n_nodes + 1, 0), code(2 * m);
+        for (int e = 0; e < n_edges; ++e) { ++start[(size_t)edge_i[e] + 1]; ++start[(size_t)edge_j[e] + 1]; }
+        for (int i = 0; i < n_nodes; ++i) start[(size_t)i + 1] += start[(size_t)i];
+        std::vector<int> fill(start.begin(), start.end() - 1), owner(2 * m), pos(2 * m), rem(2 * m);
+        for (int e = 0; e < n_edges; ++e) {
+            owner[(size_t)fill[(size_t)edge_i[e]]] = edge_i[e];
+            rem[(size_t)fill[(size_t)edge_i[e]]] = edge_j[e];
+            pos[(size_t)2 * e] = fill[(size_t)edge_i[e]];
+            code[(size_t)fill[(size_t)edge_i[e]]++] = 2 * e;
+            owner[(size_t)fill[(size_t)edge_j[e]]] = edge_j[e];
+            rem[(size_t)fill[(size_t)edge_j[e]]] = edge_i[e];
+            pos[(size_t)2 * e + 1] = fill[(size_t)edge_j[e]];
+            code[(size_t)fill[(size_t)edge_j[e]]++] = 2 * e + 1;
+        }
+        g->h_node_start = start;
+        if (upload(g->end_pos, pos.data(), 2 * m, g->st) != STBA_OK || upload(g->end_rem, rem.data(), 2 * m, g->st) != STBA_OK ||
+            upload(g->node_start, start.data(), n + 1, g->st) != STBA_OK || upload(g->end_code, code.data(), 2 * m, g->st) != STBA_OK ||
+            upload(g->end_node, owner.data(), 2 * m, g->st) != STBA_OK || hipStreamSynchronize(g->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, "stba_pg_create: upload failed");
+    }
+    if (upload(g->poses[0], poses, n * 7, g->st) != STBA_OK || upload(g->ei, edge_i, m, g->st) != STBA_OK ||
+        upload(g->ej, edge_j, m, g->st) != STBA_OK || upload(g->meas, meas, m * 7, g->st) != STBA_OK ||
+        (node_fixed && upload(g->fixed, node_fixed, n, g->st) != STBA_OK) || hipStreamSynchronize(g->st) != hipSuccess)
+        return fail(STBA_ERR_HIP, "stba_pg_create: upload failed");
+    // The buffers of the default coarse space, the second stream and its events are made HERE (round 6): a solve used to begin with
+    // a dozen allocations (the 33 MB inversion workspace among them), a stream and four events -- ~ 0.4 ms of a 6.4 ms C4 solve
+    // on a fresh engine, inside the time every caller and bench.py measure.  (A solve with another group size makes its own; a
+    // graph too large for the default space is told so by the solve, not here.)
+    if (pg_setup_coarse(g, 0) == STBA_OK && g->agg > 0) (void)pg_second_stream(g);
+    (void)hipStreamSynchronize(g->st);
+    return STBA_OK;
+}
+
 int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses, const int* edge_i, const int* edge_j,
                    const double* meas, const unsigned char* node_fixed, void* hip_stream) {
     if (!out) return fail(STBA_ERR_INVALID_ARGUMENT, "out is null");
@@ -2085,70 +2137,8 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
     if (hip_stream) g->st = reinterpret_cast<hipStream_t>(hip_stream);
     else { if (hipStreamCreate(&g->st) != hipSuccess) { delete g; return fail(STBA_ERR_HIP, "hipStreamCreate"); } g->own = true; }
     g->nb_nodes = (n_nodes + 255) / 256; g->nb_vec = (6 * n_nodes + 255) / 256; g->nb_edges = (n_edges + 255) / 256;
-    int rc = STBA_OK;
-    auto bail = [&](int c) { pg_free(g); return c; };
-#define A_(call) do { rc = (call); if (rc != STBA_OK) return bail(rc); } while (0)
-    const size_t n = (size_t)n_nodes, m = (size_t)n_edges;
-    A_(dev_alloc(&g->poses[0], n * 7)); A_(dev_alloc(&g->poses[1], n * 7)); A_(dev_alloc(&g->ei, m)); A_(dev_alloc(&g->ej, m));
-    A_(dev_alloc(&g->meas, m * 7)); A_(dev_alloc(&g->r, m * 6)); A_(dev_alloc(&g->Ji, m * 36)); A_(dev_alloc(&g->Jj, m * 36));
-    A_(dev_alloc(&g->g, n * 42)); g->Hd = g->g + n * 6;      // [gradient 6n | diagonal blocks 36n]: one cross-rank sum
-    A_(dev_alloc(&g->Minv, n * 36)); A_(dev_alloc(&g->d, n * 6)); A_(dev_alloc(&g->scalar, 1));
-    A_(dev_alloc(&g->scale, n * 6)); A_(dev_alloc(&g->x, n * 6)); A_(dev_alloc(&g->rr, n * 6)); A_(dev_alloc(&g->z, n * 6));
-    A_(dev_alloc(&g->p, n * 6)); A_(dev_alloc(&g->q, n * 6));
-    const size_t np_ = (size_t)std::max(g->nb_vec, std::max(g->nb_nodes, g->nb_edges)) * 2 + 2;
-    A_(dev_alloc(&g->part_e, np_)); A_(dev_alloc(&g->part_a, np_)); A_(dev_alloc(&g->part_b, np_)); A_(dev_alloc(&g->part_c, np_));
-    A_(dev_alloc(&g->part_d, np_));
-    if (node_fixed) A_(dev_alloc(&g->fixed, n));
-    A_(dev_alloc(&g->node_start, n + 1)); A_(dev_alloc(&g->end_code, 2 * m)); A_(dev_alloc(&g->u, 12 * m));
-    A_(dev_alloc(&g->end_node, 2 * m)); A_(dev_alloc(&g->contrib, 2 * m * 28));
-    A_(dev_alloc(&g->end_pos, 2 * m)); A_(dev_alloc(&g->end_rem, 2 * m)); A_(dev_alloc(&g->Bend, 72 * m)); A_(dev_alloc(&g->ubuf, 12 * n));
-    A_(dev_alloc(&g->pbuf, (size_t)2 * 256 * PP_SLOT)); A_(dev_alloc(&g->ustamp, (size_t)256 * PP_STAMP)); A_(dev_alloc(&g->pstamp, (size_t)256 * PP_STAMP));
-    if (hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess ||
-        hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess)
-        return bail(fail(STBA_ERR_HIP, "stba_pg_create: memset"));
-    g->nb_nodes4 = (n_nodes + PG_NPW - 1) / PG_NPW;
-    A_(dev_alloc(&g->part_u, (size_t)g->nb_nodes * 4 + 4)); A_(dev_alloc(&g->scal_dev, 16)); A_(dev_alloc(&g->state, 1)); A_(dev_alloc(&g->cflag, 2));
-    if (g->exp.alloc((size_t)stamped_doubles(PX_COUNT)) != STBA_OK || g->fin.alloc(16) != STBA_OK)
-        return bail(fail(STBA_ERR_ALLOC, "stba_pg_create: mapped host memory"));
-    memset(&g->last_pcg, 0, sizeof g->last_pcg);
-#undef A_
-    {   // edge ends sorted by node (counting sort; stable: a node's ends in edge order)
-        std::vector<int> start((size_t)n_nodes + 1, 0), code(2 * m);
-        for (int e = 0; e < n_edges; ++e) { ++start[(size_t)edge_i[e] + 1]; ++start[(size_t)edge_j[e] + 1]; }
-        for (int i = 0; i < n_nodes; ++i) start[(size_t)i + 1] += start[(size_t)i];
-        std::vector<int> fill(start.begin(), start.end() - 1), owner(2 * m), pos(2 * m), rem(2 * m);
-        for (int e = 0; e < n_edges; ++e) {
-            owner[(size_t)fill[(size_t)edge_i[e]]] = edge_i[e];
-            rem[(size_t)fill[(size_t)edge_i[e]]] = edge_j[e];
-            pos[(size_t)2 * e] = fill[(size_t)edge_i[e]];
-            code[(size_t)fill[(size_t)edge_i[e]]++] = 2 * e;
-            owner[(size_t)fill[(size_t)edge_j[e]]] = edge_j[e];
-            rem[(size_t)fill[(size_t)edge_j[e]]] = edge_i[e];
-            pos[(size_t)2 * e + 1] = fill[(size_t)edge_j[e]];
-            code[(size_t)fill[(size_t)edge_j[e]]++] = 2 * e + 1;
-        }
-        g->h_node_start = start;
-        if (hipMemcpyAsync(g->end_pos, pos.data(), 2 * m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipMemcpyAsync(g->end_rem, rem.data(), 2 * m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipMemcpyAsync(g->node_start, start.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipMemcpyAsync(g->end_code, code.data(), 2 * m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipMemcpyAsync(g->end_node, owner.data(), 2 * m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipStreamSynchronize(g->st) != hipSuccess)
-            return bail(fail(STBA_ERR_HIP, "stba_pg_create: upload failed"));
-    }
-    if (hipMemcpyAsync(g->poses[0], poses, n * 7 * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        hipMemcpyAsync(g->ei, edge_i, m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        hipMemcpyAsync(g->ej, edge_j, m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        hipMemcpyAsync(g->meas, meas, m * 7 * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        (node_fixed && hipMemcpyAsync(g->fixed, node_fixed, n, hipMemcpyHostToDevice, g->st) != hipSuccess) ||
-        hipStreamSynchronize(g->st) != hipSuccess)
-        return bail(fail(STBA_ERR_HIP, "stba_pg_create: upload failed"));
-    // The buffers of the default coarse space, the second stream and its events are made HERE (round 6): a solve used to begin with
-    // a dozen allocations (the 33 MB inversion workspace among them), a stream and four events -- ~ 0.4 ms of a 6.4 ms C4 solve
-    // on a fresh engine, inside the time every caller and bench.py measure.  (A solve with another group size makes its own; a
-    // graph too large for the default space is told so by the solve, not here.)
-    if (pg_setup_coarse(g, 0) == STBA_OK && g->agg > 0) (void)pg_second_stream(g);
-    (void)hipStreamSynchronize(g->st);
+    const int rc = pg_fill(g, n_nodes, n_edges, poses, edge_i, edge_j, meas, node_fixed);
+    if (rc != STBA_OK) { pg_free(g); return rc; }
     *out = g;
     return STBA_OK;
 }
@@ -2163,7 +2153,6 @@ int stba_pg_set_allreduce(stba_pg* g, stba_allreduce_fn fn, void* user, int rank
 
 int stba_pg_destroy(stba_pg* g) {
     if (!g) return STBA_OK;
-    if (g->st) (void)hipStreamSynchronize(g->st);
     pg_free(g);
     return STBA_OK;
 }
@@ -2357,38 +2346,26 @@ int stba_pg_solve(stba_pg* g, const stba_lm_options* opt_in, const stba_pcg_opti
 // swaps it in (a refused one leaves the engine with the weights it had), NULL releases the array
 static int pg_set_weights(stba_pg* g, const double* in, int sqrt_form, const char* who) {
     if (!g) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    double* Wnew = nullptr;
+    DevBuf<double> Wnew;
     if (in) {
         const size_t cnt = (size_t)g->m * 36;
-        double* stage = nullptr;
-        int* bad = nullptr;
+        DevBuf<double> stage;
+        DevBuf<int> bad;
         int bad_h = INT_MAX;
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        int rc = dev_alloc(&Wnew, cnt);
-        if (rc == STBA_OK) rc = dev_alloc(&stage, cnt);
-        if (rc == STBA_OK) rc = dev_alloc(&bad, 1);
-        if (rc == STBA_OK &&
-            (hipMemcpyAsync(stage, in, cnt * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-             hipMemcpyAsync(bad, &bad_h, sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess))
-            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-        if (rc == STBA_OK) {
-            hipLaunchKernelGGL(pg_information_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, (const double*)stage, sqrt_form, Wnew, bad);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, g->st) != hipSuccess ||
-                hipStreamSynchronize(g->st) != hipSuccess)
-                rc = fail(STBA_ERR_HIP, std::string(who) + ": the conversion kernel failed");
-        }
-        F(stage); F(bad);
-        if (rc == STBA_OK && bad_h != INT_MAX)
-            rc = sqrt_form ? fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": edge " + std::to_string(bad_h) + ": the square-root information has an entry that is not finite")
-                           : fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string(who) + ": edge " + std::to_string(bad_h) + ": the information matrix is not positive definite (or has an entry that is not finite)");
-        if (rc != STBA_OK) { F(Wnew); return rc; }
+        STBA_TRY(Wnew.alloc(cnt)); STBA_TRY(stage.alloc(cnt)); STBA_TRY(bad.alloc(1));
+        if (upload(stage, in, cnt, g->st) != STBA_OK || upload(bad, &bad_h, 1, g->st) != STBA_OK)
+            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
+        hipLaunchKernelGGL(pg_information_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, (const double*)stage, sqrt_form, Wnew.get(), bad.get());
+        if (hipGetLastError() != hipSuccess || download(&bad_h, bad, 1, g->st) != STBA_OK || hipStreamSynchronize(g->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, std::string(who) + ": the conversion kernel failed");
+        if (bad_h != INT_MAX)
+            return sqrt_form ? fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": edge " + std::to_string(bad_h) + ": the square-root information has an entry that is not finite")
+                             : fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string(who) + ": edge " + std::to_string(bad_h) + ": the information matrix is not positive definite (or has an entry that is not finite)");
     }
-    // (nothing of the engine may still be reading the old array or what was linearised with it)
+    // (nothing of the engine may still be reading the old array or what was linearised with it: the move below frees it)
     STBA_HIP(hipStreamSynchronize(g->st));
     if (g->st2) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; g->job_reads_pending = false; }
-    if (g->Winfo) (void)hipFree(g->Winfo);
-    g->Winfo = Wnew;
+    g->Winfo = std::move(Wnew);
     g->bend_valid = false; g->coarse_valid = false; g->ac0_valid = false;      // what pg_linearize and the solve's linearisation reset
     return STBA_OK;
 }
@@ -2406,42 +2383,22 @@ int stba_pg_has_information(const stba_pg* g, int* has) {
 int stba_pg_set_loss(stba_pg* g, const int* kind, const double* a, const double* b, const double* scale) {
     const char* who = "stba_pg_set_loss";
     if (!g) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    int* k_new = nullptr;
-    double *a_new = nullptr, *b_new = nullptr, *s_new = nullptr;
+    DevBuf<int> k_new;
+    DevBuf<double> a_new, b_new, s_new;
     if (kind) {
         const size_t m = (size_t)g->m;
-        std::vector<double> ha(m, 1.0), hb(m, 1.0), hs(m, 1.0);
-        for (size_t e = 0; e < m; ++e) {
-            const int kd = kind[e];
-            std::string why;
-            if (kd < STBA_LOSS_TRIVIAL || kd > STBA_LOSS_TUKEY) why = "unknown loss kind " + std::to_string(kd);
-            else if (kd != STBA_LOSS_TRIVIAL && (!a || !std::isfinite(a[e]) || !(a[e] > 0.0))) why = "the loss parameter a must be finite and positive";
-            else if (kd == STBA_LOSS_TOLERANT && (!b || !std::isfinite(b[e]) || !(b[e] > 0.0))) why = "the loss parameter b must be finite and positive";
-            else if (scale && (!std::isfinite(scale[e]) || !(scale[e] >= 0.0))) why = "the loss scale must be finite and not negative";
-            if (!why.empty()) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": edge " + std::to_string(e) + ": " + why);
-            if (kd != STBA_LOSS_TRIVIAL) ha[e] = a[e];
-            if (kd == STBA_LOSS_TOLERANT) hb[e] = b[e];
-            if (scale) hs[e] = scale[e];
-        }
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        int rc = dev_alloc(&k_new, m);
-        if (rc == STBA_OK) rc = dev_alloc(&a_new, m);
-        if (rc == STBA_OK) rc = dev_alloc(&b_new, m);
-        if (rc == STBA_OK) rc = dev_alloc(&s_new, m);
-        if (rc == STBA_OK &&
-            (hipMemcpyAsync(k_new, kind, m * sizeof(int), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-             hipMemcpyAsync(a_new, ha.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-             hipMemcpyAsync(b_new, hb.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-             hipMemcpyAsync(s_new, hs.data(), m * sizeof(double), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-             hipStreamSynchronize(g->st) != hipSuccess))
-            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-        if (rc != STBA_OK) { F(k_new); F(a_new); F(b_new); F(s_new); return rc; }
+        std::vector<double> ha, hb, hs;
+        STBA_TRY(loss_table_check(who, "edge", m, kind, a, b, scale, ha, hb, hs));
+        STBA_TRY(k_new.alloc(m)); STBA_TRY(a_new.alloc(m)); STBA_TRY(b_new.alloc(m)); STBA_TRY(s_new.alloc(m));
+        if (upload(k_new, kind, m, g->st) != STBA_OK || upload(a_new, ha.data(), m, g->st) != STBA_OK ||
+            upload(b_new, hb.data(), m, g->st) != STBA_OK || upload(s_new, hs.data(), m, g->st) != STBA_OK ||
+            hipStreamSynchronize(g->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
     }
-    // (nothing of the engine may still be reading the old table or what was linearised with it)
+    // (nothing of the engine may still be reading the old table or what was linearised with it: the moves below free it)
     STBA_HIP(hipStreamSynchronize(g->st));
     if (g->st2) { STBA_HIP(hipStreamSynchronize(g->st2)); g->job_in_flight = false; g->job_reads_pending = false; }
-    for (void* p : {(void*)g->loss_kind, (void*)g->loss_a, (void*)g->loss_b, (void*)g->loss_scale}) if (p) (void)hipFree(p);
-    g->loss_kind = k_new; g->loss_a = a_new; g->loss_b = b_new; g->loss_scale = s_new;
+    g->loss_kind = std::move(k_new); g->loss_a = std::move(a_new); g->loss_b = std::move(b_new); g->loss_scale = std::move(s_new);
     g->bend_valid = false; g->coarse_valid = false; g->ac0_valid = false;
     return STBA_OK;
 }

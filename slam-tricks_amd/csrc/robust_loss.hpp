@@ -2,6 +2,7 @@
 // (pg_engine.hip) and bundle adjustment's (ba_kernels.hip)
 #pragma once
 #include <cfloat>
+#include <vector>
 
 #include "common.hpp"      // (with include/stba.h: the STBA_LOSS_* kinds)
 
@@ -51,6 +52,27 @@ __device__ inline void robust_loss(int kind, double a, double b, double s, doubl
     default:                                    // TRIVIAL with a scale
         rho[0] = s; rho[1] = 1.0; rho[2] = 0.0;
     }
+}
+
+// host: a caller's loss table (m entries; a, b, scale may be null) checked before an engine takes it.  The first bad entry is
+// refused as "<who>: <noun> <index>: <reason>"; otherwise ha, hb, hs hold a, b, scale with the defaults (1) where an entry's kind does
+// not read them.  `noun`: what an entry belongs to ("observation", "edge")
+inline int loss_table_check(const char* who, const char* noun, size_t m, const int* kind, const double* a, const double* b,
+                            const double* scale, std::vector<double>& ha, std::vector<double>& hb, std::vector<double>& hs) {
+    ha.assign(m, 1.0); hb.assign(m, 1.0); hs.assign(m, 1.0);
+    for (size_t e = 0; e < m; ++e) {
+        const int kd = kind[e];
+        std::string why;
+        if (kd < STBA_LOSS_TRIVIAL || kd > STBA_LOSS_TUKEY) why = "unknown loss kind " + std::to_string(kd);
+        else if (kd != STBA_LOSS_TRIVIAL && (!a || !std::isfinite(a[e]) || !(a[e] > 0.0))) why = "the loss parameter a must be finite and positive";
+        else if (kd == STBA_LOSS_TOLERANT && (!b || !std::isfinite(b[e]) || !(b[e] > 0.0))) why = "the loss parameter b must be finite and positive";
+        else if (scale && (!std::isfinite(scale[e]) || !(scale[e] >= 0.0))) why = "the loss scale must be finite and not negative";
+        if (!why.empty()) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": " + noun + " " + std::to_string(e) + ": " + why);
+        if (kd != STBA_LOSS_TRIVIAL) ha[e] = a[e];
+        if (kd == STBA_LOSS_TOLERANT) hb[e] = b[e];
+        if (scale) hs[e] = scale[e];
+    }
+    return STBA_OK;
 }
 
 }  // namespace stba

@@ -17,6 +17,7 @@
 #include "dogleg.hpp"
 #include "inner_iterations.hpp"
 #include "lm_policy.hpp"
+#include "robust_loss.hpp"
 
 namespace stba {
 
@@ -29,20 +30,6 @@ int require_device() {
         return fail(STBA_ERR_NO_DEVICE, std::string("no HIP device visible (") +
                                             (e == hipSuccess ? "count=0" : hipGetErrorString(e)) +
                                             "); libstba has no CPU fallback");
-    return STBA_OK;
-}
-
-template <class T>
-static int upload(T* dst, const T* src, size_t count, hipStream_t st) {
-    if (count == 0) return STBA_OK;
-    STBA_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return STBA_OK;
-}
-
-template <class T>
-static int download(T* dst, const T* src, size_t count, hipStream_t st) {
-    if (count == 0) return STBA_OK;
-    STBA_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, st));
     return STBA_OK;
 }
 
@@ -76,67 +63,66 @@ struct stba_ba {
     bool own_stream = false;
     std::vector<int> perm;   // sorted position -> caller's observation index
     // device
-    double* cams[2] = {nullptr, nullptr};
-    double* pts[2] = {nullptr, nullptr};
+    DevBuf<double> cams[2], pts[2];
     int cur = 0;
-    double2* feat = nullptr;
-    int *obs_cam = nullptr, *obs_pt = nullptr, *pt_start = nullptr;
-    int *cam_perm = nullptr, *chunk_begin = nullptr, *chunk_end = nullptr, *cam_chunk_start = nullptr;
+    DevBuf<double2> feat;
+    DevBuf<int> obs_cam, obs_pt, pt_start;
+    DevBuf<int> cam_perm, chunk_begin, chunk_end, cam_chunk_start;
     int n_chunks = 0;
     // Schur plan: task = (camera row, slice [lo, hi) of the row's column list), see build_schur_plan (schur_plan.hpp)
-    int *task_cam = nullptr, *cam_start = nullptr, *row_col_ptr = nullptr, *row_cols = nullptr;
-    int *task_col_lo = nullptr, *task_col_hi = nullptr;
+    DevBuf<int> task_cam, cam_start, row_col_ptr, row_cols;
+    DevBuf<int> task_col_lo, task_col_hi;
     int n_tasks = 0, max_cols = 0;
     // round 6, FEW camera rows (landmark-heavy problems): a task = (camera row, a RANGE of the camera's observation list), all columns of
     // the row; the slices of a row write partial blocks, ba_schur_reduce_slices_kernel adds them in order (see plan_rows, schur_plan.hpp)
-    int *task_p_lo = nullptr, *task_p_hi = nullptr, *row_task_ptr = nullptr, *row_tasks = nullptr;
-    long long* task_part_off = nullptr;
-    double* schur_part = nullptr;
+    DevBuf<int> task_p_lo, task_p_hi, row_task_ptr, row_tasks;
+    DevBuf<long long> task_part_off;
+    DevBuf<double> schur_part;
     bool lm_slices = false;
     std::shared_ptr<SchurPlan> create_leftovers;     // the host-side plan of ba_create, kept until the engine goes (see there)
     std::vector<unsigned char> create_omask;         // (the host copy of omask: kept, and freed, with it)
     // pair plan of the Schur kernel (see ba_schur_pairs_kernel)
-    int *pair_begin = nullptr, *pair_end = nullptr;      // per (task, wave)
-    int *task_vs_ptr = nullptr, *vs_first = nullptr;     // per task: first accumulator slot of every block of its slice (+ the slot count)
+    DevBuf<int> pair_begin, pair_end;      // per (task, wave)
+    DevBuf<int> task_vs_ptr, vs_first;     // per task: first accumulator slot of every block of its slice (+ the slot count)
     int schur_plan_mode = 0;                              // SchurArgs::mode the plan was built for
-    int4* pair_rec = nullptr;           // (i, l, landmark, slot | flags)
+    DevBuf<int4> pair_rec;           // (i, l, landmark, slot | flags)
     double schur_pairs = 0.0, schur_lds_atomics = 0.0;   // per launch of the Schur kernel (measurement)
     // the Schur complement as a dense symmetric product (dense visibility; ba_kernels.hip "DENSE visibility", stba_ba_set_schur_mode)
     int schur_mode = STBA_SCHUR_PAIRS, schur_mode_auto = STBA_SCHUR_PAIRS;
     bool have_pair_plan = false;
-    double* Y = nullptr; size_t ldy = 0, ykcols = 0;     // [lda][ldy]
-    double *yv = nullptr, *yws = nullptr;
-    unsigned char* dup_run = nullptr;                    // repeated (camera, landmark) pairs, per position of cam_perm (null: none)
+    DevBuf<double> Y; size_t ldy = 0, ykcols = 0;     // [lda][ldy]
+    DevBuf<double> yv, yws;
+    DevBuf<unsigned char> dup_run;                    // repeated (camera, landmark) pairs, per position of cam_perm (null: none)
     bool dup_overflow = false;                           // some pair has more than 255 observations: the DENSE form cannot take this problem
     int stage_cooldown = 0;                              // several ranks: factorisations left that take the stage kernels (see ba_run_lm)
-    unsigned char *cam_fixed = nullptr, *pt_fixed = nullptr;
-    double2* r = nullptr;
-    double* J8 = nullptr;            // compact Jacobian [n_obs][8] (ba_kernels.hip)
+    DevBuf<unsigned char> cam_fixed, pt_fixed;
+    DevBuf<double2> r;
+    DevBuf<double> J8;            // compact Jacobian [n_obs][8] (ba_kernels.hip)
     // host-linearised factors (stba_ba_set_host_linearizer): the user's cost functions make r and the 2x6 | 2x3 Jacobians on the
     // host; J8 then holds {0, 0, Jp} per observation and Jc12 the camera blocks -- everything behind the linearisation is unchanged
     stba_ba_linearize_fn hl_fn = nullptr;
     void* hl_user = nullptr;
-    double* Jc12 = nullptr;          // [n_obs][12]
+    DevBuf<double> Jc12;          // [n_obs][12]
     std::vector<double> hl_cams, hl_pts, hl_r, hl_jc, hl_jp, hl_stage, hl_cost_stage;   // host staging (caller order | engine order)
     // per-observation robust losses (stba_ba_set_loss): kind (STBA_LOSS_*), a, b, scale, each [n_obs] in the engine's
     // order; all null: no table.  With one, ba_linearize_robust_kernel writes the corrected r', J8 = {0, 0, Jp'} and Jc12 = Jc', and
     // everything behind the linearisation runs its general form on them, as for host-linearised factors
-    int* loss_kind = nullptr;
-    double *loss_a = nullptr, *loss_b = nullptr, *loss_scale = nullptr;
+    DevBuf<int> loss_kind;
+    DevBuf<double> loss_a, loss_b, loss_scale;
     // per-observation square-root information W_i (stba_ba_set_information / _sqrt_information): [n_obs][4], 2 x 2
     // row-major in the engine's order; null: the identity.  With it the same kernel whitens r, Jc, Jp in front of the corrector
-    double* winfo = nullptr;
-    unsigned char* omask = nullptr;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
-    double *Hpp6 = nullptr, *gp = nullptr, *Hinv6 = nullptr, *Rinv9 = nullptr, *dp = nullptr, *scale_p = nullptr;
-    double *Hcc = nullptr, *gc = nullptr, *cam_partial = nullptr, *dc = nullptr, *scale_c = nullptr;
-    double* Sbuf = nullptr;   // [S lda*lda | ex_diag lda | ex_gc lda | rhs lda | ex_scalar lda]
-    double *dxc = nullptr, *dxp = nullptr;
-    double *cost_partial = nullptr, *upd_partial_c = nullptr, *upd_partial_p = nullptr;
-    double* trial = nullptr;   // TS_BLOCK doubles
+    DevBuf<double> winfo;
+    DevBuf<unsigned char> omask;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
+    DevBuf<double> Hpp6, gp, Hinv6, Rinv9, dp, scale_p;
+    DevBuf<double> Hcc, gc, cam_partial, dc, scale_c;
+    DevBuf<double> Sbuf;   // [S lda*lda | ex_diag lda | ex_gc lda | rhs lda | ex_scalar lda]
+    DevBuf<double> dxc, dxp;
+    DevBuf<double> cost_partial, upd_partial_c, upd_partial_p;
+    DevBuf<double> trial;   // TS_BLOCK doubles
     MappedBuffer ts_host;        // the trial block + the factorisation flag as a stamped block, written by a kernel
     double ts_seq = 0.0;         // sequence number of the last trial block asked for (the stamp of the block's lines)
     double ts_vals[TS_BLOCK] = {0};          // the host's copy of the last trial block (validated, or downloaded after a synchronise)
-    int* flag = nullptr;
+    DevBuf<int> flag;
     int lin_grid = 1;
     stba_allreduce_fn ar = nullptr;
     void* ar_user = nullptr;
@@ -155,8 +141,8 @@ struct stba_ba {
     int pcg_precond = STBA_PRECOND_JACOBI, pcg_min = 0, pcg_max = 500, pcg_check = 4;
     double pcg_eta = 0.1;
     stba_pcg_summary pcg_sum{};
-    double *pcg_vec = nullptr, *pcg_minv = nullptr, *pcg_sj = nullptr, *pcg_part = nullptr;
-    PcgState* pcg_state = nullptr;
+    DevBuf<double> pcg_vec, pcg_minv, pcg_sj, pcg_part;
+    DevBuf<PcgState> pcg_state;
     MappedBuffer pcg_host;
     double pcg_seq = 0.0;
     int pcg_last_it = 0, pcg_last_cap = 0;     // the last solve, counted into pcg_sum once the LM loop keeps its step
@@ -164,7 +150,7 @@ struct stba_ba {
     // DOGLEG (stba_ba_set_trust_region; dogleg.hip): s .* u of cameras and landmarks, the terms kernel's partials, the six scalars,
     // the step's stamped block for the host; the summary of the last solve
     int trust_region = STBA_TR_LEVENBERG_MARQUARDT;
-    double *dl_uc = nullptr, *dl_up = nullptr, *dl_part = nullptr, *dl_sc = nullptr;
+    DevBuf<double> dl_uc, dl_up, dl_part, dl_sc;
     MappedBuffer dl_host;
     double dl_seq = 0.0;
     stba_dogleg_summary dl_sum{};
@@ -177,9 +163,9 @@ struct stba_ba {
     std::vector<InnerGroup> inner_groups;
     std::vector<int> inner_cam_h, inner_pt_h;
     std::vector<unsigned char> inner_mask_h, inner_kind_h;   // kind: 1 rotation, 2 position, 3 both (a 6-dof block)
-    int *inner_cam = nullptr, *inner_pt = nullptr, *inner_it = nullptr, *inner_gate = nullptr;
-    unsigned char* inner_mask = nullptr;
-    double *inner_sc = nullptr, *inner_part = nullptr;
+    DevBuf<int> inner_cam, inner_pt, inner_it, inner_gate;
+    DevBuf<unsigned char> inner_mask;
+    DevBuf<double> inner_sc, inner_part;
     hipEvent_t inner_ev[2] = {};
     stba_inner_summary inner_sum{};
     // camera pose priors (stba_ba_set_pose_priors; ba_prior.hip): grouped by camera -- CSR over the cameras that have
@@ -188,8 +174,8 @@ struct stba_ba {
     // the lineariser's lin_grid (n_cost), filled by the cost form at every linearisation; the block form adds to Hcc, gc behind the
     // Schur step at lin_which, the parameter buffer the Jacobian records were last made at
     int n_prior = 0, n_prior_groups = 0;
-    int *prior_ptr = nullptr, *prior_cam = nullptr;
-    double *prior_pose = nullptr, *prior_W = nullptr;
+    DevBuf<int> prior_ptr, prior_cam;
+    DevBuf<double> prior_pose, prior_W;
     std::vector<int> prior_order;
     int lin_which = 0;
     int n_cost() const { return lin_grid + (n_prior ? 1 : 0); }
@@ -206,11 +192,11 @@ struct stba_ba {
     // triangle is ever read), followed by the four extras vectors: [tri n(n+1)/2 | ex_diag | ex_gc | rhs | scalars]
     // When the union over ranks of the non-zero 6x6 blocks is sparse (C5: 14 % of the camera pairs share a
     // landmark), only those blocks travel: [blocks pk_nz * 36 | extras] -- 20 MB instead of 144 MB at C5.
-    double* Spack = nullptr;
+    DevBuf<double> Spack;
     std::vector<int> h_row_col_ptr, h_row_cols;   // host copy of the local block pattern (lower triangle, by camera)
     int pk_state = 0;           // 0: not planned yet, 1: triangle, 2: block list
     int pk_nz = 0;
-    int2* pk_blocks = nullptr;  // (row camera, column camera) of every travelling block
+    DevBuf<int2> pk_blocks;  // (row camera, column camera) of every travelling block
     size_t pack_count() const {
         return (pk_state == 2 ? (size_t)pk_nz * 36 : (size_t)n * (n + 1) / 2) + 4 * (size_t)lda;
     }
@@ -218,30 +204,20 @@ struct stba_ba {
 
 namespace stba {
 
+// Everything of an engine that is not memory, then the engine: its DevBuf members free themselves in `delete`.  The order: the
+// stream is synchronised FIRST (nothing on the device reads a buffer that is about to go), then the Cholesky's per-stream cache
+// forgets it, then the events, the mapped blocks and the stream itself, and the buffers last.
 static void ba_free(stba_ba* b) {
+    if (b->st) { (void)hipStreamSynchronize(b->st); chol_forget_stream(b->st); }
     b->create_leftovers.reset();                        // (what ba_create's plan left on the host)
     std::vector<unsigned char>().swap(b->create_omask);
     cov_store_free(b->cov);
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    F(b->cams[0]); F(b->cams[1]); F(b->pts[0]); F(b->pts[1]); F(b->feat); F(b->obs_cam); F(b->obs_pt);
-    F(b->pt_start); F(b->cam_perm); F(b->chunk_begin); F(b->chunk_end); F(b->cam_chunk_start); F(b->cam_fixed);
-    F(b->pt_fixed); F(b->r); F(b->J8); F(b->Jc12); F(b->loss_kind); F(b->loss_a); F(b->loss_b); F(b->loss_scale); F(b->winfo); F(b->omask); F(b->Hpp6); F(b->gp); F(b->Hinv6); F(b->Rinv9); F(b->dp); F(b->scale_p);
-    F(b->Hcc); F(b->gc); F(b->cam_partial); F(b->dc); F(b->scale_c); F(b->Sbuf); F(b->Spack); F(b->pk_blocks); F(b->dxc); F(b->dxp);
-    F(b->task_cam); F(b->cam_start); F(b->task_col_lo); F(b->task_col_hi); F(b->row_col_ptr); F(b->row_cols);
-    F(b->task_p_lo); F(b->task_p_hi); F(b->row_task_ptr); F(b->row_tasks); F(b->task_part_off); F(b->schur_part);
-    F(b->pair_begin); F(b->pair_end); F(b->pair_rec); F(b->task_vs_ptr); F(b->vs_first); F(b->Y); F(b->yv); F(b->yws); F(b->dup_run);
-    F(b->cost_partial); F(b->upd_partial_c); F(b->upd_partial_p); F(b->trial); F(b->flag);
-    F(b->pcg_vec); F(b->pcg_minv); F(b->pcg_sj); F(b->pcg_part); F(b->pcg_state);
-    b->pcg_host.release();
-    F(b->dl_uc); F(b->dl_up); F(b->dl_part); F(b->dl_sc);
-    b->dl_host.release();
-    F(b->prior_ptr); F(b->prior_cam); F(b->prior_pose); F(b->prior_W);
-    F(b->inner_cam); F(b->inner_pt); F(b->inner_it); F(b->inner_gate); F(b->inner_mask); F(b->inner_sc); F(b->inner_part);
     for (auto& e : b->inner_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
+    b->pcg_host.release();
+    b->dl_host.release();
     b->ts_host.release();
-    if (b->st) { (void)hipStreamSynchronize(b->st); chol_forget_stream(b->st); }
     if (b->own_stream && b->st) (void)hipStreamDestroy(b->st);
     delete b;
 }
@@ -283,7 +259,7 @@ static int ba_host_linearize(stba_ba* b, int which, bool with_jac) {
     if (with_jac) {
         st.resize(no * 12);
         for (size_t p = 0; p < no; ++p) { const size_t i = (size_t)b->perm[p]; memcpy(&st[p * 2], &b->hl_r[i * 2], 2 * sizeof(double)); }
-        STBA_TRY(upload(reinterpret_cast<double*>(b->r), st.data(), no * 2, b->st));
+        STBA_TRY(upload(reinterpret_cast<double*>(b->r.get()), st.data(), no * 2, b->st));
         STBA_HIP(hipStreamSynchronize(b->st));              // (the staging buffer is reused)
         for (size_t p = 0; p < no; ++p) {
             const size_t i = (size_t)b->perm[p];
@@ -301,7 +277,7 @@ static int ba_host_linearize(stba_ba* b, int which, bool with_jac) {
 
 // the camera blocks of the GENERAL form (J8 = {0, 0, Jp}, Jc12 = the 2 x 6 blocks), which every kernel behind the linearisation
 // takes in its GEN instantiation: host-linearised factors and engines with a loss table or weights; null: the compact record
-static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind || b->winfo) ? b->Jc12 : nullptr; }
+static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind || b->winfo) ? b->Jc12.get() : nullptr; }
 
 // THE linearisation at parameter buffer `which`: the host's callback, the robust kernel (a loss table and / or weights are set: its
 // INFO / LOSS pair follows from which of the two the engine holds) or the lossless kernel.  The cost partials (sum r^2, or sum rho with a table) are left in cost_partial; with_jac: r, J8 (and Jc12) are stored
@@ -408,28 +384,27 @@ static int ba_plan_pack(stba_ba* b) {
             for (int k = b->h_row_col_ptr[(size_t)c]; k < b->h_row_col_ptr[(size_t)c + 1]; ++k)
                 mask[(size_t)c * (c + 1) / 2 + b->h_row_cols[(size_t)k]] = 1.0;
         }
-        double* dmask = nullptr;
-        STBA_TRY(dev_alloc(&dmask, nb));
-        int rc = upload(dmask, mask.data(), nb, b->st);
-        if (rc == STBA_OK && b->ar(b->ar_user, dmask, nb, b->st) != 0) rc = fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
-        if (rc == STBA_OK && hipMemcpyAsync(mask.data(), dmask, nb * sizeof(double), hipMemcpyDeviceToHost, b->st) != hipSuccess)
-            rc = fail(STBA_ERR_HIP, "mask download failed");
-        if (rc == STBA_OK && hipStreamSynchronize(b->st) != hipSuccess) rc = fail(STBA_ERR_HIP, "mask download failed");
-        (void)hipFree(dmask);
-        if (rc != STBA_OK) return rc;
+        DevBuf<double> dmask;
+        STBA_TRY(dmask.alloc(nb));
+        STBA_TRY(upload(dmask, mask.data(), nb, b->st));
+        if (b->ar(b->ar_user, dmask, nb, b->st) != 0) return fail(STBA_ERR_CALLBACK, "all-reduce hook failed");
+        if (hipMemcpyAsync(mask.data(), dmask, nb * sizeof(double), hipMemcpyDeviceToHost, b->st) != hipSuccess ||
+            hipStreamSynchronize(b->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, "mask download failed");
+        dmask.reset();
         std::vector<int2> blocks;
         for (int c = 0; c < b->nc; ++c)
             for (int c2 = 0; c2 <= c; ++c2)
                 if (mask[(size_t)c * (c + 1) / 2 + c2] > 0.5) blocks.push_back(make_int2(c, c2));
         if (blocks.size() * 36 * 2 < (size_t)b->n * (b->n + 1) / 2) {      // worth it below 50 % of the triangle
-            STBA_TRY(dev_alloc(&b->pk_blocks, blocks.size()));
+            STBA_TRY(b->pk_blocks.alloc(blocks.size()));
             STBA_TRY(upload(b->pk_blocks, blocks.data(), blocks.size(), b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
             b->pk_nz = (int)blocks.size();
             b->pk_state = 2;
         }
     }
-    STBA_TRY(dev_alloc(&b->Spack, b->pack_count()));
+    STBA_TRY(b->Spack.alloc(b->pack_count()));
     return STBA_OK;
 }
 
@@ -453,16 +428,16 @@ static int ba_dense_alloc(stba_ba* b) {
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (ycount + wcount + kcols) * sizeof(double) > free_b / 10 * 9)
         return fail(STBA_ERR_INVALID_ARGUMENT, "the dense form of the Schur complement needs " + std::to_string((ycount + wcount) * 8 / (1 << 20)) +
                     " MiB (6 cameras x 3 landmarks doubles, padded), more than the device has free");
-    STBA_TRY(dev_alloc(&b->Y, ycount));
-    STBA_TRY(dev_alloc(&b->yv, schur_dense_partial_doubles(b->n_chunks)));      // (the chunk partials of the camera sums)
-    if (wcount) STBA_TRY(dev_alloc(&b->yws, wcount));
+    STBA_TRY(b->Y.alloc(ycount));
+    STBA_TRY(b->yv.alloc(schur_dense_partial_doubles(b->n_chunks)));      // (the chunk partials of the camera sums)
+    if (wcount) STBA_TRY(b->yws.alloc(wcount));
     STBA_HIP(hipMemsetAsync(b->Y, 0, ycount * sizeof(double), b->st));
     b->ldy = ldy; b->ykcols = kcols;
     return STBA_OK;
 }
 
 // where the landmark inversion in front of a Schur step puts the root of the inverse: only the dense form reads it
-static double* ba_rinv(stba_ba* b) { return b->schur_mode == STBA_SCHUR_DENSE ? b->Rinv9 : nullptr; }
+static double* ba_rinv(stba_ba* b) { return b->schur_mode == STBA_SCHUR_DENSE ? b->Rinv9.get() : nullptr; }
 
 // S (lower triangle), rhs, Hcc, gc from the linearisation and the inverse landmark blocks: the pair plan or the dense product
 static int ba_schur_step(stba_ba* b) {
@@ -657,11 +632,11 @@ static PcgVecs pcg_vecs(stba_ba* b) {
 }
 
 static int ba_pcg_alloc(stba_ba* b) {
-    STBA_TRY(dev_alloc(&b->pcg_vec, 4 * (size_t)b->lda));
-    STBA_TRY(dev_alloc(&b->pcg_minv, (size_t)b->nc * 36));
-    STBA_TRY(dev_alloc(&b->pcg_sj, (size_t)std::max(b->n_chunks, 1) * 24));
-    STBA_TRY(dev_alloc(&b->pcg_part, 3 * (size_t)is_vec_grid(b->nc)));
-    STBA_TRY(dev_alloc(&b->pcg_state, 1));
+    STBA_TRY(b->pcg_vec.alloc(4 * (size_t)b->lda));
+    STBA_TRY(b->pcg_minv.alloc((size_t)b->nc * 36));
+    STBA_TRY(b->pcg_sj.alloc((size_t)std::max(b->n_chunks, 1) * 24));
+    STBA_TRY(b->pcg_part.alloc(3 * (size_t)is_vec_grid(b->nc)));
+    STBA_TRY(b->pcg_state.alloc(1));
     STBA_HIP(hipMemsetAsync(b->pcg_vec, 0, 4 * (size_t)b->lda * sizeof(double), b->st));
     STBA_HIP(hipMemsetAsync(b->pcg_state, 0, sizeof(PcgState), b->st));
     STBA_HIP(hipMemsetAsync(b->flag, 0, sizeof(int), b->st));       // (no factorisation: the trial block's flag stays 0)
@@ -1194,10 +1169,10 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
 // ba_run_lm), unless somebody watches the iterations.
 static int ba_dogleg_alloc(stba_ba* b) {
     if (b->dl_sc) return STBA_OK;
-    STBA_TRY(dev_alloc(&b->dl_uc, (size_t)std::max(b->n, 1)));
-    STBA_TRY(dev_alloc(&b->dl_up, (size_t)std::max(b->np, 1) * 3));
-    STBA_TRY(dev_alloc(&b->dl_part, dogleg_partial_doubles(b->nc, b->np)));
-    STBA_TRY(dev_alloc(&b->dl_sc, 8));
+    STBA_TRY(b->dl_uc.alloc((size_t)std::max(b->n, 1)));
+    STBA_TRY(b->dl_up.alloc((size_t)std::max(b->np, 1) * 3));
+    STBA_TRY(b->dl_part.alloc(dogleg_partial_doubles(b->nc, b->np)));
+    STBA_TRY(b->dl_sc.alloc(8));
     return b->dl_host.alloc((size_t)stamped_doubles(DL_BLOCK));
 }
 
@@ -1373,6 +1348,11 @@ const char* stba_status_string(int status) {
 
 const char* stba_last_error(void) { return g_last_error.c_str(); }
 int stba_version(void) { return STBA_VERSION; }
+int stba_live_device_buffers(long long* count) {
+    if (!count) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_live_device_buffers: null argument");
+    *count = g_live_device_buffers.load(std::memory_order_relaxed);
+    return STBA_OK;
+}
 
 int stba_device_count(void) {
     int n = 0;
@@ -1382,30 +1362,11 @@ int stba_device_count(void) {
 
 void stba_lm_default_options(stba_lm_options* opt) { if (opt) default_options(opt); }
 
-// (iterative: ITERATIVE_SCHUR -- no Schur plan, no dense Y, no S: see stba_ba_create_ex)
-static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
-                     const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
-                     const unsigned char* pt_fixed, void* hip_stream, bool iterative) {
-    if (!out) return fail(STBA_ERR_INVALID_ARGUMENT, "out is null");
-    *out = nullptr;
-    if (n_cams <= 0 || n_pts < 0 || n_obs < 0 || !cams || (n_pts > 0 && !pts) ||
-        (n_obs > 0 && (!obs_cam || !obs_pt || !obs_feat)))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: null or empty input");
-    for (int i = 0; i < n_obs; ++i)
-        if (obs_cam[i] < 0 || obs_cam[i] >= n_cams || obs_pt[i] < 0 || obs_pt[i] >= n_pts)
-            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: observation index out of range");
-    STBA_TRY(require_device());
-    stba_ba* b = new stba_ba();
-    b->iterative = iterative;
-    b->nc = n_cams; b->np = n_pts; b->no = n_obs; b->n = 6 * n_cams; b->lda = chol_padded_dim(b->n);
-    if (hip_stream) b->st = reinterpret_cast<hipStream_t>(hip_stream);
-    else {
-        hipError_t e = hipStreamCreate(&b->st);
-        if (e != hipSuccess) { delete b; return fail(STBA_ERR_HIP, hipGetErrorString(e)); }
-        b->own_stream = true;
-    }
-    int rc = STBA_OK;
-    auto bail = [&](int code) { ba_free(b); return code; };
+// everything of ba_create behind the engine object and its stream: the plan, the buffers, their contents.  A failure leaves a partly
+// filled engine, which ba_create frees
+static int ba_fill(stba_ba* b, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts, const int* obs_cam,
+                   const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed, const unsigned char* pt_fixed) {
+    const bool iterative = b->iterative;
     static const bool TIMING = knob_int("STBA_CREATE_TIMING", 0) != 0;
     // (declared before the plan's vectors: destroyed after them, so its message includes what freeing them costs)
     struct TotalTimer { bool on; std::chrono::steady_clock::time_point t; ~TotalTimer() { if (on) fprintf(stderr, "stba_ba_create: %-28s %8.2f ms\n", "total, temporaries freed", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count()); } } total_timer{TIMING, std::chrono::steady_clock::now()};
@@ -1417,7 +1378,7 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
         tc0 = t1;
     };
     for (auto& e : b->ev) {
-        if (hipEventCreate(&e) != hipSuccess) return bail(fail(STBA_ERR_HIP, "hipEventCreate"));
+        if (hipEventCreate(&e) != hipSuccess) return fail(STBA_ERR_HIP, "hipEventCreate");
     }
     hipDeviceProp_t prop;
     int dev = 0;
@@ -1442,7 +1403,7 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     auto plan = std::make_shared<SchurPlan>();
     std::string why;
     if (build_schur_plan(n_cams, n_pts, n_obs, obs_cam, obs_pt, obs_feat, popt, plan.get(), &why) != 0)
-        return bail(fail(STBA_ERR_INVALID_ARGUMENT, why));
+        return fail(STBA_ERR_INVALID_ARGUMENT, why);
     const SchurPlan& P = *plan;
     b->n_chunks = (int)P.chunk_begin.size();
     b->dup_overflow = P.dup_overflow;
@@ -1467,76 +1428,74 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     b->lin_grid = std::max(1, std::min(n_tiles, num_cu * per_cu));
 
     tmark("masks");
-#define A_(call) do { rc = (call); if (rc != STBA_OK) return bail(rc); } while (0)
     const size_t no = (size_t)n_obs, np = (size_t)n_pts, nc = (size_t)n_cams;
-    for (int k = 0; k < 2; ++k) { A_(dev_alloc(&b->cams[k], nc * 7)); A_(dev_alloc(&b->pts[k], np * 3)); }
-    A_(dev_alloc(&b->feat, no)); A_(dev_alloc(&b->obs_cam, no)); A_(dev_alloc(&b->obs_pt, no));
-    A_(dev_alloc(&b->pt_start, np + 1)); A_(dev_alloc(&b->cam_perm, no));
-    A_(dev_alloc(&b->chunk_begin, (size_t)b->n_chunks)); A_(dev_alloc(&b->chunk_end, (size_t)b->n_chunks));
-    A_(dev_alloc(&b->cam_chunk_start, nc + 1));
-    A_(dev_alloc(&b->task_cam, P.task_cam.size())); A_(dev_alloc(&b->cam_start, nc + 1));
-    A_(dev_alloc(&b->task_col_lo, P.task_cam.size())); A_(dev_alloc(&b->task_col_hi, P.task_cam.size()));
-    A_(dev_alloc(&b->row_col_ptr, nc + 1)); A_(dev_alloc(&b->row_cols, P.row_cols.size()));
-    A_(dev_alloc(&b->pair_begin, P.pair_begin.size())); A_(dev_alloc(&b->pair_end, P.pair_end.size()));
-    A_(dev_alloc(&b->pair_rec, P.pairs));
-    A_(dev_alloc(&b->task_vs_ptr, P.task_vs_ptr.size())); A_(dev_alloc(&b->vs_first, P.vs_first.size()));
-    if (cam_fixed) A_(dev_alloc(&b->cam_fixed, nc));
-    if (pt_fixed) A_(dev_alloc(&b->pt_fixed, np));
+    for (int k = 0; k < 2; ++k) { STBA_TRY(b->cams[k].alloc(nc * 7)); STBA_TRY(b->pts[k].alloc(np * 3)); }
+    STBA_TRY(b->feat.alloc(no)); STBA_TRY(b->obs_cam.alloc(no)); STBA_TRY(b->obs_pt.alloc(no));
+    STBA_TRY(b->pt_start.alloc(np + 1)); STBA_TRY(b->cam_perm.alloc(no));
+    STBA_TRY(b->chunk_begin.alloc((size_t)b->n_chunks)); STBA_TRY(b->chunk_end.alloc((size_t)b->n_chunks));
+    STBA_TRY(b->cam_chunk_start.alloc(nc + 1));
+    STBA_TRY(b->task_cam.alloc(P.task_cam.size())); STBA_TRY(b->cam_start.alloc(nc + 1));
+    STBA_TRY(b->task_col_lo.alloc(P.task_cam.size())); STBA_TRY(b->task_col_hi.alloc(P.task_cam.size()));
+    STBA_TRY(b->row_col_ptr.alloc(nc + 1)); STBA_TRY(b->row_cols.alloc(P.row_cols.size()));
+    STBA_TRY(b->pair_begin.alloc(P.pair_begin.size())); STBA_TRY(b->pair_end.alloc(P.pair_end.size()));
+    STBA_TRY(b->pair_rec.alloc(P.pairs));
+    STBA_TRY(b->task_vs_ptr.alloc(P.task_vs_ptr.size())); STBA_TRY(b->vs_first.alloc(P.vs_first.size()));
+    if (cam_fixed) STBA_TRY(b->cam_fixed.alloc(nc));
+    if (pt_fixed) STBA_TRY(b->pt_fixed.alloc(np));
     if (b->lm_slices) {
-        A_(dev_alloc(&b->task_p_lo, P.task_p_lo.size())); A_(dev_alloc(&b->task_p_hi, P.task_p_hi.size())); A_(dev_alloc(&b->task_part_off, P.task_part_off.size()));
-        A_(dev_alloc(&b->row_task_ptr, P.row_task_ptr.size())); A_(dev_alloc(&b->row_tasks, P.row_tasks.size()));
-        A_(dev_alloc(&b->schur_part, P.part_doubles));
-        A_(upload(b->task_p_lo, P.task_p_lo.data(), P.task_p_lo.size(), b->st)); A_(upload(b->task_p_hi, P.task_p_hi.data(), P.task_p_hi.size(), b->st));
-        A_(upload(b->task_part_off, P.task_part_off.data(), P.task_part_off.size(), b->st));
-        A_(upload(b->row_task_ptr, P.row_task_ptr.data(), P.row_task_ptr.size(), b->st)); A_(upload(b->row_tasks, P.row_tasks.data(), P.row_tasks.size(), b->st));
+        STBA_TRY(b->task_p_lo.alloc(P.task_p_lo.size())); STBA_TRY(b->task_p_hi.alloc(P.task_p_hi.size())); STBA_TRY(b->task_part_off.alloc(P.task_part_off.size()));
+        STBA_TRY(b->row_task_ptr.alloc(P.row_task_ptr.size())); STBA_TRY(b->row_tasks.alloc(P.row_tasks.size()));
+        STBA_TRY(b->schur_part.alloc(P.part_doubles));
+        STBA_TRY(upload(b->task_p_lo, P.task_p_lo.data(), P.task_p_lo.size(), b->st)); STBA_TRY(upload(b->task_p_hi, P.task_p_hi.data(), P.task_p_hi.size(), b->st));
+        STBA_TRY(upload(b->task_part_off, P.task_part_off.data(), P.task_part_off.size(), b->st));
+        STBA_TRY(upload(b->row_task_ptr, P.row_task_ptr.data(), P.row_task_ptr.size(), b->st)); STBA_TRY(upload(b->row_tasks, P.row_tasks.data(), P.row_tasks.size(), b->st));
     }
-    if (!P.dup_run.empty()) { A_(dev_alloc(&b->dup_run, no)); A_(upload(b->dup_run, P.dup_run.data(), no, b->st)); }
-    A_(dev_alloc(&b->r, no)); A_(dev_alloc(&b->J8, no * 8));
-    if (cam_fixed || pt_fixed) A_(dev_alloc(&b->omask, no));
-    A_(dev_alloc(&b->Hpp6, np * 6)); A_(dev_alloc(&b->gp, np * 3)); A_(dev_alloc(&b->Hinv6, np * 6)); A_(dev_alloc(&b->Rinv9, np * 9));
-    A_(dev_alloc(&b->dp, np * 3)); A_(dev_alloc(&b->scale_p, np * 3));
-    A_(dev_alloc(&b->Hcc, nc * 36)); A_(dev_alloc(&b->gc, nc * 6)); A_(dev_alloc(&b->cam_partial, (size_t)b->n_chunks * 28));
-    A_(dev_alloc(&b->dc, nc * 6)); A_(dev_alloc(&b->scale_c, nc * 6));
-    A_(dev_alloc(&b->Sbuf, b->sbuf_count()));
-    A_(dev_alloc(&b->dxc, (size_t)b->lda)); A_(dev_alloc(&b->dxp, np * 3));
-    A_(dev_alloc(&b->cost_partial, (size_t)b->lin_grid + 1));     // (+ 1: the pose priors' slot, see n_cost)
-    A_(dev_alloc(&b->upd_partial_c, (size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
-    A_(dev_alloc(&b->upd_partial_p, (size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
-    A_(dev_alloc(&b->trial, (size_t)TS_BLOCK)); A_(dev_alloc(&b->flag, 1));
-    if (iterative) A_(ba_pcg_alloc(b));
+    if (!P.dup_run.empty()) { STBA_TRY(b->dup_run.alloc(no)); STBA_TRY(upload(b->dup_run, P.dup_run.data(), no, b->st)); }
+    STBA_TRY(b->r.alloc(no)); STBA_TRY(b->J8.alloc(no * 8));
+    if (cam_fixed || pt_fixed) STBA_TRY(b->omask.alloc(no));
+    STBA_TRY(b->Hpp6.alloc(np * 6)); STBA_TRY(b->gp.alloc(np * 3)); STBA_TRY(b->Hinv6.alloc(np * 6)); STBA_TRY(b->Rinv9.alloc(np * 9));
+    STBA_TRY(b->dp.alloc(np * 3)); STBA_TRY(b->scale_p.alloc(np * 3));
+    STBA_TRY(b->Hcc.alloc(nc * 36)); STBA_TRY(b->gc.alloc(nc * 6)); STBA_TRY(b->cam_partial.alloc((size_t)b->n_chunks * 28));
+    STBA_TRY(b->dc.alloc(nc * 6)); STBA_TRY(b->scale_c.alloc(nc * 6));
+    STBA_TRY(b->Sbuf.alloc(b->sbuf_count()));
+    STBA_TRY(b->dxc.alloc((size_t)b->lda)); STBA_TRY(b->dxp.alloc(np * 3));
+    STBA_TRY(b->cost_partial.alloc((size_t)b->lin_grid + 1));     // (+ 1: the pose priors' slot, see n_cost)
+    STBA_TRY(b->upd_partial_c.alloc((size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
+    STBA_TRY(b->upd_partial_p.alloc((size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
+    STBA_TRY(b->trial.alloc((size_t)TS_BLOCK)); STBA_TRY(b->flag.alloc(1));
+    if (iterative) STBA_TRY(ba_pcg_alloc(b));
 
     tmark("device allocations");
-    A_(upload(b->cams[0], cams, nc * 7, b->st)); A_(upload(b->pts[0], pts, np * 3, b->st));
-    A_(upload(reinterpret_cast<double*>(b->feat), P.s_feat.data(), no * 2, b->st));
-    A_(upload(b->obs_cam, P.s_cam.data(), no, b->st)); A_(upload(b->obs_pt, P.s_pt.data(), no, b->st));
-    A_(upload(b->pt_start, P.pt_start.data(), np + 1, b->st)); A_(upload(b->cam_perm, P.cam_perm.data(), no, b->st));
-    A_(upload(b->chunk_begin, P.chunk_begin.data(), (size_t)b->n_chunks, b->st));
-    A_(upload(b->chunk_end, P.chunk_end.data(), (size_t)b->n_chunks, b->st));
-    A_(upload(b->cam_chunk_start, P.cam_chunk_start.data(), nc + 1, b->st));
-    A_(upload(b->task_cam, P.task_cam.data(), P.task_cam.size(), b->st));
-    A_(upload(b->cam_start, P.cam_start.data(), nc + 1, b->st));
-    A_(upload(b->task_col_lo, P.task_col_lo.data(), P.task_cam.size(), b->st));
-    A_(upload(b->task_col_hi, P.task_col_hi.data(), P.task_cam.size(), b->st));
+    STBA_TRY(upload(b->cams[0], cams, nc * 7, b->st)); STBA_TRY(upload(b->pts[0], pts, np * 3, b->st));
+    STBA_TRY(upload(reinterpret_cast<double*>(b->feat.get()), P.s_feat.data(), no * 2, b->st));
+    STBA_TRY(upload(b->obs_cam, P.s_cam.data(), no, b->st)); STBA_TRY(upload(b->obs_pt, P.s_pt.data(), no, b->st));
+    STBA_TRY(upload(b->pt_start, P.pt_start.data(), np + 1, b->st)); STBA_TRY(upload(b->cam_perm, P.cam_perm.data(), no, b->st));
+    STBA_TRY(upload(b->chunk_begin, P.chunk_begin.data(), (size_t)b->n_chunks, b->st));
+    STBA_TRY(upload(b->chunk_end, P.chunk_end.data(), (size_t)b->n_chunks, b->st));
+    STBA_TRY(upload(b->cam_chunk_start, P.cam_chunk_start.data(), nc + 1, b->st));
+    STBA_TRY(upload(b->task_cam, P.task_cam.data(), P.task_cam.size(), b->st));
+    STBA_TRY(upload(b->cam_start, P.cam_start.data(), nc + 1, b->st));
+    STBA_TRY(upload(b->task_col_lo, P.task_col_lo.data(), P.task_cam.size(), b->st));
+    STBA_TRY(upload(b->task_col_hi, P.task_col_hi.data(), P.task_cam.size(), b->st));
     b->h_row_col_ptr = P.row_col_ptr; b->h_row_cols = P.row_cols;
-    A_(upload(b->row_col_ptr, P.row_col_ptr.data(), nc + 1, b->st));
-    if (!P.row_cols.empty()) A_(upload(b->row_cols, P.row_cols.data(), P.row_cols.size(), b->st));
-    A_(upload(b->pair_begin, P.pair_begin.data(), P.pair_begin.size(), b->st)); A_(upload(b->pair_end, P.pair_end.data(), P.pair_end.size(), b->st));
-    if (P.pairs > 0) A_(upload(b->pair_rec, reinterpret_cast<const int4*>(P.pair_rec.get()), P.pairs, b->st));
-    A_(upload(b->task_vs_ptr, P.task_vs_ptr.data(), P.task_vs_ptr.size(), b->st)); A_(upload(b->vs_first, P.vs_first.data(), P.vs_first.size(), b->st));
-    if (cam_fixed) A_(upload(b->cam_fixed, cmask.data(), nc, b->st));
+    STBA_TRY(upload(b->row_col_ptr, P.row_col_ptr.data(), nc + 1, b->st));
+    if (!P.row_cols.empty()) STBA_TRY(upload(b->row_cols, P.row_cols.data(), P.row_cols.size(), b->st));
+    STBA_TRY(upload(b->pair_begin, P.pair_begin.data(), P.pair_begin.size(), b->st)); STBA_TRY(upload(b->pair_end, P.pair_end.data(), P.pair_end.size(), b->st));
+    if (P.pairs > 0) STBA_TRY(upload(b->pair_rec, reinterpret_cast<const int4*>(P.pair_rec.get()), P.pairs, b->st));
+    STBA_TRY(upload(b->task_vs_ptr, P.task_vs_ptr.data(), P.task_vs_ptr.size(), b->st)); STBA_TRY(upload(b->vs_first, P.vs_first.data(), P.vs_first.size(), b->st));
+    if (cam_fixed) STBA_TRY(upload(b->cam_fixed, cmask.data(), nc, b->st));
     std::vector<unsigned char>& omask = b->create_omask;
     if (b->omask) {
         omask.resize(no);
         for (size_t p2 = 0; p2 < no; ++p2)
             omask[p2] = (unsigned char)((cam_fixed ? cmask[(size_t)P.s_cam[p2]] : 0u) | ((pt_fixed && pt_fixed[(size_t)P.s_pt[p2]]) ? 64u : 0u));
-        A_(upload(b->omask, omask.data(), no, b->st));
+        STBA_TRY(upload(b->omask, omask.data(), no, b->st));
     }
-    if (pt_fixed) A_(upload(b->pt_fixed, pt_fixed, np, b->st));
+    if (pt_fixed) STBA_TRY(upload(b->pt_fixed, pt_fixed, np, b->st));
     if (hipMemsetAsync(b->dxc, 0, (size_t)b->lda * sizeof(double), b->st) != hipSuccess ||
         hipMemsetAsync(b->Sbuf, 0, b->sbuf_count() * sizeof(double), b->st) != hipSuccess ||
         hipStreamSynchronize(b->st) != hipSuccess)
-        return bail(fail(STBA_ERR_HIP, "stba_ba_create: initial memset/sync failed"));
-#undef A_
+        return fail(STBA_ERR_HIP, "stba_ba_create: initial memset/sync failed");
     tmark("uploads + sync");
     // The plan's host-side temporaries -- 16 bytes per pair, the regrouped observations: ~110 MB at C5 -- cost 11 of the 43 ms of this
     // function just to FREE (measured: STBA_CREATE_TIMING in a debug build).  The engine keeps them and frees them when it is destroyed:
@@ -1545,6 +1504,33 @@ static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const doub
     // munmap of 110 MB holds the process's address-space lock while the calling thread faults pages in.)
     b->perm = std::move(plan->perm);
     b->create_leftovers = std::move(plan);
+    return STBA_OK;
+}
+
+// (iterative: ITERATIVE_SCHUR -- no Schur plan, no dense Y, no S: see stba_ba_create_ex)
+static int ba_create(stba_ba** out, int n_cams, int n_pts, int n_obs, const double* cams, const double* pts,
+                     const int* obs_cam, const int* obs_pt, const double* obs_feat, const unsigned char* cam_fixed,
+                     const unsigned char* pt_fixed, void* hip_stream, bool iterative) {
+    if (!out) return fail(STBA_ERR_INVALID_ARGUMENT, "out is null");
+    *out = nullptr;
+    if (n_cams <= 0 || n_pts < 0 || n_obs < 0 || !cams || (n_pts > 0 && !pts) ||
+        (n_obs > 0 && (!obs_cam || !obs_pt || !obs_feat)))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: null or empty input");
+    for (int i = 0; i < n_obs; ++i)
+        if (obs_cam[i] < 0 || obs_cam[i] >= n_cams || obs_pt[i] < 0 || obs_pt[i] >= n_pts)
+            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_create: observation index out of range");
+    STBA_TRY(require_device());
+    stba_ba* b = new stba_ba();
+    b->iterative = iterative;
+    b->nc = n_cams; b->np = n_pts; b->no = n_obs; b->n = 6 * n_cams; b->lda = chol_padded_dim(b->n);
+    if (hip_stream) b->st = reinterpret_cast<hipStream_t>(hip_stream);
+    else {
+        hipError_t e = hipStreamCreate(&b->st);
+        if (e != hipSuccess) { delete b; return fail(STBA_ERR_HIP, hipGetErrorString(e)); }
+        b->own_stream = true;
+    }
+    const int rc = ba_fill(b, n_cams, n_pts, n_obs, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed, pt_fixed);
+    if (rc != STBA_OK) { ba_free(b); return rc; }
     *out = b;
     return STBA_OK;
 }
@@ -1669,7 +1655,6 @@ int stba_ba_schur_mode(const stba_ba* ba, int* mode) {
 
 int stba_ba_destroy(stba_ba* ba) {
     if (!ba) return STBA_OK;
-    if (ba->st) (void)hipStreamSynchronize(ba->st);
     ba_free(ba);
     return STBA_OK;
 }
@@ -1691,7 +1676,7 @@ int stba_ba_set_features(stba_ba* b, const double* obs_feat) {
         const size_t i = (size_t)b->perm[(size_t)p];
         s_feat[2 * (size_t)p] = obs_feat[2 * i]; s_feat[2 * (size_t)p + 1] = obs_feat[2 * i + 1];
     }
-    STBA_TRY(upload(reinterpret_cast<double*>(b->feat), s_feat.data(), (size_t)b->no * 2, b->st));
+    STBA_TRY(upload(reinterpret_cast<double*>(b->feat.get()), s_feat.data(), (size_t)b->no * 2, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     return STBA_OK;
@@ -1723,7 +1708,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
     if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
     if (fn && b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has information matrices (the callback's factors whiten themselves; not supported together)");
     if (fn && b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has pose priors (priors need device residuals; not supported together)");
-    if (fn && !b->Jc12) STBA_TRY(dev_alloc(&b->Jc12, (size_t)b->no * 12));
+    if (fn && !b->Jc12) STBA_TRY(b->Jc12.alloc((size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     return STBA_OK;
@@ -1734,54 +1719,33 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
 int stba_ba_set_loss(stba_ba* b, const int* kind, const double* a, const double* lb, const double* scale) {
     const char* who = "stba_ba_set_loss";
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    int* k_new = nullptr;
-    double *a_new = nullptr, *b_new = nullptr, *s_new = nullptr, *jc_new = nullptr;
+    DevBuf<int> k_new;
+    DevBuf<double> a_new, b_new, s_new, jc_new;
     if (kind) {
         if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has a host lineariser (losses need device residuals; not supported together)");
         if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has inner iterations (inner iterations with losses are not supported)");
         if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and losses run on one rank only");
         const size_t m = (size_t)b->no;
-        std::vector<double> ha(m, 1.0), hb(m, 1.0), hs(m, 1.0);
-        for (size_t e = 0; e < m; ++e) {
-            const int kd = kind[e];
-            std::string why;
-            if (kd < STBA_LOSS_TRIVIAL || kd > STBA_LOSS_TUKEY) why = "unknown loss kind " + std::to_string(kd);
-            else if (kd != STBA_LOSS_TRIVIAL && (!a || !std::isfinite(a[e]) || !(a[e] > 0.0))) why = "the loss parameter a must be finite and positive";
-            else if (kd == STBA_LOSS_TOLERANT && (!lb || !std::isfinite(lb[e]) || !(lb[e] > 0.0))) why = "the loss parameter b must be finite and positive";
-            else if (scale && (!std::isfinite(scale[e]) || !(scale[e] >= 0.0))) why = "the loss scale must be finite and not negative";
-            if (!why.empty()) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": observation " + std::to_string(e) + ": " + why);
-            if (kd != STBA_LOSS_TRIVIAL) ha[e] = a[e];
-            if (kd == STBA_LOSS_TOLERANT) hb[e] = lb[e];
-            if (scale) hs[e] = scale[e];
-        }
+        std::vector<double> ha, hb, hs;
+        STBA_TRY(loss_table_check(who, "observation", m, kind, a, lb, scale, ha, hb, hs));
         std::vector<int> pk(m);
         std::vector<double> pa(m), pb(m), ps(m);
         for (size_t p = 0; p < m; ++p) {                    // the engine's order: b->perm = position -> the caller's index
             const size_t i = (size_t)b->perm[p];
             pk[p] = kind[i]; pa[p] = ha[i]; pb[p] = hb[i]; ps[p] = hs[i];
         }
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        const size_t ma = std::max<size_t>(m, 1);
-        int rc = dev_alloc(&k_new, ma);
-        if (rc == STBA_OK) rc = dev_alloc(&a_new, ma);
-        if (rc == STBA_OK) rc = dev_alloc(&b_new, ma);
-        if (rc == STBA_OK) rc = dev_alloc(&s_new, ma);
-        if (rc == STBA_OK && !b->Jc12) rc = dev_alloc(&jc_new, ma * 12);
-        if (rc == STBA_OK && m > 0 &&
-            (hipMemcpyAsync(k_new, pk.data(), m * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(a_new, pa.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(b_new, pb.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(s_new, ps.data(), m * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipStreamSynchronize(b->st) != hipSuccess))
-            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-        if (rc != STBA_OK) { F(k_new); F(a_new); F(b_new); F(s_new); F(jc_new); return rc; }
+        STBA_TRY(k_new.alloc(m)); STBA_TRY(a_new.alloc(m)); STBA_TRY(b_new.alloc(m)); STBA_TRY(s_new.alloc(m));
+        if (!b->Jc12) STBA_TRY(jc_new.alloc(std::max<size_t>(m, 1) * 12));
+        if (upload(k_new, pk.data(), m, b->st) != STBA_OK || upload(a_new, pa.data(), m, b->st) != STBA_OK ||
+            upload(b_new, pb.data(), m, b->st) != STBA_OK || upload(s_new, ps.data(), m, b->st) != STBA_OK ||
+            (m > 0 && hipStreamSynchronize(b->st) != hipSuccess))
+            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
     }
-    // (nothing of the engine may still be reading the old table or what was linearised with it)
+    // (nothing of the engine may still be reading the old table or what was linearised with it: the moves below free it)
     STBA_HIP(hipStreamSynchronize(b->st));
-    for (void* p : {(void*)b->loss_kind, (void*)b->loss_a, (void*)b->loss_b, (void*)b->loss_scale}) if (p) (void)hipFree(p);
-    b->loss_kind = k_new; b->loss_a = a_new; b->loss_b = b_new; b->loss_scale = s_new;
-    if (jc_new) b->Jc12 = jc_new;
-    if (!kind && !b->hl_fn && !b->winfo && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }      // (96 B per observation nobody reads any more)
+    b->loss_kind = std::move(k_new); b->loss_a = std::move(a_new); b->loss_b = std::move(b_new); b->loss_scale = std::move(s_new);
+    if (jc_new) b->Jc12 = std::move(jc_new);
+    if (!kind && !b->hl_fn && !b->winfo) b->Jc12.reset();      // (96 B per observation nobody reads any more)
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     cov_store_free(b->cov);
     b->cov = nullptr;
@@ -1813,7 +1777,7 @@ static bool ba_information_factor(const double* in, double* W) {
 // exactly the identity, goes back to the identity (no array held)
 static int ba_set_weights(stba_ba* b, const double* in, bool sqrt_form, const char* who) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    double *w_new = nullptr, *jc_new = nullptr;
+    DevBuf<double> w_new, jc_new;
     const size_t m = (size_t)b->no;
     std::vector<double> hw;
     if (in) {
@@ -1843,22 +1807,16 @@ static int ba_set_weights(stba_ba* b, const double* in, bool sqrt_form, const ch
         if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and information matrices run on one rank only");
         std::vector<double> pw(m * 4);
         for (size_t p = 0; p < m; ++p) memcpy(&pw[p * 4], &hw[(size_t)b->perm[p] * 4], 4 * sizeof(double));   // the engine's order
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        const size_t ma = std::max<size_t>(m, 1);
-        int rc = dev_alloc(&w_new, ma * 4);
-        if (rc == STBA_OK && !b->Jc12) rc = dev_alloc(&jc_new, ma * 12);
-        if (rc == STBA_OK && m > 0 &&
-            (hipMemcpyAsync(w_new, pw.data(), m * 4 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipStreamSynchronize(b->st) != hipSuccess))
-            rc = fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-        if (rc != STBA_OK) { F(w_new); F(jc_new); return rc; }
+        STBA_TRY(w_new.alloc(m * 4));
+        if (!b->Jc12) STBA_TRY(jc_new.alloc(std::max<size_t>(m, 1) * 12));
+        if (upload(w_new, pw.data(), m * 4, b->st) != STBA_OK || (m > 0 && hipStreamSynchronize(b->st) != hipSuccess))
+            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
     }
-    // (nothing of the engine may still be reading the old array or what was linearised with it)
+    // (nothing of the engine may still be reading the old array or what was linearised with it: the moves below free it)
     STBA_HIP(hipStreamSynchronize(b->st));
-    if (b->winfo) (void)hipFree(b->winfo);
-    b->winfo = w_new;
-    if (jc_new) b->Jc12 = jc_new;
-    if (!in && !b->hl_fn && !b->loss_kind && b->Jc12) { (void)hipFree(b->Jc12); b->Jc12 = nullptr; }
+    b->winfo = std::move(w_new);
+    if (jc_new) b->Jc12 = std::move(jc_new);
+    if (!in && !b->hl_fn && !b->loss_kind) b->Jc12.reset();
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
     cov_store_free(b->cov);
     b->cov = nullptr;
@@ -1896,8 +1854,8 @@ int stba_ba_set_pose_priors(stba_ba* b, int n, const int* cam, const double* pos
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
     if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
     if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
-    int *ptr_new = nullptr, *cam_new = nullptr;
-    double *pose_new = nullptr, *w_new = nullptr;
+    DevBuf<int> ptr_new, cam_new;
+    DevBuf<double> pose_new, w_new;
     std::vector<int> order;
     int n_groups = 0;
     if (n > 0) {
@@ -1948,24 +1906,15 @@ int stba_ba_set_pose_priors(stba_ba* b, int n, const int* cam, const double* pos
         }
         gptr.push_back(n);
         n_groups = (int)gcam.size();
-        auto F = [](void* p) { if (p) (void)hipFree(p); };
-        int rc = dev_alloc(&ptr_new, gptr.size());
-        if (rc == STBA_OK) rc = dev_alloc(&cam_new, gcam.size());
-        if (rc == STBA_OK) rc = dev_alloc(&pose_new, m * 7);
-        if (rc == STBA_OK) rc = dev_alloc(&w_new, m * 36);
-        if (rc == STBA_OK &&
-            (hipMemcpyAsync(ptr_new, gptr.data(), gptr.size() * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(cam_new, gcam.data(), gcam.size() * sizeof(int), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(pose_new, gp.data(), m * 7 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipMemcpyAsync(w_new, gw.data(), m * 36 * sizeof(double), hipMemcpyHostToDevice, b->st) != hipSuccess ||
-             hipStreamSynchronize(b->st) != hipSuccess))
-            rc = fail(STBA_ERR_HIP, who + ": upload failed");
-        if (rc != STBA_OK) { F(ptr_new); F(cam_new); F(pose_new); F(w_new); return rc; }
+        STBA_TRY(ptr_new.alloc(gptr.size())); STBA_TRY(cam_new.alloc(gcam.size())); STBA_TRY(pose_new.alloc(m * 7)); STBA_TRY(w_new.alloc(m * 36));
+        if (upload(ptr_new, gptr.data(), gptr.size(), b->st) != STBA_OK || upload(cam_new, gcam.data(), gcam.size(), b->st) != STBA_OK ||
+            upload(pose_new, gp.data(), m * 7, b->st) != STBA_OK || upload(w_new, gw.data(), m * 36, b->st) != STBA_OK ||
+            hipStreamSynchronize(b->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, who + ": upload failed");
     }
-    // (nothing of the engine may still be reading the old priors or what was linearised with them)
+    // (nothing of the engine may still be reading the old priors or what was linearised with them: the moves below free them)
     STBA_HIP(hipStreamSynchronize(b->st));
-    for (void* p : {(void*)b->prior_ptr, (void*)b->prior_cam, (void*)b->prior_pose, (void*)b->prior_W}) if (p) (void)hipFree(p);
-    b->prior_ptr = ptr_new; b->prior_cam = cam_new; b->prior_pose = pose_new; b->prior_W = w_new;
+    b->prior_ptr = std::move(ptr_new); b->prior_cam = std::move(cam_new); b->prior_pose = std::move(pose_new); b->prior_W = std::move(w_new);
     b->n_prior = n; b->n_prior_groups = n_groups;
     b->prior_order = std::move(order);
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
@@ -1993,20 +1942,19 @@ int stba_ba_evaluate_pose_priors(stba_ba* b, double* cost, double* r, double* J)
     if (cost) *cost = 0.0;
     if (!b->n_prior) return STBA_OK;
     const size_t m = (size_t)b->n_prior;
-    double *dr = nullptr, *dj = nullptr, *dcost = nullptr;
-    struct TmpGuard { double*& a; double*& c; double*& d; ~TmpGuard() { if (a) (void)hipFree(a); if (c) (void)hipFree(c); if (d) (void)hipFree(d); } } guard{dr, dj, dcost};
+    DevBuf<double> dr, dj, dcost;
     std::vector<double> hr, hj;
     double c2 = 0.0;
     if (r || J) {
-        STBA_TRY(dev_alloc(&dr, m * 6));
-        STBA_TRY(dev_alloc(&dj, m * 36));
+        STBA_TRY(dr.alloc(m * 6));
+        STBA_TRY(dj.alloc(m * 36));
         STBA_TRY(launch_prior_blocks(b->prior_args(), b->cams[b->cur], nullptr, nullptr, dr, dj, b->st));
         hr.resize(m * 6); hj.resize(m * 36);
         STBA_TRY(download(hr.data(), dr, m * 6, b->st));
         STBA_TRY(download(hj.data(), dj, m * 36, b->st));
     }
     if (cost) {
-        STBA_TRY(dev_alloc(&dcost, 1));
+        STBA_TRY(dcost.alloc(1));
         STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[b->cur], dcost, b->st));
         STBA_TRY(download(&c2, dcost, 1, b->st));
     }
@@ -2052,8 +2000,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
     b->ar = fn; b->ar_user = user; b->rank = rank; b->world = world_size;
     // what travels is decided again with the new group (the union pattern belongs to the group)
     b->pk_state = 0; b->pk_nz = 0;
-    if (b->pk_blocks) { (void)hipFree(b->pk_blocks); b->pk_blocks = nullptr; }
-    if (b->Spack) { (void)hipFree(b->Spack); b->Spack = nullptr; }
+    b->pk_blocks.reset();
+    b->Spack.reset();
     return STBA_OK;
 }
 
@@ -2071,13 +2019,12 @@ int stba_ba_evaluate(stba_ba* b, double* cost, double* r, double* Jc, double* Jp
     STBA_TRY(download(&c2, b->trial + TS_COST2, 1, b->st));
     const size_t no = (size_t)b->no;
     std::vector<double> tr, tjc, tjp;
-    if (r) { tr.resize(no * 2); STBA_TRY(download(tr.data(), reinterpret_cast<double*>(b->r), no * 2, b->st)); }
-    double *djc = nullptr, *djp = nullptr;     // the device holds the compact Jacobian; the 2x6 | 2x3 form is expanded for the caller
-    struct TmpGuard { double*& a; double*& c; ~TmpGuard() { if (a) (void)hipFree(a); if (c) (void)hipFree(c); } } tmp_guard{djc, djp};
+    if (r) { tr.resize(no * 2); STBA_TRY(download(tr.data(), reinterpret_cast<double*>(b->r.get()), no * 2, b->st)); }
+    DevBuf<double> djc, djp;     // the device holds the compact Jacobian; the 2x6 | 2x3 form is expanded for the caller
     if ((Jc || Jp) && b->hl_fn) return fail(STBA_ERR_STATE, "stba_ba_evaluate: with a host lineariser the Jacobians are the caller's own");
     if (Jc || Jp) {
-        if (Jc) STBA_TRY(dev_alloc(&djc, no * 12));
-        if (Jp) STBA_TRY(dev_alloc(&djp, no * 6));
+        if (Jc) STBA_TRY(djc.alloc(no * 12));
+        if (Jp) STBA_TRY(djp.alloc(no * 6));
         STBA_TRY(launch_expand_jacobian(b->no, b->J8, b->omask, djc, djp, b->st, ba_general_jc(b)));
         if (Jc) { tjc.resize(no * 12); STBA_TRY(download(tjc.data(), djc, no * 12, b->st)); }
         if (Jp) { tjp.resize(no * 6); STBA_TRY(download(tjp.data(), djp, no * 6, b->st)); }
@@ -2308,28 +2255,23 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     // device lists: the new ones are allocated and filled first and swapped in only when all of them are there, so that a failed
     // allocation leaves the engine's state (and an earlier ordering) as it was
     const size_t n_it = std::max<size_t>(cam_l.size() + pt_l.size(), 1);
-    int *n_cam = nullptr, *n_pt = nullptr, *n_itb = nullptr, *n_gate = nullptr;
-    unsigned char* n_mask = nullptr;
-    double *n_sc = nullptr, *n_part = nullptr;
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    auto drop = [&]() { F(n_cam); F(n_pt); F(n_itb); F(n_mask); F(n_gate); F(n_sc); F(n_part); };
-    int rc = STBA_OK;
-    if ((rc = dev_alloc(&n_cam, std::max<size_t>(cam_l.size(), 1))) != STBA_OK || (rc = dev_alloc(&n_mask, std::max<size_t>(mask_l.size(), 1))) != STBA_OK ||
-        (rc = dev_alloc(&n_pt, std::max<size_t>(pt_l.size(), 1))) != STBA_OK || (rc = dev_alloc(&n_itb, n_it)) != STBA_OK ||
-        (!b->inner_gate && (rc = dev_alloc(&n_gate, 1)) != STBA_OK) || (!b->inner_sc && (rc = dev_alloc(&n_sc, 4)) != STBA_OK) ||
-        (!b->inner_part && (rc = dev_alloc(&n_part, (size_t)inner_step_grid(nc, np))) != STBA_OK)) { drop(); return rc; }
-    if ((!cam_l.empty() && ((rc = upload(n_cam, cam_l.data(), cam_l.size(), b->st)) != STBA_OK ||
-                            (rc = upload(n_mask, mask_l.data(), mask_l.size(), b->st)) != STBA_OK)) ||
-        (!pt_l.empty() && (rc = upload(n_pt, pt_l.data(), pt_l.size(), b->st)) != STBA_OK) ||
-        hipMemsetAsync(n_itb, 0, n_it * sizeof(int), b->st) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) {
-        drop();
-        return rc != STBA_OK ? rc : fail(STBA_ERR_HIP, "stba_ba_set_inner_iterations: upload failed");
-    }
-    F(b->inner_cam); F(b->inner_pt); F(b->inner_it); F(b->inner_mask);
-    b->inner_cam = n_cam; b->inner_pt = n_pt; b->inner_it = n_itb; b->inner_mask = n_mask;
-    if (n_gate) b->inner_gate = n_gate;
-    if (n_sc) b->inner_sc = n_sc;
-    if (n_part) b->inner_part = n_part;
+    DevBuf<int> n_cam, n_pt, n_itb, n_gate;
+    DevBuf<unsigned char> n_mask;
+    DevBuf<double> n_sc, n_part;
+    STBA_TRY(n_cam.alloc(cam_l.size())); STBA_TRY(n_mask.alloc(mask_l.size())); STBA_TRY(n_pt.alloc(pt_l.size())); STBA_TRY(n_itb.alloc(n_it));
+    if (!b->inner_gate) STBA_TRY(n_gate.alloc(1));
+    if (!b->inner_sc) STBA_TRY(n_sc.alloc(4));
+    if (!b->inner_part) STBA_TRY(n_part.alloc((size_t)inner_step_grid(nc, np)));
+    STBA_TRY(upload(n_cam, cam_l.data(), cam_l.size(), b->st));
+    STBA_TRY(upload(n_mask, mask_l.data(), mask_l.size(), b->st));
+    STBA_TRY(upload(n_pt, pt_l.data(), pt_l.size(), b->st));
+    if (hipMemsetAsync(n_itb, 0, n_it * sizeof(int), b->st) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess)
+        return fail(STBA_ERR_HIP, "stba_ba_set_inner_iterations: upload failed");
+    // (the stream is idle: the moves free the earlier ordering)
+    b->inner_cam = std::move(n_cam); b->inner_pt = std::move(n_pt); b->inner_it = std::move(n_itb); b->inner_mask = std::move(n_mask);
+    if (n_gate) b->inner_gate = std::move(n_gate);
+    if (n_sc) b->inner_sc = std::move(n_sc);
+    if (n_part) b->inner_part = std::move(n_part);
     b->inner_groups = std::move(groups);
     b->inner_cam_h = std::move(cam_l); b->inner_pt_h = std::move(pt_l);
     b->inner_mask_h = std::move(mask_l); b->inner_kind_h = std::move(kind_l);
@@ -2489,15 +2431,11 @@ int stba_ba_covariance_release(stba_ba* b) {
 // ---------------------------------------------------------------------------------------------
 struct DenseWs {
     int n = 0, lda = 0;
-    double *A = nullptr, *x = nullptr, *rhs = nullptr;
-    int* flag = nullptr;
+    DevBuf<double> A, x, rhs;
+    DevBuf<int> flag;
     hipStream_t st = nullptr;
     bool own = false;
-    ~DenseWs() {
-        if (A) (void)hipFree(A);
-        if (x) (void)hipFree(x);
-        if (rhs) (void)hipFree(rhs);
-        if (flag) (void)hipFree(flag);
+    ~DenseWs() {          // (the stream is synchronised here; the buffers go behind it, with the members)
         if (st) { (void)hipStreamSynchronize(st); chol_forget_stream(st); }
         if (own && st) (void)hipStreamDestroy(st);
     }
@@ -2505,8 +2443,8 @@ struct DenseWs {
         n = n_; lda = chol_padded_dim(n);
         if (stream) st = reinterpret_cast<hipStream_t>(stream);
         else { STBA_HIP(hipStreamCreate(&st)); own = true; }
-        STBA_TRY(dev_alloc(&A, (size_t)lda * lda)); STBA_TRY(dev_alloc(&x, (size_t)lda));
-        STBA_TRY(dev_alloc(&rhs, (size_t)lda)); STBA_TRY(dev_alloc(&flag, 1));
+        STBA_TRY(A.alloc((size_t)lda * lda)); STBA_TRY(x.alloc((size_t)lda));
+        STBA_TRY(rhs.alloc((size_t)lda)); STBA_TRY(flag.alloc(1));
         return STBA_OK;
     }
     // host A (n x n, lower used) -> padded device matrix
@@ -2705,25 +2643,20 @@ namespace {
 struct CalibWs {
     int V = 0, C = 0, n = 0;
     size_t no = 0;
-    double *params = nullptr, *obj = nullptr, *img = nullptr, *e = nullptr, *Ji = nullptr, *Jx = nullptr,
-           *gram = nullptr, *scratch = nullptr, *trace = nullptr, *part = nullptr, *sse = nullptr;
-    int* state = nullptr;
+    DevBuf<double> params, obj, img, e, Ji, Jx, gram, scratch, trace, part, sse;
+    DevBuf<int> state;
     hipStream_t st = nullptr;
-    ~CalibWs() {
-        for (double* p : {params, obj, img, e, Ji, Jx, gram, scratch, trace, part, sse}) if (p) (void)hipFree(p);
-        if (state) (void)hipFree(state);
-    }
     // arrow: the Gauss-Newton buffers (per-view Gram blocks, step scratch, iteration state, cost trace) instead of the
     // per-corner outputs of stba_calib_evaluate
     int init(int n_views, int n_corners, const double* h_obj, const double* h_img, bool arrow, int max_iter) {
         V = n_views; C = n_corners; n = 9 + 6 * V; no = (size_t)V * C;
-        STBA_TRY(dev_alloc(&params, (size_t)n)); STBA_TRY(dev_alloc(&obj, no * 2)); STBA_TRY(dev_alloc(&img, no * 2));
+        STBA_TRY(params.alloc((size_t)n)); STBA_TRY(obj.alloc(no * 2)); STBA_TRY(img.alloc(no * 2));
         if (arrow) {
-            STBA_TRY(dev_alloc(&gram, (size_t)V * CALIB_GRAM_DOUBLES)); STBA_TRY(dev_alloc(&scratch, (size_t)V * CALIB_SCRATCH_DOUBLES));
-            STBA_TRY(dev_alloc(&trace, (size_t)max_iter)); STBA_TRY(dev_alloc(&state, (size_t)4));
+            STBA_TRY(gram.alloc((size_t)V * CALIB_GRAM_DOUBLES)); STBA_TRY(scratch.alloc((size_t)V * CALIB_SCRATCH_DOUBLES));
+            STBA_TRY(trace.alloc((size_t)max_iter)); STBA_TRY(state.alloc((size_t)4));
         } else {
-            STBA_TRY(dev_alloc(&e, no * 2)); STBA_TRY(dev_alloc(&Ji, no * 18)); STBA_TRY(dev_alloc(&Jx, no * 12));
-            STBA_TRY(dev_alloc(&part, (no + 255) / 256)); STBA_TRY(dev_alloc(&sse, (size_t)1));
+            STBA_TRY(e.alloc(no * 2)); STBA_TRY(Ji.alloc(no * 18)); STBA_TRY(Jx.alloc(no * 12));
+            STBA_TRY(part.alloc((no + 255) / 256)); STBA_TRY(sse.alloc((size_t)1));
         }
         STBA_TRY(upload(obj, h_obj, no * 2, st)); STBA_TRY(upload(img, h_img, no * 2, st));
         return STBA_OK;
@@ -2838,16 +2771,15 @@ struct GeneralDenseSteps {
     const stba_lm_options& opt;
     const int n_res, n;
     DenseWs w;
-    double *dJ = nullptr, *dr = nullptr, *dH = nullptr, *dg = nullptr;
+    DevBuf<double> dJ, dr, dH, dg;
     std::vector<double> rv, Jv, H, Hd, gv, dxv, scale, dvec;
     double *r = nullptr, *J = nullptr, *g = nullptr, *dx = nullptr;
     bool first = true;
     GeneralDenseSteps(const stba_lm_options& o, int n_res_, int n_) : opt(o), n_res(n_res_), n(n_) {}
-    ~GeneralDenseSteps() { (void)hipFree(dJ); (void)hipFree(dr); (void)hipFree(dH); (void)hipFree(dg); }
     int init() {
         STBA_TRY(w.init(n, nullptr));
-        STBA_TRY(dev_alloc(&dJ, (size_t)n_res * n)); STBA_TRY(dev_alloc(&dr, (size_t)n_res));
-        STBA_TRY(dev_alloc(&dH, (size_t)n * n)); STBA_TRY(dev_alloc(&dg, (size_t)n));
+        STBA_TRY(dJ.alloc((size_t)n_res * n)); STBA_TRY(dr.alloc((size_t)n_res));
+        STBA_TRY(dH.alloc((size_t)n * n)); STBA_TRY(dg.alloc((size_t)n));
         rv.resize(n_res); Jv.resize((size_t)n_res * n); H.resize((size_t)n * n); Hd.resize((size_t)n * n);
         gv.resize(n); dxv.resize(n); scale.resize(n); dvec.resize(n);
         r = rv.data(); J = Jv.data(); g = gv.data(); dx = dxv.data();
@@ -3029,9 +2961,8 @@ int stba_dense_covariance(stba_residual_fn fn, void* user, int n_params, int n_l
     for (int i = 0; i < n_res; ++i)
         if (!std::isfinite(S.r[i])) return fail(STBA_ERR_CALLBACK, "stba_dense_covariance: non-finite residual");
     STBA_TRY(S.linearize(0.0));
-    double* sig = nullptr;
-    STBA_TRY(dev_alloc(&sig, (size_t)n * (n + 1) / 2));
-    struct Guard { double*& p; ~Guard() { if (p) (void)hipFree(p); } } guard{sig};
+    DevBuf<double> sig;
+    STBA_TRY(sig.alloc((size_t)n * (n + 1) / 2));
     double rc = 0.0;
     int piv = 0;
     STBA_TRY(cov_spd_inverse_packed(S.dH, n, n, nullptr, sig, &rc, &piv, S.w.st));

@@ -173,23 +173,18 @@ extern "C" int stba_two_view_init(int n, const double* f1, const double* f2, con
     if (n < 8 || !f1 || !f2 || !K || !R_out || !t_out) return fail(STBA_ERR_INVALID_ARGUMENT, "two_view_init: bad argument");
     STBA_TRY(require_device());
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    double *d1 = nullptr, *d2 = nullptr, *dR = nullptr, *dP = nullptr;
-    int* dF = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d1); (void)hipFree(d2); (void)hipFree(dR); (void)hipFree(dP); (void)hipFree(dF); };
+    DevBuf<double> d1, d2, dR, dP;
+    DevBuf<int> dF;
     const int qr_blocks = std::max(1, std::min(64, (n + QR_THREADS * 4 - 1) / (QR_THREADS * 4)));
-#define TV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return fail(STBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-    TV_HIP(hipMalloc(reinterpret_cast<void**>(&d1), (size_t)n * 2 * sizeof(double)));
-    TV_HIP(hipMalloc(reinterpret_cast<void**>(&d2), (size_t)n * 2 * sizeof(double)));
-    TV_HIP(hipMalloc(reinterpret_cast<void**>(&dR), (size_t)qr_blocks * 45 * sizeof(double)));
-    TV_HIP(hipMalloc(reinterpret_cast<void**>(&dP), (size_t)n * 3 * sizeof(double)));
-    TV_HIP(hipMalloc(reinterpret_cast<void**>(&dF), 4 * sizeof(int)));
-    TV_HIP(hipMemcpyAsync(d1, f1, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
-    TV_HIP(hipMemcpyAsync(d2, f2, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    STBA_TRY(d1.alloc((size_t)n * 2)); STBA_TRY(d2.alloc((size_t)n * 2)); STBA_TRY(dR.alloc((size_t)qr_blocks * 45));
+    STBA_TRY(dP.alloc((size_t)n * 3)); STBA_TRY(dF.alloc(4));
+    STBA_HIP(hipMemcpyAsync(d1, f1, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    STBA_HIP(hipMemcpyAsync(d2, f2, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
     // 1. fundamental matrix: triangular factor on the device, 9x9 SVD on the host
     hipLaunchKernelGGL(tv_qr_kernel, dim3(qr_blocks), dim3(QR_THREADS), 0, st, n, d1, d2, dR);
     std::vector<double> hR((size_t)qr_blocks * 45);
-    TV_HIP(hipMemcpyAsync(hR.data(), dR, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    TV_HIP(hipStreamSynchronize(st));
+    STBA_HIP(hipMemcpyAsync(hR.data(), dR, hR.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    STBA_HIP(hipStreamSynchronize(st));
     double Rm[45];
     for (int k = 0; k < 45; ++k) Rm[k] = hR[(size_t)k];
     for (int b = 1; b < qr_blocks; ++b) {
@@ -232,16 +227,16 @@ extern "C" int stba_two_view_init(int n, const double* f1, const double* f2, con
         for (int j = 0; j < 3; ++j) h.t[k][j] = ts[k][j];
     }
     // 3. cheirality: every point in front of both cameras, for exactly one hypothesis
-    TV_HIP(hipMemsetAsync(dF, 0, 4 * sizeof(int), st));
+    STBA_HIP(hipMemsetAsync(dF, 0, 4 * sizeof(int), st));
     hipLaunchKernelGGL(tv_cheirality_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d1, d2, h, dF);
     int fails[4];
-    TV_HIP(hipMemcpyAsync(fails, dF, sizeof fails, hipMemcpyDeviceToHost, st));
-    TV_HIP(hipStreamSynchronize(st));
+    STBA_HIP(hipMemcpyAsync(fails, dF, sizeof fails, hipMemcpyDeviceToHost, st));
+    STBA_HIP(hipStreamSynchronize(st));
     if (fails_out) std::memcpy(fails_out, fails, sizeof fails);
     int winner = -1, n_ok = 0;
     for (int k = 0; k < 4; ++k)
         if (fails[k] == 0) { winner = k; ++n_ok; }
-    if (n_ok != 1) { cleanup(); return fail(STBA_ERR_NO_SOLUTION, "two_view_init: no unique pose hypothesis passes the cheirality test"); }
+    if (n_ok != 1) return fail(STBA_ERR_NO_SOLUTION, "two_view_init: no unique pose hypothesis passes the cheirality test");
     // AdjustRotationMatrix (two_view_simu.h:19-26): nearest rotation U V^T
     double Ua[9], Sa[3], Va[9], Vat[9];
     svd3(Rs[winner], Ua, Sa, Va);
@@ -251,11 +246,9 @@ extern "C" int stba_two_view_init(int n, const double* f1, const double* f2, con
     // 4. landmarks in frame 1
     if (pts_out) {
         hipLaunchKernelGGL(tv_triangulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d1, d2, h, winner, dP);
-        TV_HIP(hipMemcpyAsync(pts_out, dP, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        TV_HIP(hipStreamSynchronize(st));
+        STBA_HIP(hipMemcpyAsync(pts_out, dP, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        STBA_HIP(hipStreamSynchronize(st));
     }
-    TV_HIP(hipGetLastError());
-#undef TV_HIP
-    cleanup();
+    STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
