@@ -799,6 +799,44 @@ int stba_ba_pose_prior_count(const stba_ba* ba, int* n);
 int stba_ba_evaluate_pose_priors(stba_ba* ba, double* cost, double* r /*[n*6]*/, double* J /*[n*36], 6x6 row-major*/);
 int stba_ba_pose_prior_kernel_geometry(const stba_ba* ba, int* cameras_per_workgroup);
 
+/* ================================ bundle adjustment: camera-to-camera relative-pose factors ================================ */
+/* An edge k names two distinct cameras i_k, j_k, a measured relative pose (qz_k, tz_k) -- "camera j seen from camera i",
+ * [qx, qy, qz, qw, tx, ty, tz]: wheel odometry, a pre-integrated IMU, ICP, a loop closure -- and a 6 x 6 square-root information W_k
+ * (row-major).  Conventions of the engine and of the pose priors, NOT the pose graph's: poses camera to world, chart
+ * q <- q (x) exp(dtheta), t <- t + dt, order [rot(3), pos(3)]:
+ *     r_k = [ Log(qz^-1 (x) (q_i^-1 (x) q_j)) ; R_i^T (t_j - t_i) - tz ]
+ *     d r_theta / d dtheta_j = Jr^-1(r_theta)        d r_theta / d dtheta_i = -Jr^-1(r_theta) R_j^T R_i
+ *     d r_p / d dt_j = R_i^T      d r_p / d dt_i = -R_i^T      d r_p / d dtheta_i = hat(R_i^T (t_j - t_i))
+ *     cost += 1/2 |W_k r_k|^2
+ * Log and Jr^-1 are the priors': the short way round, the same bits when any one of qz, q_i, q_j is negated.  Columns of a camera's
+ * constant dofs (cam_fixed) are exactly 0.  Any number of edges, several on one pair, in either direction; the two cameras need
+ * not share a landmark.
+ *   stba_ba_set_relative_poses   cam_i[n], cam_j[n], meas[n*7], and at most ONE of information[n*36] (symmetric positive definite,
+ *                      factored on the host as stba_ba_set_pose_priors does; else STBA_ERR_NOT_POSITIVE_DEFINITE) and
+ *                      sqrt_information[n*36] (any finite W, rank-deficient included).  Both NULL: the identity.  Quaternions are
+ *                      normalised on the host (one that is unit to 8 eps keeps its bits).  n = 0 clears the edges: the engine then
+ *                      enqueues exactly what one that never had any enqueues.  STBA_ERR_INVALID_ARGUMENT, stba_last_error() naming
+ *                      the smallest such edge, nothing changed: a camera index out of range, cam_i == cam_j, an entry that is not
+ *                      finite, a zero quaternion; also both weight arrays given.
+ *   stba_ba_relative_pose_count  *n = the number of edges held.
+ *   stba_ba_evaluate_relative_poses   at the current parameters: cost = 1/2 sum |W r|^2 of the edges alone, r[n*6] = W_k r_k,
+ *                      Ji[n*36] = W_k d r_k / d[dtheta_i, dt_i], Jj[n*36] likewise (6 x 6 row-major), the caller's order; any may be NULL.
+ *   stba_ba_relative_pose_kernel_geometry   DIAGNOSTIC, NOT A STABLE INTERFACE (the tests derive their scenes from it): groups
+ *                      (cameras with edges, then pairs with edges) per workgroup of the block kernel.
+ * With edges, stba_ba_evaluate's and stba_ba_cost's cost, the LM summary and trace and the gradient norm are those of the SUM;
+ * stba_ba_normal_blocks' Hcc, gc include the edges' J_x'^T J_x', J_x'^T r' (the off-diagonal part lives in the reduced system only:
+ * stba_ba_reduced_system's S carries sum J_hi'^T J_lo' in its block (hi, lo), hi > lo); stba_ba_solve / _lm_iterations (LM; PAIRS and
+ * DENSE), the stage entry points, stba_ba_covariance_compute and its getters run on the sum; pose priors, losses and information
+ * matrices on the observations combine freely.  A setter that succeeds invalidates the current linearisation and releases a held
+ * covariance.  LIMITS, refused with STBA_ERR_INVALID_ARGUMENT, the state untouched, in both orders of the two calls: ITERATIVE_SCHUR
+ * engines, DOGLEG, inner iterations, a host lineariser, an all-reduce hook / communicator / world_size > 1 (the packing of the
+ * cross-rank sum knows the landmarks' sparsity only).  STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_relative_poses(stba_ba* ba, int n, const int* cam_i, const int* cam_j, const double* meas /*[n*7]*/,
+                               const double* information /*[n*36] or NULL*/, const double* sqrt_information /*[n*36] or NULL*/);
+int stba_ba_relative_pose_count(const stba_ba* ba, int* n);
+int stba_ba_evaluate_relative_poses(stba_ba* ba, double* cost, double* r /*[n*6]*/, double* Ji /*[n*36]*/, double* Jj /*[n*36]*/);
+int stba_ba_relative_pose_kernel_geometry(const stba_ba* ba, int* groups_per_workgroup);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

@@ -88,6 +88,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry",
            "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information",
            "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry",
+           "stba_ba_set_relative_poses", "stba_ba_relative_pose_count", "stba_ba_evaluate_relative_poses",
+           "stba_ba_relative_pose_kernel_geometry",
            "stba_live_device_buffers"]
 
 
@@ -241,10 +243,11 @@ class BAEngine:
     implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
 
     def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur",
-                 loss=None, information=None, sqrt_information=None, pose_priors=None):
+                 loss=None, information=None, sqrt_information=None, pose_priors=None, relative_poses=None):
         """loss: per-observation robust losses as PGEngine takes them -- a kind name, a tuple (kind, a[, b[, scale]]) or a dict of
         set_loss's arguments.  information / sqrt_information (one of the two): per-observation 2 x 2 weights, the shapes that
-        set_information takes.  pose_priors: dict(cams=, poses=, information= | sqrt_information=), set_pose_priors' arguments"""
+        set_information takes.  pose_priors: dict(cams=, poses=, information= | sqrt_information=), set_pose_priors' arguments.
+        relative_poses: dict(cam_i=, cam_j=, measurements=, information= | sqrt_information=), set_relative_poses' arguments"""
         if information is not None and sqrt_information is not None:
             raise ValueError("BAEngine: give information or sqrt_information, not both")
         self._h = C.c_void_p()
@@ -279,6 +282,8 @@ class BAEngine:
             self._set_loss_table(table)
         if pose_priors is not None:
             self.set_pose_priors(**pose_priors)
+        if relative_poses is not None:
+            self.set_relative_poses(**relative_poses)
 
     def close(self):
         if self._h:
@@ -432,6 +437,58 @@ class BAEngine:
         """cameras with priors per workgroup of the block kernel (a diagnostic: stba_ba_pose_prior_kernel_geometry)"""
         k = C.c_int()
         _chk(lib().stba_ba_pose_prior_kernel_geometry(self._h, C.byref(k)), "stba_ba_pose_prior_kernel_geometry")
+        return k.value
+
+    # ---- camera-to-camera relative-pose factors
+    def set_relative_poses(self, cam_i, cam_j, measurements, information=None, sqrt_information=None):
+        """odometry / loop-closure edges between cameras (stba_ba_set_relative_poses): edge k says that camera cam_j[k], seen from camera
+        cam_i[k], sits at measurements[k] = [qx, qy, qz, qw, tx, ty, tz], with cost 1/2 |W_k r_k|^2, r_k = [Log(qz^-1 q_i^-1 q_j);
+        R_i^T (t_j - t_i) - tz] in the order [rot(3), pos(3)].  information / sqrt_information: the shapes set_pose_priors takes.
+        Several edges may name one pair, in either direction.  cam_i empty (or None) clears the edges."""
+        if information is not None and sqrt_information is not None:
+            raise ValueError("BAEngine: give information or sqrt_information, not both")
+        ci = np.ascontiguousarray([] if cam_i is None else cam_i, dtype=np.int32).reshape(-1)
+        n = len(ci)
+        if n == 0:
+            _chk(lib().stba_ba_set_relative_poses(self._h, 0, None, None, None, None, None), "stba_ba_set_relative_poses")
+            return
+        cj = np.ascontiguousarray(cam_j, dtype=np.int32).reshape(-1)
+        ms = _f64(measurements).reshape(-1, 7)
+        if len(cj) != n or len(ms) != n:
+            raise ValueError(f"BAEngine: {n} cam_i but {len(cj)} cam_j and {len(ms)} measurements")
+
+        def blocks(w, name):
+            if w is None:
+                return None
+            w = np.asarray(w, np.float64)
+            if w.shape == (6, 6):
+                w = np.broadcast_to(w, (n, 6, 6))
+            if w.shape != (n, 6, 6):
+                raise ValueError(f"BAEngine: relative-pose {name} must have shape (6, 6) or ({n}, 6, 6), got {w.shape}")
+            return np.ascontiguousarray(w)
+        om, w = blocks(information, "information"), blocks(sqrt_information, "sqrt_information")
+        _chk(lib().stba_ba_set_relative_poses(self._h, n, _p(ci), _p(cj), _p(ms), _p(om), _p(w)), "stba_ba_set_relative_poses")
+
+    def relative_pose_count(self):
+        n = C.c_int()
+        _chk(lib().stba_ba_relative_pose_count(self._h, C.byref(n)), "stba_ba_relative_pose_count")
+        return n.value
+
+    def evaluate_relative_poses(self, jac=True):
+        """(cost, r [n, 6], Ji [n, 6, 6] | None, Jj [n, 6, 6] | None) of the edges alone at the current parameters: whitened, in the
+        order they were set"""
+        n = self.relative_pose_count()
+        cost = C.c_double()
+        r = np.zeros((n, 6))
+        Ji = np.zeros((n, 6, 6)) if jac else None
+        Jj = np.zeros((n, 6, 6)) if jac else None
+        _chk(lib().stba_ba_evaluate_relative_poses(self._h, C.byref(cost), _p(r), _p(Ji), _p(Jj)), "stba_ba_evaluate_relative_poses")
+        return cost.value, r, Ji, Jj
+
+    def relative_pose_kernel_geometry(self):
+        """groups (cameras with edges, then pairs with edges) per workgroup of the block kernel (a diagnostic)"""
+        k = C.c_int()
+        _chk(lib().stba_ba_relative_pose_kernel_geometry(self._h, C.byref(k)), "stba_ba_relative_pose_kernel_geometry")
         return k.value
 
     def loss_kernel_geometry(self):

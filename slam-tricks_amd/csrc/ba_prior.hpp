@@ -1,7 +1,17 @@
 // ba_prior.hpp -- camera pose priors of the bundle adjustment: the factor's maths (host and device) and the launch
 // wrappers of its two kernels (definitions in ba_prior.hip)
 #pragma once
+#if defined(__HIPCC__)
 #include "common.hpp"
+#else
+// a plain host compiler (tests/cpp/ba_between_driver.cpp): the factor's maths only, nothing of HIP
+#include <cmath>
+#define STBA_MATHS_ONLY
+#ifndef __host__
+#define __host__
+#define __device__
+#endif
+#endif
 
 namespace stba {
 
@@ -122,6 +132,7 @@ inline bool prior_information_factor(const double* A, double* W) {
     return true;
 }
 
+#ifndef STBA_MATHS_ONLY
 // the priors on the device, grouped by camera (CSR over the cameras that have any; inside a group the caller's order)
 struct PriorArgs {
     int n_groups = 0;
@@ -139,5 +150,6 @@ int launch_prior_cost(const PriorArgs& a, const double* cams, double* slot, hipS
 // block form: Hcc[c] += sum J'^T J', gc[c] += sum J'^T r' at the cameras `cams` (Hcc, gc both given or both null); out_r [n][6] and
 // out_J [n][36], in the grouped order, receive r' and J' when given
 int launch_prior_blocks(const PriorArgs& a, const double* cams, double* Hcc, double* gc, double* out_r, double* out_J, hipStream_t st);
+#endif
 
 }  // namespace stba

@@ -13,6 +13,7 @@
 
 #include "ba_kernels.hpp"
 #include "ba_prior.hpp"
+#include "ba_between.hpp"
 #include "iterative_schur.hpp"
 #include "dogleg.hpp"
 #include "inner_iterations.hpp"
@@ -178,8 +179,19 @@ struct stba_ba {
     DevBuf<double> prior_pose, prior_W;
     std::vector<int> prior_order;
     int lin_which = 0;
-    int n_cost() const { return lin_grid + (n_prior ? 1 : 0); }
+    // camera-to-camera relative-pose factors (stba_ba_set_relative_poses; ba_between.hip): the edges in the caller's
+    // order and two CSRs of references into them, by camera and by unordered pair.  With edges the cost partials carry one more slot,
+    // behind the priors' where there are priors; the block form adds to Hcc, gc AND to the blocks (hi, lo) of S behind the Schur step
+    int n_btw = 0, n_btw_cg = 0, n_btw_pg = 0;
+    DevBuf<int> btw_i, btw_j, btw_cg_ptr, btw_cg_cam, btw_cg_ref, btw_pg_ptr, btw_pg_ref;
+    DevBuf<int2> btw_pg_pair;
+    DevBuf<double> btw_meas, btw_W;
+    int n_cost() const { return lin_grid + (n_prior ? 1 : 0) + (n_btw ? 1 : 0); }
     PriorArgs prior_args() const { return PriorArgs{n_prior_groups, prior_ptr, prior_cam, prior_pose, prior_W, cam_fixed}; }
+    BetweenArgs between_args() const {
+        return BetweenArgs{n_btw, n_btw_cg, n_btw_pg, btw_i, btw_j, btw_meas, btw_W, btw_cg_ptr, btw_cg_cam, btw_cg_ref,
+                           btw_pg_ptr, btw_pg_pair, btw_pg_ref, cam_fixed};
+    }
 
     size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
     double* S() const { return iterative ? nullptr : Sbuf; }
@@ -291,6 +303,8 @@ static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
         STBA_TRY(launch_linearize(a, with_jac, b->lin_grid, b->st));
     // pose priors: their cost at the same parameters into the slot behind the lineariser's partials (one launch; n_cost counts it)
     if (b->n_prior) STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[which], b->cost_partial + b->lin_grid, b->st));
+    // relative-pose factors: theirs into the next slot
+    if (b->n_btw) STBA_TRY(launch_between_cost(b->between_args(), b->cams[which], b->cost_partial + b->lin_grid + (b->n_prior ? 1 : 0), b->st));
     return STBA_OK;
 }
 
@@ -299,6 +313,15 @@ static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
 static int ba_prior_blocks(stba_ba* b) {
     if (!b->n_prior) return STBA_OK;
     return launch_prior_blocks(b->prior_args(), b->cams[b->lin_which], b->Hcc, b->gc, nullptr, nullptr, b->st);
+}
+
+// relative-pose factors: sum J_x'^T J_x' into Hcc, sum J_x'^T r' into gc and -- with_S -- sum J_hi'^T J_lo' onto the block (hi, lo) of S,
+// which the Schur step has just zeroed and written (every build: nothing accumulates from one build to the next).  One launch; none
+// without edges
+static int ba_between_blocks(stba_ba* b, bool with_S) {
+    if (!b->n_btw) return STBA_OK;
+    return launch_between_blocks(b->between_args(), b->cams[b->lin_which], b->Hcc, b->gc, with_S ? b->S() : nullptr, b->lda, nullptr, nullptr,
+                                 nullptr, b->st);
 }
 
 // residuals + Jacobians at parameter buffer `which`; sum r^2 -> *cost2_dev
@@ -481,6 +504,7 @@ static int ba_build_reduced(stba_ba* b, const Damping& dm) {
     // S is zeroed (pair plan) or overwritten (dense product) by the Schur step itself
     STBA_TRY(ba_schur_step(b));
     STBA_TRY(ba_prior_blocks(b));
+    STBA_TRY(ba_between_blocks(b, true));
     if (!b->ar && !dm.explicit_d && b->n == 6 * b->nc) {
         // one rank: camera blocks, LM diagonal, damping and padding in one launch
         STBA_TRY(launch_reduced_finalize(b->nc, b->n, b->Hcc, b->gc, b->cam_fixed, b->S(), b->lda, b->rhs(), b->ex_diag(), b->ex_gc(),
@@ -1459,7 +1483,7 @@ static int ba_fill(stba_ba* b, int n_cams, int n_pts, int n_obs, const double* c
     STBA_TRY(b->dc.alloc(nc * 6)); STBA_TRY(b->scale_c.alloc(nc * 6));
     STBA_TRY(b->Sbuf.alloc(b->sbuf_count()));
     STBA_TRY(b->dxc.alloc((size_t)b->lda)); STBA_TRY(b->dxp.alloc(np * 3));
-    STBA_TRY(b->cost_partial.alloc((size_t)b->lin_grid + 1));     // (+ 1: the pose priors' slot, see n_cost)
+    STBA_TRY(b->cost_partial.alloc((size_t)b->lin_grid + 2));     // (+ 2: the pose priors' slot and the relative-pose factors', see n_cost)
     STBA_TRY(b->upd_partial_c.alloc((size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
     STBA_TRY(b->upd_partial_p.alloc((size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
     STBA_TRY(b->trial.alloc((size_t)TS_BLOCK)); STBA_TRY(b->flag.alloc(1));
@@ -1708,6 +1732,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
     if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
     if (fn && b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has information matrices (the callback's factors whiten themselves; not supported together)");
     if (fn && b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has pose priors (priors need device residuals; not supported together)");
+    if (fn && b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has relative-pose factors (the factors need device residuals; not supported together)");
     if (fn && !b->Jc12) STBA_TRY(b->Jc12.alloc((size_t)b->no * 12));
     b->hl_fn = fn; b->hl_user = user;
     b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
@@ -1968,6 +1993,141 @@ int stba_ba_evaluate_pose_priors(stba_ba* b, double* cost, double* r, double* J)
     return STBA_OK;
 }
 
+// ---- camera-to-camera relative-pose factors.  As with the priors everything is checked -- and, for the information
+// form, factored -- on the host BEFORE anything is replaced.  The edges stay in the caller's order; two stable sorts make the
+// references by camera and by unordered pair (inside a group the caller's order).  n == 0 releases everything: the engine then
+// enqueues exactly what one that never had edges enqueues
+int stba_ba_set_relative_poses(stba_ba* b, int n, const int* cam_i, const int* cam_j, const double* meas, const double* information,
+                               const double* sqrt_information) {
+    const std::string who = "stba_ba_set_relative_poses";
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
+    if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
+    if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
+    DevBuf<int> i_new, j_new, cgp_new, cgc_new, cgr_new, pgp_new, pgr_new;
+    DevBuf<int2> pgq_new;
+    DevBuf<double> meas_new, w_new;
+    int n_cg = 0, n_pg = 0;
+    if (n > 0) {
+        if (!cam_i || !cam_j || !meas) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null cam_i, cam_j or meas array");
+        if (b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses ITERATIVE_SCHUR (its inexact-step model is summed from the observation records; relative-pose factors are not supported)");
+        if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses DOGLEG (DOGLEG with relative-pose factors is not supported)");
+        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has inner iterations (inner iterations with relative-pose factors are not supported)");
+        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has a host lineariser (the factors need device residuals; not supported together)");
+        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has an all-reduce hook, and relative-pose factors run on one rank only");
+        const size_t m = (size_t)n;
+        std::vector<double> hm(m * 7), hw(m * 36);
+        for (size_t k = 0; k < m; ++k) {
+            const std::string at = who + ": edge " + std::to_string(k) + ": ";
+            for (int c : {cam_i[k], cam_j[k]})
+                if (c < 0 || c >= b->nc) return fail(STBA_ERR_INVALID_ARGUMENT, at + "camera index " + std::to_string(c) + " out of range");
+            if (cam_i[k] == cam_j[k]) return fail(STBA_ERR_INVALID_ARGUMENT, at + "cam_i == cam_j (" + std::to_string(cam_i[k]) + ")");
+            for (int j = 0; j < 7; ++j)
+                if (!std::isfinite(meas[k * 7 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the measurement has an entry that is not finite");
+            const double* q = meas + k * 7;
+            const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+            if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(STBA_ERR_INVALID_ARGUMENT, at + "zero quaternion");
+            // (as the priors: a quaternion that is unit to rounding keeps its bits)
+            const double sc = std::fabs(n2 - 1.0) <= 8 * 2.220446049250313e-16 ? 1.0 : 1.0 / std::sqrt(n2);
+            for (int j = 0; j < 4; ++j) hm[k * 7 + j] = q[j] * sc;
+            for (int j = 4; j < 7; ++j) hm[k * 7 + j] = q[j];
+            if (sqrt_information) {
+                for (int j = 0; j < 36; ++j) {
+                    if (!std::isfinite(sqrt_information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the square-root information has an entry that is not finite");
+                    hw[k * 36 + j] = sqrt_information[k * 36 + j];
+                }
+            } else if (information) {
+                for (int j = 0; j < 36; ++j)
+                    if (!std::isfinite(information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the information matrix has an entry that is not finite");
+                if (!prior_information_factor(information + k * 36, &hw[k * 36]))
+                    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, at + "the information matrix is not positive definite");
+            } else {
+                for (int j = 0; j < 36; ++j) hw[k * 36 + j] = (j % 7 == 0) ? 1.0 : 0.0;
+            }
+        }
+        // by camera: 2 n references (2 * edge + side), side 1 where the camera is the edge's j
+        std::vector<int> cref(2 * m);
+        for (size_t k = 0; k < 2 * m; ++k) cref[k] = (int)k;
+        auto cam_of = [cam_i, cam_j](int ref) { return (ref & 1) ? cam_j[ref >> 1] : cam_i[ref >> 1]; };
+        std::stable_sort(cref.begin(), cref.end(), [&](int x, int y) { return cam_of(x) < cam_of(y); });
+        std::vector<int> cgp, cgc;
+        for (size_t p = 0; p < 2 * m; ++p)
+            if (p == 0 || cam_of(cref[p]) != cgc.back()) { cgp.push_back((int)p); cgc.push_back(cam_of(cref[p])); }
+        cgp.push_back(2 * n);
+        n_cg = (int)cgc.size();
+        // by unordered pair (hi, lo): n references, side 1 where hi is the edge's j
+        std::vector<int> pref(m);
+        for (size_t k = 0; k < m; ++k) pref[k] = 2 * (int)k + (cam_j[k] > cam_i[k] ? 1 : 0);
+        auto pair_of = [cam_i, cam_j](int ref) { const int e = ref >> 1; return std::make_pair(std::max(cam_i[e], cam_j[e]), std::min(cam_i[e], cam_j[e])); };
+        std::stable_sort(pref.begin(), pref.end(), [&](int x, int y) { return pair_of(x) < pair_of(y); });
+        std::vector<int> pgp;
+        std::vector<int2> pgq;
+        for (size_t p = 0; p < m; ++p) {
+            const auto hl = pair_of(pref[p]);
+            if (p == 0 || hl.first != pgq.back().x || hl.second != pgq.back().y) { pgp.push_back((int)p); pgq.push_back(make_int2(hl.first, hl.second)); }
+        }
+        pgp.push_back(n);
+        n_pg = (int)pgq.size();
+        STBA_TRY(i_new.alloc(m)); STBA_TRY(j_new.alloc(m)); STBA_TRY(meas_new.alloc(m * 7)); STBA_TRY(w_new.alloc(m * 36));
+        STBA_TRY(cgp_new.alloc(cgp.size())); STBA_TRY(cgc_new.alloc(cgc.size())); STBA_TRY(cgr_new.alloc(cref.size()));
+        STBA_TRY(pgp_new.alloc(pgp.size())); STBA_TRY(pgq_new.alloc(pgq.size())); STBA_TRY(pgr_new.alloc(pref.size()));
+        if (upload(i_new, cam_i, m, b->st) != STBA_OK || upload(j_new, cam_j, m, b->st) != STBA_OK ||
+            upload(meas_new, hm.data(), m * 7, b->st) != STBA_OK || upload(w_new, hw.data(), m * 36, b->st) != STBA_OK ||
+            upload(cgp_new, cgp.data(), cgp.size(), b->st) != STBA_OK || upload(cgc_new, cgc.data(), cgc.size(), b->st) != STBA_OK ||
+            upload(cgr_new, cref.data(), cref.size(), b->st) != STBA_OK || upload(pgp_new, pgp.data(), pgp.size(), b->st) != STBA_OK ||
+            upload(pgq_new, pgq.data(), pgq.size(), b->st) != STBA_OK || upload(pgr_new, pref.data(), pref.size(), b->st) != STBA_OK ||
+            hipStreamSynchronize(b->st) != hipSuccess)
+            return fail(STBA_ERR_HIP, who + ": upload failed");
+    }
+    // (nothing of the engine may still be reading the old edges or what was linearised with them: the moves below free them)
+    STBA_HIP(hipStreamSynchronize(b->st));
+    b->btw_i = std::move(i_new); b->btw_j = std::move(j_new); b->btw_meas = std::move(meas_new); b->btw_W = std::move(w_new);
+    b->btw_cg_ptr = std::move(cgp_new); b->btw_cg_cam = std::move(cgc_new); b->btw_cg_ref = std::move(cgr_new);
+    b->btw_pg_ptr = std::move(pgp_new); b->btw_pg_pair = std::move(pgq_new); b->btw_pg_ref = std::move(pgr_new);
+    b->n_btw = n; b->n_btw_cg = n_cg; b->n_btw_pg = n_pg;
+    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    cov_store_free(b->cov);
+    b->cov = nullptr;
+    return STBA_OK;
+}
+
+int stba_ba_relative_pose_count(const stba_ba* b, int* n) {
+    if (!b || !n) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_relative_pose_count: null argument");
+    *n = b->n_btw;
+    return STBA_OK;
+}
+
+int stba_ba_relative_pose_kernel_geometry(const stba_ba* b, int* groups_per_workgroup) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_relative_pose_kernel_geometry: null engine");
+    if (groups_per_workgroup) *groups_per_workgroup = BETWEEN_GROUPS_PER_WG;
+    return STBA_OK;
+}
+
+// the whitened residuals and Jacobians of the edges at the current parameters, by the pair groups of the block kernel itself (no
+// blocks written), and their cost by the cost kernel; the caller's order.  The engine's linearisation state is not touched
+int stba_ba_evaluate_relative_poses(stba_ba* b, double* cost, double* r, double* Ji, double* Jj) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_evaluate_relative_poses: null engine");
+    if (cost) *cost = 0.0;
+    if (!b->n_btw) return STBA_OK;
+    const size_t m = (size_t)b->n_btw;
+    DevBuf<double> dr, dji, djj, dcost;
+    double c2 = 0.0;
+    if (r || Ji || Jj) {
+        STBA_TRY(dr.alloc(m * 6)); STBA_TRY(dji.alloc(m * 36)); STBA_TRY(djj.alloc(m * 36));
+        STBA_TRY(launch_between_blocks(b->between_args(), b->cams[b->cur], nullptr, nullptr, nullptr, b->lda, dr, dji, djj, b->st));
+        if (r) STBA_TRY(download(r, dr, m * 6, b->st));
+        if (Ji) STBA_TRY(download(Ji, dji, m * 36, b->st));
+        if (Jj) STBA_TRY(download(Jj, djj, m * 36, b->st));
+    }
+    if (cost) {
+        STBA_TRY(dcost.alloc(1));
+        STBA_TRY(launch_between_cost(b->between_args(), b->cams[b->cur], dcost, b->st));
+        STBA_TRY(download(&c2, dcost, 1, b->st));
+    }
+    STBA_HIP(hipStreamSynchronize(b->st));
+    if (cost) *cost = 0.5 * c2;
+    return STBA_OK;
+}
+
 int stba_ba_has_loss(const stba_ba* b, int* has) {
     if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_loss: null argument");
     *has = b->loss_kind ? 1 : 0;
@@ -1994,6 +2154,8 @@ int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has information matrices, which run on one rank only");
     if (b && b->n_prior && (fn || world_size > 1))
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has pose priors, which run on one rank only");
+    if (b && b->n_btw && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has relative-pose factors, which run on one rank only");
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -2058,6 +2220,7 @@ int stba_ba_normal_blocks(stba_ba* b, double* Hcc, double* gc, double* Hpp, doub
     STBA_TRY(ba_normal_blocks(b));
     STBA_TRY(ba_camera_blocks(b));
     STBA_TRY(ba_prior_blocks(b));
+    STBA_TRY(ba_between_blocks(b, false));
     std::vector<double> h6;
     if (Hcc) STBA_TRY(download(Hcc, b->Hcc, (size_t)b->nc * 36, b->st));
     if (gc) STBA_TRY(download(gc, b->gc, (size_t)b->nc * 6, b->st));
@@ -2169,6 +2332,7 @@ int stba_ba_set_trust_region(stba_ba* b, int strategy) {
                         "(this engine uses ITERATIVE_SCHUR)");
         if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG runs on one rank only (an all-reduce hook is set)");
         if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: this engine has pose priors (DOGLEG with pose priors is not supported)");
+        if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: this engine has relative-pose factors (DOGLEG with relative-pose factors is not supported)");
     }
     b->trust_region = strategy;
     return STBA_OK;
@@ -2199,6 +2363,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has a loss table (inner iterations with losses are not supported)");
     if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has information matrices (inner iterations with information matrices are not supported)");
     if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has pose priors (inner iterations with pose priors are not supported)");
+    if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has relative-pose factors (inner iterations with relative-pose factors are not supported)");
     const int nc = b->nc, np = b->np, no = b->no;
     // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
     std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
@@ -2287,6 +2452,7 @@ int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int
     if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has a loss table (inner iterations with losses are not supported)");
     if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has information matrices (inner iterations with information matrices are not supported)");
     if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has pose priors (inner iterations with pose priors are not supported)");
+    if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has relative-pose factors (inner iterations with relative-pose factors are not supported)");
     const bool was_on = b->inner_on;
     if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
     STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
