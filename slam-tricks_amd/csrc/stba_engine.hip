@@ -11,14 +11,10 @@
 #include <thread>
 #include <vector>
 
-#include "ba_kernels.hpp"
-#include "ba_prior.hpp"
-#include "ba_between.hpp"
-#include "iterative_schur.hpp"
+#include "ba_engine.hpp"
 #include "dogleg.hpp"
 #include "inner_iterations.hpp"
 #include "lm_policy.hpp"
-#include "robust_loss.hpp"
 
 namespace stba {
 
@@ -34,185 +30,10 @@ int require_device() {
     return STBA_OK;
 }
 
-// scalar slots in the extras region behind S (summed across ranks together with S)
-enum { SC_COST2 = 0, SC_GPMAX0 = 8, SC_MAX_WORLD = 64 };
-// trial-point scalars: [0..3] summed across ranks (landmark shards), [4..6] camera terms
-// (TS_TIMEOUT: 1.0 if this rank's persistent factorisation gave up -- it sits inside the all-reduced prefix of the block, so with
-// several ranks every rank sees the NUMBER of ranks that timed out and they all take the recovery path together)
-// Behind them: TS_SPEC_COST2, the cost of the speculative linearisation at the trial point (in the host's copy of the block: the
-// factorisation's flag); then cost2 and |g|max of the LAST reduced-system build (ex_scalar, ex_gc), which the LM loop reads one
-// iteration late -- outside the summed prefix, and equal on every rank (both come from the all-reduced extras).
-enum { TS_COST2 = 0, TS_STEP2 = 1, TS_X2 = 2, TS_MODEL = 3, TS_TIMEOUT = 4, TS_CAM = 5, TS_COUNT = 8,
-       TS_SPEC_COST2 = 8, TS_LIN_COST2 = 9, TS_LIN_GMAX = 10, TS_BLOCK = 11 };
-// phase-timing events of a BA solve (stba_ba::ev; recorded only with stba_lm_options::phase_timing).  A pair is {X, X + 1}:
-// the linearisation and the build the loop reads in the same iteration; the ends of the solve, the back-substitution and the trial
-// evaluation; the two pairs the speculative linearisation alternates between; the build whose pair is read one solve later
-// (ba_step_events).  stba_ba_time_linearize / _schur / _schur_apply borrow the first pair.
-enum { EV_LIN = 0, EV_LIN_END, EV_BUILD, EV_BUILD_END, EV_SOLVE_END, EV_BACKSUB_END, EV_TRIAL_END,
-       EV_SPEC_A, EV_SPEC_A_END, EV_SPEC_B, EV_SPEC_B_END, EV_DBUILD, EV_DBUILD_END, EV_COUNT };
-
 }  // namespace stba
-
-using namespace stba;
 
 static_assert(sizeof(PairRec) == sizeof(int4) && alignof(int4) % alignof(PairRec) == 0, "the Schur kernel reads a pair record as one int4");
 static_assert(SCHUR_FORM_PAIRS == STBA_SCHUR_PAIRS && SCHUR_FORM_DENSE == STBA_SCHUR_DENSE, "schur_plan.hpp mirrors include/stba.h");
-
-struct stba_ba {
-    int nc = 0, np = 0, no = 0, n = 0, lda = 0;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    std::vector<int> perm;   // sorted position -> caller's observation index
-    // device
-    DevBuf<double> cams[2], pts[2];
-    int cur = 0;
-    DevBuf<double2> feat;
-    DevBuf<int> obs_cam, obs_pt, pt_start;
-    DevBuf<int> cam_perm, chunk_begin, chunk_end, cam_chunk_start;
-    int n_chunks = 0;
-    // Schur plan: task = (camera row, slice [lo, hi) of the row's column list), see build_schur_plan (schur_plan.hpp)
-    DevBuf<int> task_cam, cam_start, row_col_ptr, row_cols;
-    DevBuf<int> task_col_lo, task_col_hi;
-    int n_tasks = 0, max_cols = 0;
-    // round 6, FEW camera rows (landmark-heavy problems): a task = (camera row, a RANGE of the camera's observation list), all columns of
-    // the row; the slices of a row write partial blocks, ba_schur_reduce_slices_kernel adds them in order (see plan_rows, schur_plan.hpp)
-    DevBuf<int> task_p_lo, task_p_hi, row_task_ptr, row_tasks;
-    DevBuf<long long> task_part_off;
-    DevBuf<double> schur_part;
-    bool lm_slices = false;
-    std::shared_ptr<SchurPlan> create_leftovers;     // the host-side plan of ba_create, kept until the engine goes (see there)
-    std::vector<unsigned char> create_omask;         // (the host copy of omask: kept, and freed, with it)
-    // pair plan of the Schur kernel (see ba_schur_pairs_kernel)
-    DevBuf<int> pair_begin, pair_end;      // per (task, wave)
-    DevBuf<int> task_vs_ptr, vs_first;     // per task: first accumulator slot of every block of its slice (+ the slot count)
-    int schur_plan_mode = 0;                              // SchurArgs::mode the plan was built for
-    DevBuf<int4> pair_rec;           // (i, l, landmark, slot | flags)
-    double schur_pairs = 0.0, schur_lds_atomics = 0.0;   // per launch of the Schur kernel (measurement)
-    // the Schur complement as a dense symmetric product (dense visibility; ba_kernels.hip "DENSE visibility", stba_ba_set_schur_mode)
-    int schur_mode = STBA_SCHUR_PAIRS, schur_mode_auto = STBA_SCHUR_PAIRS;
-    bool have_pair_plan = false;
-    DevBuf<double> Y; size_t ldy = 0, ykcols = 0;     // [lda][ldy]
-    DevBuf<double> yv, yws;
-    DevBuf<unsigned char> dup_run;                    // repeated (camera, landmark) pairs, per position of cam_perm (null: none)
-    bool dup_overflow = false;                           // some pair has more than 255 observations: the DENSE form cannot take this problem
-    int stage_cooldown = 0;                              // several ranks: factorisations left that take the stage kernels (see ba_run_lm)
-    DevBuf<unsigned char> cam_fixed, pt_fixed;
-    DevBuf<double2> r;
-    DevBuf<double> J8;            // compact Jacobian [n_obs][8] (ba_kernels.hip)
-    // host-linearised factors (stba_ba_set_host_linearizer): the user's cost functions make r and the 2x6 | 2x3 Jacobians on the
-    // host; J8 then holds {0, 0, Jp} per observation and Jc12 the camera blocks -- everything behind the linearisation is unchanged
-    stba_ba_linearize_fn hl_fn = nullptr;
-    void* hl_user = nullptr;
-    DevBuf<double> Jc12;          // [n_obs][12]
-    std::vector<double> hl_cams, hl_pts, hl_r, hl_jc, hl_jp, hl_stage, hl_cost_stage;   // host staging (caller order | engine order)
-    // per-observation robust losses (stba_ba_set_loss): kind (STBA_LOSS_*), a, b, scale, each [n_obs] in the engine's
-    // order; all null: no table.  With one, ba_linearize_robust_kernel writes the corrected r', J8 = {0, 0, Jp'} and Jc12 = Jc', and
-    // everything behind the linearisation runs its general form on them, as for host-linearised factors
-    DevBuf<int> loss_kind;
-    DevBuf<double> loss_a, loss_b, loss_scale;
-    // per-observation square-root information W_i (stba_ba_set_information / _sqrt_information): [n_obs][4], 2 x 2
-    // row-major in the engine's order; null: the identity.  With it the same kernel whitens r, Jc, Jp in front of the corrector
-    DevBuf<double> winfo;
-    DevBuf<unsigned char> omask;  // per observation: constant dofs of its camera (bits 0..5) | constant landmark (bit 6); null if none
-    DevBuf<double> Hpp6, gp, Hinv6, Rinv9, dp, scale_p;
-    DevBuf<double> Hcc, gc, cam_partial, dc, scale_c;
-    DevBuf<double> Sbuf;   // [S lda*lda | ex_diag lda | ex_gc lda | rhs lda | ex_scalar lda]
-    DevBuf<double> dxc, dxp;
-    DevBuf<double> cost_partial, upd_partial_c, upd_partial_p;
-    DevBuf<double> trial;   // TS_BLOCK doubles
-    MappedBuffer ts_host;        // the trial block + the factorisation flag as a stamped block, written by a kernel
-    double ts_seq = 0.0;         // sequence number of the last trial block asked for (the stamp of the block's lines)
-    double ts_vals[TS_BLOCK] = {0};          // the host's copy of the last trial block (validated, or downloaded after a synchronise)
-    DevBuf<int> flag;
-    int lin_grid = 1;
-    stba_allreduce_fn ar = nullptr;
-    void* ar_user = nullptr;
-    int rank = 0, world = 1;
-    bool have_lin = false, have_blocks = false, have_reduced = false, have_dxc = false, have_dxp = false;
-    bool scale_init = false;
-    hipEvent_t ev_ar[2] = {};   // around the cross-rank sum of the reduced system (several ranks only)
-    bool ar_timing_pending = false, ar_timing_on = false;
-    double ar_ms = 0.0, ar_bytes = 0.0; int ar_calls = 0;   // accumulated over one LM run
-    hipEvent_t ev[EV_COUNT] = {};   // phase timing of a solve (the EV_ enum)
-    CovStore* cov = nullptr;    // the last stba_ba_covariance_compute (covariance.hip), until the next one, a release or destroy
-    // ITERATIVE_SCHUR (stba_ba_create_ex; iterative_schur.hip): no S, no pair plan, no Y -- Sbuf holds only the extras tail.
-    // PCG vectors x = dxc, r, z, p, q; one 6x6 preconditioner inverse per camera; the chunk partials of the Schur-Jacobi blocks;
-    // three per-workgroup partial arrays; the solve's device state and its stamped hand-off to the host
-    bool iterative = false;
-    int pcg_precond = STBA_PRECOND_JACOBI, pcg_min = 0, pcg_max = 500, pcg_check = 4;
-    double pcg_eta = 0.1;
-    stba_pcg_summary pcg_sum{};
-    DevBuf<double> pcg_vec, pcg_minv, pcg_sj, pcg_part;
-    DevBuf<PcgState> pcg_state;
-    MappedBuffer pcg_host;
-    double pcg_seq = 0.0;
-    int pcg_last_it = 0, pcg_last_cap = 0;     // the last solve, counted into pcg_sum once the LM loop keeps its step
-    std::vector<int> pcg_per_iter;             // PCG iterations of every LM iteration of the last solve (1, 2, ...)
-    // DOGLEG (stba_ba_set_trust_region; dogleg.hip): s .* u of cameras and landmarks, the terms kernel's partials, the six scalars,
-    // the step's stamped block for the host; the summary of the last solve
-    int trust_region = STBA_TR_LEVENBERG_MARQUARDT;
-    DevBuf<double> dl_uc, dl_up, dl_part, dl_sc;
-    MappedBuffer dl_host;
-    double dl_seq = 0.0;
-    stba_dogleg_summary dl_sum{};
-    // inner iterations (stba_ba_set_inner_iterations; inner_iterations.hip): the ordering as per-group ranges of a
-    // camera list (with each entry's dof mask) and a landmark list, in ascending group id; the entries' iteration counts; the gate of
-    // the sweep behind a trial point, its two scalars {cost2 at x*, |x - x*|^2} and the partials of the latter
-    bool inner_on = false;
-    double inner_tol = 1e-3;
-    struct InnerGroup { int cam_lo, cam_hi, pt_lo, pt_hi; };
-    std::vector<InnerGroup> inner_groups;
-    std::vector<int> inner_cam_h, inner_pt_h;
-    std::vector<unsigned char> inner_mask_h, inner_kind_h;   // kind: 1 rotation, 2 position, 3 both (a 6-dof block)
-    DevBuf<int> inner_cam, inner_pt, inner_it, inner_gate;
-    DevBuf<unsigned char> inner_mask;
-    DevBuf<double> inner_sc, inner_part;
-    hipEvent_t inner_ev[2] = {};
-    stba_inner_summary inner_sum{};
-    // camera pose priors (stba_ba_set_pose_priors; ba_prior.hip): grouped by camera -- CSR over the cameras that have
-    // any, inside a group the caller's order -- with the poses (quaternions normalised) and the 6 x 6 square-root informations in
-    // that order; prior_order: grouped position -> the caller's index.  With priors the cost partials carry ONE more slot behind
-    // the lineariser's lin_grid (n_cost), filled by the cost form at every linearisation; the block form adds to Hcc, gc behind the
-    // Schur step at lin_which, the parameter buffer the Jacobian records were last made at
-    int n_prior = 0, n_prior_groups = 0;
-    DevBuf<int> prior_ptr, prior_cam;
-    DevBuf<double> prior_pose, prior_W;
-    std::vector<int> prior_order;
-    int lin_which = 0;
-    // camera-to-camera relative-pose factors (stba_ba_set_relative_poses; ba_between.hip): the edges in the caller's
-    // order and two CSRs of references into them, by camera and by unordered pair.  With edges the cost partials carry one more slot,
-    // behind the priors' where there are priors; the block form adds to Hcc, gc AND to the blocks (hi, lo) of S behind the Schur step
-    int n_btw = 0, n_btw_cg = 0, n_btw_pg = 0;
-    DevBuf<int> btw_i, btw_j, btw_cg_ptr, btw_cg_cam, btw_cg_ref, btw_pg_ptr, btw_pg_ref;
-    DevBuf<int2> btw_pg_pair;
-    DevBuf<double> btw_meas, btw_W;
-    int n_cost() const { return lin_grid + (n_prior ? 1 : 0) + (n_btw ? 1 : 0); }
-    PriorArgs prior_args() const { return PriorArgs{n_prior_groups, prior_ptr, prior_cam, prior_pose, prior_W, cam_fixed}; }
-    BetweenArgs between_args() const {
-        return BetweenArgs{n_btw, n_btw_cg, n_btw_pg, btw_i, btw_j, btw_meas, btw_W, btw_cg_ptr, btw_cg_cam, btw_cg_ref,
-                           btw_pg_ptr, btw_pg_pair, btw_pg_ref, cam_fixed};
-    }
-
-    size_t s_count() const { return iterative ? 0 : (size_t)lda * lda; }
-    double* S() const { return iterative ? nullptr : Sbuf; }
-    double* ex_diag() const { return Sbuf + s_count(); }
-    double* ex_gc() const { return Sbuf + s_count() + lda; }
-    double* rhs() const { return Sbuf + s_count() + 2 * (size_t)lda; }
-    double* ex_scalar() const { return Sbuf + s_count() + 3 * (size_t)lda; }
-    size_t sbuf_count() const { return s_count() + 4 * (size_t)lda; }
-    // cross-rank sum: only the lower triangle of the n x n system travels (S is symmetric and only its lower
-    // triangle is ever read), followed by the four extras vectors: [tri n(n+1)/2 | ex_diag | ex_gc | rhs | scalars]
-    // When the union over ranks of the non-zero 6x6 blocks is sparse (C5: 14 % of the camera pairs share a
-    // landmark), only those blocks travel: [blocks pk_nz * 36 | extras] -- 20 MB instead of 144 MB at C5.
-    DevBuf<double> Spack;
-    std::vector<int> h_row_col_ptr, h_row_cols;   // host copy of the local block pattern (lower triangle, by camera)
-    int pk_state = 0;           // 0: not planned yet, 1: triangle, 2: block list
-    int pk_nz = 0;
-    DevBuf<int2> pk_blocks;  // (row camera, column camera) of every travelling block
-    size_t pack_count() const {
-        return (pk_state == 2 ? (size_t)pk_nz * 36 : (size_t)n * (n + 1) / 2) + 4 * (size_t)lda;
-    }
-};
 
 namespace stba {
 
@@ -287,31 +108,27 @@ static int ba_host_linearize(stba_ba* b, int which, bool with_jac) {
     return STBA_OK;
 }
 
-// the camera blocks of the GENERAL form (J8 = {0, 0, Jp}, Jc12 = the 2 x 6 blocks), which every kernel behind the linearisation
-// takes in its GEN instantiation: host-linearised factors and engines with a loss table or weights; null: the compact record
-static const double* ba_general_jc(const stba_ba* b) { return (b->hl_fn || b->loss_kind || b->winfo) ? b->Jc12.get() : nullptr; }
-
 // THE linearisation at parameter buffer `which`: the host's callback, the robust kernel (a loss table and / or weights are set: its
 // INFO / LOSS pair follows from which of the two the engine holds) or the lossless kernel.  The cost partials (sum r^2, or sum rho with a table) are left in cost_partial; with_jac: r, J8 (and Jc12) are stored
 static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
     if (b->hl_fn) return ba_host_linearize(b, which, with_jac);
     const LinArgs a = lin_args(b, which, with_jac);
     if (with_jac) b->lin_which = which;
-    if (b->loss_kind || b->winfo)
-        STBA_TRY(launch_linearize_robust(a, LinLoss{b->loss_kind, b->loss_a, b->loss_b, b->loss_scale, b->Jc12, b->winfo}, with_jac, b->lin_grid, b->st));
+    if (b->loss.kind || b->winfo)
+        STBA_TRY(launch_linearize_robust(a, LinLoss{b->loss.kind, b->loss.a, b->loss.b, b->loss.scale, b->Jc12, b->winfo}, with_jac, b->lin_grid, b->st));
     else
         STBA_TRY(launch_linearize(a, with_jac, b->lin_grid, b->st));
     // pose priors: their cost at the same parameters into the slot behind the lineariser's partials (one launch; n_cost counts it)
-    if (b->n_prior) STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[which], b->cost_partial + b->lin_grid, b->st));
+    if (b->prior.n) STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[which], b->cost_partial + b->lin_grid, b->st));
     // relative-pose factors: theirs into the next slot
-    if (b->n_btw) STBA_TRY(launch_between_cost(b->between_args(), b->cams[which], b->cost_partial + b->lin_grid + (b->n_prior ? 1 : 0), b->st));
+    if (b->btw.n) STBA_TRY(launch_between_cost(b->between_args(), b->cams[which], b->cost_partial + b->lin_grid + (b->prior.n ? 1 : 0), b->st));
     return STBA_OK;
 }
 
 // pose priors: sum J'^T J' into Hcc and sum J'^T r' into gc, at the parameters the Jacobian records were made at (one launch; none
 // without priors).  Behind whatever has just WRITTEN the camera blocks: the Schur step or the camera-block kernel
 static int ba_prior_blocks(stba_ba* b) {
-    if (!b->n_prior) return STBA_OK;
+    if (!b->prior.n) return STBA_OK;
     return launch_prior_blocks(b->prior_args(), b->cams[b->lin_which], b->Hcc, b->gc, nullptr, nullptr, b->st);
 }
 
@@ -319,7 +136,7 @@ static int ba_prior_blocks(stba_ba* b) {
 // which the Schur step has just zeroed and written (every build: nothing accumulates from one build to the next).  One launch; none
 // without edges
 static int ba_between_blocks(stba_ba* b, bool with_S) {
-    if (!b->n_btw) return STBA_OK;
+    if (!b->btw.n) return STBA_OK;
     return launch_between_blocks(b->between_args(), b->cams[b->lin_which], b->Hcc, b->gc, with_S ? b->S() : nullptr, b->lda, nullptr, nullptr,
                                  nullptr, b->st);
 }
@@ -978,7 +795,7 @@ static int ba_solve_end(stba_ba* b, BaSolve& sv, double radius, stba_lm_summary*
     sv.s.ms_allreduce = b->ar_ms; sv.s.allreduce_bytes = b->ar_bytes; sv.s.allreduce_calls = b->ar_calls;
     finish_summary(&sv.s, sv.iter, sv.cost, radius, sv.gmax, sv.t_start);
     b->pcg_sum.linear_solve_ms = b->iterative ? sv.s.ms_solve : 0.0;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     if (sum) *sum = sv.s;
     return STBA_OK;
 }
@@ -1581,7 +1398,8 @@ int stba_ba_create_ex(stba_ba** out, int n_cams, int n_pts, int n_obs, const dou
                      solver == STBA_LINEAR_ITERATIVE_SCHUR);
 }
 
-// what an ITERATIVE_SCHUR engine refuses: everything that needs the explicit reduced system, and several ranks
+// what an ITERATIVE_SCHUR engine refuses for want of the explicit reduced system: the stage and measurement entry points and the
+// covariance (the features it does not go together with are rows of ba_features.hpp)
 static int refuse_iterative(const stba_ba* b, const char* who, const char* why) {
     if (!b || !b->iterative) return STBA_OK;
     return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine uses ITERATIVE_SCHUR, " + why);
@@ -1688,7 +1506,7 @@ int stba_ba_set_params(stba_ba* b, const double* cams, const double* pts) {
     if (cams) STBA_TRY(upload(b->cams[b->cur], cams, (size_t)b->nc * 7, b->st));
     if (pts) STBA_TRY(upload(b->pts[b->cur], pts, (size_t)b->np * 3, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     return STBA_OK;
 }
 
@@ -1702,7 +1520,7 @@ int stba_ba_set_features(stba_ba* b, const double* obs_feat) {
     }
     STBA_TRY(upload(reinterpret_cast<double*>(b->feat.get()), s_feat.data(), (size_t)b->no * 2, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     return STBA_OK;
 }
 
@@ -1726,436 +1544,8 @@ int stba_ba_get_params(stba_ba* b, double* cams, double* pts) {
     return STBA_OK;
 }
 
-int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
-    if (fn && b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has inner iterations (device residuals only)");
-    if (fn && b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has a loss table (losses need device residuals; not supported together)");
-    if (fn && b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has information matrices (the callback's factors whiten themselves; not supported together)");
-    if (fn && b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has pose priors (priors need device residuals; not supported together)");
-    if (fn && b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_host_linearizer: this engine has relative-pose factors (the factors need device residuals; not supported together)");
-    if (fn && !b->Jc12) STBA_TRY(b->Jc12.alloc((size_t)b->no * 12));
-    b->hl_fn = fn; b->hl_user = user;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    return STBA_OK;
-}
-
-// the per-observation loss table: checked on the host BEFORE anything is replaced (a refused call leaves the engine with the table it
-// had), permuted into the engine's landmark-major order, uploaded into NEW arrays that are swapped in; kind == NULL releases the table
-int stba_ba_set_loss(stba_ba* b, const int* kind, const double* a, const double* lb, const double* scale) {
-    const char* who = "stba_ba_set_loss";
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    DevBuf<int> k_new;
-    DevBuf<double> a_new, b_new, s_new, jc_new;
-    if (kind) {
-        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has a host lineariser (losses need device residuals; not supported together)");
-        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has inner iterations (inner iterations with losses are not supported)");
-        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and losses run on one rank only");
-        const size_t m = (size_t)b->no;
-        std::vector<double> ha, hb, hs;
-        STBA_TRY(loss_table_check(who, "observation", m, kind, a, lb, scale, ha, hb, hs));
-        std::vector<int> pk(m);
-        std::vector<double> pa(m), pb(m), ps(m);
-        for (size_t p = 0; p < m; ++p) {                    // the engine's order: b->perm = position -> the caller's index
-            const size_t i = (size_t)b->perm[p];
-            pk[p] = kind[i]; pa[p] = ha[i]; pb[p] = hb[i]; ps[p] = hs[i];
-        }
-        STBA_TRY(k_new.alloc(m)); STBA_TRY(a_new.alloc(m)); STBA_TRY(b_new.alloc(m)); STBA_TRY(s_new.alloc(m));
-        if (!b->Jc12) STBA_TRY(jc_new.alloc(std::max<size_t>(m, 1) * 12));
-        if (upload(k_new, pk.data(), m, b->st) != STBA_OK || upload(a_new, pa.data(), m, b->st) != STBA_OK ||
-            upload(b_new, pb.data(), m, b->st) != STBA_OK || upload(s_new, ps.data(), m, b->st) != STBA_OK ||
-            (m > 0 && hipStreamSynchronize(b->st) != hipSuccess))
-            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-    }
-    // (nothing of the engine may still be reading the old table or what was linearised with it: the moves below free it)
-    STBA_HIP(hipStreamSynchronize(b->st));
-    b->loss_kind = std::move(k_new); b->loss_a = std::move(a_new); b->loss_b = std::move(b_new); b->loss_scale = std::move(s_new);
-    if (jc_new) b->Jc12 = std::move(jc_new);
-    if (!kind && !b->hl_fn && !b->winfo) b->Jc12.reset();      // (96 B per observation nobody reads any more)
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    cov_store_free(b->cov);
-    b->cov = nullptr;
-    return STBA_OK;
-}
-
-// Omega = L L^T, W = L^T of ONE symmetric 2 x 2 from its lower triangle (a, b, c) = (in[0], in[2], in[3]): l11 = sqrt(a), l21 = b / l11,
-// l22 = sqrt(c - b^2 / a).  The pivot is formed directly from a, b, c with error-free products: t = fl(b / a), t b = p + e and
-// b - t a = rem exactly (FMA), c - p = sum + err exactly (two-sum), so pivot = sum + (err - e - rem b / a) carries one rounding where
-// c - l21^2 would carry kappa(Omega) of them: every entry of W is within 4 eps of the exact factor of the matrix given.
-// false: an entry that is not finite, or a pivot that is not a positive finite number.
-static bool ba_information_factor(const double* in, double* W) {
-    const double a = in[0], bb = in[2], c = in[3];
-    if (!std::isfinite(a) || !std::isfinite(in[1]) || !std::isfinite(bb) || !std::isfinite(c) || !(a > 0.0)) return false;
-    const double l11 = std::sqrt(a);
-    const double t = bb / a;
-    const double p = t * bb, e = std::fma(t, bb, -p);
-    const double rem = std::fma(-t, a, bb);
-    const double sum = c - p, z = sum - c;
-    const double err = (c - (sum - z)) + (-p - z);
-    const double pivot = sum + ((err - e) - rem * bb / a);
-    if (!(pivot > 0.0) || !std::isfinite(pivot)) return false;
-    W[0] = l11; W[1] = bb / l11; W[2] = 0.0; W[3] = std::sqrt(pivot);
-    return std::isfinite(W[0]) && std::isfinite(W[1]) && std::isfinite(W[3]);
-}
-
-// the per-observation weights: checked (and, for the information form, factored) on the host BEFORE anything is replaced, permuted
-// into the engine's landmark-major order, uploaded into a NEW array that is swapped in; in == NULL, or an array whose every W is
-// exactly the identity, goes back to the identity (no array held)
-static int ba_set_weights(stba_ba* b, const double* in, bool sqrt_form, const char* who) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": null engine");
-    DevBuf<double> w_new, jc_new;
-    const size_t m = (size_t)b->no;
-    std::vector<double> hw;
-    if (in) {
-        // (the messages below name the row as "observation <index>:" -- include/stba/g2o.h reads the index out of that text to name the
-        // edge; keep the wording)
-        hw.resize(m * 4);
-        bool all_identity = true;
-        for (size_t e = 0; e < m; ++e) {
-            if (sqrt_form) {
-                for (int k = 0; k < 4; ++k) {
-                    if (!std::isfinite(in[e * 4 + k]))
-                        return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": observation " + std::to_string(e) + ": the square-root information has an entry that is not finite");
-                    hw[e * 4 + k] = in[e * 4 + k];
-                }
-            } else if (!ba_information_factor(in + e * 4, &hw[e * 4])) {
-                return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string(who) + ": observation " + std::to_string(e) + ": the information matrix is not positive definite (or has an entry that is not finite)");
-            }
-            const double* w = &hw[e * 4];
-            all_identity = all_identity && w[0] == 1.0 && w[1] == 0.0 && w[2] == 0.0 && w[3] == 1.0;
-        }
-        // every W exactly the identity IS the engine without weights: the array is not held (as for NULL), the lossless kernels run
-        if (all_identity) in = nullptr;
-    }
-    if (in) {
-        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has a host lineariser (the callback's factors whiten themselves; not supported together)");
-        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has inner iterations (inner iterations with information matrices are not supported)");
-        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, std::string(who) + ": this engine has an all-reduce hook, and information matrices run on one rank only");
-        std::vector<double> pw(m * 4);
-        for (size_t p = 0; p < m; ++p) memcpy(&pw[p * 4], &hw[(size_t)b->perm[p] * 4], 4 * sizeof(double));   // the engine's order
-        STBA_TRY(w_new.alloc(m * 4));
-        if (!b->Jc12) STBA_TRY(jc_new.alloc(std::max<size_t>(m, 1) * 12));
-        if (upload(w_new, pw.data(), m * 4, b->st) != STBA_OK || (m > 0 && hipStreamSynchronize(b->st) != hipSuccess))
-            return fail(STBA_ERR_HIP, std::string(who) + ": upload failed");
-    }
-    // (nothing of the engine may still be reading the old array or what was linearised with it: the moves below free it)
-    STBA_HIP(hipStreamSynchronize(b->st));
-    b->winfo = std::move(w_new);
-    if (jc_new) b->Jc12 = std::move(jc_new);
-    if (!in && !b->hl_fn && !b->loss_kind) b->Jc12.reset();
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    cov_store_free(b->cov);
-    b->cov = nullptr;
-    return STBA_OK;
-}
-
-int stba_ba_set_information(stba_ba* b, const double* information) { return ba_set_weights(b, information, false, "stba_ba_set_information"); }
-int stba_ba_set_sqrt_information(stba_ba* b, const double* sqrt_information) { return ba_set_weights(b, sqrt_information, true, "stba_ba_set_sqrt_information"); }
-
-int stba_ba_has_information(const stba_ba* b, int* has) {
-    if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_information: null argument");
-    *has = b->winfo ? 1 : 0;
-    return STBA_OK;
-}
-
-int stba_ba_get_sqrt_information(stba_ba* b, double* out) {
-    if (!b || !out) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_get_sqrt_information: null argument");
-    const size_t m = (size_t)b->no;
-    if (!b->winfo) {
-        for (size_t e = 0; e < m; ++e) { out[e * 4] = 1.0; out[e * 4 + 1] = 0.0; out[e * 4 + 2] = 0.0; out[e * 4 + 3] = 1.0; }
-        return STBA_OK;
-    }
-    std::vector<double> pw(m * 4);
-    if (m > 0) STBA_TRY(download(pw.data(), b->winfo, m * 4, b->st));
-    STBA_HIP(hipStreamSynchronize(b->st));
-    for (size_t p = 0; p < m; ++p) memcpy(&out[(size_t)b->perm[p] * 4], &pw[p * 4], 4 * sizeof(double));
-    return STBA_OK;
-}
-
-// ---- camera pose priors.  Everything is checked -- and, for the information form, factored -- on the host BEFORE
-// anything is replaced; the priors are grouped by camera (a stable sort: inside a group the caller's order), uploaded into NEW arrays
-// that are swapped in.  n == 0 releases them: the engine then enqueues exactly what one that never had priors enqueues
-int stba_ba_set_pose_priors(stba_ba* b, int n, const int* cam, const double* pose, const double* information, const double* sqrt_information) {
-    const std::string who = "stba_ba_set_pose_priors";
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
-    if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
-    if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
-    DevBuf<int> ptr_new, cam_new;
-    DevBuf<double> pose_new, w_new;
-    std::vector<int> order;
-    int n_groups = 0;
-    if (n > 0) {
-        if (!cam || !pose) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null cam or pose array");
-        if (b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses ITERATIVE_SCHUR (its inexact-step model is summed from the observation records; pose priors are not supported)");
-        if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses DOGLEG (DOGLEG with pose priors is not supported)");
-        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has inner iterations (inner iterations with pose priors are not supported)");
-        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has a host lineariser (priors need device residuals; not supported together)");
-        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has an all-reduce hook, and pose priors run on one rank only");
-        const size_t m = (size_t)n;
-        std::vector<double> hp(m * 7), hw(m * 36);
-        for (size_t k = 0; k < m; ++k) {
-            const std::string at = who + ": prior " + std::to_string(k) + ": ";
-            if (cam[k] < 0 || cam[k] >= b->nc) return fail(STBA_ERR_INVALID_ARGUMENT, at + "camera index " + std::to_string(cam[k]) + " out of range");
-            for (int j = 0; j < 7; ++j)
-                if (!std::isfinite(pose[k * 7 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the pose has an entry that is not finite");
-            const double* q = pose + k * 7;
-            const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
-            if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(STBA_ERR_INVALID_ARGUMENT, at + "zero quaternion");
-            // (a quaternion that is unit to rounding keeps its bits: a prior AT a camera's pose then has the residual exactly 0)
-            const double sc = std::fabs(n2 - 1.0) <= 8 * 2.220446049250313e-16 ? 1.0 : 1.0 / std::sqrt(n2);
-            for (int j = 0; j < 4; ++j) hp[k * 7 + j] = q[j] * sc;
-            for (int j = 4; j < 7; ++j) hp[k * 7 + j] = q[j];
-            if (sqrt_information) {
-                for (int j = 0; j < 36; ++j) {
-                    if (!std::isfinite(sqrt_information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the square-root information has an entry that is not finite");
-                    hw[k * 36 + j] = sqrt_information[k * 36 + j];
-                }
-            } else if (information) {
-                for (int j = 0; j < 36; ++j)
-                    if (!std::isfinite(information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the information matrix has an entry that is not finite");
-                if (!prior_information_factor(information + k * 36, &hw[k * 36]))
-                    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, at + "the information matrix is not positive definite");
-            } else {
-                for (int j = 0; j < 36; ++j) hw[k * 36 + j] = (j % 7 == 0) ? 1.0 : 0.0;
-            }
-        }
-        order.resize(m);
-        for (size_t k = 0; k < m; ++k) order[k] = (int)k;
-        std::stable_sort(order.begin(), order.end(), [cam](int x, int y) { return cam[x] < cam[y]; });
-        std::vector<int> gptr, gcam;
-        std::vector<double> gp(m * 7), gw(m * 36);
-        for (size_t p = 0; p < m; ++p) {
-            const size_t k = (size_t)order[p];
-            if (p == 0 || cam[k] != gcam.back()) { gptr.push_back((int)p); gcam.push_back(cam[k]); }
-            memcpy(&gp[p * 7], &hp[k * 7], 7 * sizeof(double));
-            memcpy(&gw[p * 36], &hw[k * 36], 36 * sizeof(double));
-        }
-        gptr.push_back(n);
-        n_groups = (int)gcam.size();
-        STBA_TRY(ptr_new.alloc(gptr.size())); STBA_TRY(cam_new.alloc(gcam.size())); STBA_TRY(pose_new.alloc(m * 7)); STBA_TRY(w_new.alloc(m * 36));
-        if (upload(ptr_new, gptr.data(), gptr.size(), b->st) != STBA_OK || upload(cam_new, gcam.data(), gcam.size(), b->st) != STBA_OK ||
-            upload(pose_new, gp.data(), m * 7, b->st) != STBA_OK || upload(w_new, gw.data(), m * 36, b->st) != STBA_OK ||
-            hipStreamSynchronize(b->st) != hipSuccess)
-            return fail(STBA_ERR_HIP, who + ": upload failed");
-    }
-    // (nothing of the engine may still be reading the old priors or what was linearised with them: the moves below free them)
-    STBA_HIP(hipStreamSynchronize(b->st));
-    b->prior_ptr = std::move(ptr_new); b->prior_cam = std::move(cam_new); b->prior_pose = std::move(pose_new); b->prior_W = std::move(w_new);
-    b->n_prior = n; b->n_prior_groups = n_groups;
-    b->prior_order = std::move(order);
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    cov_store_free(b->cov);
-    b->cov = nullptr;
-    return STBA_OK;
-}
-
-int stba_ba_pose_prior_count(const stba_ba* b, int* n) {
-    if (!b || !n) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_pose_prior_count: null argument");
-    *n = b->n_prior;
-    return STBA_OK;
-}
-
-int stba_ba_pose_prior_kernel_geometry(const stba_ba* b, int* cameras_per_workgroup) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_pose_prior_kernel_geometry: null engine");
-    if (cameras_per_workgroup) *cameras_per_workgroup = PRIOR_CAMS_PER_WG;
-    return STBA_OK;
-}
-
-// the whitened residuals and Jacobians of the priors at the current parameters, by the block kernel itself (no blocks written),
-// and their cost by the cost kernel; the caller's order.  The engine's linearisation state is not touched
-int stba_ba_evaluate_pose_priors(stba_ba* b, double* cost, double* r, double* J) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_evaluate_pose_priors: null engine");
-    if (cost) *cost = 0.0;
-    if (!b->n_prior) return STBA_OK;
-    const size_t m = (size_t)b->n_prior;
-    DevBuf<double> dr, dj, dcost;
-    std::vector<double> hr, hj;
-    double c2 = 0.0;
-    if (r || J) {
-        STBA_TRY(dr.alloc(m * 6));
-        STBA_TRY(dj.alloc(m * 36));
-        STBA_TRY(launch_prior_blocks(b->prior_args(), b->cams[b->cur], nullptr, nullptr, dr, dj, b->st));
-        hr.resize(m * 6); hj.resize(m * 36);
-        STBA_TRY(download(hr.data(), dr, m * 6, b->st));
-        STBA_TRY(download(hj.data(), dj, m * 36, b->st));
-    }
-    if (cost) {
-        STBA_TRY(dcost.alloc(1));
-        STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[b->cur], dcost, b->st));
-        STBA_TRY(download(&c2, dcost, 1, b->st));
-    }
-    STBA_HIP(hipStreamSynchronize(b->st));
-    if (cost) *cost = 0.5 * c2;
-    for (size_t p = 0; p < m && (r || J); ++p) {
-        const size_t k = (size_t)b->prior_order[p];
-        if (r) memcpy(r + k * 6, &hr[p * 6], 6 * sizeof(double));
-        if (J) memcpy(J + k * 36, &hj[p * 36], 36 * sizeof(double));
-    }
-    return STBA_OK;
-}
-
-// ---- camera-to-camera relative-pose factors.  As with the priors everything is checked -- and, for the information
-// form, factored -- on the host BEFORE anything is replaced.  The edges stay in the caller's order; two stable sorts make the
-// references by camera and by unordered pair (inside a group the caller's order).  n == 0 releases everything: the engine then
-// enqueues exactly what one that never had edges enqueues
-int stba_ba_set_relative_poses(stba_ba* b, int n, const int* cam_i, const int* cam_j, const double* meas, const double* information,
-                               const double* sqrt_information) {
-    const std::string who = "stba_ba_set_relative_poses";
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
-    if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
-    if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
-    DevBuf<int> i_new, j_new, cgp_new, cgc_new, cgr_new, pgp_new, pgr_new;
-    DevBuf<int2> pgq_new;
-    DevBuf<double> meas_new, w_new;
-    int n_cg = 0, n_pg = 0;
-    if (n > 0) {
-        if (!cam_i || !cam_j || !meas) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null cam_i, cam_j or meas array");
-        if (b->iterative) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses ITERATIVE_SCHUR (its inexact-step model is summed from the observation records; relative-pose factors are not supported)");
-        if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine uses DOGLEG (DOGLEG with relative-pose factors is not supported)");
-        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has inner iterations (inner iterations with relative-pose factors are not supported)");
-        if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has a host lineariser (the factors need device residuals; not supported together)");
-        if (b->ar || b->world > 1) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": this engine has an all-reduce hook, and relative-pose factors run on one rank only");
-        const size_t m = (size_t)n;
-        std::vector<double> hm(m * 7), hw(m * 36);
-        for (size_t k = 0; k < m; ++k) {
-            const std::string at = who + ": edge " + std::to_string(k) + ": ";
-            for (int c : {cam_i[k], cam_j[k]})
-                if (c < 0 || c >= b->nc) return fail(STBA_ERR_INVALID_ARGUMENT, at + "camera index " + std::to_string(c) + " out of range");
-            if (cam_i[k] == cam_j[k]) return fail(STBA_ERR_INVALID_ARGUMENT, at + "cam_i == cam_j (" + std::to_string(cam_i[k]) + ")");
-            for (int j = 0; j < 7; ++j)
-                if (!std::isfinite(meas[k * 7 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the measurement has an entry that is not finite");
-            const double* q = meas + k * 7;
-            const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
-            if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(STBA_ERR_INVALID_ARGUMENT, at + "zero quaternion");
-            // (as the priors: a quaternion that is unit to rounding keeps its bits)
-            const double sc = std::fabs(n2 - 1.0) <= 8 * 2.220446049250313e-16 ? 1.0 : 1.0 / std::sqrt(n2);
-            for (int j = 0; j < 4; ++j) hm[k * 7 + j] = q[j] * sc;
-            for (int j = 4; j < 7; ++j) hm[k * 7 + j] = q[j];
-            if (sqrt_information) {
-                for (int j = 0; j < 36; ++j) {
-                    if (!std::isfinite(sqrt_information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the square-root information has an entry that is not finite");
-                    hw[k * 36 + j] = sqrt_information[k * 36 + j];
-                }
-            } else if (information) {
-                for (int j = 0; j < 36; ++j)
-                    if (!std::isfinite(information[k * 36 + j])) return fail(STBA_ERR_INVALID_ARGUMENT, at + "the information matrix has an entry that is not finite");
-                if (!prior_information_factor(information + k * 36, &hw[k * 36]))
-                    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, at + "the information matrix is not positive definite");
-            } else {
-                for (int j = 0; j < 36; ++j) hw[k * 36 + j] = (j % 7 == 0) ? 1.0 : 0.0;
-            }
-        }
-        // by camera: 2 n references (2 * edge + side), side 1 where the camera is the edge's j
-        std::vector<int> cref(2 * m);
-        for (size_t k = 0; k < 2 * m; ++k) cref[k] = (int)k;
-        auto cam_of = [cam_i, cam_j](int ref) { return (ref & 1) ? cam_j[ref >> 1] : cam_i[ref >> 1]; };
-        std::stable_sort(cref.begin(), cref.end(), [&](int x, int y) { return cam_of(x) < cam_of(y); });
-        std::vector<int> cgp, cgc;
-        for (size_t p = 0; p < 2 * m; ++p)
-            if (p == 0 || cam_of(cref[p]) != cgc.back()) { cgp.push_back((int)p); cgc.push_back(cam_of(cref[p])); }
-        cgp.push_back(2 * n);
-        n_cg = (int)cgc.size();
-        // by unordered pair (hi, lo): n references, side 1 where hi is the edge's j
-        std::vector<int> pref(m);
-        for (size_t k = 0; k < m; ++k) pref[k] = 2 * (int)k + (cam_j[k] > cam_i[k] ? 1 : 0);
-        auto pair_of = [cam_i, cam_j](int ref) { const int e = ref >> 1; return std::make_pair(std::max(cam_i[e], cam_j[e]), std::min(cam_i[e], cam_j[e])); };
-        std::stable_sort(pref.begin(), pref.end(), [&](int x, int y) { return pair_of(x) < pair_of(y); });
-        std::vector<int> pgp;
-        std::vector<int2> pgq;
-        for (size_t p = 0; p < m; ++p) {
-            const auto hl = pair_of(pref[p]);
-            if (p == 0 || hl.first != pgq.back().x || hl.second != pgq.back().y) { pgp.push_back((int)p); pgq.push_back(make_int2(hl.first, hl.second)); }
-        }
-        pgp.push_back(n);
-        n_pg = (int)pgq.size();
-        STBA_TRY(i_new.alloc(m)); STBA_TRY(j_new.alloc(m)); STBA_TRY(meas_new.alloc(m * 7)); STBA_TRY(w_new.alloc(m * 36));
-        STBA_TRY(cgp_new.alloc(cgp.size())); STBA_TRY(cgc_new.alloc(cgc.size())); STBA_TRY(cgr_new.alloc(cref.size()));
-        STBA_TRY(pgp_new.alloc(pgp.size())); STBA_TRY(pgq_new.alloc(pgq.size())); STBA_TRY(pgr_new.alloc(pref.size()));
-        if (upload(i_new, cam_i, m, b->st) != STBA_OK || upload(j_new, cam_j, m, b->st) != STBA_OK ||
-            upload(meas_new, hm.data(), m * 7, b->st) != STBA_OK || upload(w_new, hw.data(), m * 36, b->st) != STBA_OK ||
-            upload(cgp_new, cgp.data(), cgp.size(), b->st) != STBA_OK || upload(cgc_new, cgc.data(), cgc.size(), b->st) != STBA_OK ||
-            upload(cgr_new, cref.data(), cref.size(), b->st) != STBA_OK || upload(pgp_new, pgp.data(), pgp.size(), b->st) != STBA_OK ||
-            upload(pgq_new, pgq.data(), pgq.size(), b->st) != STBA_OK || upload(pgr_new, pref.data(), pref.size(), b->st) != STBA_OK ||
-            hipStreamSynchronize(b->st) != hipSuccess)
-            return fail(STBA_ERR_HIP, who + ": upload failed");
-    }
-    // (nothing of the engine may still be reading the old edges or what was linearised with them: the moves below free them)
-    STBA_HIP(hipStreamSynchronize(b->st));
-    b->btw_i = std::move(i_new); b->btw_j = std::move(j_new); b->btw_meas = std::move(meas_new); b->btw_W = std::move(w_new);
-    b->btw_cg_ptr = std::move(cgp_new); b->btw_cg_cam = std::move(cgc_new); b->btw_cg_ref = std::move(cgr_new);
-    b->btw_pg_ptr = std::move(pgp_new); b->btw_pg_pair = std::move(pgq_new); b->btw_pg_ref = std::move(pgr_new);
-    b->n_btw = n; b->n_btw_cg = n_cg; b->n_btw_pg = n_pg;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
-    cov_store_free(b->cov);
-    b->cov = nullptr;
-    return STBA_OK;
-}
-
-int stba_ba_relative_pose_count(const stba_ba* b, int* n) {
-    if (!b || !n) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_relative_pose_count: null argument");
-    *n = b->n_btw;
-    return STBA_OK;
-}
-
-int stba_ba_relative_pose_kernel_geometry(const stba_ba* b, int* groups_per_workgroup) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_relative_pose_kernel_geometry: null engine");
-    if (groups_per_workgroup) *groups_per_workgroup = BETWEEN_GROUPS_PER_WG;
-    return STBA_OK;
-}
-
-// the whitened residuals and Jacobians of the edges at the current parameters, by the pair groups of the block kernel itself (no
-// blocks written), and their cost by the cost kernel; the caller's order.  The engine's linearisation state is not touched
-int stba_ba_evaluate_relative_poses(stba_ba* b, double* cost, double* r, double* Ji, double* Jj) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_evaluate_relative_poses: null engine");
-    if (cost) *cost = 0.0;
-    if (!b->n_btw) return STBA_OK;
-    const size_t m = (size_t)b->n_btw;
-    DevBuf<double> dr, dji, djj, dcost;
-    double c2 = 0.0;
-    if (r || Ji || Jj) {
-        STBA_TRY(dr.alloc(m * 6)); STBA_TRY(dji.alloc(m * 36)); STBA_TRY(djj.alloc(m * 36));
-        STBA_TRY(launch_between_blocks(b->between_args(), b->cams[b->cur], nullptr, nullptr, nullptr, b->lda, dr, dji, djj, b->st));
-        if (r) STBA_TRY(download(r, dr, m * 6, b->st));
-        if (Ji) STBA_TRY(download(Ji, dji, m * 36, b->st));
-        if (Jj) STBA_TRY(download(Jj, djj, m * 36, b->st));
-    }
-    if (cost) {
-        STBA_TRY(dcost.alloc(1));
-        STBA_TRY(launch_between_cost(b->between_args(), b->cams[b->cur], dcost, b->st));
-        STBA_TRY(download(&c2, dcost, 1, b->st));
-    }
-    STBA_HIP(hipStreamSynchronize(b->st));
-    if (cost) *cost = 0.5 * c2;
-    return STBA_OK;
-}
-
-int stba_ba_has_loss(const stba_ba* b, int* has) {
-    if (!b || !has) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_has_loss: null argument");
-    *has = b->loss_kind ? 1 : 0;
-    return STBA_OK;
-}
-
-int stba_ba_loss_kernel_geometry(const stba_ba* b, int* tile_observations, int* cameras_in_lds, int* max_cameras_in_lds) {
-    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_loss_kernel_geometry: null engine");
-    if (tile_observations) *tile_observations = LIN_ROBUST_THREADS;
-    if (cameras_in_lds) *cameras_in_lds = lin_robust_cams_in_lds(b->nc) ? 1 : 0;
-    if (max_cameras_in_lds) *max_cameras_in_lds = (int)(((size_t)LIN_MAX_LDS - lin_robust_lds_bytes(0, true, true)) / (7 * sizeof(double)));
-    return STBA_OK;
-}
-
 int stba_ba_set_allreduce(stba_ba* b, stba_allreduce_fn fn, void* user, int rank, int world_size) {
-    STBA_TRY(refuse_iterative(b, "stba_ba_set_allreduce", "which runs on one rank only"));
-    if (b && b->trust_region == STBA_TR_TRADITIONAL_DOGLEG)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine uses DOGLEG, which runs on one rank only");
-    if (b && b->inner_on && (fn || world_size > 1))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has inner iterations, which run on one rank only");
-    if (b && b->loss_kind && (fn || world_size > 1))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has a loss table, and losses run on one rank only");
-    if (b && b->winfo && (fn || world_size > 1))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has information matrices, which run on one rank only");
-    if (b && b->n_prior && (fn || world_size > 1))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has pose priors, which run on one rank only");
-    if (b && b->n_btw && (fn || world_size > 1))
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: this engine has relative-pose factors, which run on one rank only");
+    if (b) STBA_TRY(ba_refuse(b, "stba_ba_set_allreduce", fn || world_size > 1));
     if (!b || world_size < 1 || rank < 0 || rank >= world_size || world_size > SC_MAX_WORLD)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: bad rank/world");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_allreduce: world_size > 1 needs a hook");
@@ -2306,7 +1696,7 @@ int stba_ba_apply_step(stba_ba* b, int accept, double* new_cost) {
     if (new_cost) *new_cost = 0.5 * ts[TS_COST2];
     if (accept) {
         b->cur ^= 1;
-        b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+        ba_invalidate(b);
     }
     return STBA_OK;
 }
@@ -2315,10 +1705,8 @@ int stba_ba_solve(stba_ba* b, const stba_lm_options* opt, stba_lm_summary* summa
                   stba_iteration_callback cb, void* cb_user) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     b->dl_sum = stba_dogleg_summary{};
-    if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) {
-        if (b->inner_on) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_solve: inner iterations are not supported with DOGLEG");
-        return ba_run_dogleg(b, opt, summary, trace, cb, cb_user);
-    }
+    STBA_TRY(ba_refuse(b, "stba_ba_solve"));
+    if (b->trust_region == STBA_TR_TRADITIONAL_DOGLEG) return ba_run_dogleg(b, opt, summary, trace, cb, cb_user);
     return ba_run_lm(b, opt, 0, summary, trace, cb, cb_user);
 }
 
@@ -2326,14 +1714,7 @@ int stba_ba_set_trust_region(stba_ba* b, int strategy) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (strategy != STBA_TR_LEVENBERG_MARQUARDT && strategy != STBA_TR_TRADITIONAL_DOGLEG)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: unknown strategy " + std::to_string(strategy));
-    if (strategy == STBA_TR_TRADITIONAL_DOGLEG) {
-        if (b->iterative)
-            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG only supports exact factorization based linear solvers "
-                        "(this engine uses ITERATIVE_SCHUR)");
-        if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: DOGLEG runs on one rank only (an all-reduce hook is set)");
-        if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: this engine has pose priors (DOGLEG with pose priors is not supported)");
-        if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_trust_region: this engine has relative-pose factors (DOGLEG with relative-pose factors is not supported)");
-    }
+    STBA_TRY(ba_refuse(b, "stba_ba_set_trust_region", strategy == STBA_TR_TRADITIONAL_DOGLEG));
     b->trust_region = strategy;
     return STBA_OK;
 }
@@ -2358,12 +1739,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     }
     if (!(tolerance >= 0.0) || !std::isfinite(tolerance))
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: the tolerance must be finite and >= 0");
-    if (b->ar) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: inner iterations run on one rank only (an all-reduce hook is set)");
-    if (b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: not with a host lineariser");
-    if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has a loss table (inner iterations with losses are not supported)");
-    if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has information matrices (inner iterations with information matrices are not supported)");
-    if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has pose priors (inner iterations with pose priors are not supported)");
-    if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: this engine has relative-pose factors (inner iterations with relative-pose factors are not supported)");
+    STBA_TRY(ba_refuse(b, "stba_ba_set_inner_iterations"));
     const int nc = b->nc, np = b->np, no = b->no;
     // constant parts, from the device's masks (cam_fixed: bit a = dof a constant)
     std::vector<unsigned char> cf((size_t)nc, 0), pf((size_t)np, 0);
@@ -2448,11 +1824,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
 
 int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int* iterations_per_block) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
-    if (b->ar || b->hl_fn) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: one rank, device residuals only");
-    if (b->loss_kind) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has a loss table (inner iterations with losses are not supported)");
-    if (b->winfo) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has information matrices (inner iterations with information matrices are not supported)");
-    if (b->n_prior) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has pose priors (inner iterations with pose priors are not supported)");
-    if (b->n_btw) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_inner_sweep: this engine has relative-pose factors (inner iterations with relative-pose factors are not supported)");
+    STBA_TRY(ba_refuse(b, "stba_ba_inner_sweep"));
     const bool was_on = b->inner_on;
     if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
     STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
@@ -2464,7 +1836,7 @@ int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int
     std::vector<int> it(ncl + npl);
     if (!it.empty()) STBA_TRY(download(it.data(), b->inner_it, it.size(), b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     inner_summary_reset(b);
     b->inner_sum.sweeps = 1;
     b->inner_on = was_on;
@@ -2503,7 +1875,7 @@ int stba_ba_triangulate(stba_ba* b, int max_iter) {
     STBA_TRY(launch_triangulate(b->np, b->pt_start, b->obs_cam, b->feat, b->cams[b->cur], b->pts[b->cur], b->pt_fixed,
                                 max_iter, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     return STBA_OK;
 }
 
@@ -2517,7 +1889,7 @@ int stba_ba_time_linearize(stba_ba* b, int reps, double* ms_avg) {
     float ms = 0.f;
     STBA_HIP(hipEventElapsedTime(&ms, b->ev[EV_LIN], b->ev[EV_LIN_END]));
     *ms_avg = (double)ms / reps;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     return STBA_OK;
 }
 
@@ -2542,7 +1914,7 @@ int stba_ba_time_schur(stba_ba* b, int reps, double* ms_avg, double* lds_atomics
     *ms_avg = (double)ms / reps;
     if (lds_atomics_per_launch) *lds_atomics_per_launch = b->schur_lds_atomics;
     if (pairs_per_launch) *pairs_per_launch = b->schur_pairs;
-    b->have_lin = b->have_blocks = b->have_reduced = b->have_dxc = b->have_dxp = false;
+    ba_invalidate(b);
     return STBA_OK;
 }
 
@@ -2550,8 +1922,7 @@ int stba_ba_covariance_compute(stba_ba* b, double min_rcond, double* rcond_out) 
     STBA_TRY(refuse_iterative(b, "stba_ba_covariance_compute", "and the covariance needs the explicit reduced system S"));
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (b->ar) return fail(STBA_ERR_STATE, "stba_ba_covariance_compute: the engine holds one landmark shard of several ranks; covariance needs one rank");
-    cov_store_free(b->cov);
-    b->cov = nullptr;
+    ba_drop_covariance(b);
     STBA_TRY(ba_cov_build(b));
     BaCovInputs in;
     in.nc = b->nc; in.np = b->np; in.no = b->no; in.n = b->n; in.lda = b->lda; in.st = b->st;
@@ -2587,8 +1958,7 @@ int stba_ba_point_pair_covariance(stba_ba* b, int n_pairs, const int* pt_a, cons
 
 int stba_ba_covariance_release(stba_ba* b) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
-    cov_store_free(b->cov);
-    b->cov = nullptr;
+    ba_drop_covariance(b);
     return STBA_OK;
 }
 
