@@ -544,7 +544,7 @@ private:
 // prior AT the camera's pose has the rotation residual exactly 0 in a build without FMA contraction), theta = 2 atan2(|v|, w) behind
 // the sign choice w >= 0 (q and -q: the same residual), the hat^2 coefficient (1 - (theta / 2) cot(theta / 2)) / theta^2 with
 // cot(theta / 2) = w / |v| (no 0 / 0 at pi), its series below 0.1 rad.
-// On a problem that otherwise takes "gpu-ba", DetectBa sets these blocks aside and Solve / Covariance hand them to the device engine
+// On a problem that otherwise takes "gpu-ba", the recognition (BaStructure) sets these blocks aside and Solve / Covariance hand them to the device engine
 // (stba_ba_set_pose_priors), provided the two blocks are the rotation and the position block of ONE camera that some observation
 // names and the block has no LossFunction; otherwise, and on every other route, it is an ordinary host cost function.  With
 // ITERATIVE_SCHUR, DOGLEG or use_inner_iterations the solve is refused (FAILURE, parameters untouched, the reason in the message).
@@ -629,7 +629,7 @@ private:
 // ambient: the quaternions' are the local ones (6 x 3, the device factor's under q <- q (x) exp(delta)) times P^+ = 4 P^T / |q|^2,
 // the left inverse of P = QuaternionRightPlus::ComputeJacobian(q), as PosePriorFactor's.  Same operations in the same order as the
 // device (slam-tricks_amd/csrc/ba_between.hpp): negating any of the three quaternions leaves the residual's bits.
-// On a problem that otherwise takes "gpu-ba", DetectBa sets these blocks aside and Solve / Covariance hand them to the device engine,
+// On a problem that otherwise takes "gpu-ba", the recognition (BaStructure) sets these blocks aside and Solve / Covariance hand them to the device engine,
 // provided the four blocks are the rotation and position blocks of two DISTINCT cameras that observations name and the block has no
 // LossFunction; otherwise, and on every other route, it is an ordinary host cost function.  With ITERATIVE_SCHUR, DOGLEG or
 // use_inner_iterations the solve is refused (FAILURE, parameters untouched, the reason in the message).
@@ -1118,7 +1118,7 @@ public:
         double initial_cost = 0, final_cost = 0;
         // Ceres' own timing fields: everything inside Solve() / in front of the minimiser / the minimiser / behind it
         double total_time_in_seconds = 0, preprocessor_time_in_seconds = 0, minimizer_time_in_seconds = 0, postprocessor_time_in_seconds = 0;
-        // (not in Ceres) where the host side of the drop-in spends its time, seconds: recognise = DetectBa (structure, probes, every
+        // (not in Ceres) where the host side of the drop-in spends its time, seconds: recognise = the recognition and the route decision (structure, probes, every
         // user block at its start point); pack = parameters and masks into the engine's arrays; engine_create = stba_*_create (regrouping,
         // Schur plan, uploads); device_solve = stba_*_solve; write_back = parameters back into the user's blocks; verify = every
         // recognised user block at the end point; resolve = a second solve with the user's own code, if the verification failed
@@ -1335,18 +1335,46 @@ template <class F> inline void ParallelRanges(size_t n, int threads, F fn) {
     for (auto& t : th) t.join();
 }
 
-// ---- path 1: every residual block is the reprojection factor (built-in or recognised) --------
-struct BaLayout {
-    // [n_obs] each, the residual blocks' losses as stba_ba_set_loss takes them (TRIVIAL, scale 1 for a block without one), in the
-    // order of the residual blocks, which is the order of obs_cam / obs_pt / feat; EMPTY if no block has a loss (BaLossTable)
+// ---- Problem -> layout: the tables both engines take, built the same way ----------------------
+// [n] each, the residual blocks' losses as stba_ba_set_loss / stba_pg_set_loss take them (TRIVIAL, scale 1 for a block without one), in
+// the order of the observations / edges; EMPTY if no block has a loss.  losses_known: every loss is a built-in (KnownLossRow)
+struct LossTable {
     std::vector<int> loss_kind;
     std::vector<double> loss_a, loss_b, loss_scale;
+    bool losses_known = true;
+};
+// the table of n blocks; block k is residual block res_of[k] (res_of EMPTY: residual block k)
+inline void FillLossTable(Problem& p, const std::vector<int>& res_of, size_t n, LossTable* t) {
+    t->loss_kind.clear(); t->loss_a.clear(); t->loss_b.clear(); t->loss_scale.clear();
+    t->losses_known = true;
+    if (p.NumLossFunctions() == 0) return;
+    for (size_t k = 0; k < n; ++k) {
+        const auto& r = p.residuals()[res_of.empty() ? k : (size_t)res_of[k]];
+        int kind = STBA_LOSS_TRIVIAL;
+        double a = 1.0, b = 1.0, scale = 1.0;
+        if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) t->losses_known = false;
+        t->loss_kind.push_back(kind); t->loss_a.push_back(a); t->loss_b.push_back(b); t->loss_scale.push_back(scale);
+    }
+}
+// row k of a per-block square-root-information table [n][dim x dim] (2 x 2: observations; 6 x 6: edges).  The table is EMPTY until
+// the first factor that has one: that makes it, with the identity in every other row
+inline void SetSqrtInfoRow(std::vector<double>* t, size_t n, int dim, size_t k, const double* w) {
+    const size_t sz = (size_t)dim * dim;
+    if (t->empty()) {
+        t->assign(n * sz, 0.0);
+        for (size_t i = 0; i < n; ++i) for (int a = 0; a < dim; ++a) (*t)[i * sz + (size_t)a * (dim + 1)] = 1.0;
+    }
+    std::memcpy(&(*t)[k * sz], w, sz * sizeof(double));
+}
+
+// ---- path 1: every residual block is the reprojection factor (built-in or recognised) --------
+struct BaLayout : LossTable {                // (the losses: per observation, the order of obs_cam / obs_pt / feat)
     std::vector<int> rot_block, pos_block;   // per camera: Problem block indices
     std::vector<int> pt_block;               // per landmark
     std::vector<int> obs_cam, obs_pt;
     std::vector<double> feat;
-    // [n_obs][4], the built-in factors' square-root information as stba_ba_set_sqrt_information takes it (the identity for a factor
-    // made without one), gathered next to feat; EMPTY if no factor has one
+    // [n_obs][4], the built-in factors' square-root information as stba_ba_set_sqrt_information takes it, gathered next to feat
+    // (SetSqrtInfoRow)
     std::vector<double> sqrt_info;
     std::vector<unsigned char> user;         // per residual block: 1 = a user cost function taken over (0: the built-in factor)
     size_t n_user = 0;
@@ -1362,8 +1390,9 @@ struct BaLayout {
     const Problem::Residual& res_of(Problem& p, size_t k) const { return p.residuals()[obs_res.empty() ? k : (size_t)obs_res[k]]; }
 };
 
-// every recognised USER block evaluated at the parameter values its blocks hold right now (before the solve: DetectBa; after it: Solve)
-inline bool VerifyRecognisedBlocks(Problem& p, const BaLayout& L, int threads) {
+// every user block at the parameter values its blocks hold right now, against the factor with the block's feature.  take_features
+// (L.feat's own storage): first take each block's feature, its residual at the canonical point; null: L.feat as it stands
+inline bool CheckUserBlocks(Problem& p, const BaLayout& L, int threads, double* take_features) {
     if (!L.n_user) return true;
     auto& blk = p.blocks();
     std::atomic<int> bad{0};
@@ -1371,46 +1400,33 @@ inline bool VerifyRecognisedBlocks(Problem& p, const BaLayout& L, int threads) {
         for (size_t k = lo; k < hi; ++k) {
             if (!L.user[k]) continue;
             const auto& r = L.res_of(p, k);
-            if (!ReprojectionValueAtData(r.cost, blk[r.blocks[0]].ptr, blk[r.blocks[1]].ptr, blk[r.blocks[2]].ptr, &L.feat[2 * k])) { bad.store(1); return; }
+            if ((take_features && !CanonicalFeature(r.cost, take_features + 2 * k)) ||
+                !ReprojectionValueAtData(r.cost, blk[r.blocks[0]].ptr, blk[r.blocks[1]].ptr, blk[r.blocks[2]].ptr, &L.feat[2 * k])) { bad.store(1); return; }
         }
     });
     return bad.load() == 0;
 }
+// the end-point check of Solve: every recognised USER block once more, where the solve ended
+inline bool VerifyRecognisedBlocks(Problem& p, const BaLayout& L, int threads) { return CheckUserBlocks(p, L, threads, nullptr); }
+// the PER-BLOCK half of the recognition: every user block's feature and its value at its own data.  10^6 blocks = 2 x 10^6 calls of the
+// user's Evaluate, on the calling thread (options.num_threads of them): the one part of the recognition that costs time -- Solve runs
+// it while a helper thread creates the device engine (BaRun::Create).
+inline bool DetectBaBlocks(Problem& p, BaLayout* L, int threads) { return CheckUserBlocks(p, *L, threads, L->feat.data()); }
 
-// the PER-BLOCK half of the recognition: every user block's feature (its residual at the canonical point) and its value at its own
-// data.  10^6 blocks = 2 x 10^6 calls of the user's Evaluate, on the calling thread (options.num_threads of them): the one part of the
-// recognition that costs time -- Solve runs it while a helper thread creates the device engine (SolveBa).
-inline bool DetectBaBlocks(Problem& p, BaLayout* L, int threads) {
-    auto& blk = p.blocks();
-    std::atomic<int> bad{0};
-    ParallelRanges(L->obs_cam.size(), threads, [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; ++k) {
-            if (!L->user[k]) continue;
-            const auto& r = L->res_of(p, k);
-            if (!CanonicalFeature(r.cost, &L->feat[2 * k]) ||
-                !ReprojectionValueAtData(r.cost, blk[r.blocks[0]].ptr, blk[r.blocks[1]].ptr, blk[r.blocks[2]].ptr, &L->feat[2 * k])) { bad.store(1); return; }
-        }
-    });
-    return bad.load() == 0;
-}
-
-// probe = false: only the SHAPE is required (blocks 4 / 3 / 3 -> 2 residuals, quaternion chart on the first block, no bounds);
-// the factor itself stays the user's (host-linearised path, see Solve) and L->feat is left at zero.
-// blocks_later = true: the structure and the per-TYPE probes only; the caller runs DetectBaBlocks itself.
-inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1, bool blocks_later = false) {
+// The STRUCTURE of a bundle adjustment, one pass, no Evaluate: every residual block {quaternion 4, position 3, landmark 3} -> 2 on
+// blocks that form cameras and landmarks (4 -> 3 chart on the rotation, no other chart, no bounds), PosePriorFactor and
+// CameraRelativePoseFactor blocks without a loss set aside.  The built-in factors' features and weights go to L; every other block is
+// marked `user`, the first of each C++ type listed in *user_types for the per-type probes.
+inline bool BaStructure(Problem& p, BaLayout* L, std::vector<const CostFunction*>* user_types) {
     auto& res = p.residuals();
     auto& blk = p.blocks();
     if (res.empty()) return false;
     const size_t nr = res.size();
-    // ---- structure: one pass, flat tables (block index -> camera / landmark)
     std::vector<int> cam_of_rot(blk.size(), -1), cam_of_pos(blk.size(), -1), pt_of(blk.size(), -1);
-    L->obs_cam.resize(nr); L->obs_pt.resize(nr); L->feat.assign(2 * nr, 0.0); L->user.assign(nr, 0); L->n_user = 0;
-    L->sqrt_info.clear();
-    L->prior_cam.clear(); L->obs_res.clear(); L->prior_pose.clear(); L->prior_w.clear();
-    L->rel_i.clear(); L->rel_j.clear(); L->rel_meas.clear(); L->rel_w.clear();
+    L->obs_cam.resize(nr); L->obs_pt.resize(nr); L->feat.assign(2 * nr, 0.0); L->user.assign(nr, 0);
     const std::type_info* last_type = nullptr;
     bool last_builtin = false;
-    std::vector<std::pair<const std::type_info*, const CostFunction*>> first_of_type;
+    std::vector<const std::type_info*> seen_types;
     // PosePriorFactor blocks are set aside (their residual block index and their two parameter blocks, resolved to a camera behind
     // the loop): from the first one on, observation k (the index of every per-observation array) is no longer residual block kr
     std::vector<size_t> prior_res, rel_res;          // (rel_res: CameraRelativePoseFactor blocks, the same way)
@@ -1418,40 +1434,32 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
     for (size_t kr = 0; kr < nr; ++kr) {
         const auto& r = res[kr];
         if (r.blocks.size() != 3 || !IsReprojectionShape(r.cost)) {
-            // (probe = false is the host-lineariser route, which has no priors: such a problem is not BA-shaped there, as before)
             const bool is_prior = r.blocks.size() == 2 && dynamic_cast<const PosePriorFactor*>(r.cost);
             const bool is_rel = r.blocks.size() == 4 && dynamic_cast<const CameraRelativePoseFactor*>(r.cost);
-            if (!probe || r.loss || !(is_prior || is_rel)) return false;
+            if (r.loss || !(is_prior || is_rel)) return false;
             if (prior_res.empty() && rel_res.empty()) { L->obs_res.resize(k); for (size_t i = 0; i < k; ++i) L->obs_res[i] = (int)i; }
             (is_prior ? prior_res : rel_res).push_back(kr);
             continue;
         }
         if (!prior_res.empty() || !rel_res.empty()) L->obs_res.push_back((int)kr);
-        if (probe) {
-            const std::type_info& ti = typeid(*r.cost);
-            if (!last_type || !(ti == *last_type)) {
-                last_type = &ti;
-                last_builtin = dynamic_cast<const ReprojectionFactor*>(r.cost) != nullptr;
-                bool seen = false;
-                for (auto& ft : first_of_type) seen = seen || (*ft.first == ti);
-                if (!seen) first_of_type.emplace_back(&ti, last_builtin ? nullptr : r.cost);
-            }
-            if (last_builtin) {
-                auto* f = static_cast<const ReprojectionFactor*>(r.cost); L->feat[2 * k] = f->fx(); L->feat[2 * k + 1] = f->fy();
-                if (const double* w = f->sqrt_information()) {
-                    if (L->sqrt_info.empty()) {                         // the first weighted factor: the identity for every other block
-                        L->sqrt_info.assign(4 * nr, 0.0);
-                        for (size_t i = 0; i < nr; ++i) L->sqrt_info[4 * i] = L->sqrt_info[4 * i + 3] = 1.0;
-                    }
-                    std::memcpy(&L->sqrt_info[4 * k], w, 4 * sizeof(double));
-                }
-            }
-            else { L->user[k] = 1; ++L->n_user; }
+        const std::type_info& ti = typeid(*r.cost);
+        if (!last_type || !(ti == *last_type)) {
+            last_type = &ti;
+            last_builtin = dynamic_cast<const ReprojectionFactor*>(r.cost) != nullptr;
+            bool seen = false;
+            for (auto* st : seen_types) seen = seen || (*st == ti);
+            if (!seen) { seen_types.push_back(&ti); if (!last_builtin) user_types->push_back(r.cost); }
         }
+        if (last_builtin) {
+            auto* f = static_cast<const ReprojectionFactor*>(r.cost); L->feat[2 * k] = f->fx(); L->feat[2 * k + 1] = f->fy();
+            // (a table of nr rows, filled at the observation index: cut to the observations below)
+            if (const double* w = f->sqrt_information()) SetSqrtInfoRow(&L->sqrt_info, nr, 2, k, w);
+        }
+        else { L->user[k] = 1; ++L->n_user; }
         const int b0 = r.blocks[0], b1 = r.blocks[1], b2 = r.blocks[2];
         const auto& rb = blk[b0];
         // a user LocalParameterization with the 4 -> 3 signature is accepted only if it IS the quaternion right-plus (checked
-        // numerically by the caller through UsesQuaternionRightPlus)
+        // numerically: UsesQuaternionRightPlus, Recognition::charts)
         if (!rb.local || rb.local->GlobalSize() != 4 || rb.local->LocalSize() != 3) return false;
         if (blk[b1].local || blk[b2].local) return false;
         if (!rb.lower.empty() || !blk[b1].lower.empty() || !blk[b2].lower.empty()) return false;
@@ -1469,10 +1477,7 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
         const size_t no = k;
         if (no == 0) return false;
         L->obs_cam.resize(no); L->obs_pt.resize(no); L->feat.resize(2 * no); L->user.resize(no);
-        if (!L->sqrt_info.empty()) {
-            // (filled at 4 * observation index, but made for nr rows with the identity: cut to the observations)
-            L->sqrt_info.resize(4 * no);
-        }
+        if (!L->sqrt_info.empty()) L->sqrt_info.resize(4 * no);
         for (size_t kr : prior_res) {
             // a prior's two blocks must be the rotation and the position block of ONE camera that some observation names
             const auto& r = res[kr];
@@ -1497,14 +1502,7 @@ inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1
     }
     for (size_t c = 0; c < L->rot_block.size(); ++c)                // a block cannot be a rotation AND a landmark / position
         if (pt_of[(size_t)L->rot_block[c]] >= 0 || pt_of[(size_t)L->pos_block[c]] >= 0 || cam_of_pos[(size_t)L->rot_block[c]] >= 0) return false;
-    if (!probe || !L->n_user) return true;
-    // ---- the user's own cost functions (test_ceres.h:111-121): accepted iff they ARE the reprojection factor
-    for (auto& ft : first_of_type) {
-        double f[2];
-        if (ft.second && (!ProbeReprojectionValue(ft.second, f) || !ProbeReprojectionJacobian(ft.second))) return false;
-    }
-    if (blocks_later) return true;
-    return DetectBaBlocks(p, L, threads);
+    return true;
 }
 
 // numerically confirms that a user-supplied 4->3 parameterisation is q (x) exp(delta)
@@ -1520,16 +1518,152 @@ inline bool UsesQuaternionRightPlus(const LocalParameterization* lp) {
     return true;
 }
 
-struct BaSync { stba_ba* ba; Problem* p; const BaLayout* L; std::vector<double> cams, pts; };
+// ---- path 3's layout: a pose graph ------------------------------------------------------------
+// every residual block a RelativePoseFactor on two distinct 7-double blocks with the SE3RightPlus chart and no bounds.  Nodes are
+// numbered in the order the residual blocks first name them.
+struct PoseGraphLayout : LossTable {       // (the losses: per edge)
+    std::map<int, int> node_of;            // parameter block index -> node
+    std::vector<int> node_block, ei, ej;   // node -> parameter block index; the edges
+    std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
+    std::vector<unsigned char> fixed;      // [n]
+    std::vector<double> sqrt_info;         // [m][36] the factors' W (SetSqrtInfoRow)
+};
+inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
+    const size_t m = p->residuals().size();
+    if (m == 0) return false;
+    for (size_t e = 0; e < m; ++e) {
+        const auto& r = p->residuals()[e];
+        auto* f = dynamic_cast<RelativePoseFactor*>(r.cost);
+        if (!f || r.blocks.size() != 2 || r.blocks[0] == r.blocks[1]) return false;
+        int ends[2];
+        for (int k = 0; k < 2; ++k) {
+            const auto& b = p->blocks()[r.blocks[k]];
+            if (b.size != 7 || !b.local || !dynamic_cast<SE3RightPlus*>(b.local) || !b.lower.empty()) return false;
+            auto it = L->node_of.find(r.blocks[k]);
+            if (it == L->node_of.end()) { ends[k] = (int)L->node_block.size(); L->node_of[r.blocks[k]] = ends[k]; L->node_block.push_back(r.blocks[k]); }
+            else ends[k] = it->second;
+        }
+        L->ei.push_back(ends[0]); L->ej.push_back(ends[1]);
+        L->meas.insert(L->meas.end(), f->measurement(), f->measurement() + 7);
+        if (f->sqrt_information()) SetSqrtInfoRow(&L->sqrt_info, m, 6, e, f->sqrt_information());
+    }
+    FillLossTable(*p, std::vector<int>(), m, L);
+    const int n = (int)L->node_block.size();
+    L->poses.assign((size_t)n * 7, 0.0);
+    L->fixed.assign((size_t)n, 0);
+    for (int k = 0; k < n; ++k) {
+        std::memcpy(&L->poses[(size_t)k * 7], p->blocks()[L->node_block[k]].ptr, 7 * sizeof(double));
+        L->fixed[k] = p->blocks()[L->node_block[k]].constant ? 1 : 0;
+    }
+    return true;
+}
+
+// ---- the recognition: what a Problem is, read ONCE per Solve / Covariance::Compute -------------
+// CONTRACT.  A user cost function is replaced by the built-in device factor if
+//   * the first block of its C++ type equals proj(conj(q)(L - t)) - feature at four generic probe points, one of them behind the
+//     camera (1e-12), and its Jacobian, composed with the chart, equals the closed form at a probe point (1e-9)  [Types()];
+//   * EVERY block equals the factor AT ITS OWN DATA -- the parameter values it holds when Solve is called (1e-11) -- with the
+//     feature it shows at the canonical point  [Blocks()], and once more at the point the solve ENDED at: a cost that departed from
+//     the factor on the way is solved again with its own code (SolveDispatch).
+// What remains unchecked is a cost that differs from the factor only at iterates in between; Solver::Options::force_callback_path
+// = true (or STBA_CERES_FORCE_CALLBACK=1 in the environment) keeps every block on the generic path, where the user's Evaluate is
+// what runs.  The summary's message names the number of blocks taken over.
+// NOTE for callers with IterationCallbacks: if the end-point check fails, the callbacks have already fired for the discarded
+// device solve and fire again for the second one (the summary's message says that a second solve ran; its iterations are the
+// ones reported, the time of both is in total_time_in_seconds, the first one's under phases.resolve's complement).
+//
+// The two halves that call the user's Evaluate are lazy and cached: Types() (six calls per C++ type) and Blocks() (two calls per
+// user block) run when a decision first needs them, at most once each, so no route calls Evaluate for an answer it does not use.
+struct Recognition {
+    Problem* problem = nullptr;
+    int threads = 1;
+    bool force_callback = false;     // force_callback_path or STBA_CERES_FORCE_CALLBACK: never take a user cost for the device factor
+    bool structure = false;          // BaStructure holds; `ba` is its layout (priors, relative poses, sqrt_info included)
+    bool charts = false;             // ... and every rotation block's chart is the quaternion right-plus
+    bool ba_losses = false;          // asked for, and: the device-factor reading holds, blocks included, and every loss is a built-in
+    bool is_pg = false;              // DetectPoseGraph holds; `pg` is its layout.  Looked at only where the BA structure does not hold
+    BaLayout ba;
+    PoseGraphLayout pg;
+    std::vector<const CostFunction*> user_types;
+    int types = -1, blocks = -1;     // the lazy halves: -1 not asked yet, 0 failed, 1 passed
+    bool dropped = false;            // the end-point check failed: the device-factor reading is off
+
+    bool Special() const { return !ba.prior_cam.empty() || !ba.rel_i.empty(); }
+    // the shape-only reading (blocks 4 / 3 / 3 -> 2, no prior or relative-pose block): the factor may stay the user's ("gpu-ba-hostjac")
+    bool ShapeRaw() const { return structure && !Special(); }
+    bool Shape() const { return ShapeRaw() && charts; }
+    bool Types() {
+        if (types < 0) {
+            types = 1;
+            double f[2];
+            for (auto* c : user_types) if (!ProbeReprojectionValue(c, f) || !ProbeReprojectionJacobian(c)) { types = 0; break; }
+        }
+        return types == 1;
+    }
+    bool Blocks() {
+        if (blocks < 0) blocks = DetectBaBlocks(*problem, &ba, threads) ? 1 : 0;
+        return blocks == 1;
+    }
+    // the device-factor reading ("gpu-ba"), as far as it has been checked: Blocks() may still be to come.  NOT a plain query: the
+    // first call that gets past the cheap conditions runs the per-type probes (Types(): the user's Evaluate)
+    bool Factor() { return !force_callback && !dropped && structure && charts && blocks != 0 && Types(); }
+    // `ba` as the shape-only reading hands it to the engine: no features, nothing taken over, no weights (the factors whiten themselves)
+    void MakeShapeOnly() {
+        std::fill(ba.feat.begin(), ba.feat.end(), 0.0); std::fill(ba.user.begin(), ba.user.end(), 0);
+        ba.n_user = 0; ba.sqrt_info.clear();
+    }
+};
+
+// the one parsing of the force-callback switch
+inline bool ForceCallbackPath(bool option) {
+    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
+    return option || (fe && *fe && *fe != '0');
+}
+
+// want_ba_losses: the caller would take built-in losses on "gpu-ba" -- then, on a problem that has losses, the whole device-factor
+// reading is checked here, blocks included, because the answer decides a refusal that comes before any device work
+inline void Recognise(Problem& p, bool force_callback, bool want_ba_losses, int threads, Recognition* r) {
+    r->problem = &p; r->threads = threads; r->force_callback = force_callback;
+    r->structure = BaStructure(p, &r->ba, &r->user_types);
+    if (!r->structure) { r->is_pg = DetectPoseGraph(&p, &r->pg); return; }
+    r->charts = true;
+    for (int rb : r->ba.rot_block) r->charts = r->charts && UsesQuaternionRightPlus(p.blocks()[rb].local);
+    if (!want_ba_losses || p.NumLossFunctions() == 0 || !r->Factor()) return;
+    FillLossTable(p, r->ba.obs_res, r->ba.obs_cam.size(), &r->ba);
+    r->ba_losses = r->ba.losses_known && r->Blocks();
+    if (!r->ba_losses) {        // (no table on any other route; losses_known keeps what was found)
+        r->ba.loss_kind.clear(); r->ba.loss_a.clear(); r->ba.loss_b.clear(); r->ba.loss_scale.clear();
+    }
+}
+
+// ---- the BA engine behind Solve and Covariance: pack, create, configure -----------------------
+// cameras [nc][7], landmarks [np][3] and the fixed masks ([nc][6]: rotation, position; [np]) as stba_ba_create takes them
+struct BaPacked { std::vector<double> cams, pts; std::vector<unsigned char> cam_fixed, pt_fixed; };
+inline void PackBa(Problem& p, const BaLayout& L, BaPacked* out) {
+    const size_t nc = L.rot_block.size(), np = L.pt_block.size();
+    out->cams.resize(nc * 7); out->pts.resize(np * 3); out->cam_fixed.assign(nc * 6, 0); out->pt_fixed.assign(np, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        const auto& rb = p.blocks()[L.rot_block[c]]; const auto& pb = p.blocks()[L.pos_block[c]];
+        std::memcpy(&out->cams[c * 7], rb.ptr, 4 * sizeof(double));
+        std::memcpy(&out->cams[c * 7 + 4], pb.ptr, 3 * sizeof(double));
+        for (int k = 0; k < 3; ++k) { out->cam_fixed[c * 6 + k] = rb.constant ? 1 : 0; out->cam_fixed[c * 6 + 3 + k] = pb.constant ? 1 : 0; }
+    }
+    for (size_t j = 0; j < np; ++j) {
+        std::memcpy(&out->pts[j * 3], p.blocks()[L.pt_block[j]].ptr, 3 * sizeof(double));
+        out->pt_fixed[j] = p.blocks()[L.pt_block[j]].constant ? 1 : 0;
+    }
+}
+// the engine's parameters back into the user's blocks (also the IterationCallbacks' sync_state)
+struct BaSync { stba_ba* ba; Problem* p; const BaLayout* L; BaPacked* x; };
 inline void BaCopyOut(void* user) {
     auto* s = static_cast<BaSync*>(user);
-    if (stba_ba_get_params(s->ba, s->cams.data(), s->pts.data()) != STBA_OK) return;
+    if (stba_ba_get_params(s->ba, s->x->cams.data(), s->x->pts.data()) != STBA_OK) return;
     for (size_t c = 0; c < s->L->rot_block.size(); ++c) {
-        std::memcpy(s->p->blocks()[s->L->rot_block[c]].ptr, &s->cams[c * 7], 4 * sizeof(double));
-        std::memcpy(s->p->blocks()[s->L->pos_block[c]].ptr, &s->cams[c * 7 + 4], 3 * sizeof(double));
+        std::memcpy(s->p->blocks()[s->L->rot_block[c]].ptr, &s->x->cams[c * 7], 4 * sizeof(double));
+        std::memcpy(s->p->blocks()[s->L->pos_block[c]].ptr, &s->x->cams[c * 7 + 4], 3 * sizeof(double));
     }
     for (size_t j = 0; j < s->L->pt_block.size(); ++j)
-        std::memcpy(s->p->blocks()[s->L->pt_block[j]].ptr, &s->pts[j * 3], 3 * sizeof(double));
+        std::memcpy(s->p->blocks()[s->L->pt_block[j]].ptr, &s->x->pts[j * 3], 3 * sizeof(double));
 }
 
 // host lineariser of the "gpu-ba-hostjac" path (stba_ba_set_host_linearizer): the user's cost functions, evaluated in bulk at
@@ -1570,10 +1704,6 @@ inline int BaHostLinearize(void* user, const double* cams, const double* pts, do
 
 inline double WallSeconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// blocks_layout / blocks_ok (round 6): the per-block half of the recognition is still to be done (DetectBa(..., blocks_later)): it runs
-// HERE, on the calling thread, while a helper thread creates the device engine (regrouping, Schur plan, uploads: ~50 ms at 10^6
-// observations, next to ~35 ms of user Evaluate calls); the features it finds go to the engine afterwards (stba_ba_set_features).
-// *blocks_ok = false: a block is not the reprojection factor -- nothing was solved, the engine is gone, the caller goes on.
 // the inner iterations' ordering in the engine's terms (stba_ba_set_inner_iterations): a group id per camera rotation, camera position
 // and landmark (-1: not swept), and the sizes of the groups used (constant blocks left out)
 struct InnerGroups {
@@ -1628,189 +1758,195 @@ inline bool MakeInnerGroups(const Solver::Options& o, Problem& p, const BaLayout
     return true;
 }
 
-// the per-observation loss table of a BA-shaped problem -> L (as DetectPoseGraph builds the per-edge one); false if a loss is not a
-// built-in (KnownLossRow)
-inline bool BaLossTable(Problem& p, BaLayout* L) {
-    L->loss_kind.clear(); L->loss_a.clear(); L->loss_b.clear(); L->loss_scale.clear();
-    if (p.NumLossFunctions() == 0) return true;
-    bool known = true;
-    const size_t no = L->obs_res.empty() ? p.residuals().size() : L->obs_res.size();      // (prior blocks carry no loss: DetectBa)
-    for (size_t k = 0; k < no; ++k) {
-        const auto& r = L->res_of(p, k);
-        int kind = STBA_LOSS_TRIVIAL;
-        double a = 1.0, b = 1.0, scale = 1.0;
-        if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) known = false;
-        L->loss_kind.push_back(kind); L->loss_a.push_back(a); L->loss_b.push_back(b); L->loss_scale.push_back(scale);
+// owns an engine handle: the one place that destroys it
+struct BaEngine {
+    stba_ba* h = nullptr;
+    BaEngine() = default;
+    BaEngine(const BaEngine&) = delete;
+    BaEngine& operator=(const BaEngine&) = delete;
+    ~BaEngine() { Reset(); }
+    void Reset() { if (h) stba_ba_destroy(h); h = nullptr; }
+};
+
+// stba_ba_create, or stba_ba_create_ex + stba_ba_set_pcg for ITERATIVE_SCHUR (solve null: Covariance, the direct solver).  false with
+// *error "call: text" -- the text taken here, on the thread that ran the call (stba_last_error is thread-local)
+inline bool CreateBa(const BaLayout& L, const BaPacked& x, const Solver::Options* solve, BaEngine* e, std::string* error) {
+    const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
+    int rc;
+    if (!solve || solve->linear_solver_type != ITERATIVE_SCHUR)
+        rc = stba_ba_create(&e->h, nc, np, no, x.cams.data(), x.pts.data(), L.obs_cam.data(), L.obs_pt.data(), L.feat.data(), x.cam_fixed.data(),
+                            x.pt_fixed.data(), nullptr);
+    else {
+        const Solver::Options& o = *solve;
+        stba_ba_create_options co;
+        co.struct_size = sizeof co;
+        co.linear_solver = STBA_LINEAR_ITERATIVE_SCHUR;
+        rc = stba_ba_create_ex(&e->h, nc, np, no, x.cams.data(), x.pts.data(), L.obs_cam.data(), L.obs_pt.data(), L.feat.data(),
+                               x.cam_fixed.data(), x.pt_fixed.data(), nullptr, &co);
+        const int pc = o.preconditioner_type == IDENTITY ? STBA_PRECOND_IDENTITY : o.preconditioner_type == JACOBI ? STBA_PRECOND_JACOBI
+                                                                                                                   : STBA_PRECOND_SCHUR_JACOBI;
+        if (rc == STBA_OK) rc = stba_ba_set_pcg(e->h, pc, o.eta, o.min_linear_solver_iterations, o.max_linear_solver_iterations, 4);
     }
-    return known;
-}
-// a problem with losses that, without them, takes "gpu-ba" -- every block the reprojection factor (the per-block half of the
-// recognition included), quaternion right-plus charts -- and whose losses are all built-ins; *L gets the layout and the table
-inline bool BaWithKnownLosses(Problem* problem, int threads, BaLayout* L) {
-    bool ba = DetectBa(*problem, L, true, threads);
-    if (ba) for (int rb : L->rot_block) ba = ba && UsesQuaternionRightPlus(problem->blocks()[rb].local);
-    return ba && BaLossTable(*problem, L);
+    if (rc == STBA_OK) return true;
+    *error = std::string("stba_ba_create: ") + stba_last_error();
+    e->Reset();
+    return false;
 }
 
-inline bool SolveBa(const Solver::Options& o, Problem* p, const BaLayout& L, Solver::Summary* sum, bool host_jacobians = false,
-                    BaLayout* blocks_layout = nullptr, bool* blocks_ok = nullptr, std::thread* destroyer = nullptr,
-                    const InnerGroups* inner = nullptr) {
-    double t0 = WallSeconds();
-    auto lap = [&](double* acc) { const double t1 = WallSeconds(); *acc += t1 - t0; t0 = t1; };
-    const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
-    const bool iterative = o.linear_solver_type == ITERATIVE_SCHUR;
-    if (iterative && o.preconditioner_type != IDENTITY && o.preconditioner_type != JACOBI && o.preconditioner_type != SCHUR_JACOBI) {
-        // (refused like a LossFunction: before any device work, parameters untouched)
-        sum->termination_type = FAILURE;
-        sum->message = "stba_ceres: ITERATIVE_SCHUR with the CLUSTER_JACOBI, CLUSTER_TRIDIAGONAL or SUBSET preconditioner is not implemented by "
-                       "this layer (IDENTITY, JACOBI and SCHUR_JACOBI are) -- nothing was solved.";
-        std::fprintf(stderr, "%s\n", sum->message.c_str());
-        return false;
-    }
-    BaSync sync{nullptr, p, &L, std::vector<double>((size_t)nc * 7), std::vector<double>((size_t)np * 3)};
-    std::vector<unsigned char> cam_fixed((size_t)nc * 6, 0), pt_fixed((size_t)np, 0);
-    for (int c = 0; c < nc; ++c) {
-        const auto& rb = p->blocks()[L.rot_block[c]]; const auto& pb = p->blocks()[L.pos_block[c]];
-        std::memcpy(&sync.cams[(size_t)c * 7], rb.ptr, 4 * sizeof(double));
-        std::memcpy(&sync.cams[(size_t)c * 7 + 4], pb.ptr, 3 * sizeof(double));
-        if (rb.constant) cam_fixed[c * 6] = cam_fixed[c * 6 + 1] = cam_fixed[c * 6 + 2] = 1;
-        if (pb.constant) cam_fixed[c * 6 + 3] = cam_fixed[c * 6 + 4] = cam_fixed[c * 6 + 5] = 1;
-    }
-    for (int j = 0; j < np; ++j) {
-        std::memcpy(&sync.pts[(size_t)j * 3], p->blocks()[L.pt_block[j]].ptr, 3 * sizeof(double));
-        pt_fixed[j] = p->blocks()[L.pt_block[j]].constant ? 1 : 0;
-    }
-    lap(&sum->phases.pack);
-    int rc = STBA_OK;
-    std::string create_error;
-    auto create = [&]() {
-        if (!iterative)
-            rc = stba_ba_create(&sync.ba, nc, np, no, sync.cams.data(), sync.pts.data(), L.obs_cam.data(), L.obs_pt.data(),
-                                L.feat.data(), cam_fixed.data(), pt_fixed.data(), nullptr);
-        else {
-            stba_ba_create_options co;
-            co.struct_size = sizeof co;
-            co.linear_solver = STBA_LINEAR_ITERATIVE_SCHUR;
-            rc = stba_ba_create_ex(&sync.ba, nc, np, no, sync.cams.data(), sync.pts.data(), L.obs_cam.data(), L.obs_pt.data(),
-                                   L.feat.data(), cam_fixed.data(), pt_fixed.data(), nullptr, &co);
-            const int pc = o.preconditioner_type == IDENTITY ? STBA_PRECOND_IDENTITY : o.preconditioner_type == JACOBI ? STBA_PRECOND_JACOBI
-                                                                                                                       : STBA_PRECOND_SCHUR_JACOBI;
-            if (rc == STBA_OK && (rc = stba_ba_set_pcg(sync.ba, pc, o.eta, o.min_linear_solver_iterations, o.max_linear_solver_iterations, 4)) != STBA_OK)
-                { create_error = stba_last_error(); stba_ba_destroy(sync.ba); sync.ba = nullptr; return; }
-        }
-        if (rc != STBA_OK) create_error = stba_last_error();      // (the error text is thread-local: taken where it was set)
-    };
-    int device = 0;
-    if (blocks_layout && !std::getenv("STBA_CERES_NO_OVERLAP") && stba_get_device(&device) == STBA_OK) {
-        // (the helper thread creates the engine from the layout as it stands -- the user blocks' features still zero: nothing reads
-        // them before the first linearisation; it starts on device 0 whatever this thread has selected, hence stba_set_device)
-        std::thread helper([&]() { if ((rc = stba_set_device(device)) != STBA_OK) create_error = stba_last_error(); else create(); });
-        JoinOnExit helper_guard{&helper};                           // (a user Evaluate that throws must not leave the thread running)
-        const double tb0 = WallSeconds();
-        const bool ok = DetectBaBlocks(*p, blocks_layout, o.num_threads);
-        const double t_blocks = WallSeconds() - tb0;
-        helper.join();
-        sum->phases.recognise += t_blocks;
-        t0 += t_blocks;                                             // (what is left of the creation's wall time goes to engine_create)
-        if (!ok) {
-            if (rc == STBA_OK) stba_ba_destroy(sync.ba);
-            lap(&sum->phases.engine_create);
-            if (blocks_ok) *blocks_ok = false;
-            return false;
-        }
-        if (rc == STBA_OK && (rc = stba_ba_set_features(sync.ba, L.feat.data())) != STBA_OK) { create_error = stba_last_error(); stba_ba_destroy(sync.ba); }
-    } else {
-        if (blocks_layout && !DetectBaBlocks(*p, blocks_layout, o.num_threads)) { if (blocks_ok) *blocks_ok = false; lap(&sum->phases.recognise); return false; }
-        if (blocks_layout) lap(&sum->phases.recognise);
-        create();
-    }
-    lap(&sum->phases.engine_create);
-    if (rc != STBA_OK) { sum->termination_type = FAILURE; sum->message = std::string("stba_ba_create: ") + create_error; return false; }
+// what ConfigureBa hands to an engine besides the layout's own tables
+struct BaSetup {
+    bool losses;                       // the layout's loss table (Covariance with apply_loss_function = false: not)
+    BaHostCtx* host;                   // "gpu-ba-hostjac": the user's cost functions as the engine's lineariser; null: device factors
+    const Solver::Options* solve;      // Solve: the trust-region strategy; null: Covariance
+    const InnerGroups* inner;          // Solve with inner iterations; null: none
+};
+// The layout's sqrt_info, losses, relative poses, priors and the host lineariser to the engine, then Solve's trust region and inner
+// iterations.  Returns the NAME of the first call that failed (its text: stba_last_error()), or null.  One order for Solve and
+// Covariance: relative poses before priors, so that an engine that takes neither (ITERATIVE_SCHUR) names the relative poses.
+inline const char* ConfigureBa(stba_ba* ba, const BaLayout& L, const BaSetup& s) {
     // (weighted ReprojectionFactors; with host Jacobians the factors whiten themselves)
-    if (!host_jacobians && !L.sqrt_info.empty() && (rc = stba_ba_set_sqrt_information(sync.ba, L.sqrt_info.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_sqrt_information: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
+    if (!s.host && !L.sqrt_info.empty() && stba_ba_set_sqrt_information(ba, L.sqrt_info.data()) != STBA_OK) return "stba_ba_set_sqrt_information";
+    if (s.losses && !L.loss_kind.empty() && stba_ba_set_loss(ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
+        return "stba_ba_set_loss";
+    // (PosePriorFactor / CameraRelativePoseFactor blocks: the engine refuses them on an ITERATIVE_SCHUR engine here -- before any solve,
+    // the parameters untouched, the engine's reason in the message; DOGLEG and inner iterations are refused by DecideSolve)
+    if (!L.rel_i.empty() && stba_ba_set_relative_poses(ba, (int)L.rel_i.size(), L.rel_i.data(), L.rel_j.data(), L.rel_meas.data(), nullptr,
+                                                       L.rel_w.data()) != STBA_OK) return "stba_ba_set_relative_poses";
+    if (!L.prior_cam.empty() && stba_ba_set_pose_priors(ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
+                                                        L.prior_w.data()) != STBA_OK) return "stba_ba_set_pose_priors";
+    if (s.host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, s.host) != STBA_OK) return "stba_ba_set_host_linearizer";
+    if (s.solve && s.solve->trust_region_strategy_type == DOGLEG && stba_ba_set_trust_region(ba, STBA_TR_TRADITIONAL_DOGLEG) != STBA_OK)
+        return "stba_ba_set_trust_region";
+    if (s.inner && stba_ba_set_inner_iterations(ba, 1, s.solve->inner_iteration_tolerance, s.inner->rot.data(), s.inner->pos.data(),
+                                                s.inner->pt.data()) != STBA_OK) return "stba_ba_set_inner_iterations";
+    return nullptr;
+}
+
+// ---- one "gpu-ba" / "gpu-ba-hostjac" solve: named steps over one state -----------------------
+struct BaRun {
+    const Solver::Options& o;
+    Problem* p;
+    Recognition* rec;                  // its `ba` is the layout
+    Solver::Summary* sum;
+    bool host_jacobians = false;       // "gpu-ba-hostjac"
+    const InnerGroups* inner = nullptr;   // null: no inner iterations
+    bool blocks_failed = false;        // Create(): the per-block half of the recognition said no -- nothing was solved, the caller goes on
+    BaPacked x;
+    BaEngine engine;
+    BaSync sync{nullptr, nullptr, nullptr, nullptr};
+    BaHostCtx host{nullptr, nullptr, 1};
+    std::thread destroyer;             // Destroy(): frees the engine next to the caller's end-point check; joined with this object
+    double t0 = WallSeconds();
+
+    BaRun(const Solver::Options& options, Problem* problem, Recognition* recognition, Solver::Summary* summary)
+        : o(options), p(problem), rec(recognition), sum(summary) {}
+    ~BaRun() { if (destroyer.joinable()) destroyer.join(); }
+    const BaLayout& L() const { return rec->ba; }
+    void Lap(double* acc) { const double t1 = WallSeconds(); *acc += t1 - t0; t0 = t1; }
+    bool Fail(const std::string& message) { sum->termination_type = FAILURE; sum->message = message; return false; }
+
+    void Pack() { PackBa(*p, L(), &x); Lap(&sum->phases.pack); }
+
+    // With user blocks whose per-block check is still to come (Recognition::blocks < 0) that check runs HERE, on the calling thread,
+    // while a helper thread creates the device engine (regrouping, Schur plan, uploads: ~50 ms at 10^6 observations, next to ~35 ms of
+    // user Evaluate calls); the features it finds go to the engine afterwards (stba_ba_set_features).
+    bool Create() {
+        std::string error;
+        bool ok = false;
+        const bool check_blocks = L().n_user && rec->blocks < 0;
+        int device = 0;
+        if (check_blocks && !std::getenv("STBA_CERES_NO_OVERLAP") && stba_get_device(&device) == STBA_OK) {
+            // (the helper thread creates the engine from the layout as it stands.  stba_ba_create READS L.feat while Blocks() writes the
+            // user blocks' entries: a data race in the letter of the language, harmless in effect -- whatever the upload saw of those
+            // entries is replaced by stba_ba_set_features below before anything is linearised.  Removing it needs a second n_obs-sized
+            // array or another C ABI.  The thread starts on device 0 whatever this thread has selected, hence stba_set_device)
+            std::thread helper([&]() {
+                if (stba_set_device(device) != STBA_OK) error = std::string("stba_ba_create: ") + stba_last_error();
+                else ok = CreateBa(L(), x, &o, &engine, &error);
+            });
+            JoinOnExit helper_guard{&helper};                           // (a user Evaluate that throws must not leave the thread running)
+            const double tb0 = WallSeconds();
+            const bool blocks_ok = rec->Blocks();
+            const double t_blocks = WallSeconds() - tb0;
+            helper.join();
+            sum->phases.recognise += t_blocks;
+            t0 += t_blocks;                                             // (what is left of the creation's wall time goes to engine_create)
+            if (!blocks_ok) { engine.Reset(); Lap(&sum->phases.engine_create); blocks_failed = true; return false; }
+            if (ok && stba_ba_set_features(engine.h, L().feat.data()) != STBA_OK) { ok = false; error = std::string("stba_ba_create: ") + stba_last_error(); }
+        } else {
+            if (check_blocks) {
+                const bool blocks_ok = rec->Blocks();
+                Lap(&sum->phases.recognise);
+                if (!blocks_ok) { blocks_failed = true; return false; }
+            }
+            ok = CreateBa(L(), x, &o, &engine, &error);
+        }
+        Lap(&sum->phases.engine_create);
+        return ok || Fail(error);
     }
-    if (!L.loss_kind.empty() && (rc = stba_ba_set_loss(sync.ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_loss: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
+
+    bool Configure() {
+        host = BaHostCtx{p, &L(), o.num_threads};
+        const BaSetup setup{true, host_jacobians ? &host : nullptr, &o, inner};
+        const char* failed = ConfigureBa(engine.h, L(), setup);
+        if (!failed) return true;
+        // (the one message with a gloss of its own, kept as it always read)
+        const bool rel = std::strcmp(failed, "stba_ba_set_relative_poses") == 0;
+        return Fail(std::string(failed) + (rel ? " (relative pose factors): " : ": ") + stba_last_error());
     }
-    // (PosePriorFactor blocks: the engine refuses them on an ITERATIVE_SCHUR engine here, and DOGLEG / inner iterations below refuse
-    // an engine that holds them -- each before any solve, the parameters untouched, the engine's reason in the message)
-    // (CameraRelativePoseFactor blocks: refused the same way; handed over first, so that a problem with both kinds names these)
-    if (!L.rel_i.empty() && (rc = stba_ba_set_relative_poses(sync.ba, (int)L.rel_i.size(), L.rel_i.data(), L.rel_j.data(), L.rel_meas.data(), nullptr,
-                                                             L.rel_w.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_relative_poses (relative pose factors): ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
-    }
-    if (!L.prior_cam.empty() && (rc = stba_ba_set_pose_priors(sync.ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
-                                                              L.prior_w.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_pose_priors: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
-    }
-    BaHostCtx hctx{p, &L, o.num_threads};
-    if (host_jacobians && (rc = stba_ba_set_host_linearizer(sync.ba, &BaHostLinearize, &hctx)) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_host_linearizer: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
-    }
-    const bool dogleg = o.trust_region_strategy_type == DOGLEG;
-    if (dogleg && (rc = stba_ba_set_trust_region(sync.ba, STBA_TR_TRADITIONAL_DOGLEG)) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_trust_region: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
-    }
-    if (inner && (rc = stba_ba_set_inner_iterations(sync.ba, 1, o.inner_iteration_tolerance, inner->rot.data(), inner->pos.data(),
-                                                    inner->pt.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_ba_set_inner_iterations: ") + stba_last_error();
-        stba_ba_destroy(sync.ba);
-        return false;
-    }
-    stba_lm_options co = ToC(o);
-    if (inner) co.phase_timing = 1;          // (the sweeps' device time for Summary::inner_iteration_time_in_seconds)
-    stba_lm_summary cs;
-    std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
-    CallbackCtx ctx{&o, sum, &BaCopyOut, &sync};
-    rc = stba_ba_solve(sync.ba, &co, &cs, trace.data(), o.callbacks.empty() ? nullptr : &IterationTrampoline, &ctx);
-    lap(&sum->phases.device_solve);
-    if (rc == STBA_OK) {
+
+    bool Solve() {
+        stba_lm_options co = ToC(o);
+        if (inner) co.phase_timing = 1;          // (the sweeps' device time for Summary::inner_iteration_time_in_seconds)
+        stba_lm_summary cs;
+        std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
+        sync = BaSync{engine.h, p, &L(), &x};
+        CallbackCtx ctx{&o, sum, &BaCopyOut, &sync};
+        const int rc = stba_ba_solve(engine.h, &co, &cs, trace.data(), o.callbacks.empty() ? nullptr : &IterationTrampoline, &ctx);
+        Lap(&sum->phases.device_solve);
+        if (rc != STBA_OK) return Fail(std::string("stba_ba_solve: ") + stba_last_error());
         BaCopyOut(&sync);   // parameters are updated in place, like ceres::Solve
         FillSummary(cs, trace, sum);
-        if (dogleg) { sum->trust_region_strategy_type = DOGLEG; sum->dogleg_type = TRADITIONAL_DOGLEG; }
+        if (o.trust_region_strategy_type == DOGLEG) { sum->trust_region_strategy_type = DOGLEG; sum->dogleg_type = TRADITIONAL_DOGLEG; }
         stba_inner_summary is{};
         is.struct_size = sizeof is;
-        if (inner && stba_ba_last_inner_summary(sync.ba, &is) == STBA_OK) {
+        if (inner && stba_ba_last_inner_summary(engine.h, &is) == STBA_OK) {
             sum->inner_iterations_used = true;
             sum->inner_iteration_ordering_used = inner->sizes_used;
             sum->num_inner_iteration_steps = is.sweeps;
             sum->inner_iteration_time_in_seconds = is.sweep_ms * 1e-3;
         }
-        if (iterative) {
+        if (o.linear_solver_type == ITERATIVE_SCHUR) {
             sum->linear_solver_type_used = ITERATIVE_SCHUR;
             std::vector<int> its((size_t)cs.num_iterations, 0);
-            if (cs.num_iterations > 0 && stba_ba_last_pcg_iterations(sync.ba, its.data(), cs.num_iterations) == STBA_OK)
+            if (cs.num_iterations > 0 && stba_ba_last_pcg_iterations(engine.h, its.data(), cs.num_iterations) == STBA_OK)
                 for (int i = 1; i <= cs.num_iterations && i < (int)sum->iterations.size(); ++i) sum->iterations[(size_t)i].linear_solver_iterations = its[(size_t)i - 1];
         }
         if (ctx.user_abort) sum->termination_type = USER_FAILURE;
         if (ctx.user_success) sum->termination_type = USER_SUCCESS;
-    } else {
-        sum->termination_type = FAILURE;
-        sum->message = std::string("stba_ba_solve: ") + stba_last_error();
+        return true;
     }
-    // (the engine's ~40 device buffers take a few ms to free: with `destroyer` that happens on a helper thread, next to the caller's
-    // end-point check of the recognised blocks; the caller joins it)
-    int dev_now = 0;
-    if (destroyer && stba_get_device(&dev_now) == STBA_OK) {
-        stba_ba* engine = sync.ba;
-        *destroyer = std::thread([engine, dev_now]() { if (stba_set_device(dev_now) == STBA_OK) stba_ba_destroy(engine); });
-    } else stba_ba_destroy(sync.ba);
-    lap(&sum->phases.write_back);
-    return rc == STBA_OK;
-}
+
+    // (the engine's ~40 device buffers take a few ms to free: where user blocks were taken over that happens on a helper thread, next
+    // to the caller's end-point check of those blocks)
+    void Destroy() {
+        int dev_now = 0;
+        if (L().n_user && !host_jacobians && stba_get_device(&dev_now) == STBA_OK) {
+            BaEngine* e = &engine;
+            destroyer = std::thread([e, dev_now]() { if (stba_set_device(dev_now) == STBA_OK) e->Reset(); });
+        } else engine.Reset();
+        Lap(&sum->phases.write_back);
+    }
+
+    // false: nothing was solved (the summary says why, or blocks_failed)
+    bool Run() {
+        Pack();
+        if (!Create() || !Configure()) return false;
+        const bool ok = Solve();
+        Destroy();
+        return ok;
+    }
+};
 
 // ---- path 2: generic residual blocks through the host-callback dense path -------------------
 struct DenseCtx {
@@ -1952,300 +2088,247 @@ inline bool SolveDense(const Solver::Options& o, Problem* p, Solver::Summary* su
 }
 
 // ---- path 3: pose graph on the device engine (stba_pg_*) -------------------------------------
-// returns false WITHOUT touching the summary if the problem is not a pose graph of built-in factors
-// the recognition, shared by Solve and Covariance: every residual block a RelativePoseFactor on two distinct 7-double blocks with the
-// SE3RightPlus chart and no bounds.  Nodes are numbered in the order the residual blocks first name them.
-struct PoseGraphLayout {
-    std::map<int, int> node_of;            // parameter block index -> node
-    std::vector<int> node_block, ei, ej;   // node -> parameter block index; the edges
-    std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
-    std::vector<unsigned char> fixed;      // [n]
-    std::vector<double> sqrt_info;         // [m][36] the factors' W, the identity for a factor without one; EMPTY if no factor has one
-    // [m] each, the residual blocks' losses as stba_pg_set_loss takes them (TRIVIAL, scale 1 for a block without one); EMPTY if no
-    // block has a loss.  losses_known: every loss is a built-in (KnownLossRow)
-    std::vector<int> loss_kind;
-    std::vector<double> loss_a, loss_b, loss_scale;
-    bool losses_known = true;
+// owns an engine handle: the one place that destroys it
+struct PgEngine {
+    stba_pg* h = nullptr;
+    PgEngine() = default;
+    PgEngine(const PgEngine&) = delete;
+    PgEngine& operator=(const PgEngine&) = delete;
+    ~PgEngine() { if (h) stba_pg_destroy(h); }
 };
-inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
-    if (p->residuals().empty()) return false;
-    auto& node_of = L->node_of;
-    auto& node_block = L->node_block; auto& ei = L->ei; auto& ej = L->ej;
-    auto& meas = L->meas;
-    for (auto& r : p->residuals()) {
-        auto* f = dynamic_cast<RelativePoseFactor*>(r.cost);
-        if (!f || r.blocks.size() != 2 || r.blocks[0] == r.blocks[1]) return false;
-        int ends[2];
-        for (int k = 0; k < 2; ++k) {
-            const auto& b = p->blocks()[r.blocks[k]];
-            if (b.size != 7 || !b.local || !dynamic_cast<SE3RightPlus*>(b.local) || !b.lower.empty()) return false;
-            auto it = node_of.find(r.blocks[k]);
-            if (it == node_of.end()) { ends[k] = (int)node_block.size(); node_of[r.blocks[k]] = ends[k]; node_block.push_back(r.blocks[k]); }
-            else ends[k] = it->second;
-        }
-        ei.push_back(ends[0]); ej.push_back(ends[1]);
-        meas.insert(meas.end(), f->measurement(), f->measurement() + 7);
-        if (f->sqrt_information() && L->sqrt_info.empty()) {       // the first weighted factor: identity for every edge before it
-            L->sqrt_info.assign(ei.size() * 36, 0.0);
-            for (size_t e = 0; e < ei.size(); ++e) for (int a = 0; a < 6; ++a) L->sqrt_info[e * 36 + a * 7] = 1.0;
-            std::memcpy(&L->sqrt_info[(ei.size() - 1) * 36], f->sqrt_information(), 36 * sizeof(double));
-        } else if (!L->sqrt_info.empty()) {
-            const size_t at = L->sqrt_info.size();
-            L->sqrt_info.resize(at + 36, 0.0);
-            if (f->sqrt_information()) std::memcpy(&L->sqrt_info[at], f->sqrt_information(), 36 * sizeof(double));
-            else for (int a = 0; a < 6; ++a) L->sqrt_info[at + a * 7] = 1.0;
-        }
-        if (r.loss && L->loss_kind.empty()) {                       // the first block with a loss: no loss for every edge before it
-            L->loss_kind.assign(ei.size() - 1, STBA_LOSS_TRIVIAL);
-            L->loss_a.assign(ei.size() - 1, 1.0); L->loss_b.assign(ei.size() - 1, 1.0); L->loss_scale.assign(ei.size() - 1, 1.0);
-        }
-        if (r.loss || !L->loss_kind.empty()) {
-            int kind = STBA_LOSS_TRIVIAL;
-            double a = 1.0, b = 1.0, scale = 1.0;
-            if (r.loss && !KnownLossRow(r.loss, &kind, &a, &b, &scale)) L->losses_known = false;
-            L->loss_kind.push_back(kind); L->loss_a.push_back(a); L->loss_b.push_back(b); L->loss_scale.push_back(scale);
-        }
-    }
-    const int n = (int)node_block.size();
-    L->poses.assign((size_t)n * 7, 0.0);
-    L->fixed.assign((size_t)n, 0);
-    for (int k = 0; k < n; ++k) {
-        std::memcpy(&L->poses[(size_t)k * 7], p->blocks()[node_block[k]].ptr, 7 * sizeof(double));
-        L->fixed[k] = p->blocks()[node_block[k]].constant ? 1 : 0;
-    }
-    return true;
+// create, then the layout's sqrt_info and (losses: not for Covariance with apply_loss_function = false) loss table.  Returns the NAME
+// of the first call that failed (its text: stba_last_error()), or null
+inline const char* CreatePg(const PoseGraphLayout& L, bool losses, PgEngine* e) {
+    if (stba_pg_create(&e->h, (int)L.node_block.size(), (int)L.ei.size(), L.poses.data(), L.ei.data(), L.ej.data(), L.meas.data(), L.fixed.data(),
+                       nullptr) != STBA_OK) return "stba_pg_create";
+    if (!L.sqrt_info.empty() && stba_pg_set_sqrt_information(e->h, L.sqrt_info.data()) != STBA_OK) return "stba_pg_set_sqrt_information";
+    if (losses && !L.loss_kind.empty() && stba_pg_set_loss(e->h, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
+        return "stba_pg_set_loss";
+    return nullptr;
 }
-inline bool SolvePoseGraph(const Solver::Options& o, Problem* p, Solver::Summary* sum) {
-    PoseGraphLayout L;
-    if (!DetectPoseGraph(p, &L)) return false;
-    auto& node_block = L.node_block; auto& ei = L.ei; auto& ej = L.ej;
-    auto& meas = L.meas; auto& poses = L.poses; auto& fixed = L.fixed;
-    const int n = (int)node_block.size(), m = (int)ei.size();
-    sum->execution_path = "gpu-pg";
-    stba_pg* pg = nullptr;
-    int rc = stba_pg_create(&pg, n, m, poses.data(), ei.data(), ej.data(), meas.data(), fixed.data(), nullptr);
-    if (rc != STBA_OK) { sum->termination_type = FAILURE; sum->message = std::string("stba_pg_create: ") + stba_last_error(); return true; }
-    if (!L.sqrt_info.empty() && (rc = stba_pg_set_sqrt_information(pg, L.sqrt_info.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_pg_set_sqrt_information: ") + stba_last_error();
-        stba_pg_destroy(pg);
-        return true;
-    }
-    if (!L.loss_kind.empty() && (rc = stba_pg_set_loss(pg, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data())) != STBA_OK) {
-        sum->termination_type = FAILURE; sum->message = std::string("stba_pg_set_loss: ") + stba_last_error();
-        stba_pg_destroy(pg);
-        return true;
-    }
+inline void SolvePoseGraph(const Solver::Options& o, Problem* p, PoseGraphLayout& L, Solver::Summary* sum) {
+    const int n = (int)L.node_block.size();
+    PgEngine pg;
+    if (const char* failed = CreatePg(L, true, &pg)) { sum->termination_type = FAILURE; sum->message = std::string(failed) + ": " + stba_last_error(); return; }
     stba_lm_options co = ToC(o);
     stba_lm_summary cs;
     std::vector<double> trace((size_t)(o.max_num_iterations + 1) * STBA_TRACE_COLS, 0.0);
     int pcg_total = 0;
-    rc = stba_pg_solve(pg, &co, nullptr, &cs, trace.data(), &pcg_total);
-    if (rc == STBA_OK) rc = stba_pg_get_poses(pg, poses.data());
+    int rc = stba_pg_solve(pg.h, &co, nullptr, &cs, trace.data(), &pcg_total);
+    if (rc == STBA_OK) rc = stba_pg_get_poses(pg.h, L.poses.data());
     if (rc == STBA_OK) {
-        for (int k = 0; k < n; ++k) std::memcpy(p->blocks()[node_block[k]].ptr, &poses[(size_t)k * 7], 7 * sizeof(double));
+        for (int k = 0; k < n; ++k) std::memcpy(p->blocks()[L.node_block[k]].ptr, &L.poses[(size_t)k * 7], 7 * sizeof(double));
         FillSummary(cs, trace, sum);
     } else {
         sum->termination_type = FAILURE;
         sum->message = std::string("stba_pg_solve: ") + stba_last_error();
     }
-    stba_pg_destroy(pg);
-    return true;
 }
 
-}  // namespace internal
+// ---- the route decision ------------------------------------------------------------------------
+// Where a recognised problem goes.  Solve: "gpu-ba", "gpu-ba-hostjac", "gpu-pg", "gpu-dense-callback"; Covariance: the same with
+// "gpu-dense" for the last.
+enum class Route { BA, BA_HOSTJAC, PG, DENSE };
+// pg_allowed: Solve takes "gpu-pg" only without a forced callback path and without IterationCallbacks.  blocks_now: the per-block half
+// of the device-factor reading is settled here (Covariance; Solve's inner iterations), not next to the engine's creation.
+// Picking may RUN the recognition's lazy halves (Factor() -> Types(), and Blocks() with blocks_now): the user's Evaluate is called
+// here the first time, and not again.
+inline Route PickRoute(Recognition& r, bool pg_allowed, bool blocks_now) {
+    if (r.Factor() && (!blocks_now || r.Blocks())) return Route::BA;
+    if (pg_allowed && r.is_pg) return Route::PG;
+    return r.Shape() ? Route::BA_HOSTJAC : Route::DENSE;
+}
 
-namespace internal {
-// a problem with losses is let through only if it is a pose graph (DetectPoseGraph) and every loss is a built-in; Solve asks in
-// addition for what SolveDispatch asks before it calls SolvePoseGraph: no forced callback path, no iteration callbacks
-inline bool PoseGraphWithKnownLosses(Problem* problem) {
-    PoseGraphLayout G;
-    return DetectPoseGraph(problem, &G) && G.losses_known;
-}
-inline bool LossesGoToPoseGraph(const Solver::Options& options, Problem* problem) {
-    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
-    if (options.force_callback_path || (fe && *fe && *fe != '0') || !options.callbacks.empty()) return false;
-    return PoseGraphWithKnownLosses(problem);
-}
-// Solver::Options::bundle_adjustment_losses: the problem, without its losses, takes "gpu-ba" and every loss is a built-in
-inline bool LossesGoToBa(const Solver::Options& options, Problem* problem) {
-    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
-    if (!options.bundle_adjustment_losses || options.force_callback_path || (fe && *fe && *fe != '0') || options.use_inner_iterations) return false;
-    BaLayout L;
-    return BaWithKnownLosses(problem, options.num_threads, &L);
-}
-inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
-    const bool ba_losses = problem->NumLossFunctions() > 0 && !LossesGoToPoseGraph(options, problem) && LossesGoToBa(options, problem);
-    if (problem->NumLossFunctions() > 0 && !ba_losses && !LossesGoToPoseGraph(options, problem)) {
-        // (Ceres would apply the loss; outside the pose-graph route this layer has none to apply -- a solve without it would be a
-        // silently different problem)
-        summary->termination_type = FAILURE;
-        summary->message = "stba_ceres: " + std::to_string(problem->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are "
-                           "not implemented by this layer (the reference passes nullptr: test_ceres.h:120) -- nothing was solved.";
-        std::fprintf(stderr, "%s\n", summary->message.c_str());
-        return;
-    }
-    if (options.trust_region_strategy_type == DOGLEG) {
-        // (refused like a LossFunction: before any device work, parameters untouched)
-        const char* why = nullptr;
-        BaLayout shape_only;
-        if (options.dogleg_type != TRADITIONAL_DOGLEG) why = "SUBSPACE_DOGLEG is not implemented by this layer (TRADITIONAL_DOGLEG is)";
-        else if (options.linear_solver_type == ITERATIVE_SCHUR) why = "DOGLEG only supports exact factorization based linear solvers, not ITERATIVE_SCHUR";
-        else if (!DetectBa(*problem, &shape_only, false)) {
-            BaLayout with_priors;
-            const bool special = DetectBa(*problem, &with_priors, true, 1, true);
-            if (special && !with_priors.rel_i.empty())
-                why = "DOGLEG with CameraRelativePoseFactor (relative pose) blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)";
-            else if (special && !with_priors.prior_cam.empty())
-                why = "DOGLEG with PosePriorFactor blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)";
-            else
-                why = "DOGLEG is implemented for bundle adjustment (gpu-ba, gpu-ba-hostjac) only, not for problems that take gpu-pg or gpu-dense-callback";
-        }
-        if (why) {
-            summary->termination_type = FAILURE;
-            summary->message = std::string("stba_ceres: ") + why + " -- nothing was solved.";
-            std::fprintf(stderr, "%s\n", summary->message.c_str());
-            return;
+// Solve's decision: a route, or the first refusal in the order LossFunction, DOGLEG, inner iterations, preconditioner -- each before
+// any device work, the parameters untouched.  `why` is the refusal's text (empty: go); each text stands here and nowhere else.
+struct Decision {
+    enum Stage { GO, LOSS, DOGLEG_STAGE, INNER, PRECONDITIONER } stage = GO;
+    Route route = Route::DENSE;        // set with GO and with PRECONDITIONER (the route that would have run)
+    std::string why;
+    Decision& Refuse(Stage s, const std::string& text) { stage = s; why = text; return *this; }
+};
+// inner: with use_inner_iterations and no refusal, the ordering in the engine's terms.
+// A function of (options, recognition) in its RESULT, not free of effects: the recognition is mutable because deciding is what first
+// asks for Types() and Blocks(), which call the user's Evaluate and cache the answer.  The order of the short-circuits below is
+// therefore what fixes how often Evaluate runs -- e.g. `r.Special() && r.Types()` probes only a problem that has prior / relative-pose
+// blocks, and the preconditioner is refused without the per-block half -- and tests/test_*ceres_routes*.py hold the counts.
+inline Decision DecideSolve(const Solver::Options& o, Recognition& r, InnerGroups* inner) {
+    Decision d;
+    Problem& p = *r.problem;
+    const bool pg_allowed = !r.force_callback && o.callbacks.empty();
+    const bool dogleg = o.trust_region_strategy_type == DOGLEG, iterative = o.linear_solver_type == ITERATIVE_SCHUR;
+    // (Ceres would apply the loss; this layer has one to apply on "gpu-pg", and on "gpu-ba" where asked to -- a solve without it would
+    // be a silently different problem)
+    if (p.NumLossFunctions() > 0 && !r.ba_losses && !(pg_allowed && r.is_pg && r.pg.losses_known))
+        return d.Refuse(Decision::LOSS, std::to_string(p.NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are "
+                                        "not implemented by this layer (the reference passes nullptr: test_ceres.h:120)");
+    if (dogleg) {
+        if (o.dogleg_type != TRADITIONAL_DOGLEG) return d.Refuse(Decision::DOGLEG_STAGE, "SUBSPACE_DOGLEG is not implemented by this layer (TRADITIONAL_DOGLEG is)");
+        if (iterative) return d.Refuse(Decision::DOGLEG_STAGE, "DOGLEG only supports exact factorization based linear solvers, not ITERATIVE_SCHUR");
+        if (!r.ShapeRaw()) {
+            const bool special = r.structure && r.Types();
+            return d.Refuse(Decision::DOGLEG_STAGE,
+                special && !r.ba.rel_i.empty() ? "DOGLEG with CameraRelativePoseFactor (relative pose) blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)"
+                : special && !r.ba.prior_cam.empty() ? "DOGLEG with PosePriorFactor blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)"
+                : "DOGLEG is implemented for bundle adjustment (gpu-ba, gpu-ba-hostjac) only, not for problems that take gpu-pg or gpu-dense-callback");
         }
     }
-    const char* fe = std::getenv("STBA_CERES_FORCE_CALLBACK");
-    const bool force_cb = options.force_callback_path || (fe && *fe && *fe != '0');
-    summary->inner_iterations_given = options.use_inner_iterations;
-    InnerGroups inner;
-    if (options.use_inner_iterations) {
-        // (refused like a LossFunction: before any device work, parameters untouched)
+    if (o.use_inner_iterations) {
         std::string why;
-        BaLayout shape_only;
-        bool shape = DetectBa(*problem, &shape_only, false);
-        if (shape)
-            for (int rb : shape_only.rot_block) shape = shape && UsesQuaternionRightPlus(problem->blocks()[rb].local);
-        BaLayout with_priors;
-        if (options.trust_region_strategy_type == DOGLEG) why = "inner iterations are not implemented with DOGLEG";
-        else if (!(options.inner_iteration_tolerance >= 0.0)) why = "inner_iteration_tolerance must be >= 0";
-        else if (!shape && DetectBa(*problem, &with_priors, true, 1, true) && !(with_priors.prior_cam.empty() && with_priors.rel_i.empty()))
-            why = !with_priors.rel_i.empty() ? "inner iterations with CameraRelativePoseFactor (relative pose) blocks are not implemented"
-                                             : "inner iterations with PosePriorFactor blocks are not implemented";
-        else if (!shape)
+        if (dogleg) why = "inner iterations are not implemented with DOGLEG";
+        else if (!(o.inner_iteration_tolerance >= 0.0)) why = "inner_iteration_tolerance must be >= 0";
+        else if (!r.Shape() && r.structure && r.Special() && r.Types())
+            why = !r.ba.rel_i.empty() ? "inner iterations with CameraRelativePoseFactor (relative pose) blocks are not implemented"
+                                      : "inner iterations with PosePriorFactor blocks are not implemented";
+        else if (!r.Shape())
             why = "inner iterations are implemented for bundle adjustment on the gpu-ba path only, not for problems that take gpu-pg or gpu-dense-callback";
-        else if (force_cb) why = "inner iterations are implemented on the gpu-ba path only, not on gpu-ba-hostjac (force_callback_path)";
-        else MakeInnerGroups(options, *problem, shape_only, &inner, &why);
-        if (options.inner_iteration_ordering)
-            for (const auto& g : options.inner_iteration_ordering->group_to_elements()) summary->inner_iteration_ordering_given.push_back((int)g.second.size());
-        if (!why.empty()) {
-            summary->termination_type = FAILURE;
-            summary->message = "stba_ceres: " + why + " -- nothing was solved.";
-            std::fprintf(stderr, "%s\n", summary->message.c_str());
-            return;
-        }
-    }
-    BaLayout L;
-    // CONTRACT of the recognition (DetectBa): a user cost function is replaced by the built-in device factor if
-    //   * the first block of its C++ type equals proj(conj(q)(L - t)) - feature at four generic probe points, one of them behind the
-    //     camera (1e-12), and its Jacobian, composed with the chart, equals the closed form at a probe point (1e-9);
-    //   * EVERY block equals the factor AT ITS OWN DATA -- the parameter values it holds when Solve is called (1e-11) -- with the
-    //     feature it shows at the canonical point, and once more at the point the solve ENDED at: a cost that departed from the
-    //     factor on the way is solved again with its own code (below).
-    // What remains unchecked is a cost that differs from the factor only at iterates in between; Solver::Options::force_callback_path
-    // = true (or STBA_CERES_FORCE_CALLBACK=1 in the environment) keeps every block on the generic path, where the user's Evaluate is
-    // what runs.  The summary's message names the number of blocks taken over.
-    // NOTE for callers with IterationCallbacks: if the end-point check fails, the callbacks have already fired for the discarded
-    // device solve and fire again for the second one (the summary's message says that a second solve ran; its iterations are the
-    // ones reported, the time of both is in total_time_in_seconds, the first one's under phases.resolve's complement).
-    double t0 = WallSeconds();
-    bool ba = !force_cb && DetectBa(*problem, &L, true, options.num_threads, true);      // (the per-block half: inside SolveBa)
-    if (ba)
-        for (int rb : L.rot_block) ba = ba && UsesQuaternionRightPlus(problem->blocks()[rb].local);
-    if (ba && ba_losses) BaLossTable(*problem, &L);
-    summary->phases.recognise = WallSeconds() - t0;
-    if (options.use_inner_iterations) {
+        else if (r.force_callback) why = "inner iterations are implemented on the gpu-ba path only, not on gpu-ba-hostjac (force_callback_path)";
+        else if (!MakeInnerGroups(o, p, r.ba, inner, &why)) {}
         // (gpu-ba only: every block must be the reprojection factor -- the per-block half of the recognition runs here, before any
         // device work, instead of next to the engine's creation)
-        std::string why;
-        t0 = WallSeconds();
-        if (!ba || (L.n_user && !DetectBaBlocks(*problem, &L, options.num_threads)))
+        else if (PickRoute(r, false, true) != Route::BA)
             why = "inner iterations are implemented on the gpu-ba path only: this problem's cost functions are not the reprojection factor "
                   "(gpu-ba-hostjac)";
-        else if (!L.sqrt_info.empty())
-            why = "inner iterations with weighted ReprojectionFactors (sqrt_information) are not implemented";
-        else if (!MakeInnerGroups(options, *problem, L, &inner, &why)) {}
-        summary->phases.recognise += WallSeconds() - t0;
-        if (!why.empty()) {
-            summary->termination_type = FAILURE;
-            summary->message = "stba_ceres: " + why + " -- nothing was solved.";
-            std::fprintf(stderr, "%s\n", summary->message.c_str());
-            return;
-        }
+        else if (!r.ba.sqrt_info.empty()) why = "inner iterations with weighted ReprojectionFactors (sqrt_information) are not implemented";
+        if (!why.empty()) return d.Refuse(Decision::INNER, why);
     }
+    d.route = PickRoute(r, pg_allowed, false);
+    const bool ba_engine = d.route == Route::BA || d.route == Route::BA_HOSTJAC;
+    if (ba_engine && iterative && o.preconditioner_type != IDENTITY && o.preconditioner_type != JACOBI && o.preconditioner_type != SCHUR_JACOBI)
+        return d.Refuse(Decision::PRECONDITIONER, "ITERATIVE_SCHUR with the CLUSTER_JACOBI, CLUSTER_TRIDIAGONAL or SUBSET preconditioner is not implemented by "
+                                                  "this layer (IDENTITY, JACOBI and SCHUR_JACOBI are)");
+    return d;
+}
+
+// refused before any device work: FAILURE, the reason in the message and on stderr
+inline void Refuse(Solver::Summary* summary, const std::string& why) {
+    summary->termination_type = FAILURE;
+    summary->message = "stba_ceres: " + why + " -- nothing was solved.";
+    std::fprintf(stderr, "%s\n", summary->message.c_str());
+}
+inline const char* RouteName(Route route) {
+    return route == Route::BA ? "gpu-ba" : route == Route::BA_HOSTJAC ? "gpu-ba-hostjac" : route == Route::PG ? "gpu-pg" : "gpu-dense-callback";
+}
+inline void NoteRecognisedBlocks(size_t n_user, Solver::Summary* summary) {
+    if (n_user) summary->message += (summary->message.empty() ? "" : " ") + std::to_string(n_user) +
+                                    " user cost functions recognised as the reprojection factor (probe points, start point, end point) and evaluated by the device kernel.";
+}
+
+inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
+    double t0 = WallSeconds();
+    Recognition r;
+    Recognise(*problem, ForceCallbackPath(options.force_callback_path), options.bundle_adjustment_losses && !options.use_inner_iterations,
+              options.num_threads, &r);
+    InnerGroups inner;
+    Decision d = DecideSolve(options, r, &inner);
+    summary->phases.recognise = WallSeconds() - t0;
+    if (d.stage != Decision::LOSS && d.stage != Decision::DOGLEG_STAGE) {
+        summary->inner_iterations_given = options.use_inner_iterations;
+        if (options.use_inner_iterations && options.inner_iteration_ordering)
+            for (const auto& g : options.inner_iteration_ordering->group_to_elements()) summary->inner_iteration_ordering_given.push_back((int)g.second.size());
+    }
+    // (a preconditioner is refused by the BA route it would have run on: the summary names that route, and the blocks taken over)
+    auto refused = [&](const Decision& dd) {
+        if (dd.stage == Decision::GO) return false;
+        if (dd.stage == Decision::PRECONDITIONER) summary->execution_path = RouteName(dd.route);
+        Refuse(summary, dd.why);
+        if (dd.stage == Decision::PRECONDITIONER && dd.route == Route::BA) NoteRecognisedBlocks(r.ba.n_user, summary);
+        return true;
+    };
+    if (refused(d)) return;
     std::string carried;
-    std::vector<double> saved;
-    bool still_factor = true;
-    if (ba) {
-        if (L.n_user) for (auto& b : problem->blocks()) saved.insert(saved.end(), b.ptr, b.ptr + b.size);
-        summary->execution_path = "gpu-ba";
-        bool blocks_ok = true;
-        std::thread destroyer;
-        JoinOnExit destroyer_guard{&destroyer};
-        if (options.use_inner_iterations)      // (the blocks were checked above)
-            SolveBa(options, problem, L, summary, false, nullptr, &blocks_ok, L.n_user ? &destroyer : nullptr, &inner);
-        else
-            SolveBa(options, problem, L, summary, false, L.n_user ? &L : nullptr, &blocks_ok, L.n_user ? &destroyer : nullptr);
-        if (!blocks_ok) { ba = false; summary->execution_path.clear(); }       // a block is not the factor: on to the other paths, nothing was touched
-        t0 = WallSeconds();
-        still_factor = !ba || summary->termination_type == FAILURE || VerifyRecognisedBlocks(*problem, L, options.num_threads);
-        if (destroyer.joinable()) destroyer.join();
-        if (ba) summary->phases.verify = WallSeconds() - t0;
-    }
-    if (ba) {
-        const bool still = still_factor;
-        if (still) {
-            if (L.n_user) summary->message += (summary->message.empty() ? "" : " ") + std::to_string(L.n_user) +
-                                              " user cost functions recognised as the reprojection factor (probe points, start point, end point) and evaluated by the device kernel.";
-            return;
-        }
-        size_t o = 0;
-        for (auto& b : problem->blocks()) { std::copy(saved.begin() + o, saved.begin() + o + b.size, b.ptr); o += (size_t)b.size; }
-        if (ba_losses) {
-            // (the second solve would take gpu-ba-hostjac, which has no losses: refused, the parameters as they were)
+    if (d.route == Route::BA) {
+        std::vector<double> saved;
+        if (r.ba.n_user) for (auto& b : problem->blocks()) saved.insert(saved.end(), b.ptr, b.ptr + b.size);
+        summary->execution_path = RouteName(Route::BA);
+        BaRun run(options, problem, &r, summary);
+        if (options.use_inner_iterations) run.inner = &inner;
+        run.Run();
+        if (run.blocks_failed) {
+            // a block is not the factor: on to the other routes, nothing was touched
+            summary->execution_path.clear();
+            d = DecideSolve(options, r, &inner);
+        } else {
+            t0 = WallSeconds();
+            const bool still_factor = summary->termination_type == FAILURE || VerifyRecognisedBlocks(*problem, r.ba, options.num_threads);
+            if (run.destroyer.joinable()) run.destroyer.join();
+            summary->phases.verify = WallSeconds() - t0;
+            if (still_factor) { NoteRecognisedBlocks(r.ba.n_user, summary); return; }
+            size_t at = 0;
+            for (auto& b : problem->blocks()) { std::copy(saved.begin() + at, saved.begin() + at + b.size, b.ptr); at += (size_t)b.size; }
+            if (r.ba_losses) {
+                // (the second solve would take gpu-ba-hostjac, which has no losses: refused, the parameters as they were)
+                *summary = Solver::Summary();
+                Refuse(summary, "a user cost function taken for the reprojection factor differs from it at the solution, and robust losses are "
+                                "not implemented on the gpu-ba-hostjac path (LossFunction)");
+                return;
+            }
+            const Solver::Summary::Phases first = summary->phases;
+            const std::vector<int> given = summary->inner_iteration_ordering_given;
             *summary = Solver::Summary();
-            summary->termination_type = FAILURE;
-            summary->message = "stba_ceres: a user cost function taken for the reprojection factor differs from it at the solution, and robust losses are "
-                               "not implemented on the gpu-ba-hostjac path (LossFunction) -- nothing was solved.";
-            std::fprintf(stderr, "%s\n", summary->message.c_str());
-            return;
+            summary->phases = first;
+            carried = "a user cost function taken for the reprojection factor differs from it at the solution: solved again with the user's Evaluate.";
+            if (options.use_inner_iterations) {
+                // (the second solve takes gpu-ba-hostjac, which has no inner iterations: it runs without them)
+                summary->inner_iterations_given = true;
+                summary->inner_iteration_ordering_given = given;
+                carried += " The second solve ran without inner iterations (gpu-ba-hostjac has none).";
+            }
+            // the one re-reading: the recognition as it stands, with the device-factor reading struck out
+            r.dropped = true;
+            Solver::Options again = options;
+            again.use_inner_iterations = false;
+            d = DecideSolve(again, r, &inner);
         }
-        const Solver::Summary::Phases first = summary->phases;
-        const std::vector<int> given = summary->inner_iteration_ordering_given;
-        *summary = Solver::Summary();
-        summary->phases = first;
-        carried = "a user cost function taken for the reprojection factor differs from it at the solution: solved again with the user's Evaluate.";
-        if (options.use_inner_iterations) {
-            // (the second solve takes gpu-ba-hostjac, which has no inner iterations: it runs without them)
-            summary->inner_iterations_given = true;
-            summary->inner_iteration_ordering_given = given;
-            carried += " The second solve ran without inner iterations (gpu-ba-hostjac has none).";
-        }
+        if (refused(d)) return;
     }
     const double t_resolve = WallSeconds();
-    // a pose graph: every residual block a RelativePoseFactor between two 7-double pose blocks with the SE3 right-plus chart
-    if (!force_cb && options.callbacks.empty() && SolvePoseGraph(options, problem, summary)) return;
-    // BA-SHAPED, but not (or not to be taken for) the built-in factor: every residual block is {quaternion 4, position 3,
-    // landmark 3} -> 2 with the quaternion right-plus chart.  The user's cost functions are evaluated on the host, in bulk, into
-    // the device engine's residual / Jacobian buffers, and the Schur complement, the factorisation, the back-substitution and the
-    // LM loop run on the device as for the built-in factor ("gpu-ba-hostjac"): any size the engine takes, where the dense
-    // callback path below stops at 4096 local parameters.  (The reference's BA cost IS a generic functor: test_ceres.h:56.)
-    BaLayout L2;
-    bool shape = DetectBa(*problem, &L2, false);
-    if (shape)
-        for (int rb : L2.rot_block) shape = shape && UsesQuaternionRightPlus(problem->blocks()[rb].local);
-    if (shape) {
-        summary->execution_path = "gpu-ba-hostjac";
-        Solver::Summary::Phases ph = summary->phases;
-        Solver::Options o2 = options;
-        o2.use_inner_iterations = false;           // (only the end-point re-solve gets here with inner iterations asked for)
-        SolveBa(o2, problem, L2, summary, true);
+    summary->execution_path = RouteName(d.route);
+    if (d.route == Route::PG) {
+        // a pose graph: every residual block a RelativePoseFactor between two 7-double pose blocks with the SE3 right-plus chart
+        SolvePoseGraph(options, problem, r.pg, summary);
+    } else if (d.route == Route::BA_HOSTJAC) {
+        // BA-SHAPED, but not (or not to be taken for) the built-in factor: every residual block is {quaternion 4, position 3,
+        // landmark 3} -> 2 with the quaternion right-plus chart.  The user's cost functions are evaluated on the host, in bulk, into
+        // the device engine's residual / Jacobian buffers, and the Schur complement, the factorisation, the back-substitution and the
+        // LM loop run on the device as for the built-in factor: any size the engine takes, where the dense callback path stops at
+        // 4096 local parameters.  (The reference's BA cost IS a generic functor: test_ceres.h:56.)
+        r.MakeShapeOnly();
+        const Solver::Summary::Phases ph = summary->phases;
+        BaRun run(options, problem, &r, summary);
+        run.host_jacobians = true;
+        run.Run();
         if (!carried.empty()) { summary->phases = ph; summary->phases.resolve = WallSeconds() - t_resolve; }
-    }
-    else { summary->execution_path = "gpu-dense-callback"; SolveDense(options, problem, summary); }
+    } else SolveDense(options, problem, summary);
     if (!carried.empty()) summary->message = carried + (summary->message.empty() ? "" : " ") + summary->message;
+}
+
+// ---- the recognition under the names the C++ tests drive it by (tests/cpp/*_shim.cpp); nothing in this header calls these -----
+// probe = false: the shape-only reading, L->feat left at zero
+inline bool DetectBa(Problem& p, BaLayout* L, bool probe = true, int threads = 1) {
+    Recognition r;
+    Recognise(p, false, false, threads, &r);
+    const bool ok = probe ? r.structure && r.Types() && r.Blocks() : r.ShapeRaw();
+    if (!probe) r.MakeShapeOnly();
+    *L = std::move(r.ba);
+    return ok;
+}
+inline bool BaWithKnownLosses(Problem* problem, int threads, BaLayout* L) {
+    Recognition r;
+    Recognise(*problem, false, true, threads, &r);
+    const bool ok = problem->NumLossFunctions() > 0 ? r.ba_losses : r.Factor() && r.Blocks();
+    *L = std::move(r.ba);
+    return ok;
+}
+inline bool LossesGoToPoseGraph(const Solver::Options& options, Problem* problem) {
+    Recognition r;
+    Recognise(*problem, ForceCallbackPath(options.force_callback_path), false, options.num_threads, &r);
+    return !r.force_callback && options.callbacks.empty() && r.is_pg && r.pg.losses_known;
+}
+inline bool LossesGoToBa(const Solver::Options& options, Problem* problem) {
+    BaLayout L;
+    return options.bundle_adjustment_losses && !options.use_inner_iterations && !ForceCallbackPath(options.force_callback_path) &&
+           BaWithKnownLosses(problem, options.num_threads, &L);
 }
 }  // namespace internal
 
@@ -2350,15 +2433,25 @@ private:
         tangent_[{b, a}] = std::move(tt);
     }
 
-    bool ComputeImpl(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p) {
-        using namespace internal;
-        BaLayout LL;
-        const bool ba_losses = p->NumLossFunctions() > 0 && options_.bundle_adjustment_losses && BaWithKnownLosses(p, options_.num_threads, &LL);
-        if (p->NumLossFunctions() > 0 && !ba_losses && !PoseGraphWithKnownLosses(p))
-            return Fail(std::to_string(p->NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are not implemented by this layer -- no covariance computed");
+    using Pairs = std::vector<std::pair<const double*, const double*>>;
+    using BlockIndex = std::unordered_map<const double*, int>;
+
+    // the refusals that do not depend on the request, in their order: LossFunction, null_space_rank.  Empty: go
+    std::string Refusal(Problem& p, const internal::Recognition& r) const {
+        if (p.NumLossFunctions() > 0 && !r.ba_losses && !(r.is_pg && r.pg.losses_known))
+            return std::to_string(p.NumLossFunctions()) + " residual block(s) carry a LossFunction; robust losses are not implemented by this layer -- no covariance computed";
         if (options_.null_space_rank != 0)
-            return Fail("null_space_rank = " + std::to_string(options_.null_space_rank) + ": this layer has no pseudo-inverse (only 0 is supported)");
-        std::unordered_map<const double*, int> index;
+            return "null_space_rank = " + std::to_string(options_.null_space_rank) + ": this layer has no pseudo-inverse (only 0 is supported)";
+        return std::string();
+    }
+
+    bool ComputeImpl(const Pairs& pairs, Problem* p) {
+        using namespace internal;
+        Recognition r;
+        Recognise(*p, false, options_.bundle_adjustment_losses, options_.num_threads, &r);
+        const std::string refusal = Refusal(*p, r);
+        if (!refusal.empty()) return Fail(refusal);
+        BlockIndex index;
         for (auto& b : p->blocks()) index[b.ptr] = b.index;
         for (size_t k = 0; k < pairs.size(); ++k)
             if (!index.count(pairs[k].first) || !index.count(pairs[k].second)) return Fail(PairName(k) + " names a parameter block that is not in the problem");
@@ -2370,24 +2463,15 @@ private:
             else for (int k = 0; k < in.size; ++k) in.jac[(size_t)k * in.local + k] = 1.0;
             blocks_[b.ptr] = std::move(in);
         }
-        BaLayout L;
-        bool ba = DetectBa(*p, &L, true, options_.num_threads);
-        if (ba) for (int rb : L.rot_block) ba = ba && UsesQuaternionRightPlus(p->blocks()[rb].local);
-        bool host = false;
-        if (!ba) {
-            L = BaLayout();
-            host = DetectBa(*p, &L, false);
-            if (host) for (int rb : L.rot_block) host = host && UsesQuaternionRightPlus(p->blocks()[rb].local);
+        switch (PickRoute(r, true, true)) {
+        case Route::BA: return ComputeBa(pairs, p, r.ba, index, false);
+        case Route::BA_HOSTJAC: r.MakeShapeOnly(); return ComputeBa(pairs, p, r.ba, index, true);
+        case Route::PG: return ComputePoseGraph(pairs, r.pg, index);
+        default: return ComputeDense(pairs, p, index);
         }
-        if (ba && ba_losses && options_.apply_loss_function) BaLossTable(*p, &L);      // (false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
-        if (ba || host) return ComputeBa(pairs, p, L, index, host);
-        PoseGraphLayout G;
-        if (DetectPoseGraph(p, &G)) return ComputePoseGraph(pairs, G, index);
-        return ComputeDense(pairs, p, index);
     }
 
-    bool ComputePoseGraph(const std::vector<std::pair<const double*, const double*>>& pairs, const internal::PoseGraphLayout& G,
-                          const std::unordered_map<const double*, int>& index) {
+    bool ComputePoseGraph(const Pairs& pairs, const internal::PoseGraphLayout& G, const BlockIndex& index) {
         const int n = (int)G.node_block.size(), m = (int)G.ei.size();
         std::vector<int> na, nb;
         for (size_t k = 0; k < pairs.size(); ++k) {
@@ -2399,17 +2483,11 @@ private:
         if (pairs.empty()) return true;
         // (the gauge check of stba_pg_covariance, here so that a graph it refuses never needs a device)
         if (stba_pg_gauge_check(n, m, G.ei.data(), G.ej.data(), G.fixed.data()) != STBA_OK) return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
-        stba_pg* pg = nullptr;
-        if (stba_pg_create(&pg, n, m, G.poses.data(), G.ei.data(), G.ej.data(), G.meas.data(), G.fixed.data(), nullptr) != STBA_OK)
-            return Fail(std::string("stba_pg_create: ") + stba_last_error());
-        struct Destroy { stba_pg* g; ~Destroy() { stba_pg_destroy(g); } } destroy{pg};
-        if (!G.sqrt_info.empty() && stba_pg_set_sqrt_information(pg, G.sqrt_info.data()) != STBA_OK)
-            return Fail(std::string("stba_pg_set_sqrt_information: ") + stba_last_error());
+        internal::PgEngine pg;
         // (apply_loss_function = false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
-        if (options_.apply_loss_function && !G.loss_kind.empty() && stba_pg_set_loss(pg, G.loss_kind.data(), G.loss_a.data(), G.loss_b.data(), G.loss_scale.data()) != STBA_OK)
-            return Fail(std::string("stba_pg_set_loss: ") + stba_last_error());
+        if (const char* failed = internal::CreatePg(G, options_.apply_loss_function, &pg)) return Fail(std::string(failed) + ": " + stba_last_error());
         std::vector<double> blk(pairs.size() * 36);
-        if (stba_pg_covariance(pg, (int)pairs.size(), na.data(), nb.data(), nullptr, blk.data(), nullptr) != STBA_OK)
+        if (stba_pg_covariance(pg.h, (int)pairs.size(), na.data(), nb.data(), nullptr, blk.data(), nullptr) != STBA_OK)
             return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
         for (size_t k = 0; k < pairs.size(); ++k)
             Store(pairs[k].first, pairs[k].second, 6, 6, std::vector<double>(blk.begin() + (ptrdiff_t)k * 36, blk.begin() + (ptrdiff_t)(k + 1) * 36));
@@ -2421,10 +2499,9 @@ private:
         return true;
     }
 
-    bool ComputeBa(const std::vector<std::pair<const double*, const double*>>& pairs, Problem* p, const internal::BaLayout& L,
-                   const std::unordered_map<const double*, int>& index, bool host) {
+    bool ComputeBa(const Pairs& pairs, Problem* p, const internal::BaLayout& L, const BlockIndex& index, bool host) {
         using namespace internal;
-        const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size(), no = (int)L.obs_cam.size();
+        const int nc = (int)L.rot_block.size(), np = (int)L.pt_block.size();
         auto& blk = p->blocks();
         // block index -> (camera, 0 | 3) or landmark
         std::vector<int> cam_of(blk.size(), -1), off_of(blk.size(), 0), pt_of(blk.size(), -1);
@@ -2446,32 +2523,16 @@ private:
             else return Fail(PairName(k) + " names a parameter block that no residual block of the bundle adjustment uses");
         }
         path_ = host ? "gpu-ba-hostjac" : "gpu-ba";
-        std::vector<double> cams((size_t)nc * 7), pts((size_t)np * 3);
-        std::vector<unsigned char> cam_fixed((size_t)nc * 6, 0), pt_fixed((size_t)np, 0);
-        for (int c = 0; c < nc; ++c) {
-            const auto& rb = blk[L.rot_block[c]]; const auto& pb = blk[L.pos_block[c]];
-            std::memcpy(&cams[(size_t)c * 7], rb.ptr, 4 * sizeof(double));
-            std::memcpy(&cams[(size_t)c * 7 + 4], pb.ptr, 3 * sizeof(double));
-            for (int k = 0; k < 3; ++k) { cam_fixed[(size_t)c * 6 + k] = rb.constant; cam_fixed[(size_t)c * 6 + 3 + k] = pb.constant; }
-        }
-        for (int j = 0; j < np; ++j) { std::memcpy(&pts[(size_t)j * 3], blk[L.pt_block[j]].ptr, 3 * sizeof(double)); pt_fixed[j] = blk[L.pt_block[j]].constant; }
-        stba_ba* ba = nullptr;
-        if (stba_ba_create(&ba, nc, np, no, cams.data(), pts.data(), L.obs_cam.data(), L.obs_pt.data(), L.feat.data(), cam_fixed.data(),
-                           pt_fixed.data(), nullptr) != STBA_OK)
-            return Fail(std::string("stba_ba_create: ") + stba_last_error());
-        struct Destroy { stba_ba* b; ~Destroy() { stba_ba_destroy(b); } } destroy{ba};
-        if (!host && !L.sqrt_info.empty() && stba_ba_set_sqrt_information(ba, L.sqrt_info.data()) != STBA_OK)
-            return Fail(std::string("stba_ba_set_sqrt_information: ") + stba_last_error());
-        if (!host && !L.loss_kind.empty() && stba_ba_set_loss(ba, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
-            return Fail(std::string("stba_ba_set_loss: ") + stba_last_error());
-        if (!L.prior_cam.empty() && stba_ba_set_pose_priors(ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
-                                                            L.prior_w.data()) != STBA_OK)
-            return Fail(std::string("stba_ba_set_pose_priors: ") + stba_last_error());
-        if (!L.rel_i.empty() && stba_ba_set_relative_poses(ba, (int)L.rel_i.size(), L.rel_i.data(), L.rel_j.data(), L.rel_meas.data(), nullptr,
-                                                           L.rel_w.data()) != STBA_OK)
-            return Fail(std::string("stba_ba_set_relative_poses: ") + stba_last_error());
+        BaPacked x;
+        PackBa(*p, L, &x);
+        BaEngine engine;
+        std::string error;
+        if (!CreateBa(L, x, nullptr, &engine, &error)) return Fail(error);
+        stba_ba* ba = engine.h;
         BaHostCtx hctx{p, &L, options_.num_threads};
-        if (host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, &hctx) != STBA_OK) return Fail(std::string("stba_ba_set_host_linearizer: ") + stba_last_error());
+        // (apply_loss_function = false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
+        const BaSetup setup{options_.apply_loss_function, host ? &hctx : nullptr, nullptr, nullptr};
+        if (const char* failed = ConfigureBa(ba, L, setup)) return Fail(std::string(failed) + ": " + stba_last_error());
         double rc = 0.0;
         if (stba_ba_covariance_compute(ba, options_.min_reciprocal_condition_number, &rc) != STBA_OK)
             return Fail(std::string("stba_ba_covariance_compute: ") + stba_last_error());
