@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "chol_schedule.hpp"
 
 namespace stba {
 
@@ -723,16 +724,16 @@ static void launch_syrk(double* A, int lda, int k0, int tile_mode, int tiles128,
 // outputs (release fence + flag) and goes on.  Tickets are handed out in an order that is a topological order of the task
 // graph, and a workgroup only ever waits for tasks that come earlier in that order -- which are finished, held by a
 // resident workgroup, or the next ticket of some list -- so the program cannot deadlock as long as every list has a
-// resident workgroup (MEGA_NTU = 10 for the lists that carry the TU tasks).
-//   D(b)          diagonal block b                        needs ver[b][b] == 4b
+// resident workgroup (MEGA_NTU = 10 for the lists that carry the TU tasks).  What every task waits for and what it
+// publishes -- flags, counters, the hand-shake of the TU siblings -- is the table at the head of chol_schedule.hpp:
+//   D(b)          diagonal block b
 //   TU(b, q)      q = 0..9: rows of block row b+1 of the panel solve AND a 2 x 2-tile block of the update of the next
 //                 diagonal tile, fused (the critical hand-off D(b) -> D(b+1), see tu_task512)
-//                                                         needs D(b), ver[b+1][b] == ver[b+1][b+1] == 4b
-//   T(b, i)       panel solve of the 128 rows of tile row i > b+1     needs D(b), ver[i][b] == 4b
-//                 (in the last 30 panels as two half tasks of 64 rows: see mega_build_tasks)
-//   TI(b)         inverse transpose of block b (for the backward substitution)   needs D(b)
-//   U(b; i, j)    tile (i, j) -= L_ib L_jb^T       needs T(b,i), T(b,j), ver[i][j] == 4b;  ver += 4
-//   Uq(b; i,q,j)  the same for 32 rows of a tile of the NEXT panel's column (j = b+1)       ver += 1
+//   T(b, i)       panel solve of the 128 rows of tile row i > b+1
+//                 (in the last 30 panels as two half tasks of 64 rows: see mega_create_tasks)
+//   TI(b)         inverse transpose of block b (for the backward substitution)
+//   U(b; i, j)    tile (i, j) -= L_ib L_jb^T
+//   Uq(b; i,q,j)  the same for 32 rows of a tile
 // (Round 3 tried TWO CLASSES of workgroups -- 512-thread "chain" workgroups on a few CUs of every XCD for D / TU / T / Uq, and
 // 256-thread trailing-update workgroups, two per CU, on all the others, the device split with CU-masked streams.  It ran,
 // bit-exact, and LOST: 2.61-2.96 ms against 2.44 ms, whatever the split.  Two update workgroups on a CU each take 45 us
@@ -747,26 +748,22 @@ static void launch_syrk(double* A, int lda, int k0, int tile_mode, int tiles128,
 // again -- is stored write-through (sc1) and may then be cached by every other XCD: no other L2 can
 // hold an older copy, because nobody but the owner ever touched those lines before.  Flags are
 // agent-scope atomics.
-// The ticket order comes from a list-scheduling simulation on the host (mega_build_tasks).
-enum { TASK_D = 0, TASK_T = 1, TASK_TI = 2, TASK_U = 3, TASK_UQ = 4, TASK_TU = 5 };
+// The ticket order comes from a list-scheduling simulation on the host (mega_build_tasks, chol_schedule.hpp).
+static_assert(sizeof(MegaTask) == sizeof(int4) && alignof(MegaTask) == alignof(int4), "a task descriptor is an int4");
 
-constexpr int MEGA_MAX_Q = 16;         // XCDs
 struct MegaArgs {
     double* A; int lda; int n; int nblk;
-    const int4* tasks;      // the ticket lists, concatenated
+    const MegaTask* tasks;  // the ticket lists, concatenated
     int nq;                 // number of XCD queues (= XCDs seen by the probe)
     int lstart[MEGA_MAX_Q + 1];   // list q (one per XCD) holds tasks [lstart[q], lstart[q+1]), taken in order
     signed char xcc_queue[16];   // HW_REG_XCC_ID -> queue
-    int* sync;              // [0..16) tickets of the lists, [16] abort, then dflag[nblk], tuflag[nblk], tudone[nblk],
-                            // tflag[nblk*nrow], ver[nrow*nblk] (nrow = nblk + 4 nwide)
+    int* sync;              // tickets of the lists, abort, then the flag arrays: mega_flag_layout(sync, nblk, nwide)
     double* linv; size_t linv_stride;
     double* vbuf; int nwide;   // inverse transposes of the 512 x 512 diagonal blocks 0 .. nwide-1 (row-major, ld 512): see below
     long long spin_limit;   // give up waiting for a dependency after this many ticks of the 100 MHz clock
     int* flag;
     long long* trace;       // optional (STBA_MEGA_TRACE): per task {workgroup, t_ticket, t_ready, t_done}, 100 MHz clock
 };
-constexpr int MEGA_SYNC_HDR = MEGA_MAX_Q + 1;
-constexpr int MEGA_ABORT = MEGA_MAX_Q;
 constexpr int MEGA_SMEM_BYTES = 128 * 1024;   // X of the TU task: 8 waves x 8 chunks x 2 KB
 constexpr int MEGA_PREDRAW_NB = 2;            // the next ticket is drawn at the start of a task only if the task spans at most
                                               // this many panels (a ticket held for 60-80 us can be a critical one: measured -12 %)
@@ -1175,7 +1172,6 @@ __device__ __forceinline__ bool tu4_task512(double* __restrict__ A, int lda, int
 // blocks (I, I) also write their 32 rows of X.  (Until round 3 FOUR workgroups each solved the WHOLE block row redundantly
 // -- 200 KB to wait for instead of 136 / 104, two waves per SIMD -- and updated 32 rows of the tile: 17 us from the
 // diagonal block's flag to the next one's, now ~12.)
-constexpr int MEGA_NTU = 10;
 __device__ __forceinline__ bool tu_task512(double* __restrict__ A, int lda, int k0, int rb, int q,
                                            const double* __restrict__ dinv, double* smem, int t, long long* ph,
                                            int* loaded, int* done_cnt, int* ver_diag, const int* dflag, int* abortf, int* s_ok, long long spin_limit,
@@ -1286,30 +1282,16 @@ __global__ __launch_bounds__(256) void chol_reset_kernel(int* __restrict__ sync,
 }
 
 // ---- the flag arrays behind the header of MegaArgs::sync, and the readiness test of a task ----
-struct MegaView {
-    int nblk, nrow;
-    int* abortf; int* dflag; int* tuflag; int* tudone; int* tflag; int* ver;
-};
-__device__ __forceinline__ MegaView mega_view(const MegaArgs& a) {
-    MegaView v;
-    v.nblk = a.nblk;
-    // Block rows >= nblk are VIRTUAL: row nblk + p is the identity block under panel p of a wide (4-panel) diagonal
-    // block; carried through the panel solves and updates of the panels p .. 4q+3 of its wide block q = p / 4 it
-    // becomes block row p - 4q of the inverse transpose of that 512 x 512 diagonal block, which the backward
-    // substitution multiplies by (12 dependent steps instead of 47).  Its tiles live in a.vbuf, not in A.
-    v.nrow = a.nblk + 4 * a.nwide;
-    v.abortf = a.sync + MEGA_ABORT;
-    v.dflag = a.sync + MEGA_SYNC_HDR;
-    v.tuflag = v.dflag + a.nblk;
-    v.tudone = v.tuflag + a.nblk;
-    v.tflag = v.tudone + a.nblk;                // [panel b][row i], i < nrow
-    v.ver = v.tflag + a.nblk * v.nrow;          // [row i][panel j]
-    return v;
-}
+// Block rows >= nblk are VIRTUAL: row nblk + p is the identity block under panel p of a wide (4-panel) diagonal
+// block; carried through the panel solves and updates of the panels p .. 4q+3 of its wide block q = p / 4 it
+// becomes block row p - 4q of the inverse transpose of that 512 x 512 diagonal block, which the backward
+// substitution multiplies by (12 dependent steps instead of 47).  Its tiles live in a.vbuf, not in A.
+typedef MegaFlags<int*> MegaView;
+__device__ __forceinline__ MegaView mega_view(const MegaArgs& a) { return mega_flag_layout(a.sync, a.nblk, a.nwide); }
 __device__ __forceinline__ int mega_ldf(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // (tu_dset: for a TU task, whether its diagonal block was there already -- then the task fetches the factor at once)
-__device__ __forceinline__ bool mega_ready(const MegaView& v, const int4 d, bool& tu_dset) {
-    const int type = d.x & 0xff, b = d.y, ti = d.z, tj = d.w;
+__device__ __forceinline__ bool mega_ready(const MegaView& v, const MegaTask d, bool& tu_dset) {
+    const int type = MEGA_X_TYPE(d.x), b = d.y, ti = d.z, tj = d.w;
     const int nblk = v.nblk, nrow = v.nrow;
     auto first_panel = [&](int i) { return i < nblk ? 0 : i - nblk; };      // the first panel that updates row i
     if (type == TASK_D) return mega_ldf(&v.ver[b * nblk + b]) >= 4 * b;
@@ -1325,7 +1307,7 @@ __device__ __forceinline__ bool mega_ready(const MegaView& v, const int4 d, bool
         return (v0 >= 4 * b) & (v1 >= 4 * b);
     }
     const int i = (type == TASK_UQ) ? (ti >> 2) : ti;
-    const int nbp = max(1, (d.x >> 16) & 0xff);            // panels in this task (a batched trailing update: b is its last one)
+    const int nbp = MEGA_X_PANELS(d.x);            // panels in this task (a batched trailing update: b is its last one)
     const int f0 = mega_ldf(&v.tflag[b * nrow + i]), f1 = mega_ldf(&v.tflag[b * nrow + tj]), ve = mega_ldf(&v.ver[i * nblk + tj]);
     return (f0 >= 4) & (f1 >= 4) & (ve >= 4 * (b - nbp + 1 - first_panel(i)));
 }
@@ -1337,7 +1319,7 @@ __device__ __forceinline__ bool mega_ready(const MegaView& v, const int4 d, bool
 // the list is exhausted, -1 on a time-out / abort (ok = false).
 struct MegaTicket {
     int mine = -1;          // the ticket held (-1: none), wave-uniform
-    int4 md;
+    MegaTask md;
     bool done = false;      // the list is exhausted
     int m_raw = 0;          // lane 0: the ticket drawn when the previous task started
     bool m_pending = false;
@@ -1414,7 +1396,7 @@ __global__ __launch_bounds__(512) void chol_mega_kernel(MegaArgs a) {
             }
             // draw the next ticket now, look at it after the task.  Not before a TU task: it waits for its three
             // siblings, which hold LATER tickets -- this workgroup must not sit on one of them.
-            if (!tk.done && pick >= 0 && (tk.md.x & 0xff) != TASK_TU && ((tk.md.x >> 16) & 0xff) <= MEGA_PREDRAW_NB) {
+            if (!tk.done && pick >= 0 && MEGA_X_TYPE(tk.md.x) != TASK_TU && MEGA_X_BATCH(tk.md.x) <= MEGA_PREDRAW_NB) {
                 if (t == 0) tk.m_raw = lbeg + atomicAdd(ticket, 1);
                 tk.m_pending = true;
             }
@@ -1426,8 +1408,8 @@ __global__ __launch_bounds__(512) void chol_mega_kernel(MegaArgs a) {
         }
         const int task = s_task;
         if (task < 0) break;
-        const int4 d = a.tasks[task];
-        const int type = d.x & 0xff, b = d.y, ti = d.z, tj = d.w;
+        const MegaTask d = a.tasks[task];
+        const int type = MEGA_X_TYPE(d.x), b = d.y, ti = d.z, tj = d.w;
         const int k0 = b * NB;
         // a fresh copy of the thread index per task: keeps the compiler from hoisting every task's
         // lane-dependent address arithmetic out of the ticket loop (that cost 100+ spilled registers)
@@ -1466,7 +1448,7 @@ __global__ __launch_bounds__(512) void chol_mega_kernel(MegaArgs a) {
             }
         } else if (type == TASK_U) {
             if (ti < nblk) {
-                const int nbp = max(1, (d.x >> 16) & 0xff);
+                const int nbp = MEGA_X_PANELS(d.x);
                 syrk_tile512<128>(a.A, a.lda, k0 - (nbp - 1) * NB, ti * NB, tj * NB, smem, tt, nbp * (NB / 16));
             } else {
                 int ldc, ldi, ldj;
@@ -1497,427 +1479,61 @@ __global__ __launch_bounds__(512) void chol_mega_kernel(MegaArgs a) {
             else if (type == TASK_T) __hip_atomic_fetch_add(&tflag[b * nrow + ti], tj == 0 ? 4 : 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else if (type == TASK_TI) { if (b < 4 * a.nwide) __hip_atomic_fetch_add(&tflag[b * nrow + nblk + b], 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
             else if (type == TASK_TU) { if (tj != 0) __hip_atomic_fetch_add(&tflag[b * nrow + b + 1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (the four diagonal blocks: they wrote X; ver: inside the task)
-            else if (type == TASK_U) __hip_atomic_fetch_add(&ver[ti * nblk + tj], 4 * max(1, (d.x >> 16) & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (type == TASK_U) __hip_atomic_fetch_add(&ver[ti * nblk + tj], 4 * MEGA_X_PANELS(d.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else if (type == TASK_UQ) __hip_atomic_fetch_add(&ver[(ti >> 2) * nblk + tj], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (a.trace) a.trace[8 * (size_t)task + 3] = wall_clock64();
         }
     }
 }
 
-// host side: the task list for nblk block columns (static per size), in one global dataflow order,
-// then split stably into one queue per XCD by the owner of the tile each task writes
-static int mega_task_row(const int4& tk) {
-    // every task writes tiles of one tile row only (TU writes (b+1, b) and (b+1, b+1))
-    switch (tk.x & 0xff) {
-        case TASK_D: case TASK_TI: return tk.y;
-        case TASK_TU: return tk.y + 1;
-        case TASK_T: case TASK_U: return tk.z;
-        default: return tk.z >> 2;
-    }
+// host side: the ticket lists come from mega_build_tasks (chol_schedule.hpp).  The product takes mega_default_options; a debug
+// build (-DSTBA_DEBUG_KNOBS) lets the environment override every threshold, read afresh for every plan
+// (tools/chol_knobs.py, tools/sim_sweep.py; STBA_MEGA_DUR=d,t,ti,u,uq,tu: the task durations of the model)
+static MegaScheduleOptions mega_options(int nblk) {
+    MegaScheduleOptions o = mega_default_options(nblk);
+    o.qrows = knob_int("STBA_MEGA_QROWS", o.qrows);
+    o.thalf_from = knob_int("STBA_MEGA_THALF_FROM", o.thalf_from);
+    o.thalf_dur = knob_double("STBA_MEGA_THALF_DUR", o.thalf_dur);
+    o.tu10_from = knob_int("STBA_MEGA_TU10_FROM", o.tu10_from);
+    o.tu10_dur = knob_double("STBA_MEGA_TU10_DUR", o.tu10_dur);
+    o.dq_from = knob_int("STBA_MEGA_DQ_FROM", o.dq_from);
+    o.q_from = knob_int("STBA_MEGA_QFROM", o.q_from);
+    if (const int batch = knob_int("STBA_MEGA_BATCH", 0); batch > 0) o.batch = batch;
+    o.far_batch = knob_int("STBA_MEGA_FAR", o.far_batch);
+    o.batch_lag = knob_int("STBA_MEGA_BLAG", o.batch_lag);
+    o.blevel = knob_double("STBA_MEGA_BLEVEL", o.blevel);
+    if (const char* e = knob_str("STBA_MEGA_DUR")) sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf", &o.dur[0], &o.dur[1], &o.dur[2], &o.dur[3], &o.dur[4], &o.dur[5]);
+    return o;
 }
-// A tile belongs to the XCD of its tile ROW.  Row i carries ~ i^2 / 2 trailing updates, so the rows are
-// dealt out heaviest first, each to the XCD with the least work so far (LPT): the totals differ by < 1 %
-// (a boustrophedon deal leaves 8 % between the heaviest XCD and the mean when nblk is not a multiple
-// of 16, and the heaviest XCD sets the pace of the throughput-bound first half).
-static std::vector<int> mega_row_owner(int nblk, int nq, int nvirt = 0) {
-    std::vector<int> owner((size_t)(nblk + nvirt), 0);
-    for (int v = 0; v < nvirt; ++v) owner[(size_t)(nblk + v)] = v % nq;      // virtual rows (inverse blocks): a few light tasks each
-    // (dealt boustrophedon or cyclically instead: measured 8 % worse)
-    std::vector<double> load((size_t)nq, 0.0);
-    for (int row = nblk - 1; row >= 0; --row) {
-        int best = 0;
-        for (int q = 1; q < nq; ++q)
-            if (load[(size_t)q] < load[(size_t)best]) best = q;
-        owner[(size_t)row] = best;
-        load[(size_t)best] += 24.0 * row * (row - 1) / 2.0 + 23.0 * row + 110.0;
-    }
-    return owner;
-}
-// The ticket order is produced by LIST SCHEDULING a model of the machine on the host: `wg` workers per XCD queue, measured
-// task durations, and bottom-level priorities (longest path to the end of the graph, HLFET).  Sorting the tasks by the
-// time their model worker became free gives (i) one global topological order, which the deadlock argument needs, and
-// (ii) per-queue orders in which a workgroup rarely takes a ticket whose inputs are far from ready (an in-order ticket
-// list has no other notion of priority).
-struct MegaShardModel {          // what-if: the queues are spread over several GPUs (design study, DESIGN.md "sharded reduced solve")
-    int n_gpus = 1;              // queue q belongs to GPU q / (nq / n_gpus)
-    int rows_per_group = 0;      // tile rows are dealt to the GPUs in groups of this many consecutive rows (0: one XCD-round, nq / n_gpus)
-    double hop_us = 0.0;         // flag latency of a dependency that crosses GPUs
-    double tile_us = 0.0;        // + transfer time of the 128 x 128 tile it carries (128 KiB over one xGMI link)
-    double cross_edges = 0.0;    // out: dependencies that crossed GPUs
-    double tiles_in_max = 0.0;   // out: distinct remote tiles fetched by the busiest GPU
-};
-// Far trailing updates are applied `batch` panels per pass over a tile (see mega_build_tasks).  The batch trades traffic for
-// task length: a tile is read and written once per batch (round 4, PMC passes at n = 24 000 with two-panel batches: 383 GB per
-// factorisation = 4 TB/s averaged over the kernel -- HBM-bound, 256 KB of operands + 128 KB of tile per panel and tile, no
-// reuse of the operand panels in the L2s), but a batch of B panels is a task of ~6 + 18 B us that nothing can pre-empt.  Small
-// systems are chain-bound and want short tasks (n = 6000: 2.294 / 2.295 / 2.344 ms with B = 2 / 3 / 4); large ones are
-// throughput-bound (n = 12 000: 13.09 / 12.01 / 11.55 ms with B = 2 / 4 / 8; n = 24 000: 96.9 / 88.6 / 84.7 / 82.6 ms with
-// B = 2 / 4 / 8 / 16, 0.61 -> 0.71 of the FP64 matrix-core peak).  Rule: double the batch while a batch round still
-// leaves every workgroup a few tasks (nblk^2 / 2 tiles on 256 workgroups).
-static int mega_default_batch(int nblk) {
-    const double tiles_per_wg = 0.5 * nblk * nblk / 256.0;
-    int b = 2;
-    while (b < 16 && tiles_per_wg / b >= 2.2) b *= 2;
-    return b;
-}
-struct MegaMachine {
-    int nq = 8;                  // XCD queues
-    int wg = 32;                 // model workers (= resident workgroups) per queue
-};
-static void mega_build_tasks(int nblk, const MegaMachine& mach, std::vector<int4>& out, int* lstart, std::vector<float>* sim_start = nullptr,
-                             double* makespan_out = nullptr, int nwide = 0, MegaShardModel* shard = nullptr) {
-    struct Node { int4 tk; std::vector<int> succ; int indeg = 0; double dur = 0, prio = 0, start = 0, ready = 0, avail = 0; int q = 0; int last_pred = -1; };
-    std::vector<Node> nodes;
-    const int NBK = nblk;
-    const int nq = mach.nq;
-    const int nl = nq;                             // one ticket list per XCD queue
-    std::vector<int> rowq = mega_row_owner(nblk, nq, 4 * nwide);
-    const int n_gpus = shard ? shard->n_gpus : 1, q_per_gpu = nq / std::max(1, n_gpus);
-    if (shard && n_gpus > 1) {
-        // block-cyclic over the GPUs, cyclic over a GPU's XCDs: rows [g R, (g+1) R) of every round of n_gpus R rows go to GPU g
-        const int R = shard->rows_per_group > 0 ? shard->rows_per_group : q_per_gpu;
-        for (int row = 0; row < nblk; ++row) {
-            const int local = (row / (R * n_gpus)) * R + row % R;        // index among the rows of its GPU
-            rowq[(size_t)row] = ((row / R) % n_gpus) * q_per_gpu + local % q_per_gpu;
-        }
-    }
-    auto gpu_of = [&](int l) { return n_gpus > 1 ? l / q_per_gpu : 0; };
-    static const int QROWS = knob_int("STBA_MEGA_QROWS", 2);
-    // (The chains pace the last ~30 panels whatever the size: the trailing updates of panel nblk - r are r^2 / 2 tiles of ~24 us
-    // on 256 workgroups, < 45 us for r < 31.  The three thresholds below count from the END: measured at n = 6000 -- nblk = 47,
-    // panels 17 / 32 / 30 -- and at n = 12 000, where fractions of nblk cost 2-3 %.)
-    const int THALF_FROM = knob_int("STBA_MEGA_THALF_FROM", std::max(0, nblk - 30));
-    static const double THALF_DUR = knob_double("STBA_MEGA_THALF_DUR", 0.6);
-    // the fused panel-solve + diagonal-tile update of a step: ten 2 x 2-tile block tasks from panel TU10_FROM on, four
-    // quarter tasks (each solving the whole block row) before
-    // (n = 6000, medians of interleaved runs on one box, tools/chol_ab.py: never 2.388 ms; from panel 18 / 26 / 28 / 32 / 36 / 40:
-    // 2.373 / 2.357 / 2.364 / 2.351 / 2.365 / 2.382 -- while workgroups are scarce ten siblings wait for each other)
-    const int TU10_FROM = knob_int("STBA_MEGA_TU10_FROM", std::max(0, nblk - 15));
-    static const double TU10_DUR = knob_double("STBA_MEGA_TU10_DUR", 0.65);
-    auto ntu = [&](int b) { return b >= TU10_FROM ? MEGA_NTU : 4; };
-    // from panel QFROM on (the chain-bound part of the factorisation, where workgroups are idle) every row's tile in the next
-    // panel column is updated by four quarter tasks: the row sweeps T -> U -> T get shorter
-    const int DQ_FROM = knob_int("STBA_MEGA_DQ_FROM", std::max(0, nblk - 17));      // quarter updates of the diagonal tile after next, see below
-    const int QFROM = knob_int("STBA_MEGA_QFROM", std::max(0, nblk - 17));      // (panel 30 of 47; with the short TU tasks behind it: 2.351 -> 2.343 ms)
-    std::vector<int> idD((size_t)NBK, -1), idTI((size_t)NBK, -1), idTU((size_t)NBK * MEGA_NTU, -1), idT((size_t)NBK * NBK, -1), idT2((size_t)NBK * NBK, -1),
-        idUq((size_t)NBK * NBK * 4, -1), idU((size_t)NBK * NBK * NBK, -1), idUd((size_t)NBK * 4, -1);
-    // measured on MI355X (tools/mega_trace.py), microseconds, plus ~2 us of flag latency per hop
-    // (debug builds: STBA_MEGA_DUR=d,t,ti,u,uq,tu overrides them for experiments)
-    double DUR[6] = {23.0, 23.0, 19.0, 25.0, 16.5, 20.0};      // (D: 21.3 us since round 2)
-    double DUR_K = 18.0;           // one more panel (K += 128) inside a batched trailing update (measured: 24 us for one panel, 42 for two)
-    static const int BATCH_KNOB = knob_int("STBA_MEGA_BATCH", 0);
-    const int BATCH = BATCH_KNOB > 0 ? std::min(64, BATCH_KNOB) : mega_default_batch(nblk);
-    static const int FAR = std::max(0, knob_int("STBA_MEGA_FAR", 0));
-    static const int BLAG = std::max(0, knob_int("STBA_MEGA_BLAG", 2));      // (round 3, with the shorter chain tasks: 3 -> 2: -0.02 ms; 1: the same; 0: +0.25 ms)
-    if (const char* e = knob_str("STBA_MEGA_DUR")) sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf", &DUR[0], &DUR[1], &DUR[2], &DUR[3], &DUR[4], &DUR[5]);
-    auto add = [&](int type, int b, int i, int j, double prio) {
-        Node nd; nd.tk = make_int4(type, b, i, j); nd.dur = DUR[type]; nd.prio = prio;
-        nd.q = rowq[(size_t)mega_task_row(nd.tk)];
-        nodes.push_back(nd);
-        return (int)nodes.size() - 1;
-    };
-    // priorities: smaller = sooner.  The key is the block column a task works towards (10 per column)
-    // plus a class offset, so that everything the NEXT panels need goes before trailing updates of far
-    // columns, whatever step they belong to (an in-step order would bury the update of tile (b+1, b+1)
-    // by panel b-1 behind the whole backlog of panel b-2).  (Replaced by the bottom level below; kept as the tie-break.)
-    for (int b = 0; b < NBK; ++b) {
-        idD[(size_t)b] = add(TASK_D, b, 0, 0, 10.0 * b);
-        idTI[(size_t)b] = add(TASK_TI, b, 0, 0, 10.0 * NBK + b);
-        if (b + 1 < NBK)
-            for (int q = 0; q < ntu(b); ++q) {        // (tk.w = 1: a diagonal block (I, I), which writes 32 rows of X; 2: the four-workgroup form)
-                int I = 0;
-                while ((I + 1) * (I + 2) / 2 <= q) ++I;
-                const bool dg = (q == I * (I + 1) / 2 + I);
-                idTU[(size_t)b * MEGA_NTU + q] = add(TASK_TU, b, q, ntu(b) == 4 ? 2 : dg ? 1 : 0, 10.0 * b + 5 + (ntu(b) != 4 && dg ? 1e-4 : 0.0));
-                if (ntu(b) != 4) nodes[(size_t)idTU[(size_t)b * MEGA_NTU + q]].dur = TU10_DUR * DUR[TASK_TU];
-            }
-        for (int i = b + 2; i < NBK; ++i) {
-            if (b >= THALF_FROM) {
-                // two HALF tasks (64 rows each on four waves, see the kernel's TASK_T) once the chains pace the factorisation:
-                // a panel solve is one of the two links of every row sweep T -> U -> T, and as a half it waits for 136 KB
-                // instead of 200 and has a SIMD per wave -- 11 us instead of 18.4.  (Measured at n = 6000, same box: whole
-                // tasks 2.509 ms; halves from panel 0 / 10 / 14 / 17 / 20 / 24: 2.493 / 2.445 / 2.425 / 2.425 / 2.431 / 2.427;
-                // QUARTER tasks from 17 / 24: 2.517 / 2.472 -- the 72 KB of the diagonal factor every part stages do not shrink.)
-                idT[(size_t)b * NBK + i] = add(TASK_T, b, i, 1, 10.0 * b + 6 + 1e-3 * i);
-                idT2[(size_t)b * NBK + i] = add(TASK_T, b, i, 2, 10.0 * b + 6 + 1e-3 * i + 5e-4);
-                nodes[(size_t)idT[(size_t)b * NBK + i]].dur = nodes[(size_t)idT2[(size_t)b * NBK + i]].dur = THALF_DUR * DUR[TASK_T];
-            } else idT[(size_t)b * NBK + i] = add(TASK_T, b, i, 0, 10.0 * b + 6 + 1e-3 * i);
-            // the next panel's column: 32-row tasks (short latency) only for the rows the second critical chain
-            // needs soon; a quarter task costs 14.5 us of a workgroup against 23.4 us for a whole tile, so the
-            // rows further down take the whole-tile task (their panel solve comes a diagonal block later)
-            if (i <= b + 1 + QROWS || b >= QFROM) {
-                for (int q = 0; q < 4; ++q)
-                    idUq[((size_t)b * NBK + i) * 4 + q] = add(TASK_UQ, b, i * 4 + q, b + 1, 10.0 * (b + 1) + 2 + 1e-3 * i);
-            } else {
-                idUq[((size_t)b * NBK + i) * 4] = add(TASK_U, b, i, b + 1, 10.0 * (b + 1) + 2 + 1e-3 * i);
-            }
-        }
-        // Trailing updates of the tiles beyond the next panel column.  Tile (i, j) needs the panels 0 .. j-2 at some point
-        // before its last update (panel j-1, above: the latency-critical one); they are applied BATCH panels at a time in
-        // one pass over the tile, K = 128 BATCH: the tile is read and written once per batch instead of once per panel and
-        // the task's fixed costs (waiting for the first operands and the tile, the stores, the hand-over: ~10 of 24 us) are
-        // paid once per batch.  The task of a batch carries its LAST panel in .y and the panel count in bits 16..23 of .x;
-        // the MFMAs run on the same accumulators in the same order as panel-by-panel, so the result is bit-identical.
-        for (int j = b + 2; j < NBK; ++j) {
-            // panels 0 .. j-2 of column j in batches [0, BATCH), [BATCH, 2 BATCH), ...: this panel closes a batch if it
-            // is the last of its group or the last one of the column
-            // (the last BLAG panels before the final one stay single tasks: a long batch there would sit on the path to
-            // the tile's panel solve)
-            const int lim = j - 2 - BLAG;
-            // (FAR batches, debug knob STBA_MEGA_FAR = f > 0: a group of 2 BATCH panels whose last one is still more than f panels in front of
-            // column j goes in ONE pass -- longer tasks only where the chains are far away)
-            int BJ = BATCH;
-            if (FAR > 0 && BATCH > 1 && j - ((b / (2 * BATCH)) * 2 * BATCH + 2 * BATCH - 1) > FAR) BJ = 2 * BATCH;
-            const int b0 = (BJ <= 1 || b > lim) ? b : (b / BJ) * BJ, last = (BJ <= 1 || b > lim) ? b : std::min(b0 + BJ - 1, lim);
-            if (b != last) continue;
-            const int nb = b - b0 + 1;
-            for (int i = j; i < NBK; ++i) {
-                if (i == j && j == b + 2 && b >= DQ_FROM) {
-                    // The diagonal tile (b+2, b+2): its update by panel b is the last input of TU(b+1) to arrive in the
-                    // chain-bound part -- D(b) -> half panel solve of row b+2 (12 us) -> this update (24 us as a whole-tile
-                    // task) = 38 us against a step of 36 (trace: the last TU(b) block became ready 6 us AFTER D(b) every
-                    // other panel).  Four quarter tasks (32 rows each, operands straight from memory: 14.6 us) instead.
-                    for (int q = 0; q < 4; ++q) {
-                        const int id = add(TASK_UQ, b, i * 4 + q, j, 10.0 * j + 1 + 1e-3 * q);
-                        idUd[(size_t)b * 4 + q] = id;
-                        if (q == 0) idU[((size_t)b * NBK + i) * NBK + j] = id;
-                    }
-                    continue;
-                }
-                const int id = add(TASK_U, b, i, j, 10.0 * j + 3 + 1e-3 * i + 1e-6 * b);
-                nodes[(size_t)id].tk.x |= nb << 16;
-                nodes[(size_t)id].dur += (nb - 1) * DUR_K;
-                for (int bb = b0; bb <= b; ++bb) idU[((size_t)bb * NBK + i) * NBK + j] = id;
-            }
-        }
-    }
-    auto dep = [&](int from, int to) {     // `to` needs `from`
-        if (from < 0 || to < 0) return;
-        nodes[(size_t)from].succ.push_back(to);
-        nodes[(size_t)to].indeg++;
-    };
-    for (int b = 0; b < NBK; ++b) {
-        const int d = idD[(size_t)b];
-        if (b > 0)
-            for (int q = 0; q < ntu(b - 1); ++q) dep(idTU[(size_t)(b - 1) * MEGA_NTU + q], d);
-        dep(d, idTI[(size_t)b]);
-        if (b + 1 < NBK)
-            for (int q = 0; q < ntu(b); ++q) {
-                const int tu = idTU[(size_t)b * MEGA_NTU + q];
-                dep(d, tu);
-                if (b > 0) {
-                    for (int q2 = 0; q2 < 4; ++q2) dep(idUq[((size_t)(b - 1) * NBK + (b + 1)) * 4 + q2], tu);
-                    dep(idU[((size_t)(b - 1) * NBK + (b + 1)) * NBK + (b + 1)], tu);
-                    for (int q2 = 1; q2 < 4; ++q2) dep(idUd[(size_t)(b - 1) * 4 + q2], tu);     // (its quarters, if it was split)
-                }
-            }
-        for (int i = b + 2; i < NBK; ++i) {
-            const int t = idT[(size_t)b * NBK + i], t2 = idT2[(size_t)b * NBK + i];
-            dep(d, t); dep(d, t2);
-            if (b > 0)
-                for (int q2 = 0; q2 < 4; ++q2) { const int uu = idUq[((size_t)(b - 1) * NBK + i) * 4 + q2]; dep(uu, t); dep(uu, t2); }
-            for (int q = 0; q < 4; ++q) {
-                const int uq = idUq[((size_t)b * NBK + i) * 4 + q];
-                if (uq < 0) continue;            // (rows with ONE whole-tile task use slot 0 only)
-                dep(t, uq); dep(t2, uq);
-                for (int q2 = 0; q2 < ntu(b); ++q2) dep(idTU[(size_t)b * MEGA_NTU + q2], uq);
-                if (b > 0) dep(idU[((size_t)(b - 1) * NBK + i) * NBK + (b + 1)], uq);
-            }
-        }
-        for (int j = b + 2; j < NBK; ++j)
-            for (int i = j; i < NBK; ++i) {
-                const int u0 = idU[((size_t)b * NBK + i) * NBK + j];
-                if (nodes[(size_t)u0].tk.y != b) continue;          // (a batch: its dependencies hang on its last panel)
-                const bool split = (nodes[(size_t)u0].tk.x & 0xff) == TASK_UQ;       // (the diagonal tile after next, in quarters)
-                for (int q2 = 0; q2 < (split ? 4 : 1); ++q2) {
-                    const int u = split ? idUd[(size_t)b * 4 + q2] : u0;
-                    for (auto* v : {&idT, &idT2}) { dep((*v)[(size_t)b * NBK + i], u); if (j != i) dep((*v)[(size_t)b * NBK + j], u); }
-                    const int nbp = split ? 1 : std::max(1, (nodes[(size_t)u].tk.x >> 16) & 0xff);
-                    if (b - nbp >= 0) dep(idU[((size_t)(b - nbp) * NBK + i) * NBK + j], u);
-                }
-            }
-    }
-    // wide inverse blocks: the identity block under panel p = 4q + v of wide block q (virtual row nblk + p) is carried
-    // through panels p .. 4q+3: TI(p) makes its diagonal tile, then per later panel bj of the block the updates
-    // U(k; row, bj), k = p .. bj-1, and the panel solve T(bj; row)
-    for (int qw = 0; qw < nwide; ++qw)
-        for (int v = 0; v < 4; ++v) {
-            const int pnl = 4 * qw + v, iv = NBK + pnl;
-            std::vector<int> xdone(4, -1);            // task that finishes tile (iv, 4qw + j)
-            xdone[(size_t)v] = idTI[(size_t)pnl];
-            for (int j = v + 1; j < 4; ++j) {
-                const int bj = 4 * qw + j;
-                int prev = -1;
-                for (int k = pnl; k < bj; ++k) {
-                    const int u = add(TASK_U, k, iv, bj, 10.0 * NBK + bj);
-                    dep(xdone[(size_t)(k - 4 * qw)], u);
-                    if (bj == k + 1) { for (int q2 = 0; q2 < ntu(k); ++q2) dep(idTU[(size_t)k * MEGA_NTU + q2], u); }
-                    else for (auto* v : {&idT, &idT2}) dep((*v)[(size_t)k * NBK + bj], u);
-                    dep(prev, u);
-                    prev = u;
-                }
-                const int tv = add(TASK_T, bj, iv, 0, 10.0 * NBK + bj);
-                dep(idD[(size_t)bj], tv);
-                dep(prev, tv);
-                xdone[(size_t)j] = tv;
-            }
-        }
-    static const double BLW = knob_double("STBA_MEGA_BLEVEL", 1.0);
-    if (BLW > 0.0) {
-        // bottom level (longest path to the end of the graph) as the priority: HLFET list scheduling
-        std::vector<int> indeg2(nodes.size()), topo;
-        topo.reserve(nodes.size());
-        for (size_t k = 0; k < nodes.size(); ++k) { indeg2[k] = nodes[k].indeg; if (indeg2[k] == 0) topo.push_back((int)k); }
-        for (size_t h = 0; h < topo.size(); ++h)
-            for (int sidx : nodes[(size_t)topo[h]].succ)
-                if (--indeg2[(size_t)sidx] == 0) topo.push_back(sidx);
-        std::vector<double> bl(nodes.size(), 0.0);
-        for (size_t h = topo.size(); h-- > 0;) {
-            const int k = topo[h];
-            double m = 0.0;
-            for (int sidx : nodes[(size_t)k].succ) m = std::max(m, bl[(size_t)sidx]);
-            bl[(size_t)k] = nodes[(size_t)k].dur + m;
-        }
-        for (size_t k = 0; k < nodes.size(); ++k) nodes[k].prio = nodes[k].prio * (1.0 - BLW) * 5.0 - BLW * bl[k];
-    }
-    // Event-driven list scheduling.  A ticket list replays the model if the tickets are sorted by the time
-    // their worker became FREE (= the moment a workgroup picks its next ticket), not by the task's start:
-    // a workgroup that picks a ticket early parks on it until its inputs arrive.
-    // Liveness: a ticket occupies its model worker from pick to end, so at most W - 1 tickets that come later in the
-    // topological (start time) order can precede any ticket in its list, W = the list's model workers; with at least W
-    // real workgroups per list one of them always reaches the earliest unfinished task.
-    // The model is faithful (C5, one class: 2.55 ms predicted, 2.53-2.60 ms measured; tools/mega_trace.py prints the
-    // drift), which makes it the place to try policies -- tools/sim_sweep.py, no GPU.  Tried and rejected there AND on the
-    // machine in rounds 1-2 (and removed from the code since): workers reserved for the tasks of the critical chains,
-    // priority boosts for those rows, an urgent list per XCD claimed by whichever workgroup is free (a parked workgroup
-    // starts a critical task the moment its last flag flips; a claimed task pays 2-5 us per hand-over), the last update of
-    // a tile fused into the panel solve that consumes it.  DESIGN.md 4 has the numbers.
-    static const double ADV_D = knob_double("STBA_MEGA_ADV_D", 0.0), ADV_TU = knob_double("STBA_MEGA_ADV_TU", 0.0);
-    typedef std::pair<double, int> PI;
-    typedef std::priority_queue<PI, std::vector<PI>, std::greater<PI>> Heap;
-    std::vector<Heap> ready_h((size_t)nl);
-    Heap events;                                // (time, node) a task ends | (time, -(node + 1)) the last remote input of a task arrives
-    std::vector<std::vector<double>> idle_since((size_t)nl, std::vector<double>((size_t)mach.wg, 0.0));   // LIFO
-    double now = 0.0;
-    struct Pick { double key, start; int node; };
-    std::vector<std::vector<Pick>> order((size_t)nl);
-    auto push_ready = [&](int k) { ready_h[(size_t)nodes[(size_t)k].q].push(PI(nodes[(size_t)k].prio, k)); };
-    for (int k = 0; k < (int)nodes.size(); ++k)
-        if (nodes[(size_t)k].indeg == 0) push_ready(k);
-    double makespan = 0.0;
-    std::vector<double> tiles_in((size_t)std::max(1, n_gpus), 0.0);
-    for (;;) {
-        for (int l = 0; l < nl; ++l) {
-            std::vector<double>& idl = idle_since[(size_t)l];
-            Heap& hb = ready_h[(size_t)l];
-            while (!idl.empty() && !hb.empty()) {
-                const int k = hb.top().second;
-                hb.pop();
-                Node& nd = nodes[(size_t)k];
-                // (ADVANCE: the tickets of the critical hand-off -- D and TU -- are moved up in their list by so many microseconds of model
-                // time, so that a workgroup is already parked on them when their last input arrives instead of reaching them a 42 us
-                // update task later; a parked workgroup idles, which is cheap: at most five tickets per panel and list)
-                const int ty = nd.tk.x & 0xff;
-                const double adv = ty == TASK_D ? ADV_D : ty == TASK_TU ? ADV_TU : 0.0;
-                order[(size_t)l].push_back({idl.back() - adv, now, k});
-                idl.pop_back();
-                nd.start = now;
-                events.push(PI(now + nd.dur, k));
-            }
-        }
-        if (events.empty()) break;
-        const PI ev = events.top();
-        events.pop();
-        now = ev.first;
-        if (ev.second < 0) {                    // (sharded model) the last remote input of a task has arrived
-            const int k = -(ev.second + 1);
-            nodes[(size_t)k].ready = now;
-            push_ready(k);
-            continue;
-        }
-        makespan = now;
-        const Node& nd = nodes[(size_t)ev.second];
-        idle_since[(size_t)nd.q].push_back(now);
-        const int g0 = gpu_of(nd.q);
-        unsigned sent_to = 0;                   // GPUs this task's output tile has been shipped to
-        for (int sidx : nd.succ) {
-            Node& sn = nodes[(size_t)sidx];
-            double at = now;
-            const int g1 = gpu_of(sn.q);
-            if (g1 != g0) {
-                at += shard->hop_us + shard->tile_us;
-                shard->cross_edges += 1.0;
-                if (!(sent_to >> g1 & 1u)) { sent_to |= 1u << g1; tiles_in[(size_t)g1] += 1.0; }
-            }
-            if (at > sn.avail) { sn.avail = at; sn.last_pred = ev.second; }
-            if (--sn.indeg == 0) {
-                if (sn.avail <= now) { sn.ready = now; push_ready(sidx); }
-                else events.push(PI(sn.avail, -(sidx + 1)));
-            }
-        }
-    }
-    if (makespan_out) *makespan_out = makespan;
-    if (shard) shard->tiles_in_max = *std::max_element(tiles_in.begin(), tiles_in.end());
-    if (knob_str("STBA_MEGA_SIMDBG")) {
-        static const char* NM[6] = {"D", "T", "TI", "U", "Uq", "TU"};
-        for (int b = 0; b + 1 < NBK; ++b) {
-            const Node& d0 = nodes[(size_t)idD[(size_t)b]];
-            const Node& d1 = nodes[(size_t)idD[(size_t)b + 1]];
-            const Node& tu = nodes[(size_t)idTU[(size_t)b * MEGA_NTU + ntu(b) - 1]];
-            const double e0 = d0.start + d0.dur;
-            fprintf(stderr, "b=%2d step %6.1f | TU ready %+6.1f start %+6.1f | D+1 ready %+6.1f start %+6.1f", b, d1.start - d0.start,
-                    tu.ready - e0, tu.start - e0, d1.ready - e0, d1.start - e0);
-            int k = idTU[(size_t)b * MEGA_NTU + ntu(b) - 1];
-            for (int hop = 0; hop < 4 && k >= 0; ++hop) {       // walk back along the last-arriving inputs
-                const Node& nd = nodes[(size_t)k];
-                fprintf(stderr, " <- %s(%d;%d,%d) rdy %+.1f st %+.1f", NM[nd.tk.x & 0xff], nd.tk.y, nd.tk.z, nd.tk.w, nd.ready - e0, nd.start - e0);
-                k = nd.last_pred;
-            }
-            fprintf(stderr, "\n");
-        }
-    }
-    out.clear();
-    for (int l = 0; l < nl; ++l) {
-        std::stable_sort(order[(size_t)l].begin(), order[(size_t)l].end(), [](const Pick& x, const Pick& y) {
-            return x.key != y.key ? x.key < y.key : x.start < y.start;
-        });
-        lstart[l] = (int)out.size();
-        for (const Pick& pk : order[(size_t)l]) {
-            out.push_back(nodes[(size_t)pk.node].tk);
-            if (sim_start) sim_start->push_back((float)pk.start);
-        }
-    }
-    lstart[nl] = (int)out.size();
+static void mega_plan(MegaSchedule& s, int nblk, int nwide, const MegaMachine& mach, MegaShardModel* shard = nullptr) {
+    mega_build_tasks(s, nblk, nwide, mach, mega_options(nblk), shard);
+    if (knob_str("STBA_MEGA_SIMDBG")) mega_print_chains(s, stderr);
 }
 
 // diagnostics (tools/sim_sweep.py): the simulated makespan of the task graph, no GPU involved
 double chol_schedule_makespan(int nblk, int nq, int wg_per_q) {
-    std::vector<int4> tasks;
-    std::vector<int> lstart((size_t)nq + 1);
-    double ms = 0.0;
     MegaMachine m;
     m.nq = nq; m.wg = wg_per_q;
-    mega_build_tasks(nblk, m, tasks, lstart.data(), nullptr, &ms);
-    return ms;
+    MegaSchedule s;
+    mega_plan(s, nblk, 0, m);
+    return s.makespan_us;
 }
 
 // the same task graph on n_gpus x n_xcd queues: tile rows block-cyclic over the GPUs, a dependency that crosses GPUs
 // costs hop_us + tile_us (see MegaShardModel); out3 = {makespan us, cross-GPU dependencies, remote tiles fetched by the
 // busiest GPU}
 void chol_shard_model(int nblk, int n_gpus, int n_xcd, int wg_per_q, int rows_per_group, double hop_us, double tile_us, double* out3) {
-    std::vector<int4> tasks;
-    std::vector<int> lstart((size_t)n_gpus * n_xcd + 1);
     MegaShardModel sh;
     sh.n_gpus = n_gpus; sh.rows_per_group = rows_per_group; sh.hop_us = hop_us; sh.tile_us = tile_us;
-    double ms = 0.0;
     MegaMachine m;
     m.nq = n_gpus * n_xcd; m.wg = wg_per_q;
-    mega_build_tasks(nblk, m, tasks, lstart.data(), nullptr, &ms, 0, &sh);
-    out3[0] = ms; out3[1] = sh.cross_edges; out3[2] = sh.tiles_in_max;
+    MegaSchedule s;
+    mega_plan(s, nblk, 0, m, &sh);
+    out3[0] = s.makespan_us; out3[1] = sh.cross_edges; out3[2] = sh.tiles_in_max;
 }
 
 // tile row -> GPU of the block-cyclic distribution the model uses
-int chol_shard_row_owner(int row, int n_gpus, int rows_per_group) { return (row / std::max(1, rows_per_group)) % std::max(1, n_gpus); }
+int chol_shard_row_owner(int row, int n_gpus, int rows_per_group) { return mega_shard_row_gpu(row, n_gpus, rows_per_group); }
 
 // ------------------------------------------------------------------------------------------
 // backward substitution, one launch per 128-unknown block b (from the last block up):
@@ -2072,6 +1688,7 @@ struct MegaDevice {
     std::mutex m;
     bool probed = false;
     int ncu = 0, nq = 0;                // CUs of the device, XCDs seen by the probe
+    int wg_per_xcd = 0;                 // workgroups of a ncu-wide launch on the XCD that got the fewest: the lists are built for this many
     signed char xcc_queue[16];
     hipEvent_t last = nullptr;          // recorded behind the most recent persistent kernel of this device when another stream needs it ...
     hipStream_t last_stream = nullptr;  // ... which ran on this stream (null: none, or the stream is gone)
@@ -2107,9 +1724,12 @@ static int mega_device_init(MegaDevice& D, hipStream_t st) {
         if (D.xcc_queue[x & 15] < 0) D.xcc_queue[x & 15] = (signed char)D.nq++;
         per_xcc[x & 15]++;
     }
+    // a list completes if its XCD has as many resident workgroups as the model had workers (mega_simulate): the fewest count
+    D.wg_per_xcd = D.ncu;
     for (int i = 0; i < 16; ++i)
-        if (D.xcc_queue[i] >= 0 && per_xcc[i] < MEGA_NTU)
-            return fail(STBA_ERR_HIP, "chol: fewer than 10 workgroups per XCD (the TU tasks of a step need one each)");
+        if (D.xcc_queue[i] >= 0) D.wg_per_xcd = std::min(D.wg_per_xcd, per_xcc[i]);
+    if (D.wg_per_xcd < MEGA_NTU)
+        return fail(STBA_ERR_HIP, "chol: fewer than 10 workgroups per XCD (the TU tasks of a step need one each)");
     if (!D.last) STBA_HIP(hipEventCreateWithFlags(&D.last, hipEventDisableTiming));
     D.probed = true;
     return STBA_OK;
@@ -2174,7 +1794,7 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
     struct MegaPlan {
         int nblk = 0, nwide = -1, ntasks = 0;
         int lstart[MEGA_MAX_Q + 1] = {0};
-        int4* tasks = nullptr; int* sync = nullptr; size_t sync_ints = 0;
+        MegaTask* tasks = nullptr; int* sync = nullptr; size_t sync_ints = 0;
         double makespan_us = 0.0;
         std::vector<float> sim_start;     // simulated start time of every task (written to the trace file)
     };
@@ -2265,12 +1885,16 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
             plan = MegaPlan();
             MegaMachine mach;
             mach.nq = D.nq;
-            mach.wg = std::max(MEGA_NTU, D.ncu / D.nq);
-            std::vector<int4> tasks;
-            mega_build_tasks(nblk, mach, tasks, plan.lstart, &plan.sim_start, &plan.makespan_us, nwide);
-            STBA_HIP(hipMalloc(reinterpret_cast<void**>(&plan.tasks), tasks.size() * sizeof(int4)));
-            STBA_HIP(hipMemcpy(plan.tasks, tasks.data(), tasks.size() * sizeof(int4), hipMemcpyHostToDevice));
-            plan.sync_ints = MEGA_SYNC_HDR + 3 * (size_t)nblk + 2 * (size_t)nblk * (nblk + 4 * nwide);
+            mach.wg = D.wg_per_xcd;
+            MegaSchedule sched;
+            mega_plan(sched, nblk, nwide, mach);
+            const std::vector<MegaTask>& tasks = sched.tasks;
+            std::copy(sched.lstart.begin(), sched.lstart.end(), plan.lstart);
+            plan.sim_start.swap(sched.sim_start);
+            plan.makespan_us = sched.makespan_us;
+            STBA_HIP(hipMalloc(reinterpret_cast<void**>(&plan.tasks), tasks.size() * sizeof(MegaTask)));
+            STBA_HIP(hipMemcpy(plan.tasks, tasks.data(), tasks.size() * sizeof(MegaTask), hipMemcpyHostToDevice));
+            plan.sync_ints = mega_flag_ints(nblk, nwide);
             STBA_HIP(hipMalloc(reinterpret_cast<void**>(&plan.sync), plan.sync_ints * sizeof(int)));
             plan.ntasks = (int)tasks.size();
             plan.nblk = nblk; plan.nwide = nwide;
@@ -2313,13 +1937,13 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
         D.last_stream = st;
         if (TRACE) {    // debugging aid: dump the task timeline of this factorisation (tools/mega_trace.py)
             std::vector<long long> h((size_t)plan.ntasks * 8);
-            std::vector<int4> ht((size_t)plan.ntasks);
+            std::vector<MegaTask> ht((size_t)plan.ntasks);
             STBA_HIP(hipStreamSynchronize(st));
             STBA_HIP(hipMemcpy(h.data(), ma.trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            STBA_HIP(hipMemcpy(ht.data(), plan.tasks, ht.size() * sizeof(int4), hipMemcpyDeviceToHost));
+            STBA_HIP(hipMemcpy(ht.data(), plan.tasks, ht.size() * sizeof(MegaTask), hipMemcpyDeviceToHost));
             if (FILE* f = fopen(TRACE, "wb")) {
                 fwrite(&plan.ntasks, sizeof(int), 1, f);
-                fwrite(ht.data(), sizeof(int4), ht.size(), f);
+                fwrite(ht.data(), sizeof(MegaTask), ht.size(), f);
                 fwrite(h.data(), sizeof(long long), h.size(), f);
                 fwrite(plan.sim_start.data(), sizeof(float), plan.sim_start.size(), f);
                 fclose(f);
