@@ -299,6 +299,13 @@ int stba_ba_covariance_release(stba_ba* ba);
 int stba_cholesky_factor(double* A, int n, void* hip_stream);
 /* solves A x = b for one right-hand side: b overwritten by x */
 int stba_cholesky_solve(const double* A, int n, double* b, void* hip_stream);
+/* Ainv[n*n] (row-major, exactly symmetric) = A^-1 of the SPD matrix A (n*n row-major, lower triangle read), n <= 4096, by the
+ * routine behind every covariance (stba_ba_covariance_compute, stba_dense_covariance) and the pose graph's coarse operator: a
+ * partial factorisation of [A .; I 0] that leaves -A^-1 in the lower right block -- not the factor-and-solve program of the two
+ * calls above.  pivot_ratio (may be NULL): smallest / largest Cholesky pivot l_ii^2, the stand-in for a reciprocal condition number
+ * that the covariance calls compare with min_rcond.  A failed pivot: STBA_ERR_NOT_POSITIVE_DEFINITE, stba_last_error() names it as
+ * "pivot k+1" (LAPACK's info), and neither output is written.  STBA_VERSION is unchanged: test for the symbol. */
+int stba_cholesky_inverse(const double* A, int n, double* Ainv, double* pivot_ratio, void* hip_stream);
 /* device-resident timing of factor+solve on an n x n synthetic SPD system, ms per solve */
 int stba_cholesky_time(int n, int reps, double* ms_avg, void* hip_stream);
 

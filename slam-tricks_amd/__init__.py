@@ -68,7 +68,7 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_get_params", "stba_ba_set_schur_mode", "stba_ba_schur_mode", "stba_ba_set_host_linearizer", "stba_ba_set_allreduce", "stba_ba_reduced_dim", "stba_ba_evaluate",
            "stba_ba_cost", "stba_ba_normal_blocks", "stba_ba_reduced_system", "stba_ba_solve_reduced",
            "stba_ba_back_substitute", "stba_ba_apply_step", "stba_ba_solve", "stba_ba_lm_iterations",
-           "stba_ba_triangulate", "stba_ba_time_linearize", "stba_ba_time_schur", "stba_cholesky_factor", "stba_cholesky_solve",
+           "stba_ba_triangulate", "stba_ba_time_linearize", "stba_ba_time_schur", "stba_cholesky_factor", "stba_cholesky_solve", "stba_cholesky_inverse",
            "stba_cholesky_time", "stba_cholesky_time_split", "stba_cholesky_schedule_model", "stba_cholesky_timeout_count", "stba_cholesky_set_timeout_us", "stba_cholesky_shard_model", "stba_cholesky_shard_owner", "stba_cholesky_profile", "stba_calib_evaluate", "stba_calib_gauss_newton",
            "stba_pcg_default_options", "stba_pg_create", "stba_pg_destroy", "stba_pg_set_allreduce", "stba_pg_get_poses", "stba_pg_evaluate",
            "stba_pg_solve", "stba_pg_last_pcg_summary", "stba_pg_time_kernels", "stba_dense_solve", "stba_corners_read", "stba_corners_write", "stba_zhang_init", "stba_two_view_init", "stba_odometry_read", "stba_odometry_write", "stba_trajectory_ate",
@@ -991,6 +991,14 @@ def cholesky_solve(A, b, stream=None):
     return x
 
 
+def cholesky_inverse(A, stream=None):
+    """(A^-1, pivot ratio) by the routine behind the covariances (stba_cholesky_inverse): the partial factorisation of [A .; I 0]"""
+    A = _f64(A)
+    Ainv = np.zeros_like(A); rc = C.c_double()
+    _chk(lib().stba_cholesky_inverse(_p(A), A.shape[0], _p(Ainv), C.byref(rc), C.c_void_p(stream or 0)), "stba_cholesky_inverse")
+    return Ainv, rc.value
+
+
 def cholesky_time(n, reps=5, stream=None):
     ms = C.c_double()
     _chk(lib().stba_cholesky_time(int(n), int(reps), C.byref(ms), C.c_void_p(stream or 0)), "stba_cholesky_time")
@@ -1131,14 +1139,7 @@ def calib_gauss_newton(params, obj, img, max_iter=10):
     return params, it.value, tr
 
 
-def dense_solve(residual, x0, n_res, n_local=None, plus=None, lower=None, upper=None, opt=None, callback=None, **kw):
-    """residual(x) -> (r[n_res], J[n_res, n_local] or None-ignored); plus(x, d) -> x_new.
-    The residual/Jacobian callback runs on the host (it is user code, like
-    CostFunction::Evaluate); normal equations and the damped Cholesky step run on the device."""
-    x = _f64(x0).copy()
-    n_params = x.size
-    n_local = n_local or n_params
-
+def _residual_callback(residual, n_params, n_res, n_local):
     def _fn(_u, xp, rp, Jp):
         xx = np.ctypeslib.as_array(xp, shape=(n_params,)).copy()
         r, J = residual(xx)
@@ -1146,6 +1147,17 @@ def dense_solve(residual, x0, n_res, n_local=None, plus=None, lower=None, upper=
         if Jp:
             np.ctypeslib.as_array(Jp, shape=(n_res * n_local,))[:] = np.asarray(J, dtype=np.float64).reshape(-1)
         return 0
+    return _fn
+
+
+def dense_solve(residual, x0, n_res, n_local=None, plus=None, lower=None, upper=None, opt=None, callback=None, **kw):
+    """residual(x) -> (r[n_res], J[n_res, n_local] or None-ignored); plus(x, d) -> x_new.
+    The residual/Jacobian callback runs on the host (it is user code, like
+    CostFunction::Evaluate); normal equations and the damped Cholesky step run on the device."""
+    x = _f64(x0).copy()
+    n_params = x.size
+    n_local = n_local or n_params
+    _fn = _residual_callback(residual, n_params, n_res, n_local)
 
     def _plus(_u, xp, dp, op):
         xx = np.ctypeslib.as_array(xp, shape=(n_params,)).copy()
@@ -1163,3 +1175,17 @@ def dense_solve(residual, x0, n_res, n_local=None, plus=None, lower=None, upper=
     _chk(lib().stba_dense_solve(cfn, cplus, None, n_params, n_local, n_res, _p(x), _p(lo), _p(up), C.byref(opt),
                                 C.byref(summ), _p(trace), cb, None), "stba_dense_solve")
     return x, summ, trace[: summ.num_iterations + 1]
+
+
+def dense_covariance(residual, x, n_res, n_local=None, min_rcond=1e-14):
+    """(J^T J)^-1 at x (stba_dense_covariance): residual(x) -> (r[n_res], J[n_res, n_local]) as in dense_solve, evaluated once
+    on the host; J^T J and its inverse on the device.  Returns (cov [n_local, n_local], rcond = the pivot ratio of J^T J)."""
+    x = _f64(x)
+    n_params = x.size
+    n_local = n_local or n_params
+    cfn = RESIDUAL_FN(_residual_callback(residual, n_params, n_res, n_local))
+    cov = np.zeros((n_local, n_local))
+    rc = C.c_double()
+    _chk(lib().stba_dense_covariance(cfn, None, n_params, n_local, n_res, _p(x), C.c_double(min_rcond), _p(cov), C.byref(rc)),
+         "stba_dense_covariance")
+    return cov, rc.value

@@ -2040,6 +2040,32 @@ int stba_cholesky_solve(const double* A, int n, double* bvec, void* hip_stream) 
     return STBA_OK;
 }
 
+// A^-1 through covariance.hip's cov_spd_inverse_packed -- the partial factorisation of [A .; I 0] behind every covariance and the
+// pose graph's coarse operator -- on a matrix the caller holds: the seam its accuracy is tested through.  Nothing is written to
+// Ainv or pivot_ratio unless the factorisation succeeded.
+int stba_cholesky_inverse(const double* A, int n, double* Ainv, double* pivot_ratio, void* hip_stream) {
+    if (!A || !Ainv || n <= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n > 4096) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_cholesky_inverse: limited to n = 4096");
+    STBA_TRY(require_device());
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);      // (null: the default stream)
+    const size_t np = (size_t)n * (n + 1) / 2;
+    DevBuf<double> dA, sig;
+    STBA_TRY(dA.alloc((size_t)n * n));
+    STBA_TRY(sig.alloc(np));
+    STBA_TRY(upload(dA, A, (size_t)n * n, st));
+    double rc = 0.0;
+    int piv = 0;
+    STBA_TRY(cov_spd_inverse_packed(dA, n, n, nullptr, sig, &rc, &piv, st));
+    if (piv) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pivot " + std::to_string(piv));
+    std::vector<double> packed(np);
+    STBA_TRY(download(packed.data(), sig, np, st));
+    STBA_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) Ainv[(size_t)i * n + j] = Ainv[(size_t)j * n + i] = packed[(size_t)i * (i + 1) / 2 + j];
+    if (pivot_ratio) *pivot_ratio = rc;
+    return STBA_OK;
+}
+
 __global__ void synth_spd_kernel(double* A, int lda, int n) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)lda * lda) return;

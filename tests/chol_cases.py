@@ -102,6 +102,15 @@ SYNTHETIC = list(SPECS)
 ALL = SYNTHETIC + ["ba"]
 POW2 = [c for c in SYNTHETIC if SPECS[c]["family"] == "pow2"]
 
+# the explicit inverse (chol_spd_inverse_dev) pads n to np, a multiple of 128, with identity rows and runs np / 128 panels: every
+# case above (np / 128 = 1, 1, 4, 5, 9, 9 at the sizes above) and n = 129, np = 256 with 127 padding rows.  The two cases of 129
+# are not part of ALL: the factorisation's tests keep their lists.
+INVERSE_EXTRA_SIZES = [129]
+INVERSE_EXTRA = dict(s for n in INVERSE_EXTRA_SIZES for s in (_spec("spectrum", n, kappa=1e8), _spec("rbf", n, delta=1e-8)))
+SPECS.update(INVERSE_EXTRA)
+INVERSE_SYNTHETIC = SYNTHETIC + list(INVERSE_EXTRA)
+INVERSE_ALL = INVERSE_SYNTHETIC + ["ba"]
+
 
 def family(name):
     """'spectrum' | 'rbf' | 'pow2-spectrum' | 'pow2-rbf' | 'ba'"""
@@ -172,6 +181,38 @@ def reference(name, O=None, scenes=None):
         x_ref, rel = R.solve_ref(A, b)
         _cache[key] = dict(kappa=kappa, L=L, rows=rows, E_lapack=R.backward_error(A, L, rows), x_ref=x_ref, last_correction=rel,
                            tol=R.forward_tolerance(kappa))
+    return _cache[key]
+
+
+def inverse_reference(name, O=None, scenes=None):
+    """what the tests of the explicit inverse need of a case, computed once: kappa(H) and the forward tolerance, the columns `cols`
+    of the refined reference X_ref (n x len(cols)) with its last_correction, LAPACK's factor L, LAPACK's own inverse (dpotri) with
+    its forward error fe_lapack and right residual rr_lapack on the same columns, and the pivot ratio min l_ii^2 / max l_ii^2"""
+    key = ("inv", name)
+    if key not in _cache:
+        A = case(name, O, scenes)["A"]
+        L, info = factor_ref(A)
+        assert info == 0, f"{name}: LAPACK finds the matrix not positive definite (info = {info})"
+        kappa = kappa_H(A)
+        cols = R.inverse_columns(A.shape[0])
+        X_ref, rel = R.inverse_ref(A, cols)
+        X_lapack = R.inverse_lapack(A)
+        piv = np.diag(L) ** 2
+        _cache[key] = dict(kappa=kappa, tol=R.forward_tolerance(kappa), cols=cols, X_ref=X_ref, last_correction=rel, L=L,
+                           X_lapack=X_lapack, fe_lapack=R.inverse_forward_error(A, X_lapack, X_ref, cols),
+                           rr_lapack=R.inverse_right_residual(A, X_lapack, cols), pivot_ratio=float(piv.min() / piv.max()))
+    return _cache[key]
+
+
+def inverse_restatement(name, O=None, scenes=None):
+    """forward error of chol_ref.partial_factorisation_inverse at tb = 16 and tb = 128 and its right residual at tb = 16, once per case"""
+    key = ("inv-restated", name)
+    if key not in _cache:
+        A, ref = case(name, O, scenes)["A"], inverse_reference(name, O, scenes)
+        X16, X128 = R.partial_factorisation_inverse(A, 16), R.partial_factorisation_inverse(A, 128)
+        _cache[key] = dict(fe16=R.inverse_forward_error(A, X16, ref["X_ref"], ref["cols"]),
+                           fe128=R.inverse_forward_error(A, X128, ref["X_ref"], ref["cols"]),
+                           rr16=R.inverse_right_residual(A, X16, ref["cols"]))
     return _cache[key]
 
 
