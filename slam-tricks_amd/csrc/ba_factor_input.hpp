@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/stba.h"
+#include "dd6.hpp"
 
 namespace stba {
 
@@ -26,62 +27,10 @@ inline int pose7_check_normalise(const double* in, double* out, const char* what
     return 0;
 }
 
-// Omega = L L^T, W = L^T of ONE symmetric positive definite 6 x 6 (row-major; the lower triangle is factored), by an unblocked
-// Cholesky in double-double arithmetic rounded to FP64 at the end -- the pose graph's factorisation of its edge weights
-// (pg_engine.hip) on the host: an FP64 factorisation loses cond(Omega) eps in its last pivots, an error the caller could not tell
-// from one of the solver's.  false: an entry that is not finite, or a pivot that is not a positive finite number.
-namespace prior_dd {
-struct dd { double hi, lo; };
-inline dd make(double a, double b) { const double s = a + b; return {s, b - (s - a)}; }      // |a| >= |b|
-inline dd add(dd x, dd y) {
-    const double s = x.hi + y.hi, bb = s - x.hi;
-    const double e = ((x.hi - (s - bb)) + (y.hi - bb)) + (x.lo + y.lo);
-    return make(s, e);
-}
-inline dd neg(dd x) { return {-x.hi, -x.lo}; }
-inline dd mul(dd x, dd y) {
-    const double p = x.hi * y.hi;
-    const double e = std::fma(x.hi, y.hi, -p) + (x.hi * y.lo + x.lo * y.hi);
-    return make(p, e);
-}
-inline dd div(dd x, dd y) {
-    const double q1 = x.hi / y.hi;
-    dd r = add(x, neg(mul(y, dd{q1, 0.0})));
-    const double q2 = r.hi / y.hi;
-    r = add(r, neg(mul(y, dd{q2, 0.0})));
-    const double q3 = r.hi / y.hi;
-    return add(make(q1, q2), dd{q3, 0.0});
-}
-inline dd sqrt(dd x) {           // x.hi > 0
-    const double s = std::sqrt(x.hi);
-    const double p = s * s;
-    const dd r = add(x, dd{-p, -std::fma(s, s, -p)});
-    return make(s, r.hi / (2.0 * s));
-}
-}  // namespace prior_dd
-inline bool prior_information_factor(const double* A, double* W) {
-    using namespace prior_dd;
-    for (int k = 0; k < 36; ++k) { if (!std::isfinite(A[k])) return false; W[k] = 0.0; }
-    dd L[21];                                  // lower triangle, row a at a (a + 1) / 2
-    for (int k = 0; k < 21; ++k) L[k] = dd{0.0, 0.0};
-    for (int c = 0; c < 6; ++c) {
-        dd d = dd{A[c * 7], 0.0};
-        for (int k = 0; k < c; ++k) d = add(d, neg(mul(L[c * (c + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
-        if (!(d.hi > 0.0) || !std::isfinite(d.hi)) return false;
-        const dd lcc = prior_dd::sqrt(d);
-        L[c * (c + 1) / 2 + c] = lcc;
-        W[c * 7] = lcc.hi;
-        for (int a = c + 1; a < 6; ++a) {
-            dd v = dd{A[a * 6 + c], 0.0};
-            for (int k = 0; k < c; ++k) v = add(v, neg(mul(L[a * (a + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
-            v = div(v, lcc);
-            L[a * (a + 1) / 2 + c] = v;
-            W[c * 6 + a] = v.hi;              // W = L^T
-        }
-    }
-    for (int k = 0; k < 36; ++k) if (!std::isfinite(W[k])) return false;
-    return true;
-}
+// Omega = L L^T, W = L^T of ONE symmetric positive definite 6 x 6 (row-major; the lower triangle is factored): information6_factor of
+// dd6.hpp, the double-double Cholesky the pose graph factors its edge weights with on the device, under the name the factor
+// setters know it by.  false: an entry that is not finite, or a pivot that is not a positive finite number.
+inline bool prior_information_factor(const double* A, double* W) { return information6_factor(A, W); }
 
 // the 6 x 6 square-root information W [36] of one factor: the caller's square root as it is (any finite matrix, rank-deficient ones
 // included), the factor of the caller's information matrix, or -- neither given -- the identity

@@ -375,49 +375,6 @@ int launch_sum_partials(const double* partial, int n, int stride, int K, double*
     return STBA_OK;
 }
 
-// max |v[i]| over n (+ n2) entries -> out[0]: grid-stride partial maxima, last block finishes
-// (max is order-independent, so this stays deterministic)
-__global__ __launch_bounds__(256) void absmax_partial_kernel(const double* __restrict__ v, size_t n,
-                                                             const double* __restrict__ v2, size_t n2,
-                                                             double* __restrict__ partial) {
-    __shared__ double s[256];
-    double m = 0.0;
-    const size_t stride = (size_t)gridDim.x * 256, i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t i = i0; i < n; i += stride) m = fmax(m, fabs(v[i]));
-    for (size_t i = i0; i < n2; i += stride) m = fmax(m, fabs(v2[i]));
-    s[threadIdx.x] = m;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
-}
-
-__global__ __launch_bounds__(256) void absmax_final_kernel(const double* __restrict__ partial, int n,
-                                                           double* __restrict__ out) {
-    __shared__ double s[256];
-    double m = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) m = fmax(m, partial[i]);
-    s[threadIdx.x] = m;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = s[0];
-}
-
-int launch_absmax(const double* v, size_t n, const double* v2, size_t n2, double* out, double* partial, int n_partial,
-                  hipStream_t st) {
-    const size_t total = n + n2;
-    int grid = (int)std::min<size_t>((size_t)n_partial, std::max<size_t>(1, (total + 2047) / 2048));
-    hipLaunchKernelGGL(absmax_partial_kernel, dim3(grid), dim3(256), 0, st, v, n, v2, n2, partial);
-    hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, partial, grid, out);
-    STBA_HIP(hipGetLastError());
-    return STBA_OK;
-}
-
 // The whole trial block of one LM iteration in ONE launch behind the residual-only kernel: out[0] = sum of that kernel's
 // cost partials (summation order of sum_partials_kernel), out[1..3] / out[5..7] the three sums of the landmark / camera
 // update's partials (order of trial_sums_kernel), out[4] = 1 if the factorisation timed out on this rank; out[9], out[10]: cost2 and

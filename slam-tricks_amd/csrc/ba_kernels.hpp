@@ -82,8 +82,6 @@ size_t lin_robust_lds_bytes(int n_cams, bool cams_in_lds, bool with_jac);
 bool lin_robust_cams_in_lds(int n_cams);
 int launch_linearize_robust(const LinArgs& a, const LinLoss& l, bool with_jac, int grid, hipStream_t st);
 int launch_sum_partials(const double* partial, int n, int stride, int K, double* out, hipStream_t st);
-int launch_absmax(const double* v, size_t n, const double* v2, size_t n2, double* out, double* partial, int n_partial,
-                  hipStream_t st);
 // (J8: compact Jacobian [n_obs][8]; omask: per-observation mask byte of constant dofs / landmarks, or null)
 // (Jc12: the camera blocks of the general form -- host-linearised factors, robust losses -- or null)
 int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st,

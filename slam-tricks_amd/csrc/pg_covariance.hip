@@ -30,22 +30,6 @@
 
 namespace stba {
 
-bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, int* size, int* first_node) {
-    std::vector<int> parent((size_t)n);
-    std::iota(parent.begin(), parent.end(), 0);
-    auto find = [&](int a) { while (parent[(size_t)a] != a) { parent[(size_t)a] = parent[(size_t)parent[(size_t)a]]; a = parent[(size_t)a]; } return a; };
-    for (int e = 0; e < m; ++e) {
-        const int a = find(ei[e]), b = find(ej[e]);
-        if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b);      // (the root is the component's smallest node)
-    }
-    std::vector<int> count((size_t)n, 0);
-    std::vector<unsigned char> has((size_t)n, 0);
-    for (int k = 0; k < n; ++k) { const int r = find(k); ++count[(size_t)r]; if (fixed && fixed[k]) has[(size_t)r] = 1; }
-    for (int k = 0; k < n; ++k)
-        if (find(k) == k && !has[(size_t)k]) { *size = count[(size_t)k]; *first_node = k; return false; }
-    return true;
-}
-
 namespace {
 
 constexpr int PGC_K = 64;          // columns of a batch = lanes of a wave

@@ -1,9 +1,11 @@
-// pg_covariance.hpp -- what pg_covariance.hip needs from the pose-graph engine (pg_engine.hip), and the host-side gauge check.
+// pg_covariance.hpp -- what pg_covariance.hip needs from the pose-graph engine (pg_engine.hip); the host-side gauge check,
+// pg_gauge_fixed, is pg_plan.hpp's.
 #pragma once
 #include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "pg_plan.hpp"
 
 struct stba_pg;
 
@@ -30,9 +32,5 @@ struct PgCovDevice {
     const unsigned char* fixed = nullptr;  // device, or null
 };
 int pg_cov_linearize(stba_pg* g, PgCovDevice* out);
-
-// union-find over the edges: the first connected component without a constant node.  true: every component has one.
-// Otherwise *size and *first_node describe the offending component (the one whose smallest node index is smallest).
-bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, int* size, int* first_node);
 
 }  // namespace stba

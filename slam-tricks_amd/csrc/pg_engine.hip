@@ -38,8 +38,10 @@
 #include <vector>
 
 #include "ba_kernels.hpp"
+#include "dd6.hpp"
 #include "lm_policy.hpp"
 #include "pg_covariance.hpp"
+#include "pg_plan.hpp"
 #include "robust_loss.hpp"
 
 namespace stba {
@@ -154,7 +156,7 @@ __device__ inline void block_sum2(double a, double b, double* out2) {
 }
 
 // device-resident scalars of one PCG solve; every kernel of iteration k reads rz[k & 1], the direction kernel writes rz[(k + 1) & 1]
-struct PcgState {
+struct PgPcgState {
     double rz[2];
     double rr0, rr, tol2;
     int iters, done, hit_cap, ticks;
@@ -282,42 +284,11 @@ __global__ __launch_bounds__(256) void pg_linearize_kernel(int n_edges, const do
 }
 
 // ---- per-edge weights: what the caller gives ([m][36] row-major) -> the component-major array the linearisation reads
-// Double-double arithmetic (a value as an unevaluated sum hi + lo) for the Cholesky factor below: the factor is made once per call of
-// stba_pg_set_information and is a 6 x 6 per edge, so its cost does not matter, while an FP64 factorisation loses
-// about cond(Omega) eps in its last pivots -- an error the caller could not tell from one of the solver's.
-struct dd { double hi, lo; };
-__device__ inline dd dd_make(double a, double b) { const double s = a + b; return {s, b - (s - a)}; }      // |a| >= |b|
-__device__ inline dd dd_add(dd x, dd y) {
-    const double s = x.hi + y.hi, bb = s - x.hi;
-    const double e = ((x.hi - (s - bb)) + (y.hi - bb)) + (x.lo + y.lo);
-    return dd_make(s, e);
-}
-__device__ inline dd dd_neg(dd x) { return {-x.hi, -x.lo}; }
-__device__ inline dd dd_mul(dd x, dd y) {
-    const double p = x.hi * y.hi;
-    const double e = fma(x.hi, y.hi, -p) + (x.hi * y.lo + x.lo * y.hi);
-    return dd_make(p, e);
-}
-__device__ inline dd dd_div(dd x, dd y) {
-    const double q1 = x.hi / y.hi;
-    dd r = dd_add(x, dd_neg(dd_mul(y, dd{q1, 0.0})));
-    const double q2 = r.hi / y.hi;
-    r = dd_add(r, dd_neg(dd_mul(y, dd{q2, 0.0})));
-    const double q3 = r.hi / y.hi;
-    return dd_add(dd_make(q1, q2), dd{q3, 0.0});
-}
-__device__ inline dd dd_sqrt(dd x) {           // x.hi > 0
-    const double s = sqrt(x.hi);
-    const double p = s * s;
-    const dd r = dd_add(x, dd{-p, -fma(s, s, -p)});
-    return dd_make(s, r.hi / (2.0 * s));
-}
-
 // One edge per lane.  sqrt_form = 0: `in` holds an information matrix Omega_e (symmetric positive definite; the lower triangle is
-// factored), Omega = L L^T by an unblocked Cholesky in double-double, W_e = L^T rounded to FP64.  sqrt_form = 1: `in` holds W_e itself,
-// which is only transposed into the component-major array.  A non-finite entry anywhere in the 36, or a pivot that is not a positive
-// finite number, refuses the edge: the smallest such edge index ends up in *bad (which the host set to INT_MAX), and the host
-// throws the whole array away.
+// factored), Omega = L L^T by an unblocked Cholesky in double-double, W_e = L^T rounded to FP64 (information6_factor, dd6.hpp: the
+// one the bundle adjustment's factor setters call on the host).  sqrt_form = 1: `in` holds W_e itself, which is only transposed into
+// the component-major array.  A non-finite entry anywhere in the 36, or a pivot that is not a positive finite number, refuses the
+// edge: the smallest such edge index ends up in *bad (which the host set to INT_MAX), and the host throws the whole array away.
 __global__ __launch_bounds__(256) void pg_information_kernel(int n_edges, const double* __restrict__ in, int sqrt_form,
                                                              double* __restrict__ Wout, int* __restrict__ bad) {
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -329,25 +300,7 @@ __global__ __launch_bounds__(256) void pg_information_kernel(int n_edges, const 
     if (sqrt_form) {
         for (int k = 0; k < 36; ++k) Wl[k] = A[k];
     } else {
-        dd L[21];                                  // lower triangle, row a at a (a + 1) / 2
-        for (int k = 0; k < 21; ++k) L[k] = dd{0.0, 0.0};
-        for (int k = 0; k < 36; ++k) Wl[k] = 0.0;
-        for (int c = 0; c < 6 && ok; ++c) {
-            dd d = dd{A[c * 7], 0.0};
-            for (int k = 0; k < c; ++k) d = dd_add(d, dd_neg(dd_mul(L[c * (c + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
-            if (!(d.hi > 0.0) || !isfinite(d.hi)) { ok = false; break; }
-            const dd lcc = dd_sqrt(d);
-            L[c * (c + 1) / 2 + c] = lcc;
-            Wl[c * 7] = lcc.hi;
-            for (int a = c + 1; a < 6; ++a) {
-                dd v = dd{A[a * 6 + c], 0.0};
-                for (int k = 0; k < c; ++k) v = dd_add(v, dd_neg(dd_mul(L[a * (a + 1) / 2 + k], L[c * (c + 1) / 2 + k])));
-                v = dd_div(v, lcc);
-                L[a * (a + 1) / 2 + c] = v;
-                Wl[c * 6 + a] = v.hi;              // W = L^T
-            }
-        }
-        for (int k = 0; k < 36; ++k) ok = ok && isfinite(Wl[k]);
+        ok = ok && information6_factor(A, Wl);
     }
     if (!ok) { atomicMin(bad, e); return; }
     for (int k = 0; k < 36; ++k) Wout[(size_t)k * n_edges + e] = Wl[k];
@@ -494,7 +447,7 @@ __device__ inline double sum_partials_dev(const double* partial, int nb, int str
 __global__ __launch_bounds__(256) void pg_edge_product_kernel(int n_edges, const int* __restrict__ ei, const int* __restrict__ ej,
                                                               const double* __restrict__ Ji, const double* __restrict__ Jj,
                                                               const double* __restrict__ p, double* __restrict__ u,
-                                                              double* __restrict__ part_tt, const PcgState* __restrict__ state) {
+                                                              double* __restrict__ part_tt, const PgPcgState* __restrict__ state) {
     if (state && state->done) return;          // (the solve has converged: see pg_pcg_dir4_kernel)
     const int e = blockIdx.x * 256 + threadIdx.x;
     double tt2 = 0.0;
@@ -527,8 +480,7 @@ __global__ __launch_bounds__(256) void pg_edge_product_kernel(int n_edges, const
 }
 
 // ================================================================= round 4: two-level preconditioner, device-side PCG control
-constexpr int PG_NT = 1024;             // node kernels of the PCG: 1024 threads = 128 nodes x 8 lanes
-constexpr int PG_NPW = PG_NT / 8;       // nodes per workgroup
+// (PG_NT = 1024 threads = PG_NPW = 128 nodes x 8 lanes: pg_plan.hpp)
 
 // sum of nb per-workgroup partials by a workgroup of NT threads, fixed order (same bits in every workgroup and on every rank)
 template <int NT>
@@ -852,7 +804,7 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_init4_kernel(int n, int agg, con
 // chain of dependent round trips, 19 us for 10 000 nodes in round 3), the six components are summed over the lanes with a
 // butterfly, lanes 0..5 then own one component each.
 template <bool GATHER>
-__global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int agg, int slot, const PcgState* __restrict__ state,
+__global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int agg, int slot, const PgPcgState* __restrict__ state,
                                                               int nb_a, const double* __restrict__ part_a, int nb_b,
                                                               const double* __restrict__ part_b, const double* __restrict__ Minv,
                                                               const double* __restrict__ AdP, const double* __restrict__ d,
@@ -937,7 +889,7 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int
 }
 
 // coarse correction: zc = Ainv rc (one wave per row; rc = the parts of its group added in order); partial -> rc.zc
-__global__ __launch_bounds__(256) void pg_coarse_solve_kernel(int nc, int parts, const PcgState* __restrict__ state, const double* __restrict__ Ainv,
+__global__ __launch_bounds__(256) void pg_coarse_solve_kernel(int nc, int parts, const PgPcgState* __restrict__ state, const double* __restrict__ Ainv,
                                                               const double* __restrict__ rc_part, double* __restrict__ zc,
                                                               double* __restrict__ part_cz) {
     __shared__ double sw[4];
@@ -968,7 +920,7 @@ __global__ __launch_bounds__(256) void pg_coarse_solve_kernel(int nc, int parts,
 // Workgroup 0 also keeps the books of the solve: rz for the next iteration, the iteration count, and the STOPPING TEST
 // |r|^2 <= eta^2 |b|^2 (or the iteration cap) -- once `done` is set every later kernel of the solve returns at once, so the
 // host can enqueue iterations ahead of what it knows (it polls the exported block in mapped memory).
-__global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int slot, int first, double eta, int max_iters, PcgState* __restrict__ state,
+__global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int slot, int first, double eta, int max_iters, PgPcgState* __restrict__ state,
                                                            double* __restrict__ exp_, int nb_rz, const double* __restrict__ part_rz, int nb_cz,
                                                            const double* __restrict__ part_cz, const double* __restrict__ AdP,
                                                            const double* __restrict__ zc, const double* __restrict__ z, const double* __restrict__ d,
@@ -1059,12 +1011,8 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int 
 // B_e = Ji^T Jj per edge END (its transpose for the other end), written once per linearisation in the order the groups read
 // them (pg_offdiag_kernel), 36 coalesced loads per end and iteration out of the XCD's L2.
 // Several ranks (edge shards) keep the launch-per-kernel path: their product needs a cross-rank sum in every iteration.
-constexpr int PP_T = 512;            // threads of a group's workgroup (384 = 64 nodes x 6 components carry the vectors)
-constexpr int PP_VCAP = 1536;        // edge ends of one group whose products fit the LDS buffer
-constexpr int PP_NCMAX = 1536;       // coarse unknowns: three columns of the group's six inverse rows per thread
-constexpr int PP_SLOT = 16;          // doubles per group in the all-gather block (9 used)
-constexpr int PP_STAMP = 16;         // ints between two stamps (a 64-byte line each)
-constexpr int PP_TIMED_OUT = 2;      // PcgState::hit_cap: a stamp never came (the workgroups were not all resident): the caller repeats the solve with launches
+// (PP_T, PP_VCAP, PP_NCMAX, PP_SLOT, PP_STAMP and pp_lds_bytes, the layout the host sizes and this kernel indexes: pg_plan.hpp)
+constexpr int PP_TIMED_OUT = 2;      // PgPcgState::hit_cap: a stamp never came (the workgroups were not all resident): the caller repeats the solve with launches
 
 struct PpArgs {
     int n, agg, log2agg, na, nc, base, max_iters;
@@ -1073,14 +1021,12 @@ struct PpArgs {
     const double *Bend, *Hd, *d, *Minv, *AdP, *Ainv, *g;
     double *x, *ubuf, *pbuf;
     int *ustamp, *pstamp;
-    PcgState* state;
+    PgPcgState* state;
     long long spin_limit; // how long a workgroup waits for a stamp, in ticks of wall_clock64 (100 MHz); 0: not at all (the test of the way back)
     double eta_c;         // tolerance on |P^T r| / |P^T r_0| in the stopping test (<= 0: none)
     int fences;           // 1: the stamps are published behind a RELEASE fence and read in front of an ACQUIRE fence (agent scope); 0: compiler barriers only
     long long* tdbg;      // debug builds: time per phase (group 0), else null
 };
-
-inline size_t pp_lds_bytes(int na, int nc) { return ((size_t)2 * nc + (size_t)na * PP_SLOT + 768 + (size_t)PP_VCAP * 6 + 128 + 16) * sizeof(double); }
 
 __device__ __forceinline__ int pp_ld_i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double pp_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1376,7 +1322,7 @@ __global__ __launch_bounds__(PP_T) void pg_pcg_persistent_kernel(PpArgs a) {
 // (one rank) or to a device block the cross-rank sum goes over first.  out: {cost2_new, |J x|^2, g.x, |dx|^2, |x|^2, seq}
 __global__ __launch_bounds__(256) void pg_trial_finish_kernel(int nb_e, const double* __restrict__ part_e, int nb_tt,
                                                               const double* __restrict__ part_tt, int nb_u, const double* __restrict__ part_u,
-                                                              const PcgState* __restrict__ state, double* __restrict__ out, double seq) {
+                                                              const PgPcgState* __restrict__ state, double* __restrict__ out, double seq) {
     const double c2 = sum_partials_dev(part_e, nb_e, 1, 0);
     const double tt = sum_partials_dev(part_tt, nb_tt, 2, 0);
     const double gx = sum_partials_dev(part_u, nb_u, 4, 0);
@@ -1463,11 +1409,11 @@ struct stba_pg {
     int rank = 0, world = 1;
     DevBuf<double> scalar;              // one device double for the cost sums
     // ---- round 4: coarse space of the two-level preconditioner (see the header) and the device-side PCG control
-    int agg = 0, na = 0, nc = 0, np = 0, parts = 1;      // nodes per group, groups, coarse unknowns, padded, workgroups per group
+    PgCoarsePlan coarse;                                 // its sizes (pg_plan.hpp); agg 0: none planned yet, -1: off
     DevBuf<int> end_node;                                // owner node of every edge end of the CSR
     DevBuf<double> AdP, Ac0, W, Ainv, inv_work, rc_part, zc, part_cz, part_u, scal_dev, contrib, Dc;
     DevBuf<int> cflag;               // [0]: pivot flag of the coarse factorisation, [1]: coarse operators that failed (this solve)
-    DevBuf<PcgState> state;
+    DevBuf<PgPcgState> state;
     MappedBuffer exp;                                    // the launch-path PCG's stamped block (PX_*)
     double fin_vals[8] = {0};                            // the host's validated copy of the last trial / linearisation block
     MappedBuffer fin;                                    // the trial / linearisation scalars' stamped block
@@ -1477,10 +1423,9 @@ struct stba_pg {
     DevBuf<int> end_pos, end_rem;                        // CSR position of the edge end 2 e + side | remote node of the end at a CSR position
     DevBuf<double> Bend, ubuf, pbuf;
     DevBuf<int> ustamp, pstamp;
-    int max_group_ends = 0;                              // edge ends of the largest group of the coarse space
     int pp_base = 0;                                     // stamps only grow: the next solve starts behind the last one's
     bool bend_valid = false, pp_disabled = false;
-    std::vector<int> h_node_start;
+    std::vector<int> node_start_host;                    // what the engine keeps of its PgEnds: node_start, for pg_plan_coarse
     bool coarse_valid = false;
     double coarse_radius = 0.0;
     // ---- round 6: the coarse inverse OFF the critical path (stba_pcg_options::coarse_async): a second stream inverts the coarse
@@ -1599,31 +1544,19 @@ int pg_cov_linearize(stba_pg* g, PgCovDevice* out) {
 }
 }  // namespace stba
 
-// the dynamic LDS of pg_coarse_build_kernel: six coarse columns and the edge ends of the largest group; what a launch may ask for
-// at the most (+ 20 KB static in the kernel)
-static constexpr size_t PG_COARSE_BUILD_LDS_MAX = 136 * 1024;
-static size_t pg_coarse_build_lds(int nc, int max_group_ends) { return (size_t)6 * nc * sizeof(double) + (size_t)4 * max_group_ends * sizeof(int); }
-
-// ---- coarse space: sizes and buffers for a group size (lazily: the group size is an option of the solve)
+// ---- coarse space: the sizes (pg_plan_coarse) and the buffers for a group size (lazily: the group size is an option of the solve)
 static int pg_setup_coarse(stba_pg* g, int group_opt) {
-    int agg = group_opt;
-    if (agg == 0) {            // auto: about 160 groups (C4: 64 nodes per group, 942 coarse unknowns), at least 8 nodes per group
-        agg = 8;
-        while ((g->n + agg - 1) / agg > 200) agg *= 2;
-    }
-    if (agg < 0) { g->agg = -1; g->coarse_valid = false; return STBA_OK; }
-    if (agg < 2 || (agg & (agg - 1)) != 0) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_solve: coarse_group must be a power of two >= 2 (0: automatic, -1: off)");
-    if (agg == g->agg) return STBA_OK;
-    const int na = (g->n + agg - 1) / agg, nc = 6 * na, np = ((nc + 127) / 128) * 128, parts = std::max(1, agg / PG_NPW);
-    int max_ends = 0;
-    for (int a = 0; a < na; ++a)
-        max_ends = std::max(max_ends, g->h_node_start[(size_t)std::min(g->n, (a + 1) * agg)] - g->h_node_start[(size_t)std::min(g->n, a * agg)]);
-    if (pg_coarse_build_lds(nc, max_ends) > PG_COARSE_BUILD_LDS_MAX)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_solve: coarse space too large for this group size");
+    PgCoarsePlan plan;
+    std::string why;
+    const int rc = pg_plan_coarse(g->n, g->node_start_host, group_opt, &plan, &why);
+    if (rc != 0) return fail(rc, why);
+    if (plan.agg < 0) { g->coarse.agg = -1; g->coarse_valid = false; return STBA_OK; }
+    if (plan.agg == g->coarse.agg) return STBA_OK;
+    const int na = plan.na, nc = plan.nc, np = plan.np, parts = plan.parts;
     if (g->st2) STBA_HIP(hipStreamSynchronize(g->st2));       // (a job of the last solve may still be writing W / an inverse)
     g->job_in_flight = false;
     for (auto* buf : {&g->AdP, &g->Ac0, &g->W, &g->Ainv, &g->Ainv2, &g->inv_work, &g->rc_part, &g->zc, &g->part_cz, &g->Dc}) buf->reset();
-    g->agg = 0;
+    g->coarse.agg = 0;
     STBA_TRY(g->AdP.alloc((size_t)g->n * 36)); STBA_TRY(g->Ac0.alloc((size_t)nc * nc)); STBA_TRY(g->W.alloc((size_t)4 * np * np));
     STBA_TRY(g->Ainv.alloc((size_t)nc * nc)); STBA_TRY(g->Ainv2.alloc((size_t)nc * nc)); STBA_TRY(g->Dc.alloc((size_t)na * 36)); STBA_TRY(g->inv_work.alloc(chol_spd_inverse_workspace_doubles(np)));
     STBA_TRY(g->rc_part.alloc((size_t)na * parts * 6)); STBA_TRY(g->zc.alloc((size_t)nc)); STBA_TRY(g->part_cz.alloc((size_t)((nc + 3) / 4) * 2 + 2));
@@ -1633,7 +1566,7 @@ static int pg_setup_coarse(stba_pg* g, int group_opt) {
         STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_coarse_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PG_COARSE_BUILD_LDS_MAX));
         return STBA_OK;
     }));
-    g->agg = agg; g->na = na; g->nc = nc; g->np = np; g->parts = parts; g->max_group_ends = max_ends;
+    g->coarse = plan;
     g->coarse_valid = false;
     return STBA_OK;
 }
@@ -1698,21 +1631,21 @@ void pg_offdiag_if_stale(stba_pg* g) {
 
 // the coarse matrix P^T J^T J P from the blocks; add_nodes: with the diagonal blocks' part (several ranks: rank 0 alone)
 void pg_coarse_build(stba_pg* g, hipStream_t st, int add_nodes) {
-    hipLaunchKernelGGL(pg_coarse_build_kernel, dim3(g->na), dim3(256), pg_coarse_build_lds(g->nc, g->max_group_ends), st, g->n, g->agg, g->nc,
+    hipLaunchKernelGGL(pg_coarse_build_kernel, dim3(g->coarse.na), dim3(256), g->coarse.build_lds_bytes, st, g->n, g->coarse.agg, g->coarse.nc,
                        add_nodes, g->node_start, g->end_node, g->end_rem, g->Bend, g->Hd, g->AdP, g->Ac0);
 }
 
 // its damping term P^T D P, and W = the padded sum of the two
 void pg_coarse_damped(stba_pg* g, hipStream_t st) {
-    const size_t cnt = (size_t)3 * g->np * g->np;
-    hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->na), dim3(256), 0, st, g->n, g->agg, g->AdP, g->d, g->Dc);
-    hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g->nc, g->np, g->Ac0, g->Dc, g->W);
+    const size_t cnt = (size_t)3 * g->coarse.np * g->coarse.np;
+    hipLaunchKernelGGL(pg_coarse_dc_kernel, dim3(g->coarse.na), dim3(256), 0, st, g->n, g->coarse.agg, g->AdP, g->d, g->Dc);
+    hipLaunchKernelGGL(pg_coarse_assemble_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g->coarse.nc, g->coarse.np, g->Ac0, g->Dc, g->W);
 }
 
 // W^-1 -> Aout
 int pg_coarse_invert(stba_pg* g, hipStream_t st, double* Aout) {
-    STBA_TRY(chol_spd_inverse_dev(g->W, 2 * g->np, g->np, g->nc, g->cflag, g->inv_work, st));
-    hipLaunchKernelGGL(pg_coarse_finish_kernel, dim3((unsigned)(((size_t)g->nc * g->nc + 255) / 256)), dim3(256), 0, st, g->nc, g->np, g->W, Aout,
+    STBA_TRY(chol_spd_inverse_dev(g->W, 2 * g->coarse.np, g->coarse.np, g->coarse.nc, g->cflag, g->inv_work, st));
+    hipLaunchKernelGGL(pg_coarse_finish_kernel, dim3((unsigned)(((size_t)g->coarse.nc * g->coarse.nc + 255) / 256)), dim3(256), 0, st, g->coarse.nc, g->coarse.np, g->W, Aout,
                        g->cflag, g->cflag + 1);
     return STBA_OK;
 }
@@ -1739,20 +1672,20 @@ int pg_wait_for_job_reads(stba_pg* g) {
 // the PCG solve as one kernel: one rank, a coarse space whose groups fit a workgroup (<= 64 nodes, all their edge-end products
 // in LDS) and are all resident at once (one per CU)
 bool pg_one_kernel_eligible(stba_pg* g, const PgSolve& sv) {
-    bool pp_ok = sv.pcg.one_kernel_solve != 0 && !sv.multi && sv.coarse && g->agg <= 64 && g->na <= 256 && g->nc <= PP_NCMAX &&
-                 pp_lds_bytes(g->na, g->nc) <= (size_t)160 * 1024 - 64;
-    if (pp_ok) {
-        int dev = 0, cus = 0, lds_max = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g->na > cus) pp_ok = false;
-        // (the LDS a workgroup may opt in to is a property of the device and the driver: asked, not assumed -- advisor, round 5)
-        if (pp_ok && (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || pp_lds_bytes(g->na, g->nc) > (size_t)std::max(0, lds_max - 64))) pp_ok = false;
-        if (g->max_group_ends > PP_VCAP) pp_ok = false;
-    }
+    // the clauses that need no device first: a solve they rule out (several ranks, one_kernel_solve = 0, no coarse space) asks it nothing
+    if (!pg_one_kernel_fits(g->coarse, sv.pcg.one_kernel_solve, sv.multi, PgDeviceLimits{INT_MAX, INT_MAX})) return false;
+    // (the compute units, and the LDS a workgroup may opt in to, are properties of the device and the driver: asked, not assumed --
+    // advisor, round 5)
+    int dev = 0;
+    PgDeviceLimits lim{0, 0};
+    bool pp_ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&lim.cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+                 hipDeviceGetAttribute(&lim.lds_max_optin, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
+                 pg_one_kernel_fits(g->coarse, sv.pcg.one_kernel_solve, sv.multi, lim);
     if (pp_ok) {
         static DeviceOnce attr;
         // a device that refuses the attribute takes the launch path; that is not a failed solve
         if (attr.run([]() -> int {
-                STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_pcg_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+                STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_pcg_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS_MAX));
                 return STBA_OK;
             }) != STBA_OK) { pp_ok = false; g->pp_disabled = true; (void)hipGetLastError(); }
     }
@@ -1763,7 +1696,7 @@ bool pg_one_kernel_eligible(stba_pg* g, const PgSolve& sv) {
 int pg_solve_begin(stba_pg* g, PgSolve& sv) {
     const stba_pcg_options& pcg = sv.pcg;
     STBA_TRY(pg_setup_coarse(g, pcg.coarse_group));
-    sv.coarse = g->agg > 0;
+    sv.coarse = g->coarse.agg > 0;
     // the second stream of the coarse inverse (pg_coarse_refresh); a job of the previous solve may still be in flight: it is awaited here,
     // where it costs nothing, instead of at the end of that solve, where it would have been the last 0.3 ms of its wall time
     sv.async_inv = sv.coarse && pcg.coarse_async != 0;
@@ -1778,7 +1711,7 @@ int pg_solve_begin(stba_pg* g, PgSolve& sv) {
     sv.chunk = std::max(1, pcg.check_every);
     sv.forcing = pcg.forcing_eta0 > 0.0;
     sv.eta = pcg.forcing_eta0;
-    sv.ps.coarse_dim = sv.coarse ? g->nc : 0;
+    sv.ps.coarse_dim = sv.coarse ? g->coarse.nc : 0;
     sv.pp_ok = pg_one_kernel_eligible(g, sv);
     // (stba_lm_options::phase_timing: hipEvents around the linear solve -- the persistent kernel, or the launches of the PCG loop --
     // for bench.py's roofline of the C4 line; an event is a packet of its own on the queue, so only on request)
@@ -1794,13 +1727,13 @@ int pg_linearize_enqueue(stba_pg* g, const PgSolve& sv) {
     STBA_TRY(pg_hook(g, g->g, (size_t)g->n * 42));
     hipLaunchKernelGGL(pg_gnorm_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, 6 * g->n, g->g, g->part_c);
     if (sv.coarse) {
-        hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->agg, g->poses[g->cur], g->fixed, g->AdP);
+        hipLaunchKernelGGL(pg_coarse_basis_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->coarse.agg, g->poses[g->cur], g->fixed, g->AdP);
         pg_offdiag_if_stale(g);
         // (one rank with the coarse inverse on its second stream: the coarse MATRIX is only read by that job, and is built there --
         // 55 us of every LM iteration off the critical path; several ranks sum it with the hook, on the engine's stream)
         if (!sv.build_on_st2) {
             pg_coarse_build(g, g->st, (!g->ar || g->rank == 0) ? 1 : 0);
-            STBA_TRY(pg_hook(g, g->Ac0, (size_t)g->nc * g->nc));
+            STBA_TRY(pg_hook(g, g->Ac0, (size_t)g->coarse.nc * g->coarse.nc));
         }
         g->coarse_valid = false;
         g->ac0_valid = false;
@@ -1848,21 +1781,6 @@ int pg_job_rest(stba_pg* g, const PgSolve& sv, const PgJob& job) {
     return STBA_OK;
 }
 
-// does this iteration's PCG wait for the inverse of its OWN operator (or take the one made an LM iteration earlier)?
-// The first solve(s) wait (coarse_async = 2: not with a forcing sequence; coarse_async_after: how many LM iterations do -- the
-// operator changes most in the first iterations) -- and every solve that follows a LONG step: the operator is stale by exactly the
-// step that was just taken.  At C4 (profiles/r6_c4_async.txt) the steps of the first three iterations take 98 %, 97 % and 45 % off
-// the cost, the later ones 1 % and less; preconditioning iteration 3 with iteration 2's operator ends 3.9e-5 from the exact-step
-// poses, iterations 4 .. 9 with their predecessors' 2.9e-6 (in line: 2.5e-6).  Rule: lag only behind a step that took at most
-// coarse_async_decrease (0.5) off the cost.
-// (also measured, profiles/r6_c4_async_coarse_tolerance_behind_long_steps.txt: not waiting behind a long step either and
-// giving THAT solve a tolerance on the coarse residual instead -- 3e-4 is what the poses need (2.4e-6), and then the extra
-// PCG iterations cost more than the wait: 1323 against 1411 LM it/s)
-bool pg_waits_for_own_inverse(const stba_pcg_options& pcg, bool forcing, int jobs, int iter, double last_rel_decrease) {
-    const bool long_step = iter <= pcg.coarse_async_after || last_rel_decrease > pcg.coarse_async_decrease;
-    return (jobs == 0 && (!forcing || pcg.coarse_async != 2)) || (pcg.coarse_async != 2 && long_step);
-}
-
 // ---- coarse operator (P^T (J^T J + D) P)^-1 of an LM iteration
 int pg_coarse_refresh(stba_pg* g, PgSolve& sv, bool head_was_done, PgCoarseUse* use) {
     use->Ainv = g->Ainv;
@@ -1882,7 +1800,7 @@ int pg_coarse_refresh(stba_pg* g, PgSolve& sv, bool head_was_done, PgCoarseUse* 
         const int wbuf = sv.jobs & 1;
         double* Aw = wbuf ? g->Ainv2 : g->Ainv;
         double* Ar = wbuf ? g->Ainv : g->Ainv2;        // written by the previous job (or zeroed below)
-        if (sv.jobs == 0) STBA_HIP(hipMemsetAsync(Ar, 0, (size_t)g->nc * g->nc * sizeof(double), g->st));
+        if (sv.jobs == 0) STBA_HIP(hipMemsetAsync(Ar, 0, (size_t)g->coarse.nc * g->coarse.nc * sizeof(double), g->st));
         else STBA_TRY(pg_wait_if_pending(g->st, g->ev_job[(sv.jobs - 1) & 1]));
         const bool own = pg_waits_for_own_inverse(sv.pcg, sv.forcing, sv.jobs, sv.iter, sv.last_rel_decrease);
         if (!sv.build_on_st2) pg_coarse_damped(g, g->st);
@@ -1921,13 +1839,13 @@ int pg_pcg_by_launches(stba_pg* g, const PgSolve& sv, const double* Ainv_use, do
     // block can be taken back: the wait below must not see the previous solve's tick count and `done`)
     g->exp.zero();
     std::atomic_thread_fence(std::memory_order_seq_cst);
-    hipLaunchKernelGGL(pg_pcg_init4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, g->g, g->Minv, AdP, g->x, g->rr, g->z,
+    hipLaunchKernelGGL(pg_pcg_init4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, g->g, g->Minv, AdP, g->x, g->rr, g->z,
                        g->rc_part, g->part_a);
     if (coarse)
-        hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, (const PcgState*)nullptr, Ainv_use, g->rc_part,
+        hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->coarse.nc + 3) / 4), dim3(256), 0, g->st, g->coarse.nc, g->coarse.parts, (const PgPcgState*)nullptr, Ainv_use, g->rc_part,
                            g->zc, g->part_cz);
-    hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
-                       g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+    hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
+                       g->nb_nodes4, g->part_a, (g->coarse.nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
     STBA_HIP(hipGetLastError());
     int enq = 0;
     bool pcg_done = false;
@@ -1942,21 +1860,21 @@ int pg_pcg_by_launches(stba_pg* g, const PgSolve& sv, const double* Ainv_use, do
             if (!sv.multi) {
                 hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u,
                                    g->part_c, g->state);
-                hipLaunchKernelGGL(pg_pcg_update4_kernel<true>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_edges,
+                hipLaunchKernelGGL(pg_pcg_update4_kernel<true>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->coarse.agg, slot, g->state, g->nb_edges,
                                    g->part_c, g->nb_nodes4, g->part_d, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, (const double*)nullptr,
                                    g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
             } else {
                 STBA_TRY(pg_apply(g, g->p, g->q, true));
                 hipLaunchKernelGGL(pg_dot_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, 6 * g->n, g->p, g->q, g->part_c);
-                hipLaunchKernelGGL(pg_pcg_update4_kernel<false>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->agg, slot, g->state, g->nb_vec,
+                hipLaunchKernelGGL(pg_pcg_update4_kernel<false>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->coarse.agg, slot, g->state, g->nb_vec,
                                    g->part_c, 0, (const double*)nullptr, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, g->q,
                                    g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
             }
             if (coarse)
-                hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->nc + 3) / 4), dim3(256), 0, g->st, g->nc, g->parts, g->state, Ainv_use, g->rc_part, g->zc,
+                hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->coarse.nc + 3) / 4), dim3(256), 0, g->st, g->coarse.nc, g->coarse.parts, g->state, Ainv_use, g->rc_part, g->zc,
                                    g->part_cz);
-            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->agg, slot, 0, eta_k, pcg.max_iterations, g->state,
-                               g->exp.dev, g->nb_nodes4, g->part_a, (g->nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, slot, 0, eta_k, pcg.max_iterations, g->state,
+                               g->exp.dev, g->nb_nodes4, g->part_a, (g->coarse.nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
         }
         STBA_HIP(hipGetLastError());
         // one rank: the host looks at the chunk BEFORE the one it has just enqueued (the stream never runs dry; the kernels of a
@@ -1975,13 +1893,13 @@ int pg_pcg_one_kernel(stba_pg* g, const PgSolve& sv, const double* Ainv_use, dou
     const stba_pcg_options& pcg = sv.pcg;
     pg_offdiag_if_stale(g);
     if (g->pp_base > (1 << 30)) {        // (stamps only grow; long before they wrap they are taken back to zero)
-        STBA_HIP(hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
-        STBA_HIP(hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st));
+        STBA_HIP(hipMemsetAsync(g->ustamp, 0, PP_GROUPS_MAX * PP_STAMP * sizeof(int), g->st));
+        STBA_HIP(hipMemsetAsync(g->pstamp, 0, PP_GROUPS_MAX * PP_STAMP * sizeof(int), g->st));
         g->pp_base = 0;
     }
     PpArgs a;
-    a.n = g->n; a.agg = g->agg; a.log2agg = 0; while ((1 << a.log2agg) < g->agg) ++a.log2agg;
-    a.na = g->na; a.nc = g->nc; a.base = g->pp_base; a.max_iters = pcg.max_iterations; a.eta = eta_k;
+    a.n = g->n; a.agg = g->coarse.agg; a.log2agg = 0; while ((1 << a.log2agg) < g->coarse.agg) ++a.log2agg;
+    a.na = g->coarse.na; a.nc = g->coarse.nc; a.base = g->pp_base; a.max_iters = pcg.max_iterations; a.eta = eta_k;
     a.node_start = g->node_start; a.end_rem = g->end_rem; a.Bend = g->Bend; a.Hd = g->Hd; a.d = g->d; a.Minv = g->Minv; a.AdP = g->AdP;
     a.Ainv = Ainv_use; a.g = g->g; a.x = g->x; a.ubuf = g->ubuf; a.pbuf = g->pbuf; a.ustamp = g->ustamp; a.pstamp = g->pstamp;
     a.state = g->state; a.spin_limit = pcg.one_kernel_solve == 2 ? 0 : 25000000ll;      // (a quarter of a second of wall_clock64 ticks; 2: the test of the way back)
@@ -1995,7 +1913,7 @@ int pg_pcg_one_kernel(stba_pg* g, const PgSolve& sv, const double* Ainv_use, dou
         a.tdbg = tdbg_dev;
     }
 #endif
-    hipLaunchKernelGGL(pg_pcg_persistent_kernel, dim3(g->na), dim3(PP_T), pp_lds_bytes(g->na, g->nc), g->st, a);
+    hipLaunchKernelGGL(pg_pcg_persistent_kernel, dim3(g->coarse.na), dim3(PP_T), pp_lds_bytes(g->coarse.na, g->coarse.nc), g->st, a);
 #ifdef STBA_DEBUG_KNOBS
     if (a.tdbg) {
         long long h[8];
@@ -2014,29 +1932,13 @@ int pg_pcg_one_kernel(stba_pg* g, const PgSolve& sv, const double* Ainv_use, dou
 int pg_trial_point(stba_pg* g) {
     const int nxt = g->cur ^ 1;
     hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->x, g->u, g->part_b,
-                       (const PcgState*)nullptr);
+                       (const PgPcgState*)nullptr);
     hipLaunchKernelGGL(pg_update4_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->poses[g->cur], g->x, g->g, g->fixed, g->poses[nxt], g->part_u);
     STBA_TRY(pg_linearize(g, nxt, false));
     g->seq += 1.0;
     hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
                        g->state, g->ar ? g->scal_dev : g->fin.dev, g->seq);
     return pg_read_block(g, 2, 8);      // (several ranks: cost and |J x|^2 summed over the edge shards)
-}
-
-// forcing sequence (Eisenstat & Walker, choice 2) behind an accepted step: eta_{k+1} = 0.9 (|g_{k+1}| / |g_k|)^2 with their
-// safeguard, kept in [eta_min, eta0]; after a rejected step the gradient has not moved and eta stays
-double pg_next_eta(const stba_pcg_options& pcg, const stba_lm_options& opt, double eta, double g2, double g2_new, double cost_change,
-                   double new_cost) {
-    if (!(pcg.forcing_eta0 > 0.0 && g2 > 0.0 && std::isfinite(g2_new))) return eta;
-    double e2 = 0.9 * g2_new / g2;
-    if (0.9 * eta * eta > 0.1) e2 = std::max(e2, 0.9 * eta * eta);
-    eta = std::min(pcg.forcing_eta0, std::max(pcg.forcing_eta_min, e2));
-    // (round 6) about to converge -- the step just taken changed the cost by less than 100 x the function tolerance: the
-    // error of the LAST inexact step is what the converged poses keep (about eta x its length; on C4 the last step still
-    // moves poses by 3.6e-3, and Eisenstat & Walker leave eta ~ 1e-2 there: 4e-5 in the poses, north_star asks for 1e-5)
-    if (pcg.forcing_eta_final > 0.0 && cost_change <= 100.0 * opt.function_tolerance * (new_cost + cost_change))
-        eta = std::max(pcg.forcing_eta_min, std::min(eta, pcg.forcing_eta_final));
-    return eta;
 }
 }  // namespace
 
@@ -2077,35 +1979,23 @@ static int pg_fill(stba_pg* g, int n_nodes, int n_edges, const double* poses, co
     STBA_TRY(g->node_start.alloc(n + 1)); STBA_TRY(g->end_code.alloc(2 * m)); STBA_TRY(g->u.alloc(12 * m));
     STBA_TRY(g->end_node.alloc(2 * m)); STBA_TRY(g->contrib.alloc(2 * m * 28));
     STBA_TRY(g->end_pos.alloc(2 * m)); STBA_TRY(g->end_rem.alloc(2 * m)); STBA_TRY(g->Bend.alloc(72 * m)); STBA_TRY(g->ubuf.alloc(12 * n));
-    STBA_TRY(g->pbuf.alloc((size_t)2 * 256 * PP_SLOT)); STBA_TRY(g->ustamp.alloc((size_t)256 * PP_STAMP)); STBA_TRY(g->pstamp.alloc((size_t)256 * PP_STAMP));
-    if (hipMemsetAsync(g->ustamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess ||
-        hipMemsetAsync(g->pstamp, 0, 256 * PP_STAMP * sizeof(int), g->st) != hipSuccess)
+    STBA_TRY(g->pbuf.alloc((size_t)2 * PP_GROUPS_MAX * PP_SLOT)); STBA_TRY(g->ustamp.alloc((size_t)PP_GROUPS_MAX * PP_STAMP)); STBA_TRY(g->pstamp.alloc((size_t)PP_GROUPS_MAX * PP_STAMP));
+    if (hipMemsetAsync(g->ustamp, 0, PP_GROUPS_MAX * PP_STAMP * sizeof(int), g->st) != hipSuccess ||
+        hipMemsetAsync(g->pstamp, 0, PP_GROUPS_MAX * PP_STAMP * sizeof(int), g->st) != hipSuccess)
         return fail(STBA_ERR_HIP, "stba_pg_create: memset");
     g->nb_nodes4 = (n_nodes + PG_NPW - 1) / PG_NPW;
     STBA_TRY(g->part_u.alloc((size_t)g->nb_nodes * 4 + 4)); STBA_TRY(g->scal_dev.alloc(16)); STBA_TRY(g->state.alloc(1)); STBA_TRY(g->cflag.alloc(2));
     if (g->exp.alloc((size_t)stamped_doubles(PX_COUNT)) != STBA_OK || g->fin.alloc(16) != STBA_OK)
         return fail(STBA_ERR_ALLOC, "stba_pg_create: mapped host memory");
     memset(&g->last_pcg, 0, sizeof g->last_pcg);
-    {   // edge ends sorted by node (counting sort; stable: a node's ends in edge order)
-        std::vector<int> start((size_t)n_nodes + 1, 0), code(2 * m);
-        for (int e = 0; e < n_edges; ++e) { ++start[(size_t)edge_i[e] + 1]; ++start[(size_t)edge_j[e] + 1]; }
-        for (int i = 0; i < n_nodes; ++i) start[(size_t)i + 1] += start[(size_t)i];
-        std::vector<int> fill(start.begin(), start.end() - 1), owner(2 * m), pos(2 * m), rem(2 * m);
-        for (int e = 0; e < n_edges; ++e) {
-            owner[(size_t)fill[(size_t)edge_i[e]]] = edge_i[e];
-            rem[(size_t)fill[(size_t)edge_i[e]]] = edge_j[e];
-            pos[(size_t)2 * e] = fill[(size_t)edge_i[e]];
-            code[(size_t)fill[(size_t)edge_i[e]]++] = 2 * e;
-            owner[(size_t)fill[(size_t)edge_j[e]]] = edge_j[e];
-            rem[(size_t)fill[(size_t)edge_j[e]]] = edge_i[e];
-            pos[(size_t)2 * e + 1] = fill[(size_t)edge_j[e]];
-            code[(size_t)fill[(size_t)edge_j[e]]++] = 2 * e + 1;
-        }
-        g->h_node_start = start;
-        if (upload(g->end_pos, pos.data(), 2 * m, g->st) != STBA_OK || upload(g->end_rem, rem.data(), 2 * m, g->st) != STBA_OK ||
-            upload(g->node_start, start.data(), n + 1, g->st) != STBA_OK || upload(g->end_code, code.data(), 2 * m, g->st) != STBA_OK ||
-            upload(g->end_node, owner.data(), 2 * m, g->st) != STBA_OK || hipStreamSynchronize(g->st) != hipSuccess)
+    {   // the edge ends sorted by node (pg_plan.hpp)
+        PgEnds ends;
+        pg_build_ends(n_nodes, n_edges, edge_i, edge_j, &ends);
+        if (upload(g->end_pos, ends.end_pos.data(), 2 * m, g->st) != STBA_OK || upload(g->end_rem, ends.end_rem.data(), 2 * m, g->st) != STBA_OK ||
+            upload(g->node_start, ends.node_start.data(), n + 1, g->st) != STBA_OK || upload(g->end_code, ends.end_code.data(), 2 * m, g->st) != STBA_OK ||
+            upload(g->end_node, ends.end_node.data(), 2 * m, g->st) != STBA_OK || hipStreamSynchronize(g->st) != hipSuccess)
             return fail(STBA_ERR_HIP, "stba_pg_create: upload failed");
+        g->node_start_host.swap(ends.node_start);
     }
     if (upload(g->poses[0], poses, n * 7, g->st) != STBA_OK || upload(g->ei, edge_i, m, g->st) != STBA_OK ||
         upload(g->ej, edge_j, m, g->st) != STBA_OK || upload(g->meas, meas, m * 7, g->st) != STBA_OK ||
@@ -2115,7 +2005,7 @@ static int pg_fill(stba_pg* g, int n_nodes, int n_edges, const double* poses, co
     // a dozen allocations (the 33 MB inversion workspace among them), a stream and four events -- ~ 0.4 ms of a 6.4 ms C4 solve
     // on a fresh engine, inside the time every caller and bench.py measure.  (A solve with another group size makes its own; a
     // graph too large for the default space is told so by the solve, not here.)
-    if (pg_setup_coarse(g, 0) == STBA_OK && g->agg > 0) (void)pg_second_stream(g);
+    if (pg_setup_coarse(g, 0) == STBA_OK && g->coarse.agg > 0) (void)pg_second_stream(g);
     (void)hipStreamSynchronize(g->st);
     return STBA_OK;
 }
@@ -2126,9 +2016,7 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
     *out = nullptr;
     if (n_nodes <= 0 || n_edges <= 0 || !poses || !edge_i || !edge_j || !meas)
         return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_create: null or empty input");
-    for (int e = 0; e < n_edges; ++e)
-        if (edge_i[e] < 0 || edge_i[e] >= n_nodes || edge_j[e] < 0 || edge_j[e] >= n_nodes || edge_i[e] == edge_j[e])
-            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_create: bad edge");
+    if (pg_check_edges(n_nodes, n_edges, edge_i, edge_j) >= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_create: bad edge");
     STBA_TRY(require_device());
     stba_pg* g = new stba_pg();
     g->n = n_nodes; g->m = n_edges;
@@ -2201,12 +2089,12 @@ int stba_pg_time_kernels(stba_pg* g, int reps, double* ms_linearize, double* ms_
     // the product as the one-rank solve runs it: the edge kernel (t_e, u_e = J_e^T t_e, |t_e|^2) -- the node kernel gathers u
     // while it updates x, r, z and is not a product kernel of its own
     int rc = STBA_OK;
-    hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u, g->part_c, (const PcgState*)nullptr);
+    hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u, g->part_c, (const PgPcgState*)nullptr);
     if (hipEventRecord(e0, g->st) != hipSuccess) rc = fail(STBA_ERR_HIP, "hipEventRecord");
     for (int k = 0; k < reps && rc == STBA_OK; ++k) rc = pg_linearize(g, g->cur, true);
     if (rc == STBA_OK && hipEventRecord(e1, g->st) != hipSuccess) rc = fail(STBA_ERR_HIP, "hipEventRecord");
     for (int k = 0; k < reps && rc == STBA_OK; ++k)
-        hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u, g->part_c, (const PcgState*)nullptr);
+        hipLaunchKernelGGL(pg_edge_product_kernel, dim3(g->nb_edges), dim3(256), 0, g->st, g->m, g->ei, g->ej, g->Ji, g->Jj, g->p, g->u, g->part_c, (const PgPcgState*)nullptr);
     if (rc == STBA_OK && hipEventRecord(e2, g->st) != hipSuccess) rc = fail(STBA_ERR_HIP, "hipEventRecord");
     if (rc == STBA_OK && hipStreamSynchronize(g->st) != hipSuccess) rc = fail(STBA_ERR_HIP, "hipStreamSynchronize");
     float a = 0.f, b = 0.f;

@@ -41,6 +41,11 @@ def madd(*terms):
     return [[mp.fsum(c * M[i][j] for c, M in terms) for j in range(3)] for i in range(3)]
 
 
+def chol6_T(A):
+    """W = L^T (mp.matrix, upper triangular) of the symmetric positive definite A = L L^T, from A's FP64 entries as they are"""
+    return mp.cholesky(mp.matrix(np.asarray(A, float).tolist())).T
+
+
 def hat(v):
     return [[ZERO, -v[2], v[1]], [v[2], ZERO, -v[0]], [-v[1], v[0], ZERO]]
 

@@ -8,6 +8,13 @@ the thread sanitizer, which must run without a report and print the same.
   pose, W    pose7_check_normalise and sqrt_information6 on a row per branch; codes and texts against the same golden file (as the
              setters gave them before the checks moved), W in every bit what prior_information_factor gives
   grouping   group_csr against a stable numpy argsort, by camera and by unordered pair
+  6 x 6      prior_information_factor = information6_factor (dd6.hpp, the one double-double factorisation of the tree: the pose graph's kernel calls the same
+             function) against the 50-digit Cholesky factor (mp_ref.chol6_T), well conditioned and at cond 1e12: every entry of W within
+             FACTOR6_BOUND = 1 eps of the exact one, relative -- 1/2 eps is the rounding of the double-double result to FP64, the
+             other half is room for the double-double arithmetic's own error, about cond 2^-104 per operation, 1e-19 at cond 1e12;
+             an FP64 Cholesky must MISS the bound at cond 1e12 (it loses cond eps), or the bound would not notice a dropped low word.
+             Also W^T W, formed at 50 digits, within the 1e-13 of the matrix that test_sqrt_information_rows holds
+             sqrt_information6 to, on matrices of that case's scale; rank-deficient matrices and a NaN are refused
   2 x 2      ba_information_factor within the 4 eps per entry its comment claims of the 50-digit factor (ba_information_ref.chol2_mp,
              mpmath at mp_ref's 50 digits), condition numbers 1 to 1e15; the refused matrices"""
 import ctypes
@@ -19,7 +26,7 @@ import numpy as np
 import pytest
 
 import ba_information_ref as I
-import mp_ref  # noqa: F401  (mp.dps = 50)
+import mp_ref  # (mp.dps = 50)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SANITIZERS = {"plain": [], "asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"], "tsan": ["-fsanitize=thread", "-g"]}
@@ -75,6 +82,23 @@ SQRT6 = {"valid_information": ("I", spd6(3)), "valid_sqrt": ("S", np.random.defa
          "rank_deficient_sqrt": ("S", RANK_DEFICIENT), "neither": ("N", None)}
 
 
+def spd6_cond(kappa, seed):
+    """Q diag(lambda) Q^T with lambda log-spaced from 10 down to 10 / kappa, exactly symmetric"""
+    Q, _ = np.linalg.qr(np.random.default_rng(seed).normal(size=(6, 6)))
+    A = Q @ np.diag(10.0 ** (1.0 - np.linspace(0.0, np.log10(kappa), 6))) @ Q.T
+    return 0.5 * (A + A.T)
+
+
+NAN6 = spd6(3); NAN6[4, 1] = np.nan                       # in the lower triangle, which is factored
+NAN6_UPPER = spd6(3); NAN6_UPPER[1, 4] = np.nan           # in the upper one, which is not: refused all the same
+SINGULAR_BLOCK = np.eye(6); SINGULAR_BLOCK[:2, :2] = [[4.0, 2.0], [2.0, 1.0]]      # the second pivot is 1 - 1 exactly
+FACTOR6_BOUND = 1.0          # eps, relative, per entry of W against the 50-digit factor (the module's docstring)
+FACTOR6_GOOD = {"spd6_3": spd6(3), "spd6_7": spd6(7), "identity": np.eye(6), "cond_1e2": spd6_cond(1e2, 11), "cond_1e6": spd6_cond(1e6, 12),
+                "cond_1e12": spd6_cond(1e12, 13), "cond_1e12_b": spd6_cond(1e12, 14)}
+FACTOR6_REFUSED = {"rank_3_diagonal": (RANK_DEFICIENT, NPD), "rank_1_ones": (np.ones((6, 6)), NPD), "rank_5_block": (SINGULAR_BLOCK, NPD),
+                   "indefinite": (INDEFINITE, NPD), "nan_lower": (NAN6, INV), "nan_upper": (NAN6_UPPER, INV), "inf": (INF6, INV)}
+
+
 def omega2(kappa, phi=0.7, scale=3.0):
     Q = I.rot(np.array([phi]))[0]
     Om = Q @ np.diag([1.0, 1.0 / kappa]) @ Q.T * scale
@@ -102,6 +126,10 @@ def case_lines():
             lines.append(f"pose7 {what} {hexes(p)}"); names.append(("pose7", what.replace("_", " "), k))
     for k, (mode, m) in SQRT6.items():
         lines.append(f"sqrt6 {mode}" + ("" if m is None else " " + hexes(m))); names.append(("sqrt6", k))
+    for k, m in FACTOR6_GOOD.items():
+        lines.append(f"sqrt6 I {hexes(m)}"); names.append(("factor6", k))
+    for k, (m, _) in FACTOR6_REFUSED.items():
+        lines.append(f"sqrt6 I {hexes(m)}"); names.append(("factor6", k))
     for kap in KAPPAS:
         lines.append(f"info2 {hexes(omega2(kap))}"); names.append(("info2", kap))
     for k, m in INFO2_BAD.items():
@@ -232,6 +260,33 @@ def test_sqrt_information_rows(runs, golden):
             assert (get(k)["rc"], f"{who}: {row} 1: " + get(k)["why"]) == golden_error(golden, who, k)
             assert get(k)["rc"] == code
     assert not get("indefinite_information")["direct_ok"] and not get("inf_information")["direct_ok"]
+
+
+def test_information6_factor_against_the_50_digit_factor(runs):
+    mp = mp_ref.mp
+    res = runs["plain"][1]
+    for k, Om in FACTOR6_GOOD.items():
+        r = res[("factor6", k)]
+        assert r["rc"] == 0 and r["direct_ok"] and r["W"] == r["direct"], k
+        W = floats(r["direct"]).reshape(6, 6)
+        assert np.all(np.tril(W, -1) == 0) and np.all(np.diag(W) > 0), k
+        assert mp.mp.dps == 50
+        Wm, Am = mp.matrix(W.tolist()), mp.matrix(Om.tolist())
+        back = max(abs((Wm.T * Wm)[a, b] - Am[a, b]) for a in range(6) for b in range(a + 1))      # (the lower triangle is what is factored)
+        W50 = mp_ref.chol6_T(Om)
+        rel = lambda X: max(float(abs(mp.mpf(float(X[a, b])) - W50[a, b]) / abs(W50[a, b])) for a in range(6) for b in range(a, 6) if W50[a, b] != 0)
+        assert all(W[a, b] == 0.0 for a in range(6) for b in range(a, 6) if W50[a, b] == 0), "a zero of the exact factor is a zero"
+        fwd, fwd64 = rel(W), rel(np.linalg.cholesky(Om).T)
+        print(f"information6_factor {k}: cond {np.linalg.cond(Om):.2e}  |W^T W - Omega| {float(back):.2e}  worst entry against the 50-digit factor "
+              f"{fwd / EPS:.2f} eps (an FP64 Cholesky: {fwd64 / EPS:.3g} eps)")
+        assert np.abs(Om).max() <= 20.0, "the scale at which 1e-13 is the bound (spd6's)"
+        assert float(back) <= 1e-13, k
+        assert fwd <= FACTOR6_BOUND * EPS, (k, fwd / EPS)
+        if k.startswith("cond_1e12"):
+            assert np.linalg.cond(Om) > 5e11 and fwd64 > 1e6 * FACTOR6_BOUND * EPS, "an FP64 factorisation misses the bound here by far"
+    for k, (Om, code) in FACTOR6_REFUSED.items():
+        r = res[("factor6", k)]
+        assert not r["direct_ok"] and r["rc"] == code, k
 
 
 # ------------------------------------------------------------------------------------------ grouping
