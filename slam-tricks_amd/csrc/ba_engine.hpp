@@ -1,6 +1,6 @@
 // ba_engine.hpp -- the bundle-adjustment engine object behind the opaque stba_ba of include/stba.h, and the few helpers its entry
-// points share.  Private to stba_engine.hip (creation, the linearisation, the reduced system, the LM and DOGLEG loops) and
-// ba_factors.hip (the factor setters); no kernel is declared or defined here.
+// points share.  Private to stba_engine.hip (creation, the linearisation, the reduced system, the LM and DOGLEG loops, the inner
+// iterations and every other stba_ba_* entry point) and ba_factors.hip (the factor setters); no kernel is declared or defined here.
 #pragma once
 #include <memory>
 #include <vector>
@@ -10,6 +10,7 @@
 #include "ba_between.hpp"
 #include "iterative_schur.hpp"
 #include "ba_features.hpp"
+#include "inner_plan.hpp"
 
 namespace stba {
 
@@ -59,6 +60,21 @@ struct BetweenSet {
     BetweenArgs args(const unsigned char* cam_fixed) const {
         return BetweenArgs{n, n_cg, n_pg, i, j, meas, W, cg_ptr, cg_cam, cg_ref, pg_ptr, pg_pair, pg_ref, cam_fixed};
     }
+};
+
+// inner iterations (stba_ba_set_inner_iterations; inner_iterations.hip): the ordering as per-group ranges of a
+// camera list (with each entry's dof mask) and a landmark list, in ascending group id (plan: the host's copy, inner_plan.hpp; cam,
+// pt, mask: the device's); the entries' iteration counts; the gate of the sweep behind a trial point, its two scalars {cost2 at x*,
+// |x - x*|^2} and the partials of the latter; the events around a timed sweep and the summary of the last solve
+struct InnerSet {
+    bool on = false;
+    double tol = 1e-3;
+    InnerPlan plan;
+    DevBuf<int> cam, pt, it, gate;
+    DevBuf<unsigned char> mask;
+    DevBuf<double> sc, part;
+    hipEvent_t ev[2] = {};
+    stba_inner_summary sum{};
 };
 
 }  // namespace stba
@@ -158,20 +174,7 @@ struct stba_ba {
     MappedBuffer dl_host;
     double dl_seq = 0.0;
     stba_dogleg_summary dl_sum{};
-    // inner iterations (stba_ba_set_inner_iterations; inner_iterations.hip): the ordering as per-group ranges of a
-    // camera list (with each entry's dof mask) and a landmark list, in ascending group id; the entries' iteration counts; the gate of
-    // the sweep behind a trial point, its two scalars {cost2 at x*, |x - x*|^2} and the partials of the latter
-    bool inner_on = false;
-    double inner_tol = 1e-3;
-    struct InnerGroup { int cam_lo, cam_hi, pt_lo, pt_hi; };
-    std::vector<InnerGroup> inner_groups;
-    std::vector<int> inner_cam_h, inner_pt_h;
-    std::vector<unsigned char> inner_mask_h, inner_kind_h;   // kind: 1 rotation, 2 position, 3 both (a 6-dof block)
-    DevBuf<int> inner_cam, inner_pt, inner_it, inner_gate;
-    DevBuf<unsigned char> inner_mask;
-    DevBuf<double> inner_sc, inner_part;
-    hipEvent_t inner_ev[2] = {};
-    stba_inner_summary inner_sum{};
+    InnerSet inner;
     // With priors the cost partials carry ONE more slot behind the lineariser's lin_grid (n_cost), filled by the cost form at every
     // linearisation; the block form adds to Hcc, gc behind the Schur step at lin_which, the parameter buffer the Jacobian records
     // were last made at
@@ -233,7 +236,7 @@ inline const double* ba_general_jc(const stba_ba* b) { return ba_wants_general_f
 
 // `who` asks for its feature (sets: it sets it, false: it clears it) on this engine: STBA_OK, or the refusal of ba_features.hpp
 inline int ba_refuse(const stba_ba* b, const char* who, bool sets = true) {
-    const unsigned held = ba_held_features(b->iterative, b->trust_region == STBA_TR_TRADITIONAL_DOGLEG, b->inner_on, b->hl_fn != nullptr,
+    const unsigned held = ba_held_features(b->iterative, b->trust_region == STBA_TR_TRADITIONAL_DOGLEG, b->inner.on,b->hl_fn != nullptr,
                                            b->ar != nullptr, b->loss.kind.get() != nullptr, b->winfo.get() != nullptr, b->prior.n, b->btw.n);
     std::string why;
     const int code = ba_conflict(who, held, &why, sets);

@@ -1,4 +1,6 @@
-// stba_engine.hip -- host side of the MI355X NLS engine and its C ABI (include/stba.h).
+// stba_engine.hip -- host side of the bundle-adjustment engine of the MI355X NLS library: the stba_ba_* part of the C ABI
+// (include/stba.h; the factor setters are ba_factors.hip) and the process-wide entry points (status strings, the last error, the
+// version, the device functions, the default LM options).  The dense entry points are dense_engine.hip, calibration is calib.hip.
 // The Levenberg-Marquardt control flow follows Ceres' TrustRegionMinimizer +
 // LevenbergMarquardtStrategy (the solver behind ceres::Solve at
 // st20-g2o/src/include/test_ceres.h:148 and st17-ceres/src/include/solver.hpp:286) with the
@@ -45,7 +47,7 @@ static void ba_free(stba_ba* b) {
     b->create_leftovers.reset();                        // (what ba_create's plan left on the host)
     std::vector<unsigned char>().swap(b->create_omask);
     cov_store_free(b->cov);
-    for (auto& e : b->inner_ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : b->inner.ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_ar) if (e) (void)hipEventDestroy(e);
     b->pcg_host.release();
@@ -581,33 +583,33 @@ static InnerObs inner_obs_args(const stba_ba* b) {
 // verdict on the trial point (0: every workgroup returns at once)
 static int ba_inner_sweep_enqueue(stba_ba* b, int which, const int* gate) {
     const InnerObs o = inner_obs_args(b);
-    const int n_cam_entries = (int)b->inner_cam_h.size();
-    for (const auto& g : b->inner_groups) {
-        STBA_TRY(launch_inner_cameras(o, g.cam_hi - g.cam_lo, b->inner_cam + g.cam_lo, b->inner_mask + g.cam_lo, b->cams[which],
-                                      b->pts[which], b->inner_it + g.cam_lo, gate, b->st));
-        STBA_TRY(launch_inner_points(o, g.pt_hi - g.pt_lo, b->inner_pt + g.pt_lo, b->cams[which], b->pts[which],
-                                     b->inner_it + n_cam_entries + g.pt_lo, gate, b->st));
+    const int n_cam_entries = (int)b->inner.plan.cam.size();
+    for (const auto& g : b->inner.plan.groups) {
+        STBA_TRY(launch_inner_cameras(o, g.cam_hi - g.cam_lo, b->inner.cam + g.cam_lo, b->inner.mask + g.cam_lo, b->cams[which],
+                                      b->pts[which], b->inner.it + g.cam_lo, gate, b->st));
+        STBA_TRY(launch_inner_points(o, g.pt_hi - g.pt_lo, b->inner.pt + g.pt_lo, b->cams[which], b->pts[which],
+                                     b->inner.it + n_cam_entries + g.pt_lo, gate, b->st));
     }
     return STBA_OK;
 }
 // behind the trial point x+ in buffer cur ^ 1 (enqueued before the host reads the trial block): the gate, the sweep x+ -> x*, the
-// cost at x* by the trial pass's residual kernel -> inner_sc[0] (cost2), and the ambient |x - x*|^2 -> inner_sc[1]
+// cost at x* by the trial pass's residual kernel -> inner.sc[0] (cost2), and the ambient |x - x*|^2 -> inner.sc[1]
 static int ba_inner_after_trial(stba_ba* b) {
     const int cur = b->cur, nxt = cur ^ 1;
-    STBA_TRY(launch_inner_gate(b->trial, b->flag, TS_COST2, TS_MODEL, TS_CAM + 2, b->inner_gate, b->st));
-    STBA_TRY(ba_inner_sweep_enqueue(b, nxt, b->inner_gate));
-    STBA_TRY(ba_cost_only(b, nxt, b->inner_sc));
-    STBA_TRY(launch_inner_step2(b->nc, b->np, b->cams[cur], b->pts[cur], b->cams[nxt], b->pts[nxt], b->inner_part, b->st));
-    return launch_sum_partials(b->inner_part, inner_step_grid(b->nc, b->np), 1, 1, b->inner_sc + 1, b->st);
+    STBA_TRY(launch_inner_gate(b->trial, b->flag, TS_COST2, TS_MODEL, TS_CAM + 2, b->inner.gate, b->st));
+    STBA_TRY(ba_inner_sweep_enqueue(b, nxt, b->inner.gate));
+    STBA_TRY(ba_cost_only(b, nxt, b->inner.sc));
+    STBA_TRY(launch_inner_step2(b->nc, b->np, b->cams[cur], b->pts[cur], b->cams[nxt], b->pts[nxt], b->inner.part, b->st));
+    return launch_sum_partials(b->inner.part, inner_step_grid(b->nc, b->np), 1, 1, b->inner.sc + 1, b->st);
 }
 static void inner_summary_reset(stba_ba* b) {
-    b->inner_sum = stba_inner_summary{};
-    b->inner_sum.struct_size = sizeof(stba_inner_summary);
-    b->inner_sum.disabled_at_iteration = -1;
-    b->inner_sum.num_groups = (int)b->inner_groups.size();
-    for (int g = 0; g < b->inner_sum.num_groups && g < STBA_INNER_MAX_GROUPS_REPORTED; ++g) {
-        const auto& r = b->inner_groups[(size_t)g];
-        b->inner_sum.group_size[g] = (r.cam_hi - r.cam_lo) + (r.pt_hi - r.pt_lo);
+    b->inner.sum = stba_inner_summary{};
+    b->inner.sum.struct_size = sizeof(stba_inner_summary);
+    b->inner.sum.disabled_at_iteration = -1;
+    b->inner.sum.num_groups = (int)b->inner.plan.groups.size();
+    for (int g = 0; g < b->inner.sum.num_groups && g < STBA_INNER_MAX_GROUPS_REPORTED; ++g) {
+        const auto& r = b->inner.plan.groups[(size_t)g];
+        b->inner.sum.group_size[g] = (r.cam_hi - r.cam_lo) + (r.pt_hi - r.pt_lo);
     }
 }
 
@@ -814,12 +816,12 @@ static int ba_factor_solve(stba_ba* b, int* pcg_fail) {
 // isc = {cost2 at x*, |x - x*|^2}.  Returns whether the sweep brought the candidate below the current cost
 static bool ba_inner_verdict(stba_ba* b, const BaSolve& sv, const double* isc, TrialScalars& t, bool* inner_active) {
     const double inner_cost = 0.5 * isc[0];
-    ++b->inner_sum.sweeps;
+    ++b->inner.sum.sweeps;
     t.model_change += t.new_cost - inner_cost;
     const double progress = 1.0 - inner_cost / t.new_cost;
     t.new_cost = inner_cost;
     t.step_norm = std::sqrt(isc[1]);
-    if (!(progress > b->inner_tol)) { *inner_active = false; b->inner_sum.disabled_at_iteration = sv.iter; }
+    if (!(progress > b->inner.tol)) { *inner_active = false; b->inner.sum.disabled_at_iteration = sv.iter; }
     return inner_cost < sv.cost;
 }
 
@@ -870,10 +872,10 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
     stba_lm_summary& s = sv.s;
     TrustRegion region(opt);
     // inner iterations: on while the engine has them and no sweep has switched them off (rule 6)
-    bool inner_active = b->inner_on;
-    if (b->inner_on) {
+    bool inner_active = b->inner.on;
+    if (b->inner.on) {
         inner_summary_reset(b);
-        if (sv.timing) for (auto& e : b->inner_ev) if (!e) STBA_HIP(hipEventCreate(&e));
+        if (sv.timing) for (auto& e : b->inner.ev) if (!e) STBA_HIP(hipEventCreate(&e));
     }
     static const bool SPECULATE = knob_int("STBA_LM_SPECULATE", 1) != 0;
 
@@ -926,9 +928,9 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         STBA_TRY(ba_stamp(b, sv.timing, EV_TRIAL_END));
         double isc[2] = {0.0, 0.0};
         if (inner_active) {
-            if (sv.timing) STBA_HIP(hipEventRecord(b->inner_ev[0], b->st));
+            if (sv.timing) STBA_HIP(hipEventRecord(b->inner.ev[0], b->st));
             STBA_TRY(ba_inner_after_trial(b));
-            if (sv.timing) STBA_HIP(hipEventRecord(b->inner_ev[1], b->st));
+            if (sv.timing) STBA_HIP(hipEventRecord(b->inner.ev[1], b->st));
         }
         const double* ts = b->ts_vals;
         if (fast) {
@@ -944,11 +946,11 @@ static int ba_run_lm(stba_ba* b, const stba_lm_options* opt_in, int fixed_iterat
         } else {
             STBA_TRY(download(b->ts_vals, b->trial, TS_BLOCK, b->st));
             STBA_TRY(download(&flag_h, b->flag, 1, b->st));
-            if (inner_active) STBA_TRY(download(isc, b->inner_sc, 2, b->st));
+            if (inner_active) STBA_TRY(download(isc, b->inner.sc, 2, b->st));
             STBA_HIP(hipStreamSynchronize(b->st));
             if (inner_active && sv.timing) {
                 float ms = 0.f;
-                if (hipEventElapsedTime(&ms, b->inner_ev[0], b->inner_ev[1]) == hipSuccess) b->inner_sum.sweep_ms += ms;
+                if (hipEventElapsedTime(&ms, b->inner.ev[0], b->inner.ev[1]) == hipSuccess) b->inner.sum.sweep_ms += ms;
             }
         }
         if (pcg_fail) flag_h = 1;            // (the PCG failed: the step is not ok)
@@ -1734,7 +1736,7 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
                                  const int* pt_group) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     if (!enable) {
-        b->inner_on = false;
+        b->inner.on = false;
         return STBA_OK;
     }
     if (!(tolerance >= 0.0) || !std::isfinite(tolerance))
@@ -1749,75 +1751,33 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
     STBA_TRY(download(oc.data(), b->obs_cam, (size_t)no, b->st));
     STBA_TRY(download(op.data(), b->obs_pt, (size_t)no, b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
-    const bool dflt = !cam_rot_group && !cam_pos_group && !pt_group;
-    // group of every part (-1: not swept); constant parts are ignored
-    std::vector<int> gr((size_t)nc, -1), gq((size_t)nc, -1), gp((size_t)np, -1);
-    for (int c = 0; c < nc; ++c) {
-        const bool rot_const = (cf[(size_t)c] & 7u) == 7u, pos_const = (cf[(size_t)c] & 56u) == 56u;
-        const int r = dflt ? 0 : (cam_rot_group ? cam_rot_group[c] : -1), q = dflt ? 0 : (cam_pos_group ? cam_pos_group[c] : -1);
-        if (r < -1 || q < -1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: camera " + std::to_string(c) + ": a group id below -1");
-        gr[(size_t)c] = rot_const ? -1 : r;
-        gq[(size_t)c] = pos_const ? -1 : q;
-    }
-    for (int j = 0; j < np; ++j) {
-        const int g = dflt ? 1 : (pt_group ? pt_group[j] : -1);
-        if (g < -1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: landmark " + std::to_string(j) + ": a group id below -1");
-        gp[(size_t)j] = pf[(size_t)j] ? -1 : g;
-    }
-    // independence: a residual touches one camera and one landmark, so a group is independent unless it holds a part of a camera and
-    // a landmark that camera observes (a camera's rotation and position in one group are one 6-dof block)
-    for (int i = 0; i < no; ++i) {
-        const int c = oc[(size_t)i], j = op[(size_t)i], g = gp[(size_t)j];
-        if (g >= 0 && (g == gr[(size_t)c] || g == gq[(size_t)c]))
-            return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: group " + std::to_string(g) + " is not an independent set: camera " +
-                        std::to_string(c) + " and landmark " + std::to_string(j) + " share a residual");
-    }
-    std::vector<int> ids;
-    for (int c = 0; c < nc; ++c) { if (gr[(size_t)c] >= 0) ids.push_back(gr[(size_t)c]); if (gq[(size_t)c] >= 0) ids.push_back(gq[(size_t)c]); }
-    for (int j = 0; j < np; ++j) if (gp[(size_t)j] >= 0) ids.push_back(gp[(size_t)j]);
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    std::vector<stba_ba::InnerGroup> groups;
-    std::vector<int> cam_l, pt_l;
-    std::vector<unsigned char> mask_l, kind_l;
-    for (const int g : ids) {
-        stba_ba::InnerGroup r;
-        r.cam_lo = (int)cam_l.size(); r.pt_lo = (int)pt_l.size();
-        for (int c = 0; c < nc; ++c) {
-            const unsigned kind = (gr[(size_t)c] == g ? 1u : 0u) | (gq[(size_t)c] == g ? 2u : 0u);
-            if (!kind) continue;
-            const unsigned m = (((kind & 1u) ? 7u : 0u) | ((kind & 2u) ? 56u : 0u)) & ~(unsigned)cf[(size_t)c];
-            cam_l.push_back(c); mask_l.push_back((unsigned char)m); kind_l.push_back((unsigned char)kind);
-        }
-        for (int j = 0; j < np; ++j) if (gp[(size_t)j] == g) pt_l.push_back(j);
-        r.cam_hi = (int)cam_l.size(); r.pt_hi = (int)pt_l.size();
-        groups.push_back(r);
-    }
+    InnerPlan plan;
+    std::string why;
+    if (build_inner_plan(nc, np, no, oc.data(), op.data(), cf.data(), pf.data(), cam_rot_group, cam_pos_group, pt_group, &plan, &why) != 0)
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_set_inner_iterations: " + why);
     // device lists: the new ones are allocated and filled first and swapped in only when all of them are there, so that a failed
     // allocation leaves the engine's state (and an earlier ordering) as it was
-    const size_t n_it = std::max<size_t>(cam_l.size() + pt_l.size(), 1);
+    const size_t n_it = std::max<size_t>(plan.cam.size() + plan.pt.size(), 1);
     DevBuf<int> n_cam, n_pt, n_itb, n_gate;
     DevBuf<unsigned char> n_mask;
     DevBuf<double> n_sc, n_part;
-    STBA_TRY(n_cam.alloc(cam_l.size())); STBA_TRY(n_mask.alloc(mask_l.size())); STBA_TRY(n_pt.alloc(pt_l.size())); STBA_TRY(n_itb.alloc(n_it));
-    if (!b->inner_gate) STBA_TRY(n_gate.alloc(1));
-    if (!b->inner_sc) STBA_TRY(n_sc.alloc(4));
-    if (!b->inner_part) STBA_TRY(n_part.alloc((size_t)inner_step_grid(nc, np)));
-    STBA_TRY(upload(n_cam, cam_l.data(), cam_l.size(), b->st));
-    STBA_TRY(upload(n_mask, mask_l.data(), mask_l.size(), b->st));
-    STBA_TRY(upload(n_pt, pt_l.data(), pt_l.size(), b->st));
+    STBA_TRY(n_cam.alloc(plan.cam.size())); STBA_TRY(n_mask.alloc(plan.mask.size())); STBA_TRY(n_pt.alloc(plan.pt.size())); STBA_TRY(n_itb.alloc(n_it));
+    if (!b->inner.gate) STBA_TRY(n_gate.alloc(1));
+    if (!b->inner.sc) STBA_TRY(n_sc.alloc(4));
+    if (!b->inner.part) STBA_TRY(n_part.alloc((size_t)inner_step_grid(nc, np)));
+    STBA_TRY(upload(n_cam, plan.cam.data(), plan.cam.size(), b->st));
+    STBA_TRY(upload(n_mask, plan.mask.data(), plan.mask.size(), b->st));
+    STBA_TRY(upload(n_pt, plan.pt.data(), plan.pt.size(), b->st));
     if (hipMemsetAsync(n_itb, 0, n_it * sizeof(int), b->st) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess)
         return fail(STBA_ERR_HIP, "stba_ba_set_inner_iterations: upload failed");
     // (the stream is idle: the moves free the earlier ordering)
-    b->inner_cam = std::move(n_cam); b->inner_pt = std::move(n_pt); b->inner_it = std::move(n_itb); b->inner_mask = std::move(n_mask);
-    if (n_gate) b->inner_gate = std::move(n_gate);
-    if (n_sc) b->inner_sc = std::move(n_sc);
-    if (n_part) b->inner_part = std::move(n_part);
-    b->inner_groups = std::move(groups);
-    b->inner_cam_h = std::move(cam_l); b->inner_pt_h = std::move(pt_l);
-    b->inner_mask_h = std::move(mask_l); b->inner_kind_h = std::move(kind_l);
-    b->inner_tol = tolerance;
-    b->inner_on = true;
+    b->inner.cam = std::move(n_cam); b->inner.pt = std::move(n_pt); b->inner.it = std::move(n_itb); b->inner.mask = std::move(n_mask);
+    if (n_gate) b->inner.gate = std::move(n_gate);
+    if (n_sc) b->inner.sc = std::move(n_sc);
+    if (n_part) b->inner.part = std::move(n_part);
+    b->inner.plan = std::move(plan);
+    b->inner.tol = tolerance;
+    b->inner.on = true;
     inner_summary_reset(b);
     return STBA_OK;
 }
@@ -1825,32 +1785,32 @@ int stba_ba_set_inner_iterations(stba_ba* b, int enable, double tolerance, const
 int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int* iterations_per_block) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     STBA_TRY(ba_refuse(b, "stba_ba_inner_sweep"));
-    const bool was_on = b->inner_on;
-    if (!b->inner_sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner_tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
-    STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc + 2));
+    const bool was_on = b->inner.on;
+    if (!b->inner.sc) STBA_TRY(stba_ba_set_inner_iterations(b, 1, b->inner.tol, nullptr, nullptr, nullptr));   // (never set: the default ordering)
+    STBA_TRY(ba_cost_only(b, b->cur, b->inner.sc + 2));
     STBA_TRY(ba_inner_sweep_enqueue(b, b->cur, nullptr));
-    STBA_TRY(ba_cost_only(b, b->cur, b->inner_sc));
+    STBA_TRY(ba_cost_only(b, b->cur, b->inner.sc));
     double sc[3];
-    STBA_TRY(download(sc, b->inner_sc, 3, b->st));
-    const size_t ncl = b->inner_cam_h.size(), npl = b->inner_pt_h.size();
+    STBA_TRY(download(sc, b->inner.sc, 3, b->st));
+    const size_t ncl = b->inner.plan.cam.size(), npl = b->inner.plan.pt.size();
     std::vector<int> it(ncl + npl);
-    if (!it.empty()) STBA_TRY(download(it.data(), b->inner_it, it.size(), b->st));
+    if (!it.empty()) STBA_TRY(download(it.data(), b->inner.it, it.size(), b->st));
     STBA_HIP(hipStreamSynchronize(b->st));
     ba_invalidate(b);
     inner_summary_reset(b);
-    b->inner_sum.sweeps = 1;
-    b->inner_on = was_on;
+    b->inner.sum.sweeps = 1;
+    b->inner.on = was_on;
     if (cost_before) *cost_before = 0.5 * sc[2];
     if (cost_after) *cost_after = 0.5 * sc[0];
     if (iterations_per_block) {
         const int nc = b->nc;
         memset(iterations_per_block, 0, sizeof(int) * ((size_t)2 * nc + b->np));
         for (size_t k = 0; k < ncl; ++k) {
-            const int c = b->inner_cam_h[k];
-            if (b->inner_kind_h[k] & 1u) iterations_per_block[c] = it[k];
-            if (b->inner_kind_h[k] & 2u) iterations_per_block[nc + c] = it[k];
+            const int c = b->inner.plan.cam[k];
+            if (b->inner.plan.kind[k] & 1u) iterations_per_block[c] = it[k];
+            if (b->inner.plan.kind[k] & 2u) iterations_per_block[nc + c] = it[k];
         }
-        for (size_t k = 0; k < npl; ++k) iterations_per_block[2 * nc + b->inner_pt_h[k]] = it[ncl + k];
+        for (size_t k = 0; k < npl; ++k) iterations_per_block[2 * nc + b->inner.plan.pt[k]] = it[ncl + k];
     }
     return STBA_OK;
 }
@@ -1858,7 +1818,7 @@ int stba_ba_inner_sweep(stba_ba* b, double* cost_before, double* cost_after, int
 int stba_ba_last_inner_summary(stba_ba* b, stba_inner_summary* out) {
     if (!b || !out || out->struct_size < offsetof(stba_inner_summary, sweeps) + sizeof(int)) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_last_inner_summary: bad argument");
     const size_t n = std::min(out->struct_size, sizeof(stba_inner_summary));
-    stba_inner_summary s = b->inner_sum;
+    stba_inner_summary s = b->inner.sum;
     s.struct_size = out->struct_size;
     memcpy(out, &s, n);
     return STBA_OK;
@@ -1959,587 +1919,6 @@ int stba_ba_point_pair_covariance(stba_ba* b, int n_pairs, const int* pt_a, cons
 int stba_ba_covariance_release(stba_ba* b) {
     if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     ba_drop_covariance(b);
-    return STBA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// dense SPD solver entry points
-// ---------------------------------------------------------------------------------------------
-struct DenseWs {
-    int n = 0, lda = 0;
-    DevBuf<double> A, x, rhs;
-    DevBuf<int> flag;
-    hipStream_t st = nullptr;
-    bool own = false;
-    ~DenseWs() {          // (the stream is synchronised here; the buffers go behind it, with the members)
-        if (st) { (void)hipStreamSynchronize(st); chol_forget_stream(st); }
-        if (own && st) (void)hipStreamDestroy(st);
-    }
-    int init(int n_, void* stream) {
-        n = n_; lda = chol_padded_dim(n);
-        if (stream) st = reinterpret_cast<hipStream_t>(stream);
-        else { STBA_HIP(hipStreamCreate(&st)); own = true; }
-        STBA_TRY(A.alloc((size_t)lda * lda)); STBA_TRY(x.alloc((size_t)lda));
-        STBA_TRY(rhs.alloc((size_t)lda)); STBA_TRY(flag.alloc(1));
-        return STBA_OK;
-    }
-    // host A (n x n, lower used) -> padded device matrix
-    int load(const double* hostA, const double* host_rhs) {
-        STBA_HIP(hipMemsetAsync(A, 0, (size_t)lda * lda * sizeof(double), st));
-        STBA_HIP(hipMemcpy2DAsync(A, (size_t)lda * sizeof(double), hostA, (size_t)n * sizeof(double),
-                                  (size_t)n * sizeof(double), (size_t)n, hipMemcpyHostToDevice, st));
-        STBA_HIP(hipMemsetAsync(rhs, 0, (size_t)lda * sizeof(double), st));
-        if (host_rhs) STBA_TRY(upload(rhs, host_rhs, (size_t)n, st));
-        return chol_prepare_padding_dev(A, lda, n, rhs, st);
-    }
-    // factor + solve of the system the host holds; synchronises the stream and hands back the pivot flag.  If the persistent
-    // program gives up (CHOL_FLAG_TIMEOUT: not all of its workgroups were resident, the device is shared with another
-    // process), the matrix is loaded again and the stage kernels -- which need nothing resident -- do the same job.
-    int load_factor_solve(const double* hostA, const double* host_rhs, int* flag_h) {
-        STBA_TRY(load(hostA, host_rhs));
-        STBA_TRY(chol_factor_solve_dev(A, lda, n, x, flag, st));
-        STBA_TRY(download(flag_h, flag, 1, st));
-        STBA_HIP(hipStreamSynchronize(st));
-        if (*flag_h == CHOL_FLAG_TIMEOUT) {
-            chol_note_timeout();
-            STBA_TRY(load(hostA, host_rhs));
-            STBA_TRY(chol_factor_solve_stages(A, lda, n, x, flag, st));
-            STBA_TRY(download(flag_h, flag, 1, st));
-            STBA_HIP(hipStreamSynchronize(st));
-        }
-        return STBA_OK;
-    }
-};
-
-int stba_cholesky_factor(double* A, int n, void* hip_stream) {
-    if (!A || n <= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    DenseWs w;
-    STBA_TRY(w.init(n, hip_stream));
-    int flag_h = 0;
-    STBA_TRY(w.load_factor_solve(A, nullptr, &flag_h));
-    STBA_HIP(hipMemcpy2DAsync(A, (size_t)n * sizeof(double), w.A, (size_t)w.lda * sizeof(double),
-                              (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, w.st));
-    STBA_HIP(hipStreamSynchronize(w.st));
-    STBA_TRY(chol_flag_status(flag_h));
-    if (flag_h) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pivot " + std::to_string(flag_h));
-    return STBA_OK;
-}
-
-int stba_cholesky_solve(const double* A, int n, double* bvec, void* hip_stream) {
-    if (!A || !bvec || n <= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    DenseWs w;
-    STBA_TRY(w.init(n, hip_stream));
-    int flag_h = 0;
-    STBA_TRY(w.load_factor_solve(A, bvec, &flag_h));
-    STBA_TRY(download(bvec, w.x, (size_t)n, w.st));
-    STBA_HIP(hipStreamSynchronize(w.st));
-    STBA_TRY(chol_flag_status(flag_h));
-    if (flag_h) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pivot " + std::to_string(flag_h));
-    return STBA_OK;
-}
-
-// A^-1 through covariance.hip's cov_spd_inverse_packed -- the partial factorisation of [A .; I 0] behind every covariance and the
-// pose graph's coarse operator -- on a matrix the caller holds: the seam its accuracy is tested through.  Nothing is written to
-// Ainv or pivot_ratio unless the factorisation succeeded.
-int stba_cholesky_inverse(const double* A, int n, double* Ainv, double* pivot_ratio, void* hip_stream) {
-    if (!A || !Ainv || n <= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    if (n > 4096) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_cholesky_inverse: limited to n = 4096");
-    STBA_TRY(require_device());
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);      // (null: the default stream)
-    const size_t np = (size_t)n * (n + 1) / 2;
-    DevBuf<double> dA, sig;
-    STBA_TRY(dA.alloc((size_t)n * n));
-    STBA_TRY(sig.alloc(np));
-    STBA_TRY(upload(dA, A, (size_t)n * n, st));
-    double rc = 0.0;
-    int piv = 0;
-    STBA_TRY(cov_spd_inverse_packed(dA, n, n, nullptr, sig, &rc, &piv, st));
-    if (piv) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pivot " + std::to_string(piv));
-    std::vector<double> packed(np);
-    STBA_TRY(download(packed.data(), sig, np, st));
-    STBA_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j <= i; ++j) Ainv[(size_t)i * n + j] = Ainv[(size_t)j * n + i] = packed[(size_t)i * (i + 1) / 2 + j];
-    if (pivot_ratio) *pivot_ratio = rc;
-    return STBA_OK;
-}
-
-__global__ void synth_spd_kernel(double* A, int lda, int n) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (size_t)lda * lda) return;
-    const int i = (int)(idx / lda), j = (int)(idx % lda);
-    double v = 0.0;
-    if (i < n && j < n) {
-        const unsigned h = (unsigned)(i * 2654435761u) ^ (unsigned)(j * 40503u);
-        const unsigned g = (unsigned)(j * 2654435761u) ^ (unsigned)(i * 40503u);
-        v = ((double)((h ^ g) & 1023u) / 1024.0 - 0.5);   // symmetric in (i,j)
-        if (i == j) v += (double)n;
-    }
-    A[idx] = v;
-}
-
-int stba_cholesky_time(int n, int reps, double* ms_avg, void* hip_stream) {
-    if (n <= 0 || reps <= 0 || !ms_avg) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    DenseWs w;
-    STBA_TRY(w.init(n, hip_stream));
-    hipEvent_t e0, e1;
-    STBA_HIP(hipEventCreate(&e0)); STBA_HIP(hipEventCreate(&e1));
-    double total = 0.0;
-    const size_t cnt = (size_t)w.lda * w.lda;
-    for (int k = 0; k < reps + 1; ++k) {
-        hipLaunchKernelGGL(synth_spd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, w.st, w.A, w.lda, n);
-        STBA_HIP(hipMemsetAsync(w.rhs, 0, (size_t)w.lda * sizeof(double), w.st));
-        STBA_TRY(chol_prepare_padding_dev(w.A, w.lda, n, w.rhs, w.st));
-        STBA_HIP(hipEventRecord(e0, w.st));
-        STBA_TRY(chol_factor_solve_dev(w.A, w.lda, n, w.x, w.flag, w.st));
-        STBA_HIP(hipEventRecord(e1, w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        float ms = 0.f;
-        STBA_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (k > 0) total += ms;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_avg = total / reps;
-    return STBA_OK;
-}
-
-int stba_cholesky_schedule_model(int n, int n_xcd, int wg_per_xcd, double* makespan_us) {
-    if (n <= 0 || n_xcd <= 0 || n_xcd > 16 || wg_per_xcd < 4 || !makespan_us) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    const int lda = ((n + 1 + 127) / 128) * 128;      // the padded system carries the right-hand side as one more row
-    *makespan_us = chol_schedule_makespan(lda / 128, n_xcd, wg_per_xcd);
-    return STBA_OK;
-}
-
-int stba_cholesky_timeout_count(void) { return chol_timeout_count(); }
-int stba_cholesky_set_timeout_us(double us) {
-    if (!(us >= 0.0)) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    chol_set_spin_limit_us(us);
-    return STBA_OK;
-}
-
-int stba_cholesky_shard_model(int n, int n_gpus, int n_xcd, int wg_per_xcd, int rows_per_group, double hop_us, double link_gb_per_s,
-                              double* makespan_us, double* cross_gpu_dependencies, double* remote_tiles_busiest_gpu) {
-    if (n <= 0 || n_gpus < 1 || n_gpus > 32 || n_xcd <= 0 || n_xcd > 16 || wg_per_xcd < 4 || rows_per_group < 0 || hop_us < 0 ||
-        !(link_gb_per_s > 0) || !makespan_us)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    const int lda = ((n + 1 + 127) / 128) * 128;
-    double out3[3];
-    chol_shard_model(lda / 128, n_gpus, n_xcd, wg_per_xcd, rows_per_group, hop_us, 128.0 * 128.0 * 8.0 / (link_gb_per_s * 1e3), out3);
-    *makespan_us = out3[0];
-    if (cross_gpu_dependencies) *cross_gpu_dependencies = out3[1];
-    if (remote_tiles_busiest_gpu) *remote_tiles_busiest_gpu = out3[2];
-    return STBA_OK;
-}
-
-int stba_cholesky_shard_owner(int n_block_rows, int n_gpus, int rows_per_group, int* owner_gpu) {
-    if (n_block_rows <= 0 || n_gpus < 1 || rows_per_group < 1 || !owner_gpu) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    for (int r = 0; r < n_block_rows; ++r) owner_gpu[r] = chol_shard_row_owner(r, n_gpus, rows_per_group);
-    return STBA_OK;
-}
-
-int stba_cholesky_time_split(int n, int reps, double* ms_factor, double* ms_backward, void* hip_stream) {
-    if (n <= 0 || reps <= 0 || !ms_factor || !ms_backward) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    DenseWs w;
-    STBA_TRY(w.init(n, hip_stream));
-    hipEvent_t e0, ep, e1, e2;
-    STBA_HIP(hipEventCreate(&e0)); STBA_HIP(hipEventCreate(&ep)); STBA_HIP(hipEventCreate(&e1)); STBA_HIP(hipEventCreate(&e2));
-    // ms_factor = the MEDIAN over the repetitions of the persistent kernel's own duration (an event right in front of it and one
-    // right behind: what rocprofv3 reports for chol_mega_kernel; the flag reset in front, 5 us, is not in it) -- when a
-    // factorisation went through the stage kernels instead (time-out fallback, cool-down) the whole of it, from e0
-    std::vector<double> tf, tb;
-    const size_t cnt = (size_t)w.lda * w.lda;
-    for (int k = 0; k < reps + 1; ++k) {
-        hipLaunchKernelGGL(synth_spd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, w.st, w.A, w.lda, n);
-        STBA_HIP(hipMemsetAsync(w.rhs, 0, (size_t)w.lda * sizeof(double), w.st));
-        STBA_TRY(chol_prepare_padding_dev(w.A, w.lda, n, w.rhs, w.st));
-        STBA_HIP(hipEventRecord(e0, w.st));
-        STBA_HIP(hipEventRecord(ep, w.st));          // (re-recorded in front of the persistent kernel when that is what runs)
-        STBA_TRY(chol_factor_solve_split(w.A, w.lda, n, w.x, w.flag, w.st, e1, ep));
-        STBA_HIP(hipEventRecord(e2, w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        float a = 0.f, b = 0.f;
-        STBA_HIP(hipEventElapsedTime(&a, ep, e1));
-        STBA_HIP(hipEventElapsedTime(&b, e1, e2));
-        if (k > 0) { tf.push_back(a); tb.push_back(b); }
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(ep); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
-    auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); const size_t h = v.size() / 2; return (v.size() & 1) ? v[h] : 0.5 * (v[h - 1] + v[h]); };
-    *ms_factor = median(tf);
-    *ms_backward = median(tb);
-    return STBA_OK;
-}
-
-int stba_cholesky_profile(int n, double* ms4, double* syrk_flops, double* syrk_flops_padded, int* syrk_launches,
-                          void* hip_stream) {
-    if (n <= 0 || !ms4) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    DenseWs w;
-    STBA_TRY(w.init(n, hip_stream));
-    const size_t cnt = (size_t)w.lda * w.lda;
-    hipLaunchKernelGGL(synth_spd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, w.st, w.A, w.lda, n);
-    STBA_HIP(hipMemsetAsync(w.rhs, 0, (size_t)w.lda * sizeof(double), w.st));
-    STBA_TRY(chol_prepare_padding_dev(w.A, w.lda, n, w.rhs, w.st));
-    CholProfile prof;
-    // warm-up pass inside, then the timed pass on a fresh matrix
-    STBA_TRY(chol_factor_solve_dev(w.A, w.lda, n, w.x, w.flag, w.st));
-    hipLaunchKernelGGL(synth_spd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, w.st, w.A, w.lda, n);
-    STBA_TRY(chol_prepare_padding_dev(w.A, w.lda, n, w.rhs, w.st));
-    // the profiled routine factors once un-timed (on this matrix) and once timed: re-synthesise between
-    // is not possible from outside, so time a factorisation of the already-factored-then-refilled buffer:
-    STBA_TRY(chol_factor_solve_profiled(w.A, w.lda, n, w.x, w.flag, w.st, &prof));
-    ms4[0] = prof.ms_diag; ms4[1] = prof.ms_trsm; ms4[2] = prof.ms_syrk; ms4[3] = prof.ms_bwd;
-    if (syrk_flops) *syrk_flops = prof.syrk_flops;
-    if (syrk_flops_padded) *syrk_flops_padded = prof.syrk_flops_padded;
-    if (syrk_launches) *syrk_launches = prof.syrk_launches;
-    return STBA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Zhang calibration (st3-calibration): residual/Jacobian kernel + dense Gauss-Newton on the device
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct CalibWs {
-    int V = 0, C = 0, n = 0;
-    size_t no = 0;
-    DevBuf<double> params, obj, img, e, Ji, Jx, gram, scratch, trace, part, sse;
-    DevBuf<int> state;
-    hipStream_t st = nullptr;
-    // arrow: the Gauss-Newton buffers (per-view Gram blocks, step scratch, iteration state, cost trace) instead of the
-    // per-corner outputs of stba_calib_evaluate
-    int init(int n_views, int n_corners, const double* h_obj, const double* h_img, bool arrow, int max_iter) {
-        V = n_views; C = n_corners; n = 9 + 6 * V; no = (size_t)V * C;
-        STBA_TRY(params.alloc((size_t)n)); STBA_TRY(obj.alloc(no * 2)); STBA_TRY(img.alloc(no * 2));
-        if (arrow) {
-            STBA_TRY(gram.alloc((size_t)V * CALIB_GRAM_DOUBLES)); STBA_TRY(scratch.alloc((size_t)V * CALIB_SCRATCH_DOUBLES));
-            STBA_TRY(trace.alloc((size_t)max_iter)); STBA_TRY(state.alloc((size_t)4));
-        } else {
-            STBA_TRY(e.alloc(no * 2)); STBA_TRY(Ji.alloc(no * 18)); STBA_TRY(Jx.alloc(no * 12));
-            STBA_TRY(part.alloc((no + 255) / 256)); STBA_TRY(sse.alloc((size_t)1));
-        }
-        STBA_TRY(upload(obj, h_obj, no * 2, st)); STBA_TRY(upload(img, h_img, no * 2, st));
-        return STBA_OK;
-    }
-};
-
-}  // namespace
-
-int stba_calib_evaluate(int n_views, int n_corners, const double* params, const double* obj, const double* img,
-                        double* sse, double* e, double* Ji, double* Jx) {
-    if (n_views <= 0 || n_corners <= 0 || !params || !obj || !img) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    CalibWs c;
-    STBA_TRY(c.init(n_views, n_corners, obj, img, false, 0));
-    STBA_TRY(upload(c.params, params, (size_t)c.n, c.st));
-    STBA_TRY(launch_calib_linearize(c.V, c.C, c.params, c.obj, c.img, c.e, c.Ji, c.Jx, c.part, c.st));
-    STBA_TRY(launch_sum_partials(c.part, (int)((c.no + 255) / 256), 1, 1, c.sse, c.st));
-    if (sse) STBA_TRY(download(sse, c.sse, 1, c.st));
-    if (e) STBA_TRY(download(e, c.e, c.no * 2, c.st));
-    if (Ji) STBA_TRY(download(Ji, c.Ji, c.no * 18, c.st));
-    if (Jx) STBA_TRY(download(Jx, c.Jx, c.no * 12, c.st));
-    STBA_HIP(hipStreamSynchronize(c.st));
-    return STBA_OK;
-}
-
-// CalibSolver::totalOptimization (calib.cpp:282-422) with the arrow structure of its normal equations exploited and
-// everything resident on the device (ba_kernels.hip, "Gauss-Newton with the ARROW structure"): per iteration one kernel
-// forms the per-view 16 x 16 Gram blocks, one solves the 9 x 9 Schur complement, back-substitutes the poses, applies the
-// update and records {cost, stop test}.  The host enqueues max_iter iterations (the ones behind the stop are empty
-// launches) and reads parameters, trace and state once.
-int stba_calib_gauss_newton(int n_views, int n_corners, double* params, const double* obj, const double* img,
-                            int max_iter, double* sse_trace, int* iterations) {
-    if (n_views <= 0 || n_corners <= 0 || !params || !obj || !img || max_iter <= 0)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
-    STBA_TRY(require_device());
-    CalibWs c;
-    STBA_TRY(c.init(n_views, n_corners, obj, img, true, max_iter));
-    STBA_TRY(upload(c.params, params, (size_t)c.n, c.st));
-    STBA_HIP(hipMemsetAsync(c.state, 0, 4 * sizeof(int), c.st));
-    for (int iter = 0; iter != max_iter; ++iter)                           // calib.cpp:303
-        STBA_TRY(launch_calib_arrow_iteration(c.V, c.C, c.params, c.obj, c.img, c.gram, c.scratch, c.state, c.trace, c.st));
-    int state[4] = {0, 0, 0, 0};
-    std::vector<double> tr((size_t)max_iter);
-    STBA_TRY(download(state, c.state, 4, c.st));
-    STBA_TRY(download(tr.data(), c.trace, tr.size(), c.st));
-    STBA_TRY(download(params, c.params, (size_t)c.n, c.st));
-    STBA_HIP(hipStreamSynchronize(c.st));
-    const int executed = std::min(max_iter, state[0] + (state[1] != 0 ? 1 : 0));
-    if (sse_trace) for (int k = 0; k < executed; ++k) sse_trace[k] = tr[(size_t)k];
-    if (iterations) *iterations = state[0];
-    if (state[2] != 0) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "calibration normal equations: pivot " + std::to_string(state[2]));
-    return STBA_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// Dense LM problems: residual blocks evaluated by a host callback (the user's CostFunction::Evaluate), the damped normal equations
-// solved on the device.  One loop (dense_lm) over two step providers:
-//  - SmallDenseSteps, <= 32 local parameters (the reference's PnP call sites, its per-landmark triangulation, the bounds demo, the
-//    curve fit): one kernel launch per step (small_dense.hip), no allocation, no copy and no synchronise per solve -- the published
-//    workload of the reference is 0.12-0.22 ms per Solve() (st17-ceres/img/release.png), the general path took 3.5 ms;
-//  - GeneralDenseSteps: normal equations on the device, damping and model change on the host, the dense Cholesky of DenseWs.
-// A provider holds r and J (where the callback writes), g and dx of the last linearisation / step, and
-//   linearize(radius): r and J hold the callback's output at x -- make g (and on the small path the step at `radius`);
-//   step(radius, &model_change, &flag_ok): the step at `radius` for the current linearisation.
-// ---------------------------------------------------------------------------------------------
-namespace stba {
-namespace {
-
-struct SmallDenseSteps {
-    static constexpr bool linearizes_failed_start = false;     // (a non-finite start cost: no device step, row 0's gradient is 0)
-    const stba_lm_options& opt;
-    const int n_res, n;
-    SmallDenseWs* ws = nullptr;
-    double *r = nullptr, *J = nullptr;
-    double dx[SMALL_DENSE_MAX_N], g[SMALL_DENSE_MAX_N];
-    double model_change = 0.0;
-    int flag_h = 0;
-    bool first = true, have_step = false;
-    SmallDenseSteps(const stba_lm_options& o, int n_res_, int n_) : opt(o), n_res(n_res_), n(n_) {}
-    ~SmallDenseSteps() { if (ws) small_dense_release(ws); }
-    int init() {
-        STBA_TRY(small_dense_acquire(&ws, n_res, n));
-        r = small_dense_r(ws); J = small_dense_J(ws);
-        return STBA_OK;
-    }
-    int run(bool relinearize, double radius) {     // (H + D) dx = -g on the device; g refreshed when relinearised
-        const double *dxp = nullptr, *gp = nullptr;
-        STBA_TRY(small_dense_step(ws, n_res, n, relinearize, first, opt.jacobi_scaling != 0, radius, opt.min_lm_diagonal,
-                                  opt.max_lm_diagonal, &dxp, &gp, &model_change, &flag_h));
-        first = false;
-        for (int a = 0; a < n; ++a) { dx[a] = dxp[a]; g[a] = gp[a]; }
-        return STBA_OK;
-    }
-    int linearize(double radius) {      // the next iteration's step rides along with the new linearisation
-        STBA_TRY(run(true, radius));
-        have_step = true;
-        return STBA_OK;
-    }
-    int step(double radius, double* mc, bool* flag_ok) {
-        if (!have_step) STBA_TRY(run(false, radius));
-        have_step = false;
-        *mc = model_change;
-        *flag_ok = flag_h == 0;
-        return STBA_OK;
-    }
-};
-
-struct GeneralDenseSteps {
-    static constexpr bool linearizes_failed_start = true;      // (a non-finite start cost: linearised all the same, row 0 has its gradient)
-    const stba_lm_options& opt;
-    const int n_res, n;
-    DenseWs w;
-    DevBuf<double> dJ, dr, dH, dg;
-    std::vector<double> rv, Jv, H, Hd, gv, dxv, scale, dvec;
-    double *r = nullptr, *J = nullptr, *g = nullptr, *dx = nullptr;
-    bool first = true;
-    GeneralDenseSteps(const stba_lm_options& o, int n_res_, int n_) : opt(o), n_res(n_res_), n(n_) {}
-    int init() {
-        STBA_TRY(w.init(n, nullptr));
-        STBA_TRY(dJ.alloc((size_t)n_res * n)); STBA_TRY(dr.alloc((size_t)n_res));
-        STBA_TRY(dH.alloc((size_t)n * n)); STBA_TRY(dg.alloc((size_t)n));
-        rv.resize(n_res); Jv.resize((size_t)n_res * n); H.resize((size_t)n * n); Hd.resize((size_t)n * n);
-        gv.resize(n); dxv.resize(n); scale.resize(n); dvec.resize(n);
-        r = rv.data(); J = Jv.data(); g = gv.data(); dx = dxv.data();
-        return STBA_OK;
-    }
-    int linearize(double) {     // H = J^T J, g = J^T r on the device; the Jacobi scale from the first linearisation
-        STBA_TRY(upload(dJ, J, Jv.size(), w.st)); STBA_TRY(upload(dr, r, rv.size(), w.st));
-        STBA_HIP(hipMemsetAsync(dH, 0, (size_t)n * n * sizeof(double), w.st));
-        STBA_TRY(launch_dense_normal(n_res, n, dJ, dr, dH, n, dg, w.st));
-        STBA_TRY(download(H.data(), dH, H.size(), w.st)); STBA_TRY(download(g, dg, gv.size(), w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        if (first)
-            for (int a = 0; a < n; ++a) scale[a] = opt.jacobi_scaling ? 1.0 / (1.0 + std::sqrt(H[(size_t)a * n + a])) : 1.0;
-        first = false;
-        return STBA_OK;
-    }
-    int step(double radius, double* model_change, bool* flag_ok) {
-        Hd = H;
-        for (int a = 0; a < n; ++a) {
-            const double s2 = scale[a] * scale[a];
-            const double d = std::min(std::max(H[(size_t)a * n + a] * s2, opt.min_lm_diagonal), opt.max_lm_diagonal);
-            dvec[a] = d / radius / s2;
-            Hd[(size_t)a * n + a] += dvec[a];
-            dx[a] = -g[a];
-        }
-        int flag_h = 0;
-        STBA_TRY(w.load_factor_solve(Hd.data(), dx, &flag_h));
-        STBA_TRY(download(dx, w.x, (size_t)n, w.st));
-        STBA_HIP(hipStreamSynchronize(w.st));
-        STBA_TRY(chol_flag_status(flag_h));
-        *model_change = 0.0;
-        *flag_ok = flag_h == 0;
-        if (*flag_ok)
-            for (int a = 0; a < n; ++a) *model_change += -0.5 * g[a] * dx[a] + 0.5 * dvec[a] * dx[a] * dx[a];
-        return STBA_OK;
-    }
-};
-
-template <class Steps>
-int dense_lm(Steps& S, stba_residual_fn fn, stba_plus_fn plus, void* user, int n_params, int n, int n_res, double* x,
-             const double* lower, const double* upper, const stba_lm_options& opt, stba_lm_summary* summary, double* trace,
-             stba_iteration_callback cb, void* cb_user) {
-    std::vector<double> xn((size_t)n_params), rn((size_t)n_res);
-    stba_lm_summary s;
-    memset(&s, 0, sizeof s);
-    const double t_start = wall_s();
-    const bool bounded = lower || upper;
-    auto gmax_of = [&]() {
-        double m = 0.0;
-        for (int a = 0; a < n; ++a) {
-            if (!bounded) m = std::max(m, std::fabs(S.g[a]));
-            else {
-                double y = x[a] - S.g[a];
-                if (lower && y < lower[a]) y = lower[a];
-                if (upper && y > upper[a]) y = upper[a];
-                m = std::max(m, std::fabs(x[a] - y));
-            }
-        }
-        return m;
-    };
-    auto norm_of = [&](const double* v, int k) { double q = 0; for (int a = 0; a < k; ++a) q += v[a] * v[a]; return std::sqrt(q); };
-
-    if (fn(user, x, S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-    double cost = 0.0;
-    for (int i = 0; i < n_res; ++i) cost += S.r[i] * S.r[i];
-    cost *= 0.5;
-    s.initial_cost = cost;
-    TrustRegion region(opt);
-    double x_norm = norm_of(x, n_params), gmax = 0.0;
-    if (std::isfinite(cost) || Steps::linearizes_failed_start) {
-        STBA_TRY(S.linearize(region.radius));
-        gmax = gmax_of();
-    }
-    trace_start(trace, cost, gmax, region.radius);
-    int iter = 0;
-    bool done = false;
-    s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER;
-    if (!std::isfinite(cost)) { s.termination_type = STBA_FAILURE; s.termination_reason = STBA_TERM_SOLVER_FAIL; done = true; }    // (Ceres: initial evaluation failed, see stba_ba_solve)
-    else if (gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; done = true; }
-    while (!done) {
-        if (iter >= opt.max_num_iterations) { s.termination_type = STBA_NO_CONVERGENCE; s.termination_reason = STBA_TERM_MAX_ITER; break; }
-        if (region.below_min(opt)) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_MIN_RADIUS; break; }
-        ++iter;
-        double model_change = 0.0, new_cost = 0.0, step_norm = 0.0;
-        bool ok = false;
-        STBA_TRY(S.step(region.radius, &model_change, &ok));
-        if (ok && (!(model_change > 0.0) || !std::isfinite(model_change))) ok = false;
-        if (ok) {
-            if (plus) plus(user, x, S.dx, xn.data());
-            else for (int a = 0; a < n_params; ++a) xn[a] = x[a] + S.dx[a];
-            if (bounded)
-                for (int a = 0; a < n_params; ++a) {
-                    if (lower && xn[a] < lower[a]) xn[a] = lower[a];
-                    if (upper && xn[a] > upper[a]) xn[a] = upper[a];
-                }
-            if (fn(user, xn.data(), rn.data(), nullptr) != 0) ok = false;
-        }
-        if (ok) {
-            for (double v : rn) new_cost += v * v;
-            new_cost *= 0.5;
-            for (int a = 0; a < n_params; ++a) step_norm += (xn[a] - x[a]) * (xn[a] - x[a]);
-            step_norm = std::sqrt(step_norm);
-        }
-        // (a non-finite trial cost stays ok here, unlike BA and the pose graph: it is judged, and its NaN rho reaches the trace)
-        const StepVerdict v = judge_step(opt, cost, ok, new_cost, model_change, step_norm, x_norm);
-        if (v.accepted) { memcpy(x, xn.data(), sizeof(double) * n_params); cost = new_cost; ++s.num_successful_steps; }
-        if (v.stop) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = v.stop;
-            trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
-            if (cb) (void)cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, v.accepted ? 1 : 0);
-            break;
-        }
-        if (v.accepted) {
-            x_norm = norm_of(x, n_params);
-            if (fn(user, x, S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-            region.accept(v.rho, opt);
-            STBA_TRY(S.linearize(region.radius));
-            gmax = gmax_of();
-        } else {
-            ++s.num_unsuccessful_steps;
-            region.reject();
-        }
-        trace_step(trace, iter, ok, cost, new_cost, v, gmax, step_norm, region.radius);
-        if (opt.minimizer_progress_to_stdout) progress_step(iter, cost, v, gmax, step_norm, region.radius);
-        if (cb && cb(cb_user, iter, cost, v.cost_change, gmax, step_norm, region.radius, v.accepted ? 1 : 0) != 0) {
-            s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_USER; break;
-        }
-        if (v.accepted && gmax <= opt.gradient_tolerance) { s.termination_type = STBA_CONVERGENCE; s.termination_reason = STBA_TERM_GRADIENT; break; }
-    }
-    finish_summary(&s, iter, cost, region.radius, gmax, t_start);
-    if (summary) *summary = s;
-    return STBA_OK;
-}
-
-}  // namespace
-}  // namespace stba
-
-extern "C" {
-
-int stba_dense_solve(stba_residual_fn fn, stba_plus_fn plus, void* user, int n_params, int n_local, int n_res,
-                     double* x, const double* lower, const double* upper, const stba_lm_options* opt_in,
-                     stba_lm_summary* summary, double* trace, stba_iteration_callback cb, void* cb_user) {
-    if (!fn || !x || n_params <= 0 || n_local <= 0 || n_res <= 0)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_solve: bad argument");
-    if ((lower || upper) && plus)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "bounds are only supported on Euclidean parameter blocks");
-    if (!plus && n_params != n_local)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_solve: n_params != n_local needs a plus() callback");
-    STBA_TRY(require_device());
-    stba_lm_options opt;
-    if (opt_in) opt = *opt_in; else default_options(&opt);
-    const int n = n_local;
-    if (small_dense_fits(n_res, n)) {
-        SmallDenseSteps S(opt, n_res, n);
-        STBA_TRY(S.init());
-        return dense_lm(S, fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
-    }
-    GeneralDenseSteps S(opt, n_res, n);
-    STBA_TRY(S.init());
-    return dense_lm(S, fn, plus, user, n_params, n, n_res, x, lower, upper, opt, summary, trace, cb, cb_user);
-}
-
-// (J^T J)^-1 at x: one evaluation of the callback, J^T J formed on the device by GeneralDenseSteps::linearize -- the normal
-// equations of the general dense solve -- and inverted by covariance.hip's cov_spd_inverse_packed
-int stba_dense_covariance(stba_residual_fn fn, void* user, int n_params, int n_local, int n_res, const double* x, double min_rcond,
-                          double* cov, double* rcond_out) {
-    if (!fn || !x || !cov || n_params <= 0 || n_local <= 0 || n_res <= 0)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_covariance: bad argument");
-    if (n_local > 4096 || (double)n_local * n_res > 2.7e8)
-        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_dense_covariance: limited to 4096 local parameters and 2.7e8 Jacobian entries");
-    STBA_TRY(require_device());
-    stba_lm_options opt;
-    default_options(&opt);
-    const int n = n_local;
-    GeneralDenseSteps S(opt, n_res, n);
-    STBA_TRY(S.init());
-    std::vector<double> xv(x, x + n_params);
-    if (fn(user, xv.data(), S.r, S.J) != 0) return fail(STBA_ERR_CALLBACK, "residual callback failed");
-    for (int i = 0; i < n_res; ++i)
-        if (!std::isfinite(S.r[i])) return fail(STBA_ERR_CALLBACK, "stba_dense_covariance: non-finite residual");
-    STBA_TRY(S.linearize(0.0));
-    DevBuf<double> sig;
-    STBA_TRY(sig.alloc((size_t)n * (n + 1) / 2));
-    double rc = 0.0;
-    int piv = 0;
-    STBA_TRY(cov_spd_inverse_packed(S.dH, n, n, nullptr, sig, &rc, &piv, S.w.st));
-    if (rcond_out) *rcond_out = rc;
-    if (piv) return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "stba_dense_covariance: J^T J is not positive definite (pivot of row " + std::to_string(piv - 1) + ")");
-    if (!(rc >= min_rcond)) {
-        char buf[64];
-        snprintf(buf, sizeof buf, "%.3e", rc);
-        return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, std::string("stba_dense_covariance: J^T J has a pivot ratio of ") + buf + ", below min_reciprocal_condition_number");
-    }
-    std::vector<double> packed((size_t)n * (n + 1) / 2);
-    STBA_TRY(download(packed.data(), sig, packed.size(), S.w.st));
-    STBA_HIP(hipStreamSynchronize(S.w.st));
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j <= i; ++j) cov[(size_t)i * n + j] = cov[(size_t)j * n + i] = packed[(size_t)i * (i + 1) / 2 + j];
     return STBA_OK;
 }
 

@@ -115,27 +115,51 @@ def block_lm(lin, cost_at, plus, x, active, norm_sel, opts=BLOCK_OPTIONS, ftol_t
             radius /= v; v *= 2.0
 
 
-def ordering(prob, rot=None, pos=None, pt=None):
+ORDERING_MUTATIONS = ("no_constant_masking", "groups_reversed", "no_independence_check")
+
+
+def ordering(prob, rot=None, pos=None, pt=None, mut=frozenset()):
     """the C ABI's ordering (include/stba.h stba_ba_set_inner_iterations): list of (group id, [(camera, kind)], [landmarks]) in
-    ascending id; kind 1 rotation, 2 position, 3 both.  All None: {cameras as 6-dof blocks}, {landmarks}.  Constant parts ignored."""
+    ascending id; kind 1 rotation, 2 position, 3 both.  All None: {cameras as 6-dof blocks}, {landmarks}.  Constant parts ignored.
+    mut: deliberate mistakes of ORDERING_MUTATIONS (test_inner_plan_cpu.py shows that its cases tell each of them apart)"""
     nc, npt = prob.nc, prob.np_
     if rot is None and pos is None and pt is None:
         rot, pos, pt = np.zeros(nc, int), np.zeros(nc, int), np.ones(npt, int)
     rot = -np.ones(nc, int) if rot is None else np.asarray(rot, int)
     pos = -np.ones(nc, int) if pos is None else np.asarray(pos, int)
     pt = -np.ones(npt, int) if pt is None else np.asarray(pt, int)
-    rot = np.where(prob.rot_active, rot, -1)
-    pos = np.where(prob.pos_active, pos, -1)
-    pt = np.where(prob.pt_fixed, -1, pt)
+    if "no_constant_masking" not in mut:
+        rot = np.where(prob.rot_active, rot, -1)
+        pos = np.where(prob.pos_active, pos, -1)
+        pt = np.where(prob.pt_fixed, -1, pt)
     for c, j in zip(prob.oc, prob.op):
-        if pt[j] >= 0 and pt[j] in (rot[c], pos[c]):
+        if pt[j] >= 0 and pt[j] in (rot[c], pos[c]) and "no_independence_check" not in mut:
             raise ValueError(f"group {pt[j]} is not an independent set: camera {c} and landmark {j}")
-    ids = sorted(set(rot[rot >= 0]) | set(pos[pos >= 0]) | set(pt[pt >= 0]))
+    ids = sorted(set(rot[rot >= 0]) | set(pos[pos >= 0]) | set(pt[pt >= 0]), reverse="groups_reversed" in mut)
     out = []
     for gid in ids:
         cams = [(c, (1 if rot[c] == gid else 0) | (2 if pos[c] == gid else 0)) for c in range(nc) if gid in (rot[c], pos[c])]
         out.append((gid, cams, [j for j in range(npt) if pt[j] == gid]))
     return out
+
+
+def ordering_lists(prob, rot=None, pos=None, pt=None, mut=frozenset()):
+    """ordering() flattened into the five arrays of slam-tricks_amd/csrc/inner_plan.hpp: groups [(cam_lo, cam_hi, pt_lo, pt_hi)], the
+    camera list, the landmark list, and per camera entry the swept dofs as a bit mask (sweep()'s rule: the kind's dofs that are not
+    constant) and the kind"""
+    groups, cam, pts, mask, kind = [], [], [], [], []
+    for _, gcams, gpts in ordering(prob, rot, pos, pt, mut):
+        lo = (len(cam), len(pts))
+        for c, k in gcams:
+            active = np.zeros(6, bool)
+            if k & 1: active[:3] = True
+            if k & 2: active[3:] = True
+            if "no_constant_masking" not in mut:
+                active &= ~prob.cam_fixed[c]
+            cam.append(int(c)); kind.append(int(k)); mask.append(int(sum(1 << a for a in range(6) if active[a])))
+        pts.extend(int(j) for j in gpts)
+        groups.append((lo[0], len(cam), lo[1], len(pts)))
+    return dict(groups=groups, cam=cam, pt=pts, mask=mask, kind=kind)
 
 
 def sweep(prob, x, order, mut=frozenset(), opts=None):
