@@ -77,6 +77,32 @@ public:
     operator T*() const { return p_; }
 };
 
+// move-only owner of one event, destroyed with the object (an early return leaves none behind).  Converts to hipEvent_t.
+// Never an object of static or thread storage duration: the destructor calls HIP.
+class DevEvent {
+    hipEvent_t ev_ = nullptr;
+public:
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    DevEvent(DevEvent&& o) noexcept : ev_(o.ev_) { o.ev_ = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        if (this != &o) { reset(); ev_ = o.ev_; o.ev_ = nullptr; }
+        return *this;
+    }
+    ~DevEvent() { reset(); }
+    int create(unsigned flags = hipEventDefault) {      // (what the object held is destroyed first)
+        reset();
+        STBA_HIP(hipEventCreateWithFlags(&ev_, flags));
+        return STBA_OK;
+    }
+    void reset() {
+        if (ev_) (void)hipEventDestroy(ev_);
+        ev_ = nullptr;
+    }
+    operator hipEvent_t() const { return ev_; }
+};
+
 // host <-> device copies on a stream (nothing is enqueued for count 0).  The device side is not deduced, so a DevBuf converts
 template <class T> struct same_as { using type = T; };
 template <class T>
@@ -259,6 +285,8 @@ struct MappedBuffer {
 
 // ---- dense Cholesky on the device (dense_chol.hip) -----------------------------------------
 constexpr int CHOL_NB = 128;
+// workspace doubles per diagonal block: its inverse transpose, then the inverses of its eight 16x16 diagonal tiles
+constexpr size_t CHOL_LINV_STRIDE = (size_t)CHOL_NB * CHOL_NB + 8 * 256;
 // padded order: multiple of CHOL_NB with at least one spare row (the last row carries the rhs)
 inline int chol_padded_dim(int n) { return ((n + 1 + CHOL_NB - 1) / CHOL_NB) * CHOL_NB; }
 // A_dev: lda x lda row-major, lda = chol_padded_dim(n).  Rows/cols [n, lda-1) must hold the

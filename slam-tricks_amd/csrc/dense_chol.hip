@@ -27,6 +27,11 @@
 // (chol_diag_kernel / chol_trsm_kernel / chol_syrk_kernel), timed per class with hipEvents.
 // Backward substitution: one small kernel per block (GEMV with the inverse transposes the panel
 // solve produced).
+//
+// Host driver, at the end of the file: chol_run is a list of steps over one CholCall -- chol_pick_schedule (cool-down),
+// chol_workspace (per thread and device), then chol_persistent (mega_device_init, mega_plan_for, chol_launch_persistent,
+// mega_trace_dump) or chol_launch_stages (chol_stage_panels, which chol_spd_inverse_dev runs too), each behind
+// chol_follow_previous, and chol_backward; under a profile a CholTimer owns the events between them.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -969,7 +974,7 @@ __device__ __forceinline__ void syrk_tile512_gen(double* __restrict__ Cb, int ld
 // thread 0 only.  Polls with relaxed agent-scope loads; gives up (and raises the abort flag, so that
 // every other workgroup gives up too) after `limit` ticks of the 100 MHz clock instead of hanging the device
 // (MegaArgs::spin_limit: a multiple of the predicted makespan; the host then reruns the factorisation through the
-// stage kernels, see chol_run).
+// stage kernels, see chol_launch_persistent and chol_launch_stages).
 __device__ __forceinline__ bool mega_wait(const int* p, int target, int* abortf, long long limit) {
     if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return true;
     const long long t0 = wall_clock64();
@@ -1694,6 +1699,41 @@ struct MegaDevice {
     hipStream_t last_stream = nullptr;  // ... which ran on this stream (null: none, or the stream is gone)
     int cooldown = 0;                   // factorisations that take the stage kernels after a time-out of the persistent program
 };
+namespace {
+// A raw device array that only grows.  hipMalloc / hipFree directly, outside g_live_device_buffers, and no destructor: the arrays
+// below are kept for the life of the calling thread's map (chol_workspace) and never freed at thread exit, when the runtime may be gone.
+// Plain data: a copy is another name for the same array, not an owner (mega_plan_for assigns a fresh plan over a released one).
+template <class T>
+struct GrowOnly {
+    T* p = nullptr;
+    size_t count = 0;
+    int grow(size_t want) {
+        if (count >= want) return STBA_OK;
+        release();
+        STBA_HIP(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
+        count = want;
+        return STBA_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; count = 0;
+    }
+};
+// the persistent program for one (nblk, nwide) on one device: mega_plan_for
+struct MegaPlan {
+    int nblk = 0, nwide = -1, ntasks = 0;
+    int lstart[MEGA_MAX_Q + 1] = {0};
+    GrowOnly<MegaTask> tasks;
+    GrowOnly<int> sync; size_t sync_ints = 0;
+    double makespan_us = 0.0;
+    std::vector<float> sim_start;     // simulated start time of every task (written to the trace file)
+};
+// workspace and task plan are per (host thread, device): a thread that switches devices, or a second GPU in the same process, must
+// not reuse another device's pointers or XCD probe.  linv, per diagonal block (CHOL_LINV_STRIDE doubles): its inverse transpose
+// (written by the panel solve, read by the backward pass) followed by the inverses of its eight 16x16 diagonal tiles (written by
+// the diagonal kernel, read by the panel solve).  vbuf: the wide (4-panel) inverse blocks of the backward substitution
+struct DevWs { GrowOnly<double> linv, vbuf; MegaPlan plan; };
+}  // namespace
 static MegaDevice& mega_device(int dev) {
     static std::mutex mm;
     static std::map<int, MegaDevice> devs;
@@ -1701,7 +1741,7 @@ static MegaDevice& mega_device(int dev) {
     return devs[dev];
 }
 
-// once per device: which XCDs do the workgroups of a ncu-wide launch land on?
+// once per device: which XCDs do the workgroups of a ncu-wide launch land on?  (and the event and the LDS limit the program needs)
 static int mega_device_init(MegaDevice& D, hipStream_t st) {
     if (D.probed) return STBA_OK;
     int dev = 0;
@@ -1731,6 +1771,7 @@ static int mega_device_init(MegaDevice& D, hipStream_t st) {
     if (D.wg_per_xcd < MEGA_NTU)
         return fail(STBA_ERR_HIP, "chol: fewer than 10 workgroups per XCD (the TU tasks of a step need one each)");
     if (!D.last) STBA_HIP(hipEventCreateWithFlags(&D.last, hipEventDisableTiming));
+    STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_mega_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MEGA_SMEM_BYTES));
     D.probed = true;
     return STBA_OK;
 }
@@ -1761,206 +1802,46 @@ int chol_timeout_count() { return g_timeouts.load(); }
 
 // which schedule a factorisation runs through
 enum { CHOL_PERSISTENT = 0, CHOL_STAGES = 1 };
+namespace {
+// what an entry point asks of chol_run beyond the system itself
+struct CholRequest {
+    CholProfile* prof = nullptr;        // the stage kernels, timed per class (stba_cholesky_profile)
+    hipEvent_t mid_event = nullptr;     // recorded between the factorisation and the backward substitution
+    hipEvent_t pre_event = nullptr;     // recorded right in front of the persistent kernel (timing only; stage schedule: never)
+    int schedule = CHOL_PERSISTENT;
+};
+// one call of chol_run: what its steps share
+struct CholCall {
+    double* A; int lda, n; double* x; int* flag; hipStream_t st;
+    int nblk = 0, nwide = 0, dev = 0;
+    bool stages = false;                // this call runs the stage kernels
+    DevWs* ws = nullptr;                // the calling thread's workspace for dev
+};
 
-static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st, CholProfile* prof,
-                    hipEvent_t mid_event = nullptr, int schedule = CHOL_PERSISTENT, hipEvent_t pre_event = nullptr) {
-    if (lda % NB != 0 || lda < n + 1) return fail(STBA_ERR_INVALID_ARGUMENT, "chol: bad padded dimension");
-    const int nblk = lda / NB;
-    int cur_dev = 0;
-    STBA_HIP(hipGetDevice(&cur_dev));
-    if (!prof && schedule == CHOL_PERSISTENT) {
-        // after a time-out (chol_note_timeout) the device is taken to be shared: the next factorisations do not try again
-        MegaDevice& D = mega_device(cur_dev);
-        std::lock_guard<std::mutex> g(D.m);
-        if (D.cooldown > 0) { --D.cooldown; schedule = CHOL_STAGES; }
-    }
-    const bool stages = prof != nullptr || schedule == CHOL_STAGES;
-    // per diagonal block: its inverse transpose (written by the panel solve, read by the backward pass)
-    // followed by the inverses of its eight 16x16 diagonal tiles (written by the diagonal kernel, read
-    // by the panel solve)
-    constexpr size_t LINV_STRIDE = (size_t)NB * NB + 8 * 256;
-    // workspace and task plan are per (host thread, device): a thread that switches devices, or a second GPU in
-    // the same process, must not reuse another device's pointers or XCD probe
-    struct MegaPlan {
-        int nblk = 0, nwide = -1, ntasks = 0;
-        int lstart[MEGA_MAX_Q + 1] = {0};
-        MegaTask* tasks = nullptr; int* sync = nullptr; size_t sync_ints = 0;
-        double makespan_us = 0.0;
-        std::vector<float> sim_start;     // simulated start time of every task (written to the trace file)
-    };
-    struct DevWs { double* linv = nullptr; int linv_blocks = 0; double* vbuf = nullptr; int vbuf_blocks = 0; MegaPlan plan; };
-    static thread_local std::map<int, DevWs> ws_by_dev;
-    DevWs& ws = ws_by_dev[cur_dev];
-    double*& linv = ws.linv;
-    int& linv_blocks = ws.linv_blocks;
-    if (linv_blocks < nblk) {
-        if (linv) (void)hipFree(linv);
-        linv = nullptr; linv_blocks = 0;
-        STBA_HIP(hipMalloc(reinterpret_cast<void**>(&linv), (size_t)nblk * LINV_STRIDE * sizeof(double)));
-        linv_blocks = nblk;
-    }
-    // wide (4-panel) inverse blocks for the backward substitution: every panel but the last 1..4 (the tail keeps
-    // single-panel steps, so that no inverse-block task runs behind the last diagonal block)
-    const int nwide = stages ? 0 : (nblk - 1) / 4;
-    if (ws.vbuf_blocks < nwide) {
-        if (ws.vbuf) (void)hipFree(ws.vbuf);
-        ws.vbuf = nullptr; ws.vbuf_blocks = 0;
-        STBA_HIP(hipMalloc(reinterpret_cast<void**>(&ws.vbuf), (size_t)nwide * 16 * NB * NB * sizeof(double)));
-        ws.vbuf_blocks = nwide;
-    }
-    // panel of block b: diagonal kernel + panel solve of the (nblk - b - 1) * 8 row groups below it
-    static DeviceOnce diag_attr;
-    STBA_TRY(diag_attr.run([]() -> int {
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Diag2Smem)));
-        return STBA_OK;
-    }));
-    auto launch_panel_diag = [&](int b, hipStream_t s_) {
-        double* li = linv + (size_t)b * LINV_STRIDE;
-        hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(512), sizeof(Diag2Smem), s_, A, lda, b * NB, n, flag_dev, li + NB * NB);
-    };
-    auto launch_panel_trsm = [&](int b, hipStream_t s_) {
-        double* li = linv + (size_t)b * LINV_STRIDE;
-        const int groups = (nblk - b - 1) * (NB / 16);
-        hipLaunchKernelGGL(chol_trsm_kernel, dim3(groups + NB / 16), dim3(64), 0, s_, A, lda, b * NB, groups, li, li + NB * NB);
-    };
-    std::vector<hipEvent_t> ev;
-    if (prof) {
+// The events of the profiled schedule: four per panel (in front of the diagonal kernel, the panel solve and the trailing update, and
+// behind it), then one in front of and one behind the backward substitution.  Their owner: an early return destroys them.
+struct CholTimer {
+    CholProfile* prof = nullptr;
+    hipStream_t st = nullptr;
+    int nblk = 0;
+    std::vector<DevEvent> ev;
+    // *p is zeroed and its counts filled in: one trailing update per block that has rows below it
+    int start(CholProfile* p, const CholCall& c) {
+        prof = p; st = c.st; nblk = c.nblk;
         ev.resize((size_t)nblk * 4 + 2);
-        for (auto& e : ev) STBA_HIP(hipEventCreate(&e));
+        for (auto& e : ev) STBA_TRY(e.create());
         memset(prof, 0, sizeof *prof);
+        for (int b = 0, mt = nblk - 1; mt > 0; ++b, --mt) {
+            const double m = std::max(0, c.n - (b * NB + NB));
+            prof->syrk_flops += m * (m + 1.0) * NB;
+            prof->syrk_flops_padded += (double)(mt * (mt + 1) / 2) * 2.0 * NB * NB * NB;
+            prof->syrk_launches += 1;
+        }
+        return STBA_OK;
     }
-    auto mark = [&](size_t k) -> int { if (prof) STBA_HIP(hipEventRecord(ev[k], st)); return STBA_OK; };
-    if (stages) {
-        {   // the per-thread workspace (linv) is shared by every stream this host thread factors on: order this factorisation
-            // behind the previous one's backward substitution if that ran on another stream (as the persistent branch does)
-            MegaDevice& D = mega_device(cur_dev);
-            std::lock_guard<std::mutex> dev_lock(D.m);
-            if (!D.last) STBA_HIP(hipEventCreateWithFlags(&D.last, hipEventDisableTiming));
-            if (D.last_stream != nullptr && D.last_stream != st) {
-                STBA_HIP(hipEventRecord(D.last, D.last_stream));
-                STBA_HIP(hipStreamWaitEvent(st, D.last, 0));
-            }
-            D.last_stream = st;
-        }
-        STBA_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
-        // STAGE KERNELS: one kernel per stage and panel, in order on the caller's stream.  The diagnostic schedule of
-        // stba_cholesky_profile (per-class event times) and the FALLBACK of the persistent program: it needs nothing
-        // resident, so it always finishes, whoever else uses the device (see chol_factor_solve_robust).
-        for (int b = 0; b < nblk; ++b) {
-            const int k0 = b * NB;
-            const int mt = nblk - b - 1;
-            STBA_TRY(mark(4 * (size_t)b + 0));
-            launch_panel_diag(b, st);
-            STBA_TRY(mark(4 * (size_t)b + 1));
-            launch_panel_trsm(b, st);
-            STBA_TRY(mark(4 * (size_t)b + 2));
-            if (mt > 0) launch_syrk(A, lda, k0, 0, mt * (mt + 1) / 2, st);
-            STBA_TRY(mark(4 * (size_t)b + 3));
-            if (mt > 0 && prof) {
-                const double m = std::max(0, n - (k0 + NB));
-                prof->syrk_flops += m * (m + 1.0) * NB;
-                prof->syrk_flops_padded += (double)(mt * (mt + 1) / 2) * 2.0 * NB * NB * NB;
-                prof->syrk_launches += 1;
-            }
-        }
-    } else {
-        // production: the persistent dataflow program (see chol_mega_kernel)
-        MegaDevice& D = mega_device(cur_dev);
-        std::lock_guard<std::mutex> dev_lock(D.m);
-        STBA_TRY(mega_device_init(D, st));
-        MegaPlan& plan = ws.plan;
-        if (plan.nblk != nblk || plan.nwide != nwide) {
-            if (plan.tasks) (void)hipFree(plan.tasks);
-            if (plan.sync) (void)hipFree(plan.sync);
-            plan = MegaPlan();
-            MegaMachine mach;
-            mach.nq = D.nq;
-            mach.wg = D.wg_per_xcd;
-            MegaSchedule sched;
-            mega_plan(sched, nblk, nwide, mach);
-            const std::vector<MegaTask>& tasks = sched.tasks;
-            std::copy(sched.lstart.begin(), sched.lstart.end(), plan.lstart);
-            plan.sim_start.swap(sched.sim_start);
-            plan.makespan_us = sched.makespan_us;
-            STBA_HIP(hipMalloc(reinterpret_cast<void**>(&plan.tasks), tasks.size() * sizeof(MegaTask)));
-            STBA_HIP(hipMemcpy(plan.tasks, tasks.data(), tasks.size() * sizeof(MegaTask), hipMemcpyHostToDevice));
-            plan.sync_ints = mega_flag_ints(nblk, nwide);
-            STBA_HIP(hipMalloc(reinterpret_cast<void**>(&plan.sync), plan.sync_ints * sizeof(int)));
-            plan.ntasks = (int)tasks.size();
-            plan.nblk = nblk; plan.nwide = nwide;
-        }
-        hipLaunchKernelGGL(chol_reset_kernel, dim3((unsigned)((plan.sync_ints + 255) / 256)), dim3(256), 0, st, plan.sync, (int)plan.sync_ints, flag_dev);
-        MegaArgs ma;
-        ma.A = A; ma.lda = lda; ma.n = n; ma.nblk = nblk;
-        ma.tasks = plan.tasks; ma.nq = D.nq; ma.sync = plan.sync;
-        memcpy(ma.lstart, plan.lstart, sizeof ma.lstart);
-        memcpy(ma.xcc_queue, D.xcc_queue, sizeof ma.xcc_queue);
-        ma.linv = linv; ma.linv_stride = LINV_STRIDE; ma.flag = flag_dev;
-        ma.vbuf = ws.vbuf; ma.nwide = nwide;
-        // a dependency that has not arrived after many times the predicted makespan never will: some workgroup of the
-        // program is not resident (another process holds the CUs).  The host then takes the stage kernels.
-        // (25 ms at least -- a starved factorisation used to cost 100 ms before the 3.7 ms fallback ran; 40 x the makespan covers a
-        // profiler's PMC passes, which slow the kernel 2-2.5x; chol_set_spin_limit_us overrides it -- tests provoke the fallback)
-        ma.spin_limit = (long long)std::max(25e3, 40.0 * plan.makespan_us) * 100LL;
-        if (g_spin_override.load() > 0) ma.spin_limit = g_spin_override.load();
-        static const char* TRACE = knob_str("STBA_MEGA_TRACE");
-        ma.trace = nullptr;
-        if (TRACE) STBA_HIP(hipMalloc(reinterpret_cast<void**>(&ma.trace), (size_t)plan.ntasks * 8 * sizeof(long long)));
-        struct TraceGuard { long long*& p; ~TraceGuard() { if (p) { (void)hipFree(p); p = nullptr; } } } trace_guard{ma.trace};
-        static DeviceOnce attr_set;
-        STBA_TRY(attr_set.run([]() -> int {
-            STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_mega_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, MEGA_SMEM_BYTES));
-            return STBA_OK;
-        }));
-        // (the previous factorisation of this device, if it went to ANOTHER stream, must have finished; on the same stream the
-        // order is there already -- and a wait on an event costs ~10 us of idle GPU even when the event has long fired)
-        // The event is recorded on the PREVIOUS stream only now, when a factorisation arrives on another one (it then also
-        // covers what that stream was given since, which is harmless): an engine that keeps to its stream never pays for an
-        // event record behind its persistent kernel (~6 us of idle GPU in front of the backward substitution).
-        if (D.last_stream != nullptr && D.last_stream != st) {
-            STBA_HIP(hipEventRecord(D.last, D.last_stream));
-            STBA_HIP(hipStreamWaitEvent(st, D.last, 0));
-        }
-        if (pre_event) STBA_HIP(hipEventRecord(pre_event, st));    // (timing only: the persistent kernel alone, without the flag reset in front)
-        hipLaunchKernelGGL(chol_mega_kernel, dim3(D.ncu), dim3(512), MEGA_SMEM_BYTES, st, ma);
-        D.last_stream = st;
-        if (TRACE) {    // debugging aid: dump the task timeline of this factorisation (tools/mega_trace.py)
-            std::vector<long long> h((size_t)plan.ntasks * 8);
-            std::vector<MegaTask> ht((size_t)plan.ntasks);
-            STBA_HIP(hipStreamSynchronize(st));
-            STBA_HIP(hipMemcpy(h.data(), ma.trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            STBA_HIP(hipMemcpy(ht.data(), plan.tasks, ht.size() * sizeof(MegaTask), hipMemcpyDeviceToHost));
-            if (FILE* f = fopen(TRACE, "wb")) {
-                fwrite(&plan.ntasks, sizeof(int), 1, f);
-                fwrite(ht.data(), sizeof(MegaTask), ht.size(), f);
-                fwrite(h.data(), sizeof(long long), h.size(), f);
-                fwrite(plan.sim_start.data(), sizeof(float), plan.sim_start.size(), f);
-                fclose(f);
-            }
-        }
-    }
-    STBA_TRY(mark((size_t)nblk * 4));
-    if (mid_event) STBA_HIP(hipEventRecord(mid_event, st));     // factorisation | backward substitution
-    // backward substitution: one small launch per block.  (A persistent variant -- one chain workgroup plus
-    // GEMV workers synchronised with flags -- was measured at 13.7 us per block against 7.7 us for these
-    // launches: every hand-off through memory costs ~2 us on this part, a dependent launch ~3 us.)
-    for (int b = nblk - 1; b >= 4 * nwide; --b) {
-        const int k0 = b * NB;
-        const int has_next = (b < nblk - 1) ? 1 : 0;
-        const int grid = 1 + (has_next ? b : 0);       // workgroup 0: this block; workgroup 1 + j: block column j < b
-        hipLaunchKernelGGL(chol_bwd_step_kernel, dim3(grid), dim3(1024), 0, st, A, lda, k0, has_next, linv + (size_t)b * LINV_STRIDE, x_dev);
-    }
-    // wide steps: apply the solution found last to everything above it, then solve four panels at once
-    for (int qw = nwide - 1; qw >= 0; --qw) {
-        const int row0 = qw * 4 * NB;
-        if (qw == nwide - 1) hipLaunchKernelGGL(chol_bwd_apply_kernel<4>, dim3((row0 + 4 * NB) / 32), dim3(1024), 0, st, A, lda, row0 + 4 * NB, x_dev);
-        else hipLaunchKernelGGL(chol_bwd_apply_kernel<16>, dim3((row0 + 4 * NB) / 32), dim3(1024), 0, st, A, lda, row0 + 4 * NB, x_dev);
-        hipLaunchKernelGGL(chol_bwd_wide_solve_kernel, dim3(4 * NB / BWD_SOLVE_ROWS), dim3(32 * BWD_SOLVE_ROWS), 0, st, A, lda, ws.vbuf + (size_t)qw * 16 * NB * NB, row0, x_dev);
-    }
-    STBA_TRY(mark((size_t)nblk * 4 + 1));
-    STBA_HIP(hipGetLastError());
-    if (prof) {
+    int mark(size_t k) { STBA_HIP(hipEventRecord(ev[k], st)); return STBA_OK; }
+    // waits for the stream; the times per class
+    int read_out() {
         STBA_HIP(hipStreamSynchronize(st));
         float ms = 0.f;
         for (int b = 0; b < nblk; ++b) {
@@ -1969,9 +1850,211 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
             (void)hipEventElapsedTime(&ms, ev[4 * (size_t)b + 2], ev[4 * (size_t)b + 3]); prof->ms_syrk += ms;
         }
         (void)hipEventElapsedTime(&ms, ev[(size_t)nblk * 4], ev[(size_t)nblk * 4 + 1]); prof->ms_bwd = ms;
-        for (auto& e : ev) (void)hipEventDestroy(e);
+        return STBA_OK;
+    }
+};
+}  // namespace
+static int chol_mark(CholTimer* timer, size_t k) { return timer ? timer->mark(k) : STBA_OK; }     // (null except under prof)
+
+// true: this call runs the stage kernels -- asked for, profiled, or in the cool-down: after a time-out (chol_note_timeout) the
+// device is taken to be shared, and the next factorisations do not try the persistent program again
+static bool chol_pick_schedule(int dev, const CholRequest& rq) {
+    int schedule = rq.schedule;
+    if (!rq.prof && schedule == CHOL_PERSISTENT) {
+        MegaDevice& D = mega_device(dev);
+        std::lock_guard<std::mutex> g(D.m);
+        if (D.cooldown > 0) { --D.cooldown; schedule = CHOL_STAGES; }
+    }
+    return rq.prof != nullptr || schedule == CHOL_STAGES;
+}
+
+// c.ws: the calling thread's workspace for the call's device, grown for its nblk and nwide
+static int chol_workspace(CholCall& c) {
+    static thread_local std::map<int, DevWs> ws_by_dev;
+    DevWs& ws = ws_by_dev[c.dev];
+    STBA_TRY(ws.linv.grow((size_t)c.nblk * CHOL_LINV_STRIDE));
+    STBA_TRY(ws.vbuf.grow((size_t)c.nwide * 16 * NB * NB));
+    c.ws = &ws;
+    return STBA_OK;
+}
+
+// The caller holds D.m.  The previous factorisation of this device, if it went to ANOTHER stream, must have finished: the device
+// runs one persistent program at a time, and the per-thread workspace is shared by every stream its thread factors on.  (On the
+// same stream the order is there already -- and a wait on an event costs ~10 us of idle GPU even when the event has long fired.)
+// The event is recorded on the PREVIOUS stream only now, when a factorisation arrives on another one (it then also covers what
+// that stream was given since, which is harmless): an engine that keeps to its stream never pays for an event record behind its
+// persistent kernel (~6 us of idle GPU in front of the backward substitution).
+static int chol_follow_previous(MegaDevice& D, hipStream_t st) {
+    if (D.last_stream != nullptr && D.last_stream != st) {
+        STBA_HIP(hipEventRecord(D.last, D.last_stream));
+        STBA_HIP(hipStreamWaitEvent(st, D.last, 0));
     }
     return STBA_OK;
+}
+
+// The stage kernels of panels 0 .. n_panels - 1 of A (lda x lda), in order on st, behind a reset of the flag.  Panel b: the diagonal
+// kernel, the panel solve of the (nblk - b - 1) * 8 row groups below it, the trailing update of what lies below and to the right;
+// its CHOL_LINV_STRIDE doubles of workspace are at linv + b CHOL_LINV_STRIDE.
+static int chol_stage_panels(double* A, int lda, int n_real, int n_panels, double* linv, int* flag_dev, hipStream_t st, CholTimer* timer) {
+    static DeviceOnce diag_attr;
+    STBA_TRY(diag_attr.run([]() -> int {
+        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Diag2Smem)));
+        return STBA_OK;
+    }));
+    STBA_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
+    const int nblk = lda / NB;
+    for (int b = 0; b < n_panels; ++b) {
+        double* li = linv + (size_t)b * CHOL_LINV_STRIDE;
+        const int k0 = b * NB;
+        const int mt = nblk - b - 1;
+        const int groups = mt * (NB / 16);
+        STBA_TRY(chol_mark(timer, 4 * (size_t)b + 0));
+        hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(512), sizeof(Diag2Smem), st, A, lda, k0, n_real, flag_dev, li + NB * NB);
+        STBA_TRY(chol_mark(timer, 4 * (size_t)b + 1));
+        hipLaunchKernelGGL(chol_trsm_kernel, dim3(groups + NB / 16), dim3(64), 0, st, A, lda, k0, groups, li, li + NB * NB);
+        STBA_TRY(chol_mark(timer, 4 * (size_t)b + 2));
+        if (mt > 0) launch_syrk(A, lda, k0, 0, mt * (mt + 1) / 2, st);
+        STBA_TRY(chol_mark(timer, 4 * (size_t)b + 3));
+    }
+    return STBA_OK;
+}
+
+// STAGE KERNELS: one kernel per stage and panel, in order on the caller's stream.  The diagnostic schedule of stba_cholesky_profile
+// (per-class event times) and the FALLBACK of the persistent program: it needs nothing resident, so it always finishes, whoever else
+// uses the device (the callers rebuild the matrix and come back through chol_factor_solve_stages: DenseWs::load_factor_solve,
+// ba_factor_solve / stba_ba_solve_reduced).
+static int chol_launch_stages(const CholCall& c, CholTimer* timer) {
+    {   // the stage schedule never probes the device (mega_device_init): the event is made here when there is none yet
+        MegaDevice& D = mega_device(c.dev);
+        std::lock_guard<std::mutex> dev_lock(D.m);
+        if (!D.last) STBA_HIP(hipEventCreateWithFlags(&D.last, hipEventDisableTiming));
+        STBA_TRY(chol_follow_previous(D, c.st));
+        D.last_stream = c.st;
+    }
+    return chol_stage_panels(c.A, c.lda, c.n, c.nblk, c.ws->linv.p, c.flag, c.st, timer);
+}
+
+// ws.plan: the persistent program for (nblk, nwide) on D's device -- built, uploaded and given its flag array when either differs
+// from what the plan was built for
+static int mega_plan_for(DevWs& ws, const MegaDevice& D, int nblk, int nwide) {
+    MegaPlan& plan = ws.plan;
+    if (plan.nblk == nblk && plan.nwide == nwide) return STBA_OK;
+    plan.tasks.release();
+    plan.sync.release();
+    plan = MegaPlan();
+    MegaMachine mach;
+    mach.nq = D.nq;
+    mach.wg = D.wg_per_xcd;
+    MegaSchedule sched;
+    mega_plan(sched, nblk, nwide, mach);
+    std::copy(sched.lstart.begin(), sched.lstart.end(), plan.lstart);
+    plan.sim_start.swap(sched.sim_start);
+    plan.makespan_us = sched.makespan_us;
+    STBA_TRY(plan.tasks.grow(sched.tasks.size()));
+    STBA_HIP(hipMemcpy(plan.tasks.p, sched.tasks.data(), sched.tasks.size() * sizeof(MegaTask), hipMemcpyHostToDevice));
+    plan.sync_ints = mega_flag_ints(nblk, nwide);
+    STBA_TRY(plan.sync.grow(plan.sync_ints));
+    plan.ntasks = (int)sched.tasks.size();
+    plan.nblk = nblk; plan.nwide = nwide;
+    return STBA_OK;
+}
+
+// debugging aid (STBA_MEGA_TRACE): the task timeline of the factorisation just launched on st, to a file (tools/mega_trace.py)
+static int mega_trace_dump(const char* path, const MegaPlan& plan, const long long* trace_dev, hipStream_t st) {
+    std::vector<long long> h((size_t)plan.ntasks * 8);
+    std::vector<MegaTask> ht((size_t)plan.ntasks);
+    STBA_HIP(hipStreamSynchronize(st));
+    STBA_HIP(hipMemcpy(h.data(), trace_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    STBA_HIP(hipMemcpy(ht.data(), plan.tasks.p, ht.size() * sizeof(MegaTask), hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(path, "wb")) {
+        fwrite(&plan.ntasks, sizeof(int), 1, f);
+        fwrite(ht.data(), sizeof(MegaTask), ht.size(), f);
+        fwrite(h.data(), sizeof(long long), h.size(), f);
+        fwrite(plan.sim_start.data(), sizeof(float), plan.sim_start.size(), f);
+        fclose(f);
+    }
+    return STBA_OK;
+}
+
+// The caller holds D.m.  Flag reset, the program's arguments, then the persistent kernel behind the device's previous one
+static int chol_launch_persistent(const CholCall& c, MegaDevice& D, hipEvent_t pre_event) {
+    const MegaPlan& plan = c.ws->plan;
+    hipLaunchKernelGGL(chol_reset_kernel, dim3((unsigned)((plan.sync_ints + 255) / 256)), dim3(256), 0, c.st, plan.sync.p, (int)plan.sync_ints, c.flag);
+    MegaArgs ma;
+    ma.A = c.A; ma.lda = c.lda; ma.n = c.n; ma.nblk = c.nblk;
+    ma.tasks = plan.tasks.p; ma.nq = D.nq; ma.sync = plan.sync.p;
+    memcpy(ma.lstart, plan.lstart, sizeof ma.lstart);
+    memcpy(ma.xcc_queue, D.xcc_queue, sizeof ma.xcc_queue);
+    ma.linv = c.ws->linv.p; ma.linv_stride = CHOL_LINV_STRIDE; ma.flag = c.flag;
+    ma.vbuf = c.ws->vbuf.p; ma.nwide = c.nwide;
+    // a dependency that has not arrived after many times the predicted makespan never will: some workgroup of the
+    // program is not resident (another process holds the CUs).  The host then takes the stage kernels.
+    // (25 ms at least -- a starved factorisation used to cost 100 ms before the 3.7 ms fallback ran; 40 x the makespan covers a
+    // profiler's PMC passes, which slow the kernel 2-2.5x; chol_set_spin_limit_us overrides it -- tests provoke the fallback)
+    ma.spin_limit = (long long)std::max(25e3, 40.0 * plan.makespan_us) * 100LL;
+    if (g_spin_override.load() > 0) ma.spin_limit = g_spin_override.load();
+    static const char* TRACE = knob_str("STBA_MEGA_TRACE");
+    ma.trace = nullptr;
+    if (TRACE) STBA_HIP(hipMalloc(reinterpret_cast<void**>(&ma.trace), (size_t)plan.ntasks * 8 * sizeof(long long)));
+    struct TraceGuard { long long*& p; ~TraceGuard() { if (p) { (void)hipFree(p); p = nullptr; } } } trace_guard{ma.trace};
+    STBA_TRY(chol_follow_previous(D, c.st));
+    if (pre_event) STBA_HIP(hipEventRecord(pre_event, c.st));    // (the persistent kernel alone, without the flag reset in front)
+    hipLaunchKernelGGL(chol_mega_kernel, dim3(D.ncu), dim3(512), MEGA_SMEM_BYTES, c.st, ma);
+    D.last_stream = c.st;
+    if (TRACE) STBA_TRY(mega_trace_dump(TRACE, plan, ma.trace, c.st));
+    return STBA_OK;
+}
+
+// production: the persistent dataflow program (see chol_mega_kernel).  The device's lock is held from the probe to the launch
+static int chol_persistent(const CholCall& c, hipEvent_t pre_event) {
+    MegaDevice& D = mega_device(c.dev);
+    std::lock_guard<std::mutex> dev_lock(D.m);
+    STBA_TRY(mega_device_init(D, c.st));       // (also makes D.last)
+    STBA_TRY(mega_plan_for(*c.ws, D, c.nblk, c.nwide));
+    return chol_launch_persistent(c, D, pre_event);
+}
+
+// backward substitution: one small launch per block.  (A persistent variant -- one chain workgroup plus
+// GEMV workers synchronised with flags -- was measured at 13.7 us per block against 7.7 us for these
+// launches: every hand-off through memory costs ~2 us on this part, a dependent launch ~3 us.)
+static void chol_backward(const CholCall& c) {
+    const double* linv = c.ws->linv.p;
+    // the tail, the last 1..4 panels, keeps single-panel steps, so that no inverse-block task runs behind the last diagonal block
+    for (int b = c.nblk - 1; b >= 4 * c.nwide; --b) {
+        const int k0 = b * NB;
+        const int has_next = (b < c.nblk - 1) ? 1 : 0;
+        const int grid = 1 + (has_next ? b : 0);       // workgroup 0: this block; workgroup 1 + j: block column j < b
+        hipLaunchKernelGGL(chol_bwd_step_kernel, dim3(grid), dim3(1024), 0, c.st, c.A, c.lda, k0, has_next, linv + (size_t)b * CHOL_LINV_STRIDE, c.x);
+    }
+    // wide steps: apply the solution found last to everything above it, then solve four panels at once
+    for (int qw = c.nwide - 1; qw >= 0; --qw) {
+        const int row0 = qw * 4 * NB;
+        if (qw == c.nwide - 1) hipLaunchKernelGGL(chol_bwd_apply_kernel<4>, dim3((row0 + 4 * NB) / 32), dim3(1024), 0, c.st, c.A, c.lda, row0 + 4 * NB, c.x);
+        else hipLaunchKernelGGL(chol_bwd_apply_kernel<16>, dim3((row0 + 4 * NB) / 32), dim3(1024), 0, c.st, c.A, c.lda, row0 + 4 * NB, c.x);
+        hipLaunchKernelGGL(chol_bwd_wide_solve_kernel, dim3(4 * NB / BWD_SOLVE_ROWS), dim3(32 * BWD_SOLVE_ROWS), 0, c.st, c.A, c.lda, c.ws->vbuf.p + (size_t)qw * 16 * NB * NB, row0, c.x);
+    }
+}
+
+// factorisation and solve of one padded system (common.hpp): the schedule, the workspace, the factorisation, the backward substitution
+static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st, const CholRequest& rq) {
+    if (lda % NB != 0 || lda < n + 1) return fail(STBA_ERR_INVALID_ARGUMENT, "chol: bad padded dimension");
+    CholCall c{A, lda, n, x_dev, flag_dev, st};
+    c.nblk = lda / NB;
+    STBA_HIP(hipGetDevice(&c.dev));
+    c.stages = chol_pick_schedule(c.dev, rq);
+    c.nwide = c.stages ? 0 : (c.nblk - 1) / 4;     // wide (4-panel) backward steps: the persistent program alone builds their inverse blocks
+    STBA_TRY(chol_workspace(c));
+    CholTimer events;
+    CholTimer* timer = rq.prof ? &events : nullptr;
+    if (timer) STBA_TRY(timer->start(rq.prof, c));
+    if (c.stages) STBA_TRY(chol_launch_stages(c, timer));
+    else STBA_TRY(chol_persistent(c, rq.pre_event));
+    STBA_TRY(chol_mark(timer, (size_t)c.nblk * 4));
+    if (rq.mid_event) STBA_HIP(hipEventRecord(rq.mid_event, st));     // factorisation | backward substitution
+    chol_backward(c);
+    STBA_TRY(chol_mark(timer, (size_t)c.nblk * 4 + 1));
+    STBA_HIP(hipGetLastError());
+    return timer ? timer->read_out() : STBA_OK;
 }
 
 // Explicit inverse of a small SPD matrix through a PARTIAL factorisation with the stage kernels (the pose graph's coarse
@@ -1981,26 +2064,11 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
 //        [ I   0 ]     factorisation, applied to ALL 2 np rows            ->    [ L^-T   -A^-1  ]
 // the panel solves turn the identity rows into X = I L^-T, and the trailing updates subtract X X^T = A^-1 from the lower
 // right block (lower triangle).  No factorisation of the lower right block follows, so it survives.
-// workspace: (NB NB + 8 256) doubles per panel (the diagonal tiles' inverses the panel solve multiplies by).
-size_t chol_spd_inverse_workspace_doubles(int np) { return (size_t)(np / NB) * ((size_t)NB * NB + 8 * 256); }
+// workspace: CHOL_LINV_STRIDE doubles per panel (the diagonal tiles' inverses the panel solve multiplies by).
+size_t chol_spd_inverse_workspace_doubles(int np) { return (size_t)(np / NB) * CHOL_LINV_STRIDE; }
 int chol_spd_inverse_dev(double* W, int ldw, int np, int n_real, int* flag_dev, double* work, hipStream_t st) {
     if (np % NB != 0 || ldw != 2 * np || np <= 0) return fail(STBA_ERR_INVALID_ARGUMENT, "chol_spd_inverse_dev: bad dimensions");
-    constexpr size_t LINV_STRIDE = (size_t)NB * NB + 8 * 256;
-    static DeviceOnce diag_attr;
-    STBA_TRY(diag_attr.run([]() -> int {
-        STBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Diag2Smem)));
-        return STBA_OK;
-    }));
-    STBA_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
-    const int nblk = ldw / NB;
-    for (int b = 0; b < np / NB; ++b) {
-        double* li = work + (size_t)b * LINV_STRIDE;
-        const int mt = nblk - b - 1;
-        hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(512), sizeof(Diag2Smem), st, W, ldw, b * NB, n_real, flag_dev, li + NB * NB);
-        const int groups = mt * (NB / 16);
-        hipLaunchKernelGGL(chol_trsm_kernel, dim3(groups + NB / 16), dim3(64), 0, st, W, ldw, b * NB, groups, li, li + NB * NB);
-        launch_syrk(W, ldw, b * NB, 0, mt * (mt + 1) / 2, st);
-    }
+    STBA_TRY(chol_stage_panels(W, ldw, n_real, np / NB, work, flag_dev, st, nullptr));
     STBA_HIP(hipGetLastError());
     return STBA_OK;
 }
@@ -2107,21 +2175,26 @@ int chol_yyt_lower_dev(const double* Y, size_t ldy, size_t kcols, double* S, int
 }
 
 int chol_factor_solve_dev(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st) {
-    return chol_run(A, lda, n, x_dev, flag_dev, st, nullptr);
+    return chol_run(A, lda, n, x_dev, flag_dev, st, CholRequest());
 }
 
 int chol_factor_solve_stages(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st) {
-    return chol_run(A, lda, n, x_dev, flag_dev, st, nullptr, nullptr, CHOL_STAGES);
+    CholRequest rq;
+    rq.schedule = CHOL_STAGES;
+    return chol_run(A, lda, n, x_dev, flag_dev, st, rq);
 }
 
 int chol_factor_solve_split(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st, hipEvent_t mid_event, hipEvent_t pre_event) {
-    return chol_run(A, lda, n, x_dev, flag_dev, st, nullptr, mid_event, CHOL_PERSISTENT, pre_event);
+    CholRequest rq;
+    rq.mid_event = mid_event; rq.pre_event = pre_event;
+    return chol_run(A, lda, n, x_dev, flag_dev, st, rq);
 }
 
 int chol_factor_solve_profiled(double* A, int lda, int n, double* x_dev, int* flag_dev, hipStream_t st,
                                CholProfile* prof) {
-    return chol_run(A, lda, n, x_dev, flag_dev, st, prof);
+    CholRequest rq;
+    rq.prof = prof;
+    return chol_run(A, lda, n, x_dev, flag_dev, st, rq);
 }
-
 
 }  // namespace stba

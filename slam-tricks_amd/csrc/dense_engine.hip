@@ -200,8 +200,8 @@ int stba_cholesky_time(int n, int reps, double* ms_avg, void* hip_stream) {
     STBA_TRY(require_device());
     DenseWs w;
     STBA_TRY(w.init(n, hip_stream));
-    hipEvent_t e0, e1;
-    STBA_HIP(hipEventCreate(&e0)); STBA_HIP(hipEventCreate(&e1));
+    DevEvent e0, e1;
+    STBA_TRY(e0.create()); STBA_TRY(e1.create());
     double total = 0.0;
     for (int k = 0; k < reps + 1; ++k) {
         STBA_TRY(w.synthesize());
@@ -213,7 +213,6 @@ int stba_cholesky_time(int n, int reps, double* ms_avg, void* hip_stream) {
         STBA_HIP(hipEventElapsedTime(&ms, e0, e1));
         if (k > 0) total += ms;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     *ms_avg = total / reps;
     return STBA_OK;
 }
@@ -257,8 +256,8 @@ int stba_cholesky_time_split(int n, int reps, double* ms_factor, double* ms_back
     STBA_TRY(require_device());
     DenseWs w;
     STBA_TRY(w.init(n, hip_stream));
-    hipEvent_t e0, ep, e1, e2;
-    STBA_HIP(hipEventCreate(&e0)); STBA_HIP(hipEventCreate(&ep)); STBA_HIP(hipEventCreate(&e1)); STBA_HIP(hipEventCreate(&e2));
+    DevEvent e0, ep, e1, e2;
+    STBA_TRY(e0.create()); STBA_TRY(ep.create()); STBA_TRY(e1.create()); STBA_TRY(e2.create());
     // ms_factor = the MEDIAN over the repetitions of the persistent kernel's own duration (an event right in front of it and one
     // right behind: what rocprofv3 reports for chol_mega_kernel; the flag reset in front, 5 us, is not in it) -- when a
     // factorisation went through the stage kernels instead (time-out fallback, cool-down) the whole of it, from e0
@@ -275,7 +274,6 @@ int stba_cholesky_time_split(int n, int reps, double* ms_factor, double* ms_back
         STBA_HIP(hipEventElapsedTime(&b, e1, e2));
         if (k > 0) { tf.push_back(a); tb.push_back(b); }
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(ep); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
     auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); const size_t h = v.size() / 2; return (v.size() & 1) ? v[h] : 0.5 * (v[h - 1] + v[h]); };
     *ms_factor = median(tf);
     *ms_backward = median(tb);
