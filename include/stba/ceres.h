@@ -145,7 +145,7 @@ constexpr int DYNAMIC = -1;
 class LossFunction { public: virtual ~LossFunction() = default; };
 
 // Ceres' loss functions (loss_function.h): Evaluate(s, rho) gives rho(s), rho'(s), rho''(s) at s = |r|^2, the formulas of the device
-// kernel (pg_engine.hip) on the host.  The classes are final: a dynamic_cast to one of them means exactly that loss.
+// kernel (pg_linearize.hip) on the host.  The classes are final: a dynamic_cast to one of them means exactly that loss.
 class TrivialLoss final : public LossFunction {
 public:
     void Evaluate(double s, double rho[3]) const { rho[0] = s; rho[1] = 1.0; rho[2] = 0.0; }

@@ -1,5 +1,5 @@
 // dd6.hpp -- the Cholesky factor of ONE symmetric positive definite 6 x 6 in double-double arithmetic, for both sides: the pose
-// graph factors its edge weights with it on the device (pg_information_kernel, pg_engine.hip), the bundle adjustment its priors'
+// graph factors its edge weights with it on the device (pg_information_kernel, pg_linearize.hip), the bundle adjustment its priors'
 // and relative poses' information matrices on the host (sqrt_information6, ba_factor_input.hpp).  The factor is made once per
 // setter call and is a 6 x 6 per factor, so its cost does not matter, while an FP64 factorisation loses about cond(Omega) eps in
 // its last pivots -- an error the caller could not tell from one of the solver's.

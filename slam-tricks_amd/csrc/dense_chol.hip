@@ -2058,7 +2058,7 @@ static int chol_run(double* A, int lda, int n, double* x_dev, int* flag_dev, hip
 }
 
 // Explicit inverse of a small SPD matrix through a PARTIAL factorisation with the stage kernels (the pose graph's coarse
-// operator, pg_engine.hip: 6 unknowns per group of nodes, a few hundred to ~1500 in all; applied once per PCG iteration as
+// operator, pg_coarse.hip: 6 unknowns per group of nodes, a few hundred to ~1500 in all; applied once per PCG iteration as
 // a dense product, so it is wanted explicitly).  W is ldw x ldw, ldw = 2 np, np a multiple of 128:
 //        [ A   . ]     panels 0 .. np/128 - 1 of the blocked right-looking      [ L       .     ]
 //        [ I   0 ]     factorisation, applied to ALL 2 np rows            ->    [ L^-T   -A^-1  ]

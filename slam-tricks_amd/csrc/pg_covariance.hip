@@ -274,11 +274,8 @@ struct Workspace {
     DevBuf<long long> src, dst;
     DevBuf<PgcCtrl> ctrl;
     MappedBuffer exp;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Workspace() {
-        exp.release();
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    DevEvent ev[2];
+    ~Workspace() { exp.release(); }
 };
 
 struct Request {
@@ -347,7 +344,7 @@ int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt
         STBA_TRY(ws.part.alloc((size_t)3 * nb * PGC_K)); STBA_TRY(ws.ctrl.alloc(1));
         if (!whole) { STBA_TRY(ws.out.alloc(out_count)); STBA_TRY(ws.src.alloc((size_t)36 * rq.n_pairs)); STBA_TRY(ws.dst.alloc((size_t)36 * rq.n_pairs)); }
         STBA_TRY(ws.exp.alloc((size_t)stamped_doubles(CX_COUNT)));
-        STBA_HIP(hipEventCreate(&ws.ev[0])); STBA_HIP(hipEventCreate(&ws.ev[1]));
+        STBA_TRY(ws.ev[0].create()); STBA_TRY(ws.ev[1].create());
         double* part_pq = ws.part; double* part_rz = ws.part + (size_t)nb * PGC_K; double* part_rr = ws.part + (size_t)2 * nb * PGC_K;
         STBA_HIP(hipEventRecord(ws.ev[0], st));
         hipLaunchKernelGGL(pgc_pack_kernel, dim3((unsigned)(((size_t)gr.m * 72 + 255) / 256)), dim3(256), 0, st, gr.m, dv.Ji, dv.Jj, ws.Jp);

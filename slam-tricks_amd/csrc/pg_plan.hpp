@@ -1,4 +1,4 @@
-// pg_plan.hpp -- the host decisions of the pose-graph engine (pg_engine.hip) that fix what its kernels may assume: the layout
+// pg_plan.hpp -- the host decisions of the pose-graph engine (pg_engine.hip and its units) that fix what its kernels may assume: the layout
 // constants and LDS sizes that host and kernels share, the check of the edges, the CSR of the edge ends, the sizes of the coarse
 // space, whether the PCG solve may run as one kernel, the two policies of the solve loop (forcing sequence, lagged coarse inverse)
 // and the gauge check of the covariance.  A function returns 0, or a status of include/stba.h with the reason in *why.

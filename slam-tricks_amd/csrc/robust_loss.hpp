@@ -1,5 +1,5 @@
 // robust_loss.hpp -- the robust loss functions, evaluated on the device: ONE definition for the pose graph's linearisation
-// (pg_engine.hip) and bundle adjustment's (ba_kernels.hip)
+// (pg_linearize.hip) and bundle adjustment's (ba_kernels.hip)
 #pragma once
 #include <cfloat>
 #include <vector>

@@ -1,4 +1,4 @@
-"""The arithmetic of pg_pcg_persistent_kernel (pg_engine.hip) restated in numpy, without a GPU: the Chronopoulos-Gear form of
+"""The arithmetic of pg_pcg_persistent_kernel (pg_pcg.hip) restated in numpy, without a GPU: the Chronopoulos-Gear form of
 preconditioned CG -- w = A u with u = M^-1 r, p and s = A p by recurrence, both dot products of a step in ONE reduction -- with the
 coarse residual of the two-level preconditioner carried by RECURRENCE (r_c <- r_c - alpha P^T s, P^T s = P^T w + beta P^T s), so that
 an iteration needs two exchanges (the neighbours' u; nine numbers per group) and no gather for the restriction.  Checked here:
