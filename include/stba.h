@@ -844,6 +844,41 @@ int stba_ba_relative_pose_count(const stba_ba* ba, int* n);
 int stba_ba_evaluate_relative_poses(stba_ba* ba, double* cost, double* r /*[n*6]*/, double* Ji /*[n*36]*/, double* Jj /*[n*36]*/);
 int stba_ba_relative_pose_kernel_geometry(const stba_ba* ba, int* groups_per_workgroup);
 
+/* ================================ bundle adjustment: landmark position priors (control points) ================================ */
+/* A prior k names a landmark j_k, a position ph_k and a 3 x 3 square-root information W_k (row-major):
+ *     r_k = p_j - ph_k          J_k = d r_k / d p_j = I  (exactly 0 for a constant landmark, pt_fixed: the prior then adds to the cost only)
+ *     cost += 1/2 |W_k r_k|^2
+ * A surveyed ground control point with its sigma, a LiDAR or map point, a depth prior, the landmark prior a marginalised window
+ * leaves behind; the gauge of a problem that fixes no camera (priors on four landmarks that are not coplanar make
+ * stba_ba_covariance_compute well defined).  Any number of priors, several on one landmark, landmarks without any.
+ *   stba_ba_set_landmark_priors   pt[n], position[n*3], and at most ONE of information[n*9] (symmetric positive definite; the lower
+ *                      triangle is factored on the host, Omega = L L^T, W = L^T, in double-double arithmetic: every entry of W within
+ *                      1 eps of the exact factor of the matrix given up to cond(Omega) = 1e12; else STBA_ERR_NOT_POSITIVE_DEFINITE)
+ *                      and sqrt_information[n*9] (any finite W, rank-deficient included: one non-zero row is a height-only control
+ *                      point).  Both NULL: the identity.  n = 0 clears the priors and is never refused: the engine then enqueues
+ *                      exactly what one that never had any enqueues.  STBA_ERR_INVALID_ARGUMENT, stba_last_error() naming the
+ *                      smallest such prior, nothing changed: a landmark index out of range, an entry that is not finite; also both
+ *                      weight arrays given with n > 0 (n = 0 reads none of the arrays).
+ *   stba_ba_landmark_prior_count  *n = the number of priors held.
+ *   stba_ba_evaluate_landmark_priors   at the current parameters: cost = 1/2 sum |W r|^2 of the priors alone, r[n*3] = W_k r_k,
+ *                      J[n*9] = W_k J_k (3 x 3 row-major), in the caller's order; any may be NULL.
+ *   stba_ba_landmark_prior_kernel_geometry   DIAGNOSTIC, NOT A STABLE INTERFACE (the tests derive their scenes from it): landmarks
+ *                      (with priors or without) per workgroup of the block kernel.
+ * With priors, stba_ba_evaluate's and stba_ba_cost's cost, the LM summary and trace and the gradient norm are those of the SUM,
+ * observations plus priors (r, Jc, Jp stay per observation); stba_ba_normal_blocks' Hpp, gp include the priors' W^T W, W^T r' (Hcc,
+ * gc keep their bits, and so do the blocks of landmarks without priors); every solver path runs on the sum: stba_ba_solve /
+ * _lm_iterations with LM on PAIRS and DENSE, ITERATIVE_SCHUR engines with every preconditioner (the inexact-step model gains the
+ * priors' rows), DOGLEG (its three J sums do), the stage entry points, stba_ba_covariance_compute and its getters; losses,
+ * information matrices, pose priors and relative-pose factors combine freely.  A setter that succeeds invalidates the current
+ * linearisation and releases a held covariance.  LIMITS, refused with STBA_ERR_INVALID_ARGUMENT, the state untouched, in both
+ * orders of the two calls: inner iterations (the per-landmark sweep solves from the observation records), a host lineariser, an
+ * all-reduce hook / communicator / world_size > 1.  STBA_VERSION is unchanged: test for the symbols. */
+int stba_ba_set_landmark_priors(stba_ba* ba, int n, const int* pt, const double* position /*[n*3]*/,
+                                const double* information /*[n*9] or NULL*/, const double* sqrt_information /*[n*9] or NULL*/);
+int stba_ba_landmark_prior_count(const stba_ba* ba, int* n);
+int stba_ba_evaluate_landmark_priors(stba_ba* ba, double* cost, double* r /*[n*3]*/, double* J /*[n*9], 3x3 row-major*/);
+int stba_ba_landmark_prior_kernel_geometry(const stba_ba* ba, int* landmarks_per_workgroup);
+
 /* ================================ small dense LM problems ================================ */
 /* Residual blocks evaluated by a HOST callback (user CostFunction::Evaluate, solver.hpp:168-212;
  * autodiff functors are differentiated on the host by the C++ shim), normal equations + LM

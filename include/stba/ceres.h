@@ -621,6 +621,51 @@ private:
     bool has_w_ = false;
 };
 
+// A prior on a landmark's position (a control point), the host form of the device engine's factor
+// (stba_ba_set_landmark_priors): block {landmark 3} -> 3 residuals r = W (p - ph); W the 3 x 3 row-major square-root information
+// (nullptr: the identity; one non-zero row: a height-only control point).  The Jacobian is W.  Same operations in the same order as
+// the device (slam-tricks_amd/csrc/ba_landmark_prior.hpp): row i of W r as (W_i0 r_0 + W_i1 r_1) + W_i2 r_2, and like there WITHOUT
+// contraction into FMAs whatever the build's flags (W r cancels for a tight prior): clang by its pragma, GCC -- which contracts by
+// default wherever the target has FMA -- by the optimize attribute on Evaluate.
+// On a problem that otherwise takes "gpu-ba", the recognition (BaStructure) sets these blocks aside and Solve / Covariance hand them
+// to the device engine, provided the block is a landmark that some observation names, carries no chart and no bounds, and the
+// residual block has no LossFunction; otherwise, and on every other route, it is an ordinary host cost function.  ITERATIVE_SCHUR
+// and DOGLEG take them; with use_inner_iterations the solve is refused (FAILURE, parameters untouched, the reason in the message).
+#ifndef STBA_CERES_NO_CONTRACT       // (the test defines it empty to see that the compiler at hand WOULD contract)
+#if defined(__GNUC__) && !defined(__clang__)
+#define STBA_CERES_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define STBA_CERES_NO_CONTRACT
+#endif
+#endif
+class LandmarkPriorFactor : public SizedCostFunction<3, 3> {
+public:
+    LandmarkPriorFactor(const double position[3], const double* sqrt_information = nullptr) {
+        for (int k = 0; k < 3; ++k) pos_[k] = position[k];
+        for (int k = 0; k < 9; ++k) w_[k] = sqrt_information ? sqrt_information[k] : (k % 4 == 0 ? 1.0 : 0.0);
+        has_w_ = sqrt_information != nullptr;
+    }
+    static LandmarkPriorFactor* Create(const double position[3], const double* sqrt_information = nullptr) {
+        return new LandmarkPriorFactor(position, sqrt_information);
+    }
+    const double* position() const { return pos_; }
+    const double* sqrt_information() const { return has_w_ ? w_ : nullptr; }      // nullptr: made without one (identity)
+    const double* weights() const { return w_; }                                  // the 9 entries either way
+    STBA_CERES_NO_CONTRACT bool Evaluate(double const* const* p, double* residuals, double** jacobians) const override {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        const double r[3] = {p[0][0] - pos_[0], p[0][1] - pos_[1], p[0][2] - pos_[2]};
+        for (int i = 0; i < 3; ++i) residuals[i] = (w_[i * 3] * r[0] + w_[i * 3 + 1] * r[1]) + w_[i * 3 + 2] * r[2];
+        if (jacobians && jacobians[0]) for (int k = 0; k < 9; ++k) jacobians[0][k] = w_[k];
+        return true;
+    }
+private:
+    double pos_[3];
+    double w_[9];
+    bool has_w_ = false;
+};
+
 // A relative-pose measurement between two cameras, the host form of the device engine's factor
 // (stba_ba_set_relative_poses): blocks {q_i 4, t_i 3, q_j 4, t_j 3} -> 6 residuals
 //     r = W [ Log(qz^-1 (x) (q_i^-1 (x) q_j)) ; R_i^T (t_j - t_i) - tz ],   order [rot(3), pos(3)],
@@ -1387,6 +1432,10 @@ struct BaLayout : LossTable {                // (the losses: per observation, th
     // stba_ba_set_relative_poses takes them
     std::vector<int> rel_i, rel_j;
     std::vector<double> rel_meas, rel_w;
+    // LandmarkPriorFactor blocks, set aside the same way: the landmark, position [3], W [9] as
+    // stba_ba_set_landmark_priors takes them
+    std::vector<int> lp_pt;
+    std::vector<double> lp_pos, lp_w;
     const Problem::Residual& res_of(Problem& p, size_t k) const { return p.residuals()[obs_res.empty() ? k : (size_t)obs_res[k]]; }
 };
 
@@ -1429,19 +1478,20 @@ inline bool BaStructure(Problem& p, BaLayout* L, std::vector<const CostFunction*
     std::vector<const std::type_info*> seen_types;
     // PosePriorFactor blocks are set aside (their residual block index and their two parameter blocks, resolved to a camera behind
     // the loop): from the first one on, observation k (the index of every per-observation array) is no longer residual block kr
-    std::vector<size_t> prior_res, rel_res;          // (rel_res: CameraRelativePoseFactor blocks, the same way)
+    std::vector<size_t> prior_res, rel_res, lp_res;  // (rel_res: CameraRelativePoseFactor blocks, lp_res: LandmarkPriorFactor blocks, the same way)
     size_t k = 0;
     for (size_t kr = 0; kr < nr; ++kr) {
         const auto& r = res[kr];
         if (r.blocks.size() != 3 || !IsReprojectionShape(r.cost)) {
             const bool is_prior = r.blocks.size() == 2 && dynamic_cast<const PosePriorFactor*>(r.cost);
             const bool is_rel = r.blocks.size() == 4 && dynamic_cast<const CameraRelativePoseFactor*>(r.cost);
-            if (r.loss || !(is_prior || is_rel)) return false;
-            if (prior_res.empty() && rel_res.empty()) { L->obs_res.resize(k); for (size_t i = 0; i < k; ++i) L->obs_res[i] = (int)i; }
-            (is_prior ? prior_res : rel_res).push_back(kr);
+            const bool is_lp = r.blocks.size() == 1 && dynamic_cast<const LandmarkPriorFactor*>(r.cost);
+            if (r.loss || !(is_prior || is_rel || is_lp)) return false;
+            if (prior_res.empty() && rel_res.empty() && lp_res.empty()) { L->obs_res.resize(k); for (size_t i = 0; i < k; ++i) L->obs_res[i] = (int)i; }
+            (is_prior ? prior_res : is_rel ? rel_res : lp_res).push_back(kr);
             continue;
         }
-        if (!prior_res.empty() || !rel_res.empty()) L->obs_res.push_back((int)kr);
+        if (!prior_res.empty() || !rel_res.empty() || !lp_res.empty()) L->obs_res.push_back((int)kr);
         const std::type_info& ti = typeid(*r.cost);
         if (!last_type || !(ti == *last_type)) {
             last_type = &ti;
@@ -1473,7 +1523,7 @@ inline bool BaStructure(Problem& p, BaLayout* L, std::vector<const CostFunction*
         L->obs_cam[k] = c; L->obs_pt[k] = j;
         ++k;
     }
-    if (!prior_res.empty() || !rel_res.empty()) {
+    if (!prior_res.empty() || !rel_res.empty() || !lp_res.empty()) {
         const size_t no = k;
         if (no == 0) return false;
         L->obs_cam.resize(no); L->obs_pt.resize(no); L->feat.resize(2 * no); L->user.resize(no);
@@ -1498,6 +1548,16 @@ inline bool BaStructure(Problem& p, BaLayout* L, std::vector<const CostFunction*
             L->rel_i.push_back(ci); L->rel_j.push_back(cj);
             L->rel_meas.insert(L->rel_meas.end(), f->measurement(), f->measurement() + 7);
             L->rel_w.insert(L->rel_w.end(), f->weights(), f->weights() + 36);
+        }
+        for (size_t kr : lp_res) {
+            // a landmark prior's block must be a landmark that some observation names (which has neither chart nor bounds)
+            const auto& r = res[kr];
+            const int j = pt_of[(size_t)r.blocks[0]];
+            if (j < 0) return false;
+            auto* f = static_cast<const LandmarkPriorFactor*>(r.cost);
+            L->lp_pt.push_back(j);
+            L->lp_pos.insert(L->lp_pos.end(), f->position(), f->position() + 3);
+            L->lp_w.insert(L->lp_w.end(), f->weights(), f->weights() + 9);
         }
     }
     for (size_t c = 0; c < L->rot_block.size(); ++c)                // a block cannot be a rotation AND a landmark / position
@@ -1588,7 +1648,9 @@ struct Recognition {
     int types = -1, blocks = -1;     // the lazy halves: -1 not asked yet, 0 failed, 1 passed
     bool dropped = false;            // the end-point check failed: the device-factor reading is off
 
-    bool Special() const { return !ba.prior_cam.empty() || !ba.rel_i.empty(); }
+    bool Special() const { return !ba.prior_cam.empty() || !ba.rel_i.empty() || !ba.lp_pt.empty(); }
+    // the camera-side factors, which DOGLEG and ITERATIVE_SCHUR engines do not take (LandmarkPriorFactor blocks they do)
+    bool CameraSpecial() const { return !ba.prior_cam.empty() || !ba.rel_i.empty(); }
     // the shape-only reading (blocks 4 / 3 / 3 -> 2, no prior or relative-pose block): the factor may stay the user's ("gpu-ba-hostjac")
     bool ShapeRaw() const { return structure && !Special(); }
     bool Shape() const { return ShapeRaw() && charts; }
@@ -1800,8 +1862,8 @@ struct BaSetup {
     const Solver::Options* solve;      // Solve: the trust-region strategy; null: Covariance
     const InnerGroups* inner;          // Solve with inner iterations; null: none
 };
-// The layout's sqrt_info, losses, relative poses, priors and the host lineariser to the engine, then Solve's trust region and inner
-// iterations.  Returns the NAME of the first call that failed (its text: stba_last_error()), or null.  One order for Solve and
+// The layout's sqrt_info, losses, relative poses, pose priors, landmark priors and the host lineariser to the engine, then Solve's
+// trust region and inner iterations.  Returns the NAME of the first call that failed (its text: stba_last_error()), or null.  One order for Solve and
 // Covariance: relative poses before priors, so that an engine that takes neither (ITERATIVE_SCHUR) names the relative poses.
 inline const char* ConfigureBa(stba_ba* ba, const BaLayout& L, const BaSetup& s) {
     // (weighted ReprojectionFactors; with host Jacobians the factors whiten themselves)
@@ -1814,6 +1876,9 @@ inline const char* ConfigureBa(stba_ba* ba, const BaLayout& L, const BaSetup& s)
                                                        L.rel_w.data()) != STBA_OK) return "stba_ba_set_relative_poses";
     if (!L.prior_cam.empty() && stba_ba_set_pose_priors(ba, (int)L.prior_cam.size(), L.prior_cam.data(), L.prior_pose.data(), nullptr,
                                                         L.prior_w.data()) != STBA_OK) return "stba_ba_set_pose_priors";
+    // (LandmarkPriorFactor blocks: every engine that gets here takes them; inner iterations are refused by DecideSolve)
+    if (!L.lp_pt.empty() && stba_ba_set_landmark_priors(ba, (int)L.lp_pt.size(), L.lp_pt.data(), L.lp_pos.data(), nullptr, L.lp_w.data()) != STBA_OK)
+        return "stba_ba_set_landmark_priors";
     if (s.host && stba_ba_set_host_linearizer(ba, &BaHostLinearize, s.host) != STBA_OK) return "stba_ba_set_host_linearizer";
     if (s.solve && s.solve->trust_region_strategy_type == DOGLEG && stba_ba_set_trust_region(ba, STBA_TR_TRADITIONAL_DOGLEG) != STBA_OK)
         return "stba_ba_set_trust_region";
@@ -2165,7 +2230,8 @@ inline Decision DecideSolve(const Solver::Options& o, Recognition& r, InnerGroup
     if (dogleg) {
         if (o.dogleg_type != TRADITIONAL_DOGLEG) return d.Refuse(Decision::DOGLEG_STAGE, "SUBSPACE_DOGLEG is not implemented by this layer (TRADITIONAL_DOGLEG is)");
         if (iterative) return d.Refuse(Decision::DOGLEG_STAGE, "DOGLEG only supports exact factorization based linear solvers, not ITERATIVE_SCHUR");
-        if (!r.ShapeRaw()) {
+        // (LandmarkPriorFactor blocks go with DOGLEG on "gpu-ba": the engine's three J sums carry their rows)
+        if (!r.ShapeRaw() && !(r.structure && !r.CameraSpecial() && r.Factor())) {
             const bool special = r.structure && r.Types();
             return d.Refuse(Decision::DOGLEG_STAGE,
                 special && !r.ba.rel_i.empty() ? "DOGLEG with CameraRelativePoseFactor (relative pose) blocks is not implemented (the dogleg's |J g|^2 is summed from the observation records)"
@@ -2179,7 +2245,8 @@ inline Decision DecideSolve(const Solver::Options& o, Recognition& r, InnerGroup
         else if (!(o.inner_iteration_tolerance >= 0.0)) why = "inner_iteration_tolerance must be >= 0";
         else if (!r.Shape() && r.structure && r.Special() && r.Types())
             why = !r.ba.rel_i.empty() ? "inner iterations with CameraRelativePoseFactor (relative pose) blocks are not implemented"
-                                      : "inner iterations with PosePriorFactor blocks are not implemented";
+                  : !r.ba.prior_cam.empty() ? "inner iterations with PosePriorFactor blocks are not implemented"
+                                            : "inner iterations with LandmarkPriorFactor blocks are not implemented (the per-landmark sweep solves from the observation records)";
         else if (!r.Shape())
             why = "inner iterations are implemented for bundle adjustment on the gpu-ba path only, not for problems that take gpu-pg or gpu-dense-callback";
         else if (r.force_callback) why = "inner iterations are implemented on the gpu-ba path only, not on gpu-ba-hostjac (force_callback_path)";

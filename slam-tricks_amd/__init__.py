@@ -90,6 +90,8 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry",
            "stba_ba_set_relative_poses", "stba_ba_relative_pose_count", "stba_ba_evaluate_relative_poses",
            "stba_ba_relative_pose_kernel_geometry",
+           "stba_ba_set_landmark_priors", "stba_ba_landmark_prior_count", "stba_ba_evaluate_landmark_priors",
+           "stba_ba_landmark_prior_kernel_geometry",
            "stba_live_device_buffers"]
 
 
@@ -243,11 +245,13 @@ class BAEngine:
     implicitly applied reduced system, no S: stba_ba_create_ex; set_pcg / pcg_summary / schur_apply)."""
 
     def __init__(self, cams, pts, obs_cam, obs_pt, obs_feat, cam_fixed=None, pt_fixed=None, stream=None, linear_solver="dense_schur",
-                 loss=None, information=None, sqrt_information=None, pose_priors=None, relative_poses=None):
+                 loss=None, information=None, sqrt_information=None, pose_priors=None, relative_poses=None,
+                 landmark_priors=None):
         """loss: per-observation robust losses as PGEngine takes them -- a kind name, a tuple (kind, a[, b[, scale]]) or a dict of
         set_loss's arguments.  information / sqrt_information (one of the two): per-observation 2 x 2 weights, the shapes that
         set_information takes.  pose_priors: dict(cams=, poses=, information= | sqrt_information=), set_pose_priors' arguments.
-        relative_poses: dict(cam_i=, cam_j=, measurements=, information= | sqrt_information=), set_relative_poses' arguments"""
+        relative_poses: dict(cam_i=, cam_j=, measurements=, information= | sqrt_information=), set_relative_poses' arguments.
+        landmark_priors: dict(points=, positions=, information= | sqrt_information=), set_landmark_priors' arguments"""
         if information is not None and sqrt_information is not None:
             raise ValueError("BAEngine: give information or sqrt_information, not both")
         self._h = C.c_void_p()
@@ -284,6 +288,8 @@ class BAEngine:
             self.set_pose_priors(**pose_priors)
         if relative_poses is not None:
             self.set_relative_poses(**relative_poses)
+        if landmark_priors is not None:
+            self.set_landmark_priors(**landmark_priors)
 
     def close(self):
         if self._h:
@@ -489,6 +495,59 @@ class BAEngine:
         """groups (cameras with edges, then pairs with edges) per workgroup of the block kernel (a diagnostic)"""
         k = C.c_int()
         _chk(lib().stba_ba_relative_pose_kernel_geometry(self._h, C.byref(k)), "stba_ba_relative_pose_kernel_geometry")
+        return k.value
+
+    # ---- landmark position priors (control points)
+    def set_landmark_priors(self, points, positions, information=None, sqrt_information=None):
+        """soft constraints on landmark positions (stba_ba_set_landmark_priors): prior k pulls landmark points[k] towards positions[k]
+        with cost 1/2 |W_k (p - positions[k])|^2 -- a ground control point, a map or LiDAR point, a depth prior.  information:
+        (n, 3, 3) symmetric positive definite (W = L^T of its Cholesky factor) or sqrt_information: (n, 3, 3) any finite W (one
+        non-zero row: a height-only control point); a single (3, 3) is taken for every prior, an (n,) array of sigmas means I / sigma;
+        neither: the identity.  Several priors may name one landmark.  points empty (or None) clears the priors."""
+        if information is not None and sqrt_information is not None:
+            raise ValueError("BAEngine: give information or sqrt_information, not both")
+        j = np.ascontiguousarray([] if points is None else points, dtype=np.int32).reshape(-1)
+        n = len(j)
+        if n == 0:
+            _chk(lib().stba_ba_set_landmark_priors(self._h, 0, None, None, None, None), "stba_ba_set_landmark_priors")
+            return
+        ps = _f64(positions).reshape(-1, 3)
+        if len(ps) != n:
+            raise ValueError(f"BAEngine: {n} prior landmarks but {len(ps)} prior positions")
+
+        def blocks(w, name, power):
+            if w is None:
+                return None
+            w = np.asarray(w, np.float64)
+            if w.shape == (n,):                     # sigmas
+                w = (w ** power)[:, None, None] * np.eye(3)[None]
+            if w.shape == (3, 3):
+                w = np.broadcast_to(w, (n, 3, 3))
+            if w.shape != (n, 3, 3):
+                raise ValueError(f"BAEngine: landmark-prior {name} must have shape (3, 3), ({n}, 3, 3) or ({n},), got {w.shape}")
+            return np.ascontiguousarray(w)
+        om, w = blocks(information, "information", -2.0), blocks(sqrt_information, "sqrt_information", -1.0)
+        _chk(lib().stba_ba_set_landmark_priors(self._h, n, _p(j), _p(ps), _p(om), _p(w)), "stba_ba_set_landmark_priors")
+
+    def landmark_prior_count(self):
+        n = C.c_int()
+        _chk(lib().stba_ba_landmark_prior_count(self._h, C.byref(n)), "stba_ba_landmark_prior_count")
+        return n.value
+
+    def evaluate_landmark_priors(self, jac=True):
+        """(cost, r [n, 3], J [n, 3, 3] | None) of the landmark priors alone at the current parameters: whitened, in the order they
+        were set"""
+        n = self.landmark_prior_count()
+        cost = C.c_double()
+        r = np.zeros((n, 3))
+        J = np.zeros((n, 3, 3)) if jac else None
+        _chk(lib().stba_ba_evaluate_landmark_priors(self._h, C.byref(cost), _p(r), _p(J)), "stba_ba_evaluate_landmark_priors")
+        return cost.value, r, J
+
+    def landmark_prior_kernel_geometry(self):
+        """landmarks per workgroup of the block kernel (a diagnostic: stba_ba_landmark_prior_kernel_geometry)"""
+        k = C.c_int()
+        _chk(lib().stba_ba_landmark_prior_kernel_geometry(self._h, C.byref(k)), "stba_ba_landmark_prior_kernel_geometry")
         return k.value
 
     def loss_kernel_geometry(self):

@@ -8,6 +8,7 @@
 #include "ba_kernels.hpp"
 #include "ba_prior.hpp"
 #include "ba_between.hpp"
+#include "ba_landmark_prior.hpp"
 #include "iterative_schur.hpp"
 #include "ba_features.hpp"
 #include "inner_plan.hpp"
@@ -60,6 +61,17 @@ struct BetweenSet {
     BetweenArgs args(const unsigned char* cam_fixed) const {
         return BetweenArgs{n, n_cg, n_pg, i, j, meas, W, cg_ptr, cg_cam, cg_ref, pg_ptr, pg_pair, pg_ref, cam_fixed};
     }
+};
+
+// landmark position priors (stba_ba_set_landmark_priors; ba_landmark_prior.hip): grouped by landmark -- start
+// [n_pts + 1] over ALL landmarks, inside a group the caller's order -- with the landmark, the position and the 3 x 3 square-root
+// information of every prior in that order; order: grouped position -> the caller's index; cost_part: the cost form's partials
+// (landmark_prior_cost_grid(n) of them)
+struct LandmarkPriorSet {
+    int n = 0;
+    DevBuf<int> start, pt;
+    DevBuf<double> pos, W, cost_part;
+    std::vector<int> order;
 };
 
 // inner iterations (stba_ba_set_inner_iterations; inner_iterations.hip): the ordering as per-group ranges of a
@@ -183,7 +195,15 @@ struct stba_ba {
     // With edges the cost partials carry one more slot, behind the priors' where there are priors; the block form adds to Hcc, gc AND
     // to the blocks (hi, lo) of S behind the Schur step
     BetweenSet btw;
-    int n_cost() const { return lin_grid + (prior.n ? 1 : 0) + (btw.n ? 1 : 0); }
+    // With landmark priors one more slot again, the last; the block form adds to Hpp6, gp right behind the landmark-block kernel
+    // (ba_normal_blocks) and makes that kernel's max |gp| partials again, so that everything downstream sees the sum
+    LandmarkPriorSet lprior;
+    int n_cost() const { return lin_grid + (prior.n ? 1 : 0) + (btw.n ? 1 : 0) + (lprior.n ? 1 : 0); }
+    LandmarkPriorArgs landmark_prior_args() const { return LandmarkPriorArgs{lprior.n, np, lprior.start, lprior.pt, lprior.pos, lprior.W, pt_fixed}; }
+    // the priors' rows for the model terms summed from the records (made at lin_which); no priors: start null, nothing is added
+    LandmarkPriorRows landmark_prior_rows() const {
+        return lprior.n ? LandmarkPriorRows{lprior.start, lprior.pos, lprior.W, pts[lin_which]} : LandmarkPriorRows{};
+    }
     PriorArgs prior_args() const { return prior.args(cam_fixed); }
     BetweenArgs between_args() const { return btw.args(cam_fixed); }
 
@@ -237,7 +257,7 @@ inline const double* ba_general_jc(const stba_ba* b) { return ba_wants_general_f
 // `who` asks for its feature (sets: it sets it, false: it clears it) on this engine: STBA_OK, or the refusal of ba_features.hpp
 inline int ba_refuse(const stba_ba* b, const char* who, bool sets = true) {
     const unsigned held = ba_held_features(b->iterative, b->trust_region == STBA_TR_TRADITIONAL_DOGLEG, b->inner.on,b->hl_fn != nullptr,
-                                           b->ar != nullptr, b->loss.kind.get() != nullptr, b->winfo.get() != nullptr, b->prior.n, b->btw.n);
+                                           b->ar != nullptr, b->loss.kind.get() != nullptr, b->winfo.get() != nullptr, b->prior.n, b->btw.n, b->lprior.n);
     std::string why;
     const int code = ba_conflict(who, held, &why, sets);
     return code ? fail(code, why) : STBA_OK;

@@ -1,6 +1,6 @@
 // ba_factors.hip -- the factors of the bundle adjustment through the C ABI (include/stba.h): the host lineariser, the loss table, the
-// per-observation weights, the camera pose priors and the relative-pose factors -- their setters, counts, kernel geometries and
-// evaluate_* entry points.  Host code only: the kernels are in ba_kernels.hip, ba_prior.hip and ba_between.hip.
+// per-observation weights, the camera pose priors, the relative-pose factors and the landmark position priors -- their setters, counts, kernel geometries and
+// evaluate_* entry points.  Host code only: the kernels are in ba_kernels.hip, ba_prior.hip, ba_between.hip and ba_landmark_prior.hip.
 // A setter checks first (ba_features.hpp: does the engine take the factor at all; ba_factor_input.hpp: every row, into host vectors, the
 // smallest bad index named), then builds and uploads a LOCAL set, then commits: ba_factors_changed and one move assignment.
 #include "ba_engine.hpp"
@@ -324,6 +324,93 @@ int stba_ba_evaluate_relative_poses(stba_ba* b, double* cost, double* r, double*
     }
     STBA_HIP(hipStreamSynchronize(b->st));
     if (cost) *cost = 0.5 * c2;
+    return STBA_OK;
+}
+
+// ---- landmark position priors.  As with the pose priors everything is checked -- and, for the information form,
+// factored -- on the host BEFORE anything is replaced; the priors are grouped by landmark (a stable sort: inside a group the caller's
+// order), uploaded into NEW arrays that are swapped in.  n == 0 releases them and is never refused: the engine then enqueues exactly
+// what one that never had priors enqueues
+int stba_ba_set_landmark_priors(stba_ba* b, int n, const int* pt, const double* position, const double* information, const double* sqrt_information) {
+    const std::string who = "stba_ba_set_landmark_priors";
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null engine");
+    if (n < 0) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": n is negative");
+    LandmarkPriorSet fresh;
+    if (n > 0) {                // (n == 0 reads none of the arrays and is never refused)
+        if (information && sqrt_information) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": give information or sqrt_information, not both");
+        if (!pt || !position) return fail(STBA_ERR_INVALID_ARGUMENT, who + ": null pt or position array");
+        STBA_TRY(ba_refuse(b, who.c_str()));
+        const size_t m = (size_t)n;
+        std::vector<double> hw(m * 9);
+        for (size_t k = 0; k < m; ++k) {
+            std::string why;
+            const int rc = landmark_prior_check(pt[k], b->np, position + k * 3, information ? information + k * 9 : nullptr,
+                                                sqrt_information ? sqrt_information + k * 9 : nullptr, &hw[k * 9], &why);
+            if (rc) return fail(rc, who + ": prior " + std::to_string(k) + ": " + why);
+        }
+        std::vector<int> start;
+        landmark_prior_group(m, pt, b->np, fresh.order, start);
+        std::vector<int> gpt(m);
+        std::vector<double> gpos(m * 3), gw(m * 9);
+        for (size_t p = 0; p < m; ++p) {
+            const size_t k = (size_t)fresh.order[p];
+            gpt[p] = pt[k];
+            memcpy(&gpos[p * 3], position + k * 3, 3 * sizeof(double));
+            memcpy(&gw[p * 9], &hw[k * 9], 9 * sizeof(double));
+        }
+        fresh.n = n;
+        STBA_TRY(to_device(who, fresh.start, start, b->st)); STBA_TRY(to_device(who, fresh.pt, gpt, b->st));
+        STBA_TRY(to_device(who, fresh.pos, gpos, b->st)); STBA_TRY(to_device(who, fresh.W, gw, b->st));
+        STBA_TRY(fresh.cost_part.alloc((size_t)landmark_prior_cost_grid(n)));
+        if (hipStreamSynchronize(b->st) != hipSuccess) return fail(STBA_ERR_HIP, who + ": upload failed");
+    }
+    STBA_TRY(ba_factors_changed(b));
+    b->lprior = std::move(fresh);
+    return STBA_OK;
+}
+
+int stba_ba_landmark_prior_count(const stba_ba* b, int* n) {
+    if (!b || !n) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_landmark_prior_count: null argument");
+    *n = b->lprior.n;
+    return STBA_OK;
+}
+
+int stba_ba_landmark_prior_kernel_geometry(const stba_ba* b, int* landmarks_per_workgroup) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_landmark_prior_kernel_geometry: null engine");
+    if (landmarks_per_workgroup) *landmarks_per_workgroup = LP_LM_PER_WG;
+    return STBA_OK;
+}
+
+// the whitened residuals and Jacobians of the priors at the current parameters, by the block kernel itself (no blocks written),
+// and their cost by the cost kernel; the caller's order.  The engine's linearisation state is not touched
+int stba_ba_evaluate_landmark_priors(stba_ba* b, double* cost, double* r, double* J) {
+    if (!b) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_ba_evaluate_landmark_priors: null engine");
+    if (cost) *cost = 0.0;
+    if (!b->lprior.n) return STBA_OK;
+    const size_t m = (size_t)b->lprior.n;
+    DevBuf<double> dr, dj, dcost;
+    std::vector<double> hr, hj;
+    double c2 = 0.0;
+    if (r || J) {
+        STBA_TRY(dr.alloc(m * 3));
+        STBA_TRY(dj.alloc(m * 9));
+        STBA_TRY(launch_landmark_prior_blocks(b->landmark_prior_args(), b->pts[b->cur], nullptr, nullptr, nullptr, dr, dj, b->st));
+        hr.resize(m * 3); hj.resize(m * 9);
+        STBA_TRY(download(hr.data(), dr, m * 3, b->st));
+        STBA_TRY(download(hj.data(), dj, m * 9, b->st));
+    }
+    if (cost) {
+        STBA_TRY(dcost.alloc(1));
+        STBA_TRY(launch_landmark_prior_cost(b->landmark_prior_args(), b->pts[b->cur], b->lprior.cost_part, dcost, b->st));
+        STBA_TRY(download(&c2, dcost, 1, b->st));
+    }
+    STBA_HIP(hipStreamSynchronize(b->st));
+    if (cost) *cost = 0.5 * c2;
+    for (size_t p = 0; p < m && (r || J); ++p) {
+        const size_t k = (size_t)b->lprior.order[p];
+        if (r) memcpy(r + k * 3, &hr[p * 3], 3 * sizeof(double));
+        if (J) memcpy(J + k * 9, &hj[p * 9], 9 * sizeof(double));
+    }
     return STBA_OK;
 }
 

@@ -1,5 +1,5 @@
-// ba_features.hpp -- which features of the bundle-adjustment engine go together: ONE table of every refusal (DESIGN.md 7l prints it
-// as a matrix).  A row says: the C function `asker`, called to SET its feature on an engine that holds `held`, returns `code` and
+// ba_features.hpp -- which features of the bundle-adjustment engine go together: the tables of every refusal (DESIGN.md 7l prints them
+// as one matrix; why there are two: see BA_REFUSALS_MORE).  A row says: the C function `asker`, called to SET its feature on an engine that holds `held`, returns `code` and
 // leaves "<asker>: <text>" in stba_last_error().  Everything not in the table is supported.
 // Host only: the standard library and include/stba.h, nothing of HIP, so that a plain C++ compiler builds it and
 // tests/test_ba_factor_input_cpu.py checks it without a device (tests/cpp/ba_factor_input_driver.cpp).
@@ -21,16 +21,20 @@ enum BaFeature : unsigned {
     LOSS = 1u << 5,                 // stba_ba_set_loss
     INFORMATION = 1u << 6,          // stba_ba_set_information / _sqrt_information
     POSE_PRIORS = 1u << 7,          // stba_ba_set_pose_priors
-    RELATIVE_POSES = 1u << 8        // stba_ba_set_relative_poses
+    RELATIVE_POSES = 1u << 8,       // stba_ba_set_relative_poses
+    // behind the nine features BA_FEATURE_COUNT counts (see BA_REFUSALS_MORE below)
+    LANDMARK_PRIORS = 1u << 9       // stba_ba_set_landmark_priors
 };
 constexpr int BA_FEATURE_COUNT = 9;
+constexpr int BA_FEATURE_COUNT_ALL = 10;
 
 // the features an engine holds, from plain values (the engine passes its members; a test passes what it likes)
 inline unsigned ba_held_features(bool iterative, bool dogleg, bool inner_on, bool host_linearizer, bool allreduce, bool loss,
-                                 bool information, int n_priors, int n_relative_poses) {
+                                 bool information, int n_priors, int n_relative_poses, int n_landmark_priors = 0) {
     return (iterative ? ITERATIVE_SCHUR : 0u) | (dogleg ? DOGLEG : 0u) | (inner_on ? INNER_ITERATIONS : 0u) |
            (host_linearizer ? HOST_LINEARIZER : 0u) | (allreduce ? ALLREDUCE : 0u) | (loss ? LOSS : 0u) |
-           (information ? INFORMATION : 0u) | (n_priors ? POSE_PRIORS : 0u) | (n_relative_poses ? RELATIVE_POSES : 0u);
+           (information ? INFORMATION : 0u) | (n_priors ? POSE_PRIORS : 0u) | (n_relative_poses ? RELATIVE_POSES : 0u) |
+           (n_landmark_priors ? LANDMARK_PRIORS : 0u);
 }
 
 struct BaRefusal {
@@ -100,17 +104,33 @@ inline constexpr BaRefusal BA_REFUSALS[] = {
     {"stba_ba_inner_sweep", RELATIVE_POSES, STBA_INV, "this engine has relative-pose factors (inner iterations with relative-pose factors are not supported)"},
     {"stba_ba_solve", DOGLEG | INNER_ITERATIONS, STBA_INV, "inner iterations are not supported with DOGLEG"},
 };
+
+// The SECOND table: the rows of features that came after the first was pinned.  BA_REFUSALS, BA_FEATURE_COUNT and the answers for
+// every mask of the first nine bits are held row for row by tests/golden/ba_refusals.json, so a later feature brings its rows here
+// and gets a bit above them; ba_conflict searches this table behind the first (no asker has rows in both that could both apply to
+// a mask of the first nine bits: every row here asks for a bit above them, or belongs to an asker the first table does not know).
+// Landmark priors are block-diagonal in the landmark and go with ITERATIVE_SCHUR, DOGLEG, losses, weights, pose
+// priors and relative poses; what they do not go with solves from, or sums over, the observation records alone.
+inline constexpr BaRefusal BA_REFUSALS_MORE[] = {
+    {"stba_ba_set_landmark_priors", INNER_ITERATIONS, STBA_INV, "this engine has inner iterations (the per-landmark sweep solves from the observation records; landmark priors are not supported)"},
+    {"stba_ba_set_landmark_priors", HOST_LINEARIZER, STBA_INV, "this engine has a host lineariser (priors need device residuals; not supported together)"},
+    {"stba_ba_set_landmark_priors", ALLREDUCE, STBA_INV, "this engine has an all-reduce hook, and landmark priors run on one rank only"},
+    {"stba_ba_set_inner_iterations", LANDMARK_PRIORS, STBA_INV, "this engine has landmark priors (inner iterations with landmark priors are not supported)"},
+    {"stba_ba_inner_sweep", LANDMARK_PRIORS, STBA_INV, "this engine has landmark priors (inner iterations with landmark priors are not supported)"},
+    {"stba_ba_set_host_linearizer", LANDMARK_PRIORS, STBA_INV, "this engine has landmark priors (priors need device residuals; not supported together)"},
+    {"stba_ba_set_allreduce", LANDMARK_PRIORS, STBA_INV, "this engine has landmark priors, which run on one rank only"},
+};
 #undef STBA_INV
 
 // the first row of `asker` that an engine holding `held` meets: its code, and "<asker>: <text>" in *why; 0 if none.  `sets` is false
 // for a call that clears the asker's feature (only the when_clearing rows apply)
 inline int ba_conflict(const char* asker, unsigned held, std::string* why, bool sets = true) {
     const std::string who(asker);
-    for (const BaRefusal& r : BA_REFUSALS) {
-        if (who != r.asker || (held & r.held) != r.held || !(sets || r.when_clearing)) continue;
-        if (why) *why = who + ": " + r.text;
-        return r.code;
-    }
+    const auto applies = [&](const BaRefusal& r) { return who == r.asker && (held & r.held) == r.held && (sets || r.when_clearing); };
+    for (const BaRefusal& r : BA_REFUSALS)
+        if (applies(r)) { if (why) *why = who + ": " + r.text; return r.code; }
+    for (const BaRefusal& r : BA_REFUSALS_MORE)
+        if (applies(r)) { if (why) *why = who + ": " + r.text; return r.code; }
     return 0;
 }
 

@@ -497,7 +497,7 @@ int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* oma
 // for 80 MB.)
 // (records per pass = PB_TRIPS x PB_THREADS: 2 x 128 measured against 3 x 128 -- 18.5 KB of LDS instead of 27.7, eight
 // workgroups per CU instead of five: landmark blocks 19.4 -> 17.3 us; 24 landmarks per workgroup: the same, more partials)
-constexpr int PB_LM = 32, PB_THREADS = 128, PB_TRIPS = 2, PB_CHUNK = PB_TRIPS * PB_THREADS, PB_LD = PB_CHUNK + 1;
+constexpr int PB_LM = POINT_BLOCK_LANDMARKS, PB_THREADS = 128, PB_TRIPS = 2, PB_CHUNK = PB_TRIPS * PB_THREADS, PB_LD = PB_CHUNK + 1;
 __global__ __launch_bounds__(PB_THREADS) void ba_point_blocks_kernel(int n_pts, const int* __restrict__ pt_start,
                                                                      const double* __restrict__ J8,
                                                                      const unsigned char* __restrict__ omask,
@@ -1568,6 +1568,8 @@ __global__ __launch_bounds__(PB_THREADS) void ba_backsub_kernel(int n_pts, const
             const double2 rl = up.r_model[l];
             mv -= rl.x * u0 + rl.y * u1 + 0.5 * (u0 * u0 + u1 * u1);
         }
+        // (landmark priors: their rows of the same sum, one landmark per lane)
+        if (up.lp.start && t < nl) mv += lp_model_rows(up.lp, j0 + t, dsh + 3 * t);
         st[2] = mv;
     }
     if (up.pts_new) {

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "schur_plan.hpp"      // CAM_CHUNK and the SCHUR_* constants that the host-side plan shares with the kernels
+#include "ba_landmark_prior.hpp"   // LandmarkPriorRows: the priors' rows of the two model terms summed from the records
 
 namespace stba {
 
@@ -86,7 +87,8 @@ int launch_sum_partials(const double* partial, int n, int stride, int K, double*
 // (Jc12: the camera blocks of the general form -- host-linearised factors, robust losses -- or null)
 int launch_expand_jacobian(int n_obs, const double* J8, const unsigned char* omask, double* Jc, double* Jp, hipStream_t st,
                            const double* Jc12 = nullptr);
-// (gpmax_partial: optional, one max |gp| per workgroup of 256 landmarks, finished by launch_linear_finish)
+// (gpmax_partial: optional, one max |gp| per workgroup of POINT_BLOCK_LANDMARKS landmarks, finished by launch_linear_finish)
+constexpr int POINT_BLOCK_LANDMARKS = 32;
 int point_blocks_grid(int n_pts);      // workgroups of the landmark-block kernel = entries of its gpmax partial array
 int launch_point_blocks(int n_pts, const int* pt_start, const double* J8, const unsigned char* omask, const double2* r,
                         double* Hpp6, double* gp, double* gpmax_partial, hipStream_t st);
@@ -177,6 +179,8 @@ struct BacksubUpdate {
     // landmark of every record) in place of the exact-step term -1/2 g d + 1/2 d^T D d, which only holds for an exact solve
     const int* skip = nullptr;
     const double2* r_model = nullptr; const int* obs_pt = nullptr;
+    // landmark priors: with r_model, their rows of that sum, -(W d_j)^T (r' + W d_j / 2) per prior; lp.start null: none
+    LandmarkPriorRows lp{};
 };
 int backsub_grid(int n_pts);
 int backsub_cam_grid(int n_cams);

@@ -120,6 +120,8 @@ __global__ __launch_bounds__(DL_THREADS) void ba_dogleg_terms_kernel(DoglegArgs 
         v[4] += n0 * n0 + n1 * n1;
         v[5] += e0 * n0 + e1 * n1;
     }
+    // (landmark priors: their rows W su_j, W dx_j of the same three sums, one landmark per lane)
+    if (a.lp.start && t < nl) lp_dogleg_rows(a.lp, j0 + t, su_p + 3 * t, dx_p + 3 * t, &v[3], &v[4], &v[5]);
     dl_block_sum6(v, a.partial + (size_t)blockIdx.x * DL_PART);
 }
 

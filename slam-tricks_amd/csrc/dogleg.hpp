@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "dogleg_select.hpp"
+#include "ba_landmark_prior.hpp"
 
 namespace stba {
 
@@ -21,6 +22,7 @@ struct DoglegArgs {
     double* uc; double* up;                                                 // out: s .* u, u = gamma ./ d  [6 n_cams] | [3 n_pts]
     double* partial;                                                        // dogleg_partial_doubles(n_cams, n_pts)
     double* scalars;                                                        // out: DoglegScalars (6 doubles)
+    LandmarkPriorRows lp{};                                                 // landmark priors: their rows of the three J^ sums; start null: none
 };
 size_t dogleg_partial_doubles(int n_cams, int n_pts);
 // once per linearisation, behind the Gauss-Newton back-substitution: u, and the six scalars (fixed-order sums, no atomics)

@@ -124,6 +124,8 @@ static int ba_linearize_dispatch(stba_ba* b, int which, bool with_jac) {
     if (b->prior.n) STBA_TRY(launch_prior_cost(b->prior_args(), b->cams[which], b->cost_partial + b->lin_grid, b->st));
     // relative-pose factors: theirs into the next slot
     if (b->btw.n) STBA_TRY(launch_between_cost(b->between_args(), b->cams[which], b->cost_partial + b->lin_grid + (b->prior.n ? 1 : 0), b->st));
+    // landmark priors: theirs into the last slot
+    if (b->lprior.n) STBA_TRY(launch_landmark_prior_cost(b->landmark_prior_args(), b->pts[which], b->lprior.cost_part, b->cost_partial + b->n_cost() - 1, b->st));
     return STBA_OK;
 }
 
@@ -158,8 +160,14 @@ static int ba_cost_only(stba_ba* b, int which, double* cost2_dev) {
 // landmark blocks Hpp, gp.  The CAMERA blocks Hcc, gc are made by the Schur kernel on the way (ba_build_reduced: the
 // workgroup of a camera row has that camera's Jacobian records in its caches anyway); only the stage entry point
 // stba_ba_normal_blocks, which hands them out without building the reduced system, runs the camera-side kernel.
+// Landmark priors: sum W^T W into Hpp6 and sum W^T r' into gp right behind the kernel that has just written both, at the parameters
+// the Jacobian records were made at -- every reader downstream (damping and scale, the inverses, both Schur forms, the back-
+// substitution, the covariance, the implicit build) sees the sum -- and that kernel's max |gp| partials made again from it (one
+// launch; none without priors)
 static int ba_normal_blocks(stba_ba* b) {
-    return launch_point_blocks(b->np, b->pt_start, b->J8, b->omask, b->r, b->Hpp6, b->gp, b->upd_partial_p, b->st);
+    STBA_TRY(launch_point_blocks(b->np, b->pt_start, b->J8, b->omask, b->r, b->Hpp6, b->gp, b->upd_partial_p, b->st));
+    if (!b->lprior.n) return STBA_OK;
+    return launch_landmark_prior_blocks(b->landmark_prior_args(), b->pts[b->lin_which], b->Hpp6, b->gp, b->upd_partial_p, nullptr, nullptr, b->st);
 }
 // residuals + Jacobians of the LM loop: the cost partial sums stay in cost_partial and are added up by
 // ba_fill_scalar_slots behind the landmark blocks (one launch less than ba_linearize)
@@ -391,7 +399,8 @@ __global__ void export_trial_kernel(const double* __restrict__ trial, const int*
 static int ba_backsub_trial(stba_ba* b) {
     BacksubUpdate up{b->pts[b->cur], b->pt_fixed, b->dp, b->pts[b->cur ^ 1], b->upd_partial_p,
                      b->nc, b->cams[b->cur], b->cam_fixed, b->ex_gc(), b->dc, b->cams[b->cur ^ 1], b->upd_partial_c};
-    if (b->iterative) { up.r_model = b->r; up.obs_pt = b->obs_pt; }      // (an inexact step: m = -(J d)^T (r + J d / 2))
+    // (an inexact step: m = -(J d)^T (r + J d / 2), the landmark priors' rows included)
+    if (b->iterative) { up.r_model = b->r; up.obs_pt = b->obs_pt; up.lp = b->landmark_prior_rows(); }
     return launch_backsub(b->np, b->pt_start, b->obs_cam, b->J8, b->omask, b->Hinv6, b->gp, b->dxc, b->dxp, b->st, &up, ba_general_jc(b));
 }
 
@@ -1034,6 +1043,7 @@ static int ba_dogleg_gauss_newton(stba_ba* b, const Damping& dm) {
     a.dmin = dm.dmin; a.dmax = dm.dmax;
     a.dxc = b->dxc; a.dxp = b->dxp; a.uc = b->dl_uc; a.up = b->dl_up;
     a.partial = b->dl_part; a.scalars = b->dl_sc;
+    a.lp = b->landmark_prior_rows();
     return launch_dogleg_terms(a, b->st);
 }
 
@@ -1302,7 +1312,7 @@ static int ba_fill(stba_ba* b, int n_cams, int n_pts, int n_obs, const double* c
     STBA_TRY(b->dc.alloc(nc * 6)); STBA_TRY(b->scale_c.alloc(nc * 6));
     STBA_TRY(b->Sbuf.alloc(b->sbuf_count()));
     STBA_TRY(b->dxc.alloc((size_t)b->lda)); STBA_TRY(b->dxp.alloc(np * 3));
-    STBA_TRY(b->cost_partial.alloc((size_t)b->lin_grid + 2));     // (+ 2: the pose priors' slot and the relative-pose factors', see n_cost)
+    STBA_TRY(b->cost_partial.alloc((size_t)b->lin_grid + 3));     // (+ 3: the pose priors' slot, the relative-pose factors' and the landmark priors', see n_cost)
     STBA_TRY(b->upd_partial_c.alloc((size_t)backsub_cam_grid(n_cams) * 4));    // (>= (n_cams + 255) / 256 blocks of 4)
     STBA_TRY(b->upd_partial_p.alloc((size_t)(point_blocks_grid(n_pts) + 1) * 4));    // (>= (n_pts + 255) / 256 + 1 blocks of 4)
     STBA_TRY(b->trial.alloc((size_t)TS_BLOCK)); STBA_TRY(b->flag.alloc(1));
