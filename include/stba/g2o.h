@@ -252,7 +252,7 @@ public:
         }
         if (any_information && stba_ba_set_information(ba, info.data()) != STBA_OK) {
             // (an Omega that is not positive definite or not finite: the engine's message names the row as "observation <index>:", and
-            // the observation's index is the edge's; ba_set_weights in stba_engine.hip carries a note that this text is read here)
+            // the observation's index is the edge's; ba_set_weights in ba_factors.hip carries a note that this text is read here)
             const std::string why = stba_last_error();
             const size_t at = why.find("observation ");
             _message = (at == std::string::npos ? std::string() : "edge " + std::to_string(std::atoi(why.c_str() + at + 12)) + ": ") + why;

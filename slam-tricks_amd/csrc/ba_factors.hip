@@ -37,16 +37,6 @@ int se3_rows_check(const std::string& who, const char* row, const char* what, si
     return STBA_OK;
 }
 
-// host data into a new device array of its size (the copy is enqueued; the caller synchronises)
-template <class T>
-int to_device(const std::string& who, DevBuf<T>& dst, const T* src, size_t count, hipStream_t st) {
-    STBA_TRY(dst.alloc(count));
-    if (upload(dst, src, count, st) != STBA_OK) return fail(STBA_ERR_HIP, who + ": upload failed");
-    return STBA_OK;
-}
-template <class T>
-int to_device(const std::string& who, DevBuf<T>& dst, const std::vector<T>& src, hipStream_t st) { return to_device(who, dst, src.data(), src.size(), st); }
-
 }  // namespace
 
 extern "C" {
@@ -56,7 +46,7 @@ int stba_ba_set_host_linearizer(stba_ba* b, stba_ba_linearize_fn fn, void* user)
     STBA_TRY(ba_refuse(b, "stba_ba_set_host_linearizer", fn != nullptr));
     // (straight into the engine: nothing else is committed; clearing the callback keeps the buffer)
     STBA_TRY(jc12_reserve(b, ba_wants_general_form(fn != nullptr, b->loss.kind.get() != nullptr, b->winfo.get() != nullptr), b->Jc12));
-    b->hl_fn = fn; b->hl_user = user;
+    b->hl.fn = fn; b->hl.user = user;
     ba_invalidate(b);
     return STBA_OK;
 }

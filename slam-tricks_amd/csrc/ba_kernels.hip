@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256) void trial_finish_kernel(const double* __restr
     }
     __shared__ double hp[11];
     if (threadIdx.x < 8) {
-        // block layout (stba_engine.hip, TS_*): [cost2, step2, x2, model | timed out | the three camera sums]; entry 4 = 1.0 if the
+        // block layout (ba_engine.hpp, TS_*): [cost2, step2, x2, model | timed out | the three camera sums]; entry 4 = 1.0 if the
         // factorisation of this iteration timed out on this rank (CHOL_FLAG_TIMEOUT): it lies inside the prefix the ranks sum
         const int k = threadIdx.x;
         const double v = k < 4 ? res[k] : k == 4 ? ((flag[0] == CHOL_FLAG_TIMEOUT) ? 1.0 : 0.0) : res[k - 1];

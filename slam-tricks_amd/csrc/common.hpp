@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/stba.h"
 
@@ -117,6 +118,18 @@ inline int download(T* dst, const typename same_as<T>::type* src, size_t count, 
     STBA_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, st));
     return STBA_OK;
 }
+// host data into a new device array of its size (the copy is enqueued; the caller synchronises).  `who` begins the message
+// (hidden: not small enough to be inlined away, and no part of the library's dynamic symbols)
+#pragma GCC visibility push(hidden)
+template <class T>
+inline int to_device(const std::string& who, DevBuf<T>& dst, const T* src, size_t count, hipStream_t st) {
+    STBA_TRY(dst.alloc(count));
+    if (upload(dst, src, count, st) != STBA_OK) return fail(STBA_ERR_HIP, who + ": upload failed");
+    return STBA_OK;
+}
+template <class T>
+inline int to_device(const std::string& who, DevBuf<T>& dst, const std::vector<T>& src, hipStream_t st) { return to_device(who, dst, src.data(), src.size(), st); }
+#pragma GCC visibility pop
 
 // Experiment knobs (environment variables) exist only in builds with -DSTBA_DEBUG_KNOBS (STBA_DEBUG_KNOBS=1 in the
 // environment of slam-tricks_amd/build.py); the product library reads no environment variables for its schedules.

@@ -2,7 +2,7 @@
 // observations, the camera-side permutation and its chunks, the choice between the pair plan and the dense form of the Schur
 // complement, the block pattern of S, the cut of its camera rows into tasks, and every task's per-wave pair records.
 // Host only: the standard library and nothing of HIP, so that a plain C++ compiler builds it and tests/test_schur_plan_cpu.py
-// checks it without a device.  stba_engine.hip (ba_create) calls build_schur_plan and uploads what it returns; the kernels
+// checks it without a device.  stba_engine.hip (ba_fill) calls build_schur_plan and uploads what it returns; the kernels
 // that read the plan are in ba_kernels.hip.
 #pragma once
 #include <algorithm>

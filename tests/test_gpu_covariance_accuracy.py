@@ -12,7 +12,7 @@ the measure is the scaled one, max |d_i d_j (X - X_ref)_ij| / max |d_i d_j (X_re
   BAEngine.covariance   camera blocks only (the landmark blocks have their 50-digit test, test_gpu_schur_elim.py).  The reference
                      inverts the free part of the engine's OWN zero-damped S, read through reduced_system(0, 0) and symmetrised
                      from its lower triangle: stba_ba_covariance_compute builds S through the same launches (ba_cov_build in
-                     stba_engine.hip: ba_linearize, the landmark blocks, ba_build_reduced with explicit zero damping --
+                     ba_linear.hip: ba_linearize, the landmark blocks, ba_build_reduced with explicit zero damping --
                      evaluate / normal_blocks / reduced_system run exactly these; the camera-side kernel normal_blocks adds writes
                      Hcc, which the Schur kernel writes again), in the pair plan, whose S is bitwise reproducible.  Comparing with
                      the device's S keeps the cancellation in U - E V^-1 E^T out of the bound.

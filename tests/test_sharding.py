@@ -382,7 +382,7 @@ def test_two_processes_two_shards_product_engine(scenes):
 def test_a_rank_whose_factorisation_gives_up_takes_the_others_along(scenes):
     """several ranks must hold bit-identical camera blocks (include/stba.h).  The persistent factorisation and the stage kernels it
     falls back to differ in the last bits, so when ONE rank's gives up (a time-out: its device is shared) EVERY rank must go through
-    the stage kernels for as long as that rank does (stage_cooldown in stba_engine.hip, round 5: the rehearsal of four ranks on one device showed
+    the stage kernels for as long as that rank does (CrossRankSum::stage_cooldown in ba_engine.hpp, set in ba_solve.hip, round 5: the rehearsal of four ranks on one device showed
     ranks 5e-14 apart).  Here rank 1 is given a time-out of 1 us at a size the persistent program takes (200 cameras)."""
     import torch.multiprocessing as mp
     st = importlib.import_module("slam-tricks_amd")
