@@ -558,6 +558,41 @@ enum {
 int stba_pg_set_loss(stba_pg* pg, const int* kind, const double* a, const double* b, const double* scale);
 int stba_pg_has_loss(const stba_pg* pg, int* has);
 
+/* --- pose-graph node pose priors ------------------------------------------------------------ */
+/* A prior k names a node n_k, a prior pose Zh_k -- [qx, qy, qz, qw, tx, ty, tz] like the engine's poses -- and a 6 x 6 square-root
+ * information W_k (row-major, in the tangent order [rho(3), theta(3)] of the engine's residuals):
+ *     r_k = log(Zh_k^-1 T_n)      J_k = d r_k / d delta_n = Jr^-1(r_k)      cost += 1/2 |W_k r_k|^2
+ * -- the relative-pose edge whose other end is a constant node at the identity: the same log (the short way round), the same
+ * Jr^-1 = I + ad/2 + ad^2/12.  A GPS / RTK position (zero theta rows of W: a position-only prior), a surveyed start pose, a
+ * map-localisation fix, the prior a marginalised window leaves on its boundary node; the gauge of a graph that fixes no node.  Any
+ * number of priors, several on one node.  A constant node's prior has J = 0 and adds to the cost only.  Priors carry no robust loss;
+ * edge weights and edge losses combine with them freely.
+ *   stba_pg_set_priors   node[n], pose[n*7], and at most ONE of information[n*36] (symmetric positive definite; the lower triangle is
+ *                      factored on the host, Omega = L L^T, W = L^T, in double-double arithmetic, as stba_ba_set_pose_priors does;
+ *                      else STBA_ERR_NOT_POSITIVE_DEFINITE) and sqrt_information[n*36] (any finite W, rank-deficient included).
+ *                      Both NULL: the identity.  Quaternions are normalised on the host (one that is unit to 8 eps keeps its bits).
+ *                      n = 0 clears the priors: the engine then enqueues exactly what one that never had any enqueues.
+ *                      STBA_ERR_INVALID_ARGUMENT, stba_last_error() naming the smallest such prior, nothing changed: a node index
+ *                      out of range, an entry that is not finite, a zero quaternion; also both weight arrays given.
+ *   stba_pg_prior_count  *n = the number of priors held.
+ *   stba_pg_evaluate_priors   at the current poses: cost = 1/2 sum |W r|^2 of the priors alone, r[n*6] = W_k r_k, J[n*36] = W_k J_k
+ *                      (6 x 6 row-major), in the caller's order; any may be NULL.
+ *   stba_pg_prior_kernel_geometry   DIAGNOSTIC, NOT A STABLE INTERFACE (the tests derive their prior sets from it): priors per
+ *                      workgroup of the per-prior kernel, prior-bearing nodes per workgroup of the per-node kernel.
+ * With priors, stba_pg_evaluate's cost, the LM summary and trace, the gradient norm the loop stops on and
+ * stba_pg_covariance[_columns] are those of the SUM, edges plus priors (r, Ji, Jj of stba_pg_evaluate stay per edge).  For the
+ * covariance a connected component passes the gauge check if it holds a constant node OR a node with a prior that is not constant;
+ * the check is structural -- a component held only by rank-deficient priors (one position-only prior leaves the rotation about that
+ * point free) passes it, and the singular J^T J is refused by the conjugate gradient's own reports (STBA_ERR_NOT_POSITIVE_DEFINITE).
+ * stba_pg_gauge_check itself keeps its meaning: it knows no priors.  A setter that succeeds invalidates the current linearisation.
+ * LIMIT, refused with STBA_ERR_INVALID_ARGUMENT, the state untouched, in both orders of the two calls: an all-reduce hook or
+ * communicator (several ranks); a call that clears either is never refused.  STBA_VERSION is unchanged: test for the symbols. */
+int stba_pg_set_priors(stba_pg* pg, int n, const int* node, const double* pose /*[n*7]*/,
+                       const double* information /*[n*36] or NULL*/, const double* sqrt_information /*[n*36] or NULL*/);
+int stba_pg_prior_count(const stba_pg* pg, int* n);
+int stba_pg_evaluate_priors(stba_pg* pg, double* cost, double* r /*[n*6]*/, double* J /*[n*36], 6x6 row-major*/);
+int stba_pg_prior_kernel_geometry(const stba_pg* pg, int* priors_per_workgroup, int* nodes_per_workgroup);
+
 /* --- pose-graph covariance ---------------------------------------------------------------- */
 /* C = (J^T J)^-1 of the undamped, unscaled problem at the engine's current poses, in the engine's tangent coordinates (per node
  * [rho, theta] of T <- T exp(delta)); not multiplied by a residual variance (the definition of stba_ba_covariance_compute); constant

@@ -129,7 +129,7 @@ enum Ownership { DO_NOT_TAKE_OWNERSHIP, TAKE_OWNERSHIP };
 constexpr int DYNAMIC = -1;
 
 // The reference only passes nullptr (test_ceres.h:120, solver.hpp:267).  Robust losses are implemented for POSE GRAPHS only: a Problem
-// that takes the "gpu-pg" route (every residual block a RelativePoseFactor) and whose losses are all the built-in classes below
+// that takes the "gpu-pg" route (every residual block a RelativePoseFactor, or a NodePosePriorFactor without a loss) and whose losses are all the built-in classes below
 // (recognised by dynamic_cast) is solved with them -- the per-edge table goes to stba_pg_set_loss (include/stba.h), which applies Ceres'
 // corrector inside the device's linearisation kernel; Covariance on such a problem returns (J'^T J')^-1 as Ceres does.  Everything
 // else that holds a non-null LossFunction -- a bare LossFunction or a user subclass (this base class has no Evaluate to call), any
@@ -926,6 +926,41 @@ private:
     bool has_w_ = false;
 };
 
+// A node pose prior of the pose graph (stba_pg_set_priors): r = W log(Z^-1 T) on ONE pose block with the SE3RightPlus chart
+// -- RelativePoseFactor with its first pose at the identity, evaluated by that factor's own functor.  measurement: the prior pose Z
+// (qx qy qz qw tx ty tz); sqrt_information: W, 6 x 6 row-major in the tangent order [rho, theta] (null: the identity; zero theta
+// rows: a position-only prior, GPS).  A Problem of RelativePoseFactor blocks and such priors (added WITHOUT a LossFunction) still runs
+// on the device pose-graph engine ("gpu-pg"); Evaluate below is what the generic host path uses.
+class NodePosePriorFactor : public SizedCostFunction<6, 7> {
+public:
+    explicit NodePosePriorFactor(const double* measurement, const double* sqrt_information = nullptr)
+        : edge_(sqrt_information ? RelativePoseFactor(measurement, sqrt_information) : RelativePoseFactor(measurement)) {}
+    static NodePosePriorFactor* Create(const double* measurement, const double* sqrt_information = nullptr) {
+        return new NodePosePriorFactor(measurement, sqrt_information);
+    }
+    const double* measurement() const { return edge_.measurement(); }
+    const double* sqrt_information() const { return edge_.sqrt_information(); }      // nullptr: made without one (identity)
+    template <typename T>
+    bool operator()(const T* Tn, T* r) const {
+        const T I7[7] = {T(0.0), T(0.0), T(0.0), T(1.0), T(0.0), T(0.0), T(0.0)};
+        return edge_(I7, Tn, r);
+    }
+    bool Evaluate(double const* const* p, double* residuals, double** jacobians) const override {
+        if (!jacobians || !jacobians[0]) return (*this)(p[0], residuals);
+        using J7 = Jet<double, 7>;
+        J7 x[7], out[6];
+        for (int k = 0; k < 7; ++k) x[k] = J7(p[0][k], k);
+        (*this)(x, out);
+        for (int r = 0; r < 6; ++r) {
+            residuals[r] = out[r].a;
+            for (int k = 0; k < 7; ++k) jacobians[0][r * 7 + k] = out[r].v[k];
+        }
+        return true;
+    }
+private:
+    RelativePoseFactor edge_;
+};
+
 // ------------------------------------------------------------------------------------------
 // Problem
 // ------------------------------------------------------------------------------------------
@@ -1579,35 +1614,69 @@ inline bool UsesQuaternionRightPlus(const LocalParameterization* lp) {
 }
 
 // ---- path 3's layout: a pose graph ------------------------------------------------------------
-// every residual block a RelativePoseFactor on two distinct 7-double blocks with the SE3RightPlus chart and no bounds.  Nodes are
-// numbered in the order the residual blocks first name them.
+// every residual block a RelativePoseFactor on two distinct 7-double blocks, or a NodePosePriorFactor without a LossFunction on one,
+// every block with the SE3RightPlus chart and no bounds, and at least one edge.  Nodes are numbered in the order the residual blocks
+// first name them.
 struct PoseGraphLayout : LossTable {       // (the losses: per edge)
     std::map<int, int> node_of;            // parameter block index -> node
     std::vector<int> node_block, ei, ej;   // node -> parameter block index; the edges
     std::vector<double> meas, poses;       // [m][7], [n][7] (the blocks' current values)
     std::vector<unsigned char> fixed;      // [n]
     std::vector<double> sqrt_info;         // [m][36] the factors' W (SetSqrtInfoRow)
+    // NodePosePriorFactor blocks, set aside: node, pose [7], W [36] as stba_pg_set_priors takes them, in the order of the
+    // residual blocks.  edge_res: edge -> residual block index; EMPTY when the problem has no prior block -- then edge e IS residual
+    // block e, as it always was
+    std::vector<int> prior_node, edge_res;
+    std::vector<double> prior_pose, prior_w;
 };
 inline bool DetectPoseGraph(Problem* p, PoseGraphLayout* L) {
-    const size_t m = p->residuals().size();
+    const size_t nr = p->residuals().size();
+    if (nr == 0) return false;
+    // (a prior with a LossFunction, or a problem of priors only, is no pose graph of this engine)
+    size_t m = 0;
+    for (size_t k = 0; k < nr; ++k) {
+        const auto& r = p->residuals()[k];
+        if (r.blocks.size() == 1 && dynamic_cast<NodePosePriorFactor*>(r.cost)) { if (r.loss) return false; }
+        else ++m;
+    }
     if (m == 0) return false;
-    for (size_t e = 0; e < m; ++e) {
-        const auto& r = p->residuals()[e];
+    const bool has_priors = m != nr;
+    auto node_of_block = [&](int block, int* node) {
+        const auto& b = p->blocks()[block];
+        if (b.size != 7 || !b.local || !dynamic_cast<SE3RightPlus*>(b.local) || !b.lower.empty()) return false;
+        auto it = L->node_of.find(block);
+        if (it == L->node_of.end()) { *node = (int)L->node_block.size(); L->node_of[block] = *node; L->node_block.push_back(block); }
+        else *node = it->second;
+        return true;
+    };
+    size_t e = 0;
+    for (size_t k = 0; k < nr; ++k) {
+        const auto& r = p->residuals()[k];
+        if (has_priors && r.blocks.size() == 1) {
+            if (auto* pf = dynamic_cast<NodePosePriorFactor*>(r.cost)) {
+                int node;
+                if (!node_of_block(r.blocks[0], &node)) return false;
+                L->prior_node.push_back(node);
+                L->prior_pose.insert(L->prior_pose.end(), pf->measurement(), pf->measurement() + 7);
+                const size_t at = L->prior_w.size();
+                L->prior_w.resize(at + 36, 0.0);
+                if (pf->sqrt_information()) std::memcpy(&L->prior_w[at], pf->sqrt_information(), 36 * sizeof(double));
+                else for (int a = 0; a < 6; ++a) L->prior_w[at + (size_t)a * 7] = 1.0;
+                continue;
+            }
+        }
         auto* f = dynamic_cast<RelativePoseFactor*>(r.cost);
         if (!f || r.blocks.size() != 2 || r.blocks[0] == r.blocks[1]) return false;
         int ends[2];
-        for (int k = 0; k < 2; ++k) {
-            const auto& b = p->blocks()[r.blocks[k]];
-            if (b.size != 7 || !b.local || !dynamic_cast<SE3RightPlus*>(b.local) || !b.lower.empty()) return false;
-            auto it = L->node_of.find(r.blocks[k]);
-            if (it == L->node_of.end()) { ends[k] = (int)L->node_block.size(); L->node_of[r.blocks[k]] = ends[k]; L->node_block.push_back(r.blocks[k]); }
-            else ends[k] = it->second;
-        }
+        for (int q = 0; q < 2; ++q)
+            if (!node_of_block(r.blocks[q], &ends[q])) return false;
         L->ei.push_back(ends[0]); L->ej.push_back(ends[1]);
         L->meas.insert(L->meas.end(), f->measurement(), f->measurement() + 7);
         if (f->sqrt_information()) SetSqrtInfoRow(&L->sqrt_info, m, 6, e, f->sqrt_information());
+        if (has_priors) L->edge_res.push_back((int)k);
+        ++e;
     }
-    FillLossTable(*p, std::vector<int>(), m, L);
+    FillLossTable(*p, L->edge_res, m, L);
     const int n = (int)L->node_block.size();
     L->poses.assign((size_t)n * 7, 0.0);
     L->fixed.assign((size_t)n, 0);
@@ -2169,6 +2238,8 @@ inline const char* CreatePg(const PoseGraphLayout& L, bool losses, PgEngine* e) 
     if (!L.sqrt_info.empty() && stba_pg_set_sqrt_information(e->h, L.sqrt_info.data()) != STBA_OK) return "stba_pg_set_sqrt_information";
     if (losses && !L.loss_kind.empty() && stba_pg_set_loss(e->h, L.loss_kind.data(), L.loss_a.data(), L.loss_b.data(), L.loss_scale.data()) != STBA_OK)
         return "stba_pg_set_loss";
+    if (!L.prior_node.empty() && stba_pg_set_priors(e->h, (int)L.prior_node.size(), L.prior_node.data(), L.prior_pose.data(), nullptr, L.prior_w.data()) != STBA_OK)
+        return "stba_pg_set_priors";
     return nullptr;
 }
 inline void SolvePoseGraph(const Solver::Options& o, Problem* p, PoseGraphLayout& L, Solver::Summary* sum) {
@@ -2352,7 +2423,8 @@ inline void SolveDispatch(const Solver::Options& options, Problem* problem, Solv
     const double t_resolve = WallSeconds();
     summary->execution_path = RouteName(d.route);
     if (d.route == Route::PG) {
-        // a pose graph: every residual block a RelativePoseFactor between two 7-double pose blocks with the SE3 right-plus chart
+        // a pose graph: every residual block a RelativePoseFactor between two 7-double pose blocks with the SE3 right-plus chart, or a
+        // NodePosePriorFactor on one
         SolvePoseGraph(options, problem, r.pg, summary);
     } else if (d.route == Route::BA_HOSTJAC) {
         // BA-SHAPED, but not (or not to be taken for) the built-in factor: every residual block is {quaternion 4, position 3,
@@ -2416,7 +2488,8 @@ inline void Solve(const Solver::Options& options, Problem* problem, Solver::Summ
 //   * "gpu-ba": every residual block is the reprojection factor (built-in, or a user cost function recognised as it at the current
 //     point, as Solve recognises it) -> stba_ba_covariance_compute with device Jacobians;
 //   * "gpu-ba-hostjac": BA-shaped with another factor -> the same with the user's cost functions as the host lineariser;
-//   * "gpu-pg": a pose graph as Solve recognises it (every residual block a RelativePoseFactor on two SE3RightPlus blocks) ->
+//   * "gpu-pg": a pose graph as Solve recognises it (every residual block a RelativePoseFactor on two SE3RightPlus blocks, or a
+//     NodePosePriorFactor on one: a block with such a prior anchors its connected component like a constant block) ->
 //     stba_pg_covariance, a batched conjugate gradient on the device engine's matrix-free J^T J: any size the engine takes.  A
 //     requested pair is any two pose blocks of the graph; a connected component without a constant block makes J^T J singular and
 //     Compute return false (the message names the component), before any device work;
@@ -2549,7 +2622,9 @@ private:
         path_ = "gpu-pg";
         if (pairs.empty()) return true;
         // (the gauge check of stba_pg_covariance, here so that a graph it refuses never needs a device)
-        if (stba_pg_gauge_check(n, m, G.ei.data(), G.ej.data(), G.fixed.data()) != STBA_OK) return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
+        // (with NodePosePriorFactor blocks a node with a prior anchors its component too: the engine's own check knows them)
+        if (G.prior_node.empty() && stba_pg_gauge_check(n, m, G.ei.data(), G.ej.data(), G.fixed.data()) != STBA_OK)
+            return Fail(std::string("stba_pg_covariance: ") + stba_last_error());
         internal::PgEngine pg;
         // (apply_loss_function = false: (J^T J)^-1 of the uncorrected Jacobian, as in Ceres)
         if (const char* failed = internal::CreatePg(G, options_.apply_loss_function, &pg)) return Fail(std::string(failed) + ": " + stba_last_error());

@@ -85,6 +85,7 @@ EXPORTS = ["stba_status_string", "stba_last_error", "stba_version", "stba_device
            "stba_pg_covariance_default_options", "stba_pg_covariance", "stba_pg_covariance_columns", "stba_pg_gauge_check",
            "stba_pg_set_information", "stba_pg_set_sqrt_information", "stba_pg_has_information",
            "stba_pg_set_loss", "stba_pg_has_loss",
+           "stba_pg_set_priors", "stba_pg_prior_count", "stba_pg_evaluate_priors", "stba_pg_prior_kernel_geometry",
            "stba_ba_set_loss", "stba_ba_has_loss", "stba_ba_loss_kernel_geometry",
            "stba_ba_set_information", "stba_ba_set_sqrt_information", "stba_ba_has_information", "stba_ba_get_sqrt_information",
            "stba_ba_set_pose_priors", "stba_ba_pose_prior_count", "stba_ba_evaluate_pose_priors", "stba_ba_pose_prior_kernel_geometry",
@@ -881,9 +882,11 @@ def pg_loss_table(m, kind, a=None, b=None, scale=None, who="PGEngine", what="edg
 class PGEngine:
     """Device-resident pose graph (BASELINE config C4, build-defined)."""
 
-    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None, information=None, sqrt_information=None, loss=None):
+    def __init__(self, poses, edge_i, edge_j, meas, node_fixed=None, stream=None, information=None, sqrt_information=None, loss=None,
+                 priors=None):
         """information / sqrt_information: (m, 6, 6) per-edge weights (set_information / set_sqrt_information); at most one of them.
-        loss: a kind name ("huber" uses a = 1), a tuple (kind, a[, b[, scale]]) or a dict of set_loss's arguments"""
+        loss: a kind name ("huber" uses a = 1), a tuple (kind, a[, b[, scale]]) or a dict of set_loss's arguments.
+        priors: a dict of set_priors' arguments (nodes=, poses=, information= | sqrt_information=)"""
         self._h = C.c_void_p()
         if information is not None and sqrt_information is not None:
             raise ValueError("PGEngine: give information or sqrt_information, not both")
@@ -903,6 +906,64 @@ class PGEngine:
             self.set_information(weights)
         elif sqrt_information is not None:
             self.set_sqrt_information(weights)
+        if priors is not None:
+            try:
+                self.set_priors(**priors)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- node pose priors
+    def set_priors(self, nodes, poses=None, information=None, sqrt_information=None):
+        """soft constraints on node poses (stba_pg_set_priors): prior k pulls node nodes[k] towards poses[k] = [qx, qy, qz, qw, tx, ty,
+        tz] with cost 1/2 |W_k r_k|^2, r_k = log(Z_k^-1 T) in the tangent order [rho(3), theta(3)].  information: (n, 6, 6) symmetric
+        positive definite (W = L^T of its Cholesky factor) or sqrt_information: (n, 6, 6) any finite W (zero theta rows: a
+        position-only prior); a single (6, 6) is taken for every prior, an (n,) array of sigmas means I / sigma; neither: the
+        identity.  Several priors may name one node.  nodes empty (or None) clears the priors."""
+        if information is not None and sqrt_information is not None:
+            raise ValueError("PGEngine: give information or sqrt_information, not both")
+        c = np.ascontiguousarray([] if nodes is None else nodes, dtype=np.int32).reshape(-1)
+        n = len(c)
+        if n == 0:
+            _chk(lib().stba_pg_set_priors(self._h, 0, None, None, None, None), "stba_pg_set_priors")
+            return
+        ps = _f64(poses).reshape(-1, 7)
+        if len(ps) != n:
+            raise ValueError(f"PGEngine: {n} prior nodes but {len(ps)} prior poses")
+
+        def blocks(w, name, power):
+            if w is None:
+                return None
+            w = np.asarray(w, np.float64)
+            if w.shape == (n,):                           # sigmas: W = I / sigma, Omega = I / sigma^2
+                w = np.eye(6)[None, :, :] / (w ** power)[:, None, None]
+            if w.shape == (6, 6):
+                w = np.broadcast_to(w, (n, 6, 6))
+            if w.shape != (n, 6, 6):
+                raise ValueError(f"PGEngine: prior {name} must have shape (6, 6), ({n}, 6, 6) or ({n},), got {w.shape}")
+            return np.ascontiguousarray(w)
+        om, w = blocks(information, "information", 2), blocks(sqrt_information, "sqrt_information", 1)
+        _chk(lib().stba_pg_set_priors(self._h, n, _p(c), _p(ps), _p(om), _p(w)), "stba_pg_set_priors")
+
+    def prior_count(self):
+        n = C.c_int()
+        _chk(lib().stba_pg_prior_count(self._h, C.byref(n)), "stba_pg_prior_count")
+        return n.value
+
+    def evaluate_priors(self, jac=True):
+        """(cost, r [n, 6], J [n, 6, 6] | None) of the priors alone at the current poses: whitened, in the order they were set"""
+        n = self.prior_count()
+        cost = C.c_double()
+        r = np.zeros((n, 6))
+        J = np.zeros((n, 6, 6)) if jac else None
+        _chk(lib().stba_pg_evaluate_priors(self._h, C.byref(cost), _p(r), _p(J)), "stba_pg_evaluate_priors")
+        return cost.value, r, J
+
+    def prior_kernel_geometry(self):
+        """(priors per workgroup of the per-prior kernel, prior-bearing nodes per workgroup of the per-node kernel): a diagnostic"""
+        a, b = C.c_int(), C.c_int()
+        _chk(lib().stba_pg_prior_kernel_geometry(self._h, C.byref(a), C.byref(b)), "stba_pg_prior_kernel_geometry")
+        return a.value, b.value
 
     def _edge_blocks(self, a):
         a = _f64(a)

@@ -9,8 +9,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["dense_chol.hip", "ba_kernels.hip", "stba_engine.hip", "ba_linear.hip", "ba_allreduce.hip", "ba_solve.hip", "ba_stages.hip", "dense_engine.hip", "calib.hip", "ba_factors.hip", "pg_engine.hip", "pg_linearize.hip", "pg_coarse.hip", "pg_pcg.hip", "small_dense.hip", "two_view.hip", "covariance.hip", "pg_covariance.hip", "iterative_schur.hip", "dogleg.hip", "inner_iterations.hip", "ba_prior.hip", "ba_between.hip", "ba_landmark_prior.hip", "calib_io.cpp", "comm.cpp"]
-HEADERS = ["common.hpp", "lm_policy.hpp", "ba_kernels.hpp", "schur_plan.hpp", "chol_schedule.hpp", "small_linalg.hpp", "iterative_schur.hpp", "dogleg.hpp", "dogleg_select.hpp", "inner_iterations.hpp", "inner_policy.hpp", "pg_covariance.hpp", "robust_loss.hpp", "ba_prior.hpp", "ba_between.hpp", "ba_landmark_prior.hpp", "ba_features.hpp", "ba_factor_input.hpp", "ba_engine.hpp", "pg_plan.hpp", "pg_engine.hpp", "pg_device.hpp", "inner_plan.hpp", "dd6.hpp", os.path.join("..", "..", "include", "stba.h")]
+SOURCES = ["dense_chol.hip", "ba_kernels.hip", "stba_engine.hip", "ba_linear.hip", "ba_allreduce.hip", "ba_solve.hip", "ba_stages.hip", "dense_engine.hip", "calib.hip", "ba_factors.hip", "pg_engine.hip", "pg_linearize.hip", "pg_coarse.hip", "pg_pcg.hip", "pg_prior.hip", "small_dense.hip", "two_view.hip", "covariance.hip", "pg_covariance.hip", "iterative_schur.hip", "dogleg.hip", "inner_iterations.hip", "ba_prior.hip", "ba_between.hip", "ba_landmark_prior.hip", "calib_io.cpp", "comm.cpp"]
+HEADERS = ["common.hpp", "lm_policy.hpp", "ba_kernels.hpp", "schur_plan.hpp", "chol_schedule.hpp", "small_linalg.hpp", "iterative_schur.hpp", "dogleg.hpp", "dogleg_select.hpp", "inner_iterations.hpp", "inner_policy.hpp", "pg_covariance.hpp", "robust_loss.hpp", "ba_prior.hpp", "ba_between.hpp", "ba_landmark_prior.hpp", "ba_features.hpp", "ba_factor_input.hpp", "ba_engine.hpp", "pg_plan.hpp", "pg_engine.hpp", "pg_device.hpp", "pg_edge.hpp", "inner_plan.hpp", "dd6.hpp", os.path.join("..", "..", "include", "stba.h")]
 LIB = os.path.join(HERE, "libstba.so")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-result"]

@@ -12,7 +12,8 @@
 //              end_rem) and sums J_self^T (J_self p_self + J_other p_other) in that order.  Every edge is visited from both ends;
 //              no atomics, so the bits do not depend on arrival order.  The Jacobians are repacked edge-major ([m][72]: Ji | Jj)
 //              once per call, so that a wave fetches them as a few wide scalar loads instead of 72 lines of the engine's
-//              component-major layout.
+//              component-major layout.  A node that holds pose priors adds Hp_v p_v, Hp_v the summed J'^T J' of its priors (wave-uniform
+//              like the Jacobians); the preconditioner's diagonal blocks hold the priors already.
 //   PCG        K independent recurrences that share the three kernels of an iteration (product | update | direction): alpha, beta,
 //              |r|^2 are per column, reduced over the nodes by per-workgroup partial rows [workgroup][K] that every workgroup adds up
 //              in the same fixed order.  A column whose recurrence residual reaches the tolerance FREEZES (no more updates, p = 0),
@@ -102,6 +103,7 @@ __global__ __launch_bounds__(256) void pgc_block_inverse_kernel(int n, const dou
 // Q = H P and the partial rows of p^T q.  A wave per node (four nodes in turn), a lane per column.
 __global__ __launch_bounds__(PGC_NT) void pgc_product_kernel(int n, const int* __restrict__ node_start, const int* __restrict__ end_code,
                                                              const int* __restrict__ end_rem, const double* __restrict__ Jp,
+                                                             const int* __restrict__ node_slot, const double* __restrict__ Hp,
                                                              const double* __restrict__ P, double* __restrict__ Q,
                                                              double* __restrict__ part_pq, const PgcCtrl* __restrict__ ctrl, int obey_done) {
     if (obey_done && ctrl->done) return;
@@ -129,6 +131,16 @@ __global__ __launch_bounds__(PGC_NT) void pgc_product_kernel(int n, const int* _
             for (int k = 0; k < 6; ++k) {
                 double sk = 0.0;
                 for (int a = 0; a < 6; ++a) sk += Js[a * 6 + k] * te[a];
+                q[k] += sk;
+            }
+        }
+        // (node pose priors: the node's summed block, behind its edge ends; node_slot null: the engine holds none)
+        const int slot = node_slot ? node_slot[v] : -1;
+        if (slot >= 0) {
+            const double* __restrict__ H = Hp + (size_t)slot * 36;
+            for (int k = 0; k < 6; ++k) {
+                double sk = 0.0;
+                for (int a = 0; a < 6; ++a) sk += H[k * 6 + a] * ps[a];
                 q[k] += sk;
             }
         }
@@ -298,6 +310,16 @@ int pgc_options(const stba_pg_covariance_options* in, stba_pg_covariance_options
     return STBA_OK;
 }
 
+// every connected component holds a constant node, or one ANCHORED by a pose prior (a structural check: a component anchored only by
+// rank-deficient priors passes, and a singular H is then the conjugate gradient's to report)
+int pgc_gauge(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, const unsigned char* anchored) {
+    int size = 0, first = 0;
+    if (pg_gauge_fixed(n, m, ei, ej, fixed, &size, &first, anchored)) return STBA_OK;
+    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pose-graph covariance: a connected component of " + std::to_string(size) + " node" + (size == 1 ? "" : "s") +
+                                                    " (first node " + std::to_string(first) + ") contains no constant node" +
+                                                    (anchored ? " and no node with a pose prior" : "") + ": J^T J is singular (gauge freedom)");
+}
+
 int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt_in, double* out, stba_pg_covariance_summary* summary) {
     stba_pg_covariance_options opt;
     STBA_TRY(pgc_options(opt_in, &opt));
@@ -312,7 +334,7 @@ int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt
             return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_covariance: pair " + std::to_string(k) + " (" + std::to_string(rq.a[k]) + ", " + std::to_string(rq.b[k]) +
                                                        ") names a node out of range (" + std::to_string(n) + " nodes)");
     if (gr.several_ranks) return fail(STBA_ERR_STATE, "stba_pg_covariance: not available with an all-reduce hook or communicator set (one rank only)");
-    STBA_TRY(stba_pg_gauge_check(n, gr.m, gr.ei, gr.ej, gr.fixed));
+    STBA_TRY(pgc_gauge(n, gr.m, gr.ei, gr.ej, gr.fixed, gr.anchored));
     auto is_fixed = [&](int v) { return gr.fixed && gr.fixed[v]; };
     int n_free = 0;
     for (int v = 0; v < n; ++v) n_free += is_fixed(v) ? 0 : 1;
@@ -395,7 +417,7 @@ int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt
                 double prev = seq;
                 while (px[CX_DONE] == 0.0) {
                     for (int k = 0; k < chunk; ++k) {
-                        hipLaunchKernelGGL(pgc_product_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, dv.node_start, dv.end_code, dv.end_rem, ws.Jp, ws.P, ws.Q, part_pq, ws.ctrl, 1);
+                        hipLaunchKernelGGL(pgc_product_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, dv.node_start, dv.end_code, dv.end_rem, ws.Jp, dv.node_slot, dv.Hp, ws.P, ws.Q, part_pq, ws.ctrl, 1);
                         hipLaunchKernelGGL(pgc_update_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, slot, ws.ctrl, nb, part_pq, ws.Minv, ws.P, ws.Q, ws.X, ws.R, ws.Z, part_rz, part_rr);
                         direction(0);
                     }
@@ -411,7 +433,7 @@ int pgc_run(stba_pg* g, const Request& rq, const stba_pg_covariance_options* opt
                     return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, msg);
                 }
                 // ---- the true residual e - H x of every column; columns above the tolerance go on from it
-                hipLaunchKernelGGL(pgc_product_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, dv.node_start, dv.end_code, dv.end_rem, ws.Jp, ws.X, ws.Q, part_pq, ws.ctrl, 0);
+                hipLaunchKernelGGL(pgc_product_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, dv.node_start, dv.end_code, dv.end_rem, ws.Jp, dv.node_slot, dv.Hp, ws.X, ws.Q, part_pq, ws.ctrl, 0);
                 hipLaunchKernelGGL(pgc_residual_kernel, dim3(nb), dim3(PGC_NT), 0, st, n, 0, ws.ctrl, ws.Minv, ws.Q, ws.X, ws.R, ws.Z, part_rz, part_rr);
                 direction(1);
                 STBA_HIP(hipGetLastError());
@@ -507,10 +529,7 @@ int stba_pg_gauge_check(int n_nodes, int n_edges, const int* edge_i, const int* 
     if (n_nodes <= 0 || n_edges < 0 || (n_edges > 0 && (!edge_i || !edge_j))) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_gauge_check: null or empty input");
     for (int e = 0; e < n_edges; ++e)
         if (edge_i[e] < 0 || edge_i[e] >= n_nodes || edge_j[e] < 0 || edge_j[e] >= n_nodes) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_gauge_check: bad edge");
-    int size = 0, first = 0;
-    if (pg_gauge_fixed(n_nodes, n_edges, edge_i, edge_j, node_fixed, &size, &first)) return STBA_OK;
-    return fail(STBA_ERR_NOT_POSITIVE_DEFINITE, "pose-graph covariance: a connected component of " + std::to_string(size) + " node" + (size == 1 ? "" : "s") +
-                                                    " (first node " + std::to_string(first) + ") contains no constant node: J^T J is singular (gauge freedom)");
+    return pgc_gauge(n_nodes, n_edges, edge_i, edge_j, node_fixed, nullptr);
 }
 
 int stba_pg_covariance(stba_pg* pg, int n_pairs, const int* node_a, const int* node_b, const stba_pg_covariance_options* opt, double* out,

@@ -17,10 +17,11 @@ struct PgCovGraph {
     const int* ei = nullptr; const int* ej = nullptr;      // [m]
     const unsigned char* fixed = nullptr;                  // [n] or null
     bool several_ranks = false;                            // an all-reduce hook or communicator is set
+    const unsigned char* anchored = nullptr;               // [n] or null: the node holds a pose prior and is not constant
 };
 void pg_cov_graph(const stba_pg* g, PgCovGraph* out);
 
-// the linearisation at the engine's current poses, on the device.  pg_cov_linearize re-linearises and sums the diagonal blocks; it
+// the linearisation at the engine's current poses, on the device.  pg_cov_linearize re-linearises and sums the diagonal blocks (the priors' included); it
 // writes only buffers that every stba_pg_solve overwrites before it reads them (residuals, Jacobians, gradient, diagonal blocks).
 struct PgCovDevice {
     hipStream_t st = nullptr;
@@ -30,6 +31,9 @@ struct PgCovDevice {
     const double* Ji = nullptr; const double* Jj = nullptr;      // [36][m] component-major, zero for constant nodes
     const double* Hd = nullptr;            // [n][36] diagonal blocks of J^T J
     const unsigned char* fixed = nullptr;  // device, or null
+    // node pose priors (both null: none): the node's slot or -1 [n], and the slots' summed blocks J'^T J' [slots][36], which Hd holds too
+    const int* node_slot = nullptr;
+    const double* Hp = nullptr;
 };
 int pg_cov_linearize(stba_pg* g, PgCovDevice* out);
 

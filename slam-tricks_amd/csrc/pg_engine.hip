@@ -32,7 +32,8 @@
 // This unit holds the engine's creation and destruction, the LM loop (stba_pg_solve) with the steps that belong to no other unit --
 // the set-up of a solve, the linearisation's enqueue and scalars, the trial point, and the kernels that finish, export and update
 // them --, what pg_covariance.hip sees of the engine, and the rest of the stba_pg_* entry points.  The engine object and the
-// functions that cross units: pg_engine.hpp; the linearisation: pg_linearize.hip; the coarse space: pg_coarse.hip; the PCG: pg_pcg.hip.
+// functions that cross units: pg_engine.hpp; the linearisation: pg_linearize.hip; the coarse space: pg_coarse.hip; the PCG: pg_pcg.hip;
+// node pose priors: pg_prior.hip.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -191,7 +192,7 @@ int pg_linearize_enqueue(stba_pg* g, const PgSolve& sv) {
 // cost and |g|_inf of that linearisation: one kernel sums, the host reads mapped memory (several ranks: the cost goes over the hook)
 int pg_linearize_finish(stba_pg* g, double* cost, double* gmax, double* g2) {
     g->seq += 1.0;
-    hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_vec, g->part_c, g->ar ? g->scal_dev : g->fin.dev, g->seq);
+    hipLaunchKernelGGL(pg_linear_finish_kernel, dim3(1), dim3(256), 0, g->st, pg_cost_slots(g), g->part_e, g->nb_vec, g->part_c, g->ar ? g->scal_dev : g->fin.dev, g->seq);
     STBA_TRY(pg_read_block(g, 1, 3));
     *cost = 0.5 * g->fin_vals[0]; *gmax = g->fin_vals[1]; *g2 = g->fin_vals[2];
     return STBA_OK;
@@ -203,9 +204,9 @@ int pg_trial_point(stba_pg* g) {
     const int nxt = g->cur ^ 1;
     pg_edge_product(g, g->x, g->part_b, nullptr);
     hipLaunchKernelGGL(pg_update4_kernel, dim3(g->nb_nodes), dim3(256), 0, g->st, g->n, g->poses[g->cur], g->x, g->g, g->fixed, g->poses[nxt], g->part_u);
-    STBA_TRY(pg_linearize(g, nxt, false));
+    STBA_TRY(pg_linearize(g, nxt, false, g->x));      // (priors: their cost, and their |J' x|^2 behind the edge product's slots of part_b)
     g->seq += 1.0;
-    hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, g->nb_edges, g->part_e, g->nb_edges, g->part_b, g->nb_nodes, g->part_u,
+    hipLaunchKernelGGL(pg_trial_finish_kernel, dim3(1), dim3(256), 0, g->st, pg_cost_slots(g), g->part_e, pg_cost_slots(g), g->part_b, g->nb_nodes, g->part_u,
                        g->state, g->ar ? g->scal_dev : g->fin.dev, g->seq);
     return pg_read_block(g, 2, 8);      // (several ranks: cost and |J x|^2 summed over the edge shards)
 }
@@ -224,6 +225,7 @@ void pg_cov_graph(const stba_pg* g, PgCovGraph* out) {
     out->ei = g->h_ei.data(); out->ej = g->h_ej.data();
     out->fixed = g->h_fixed.empty() ? nullptr : g->h_fixed.data();
     out->several_ranks = g->ar != nullptr || g->world > 1;
+    out->anchored = g->pr.n ? g->pr.anchored.data() : nullptr;
 }
 int pg_cov_linearize(stba_pg* g, PgCovDevice* out) {
     // (a coarse inverse of the last solve may still be reading the diagonal blocks on the second stream)
@@ -233,6 +235,7 @@ int pg_cov_linearize(stba_pg* g, PgCovDevice* out) {
     STBA_HIP(hipGetLastError());
     out->st = g->st; out->node_start = g->node_start; out->end_code = g->end_code; out->end_rem = g->end_rem;
     out->Ji = g->Ji; out->Jj = g->Jj; out->Hd = g->Hd; out->fixed = g->fixed;
+    out->node_slot = g->pr.n ? g->pr.node_slot.get() : nullptr; out->Hp = g->pr.n ? g->pr.Hp.get() : nullptr;
     return STBA_OK;
 }
 }  // namespace stba
@@ -270,6 +273,7 @@ static int pg_fill(stba_pg* g, int n_nodes, int n_edges, const double* poses, co
     const size_t np_ = (size_t)std::max(g->nb_vec, std::max(g->nb_nodes, g->nb_edges)) * 2 + 2;
     STBA_TRY(g->part_e.alloc(np_)); STBA_TRY(g->part_a.alloc(np_)); STBA_TRY(g->part_b.alloc(np_)); STBA_TRY(g->part_c.alloc(np_));
     STBA_TRY(g->part_d.alloc(np_));
+    g->part_cap = np_;
     if (node_fixed) STBA_TRY(g->fixed.alloc(n));
     STBA_TRY(g->node_start.alloc(n + 1)); STBA_TRY(g->end_code.alloc(2 * m)); STBA_TRY(g->u.alloc(12 * m));
     STBA_TRY(g->end_node.alloc(2 * m)); STBA_TRY(g->contrib.alloc(2 * m * 28));
@@ -329,6 +333,9 @@ int stba_pg_create(stba_pg** out, int n_nodes, int n_edges, const double* poses,
 int stba_pg_set_allreduce(stba_pg* g, stba_allreduce_fn fn, void* user, int rank, int world_size) {
     if (!g || rank < 0 || world_size < 1 || rank >= world_size) return fail(STBA_ERR_INVALID_ARGUMENT, "bad argument");
     if (!fn && world_size > 1) return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_set_allreduce: world_size > 1 needs a hook");
+    // (node pose priors are one rank's: their terms are summed on this device only.  A call that clears the hook is never refused)
+    if (g->pr.n && (fn || world_size > 1))
+        return fail(STBA_ERR_INVALID_ARGUMENT, "stba_pg_set_allreduce: the engine holds node pose priors, which are implemented for one rank only (clear them first)");
     g->ar = (world_size > 1 || fn) ? fn : nullptr;
     g->ar_user = user; g->rank = rank; g->world = world_size;
     return STBA_OK;

@@ -1,7 +1,7 @@
 // pg_engine.hpp -- the pose-graph engine object behind the opaque stba_pg of include/stba.h, the state of one stba_pg_solve call,
 // and the few host functions that cross the pose-graph units: pg_linearize.hip (linearisation, weights and losses), pg_coarse.hip (the
-// coarse space and its second-stream job), pg_pcg.hip (the two forms of the PCG solve) and pg_engine.hip (creation, the LM loop and the
-// rest of the stba_pg_* entry points).  No kernel is declared or defined here.
+// coarse space and its second-stream job), pg_pcg.hip (the two forms of the PCG solve), pg_prior.hip (node pose priors) and pg_engine.hip
+// (creation, the LM loop and the rest of the stba_pg_* entry points).  No kernel is declared or defined here.
 #pragma once
 #include <vector>
 
@@ -48,6 +48,24 @@ struct PgCoarseJob {
         in_flight = false; reads_pending = false;
         return STBA_OK;
     }
+};
+
+// Node pose priors (stba_pg_set_priors; kernels and setter: pg_prior.hip).  Prior k names a node, a pose Z_k and a square-root
+// information W_k: r_k = log(Z_k^-1 T_node), the j side of pg_edge with T_i = I.  Held SORTED by node (stably: a node's priors in the
+// caller's order), with a CSR over the prior-bearing nodes, each of which has a compact SLOT.  n == 0: nothing is held, and the
+// engine enqueues what one that never had priors enqueues.
+constexpr int PG_PRIOR_NT = 256;             // the per-prior kernel: one lane per prior
+constexpr int PG_PRIOR_NODES_PER_WG = 32;    // the per-node kernel: eight lanes per prior-bearing node
+struct PgPriors {
+    int n = 0, n_slots = 0, nb = 0;          // priors | prior-bearing nodes | workgroups of the per-prior kernel
+    DevBuf<int> node;                        // [n]  node of the prior at a sorted position
+    DevBuf<double> pose, W;                  // [n][7], [n][36] (row-major), sorted like node
+    DevBuf<int> slot_node, slot_start;       // [n_slots] the slot's node | [n_slots + 1] its priors (CSR into the sorted order)
+    DevBuf<int> node_slot;                   // [n_nodes] the node's slot, or -1
+    DevBuf<double> r, J;                     // [n][6], [n][36]: W r and W J of the last linearisation (J == 0 on a constant node)
+    DevBuf<double> Hp;                       // [n_slots][36]: sum of J'^T J' over the slot's priors, for the matrix-free products
+    std::vector<int> order;                  // sorted position -> the caller's index
+    std::vector<unsigned char> anchored;     // [n_nodes] host: the node holds a prior and is not constant (the covariance's gauge)
 };
 
 }  // namespace stba
@@ -107,6 +125,9 @@ struct stba_pg {
     // pg_linearize launches a kernel without the corrector
     DevBuf<int> loss_kind;
     DevBuf<double> loss_a, loss_b, loss_scale;
+    // node pose priors (n == 0: none).  part_cap: doubles in part_e and part_b, which grow with the priors' partial slots
+    PgPriors pr;
+    size_t part_cap = 0;
 };
 
 namespace stba {
@@ -144,10 +165,20 @@ inline void pg_invalidate_linearisation(stba_pg* g) { g->bend_valid = false; g->
 int pg_hook(stba_pg* g, double* buf, size_t count);
 
 // ---- pg_linearize.hip
-// residuals (and, with jac, Jacobians and the per-end contributions) at poses[which]; part_e gets the cost's partial sums
-int pg_linearize(stba_pg* g, int which, bool jac);
-// gradient | diagonal blocks of the last pg_linearize(jac), gathered per node
+// residuals (and, with jac, Jacobians and the per-end contributions) at poses[which]; part_e gets the cost's partial sums -- the
+// edges' in its first nb_edges slots, the priors' behind them (pg_cost_slots).  trial_x: the step of a trial point (jac == false): the
+// priors' share of |J x|^2 goes into part_b behind the edge product's slots
+int pg_linearize(stba_pg* g, int which, bool jac, const double* trial_x = nullptr);
+// gradient | diagonal blocks of the last pg_linearize(jac), gathered per node, the priors' J'^T r' and J'^T J' included
 void pg_gather_blocks(stba_pg* g);
+// partial sums of a linearisation's cost in part_e (and of a trial point's |J x|^2 in part_b): the edge workgroups, then the priors'
+inline int pg_cost_slots(const stba_pg* g) { return g->nb_edges + g->pr.nb; }
+
+// ---- pg_prior.hip (an engine without priors: both return at once)
+// W r, W J (jac) and the cost partials of the priors at `poses`, behind the edges' slots of part_e; trial_x as for pg_linearize
+void pg_prior_linearize(stba_pg* g, const double* poses, bool jac, const double* trial_x);
+// g += sum J'^T r', Hd += sum J'^T J' per prior-bearing node, right behind pg_gather_blocks_kernel; Hp keeps the blocks
+void pg_prior_gather(stba_pg* g, bool accumulate);
 
 // ---- pg_coarse.hip
 int pg_setup_coarse(stba_pg* g, int group_opt);

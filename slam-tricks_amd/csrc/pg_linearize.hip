@@ -1,75 +1,19 @@
-// pg_linearize.hip -- the linearisation of the pose graph and everything that feeds it: the edge's residual and Jacobians (pg_edge),
-// the whitening by per-edge square-root information and the robust corrector, the kernel that writes r, Ji, Jj and the per-end
-// contributions, the gather of the gradient and the diagonal blocks, the conversion of the caller's weights; on the host pg_linearize,
-// pg_gather_blocks, the setters of weights and losses, stba_pg_evaluate and stba_pg_time_kernels (which times this unit's kernel and
-// the edge product of pg_pcg.hip).  The method: pg_engine.hip's header.
+// pg_linearize.hip -- the linearisation of the pose graph and everything that feeds it: the edge's residual and Jacobians and the
+// whitening by per-edge square-root information (pg_edge, pg_whiten_cols: pg_edge.hpp, shared with pg_prior.hip), the robust
+// corrector, the kernel that writes r, Ji, Jj and the per-end contributions, the gather of the gradient and the diagonal blocks, the
+// conversion of the caller's weights; on the host pg_linearize, pg_gather_blocks, the setters of weights and losses, stba_pg_evaluate
+// and stba_pg_time_kernels (which times this unit's kernel and the edge product of pg_pcg.hip).  The method: pg_engine.hip's header.
 #include <climits>
 #include <vector>
 
 #include "dd6.hpp"
 #include "pg_device.hpp"
+#include "pg_edge.hpp"
 #include "pg_engine.hpp"
 #include "robust_loss.hpp"
 
 namespace stba {
 namespace {
-
-// r, Ji, Jj of one edge
-__device__ inline void pg_edge(const double* Ti, const double* Tj, const double* Z, double* r, double* Ji, double* Jj) {
-    double Zi[7], Tii[7], A[7], E[7];
-    se3_inverse(Z, Zi);
-    se3_inverse(Ti, Tii);
-    se3_compose(Tii, Tj, A);
-    se3_compose(Zi, A, E);
-    if (E[3] < 0) for (int k = 0; k < 4; ++k) E[k] = -E[k];
-    se3_log7(E, r);
-    if (!Ji) return;
-    // Jr^-1 = I + ad/2 + ad^2/12, ad(xi) = [[hat(th), hat(rho)], [0, hat(th)]]
-    double Hr[9], Ht[9], ad[36], Jr[36];
-    hat3d(r, Hr); hat3d(r + 3, Ht);
-    for (int k = 0; k < 36; ++k) ad[k] = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { ad[i * 6 + j] = Ht[i * 3 + j]; ad[i * 6 + 3 + j] = Hr[i * 3 + j]; ad[(3 + i) * 6 + 3 + j] = Ht[i * 3 + j]; }
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 6; ++k) s += ad[i * 6 + k] * ad[k * 6 + j];
-            Jr[i * 6 + j] = (i == j ? 1.0 : 0.0) + 0.5 * ad[i * 6 + j] + s / 12.0;
-        }
-    for (int k = 0; k < 36; ++k) Jj[k] = Jr[k];
-    // Ad(T_j^-1 T_i) = [[R, hat(t) R], [0, R]]
-    double Ainv[7], R[9], Hh[9], AdM[36];
-    se3_inverse(A, Ainv);
-    quat_to_rot(Ainv, R);
-    hat3d(Ainv + 4, Hh);
-    for (int k = 0; k < 36; ++k) AdM[k] = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 3; ++k) s += Hh[i * 3 + k] * R[k * 3 + j];
-            AdM[i * 6 + j] = R[i * 3 + j]; AdM[i * 6 + 3 + j] = s; AdM[(3 + i) * 6 + 3 + j] = R[i * 3 + j];
-        }
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 6; ++k) s += Jr[i * 6 + k] * AdM[k * 6 + j];
-            Ji[i * 6 + j] = -s;
-        }
-}
-
-// x <- W x for `cols` columns of a 6-row matrix held row-major with row stride `ld` (a 6-vector: cols = ld = 1): one column at a
-// time through a 6-vector of temporaries, so that the product needs W (36) and six doubles on top of what is whitened in place
-__device__ inline void pg_whiten_cols(const double* W, double* x, int cols, int ld) {
-    for (int c = 0; c < cols; ++c) {
-        double t[6];
-        for (int a = 0; a < 6; ++a) {
-            double s = 0.0;
-            for (int k = 0; k < 6; ++k) s += W[a * 6 + k] * x[k * ld + c];
-            t[a] = s;
-        }
-        for (int a = 0; a < 6; ++a) x[a * ld + c] = t[a];
-    }
-}
 
 // J <- sqrt(rho') (J - k r (r^T J)) for the 6 x 6 row-major J of one edge end, one column at a time (k = alpha / s of Ceres' corrector;
 // k == 0: the scaling alone)
@@ -284,7 +228,7 @@ int pg_sum_ranks(stba_pg* g, double* v) {
 
 }  // namespace
 
-int pg_linearize(stba_pg* g, int which, bool jac) {
+int pg_linearize(stba_pg* g, int which, bool jac, const double* trial_x) {
     // (an engine that holds square-root information runs a whitening instantiation, one that holds a loss table a robust one, every
     // other one the kernel without either)
     auto launch = [&](auto kernel) {
@@ -296,14 +240,16 @@ int pg_linearize(stba_pg* g, int which, bool jac) {
     if (g->loss_kind) { if (g->Winfo) launch(pg_linearize_kernel<true, true>); else launch(pg_linearize_kernel<false, true>); }
     else if (g->Winfo) launch(pg_linearize_kernel<true, false>);
     else launch(pg_linearize_kernel<false, false>);
+    pg_prior_linearize(g, g->poses[which], jac, trial_x);
     STBA_HIP(hipGetLastError());
     if (jac) g->bend_valid = false;
     return STBA_OK;
 }
 
-// gradient | diagonal blocks of the last pg_linearize(jac), gathered per node
+// gradient | diagonal blocks of the last pg_linearize(jac), gathered per node; then the priors' terms on top
 void pg_gather_blocks(stba_pg* g) {
     hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->node_start, g->end_code, g->contrib, g->g, g->Hd);
+    pg_prior_gather(g, true);
 }
 
 }  // namespace stba
@@ -381,7 +327,7 @@ int stba_pg_evaluate(stba_pg* g, double* cost, double* r, double* Ji, double* Jj
     if (!g) return fail(STBA_ERR_INVALID_ARGUMENT, "null engine");
     STBA_TRY(pg_linearize(g, g->cur, true));
     std::vector<double> buf;
-    double c2 = host_sum(g->st, g->part_e, g->nb_edges, 1, 0, buf);
+    double c2 = host_sum(g->st, g->part_e, pg_cost_slots(g), 1, 0, buf);      // (edges plus priors)
     STBA_TRY(pg_sum_ranks(g, &c2));
     if (cost) *cost = 0.5 * c2;
     if (r) STBA_HIP(hipMemcpyAsync(r, g->r, (size_t)g->m * 6 * sizeof(double), hipMemcpyDeviceToHost, g->st));

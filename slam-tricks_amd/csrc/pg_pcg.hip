@@ -3,6 +3,9 @@
 // the only form for several ranks) and as ONE persistent kernel (one rank, all groups resident).  Holds the block-Jacobi
 // preconditioner kernel, the kernels of the launch path, the persistent kernel with its argument block and exchange helpers, and the
 // host code that launches them.  The method and the preconditioner: pg_engine.hip's header.
+// Node pose priors (pg_prior.hip) are block-diagonal: the persistent kernel applies the matrix ASSEMBLED -- Hd, which holds them, plus d
+// and the edge ends' off-diagonal blocks -- and needs nothing; the launch path is matrix-free over the edges and takes the priors'
+// summed blocks Hp in the PRIOR instantiations of its two node kernels.
 // (PG_NT = 1024 threads = PG_NPW = 128 nodes x 8 lanes: pg_plan.hpp)
 #include <algorithm>
 #include <atomic>
@@ -193,7 +196,11 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_init4_kernel(int n, int agg, con
 // the node's edge ends j, j + 8, ... (all loads of the gather in flight at once -- one lane per node walking its ends was a
 // chain of dependent round trips, 19 us for 10 000 nodes in round 3), the six components are summed over the lanes with a
 // butterfly, lanes 0..5 then own one component each.
-template <bool GATHER>
+// PRIOR = false: the engine holds no node pose priors -- the kernel as it was before there were any; node_slot and Hp are not read.
+// PRIOR = true (one rank, GATHER): q = (J^T J + D + Hp) p -- a node with a slot adds Hp_i p_i, Hp_i the summed J'^T J' of its priors
+// (pg_prior.hip); lane k holds row k of the block, the lanes of a node exchange p through shuffles.  Two instantiations and not a
+// runtime branch, as INFO / ROBUST in pg_linearize_kernel: an engine without priors runs the instruction stream it ran before.
+template <bool GATHER, bool PRIOR = false>
 __global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int agg, int slot, const PgPcgState* __restrict__ state,
                                                               int nb_a, const double* __restrict__ part_a, int nb_b,
                                                               const double* __restrict__ part_b, const double* __restrict__ Minv,
@@ -201,7 +208,8 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int
                                                               const int* __restrict__ node_start, const int* __restrict__ end_code,
                                                               const double* __restrict__ u, const double* __restrict__ qin,
                                                               const double* __restrict__ p, double* __restrict__ x, double* __restrict__ r,
-                                                              double* __restrict__ z, double* __restrict__ rc_part, double* __restrict__ part_out) {
+                                                              double* __restrict__ z, double* __restrict__ rc_part, double* __restrict__ part_out,
+                                                              const int* __restrict__ node_slot, const double* __restrict__ Hp) {
     __shared__ double wsm[PG_NPW][6];
     __shared__ double s_red[2][PG_NT / 64];
     const int t = threadIdx.x, nl = t >> 3, k = t & 7;
@@ -223,6 +231,11 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int
         if (GATHER) dk = d[o]; else dk = qin[o];
         for (int q = 0; q < 6; ++q) mrow[q] = Minv[(size_t)node * 36 + k * 6 + q];
         if (AdP) for (int q = 0; q < 6; ++q) pcol[q] = AdP[(size_t)node * 36 + q * 6 + k];
+    }
+    double hprow[6] = {0, 0, 0, 0, 0, 0};
+    if (PRIOR && act) {
+        const int sl = node_slot[node];
+        if (sl >= 0) for (int q = 0; q < 6; ++q) hprow[q] = Hp[(size_t)sl * 36 + k * 6 + q];
     }
     if (GATHER && node < n) {
         const int e1 = node_start[node + 1];
@@ -250,12 +263,15 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_update4_kernel(int n, int m, int
             ql[q] += __shfl_xor(ql[q], 4, 8);
         }
     }
+    double hp_p = 0.0;                   // (Hp_i p_i)[k]; a node without a slot has a zero row
+    if (PRIOR) for (int q = 0; q < 6; ++q) hp_p += hprow[q] * __shfl(pk, q, 8);
     if (act) {
         double qk;
         if (GATHER) {
             qk = ql[0];
             if (k == 1) qk = ql[1]; else if (k == 2) qk = ql[2]; else if (k == 3) qk = ql[3]; else if (k == 4) qk = ql[4]; else if (k == 5) qk = ql[5];
             qk += dk * pk;
+            if (PRIOR) qk += hp_p;
         } else qk = dk;
         x[o] = xk + alpha * pk;
         rk = rk - alpha * qk;
@@ -310,11 +326,15 @@ __global__ __launch_bounds__(256) void pg_coarse_solve_kernel(int nc, int parts,
 // Workgroup 0 also keeps the books of the solve: rz for the next iteration, the iteration count, and the STOPPING TEST
 // |r|^2 <= eta^2 |b|^2 (or the iteration cap) -- once `done` is set every later kernel of the solve returns at once, so the
 // host can enqueue iterations ahead of what it knows (it polls the exported block in mapped memory).
+// PRIOR (as in pg_pcg_update4_kernel): the partial gains p_i^T Hp_i p_i of the nodes that hold pose priors -- p.q = sum |t_e|^2 +
+// sum d p^2 + sum p^T Hp p.
+template <bool PRIOR = false>
 __global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int slot, int first, double eta, int max_iters, PgPcgState* __restrict__ state,
                                                            double* __restrict__ exp_, int nb_rz, const double* __restrict__ part_rz, int nb_cz,
                                                            const double* __restrict__ part_cz, const double* __restrict__ AdP,
                                                            const double* __restrict__ zc, const double* __restrict__ z, const double* __restrict__ d,
-                                                           double* __restrict__ p, double* __restrict__ part_dp) {
+                                                           double* __restrict__ p, double* __restrict__ part_dp,
+                                                           const int* __restrict__ node_slot, const double* __restrict__ Hp) {
     __shared__ double s_red[3][PG_NT / 64];
     const int t = threadIdx.x;
     // (as in the update kernel: every load that does not depend on beta is requested before anything is waited for)
@@ -336,6 +356,11 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int 
             for (int q = 0; q < 6; ++q) zk += AdP[(size_t)node * 36 + k * 6 + q] * zc[(size_t)a * 6 + q];
         }
     }
+    double hprow[6] = {0, 0, 0, 0, 0, 0};
+    if (PRIOR && act) {
+        const int sl = node_slot[node];
+        if (sl >= 0) for (int q = 0; q < 6; ++q) hprow[q] = Hp[(size_t)sl * 36 + k * 6 + q];
+    }
     if (was_done) {
         if (blockIdx.x == 0 && t == 0) {
             const int tk = state->ticks + 1;
@@ -355,10 +380,21 @@ __global__ __launch_bounds__(PG_NT) void pg_pcg_dir4_kernel(int n, int agg, int 
     rzn += rcz;
     const double beta = first ? 0.0 : ((rzo > 0.0) ? rzn / rzo : 0.0);
     double dp2 = 0.0;
-    if (act) {
-        const double pv = first ? zk : zk + beta * pold;
-        p[o] = pv;
-        dp2 = dk * pv * pv;
+    if (!PRIOR) {
+        if (act) {
+            const double pv = first ? zk : zk + beta * pold;
+            p[o] = pv;
+            dp2 = dk * pv * pv;
+        }
+    } else {
+        // (every lane takes part in the shuffles; the lanes that carry no component hold a zero)
+        const double pv = act ? (first ? zk : zk + beta * pold) : 0.0;
+        double hp_p = 0.0;
+        for (int q = 0; q < 6; ++q) hp_p += hprow[q] * __shfl(pv, q, 8);
+        if (act) {
+            p[o] = pv;
+            dp2 = dk * pv * pv + pv * hp_p;
+        }
     }
     double out2[2];
     block_sum2_n<PG_NT>(dp2, 0.0, out2);
@@ -748,8 +784,20 @@ int pg_pcg_by_launches(stba_pg* g, const PgSolve& sv, const double* Ainv_use, do
     if (coarse)
         hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->coarse.nc + 3) / 4), dim3(256), 0, g->st, g->coarse.nc, g->coarse.parts, (const PgPcgState*)nullptr, Ainv_use, g->rc_part,
                            g->zc, g->part_cz);
-    hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, 1, 1, eta_k, pcg.max_iterations, g->state, g->exp.dev,
-                       g->nb_nodes4, g->part_a, (g->coarse.nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+    // (an engine that holds node pose priors runs the PRIOR instantiations of the node kernels, every other one the kernels as they were:
+    // no launch more per iteration either way)
+    const bool prior = g->pr.n > 0;
+    const int* node_slot = prior ? g->pr.node_slot.get() : nullptr;
+    const double* Hp = prior ? g->pr.Hp.get() : nullptr;
+    auto direction = [&](int slot, int first) {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, slot, first, eta_k, pcg.max_iterations, g->state, g->exp.dev,
+                               g->nb_nodes4, g->part_a, (g->coarse.nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d,
+                               node_slot, Hp);
+        };
+        if (prior) launch(pg_pcg_dir4_kernel<true>); else launch(pg_pcg_dir4_kernel<false>);
+    };
+    direction(1, 1);
     STBA_HIP(hipGetLastError());
     int enq = 0;
     bool pcg_done = false;
@@ -763,21 +811,23 @@ int pg_pcg_by_launches(stba_pg* g, const PgSolve& sv, const double* Ainv_use, do
             const int slot = enq & 1;
             if (!sv.multi) {
                 pg_edge_product(g, g->p, g->part_c, g->state);
-                hipLaunchKernelGGL(pg_pcg_update4_kernel<true>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->coarse.agg, slot, g->state, g->nb_edges,
-                                   g->part_c, g->nb_nodes4, g->part_d, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, (const double*)nullptr,
-                                   g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
+                auto update = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->coarse.agg, slot, g->state, g->nb_edges,
+                                       g->part_c, g->nb_nodes4, g->part_d, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, (const double*)nullptr,
+                                       g->p, g->x, g->rr, g->z, g->rc_part, g->part_a, node_slot, Hp);
+                };
+                if (prior) update(pg_pcg_update4_kernel<true, true>); else update(pg_pcg_update4_kernel<true, false>);
             } else {
                 STBA_TRY(pg_apply(g, g->p, g->q, true));
                 hipLaunchKernelGGL(pg_dot_kernel, dim3(g->nb_vec), dim3(256), 0, g->st, 6 * g->n, g->p, g->q, g->part_c);
                 hipLaunchKernelGGL(pg_pcg_update4_kernel<false>, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->m, g->coarse.agg, slot, g->state, g->nb_vec,
                                    g->part_c, 0, (const double*)nullptr, g->Minv, AdP, g->d, g->node_start, g->end_code, g->u, g->q,
-                                   g->p, g->x, g->rr, g->z, g->rc_part, g->part_a);
+                                   g->p, g->x, g->rr, g->z, g->rc_part, g->part_a, (const int*)nullptr, (const double*)nullptr);
             }
             if (coarse)
                 hipLaunchKernelGGL(pg_coarse_solve_kernel, dim3((g->coarse.nc + 3) / 4), dim3(256), 0, g->st, g->coarse.nc, g->coarse.parts, g->state, Ainv_use, g->rc_part, g->zc,
                                    g->part_cz);
-            hipLaunchKernelGGL(pg_pcg_dir4_kernel, dim3(g->nb_nodes4), dim3(PG_NT), 0, g->st, g->n, g->coarse.agg, slot, 0, eta_k, pcg.max_iterations, g->state,
-                               g->exp.dev, g->nb_nodes4, g->part_a, (g->coarse.nc + 3) / 4, coarse ? g->part_cz : nullptr, AdP, g->zc, g->z, g->d, g->p, g->part_d);
+            direction(slot, 0);
         }
         STBA_HIP(hipGetLastError());
         // one rank: the host looks at the chunk BEFORE the one it has just enqueued (the stream never runs dry; the kernels of a

@@ -145,10 +145,12 @@ inline bool pg_waits_for_own_inverse(const stba_pcg_options& pcg, bool forcing, 
 }
 
 // ---------------------------------------------------------------- the gauge (pg_covariance.hip)
-// union-find over the edges: the first connected component without a constant node.  true: every component has one.
+// union-find over the edges: the first connected component without a constant (or anchored) node.  true: every component has one.
 // Otherwise *size and *first_node describe the offending component (the one whose smallest node index is smallest).
-// fixed: [n], or null (no node is constant)
-inline bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, int* size, int* first_node) {
+// fixed: [n], or null (no node is constant).  anchored: [n], or null: nodes that hold a pose prior and are not constant -- a component
+// passes if it holds a constant node OR an anchored one
+inline bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const unsigned char* fixed, int* size, int* first_node,
+                           const unsigned char* anchored = nullptr) {
     std::vector<int> parent((size_t)n);
     std::iota(parent.begin(), parent.end(), 0);
     auto find = [&](int a) { while (parent[(size_t)a] != a) { parent[(size_t)a] = parent[(size_t)parent[(size_t)a]]; a = parent[(size_t)a]; } return a; };
@@ -158,7 +160,7 @@ inline bool pg_gauge_fixed(int n, int m, const int* ei, const int* ej, const uns
     }
     std::vector<int> count((size_t)n, 0);
     std::vector<unsigned char> has((size_t)n, 0);
-    for (int k = 0; k < n; ++k) { const int r = find(k); ++count[(size_t)r]; if (fixed && fixed[k]) has[(size_t)r] = 1; }
+    for (int k = 0; k < n; ++k) { const int r = find(k); ++count[(size_t)r]; if ((fixed && fixed[k]) || (anchored && anchored[k])) has[(size_t)r] = 1; }
     for (int k = 0; k < n; ++k)
         if (find(k) == k && !has[(size_t)k]) { *size = count[(size_t)k]; *first_node = k; return false; }
     return true;
